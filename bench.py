@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- views/s forward+backward of the MI355X Gaussian-splat rasterizer (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3|c2|c3box|c4shape|c5shape] [--views V]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3|c2|c3box|c4shape|c5shape] [--views V] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -24,7 +24,8 @@ Workloads (BASELINE.json configs):
   ld512: 1e6 pixel-sized Gaussians in one layer on a panorama band, 512x512 views of the rotate360 path (LucidDreamer's own
       scene statistics: a quarter of the cloud in view, about one Gaussian per pixel).
 
-Prints ONE JSON line (rank 0).  `value` is the headline entry point (one lr_views_accumulate call per step, async mode,
+Prints ONE JSON line (rank 0): the result record without the descriptions of how its figures were produced
+(printed_record; `--details FILE` writes the whole record).  `value` is the headline entry point (one lr_views_accumulate call per step, async mode,
 3 streams).  In the default run (N = 1, workload c3) the same process also times, with the same K and W,
   * `entry_points`: the drop-in autograd operator (`drop_in_views_per_s`), the same in the reference's exact mode with a
     host round trip per view (`exact_mode_views_per_s`) and the views step with the fused L1+DSSIM loss inside
@@ -307,6 +308,70 @@ def run_leg(wl, api, exact, streams, steps, warmup, world, dev, fused=True):
     dt, host_ms = timed(step, steps, world, dev, collect=False)
     wl.finish()
     return wl.total_views * steps / dt, dt / steps * 1e3, host_ms, step
+
+
+# prose that describes how a figure was produced; the printed line leaves it out (--details FILE keeps it)
+PROSE_KEYS = ("what", "note", "sample", "traffic_source", "traffic_committed_file_source", "live_pmc")
+WHOLE_KEYS = ("config", "parity", "strict_mode_parity")       # printed exactly as recorded, prose included
+
+
+def printed_record(line):
+    """The result line as printed: the record without the descriptions under PROSE_KEYS outside WHOLE_KEYS, with compact
+    separators.  Every figure, label, error and trace stays.  (The whole record grew past 22 kB and its readers stopped taking
+    it; without the descriptions it is about 17.5 kB.)"""
+    def strip(o):
+        if isinstance(o, dict):
+            return {k: strip(v) for k, v in o.items() if k not in PROSE_KEYS}
+        if isinstance(o, list):
+            return [strip(v) for v in o]
+        return o
+    return json.dumps({k: (v if k in WHOLE_KEYS else strip(v)) for k, v in line.items()}, separators=(",", ":"))
+
+
+DUMP_LIMIT_BYTES = 64_000_000       # --dump-outputs: every file together
+DUMP_SAMPLE_BYTES = 48_000_000      # per-Gaussian arrays above this are cut to the same seeded sample of rows
+DUMP_SEED = 1234
+
+
+def dump_outputs(wl, directory):
+    """--dump-outputs: what the step just timed handed its caller after its last run, as float32 .npy files -- the gradient
+    of every parameter (grad_<name>: the step's bucket) and the screen-space gradient accumulator (grad_means2D); the per-view
+    losses of the views-loss step; the parameters after the optimizer of the sharded-adam exchanges.  When the per-Gaussian
+    arrays exceed DUMP_SAMPLE_BYTES, every one of them keeps the same seeded sample of rows (a power of two of them, ascending;
+    rows.npy holds their indices in float64, all rows when nothing is cut).  The inputs are seeded: the same arguments give
+    the same inputs in every run.  Call after wl.finish() (the device is idle)."""
+    import numpy as np
+    from luciddreamer_amd import parallel
+    names = parallel.ChunkedViewStep.ORDER
+    grads = wl.batch.grads if wl.batch is not None else wl.grads          # the bucket this step accumulated into
+    per_row = {"grad_" + k: v for k, v in zip(names, grads.views)}
+    m2d = wl.means2D.grad if wl.batch is None and wl.means2D.grad is not None else wl.m2d_grad
+    per_row["grad_means2D"] = m2d
+    if getattr(wl, "opt", None) is not None:
+        per_row.update({"param_" + k: v for k, v in wl.batch.named.items()})
+    other = {}
+    if wl.batch is not None and wl.batch.batches[0].losses is not None:
+        other["losses"] = torch.cat([b.losses for b in wl.batch.batches])       # [views, 3]: loss, L1, 1 - SSIM per view
+    P = wl.P
+    row_bytes = sum(v[0].numel() for v in per_row.values()) * 4 + 8
+    n = P
+    if P * row_bytes > DUMP_SAMPLE_BYTES:
+        n = 1 << int(math.floor(math.log2(DUMP_SAMPLE_BYTES / row_bytes)))
+    if n < P:
+        rows = torch.randperm(P, generator=torch.Generator().manual_seed(DUMP_SEED))[:n].sort().values
+    else:
+        rows = torch.arange(P)
+    idx = rows.to(wl.dev)
+    arrays = {k: v.detach().reshape(P, -1).index_select(0, idx).reshape((n,) + tuple(v.shape[1:])) for k, v in per_row.items()}
+    arrays.update(other)
+    out = {k: v.float().cpu().numpy() for k, v in arrays.items()}
+    out["rows"] = rows.numpy().astype(np.float64)
+    total = sum(a.nbytes for a in out.values())
+    assert total <= DUMP_LIMIT_BYTES - 128 * len(out), total
+    os.makedirs(directory, exist_ok=True)
+    for k, a in out.items():
+        np.save(os.path.join(directory, k + ".npy"), a)
+    return {"dir": directory, "files": len(out), "bytes": total, "rows": n, "of_rows": P}
 
 
 def read_counter_csv(directory, counter, acc):
@@ -727,6 +792,12 @@ def main():
                     help="after the K contract steps, time the same step for at least this long (reported as `sustained`)")
     ap.add_argument("--no-fused-accumulate", action="store_true",
                     help="let autograd accumulate dense per-view gradients instead of the in-kernel accumulation")
+    ap.add_argument("--details", default=None, metavar="FILE",
+                    help="write the whole result record to FILE; the printed line leaves out the descriptions of how "
+                         "figures were produced (printed_record)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last of them computed (parameter gradients, ...) to "
+                         "DIR/<name>.npy, float32, at most 64 MB in all (a seeded sample of rows when larger); rank 0 only")
     args = ap.parse_args()
 
     from luciddreamer_amd import parallel
@@ -766,6 +837,7 @@ def main():
            "grad_bucket_bytes": int(wl.grads.flat.numel() * 4)}
     fused = not args.no_fused_accumulate
     value, ms_per_step, host_issue_ms, step_fn = run_leg(wl, args.api, args.exact, args.streams, args.steps, args.warmup, world, dev, fused)
+    dumped = dump_outputs(wl, args.dump_outputs) if args.dump_outputs and rank == 0 else None
     chunks = wl.chunks
     exchange_phases = getattr(wl, "exchange_phases", None)
     exchange_bytes, exchange_detail = None, None
@@ -916,6 +988,7 @@ def main():
             "metric": metric,
             "value": round(value, 3), "unit": "views/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": round(ms_per_step, 3), "higher_is_better": True, "scaling": scaling, "vs_baseline": None,
+            "dumped_outputs": dumped,
             "dtype": "f32", "data": "synthetic",
             # the same step with the blend evaluated in the reference's own float operations (config.set_strict_parity): the
             # figure that meets the stated tolerance on EVERY pixel and gradient row with nothing masked (parity.strict_mode)
@@ -930,7 +1003,10 @@ def main():
             "f_rows": f_rows,
             "cpu_baseline": cpu_baseline,
         }
-        print(json.dumps(line), flush=True)
+        if args.details:
+            with open(args.details, "w") as f:
+                f.write(json.dumps(line) + "\n")
+        print(printed_record(line), flush=True)
     if world > 1:
         torch.distributed.destroy_process_group()
 

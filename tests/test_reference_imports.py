@@ -1,6 +1,7 @@
 """Zero-change route: the reference's own modules import against THIS repository's
-`depth_diff_gaussian_rasterization_min` and `simple_knn` packages.  Runs only where /root/reference exists (the build
-container); the GPU box skips it.  Nothing of the reference is executed on a device here."""
+`depth_diff_gaussian_rasterization_min` and `simple_knn` packages.  Runs where the reference's Python files are present:
+the reference checkout, or the copy build() stages under oracle/_ref/py (oracle/ref_python.py).  Nothing of the reference
+is executed on a device here."""
 import importlib
 import os
 import sys
@@ -8,8 +9,10 @@ import types
 
 import pytest
 
-REF = "/root/reference"
-pytestmark = pytest.mark.skipif(not os.path.isdir(REF), reason="reference checkout not present")
+from oracle import ref_python as rp
+
+REF = rp.root()
+pytestmark = pytest.mark.skipif(REF is None, reason="reference Python sources not present")
 
 
 @pytest.fixture()

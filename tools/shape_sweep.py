@@ -5,6 +5,8 @@ tile), with three views in flight (the multi-view entry points) and with one (a 
 
     python tools/shape_sweep.py [--workloads c2,c3,c3box,c4shape,c5shape,ld512] [--steps 6] [--rounds 2] [--out gpurun_out/shape_sweep.json]
 
+--fwd: the forward shapes forced (the product library has quadrant and tile; candidate pairs needs the diagnostics build).
+
 tests/test_gpu_zz_heuristics.py asserts the same on a reduced sweep."""
 import argparse
 import json
@@ -55,6 +57,7 @@ def main():
     ap.add_argument("--workloads", default="c2,c3,c3box,c4shape,c5shape,ld512")
     ap.add_argument("--steps", type=int, default=6)
     ap.add_argument("--rounds", type=int, default=2)
+    ap.add_argument("--fwd", default="0,2", help="forward shapes to force (1 = candidate pairs: diagnostics build only)")
     ap.add_argument("--out", default=os.path.join(ROOT, "gpurun_out", "shape_sweep.json"))
     a = ap.parse_args()
     dev = torch.device("cuda:0")
@@ -63,7 +66,8 @@ def main():
     for name in a.workloads.split(","):
         report[name] = {}
         for streams in (3, 1):
-            r = sweep(name, streams, a.steps, a.rounds, dev)
+            fwd = [int(f) for f in a.fwd.split(",")]
+            r = sweep(name, streams, a.steps, a.rounds, dev, [(-1, -1)] + [(b, f) for b in (0, 1, 2) for f in fwd])
             report[name][f"{streams}_in_flight"] = r
             print(f"{name:8s} {streams} in flight: default {r['default_shapes']} {r['default_views_per_s']:8.1f} views/s; best forced "
                   f"{r['best_forced']} {r['best_forced_views_per_s']:8.1f}  -> default / best = {r['default_over_best']:.3f}", flush=True)
