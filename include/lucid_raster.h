@@ -127,7 +127,7 @@ int lr_forward(lr_alloc_fn geom_alloc, void* geom_user,
  * lr_check on the view's geom buffer and, with debug != 0, by lr_backward itself.  Larger values only cost idle workgroups;
  * R = LR_NUM_RENDERED_ON_DEVICE with capacity 0 ("unknown") selects kernels that are correct for any launch size.
  * dL_depths is accepted and ignored, exactly as the reference does
- * (RAST/cuda_rasterizer/backward.cu:457-464, 539-554 are commented out).
+ * (RAST/cuda_rasterizer/backward.cu:457-464, 539-554 are commented out); lr_backward_depth below honours it.
  * accumulate_mask: bit k set (LR_ACC_*) => that output is ACCUMULATED into (rows of visible Gaussians are
  * added to the existing contents, rows of culled Gaussians are not touched); bit clear => the output is
  * fully written (zero rows for culled Gaussians), no pre-fill needed.  0 reproduces the reference contract.
@@ -247,6 +247,93 @@ int lr_backward_raw(int P, int D, int M, int R,
                     long long binning_capacity,
                     unsigned int accumulate_mask,
                     void* stream);
+
+/*
+ * Depth mode: lr_backward / lr_backward_raw with a gradient through the depth output.  Each takes its counterpart's
+ * arguments plus the forward's depth image `depth_image` [1,H,W] (out_depth of the same view); lr_backward_raw_depth also
+ * takes dL_depths, right after dL_dpix.  Here dL_depths [1,H,W] is HONOURED; with dL_depths == NULL the call is exactly
+ * its counterpart (same kernels, same bits).  lr_backward / lr_backward_raw do not change and still ignore dL_depths.
+ * The derivative is that of what the forward outputs, depth = D / acc where acc > 0.5 and 0 elsewhere, with
+ * D = sum z_i w_i, acc = 1e-6 + sum w_i, w_i = alpha_i T_i and z_i the view-space depth of Gaussian i; for an upstream g
+ * and a pixel with depth != 0 (gz = g / acc, ga = -g depth / acc; pixels whose depth is 0 contribute nothing):
+ *   - direct term: dL/dz_i += w_i gz, reaching dL/dmean3D (raw: dL/dxyz) through z = view[2] x + view[6] y + view[10] z + view[14];
+ *   - through alpha: depth and coverage act as two more colour channels with values (z_i, 1), weights (gz, ga) and
+ *     background 0, so dL/dmean2D, dL/dconic, dL/dopacity (and what follows from them) carry the depth loss's share --
+ *     dL_dmean2D, which feeds densification, included.
+ * The conventions of the colour path hold: the 0.99 clamp of alpha is not differentiated; the T < 1e-4 stop, the
+ * alpha < 1/255 and power > 0 skips, the sort order and the acc > 0.5 mask are constants; the fov clamp is treated as there.
+ * acc is taken as 1e-6 + (1 - final T) (equal to the forward's float sum up to rounding).  The blend backward walks every
+ * tile's whole list in this mode (no list segments); no global float atomics: the result is bit-repeatable.  An async view
+ * that overflowed its binning buffer writes nothing, as in lr_backward.  accumulate_mask, errors and the return value are
+ * those of the counterpart; dL_depths without depth_image is LR_ERR_INVALID_ARG.
+ */
+int lr_backward_depth(int P, int D, int M, int R,
+                      const float* background,
+                      int width, int height,
+                      const float* means3D,
+                      const float* shs,
+                      const float* colors_precomp,
+                      const float* scales,
+                      float scale_modifier,
+                      const float* rotations,
+                      const float* cov3D_precomp,
+                      const float* viewmatrix,
+                      const float* projmatrix,
+                      const float* campos,
+                      float tan_fovx, float tan_fovy,
+                      const int* radii,
+                      char* geom_buffer,
+                      char* binning_buffer,
+                      char* image_buffer,
+                      const float* dL_dpix,
+                      const float* dL_depths,
+                      const float* depth_image,
+                      float* dL_dmean2D,
+                      float* dL_dconic,
+                      float* dL_dopacity,
+                      float* dL_dcolor,
+                      float* dL_dmean3D,
+                      float* dL_dcov3D,
+                      float* dL_dsh,
+                      float* dL_dscale,
+                      float* dL_drot,
+                      int debug,
+                      long long binning_capacity,
+                      unsigned int accumulate_mask,
+                      void* stream);
+
+int lr_backward_raw_depth(int P, int D, int M, int R,
+                          const float* background,
+                          int width, int height,
+                          const float* xyz,
+                          const float* features_dc,
+                          const float* features_rest,
+                          const float* opacity_raw,
+                          const float* scaling_raw,
+                          float scale_modifier,
+                          const float* rotation_raw,
+                          const float* viewmatrix,
+                          const float* projmatrix,
+                          const float* campos,
+                          float tan_fovx, float tan_fovy,
+                          const int* radii,
+                          char* geom_buffer,
+                          char* binning_buffer,
+                          char* image_buffer,
+                          const float* dL_dpix,
+                          const float* dL_depths,
+                          const float* depth_image,
+                          float* dL_dmean2D,
+                          float* dL_dopacity_raw,
+                          float* dL_dxyz,
+                          float* dL_dfeatures_dc,
+                          float* dL_dfeatures_rest,
+                          float* dL_dscaling_raw,
+                          float* dL_drotation_raw,
+                          int debug,
+                          long long binning_capacity,
+                          unsigned int accumulate_mask,
+                          void* stream);
 
 /*
  * Multi-view step (new; the reference renders one view per Python iteration, luciddreamer.py:291-304).

@@ -44,18 +44,20 @@ def rasterize_gaussians(background, means3D, colors, opacity, scales, rotations,
 def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rotations, scale_modifier,
                                  cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color,
                                  dL_dout_depth, sh, degree, campos, geomBuffer, R, binningBuffer, imageBuffer,
-                                 debug, *, binning_capacity=0, accumulate_into=None, skip_unused=False):
+                                 debug, *, binning_capacity=0, accumulate_into=None, skip_unused=False, depth_image=None):
     """accumulate_into (optional): {name: tensor} with names among ACC_BITS; the gradient of that input is
     ADDED in place into the given contiguous float32 tensor (rows of culled Gaussians untouched) and the
     corresponding slot of the returned tuple is None.
     skip_unused: do not materialise gradients of inputs that are absent (dL_dcolors when SHs are used, dL_dcov3D /
     dL_dscales / dL_drotations for the representation not in use); their slots are None.  The reference always
-    returns all eight tensors, so the default keeps that."""
+    returns all eight tensors, so the default keeps that.
+    depth_image (optional): the forward's depth output -- depth mode (lr_backward_depth): dL_dout_depth is honoured.  Without
+    it dL_dout_depth is ignored, as in the reference."""
     acc = _NONE8 if not accumulate_into else [accumulate_into.get(k) for k in GRAD_ORDER]
     return tuple(_C_ext.rasterize_gaussians_backward(
         background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix, projmatrix,
         tan_fovx, tan_fovy, dL_dout_color, dL_dout_depth, sh, degree, campos, geomBuffer, R, binningBuffer, imageBuffer,
-        debug, binning_capacity, acc, skip_unused))
+        debug, binning_capacity, acc, skip_unused, depth_image=depth_image))
 
 
 def rasterize_gaussians_raw(background, xyz, features_dc, features_rest, opacity_raw, scaling_raw, rotation_raw,
@@ -74,10 +76,12 @@ def rasterize_gaussians_raw(background, xyz, features_dc, features_rest, opacity
 def rasterize_gaussians_raw_backward(background, xyz, radii, features_dc, features_rest, opacity_raw, scaling_raw,
                                      rotation_raw, scale_modifier, viewmatrix, projmatrix, tan_fovx, tan_fovy,
                                      dL_dout_color, degree, campos, geomBuffer, R, binningBuffer, imageBuffer, debug, *,
-                                     binning_capacity=0, accumulate_into=None, no_zero_fill=False):
+                                     binning_capacity=0, accumulate_into=None, no_zero_fill=False, dL_dout_depth=None,
+                                     depth_image=None):
     """Gradients w.r.t. the stored tensors: (means2D, xyz, features_dc, features_rest, opacity, scaling, rotation).
     accumulate_into: {"means2D","xyz","opacity","scaling","rotation": tensor, "features": (dc_grad, rest_grad)} adds
-    in place (slot returned as None)."""
+    in place (slot returned as None).
+    dL_dout_depth + depth_image (the forward's depth output): depth mode (lr_backward_raw_depth)."""
     acc = _NONE8
     if accumulate_into:
         f = accumulate_into.get("features") or (None, None)
@@ -86,7 +90,7 @@ def rasterize_gaussians_raw_backward(background, xyz, radii, features_dc, featur
     return tuple(_C_ext.rasterize_gaussians_raw_backward(
         background, xyz, radii, features_dc, features_rest, opacity_raw, scaling_raw, rotation_raw, scale_modifier, viewmatrix,
         projmatrix, tan_fovx, tan_fovy, dL_dout_color, degree, campos, geomBuffer, R, binningBuffer, imageBuffer, debug,
-        binning_capacity, acc, bool(no_zero_fill)))
+        binning_capacity, acc, bool(no_zero_fill), dL_dout_depth=dL_dout_depth, depth_image=depth_image))
 
 
 # one Adam step whose gradients are valid only in the rows of the Gaussians one view visited (lr_adam_step_masked)

@@ -35,6 +35,7 @@ import warnings
 
 _async = os.environ.get("LUCID_RASTER_EXACT", "0") != "1"
 _fused_accumulate = False
+_depth_gradient = False       # set_depth_gradient
 _headroom = 1.3
 _hwm = {}            # (device, P, H, W) -> largest instance count observed
 _pending = []        # "drop" / "raise": [[ticket of lr_header_post, key, policy]]
@@ -143,6 +144,23 @@ def set_fused_grad_accumulation(enabled: bool):
 
 def fused_grad_accumulation() -> bool:
     return _fused_accumulate
+
+
+def set_depth_gradient(enabled: bool):
+    """Differentiable depth output (off by default; process-wide).  The reference's backward drops the gradient of its depth
+    output (a loss on `depth` gives exactly zero parameter gradient), and so does this rasterizer unless this switch is on.
+    When it is on at a FORWARD, that forward keeps its depth image on the autograd node, and a backward that then receives a
+    gradient for `depth` runs the depth-mode kernels (lr_backward_depth / lr_backward_raw_depth): the true derivative of the
+    forward's depth = D / acc (0 where acc <= 0.5), reaching means3D directly and means2D, conics, opacities, scales and
+    rotations through alpha -- means2D.grad, which feeds densification, included.  A backward without a depth gradient is
+    today's, same kernels and bits.  Read at forward time and recorded on the node: flipping it between a forward and its
+    backward does not change that backward.  INTEGRATION.md "Depth supervision" has the semantics and the cost."""
+    global _depth_gradient
+    _depth_gradient = bool(enabled)
+
+
+def depth_gradient() -> bool:
+    return _depth_gradient
 
 
 def is_async() -> bool:

@@ -26,7 +26,7 @@ static_assert(sizeof(GaussRec) == 48, "GaussRec must be 48 bytes");
 struct __attribute__((aligned(16))) GradRec {
     float dmx, dmy, dca, dcb;       // dL/dmean2D.xy (NDC-scaled), dL/dconic a, b
     float dcc, dop, dr, dg;         // dL/dconic c, dL/dopacity, dL/dcolour r, g
-    float db, pad0, pad1, pad2;
+    float db, pad0, pad1, pad2;     // pad0: dL/d(view depth) in depth mode (lr_backward_depth), else 0
 };
 static_assert(sizeof(GradRec) == 48, "GradRec must be 48 bytes");
 
@@ -438,10 +438,13 @@ void launch_render_fwd(int W, int H, int gx, int gy, const uint2* ranges, const 
                        GeomHeader* hdr, uint2* seg_list, float4* ckpt, uint32_t* tile_seg0, float4* c_final,
                        long long inst_hint, hipStream_t s);
 // seg_bound: upper bound of GeomHeader::n_seg known to the host (bin_seg_capacity of the instance bound of the call)
+// dL_ddepth != nullptr: depth mode (lr_backward_depth) -- the depth-mode kernels differentiate the forward's depth image
+// depth_img [H*W] for the upstream gradient dL_ddepth [H*W] as well, and write dL/dz of every instance to its slot's free float
 void launch_render_bwd(int W, int H, int gx, int gy, const uint2* ranges, const uint32_t* point_list,
                        const GaussRec* rec, const float* bg, const float* final_T,
                        const uint32_t* n_contrib, const float* dL_dpix, char* bin_base, const GeomHeader* hdr,
-                       const uint32_t* tile_seg0, const float4* c_final, long long seg_bound, hipStream_t s);
+                       const uint32_t* tile_seg0, const float4* c_final, long long seg_bound, hipStream_t s,
+                       const float* dL_ddepth = nullptr, const float* depth_img = nullptr);
 // ---- Adam, element-wise (adam.hip and the step fused into the per-Gaussian backward, gauss_bwd.hip) -----------------------
 // torch's single-tensor Adam (torch/optim/adam.py _single_tensor_adam; no weight decay, amsgrad or maximize) with the roundings
 // of torch's own kernels: lerp = fma(w, b - a, a), addcmul = fma(value * t1, t2, self), addcdiv = fma(value, t1 / t2, self);
@@ -462,7 +465,9 @@ void launch_gauss_bwd(const ViewParams& vp, const float* means3D, const float* s
                       const char* bin_base, const GeomHeader* hdr,
                       float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor,
                       float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot,
-                      uint32_t accum_mask, float* acc16, hipStream_t s);
+                      uint32_t accum_mask, float* acc16, hipStream_t s, bool depth = false);
+// depth: the depth-mode kernel (k_gauss_bwd_depth), which adds each Gaussian's summed dL/dz (GradRec::pad0, written by the
+// depth-mode blend backward) to dL/dmean3D through z = view[2] x + view[6] y + view[10] z + view[14]
 // acc16 [P][16]: per-step interleaved accumulator of the five small gradient rows (gauss_bwd.hip); added to the caller's
 // tensors once per step
 void launch_uninterleave_add(int P, const float* acc16, float* mean2D, float* opacity, float* mean3D, float* scale, float* rot,

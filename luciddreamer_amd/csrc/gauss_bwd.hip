@@ -116,7 +116,10 @@ __device__ __forceinline__ float row_sum(float v)
 // Gaussian by the caller, which passes the resulting dL/d(view direction) in `dL_ddir` when `have_sh`).
 // RAW (lr_backward_raw) is a template parameter, not a run-time branch: with `if (vp.raw)` blocks in this function
 // ROCm 7.2 hipcc produced wrong dL/dcov3D in the NON-raw path (verified on hardware by removing either block).
-template <bool RAW>
+// DEPTH (k_gauss_bwd_depth): g2.y is the Gaussian's dL/d(view depth) from the depth-mode blend backward; it reaches the mean
+// through z = view[2] x + view[6] y + view[10] z + view[14] (column-major view matrix, auxiliary.h:58-66) -- in the raw path
+// the same term is dL/dxyz.
+template <bool RAW, bool DEPTH = false>
 __device__ __forceinline__ void
 gauss_backward_one(const int idx, const ViewParams& vp, const float* __restrict__ means3D, const float* __restrict__ scales,
             const float* __restrict__ rotations, const bool have_sh, const V3 dL_ddir,
@@ -252,6 +255,10 @@ gauss_backward_one(const int idx, const ViewParams& vp, const float* __restrict_
             o_m3d[1] += (-v.x * v.y * dv.x + (sum2 - v.y * v.y) * dv.y - v.z * v.y * dv.z) * invsum32;
             o_m3d[2] += (-v.x * v.z * dv.x - v.y * v.z * dv.y + (sum2 - v.z * v.z) * dv.z) * invsum32;
         }
+        if constexpr (DEPTH) {
+            const float gz = g2.y;
+            o_m3d[0] += V[2] * gz; o_m3d[1] += V[6] * gz; o_m3d[2] += V[10] * gz;
+        }
 
         // ---- cov3D -> scale / rotation (backward.cu:278-341) ----
         if (scales != nullptr) {
@@ -352,178 +359,32 @@ __device__ __forceinline__ float wave_sum(float v)
     return v;
 }
 
+#define LR_GB_PARAMS ViewParams vp, const float* __restrict__ means3D, const float* __restrict__ scales,                          \
+            const float* __restrict__ rotations, const float* __restrict__ shs,                                                 \
+            const float* __restrict__ cov3D_precomp, const uint32_t* __restrict__ vis_list,                                     \
+            const uint8_t* __restrict__ clamped, const uint32_t* __restrict__ offsets,                                          \
+            const char* __restrict__ bin_base, const GeomHeader* __restrict__ hdr,                                              \
+            float* __restrict__ dL_dmean2D, float* __restrict__ dL_dconic, float* __restrict__ dL_dopacity,                     \
+            float* __restrict__ dL_dcolor, float* __restrict__ dL_dmean3D, float* __restrict__ dL_dcov3D,                       \
+            float* __restrict__ dL_dsh, float* __restrict__ dL_dscale, float* __restrict__ dL_drot,                             \
+            uint32_t accum_mask, float* __restrict__ acc16
+
 template <bool RAW>
 __global__ void __launch_bounds__(GB_THREADS) __attribute__((amdgpu_waves_per_eu(LR_GB_WAVES, 8)))
-k_gauss_bwd(ViewParams vp, const float* __restrict__ means3D, const float* __restrict__ scales,
-            const float* __restrict__ rotations, const float* __restrict__ shs,
-            const float* __restrict__ cov3D_precomp, const uint32_t* __restrict__ vis_list,
-            const uint8_t* __restrict__ clamped, const uint32_t* __restrict__ offsets,
-            const char* __restrict__ bin_base, const GeomHeader* __restrict__ hdr,
-            float* __restrict__ dL_dmean2D, float* __restrict__ dL_dconic, float* __restrict__ dL_dopacity,
-            float* __restrict__ dL_dcolor, float* __restrict__ dL_dmean3D, float* __restrict__ dL_dcov3D,
-            float* __restrict__ dL_dsh, float* __restrict__ dL_dscale, float* __restrict__ dL_drot,
-            uint32_t accum_mask, float* __restrict__ acc16)
+k_gauss_bwd(LR_GB_PARAMS)
 {
-    constexpr uint32_t SERIAL_MAX = 24;      // instances summed by the owning lane; more -> whole wave helps
-    constexpr int BST = 17;                  // LDS row stride (floats) of the per-Gaussian basis rows: odd -> no conflicts
-    __shared__ uint32_t s_idx[GB_THREADS];
-    __shared__ float s_b[4][32 * BST];           // basis, d/dx, d/dy, d/dz of 32 Gaussians (half a round)
-    __shared__ float s_rgb[3][GB_THREADS];       // dL/dRGB after the clamp mask
-    __shared__ float s_ddir[3][GB_THREADS];      // dL/d(view direction)
-    const int lane = threadIdx.x;
-    const uint32_t n = hdr->num_compact;
-    if (n == 0) return;
-    if (hdr->overflow != 0u) return;         // async mode: an overflowed view contributes nothing (see k_render_bwd)
-    // per-instance partial sums written by k_render_bwd (48-byte slots, contiguous per Gaussian in emission
-    // order); slots at or beyond num_sorted were never built (async-mode overflow) and are ignored
-    const float4* __restrict__ inst_grad =
-        reinterpret_cast<const float4*>(bin_base + bin_layout((long long)hdr->bin_bound).inst_grad);
-    const uint32_t n_slots = hdr->num_sorted;
-
-    for (uint32_t t0 = blockIdx.x * GB_THREADS; t0 < n; t0 += gridDim.x * GB_THREADS) {
-        const uint32_t t = t0 + threadIdx.x;
-        const bool live = t < n;
-        const int idx = live ? (int)vis_list[t] : 0;
-        s_idx[lane] = (uint32_t)idx;
-        // first instance slot and instance count from the rank-ordered `offsets` (dense reads: neighbouring lanes read
-        // neighbouring words) instead of goff[idx] / tiles_touched[idx] -- two more 64-byte lines per visible Gaussian for
-        // 4 useful bytes each when ~9 % of the Gaussians are visible
-        const uint32_t off = live ? offsets[t] : 0u;
-        const uint32_t tt = live ? ((t + 1 < n) ? offsets[t + 1] : hdr->num_instances) - off : 0u;
-        float4 g0 = make_float4(0.f, 0.f, 0.f, 0.f), g1 = g0, g2 = g0;
-        if (tt <= SERIAL_MAX && off < n_slots) {
-            // four slots per step with independent loads (a one-slot loop pays one memory latency per instance)
-            const uint32_t cnt = min(tt, n_slots - off);
-            const float4* first = inst_grad + 3 * (size_t)off;
-            for (uint32_t j = 0; j < cnt; j += 4) {
-                float4 a[4][3];
-#pragma unroll
-                for (uint32_t q = 0; q < 4; q++) {
-                    const float4* slot = first + 3 * (size_t)min(j + q, cnt - 1);
-                    a[q][0] = slot[0]; a[q][1] = slot[1]; a[q][2] = slot[2];
-                }
-#pragma unroll
-                for (uint32_t q = 0; q < 4; q++)
-                    if (j + q < cnt) { add4(g0, a[q][0]); add4(g1, a[q][1]); add4(g2, a[q][2]); }
-            }
-        }
-        uint64_t big = __ballot(tt > SERIAL_MAX);
-        while (big) {
-            const int src = __ffsll((long long)big) - 1;
-            big &= big - 1;
-            const uint32_t b_tt = __shfl(tt, src), b_off = __shfl(off, src);
-            float4 p0 = make_float4(0.f, 0.f, 0.f, 0.f), p1 = p0, p2 = p0;
-            for (uint32_t j = lane; j < b_tt; j += 64) {
-                if (b_off + j >= n_slots) break;
-                const float4* slot = inst_grad + 3 * (size_t)(b_off + j);
-                add4(p0, slot[0]); add4(p1, slot[1]); add4(p2, slot[2]);
-            }
-            p0.x = wave_sum(p0.x); p0.y = wave_sum(p0.y); p0.z = wave_sum(p0.z); p0.w = wave_sum(p0.w);
-            p1.x = wave_sum(p1.x); p1.y = wave_sum(p1.y); p1.z = wave_sum(p1.z); p1.w = wave_sum(p1.w);
-            p2.x = wave_sum(p2.x);
-            if (lane == src) { g0 = p0; g1 = p1; g2 = p2; }
-        }
-        // ---- spherical harmonics: rows are 3*M floats per Gaussian.  One lane per Gaussian would make every
-        // load/store instruction touch 64 different rows (64 cache lines for 16 useful bytes each, and the working
-        // set of a wave overflows the L1); instead each lane computes the 16 basis values and their direction
-        // derivatives of ITS Gaussian into LDS, and then 16 LANES share one Gaussian, lane k owning coefficient k:
-        // a wave reads/updates 4 complete rows per step with fully used cache lines.
-        V3 dL_ddir = { 0.f, 0.f, 0.f };
-        const bool have_sh = shs != nullptr && dL_dsh != nullptr;
-        if (have_sh) {
-            const int k = lane & 15, sub = lane >> 4;
-            const int K = (vp.D + 1) * (vp.D + 1);
-            const size_t shrow = (size_t)vp.M * 3;
-            const bool acc = (accum_mask >> ACC_SH) & 1u;
-            const bool no_fill = !acc && (accum_mask >> 31) != 0u;          // LR_ACC_NO_ZERO_FILL (lucid_raster.h)
-            const int n_here = (int)min((uint32_t)GB_THREADS, n - t0);
-            if (live) {
-                const uint8_t cb = clamped[idx];
-                s_rgb[0][lane] = (cb & 1) ? 0.f : g1.z;
-                s_rgb[1][lane] = (cb & 2) ? 0.f : g1.w;
-                s_rgb[2][lane] = (cb & 4) ? 0.f : g2.x;
-            }
-            // two half rounds of 32 Gaussians keep the LDS footprint (and with it the occupancy limit) small
-            for (int half = 0; half < 2; half++) {
-                if (half * 32 >= n_here) break;
-                if (live && (lane >> 5) == half) {
-                    const size_t i = (size_t)idx;
-                    const V3 d0 = { means3D[3 * i] - vp.campos[0], means3D[3 * i + 1] - vp.campos[1], means3D[3 * i + 2] - vp.campos[2] };
-                    const float len = sqrtf(dot(d0, d0));
-                    const V3 dir = { d0.x / len, d0.y / len, d0.z / len };
-                    float b[16], bx[16], by[16], bz[16];
-                    switch (vp.D) {
-                        case 0: sh_basis<0>(dir, b, bx, by, bz); break;
-                        case 1: sh_basis<1>(dir, b, bx, by, bz); break;
-                        case 2: sh_basis<2>(dir, b, bx, by, bz); break;
-                        default: sh_basis<3>(dir, b, bx, by, bz); break;
-                    }
-                    const int o = (lane & 31) * BST;
-#pragma unroll
-                    for (int q = 0; q < 16; q++) {
-                        s_b[0][o + q] = b[q]; s_b[1][o + q] = bx[q]; s_b[2][o + q] = by[q]; s_b[3][o + q] = bz[q];
-                    }
-                }
-                lds_barrier();
-                // four steps (16 Gaussians) at a time: all row loads are issued before the first store, which the
-                // compiler cannot do across steps by itself (the accumulate loads may alias the previous stores)
-                for (int it0 = 0; it0 < 8; it0 += 4) {
-                    if (half * 32 + it0 * 4 >= n_here) break;
-                    float sv[4][3], dv[4][3];
-                    size_t rowv[4];
-                    bool onv[4];
-#pragma unroll
-                    for (int q = 0; q < 4; q++) {
-                        const int gl = (it0 + q) * 4 + sub, g = half * 32 + gl;
-                        onv[q] = g < n_here && k < K;
-                        const size_t gi = (size_t)s_idx[onv[q] ? g : 0];
-                        const int kk = onv[q] ? k : 0;
-                        // raw mode: coefficient 0 lives in features_dc [P,3], the others in features_rest [P,M-1,3]
-                        rowv[q] = !RAW ? gi * shrow + 3 * kk : (kk == 0 ? gi * 3 : gi * (shrow - 3) + 3 * (kk - 1));
-                    }
-#pragma unroll
-                    for (int q = 0; q < 4; q++) {
-                        const bool in_rest = RAW && onv[q] && k != 0;      // idle lanes re-read row 0 of features_dc
-                        const float* sp = (in_rest ? vp.sh_rest : shs) + rowv[q];
-                        sv[q][0] = sp[0]; sv[q][1] = sp[1]; sv[q][2] = sp[2];
-                        if (acc) { const float* dp = (in_rest ? vp.dL_dsh_rest : dL_dsh) + rowv[q]; dv[q][0] = dp[0]; dv[q][1] = dp[1]; dv[q][2] = dp[2]; }
-                        else { dv[q][0] = 0.f; dv[q][1] = 0.f; dv[q][2] = 0.f; }
-                    }
-#pragma unroll
-                    for (int q = 0; q < 4; q++) {
-                        const int gl = (it0 + q) * 4 + sub, g = half * 32 + gl;
-                        const int gs = onv[q] ? g : 0, gls = onv[q] ? gl : 0, ks = onv[q] ? k : 0;
-                        const float r0 = s_rgb[0][gs], r1 = s_rgb[1][gs], r2 = s_rgb[2][gs];
-                        const float bk = s_b[0][gls * BST + ks];
-                        if (onv[q]) {
-                            float* dp = ((RAW && k != 0) ? vp.dL_dsh_rest : dL_dsh) + rowv[q];   // onv[q] holds here
-                            dp[0] = dv[q][0] + bk * r0; dp[1] = dv[q][1] + bk * r1; dp[2] = dv[q][2] + bk * r2;
-                        } else if (no_fill && g < n_here && k >= K && k < vp.M) {
-                            // LR_ACC_NO_ZERO_FILL: nobody zero-filled the tensor, and a VISITED Gaussian's rows are read by the
-                            // masked optimizer step -- its coefficients above the active degree are written as the zeros they are
-                            const size_t gi = (size_t)s_idx[g];
-                            float* dp = !RAW ? dL_dsh + gi * shrow + 3 * k
-                                             : (k == 0 ? dL_dsh + gi * 3 : vp.dL_dsh_rest + gi * (shrow - 3) + 3 * (size_t)(k - 1));
-                            dp[0] = 0.f; dp[1] = 0.f; dp[2] = 0.f;
-                        }
-                        const float sd = onv[q] ? sv[q][0] * r0 + sv[q][1] * r1 + sv[q][2] * r2 : 0.f;
-                        const float px = row_sum(s_b[1][gls * BST + ks] * sd);
-                        const float py = row_sum(s_b[2][gls * BST + ks] * sd);
-                        const float pz = row_sum(s_b[3][gls * BST + ks] * sd);
-                        if (k == 0 && g < n_here) { s_ddir[0][g] = px; s_ddir[1][g] = py; s_ddir[2][g] = pz; }
-                    }
-                }
-                lds_barrier();
-            }
-            if (live) dL_ddir = { s_ddir[0][lane], s_ddir[1][lane], s_ddir[2][lane] };
-        }
-        if (live)
-            gauss_backward_one<RAW>(idx, vp, means3D, scales, rotations, have_sh, dL_ddir, cov3D_precomp, g0, g1, g2,
-                               dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dscale,
-                               dL_drot, accum_mask, acc16);
-        lds_barrier();                     // the LDS planes are rewritten by the next round
-    }
+    constexpr bool DEPTH = false;
+#include "gauss_bwd_body.h"
 }
+// depth mode (lr_backward_depth / lr_backward_raw_depth): its own entry point, so that k_gauss_bwd keeps its instruction stream
+template <bool RAW>
+__global__ void __launch_bounds__(GB_THREADS) __attribute__((amdgpu_waves_per_eu(LR_GB_WAVES, 8)))
+k_gauss_bwd_depth(LR_GB_PARAMS)
+{
+    constexpr bool DEPTH = true;
+#include "gauss_bwd_body.h"
+}
+#undef LR_GB_PARAMS
 
 struct ZeroSegs { float4* p[9]; unsigned long long n4[9]; unsigned long long off[10]; int count; };
 
@@ -579,11 +440,22 @@ void launch_gauss_bwd(const ViewParams& vp, const float* means3D, const float* s
                       const char* bin_base, const GeomHeader* hdr,
                       float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor,
                       float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot,
-                      uint32_t accum_mask, float* acc16, hipStream_t s)
+                      uint32_t accum_mask, float* acc16, hipStream_t s, bool depth)
 {
     (void)colors_precomp;
     if (vp.P <= 0) return;
     const int groups = std::min((vp.P + GB_THREADS - 1) / GB_THREADS, GB_MAX_GROUPS);
+    if (depth) {
+        if (vp.raw)
+            hipLaunchKernelGGL(k_gauss_bwd_depth<true>, dim3(groups), dim3(GB_THREADS), 0, s, vp, means3D, scales, rotations, shs,
+                               cov3D_precomp, vis_list, clamped, offsets, bin_base, hdr, dL_dmean2D, dL_dconic,
+                               dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, accum_mask, acc16);
+        else
+            hipLaunchKernelGGL(k_gauss_bwd_depth<false>, dim3(groups), dim3(GB_THREADS), 0, s, vp, means3D, scales, rotations, shs,
+                               cov3D_precomp, vis_list, clamped, offsets, bin_base, hdr, dL_dmean2D, dL_dconic,
+                               dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, accum_mask, acc16);
+        return;
+    }
     if (vp.raw)
         hipLaunchKernelGGL(k_gauss_bwd<true>, dim3(groups), dim3(GB_THREADS), 0, s, vp, means3D, scales, rotations, shs,
                            cov3D_precomp, vis_list, clamped, offsets, bin_base, hdr, dL_dmean2D, dL_dconic,

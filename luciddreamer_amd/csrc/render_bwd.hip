@@ -3,7 +3,7 @@
 // Replaces BACKWARD::render / renderCUDA (RAST/cuda_rasterizer/backward.cu:399-586).  The
 // per-pixel recursion is the reference's (back-to-front, T un-blended by division, colour
 // recursion through accum_rec, background term, 0.99 clamp not differentiated, depth gradient
-// ignored).  The kernel is VALU-issue bound; the design removes wave-instructions:
+// ignored -- except in the depth-mode kernels k_render_bwd_depth below, lr_backward_depth).  The kernel is VALU-issue bound; the design removes wave-instructions:
 //
 //   * same two-level loop as the forward: per 64 staged Gaussians one lane each looks up the outcome of the forward's
 //     exact quadrant test (box_hit, kept per list position in the binning buffer) -> 64-bit candidate mask; only
@@ -174,6 +174,7 @@ struct BwdPix {
     float dLr, dLg, dLb;
     float pxf;
     uint32_t last;      // list positions below this one were blended by the forward (render_fwd.hip PixState::last)
+    float gz;           // depth mode only: dL/ddepth / acc (0 where the forward's depth is 0)
 };
 
 // One layer for one pixel; adds the pixel's terms to the lane sums.  Only what varies per pixel is formed here: the
@@ -191,11 +192,14 @@ struct BwdPix {
 // CHECK_LAST: the `pos < last` test is compiled in.  A pixel the forward never stopped (T stayed above 1e-4) carries last = the
 // list length, so the test can only fail for pixels that DID stop; a wave none of whose pixels stopped (99 % of the waves of a
 // C3 view; most of a dense one do have stopped pixels) walks its candidates through the copy of the loop without it.
-template <bool FIRSTM, bool FIRSTC, bool CHECK_LAST, bool STRICT = false>
+// DEPTH (depth-mode kernels only): the layer's view depth z enters the recursion as a fourth "colour" with weight p.gz (A
+// carries the coverage term, see render_bwd_item), and the lane sums the direct term w * gz = alpha T gz into *sZ.
+template <bool FIRSTM, bool FIRSTC, bool CHECK_LAST, bool STRICT = false, bool DEPTH = false>
 __device__ __forceinline__ void bwd_pixel(BwdPix& p, const float qA, const float qB, const float qC, const float r0, const float r1,
                                           const float gx,
                                           const float op, const float cr, const float cg, const float cb, const uint32_t pos,
-                                          float& sD, float& sMx, float& sMxx, float& sR, float& sG, float& sB)
+                                          float& sD, float& sMx, float& sMxx, float& sR, float& sG, float& sB,
+                                          const float z = 0.f, float* sZ = nullptr)
 {
     const float dx = gx - p.pxf;
     float power;                                                           // (log2(e) x) the reference's power
@@ -213,7 +217,8 @@ __device__ __forceinline__ void bwd_pixel(BwdPix& p, const float qA, const float
     const float dchan = alpha * p.T;
     // colour of this Gaussian . dL/dpixel, minus the colour behind: one fma chain started at -A (three instructions, not a
     // dot product and a subtraction)
-    const float d = __builtin_fmaf(cb, p.dLb, __builtin_fmaf(cg, p.dLg, __builtin_fmaf(cr, p.dLr, -p.A)));
+    float d = __builtin_fmaf(cb, p.dLb, __builtin_fmaf(cg, p.dLg, __builtin_fmaf(cr, p.dLr, -p.A)));
+    if constexpr (DEPTH) d = __builtin_fmaf(z, p.gz, d);                   // + z . dL/dD (one fma per layer)
     const float dop = tm * (d * p.T);                                      // opacity x G x dL/dalpha
     p.A = __builtin_fmaf(alpha, d, p.A);                                   // a skipped layer (alpha = 0) leaves A as it is
     const float mx = dop * dx;
@@ -221,6 +226,10 @@ __device__ __forceinline__ void bwd_pixel(BwdPix& p, const float qA, const float
     else { sD += dop; sMx += mx; sMxx += mx * dx; }
     if (FIRSTC) { sR = dchan * p.dLr; sG = dchan * p.dLg; sB = dchan * p.dLb; }
     else { sR += dchan * p.dLr; sG += dchan * p.dLg; sB += dchan * p.dLb; }
+    if constexpr (DEPTH) {                                                 // dL/dz = w dL/dD (the direct term)
+        if (FIRSTC) *sZ = dchan * p.gz;
+        else *sZ += dchan * p.gz;
+    }
 }
 
 // MERGE: row_merge3 + one plain store per candidate into the wave's own accumulator copy (the default); false = the round-2
@@ -229,19 +238,31 @@ __device__ __forceinline__ void bwd_pixel(BwdPix& p, const float qA, const float
 // 1 M cloud 526 -> 485 us, C5 shape (QUAD) 362 -> 324 us.
 // One work item of the backward: segment `seg` of tile `tile` -- list positions [seg * BWD_SEG, (seg + 1) * BWD_SEG) -- or,
 // with seg < 0, the whole list.  ck_slot: the checkpoint the forward left at the segment's deep end (common.h BinLayout::ckpt).
-template <bool QUAD, bool MERGE, bool STRICT>
+// DEPTH (k_render_bwd_depth, whole lists only: the checkpoints hold no depth so far): the derivative of the forward's depth
+// output D / acc (render_fwd.hip; D = sum z w, acc = 1e-6 + sum w, 0 where acc <= 0.5) for g = dL_ddepth.  Depth and coverage
+// act as two more colour channels with values (z, 1), weights (gz, ga) = (g / acc, -g depth / acc) and background 0, so the
+// per-pixel recursion only gains z gz in each layer's value, and ga -- constant along the list -- is carried in A from the
+// start (A - ga instead of A: the same differences d); the direct term dL/dz = w gz is a tenth per-instance sum, which the
+// flush writes to the free float of the slot (slot[2].y, read by k_gauss_bwd_depth).  acc is taken as 1e-6 + (1 - final T)
+// -- the forward's float sum of the weights telescoped, equal up to rounding -- and depth != 0 as the mask: a blended
+// Gaussian has z > 0.2 (in_frustum), so a pixel with acc > 0.5 has a nonzero depth, exactly the forward's decision.
+// (Not the reference's commented-out depth terms, backward.cu:457-464, 539-554: they differentiate p_proj.z / p_proj.w and
+// the un-normalised D, which is not the quantity the forward outputs.)
+template <bool QUAD, bool MERGE, bool STRICT, bool DEPTH = false>
 __device__ __forceinline__ void render_bwd_item(const int tile, const int seg, const uint32_t ck_slot,
              const float4* __restrict__ c_final, int W, int H, int gx, const uint2* __restrict__ ranges,
              const uint32_t* __restrict__ point_list, const GaussRec* __restrict__ rec,
              const float* __restrict__ bg, const float* __restrict__ final_Ts,
              const uint32_t* __restrict__ n_contrib, const float* __restrict__ dL_dpix,
-             char* __restrict__ bin_base, const GeomHeader* __restrict__ hdr, int force_check)
+             char* __restrict__ bin_base, const GeomHeader* __restrict__ hdr, int force_check,
+             const float* __restrict__ dL_ddepth = nullptr, const float* __restrict__ depth_img = nullptr)
 {
+    static_assert(!DEPTH || MERGE, "depth mode uses the merged reduction");
     constexpr int BATCH = QUAD ? LR_QBATCH_BWD : BATCH2;
     __shared__ float4 s_q0[BATCH];      // x, y, Ap = -0.5 conic a, Bp = -conic b      (common.h gauss_power; x log2 e)
     __shared__ float4 s_q1[BATCH];      // Cp = -0.5 conic c (x log2 e), opacity, -, -   (16-byte stride like s_q0 / s_q2: the
                                         // three broadcast reads of a candidate share ONE address register)
-    __shared__ float4 s_q2[BATCH];      // r, g, b, -
+    __shared__ float4 s_q2[BATCH];      // r, g, b, view depth z (DEPTH; 0 otherwise)
     __shared__ uint32_t s_id[BATCH];    // emission index (instance slot) of each staged element
     __shared__ uint32_t s_hit[BATCH];   // the forward's quadrant tests of each staged element (common.h BinLayout::quad_hits)
     // per-batch gradient accumulator, columns below.  Every wave owns a copy: a wave meets a staged candidate at most once
@@ -250,7 +271,8 @@ __device__ __forceinline__ void render_bwd_item(const int tile, const int seg, c
     // into ONE copy with LDS float atomics -- two operands, so the sum does not depend on which wave comes first.)
     constexpr int NWAVES = QUAD ? 4 : 2;
     constexpr int NACC = (QUAD || MERGE) ? NWAVES : 1;
-    __shared__ float s_acc[BATCH][NACC][12];
+    constexpr int NCOL = DEPTH ? 16 : 12;   // DEPTH: columns 12-15 = the dL/dz partial of each 16-lane row
+    __shared__ float s_acc[BATCH][NACC][NCOL];
     __shared__ uint32_t s_wlast[NWAVES];
 
     const int tx = tile % gx, ty = tile / gx;
@@ -285,6 +307,19 @@ __device__ __forceinline__ void render_bwd_item(const int tile, const int seg, c
     if (insB) { PB.dLr = dL_dpix[pixB]; PB.dLg = dL_dpix[N + pixB]; PB.dLb = dL_dpix[2 * N + pixB]; }
     PA.A = bg[0] * PA.dLr + bg[1] * PA.dLg + bg[2] * PA.dLb;       // background . dL/dpixel: the deepest layer
     PB.A = bg[0] * PB.dLr + bg[1] * PB.dLg + bg[2] * PB.dLb;
+    if constexpr (DEPTH) {                                          // whole lists only (seg < 0): T is the final T here
+        auto depth_pixel = [&](BwdPix& p, bool ins, size_t pix) {
+            p.gz = 0.f;
+            const float dep = ins ? depth_img[pix] : 0.f;
+            if (dep != 0.f) {                                       // the forward's acc > 0.5 (see above)
+                const float r = dL_ddepth[pix] / (1e-6f + (1.0f - p.T));
+                p.gz = r;                                           // gz = g / acc
+                p.A = __builtin_fmaf(r, dep, p.A);                  // A - ga = A + g depth / acc
+            }
+        };
+        depth_pixel(PA, insA, pixA);
+        depth_pixel(PB, insB, pixB);
+    }
     if (seg_hi < total) {
         // The recursion starts in the middle of the list.  A pixel the forward was still blending at position seg_hi
         // (last > seg_hi: it stopped later, or never) takes the forward's own T there and the colour still to come behind it --
@@ -326,7 +361,7 @@ __device__ __forceinline__ void render_bwd_item(const int tile, const int seg, c
     // MERGE: lanes 0 / 8 / 4 of every row end up with the row's a term, b term and db partial (row_merge3)
     const int l16 = l & 15;
     const bool merge_writer = (l16 & 3) == 0 && l16 < 12;
-    const uint32_t merge_off = (uint32_t)(w * 12 + (l16 == 0 ? col_a : l16 == 8 ? col_a + 4 : 8 + row));
+    const uint32_t merge_off = (uint32_t)(w * NCOL + (l16 == 0 ? col_a : l16 == 8 ? col_a + 4 : 8 + row));
 
     for (int base = 0; base < seg_hi - seg_lo; base += BATCH) {
         // staged element i <-> list position pos = seg_hi-1-base-i (back to front)
@@ -350,14 +385,14 @@ __device__ __forceinline__ void render_bwd_item(const int tile, const int seg, c
             // as render_fwd.hip: scaled exponent coefficients, or the raw conic in strict mode
             s_q0[tid] = STRICT ? make_float4(a.x, a.y, a.z, a.w) : make_float4(a.x, a.y, (-0.5f * LOG2E) * a.z, -LOG2E * a.w);
             *reinterpret_cast<float2*>(&s_q1[tid]) = STRICT ? make_float2(b.x, b.y) : make_float2((-0.5f * LOG2E) * b.x, b.y);
-            s_q2[tid] = make_float4(b.z, b.w, c.x, 0.f);
+            s_q2[tid] = make_float4(b.z, b.w, c.x, DEPTH ? c.y : 0.f);       // GaussRec::depth
             s_id[tid] = e;
         }
         if (tid < BATCH) {
 #pragma unroll
             for (int a = 0; a < NACC; a++)
 #pragma unroll
-                for (int k = 0; k < 12; k++) s_acc[tid][a][k] = 0.f;
+                for (int k = 0; k < NCOL; k++) s_acc[tid][a][k] = 0.f;
         }
         lds_barrier();
 
@@ -391,9 +426,10 @@ __device__ __forceinline__ void render_bwd_item(const int tile, const int seg, c
                 const float dys = a.y - pyf;                      // both pixels of a lane share the row
                 float r0, r1;
                 gauss_row<STRICT>(a.w, b.x, dys, r0, r1);                                       // common.h gauss_power
-                float sD = 0.f, sMx = 0.f, sMxx = 0.f, sR = 0.f, sG = 0.f, sB = 0.f;
-                if (QUAD || ((maskL >> k) & 1ull)) bwd_pixel<true, true, CHECK, STRICT>(PA, a.z, a.w, b.x, r0, r1, a.x, b.y, c.x, c.y, c.z, pos, sD, sMx, sMxx, sR, sG, sB);
-                if (!QUAD && ((maskR >> k) & 1ull)) bwd_pixel<false, false, CHECK, STRICT>(PB, a.z, a.w, b.x, r0, r1, a.x, b.y, c.x, c.y, c.z, pos, sD, sMx, sMxx, sR, sG, sB);
+                // (sZ's address only in depth mode: taken in the default kernels as well, it renamed their registers)
+                float sD = 0.f, sMx = 0.f, sMxx = 0.f, sR = 0.f, sG = 0.f, sB = 0.f, sZ = 0.f;
+                if (QUAD || ((maskL >> k) & 1ull)) bwd_pixel<true, true, CHECK, STRICT, DEPTH>(PA, a.z, a.w, b.x, r0, r1, a.x, b.y, c.x, c.y, c.z, pos, sD, sMx, sMxx, sR, sG, sB, c.w, DEPTH ? &sZ : nullptr);
+                if (!QUAD && ((maskR >> k) & 1ull)) bwd_pixel<false, false, CHECK, STRICT, DEPTH>(PB, a.z, a.w, b.x, r0, r1, a.x, b.y, c.x, c.y, c.z, pos, sD, sMx, sMxx, sR, sG, sB, c.w, DEPTH ? &sZ : nullptr);
                 // both pixels of a lane share dy, so the dy factors are applied to the lane's sums
                 const float sMy = dys * sD, sMxy = dys * sMx;
                 const float sMyy = dys * sMy;
@@ -401,9 +437,13 @@ __device__ __forceinline__ void render_bwd_item(const int tile, const int seg, c
                 reduce8(ra, sMy, sMxx, sMxy, rb, sD, sR, sG);
                 if (MERGE) {
                     const float rc = row_merge3(ra, rb, sB);
-                    int jo = j * (12 * NACC);
+                    int jo = j * (NCOL * NACC);
                     asm volatile("" : "+s"(jo));              // scalar product, one v_add for the address (not a v_mad_u64_u32)
                     if (merge_writer) (&s_acc[0][0][0])[jo + (int)merge_off] = rc;
+                    if constexpr (DEPTH) {                    // the tenth term: a row sum, lane 12 of each row writes its column
+                        const float rz = row_sum(sZ);
+                        if (l16 == 12) (&s_acc[0][0][0])[jo + w * NCOL + 12 + row] = rz;
+                    }
                 } else {
                     ra = row_sum(ra); rb = row_sum(rb);
                     float rc = row_sum(sB);                           // every row: its partial of db
@@ -427,9 +467,9 @@ __device__ __forceinline__ void render_bwd_item(const int tile, const int seg, c
             // every instance owns one 48-byte slot: plain stores, no atomics, and the per-Gaussian sum in
             // k_gauss_bwd runs in a fixed order (the slot is written even when nothing contributed).  The factors that
             // are constant per Gaussian (opacity, conic entries, -0.5, the NDC scale of backward.cu:473-474) go in here.
-            float a9[12];                              // sums of D dx, D dy, D dx^2, D dx dy, D dy^2, D, dr, dg, db (x4)
+            float a9[NCOL];                            // sums of D dx, D dy, D dx^2, D dx dy, D dy^2, D, dr, dg, db (x4), [dz (x4)]
 #pragma unroll
-            for (int k = 0; k < 12; k++) {
+            for (int k = 0; k < NCOL; k++) {
                 float v = s_acc[tid][0][k];
 #pragma unroll
                 for (int a = 1; a < NACC; a++) v += s_acc[tid][a][k];      // fixed order over the waves
@@ -446,7 +486,9 @@ __device__ __forceinline__ void render_bwd_item(const int tile, const int seg, c
             float4* slot = inst_grad + 3 * (size_t)s_id[tid];
             slot[0] = make_float4((-ca * sx - cb * sy) * ddelx_dx, (-cc * sy - cb * sx) * ddely_dy, h * a9[2], h * a9[3]);
             slot[1] = make_float4(h * a9[4], dopac, a9[6], a9[7]);
-            slot[2] = make_float4(db, 0.f, 0.f, 0.f);
+            float dz = 0.f;
+            if constexpr (DEPTH) dz = (a9[NCOL - 4] + a9[NCOL - 3]) + (a9[NCOL - 2] + a9[NCOL - 1]);
+            slot[2] = make_float4(db, dz, 0.f, 0.f);
         }
     }
 }
@@ -727,6 +769,18 @@ k_render_bwd_tile(LR_BWD_SEG_PARAMS)
     LR_BWD_KERNEL_BODY_ONE(LR_ITEM)
 #undef LR_ITEM
 }
+// Depth mode (lr_backward_depth): the 2-wave shape with the depth terms, one workgroup per tile walking its whole list (seg_on = 0:
+// the segment checkpoints hold no depth so far, and the forward is not changed to write one).  Its own entry points, so that the
+// default kernels keep their names and instruction streams.  The two per-pixel registers and the tenth sum fit the 72-register
+// budget of k_render_bwd (72 VGPRs, no spills: 7 waves per SIMD; asked for at least 6).
+template <bool STRICT>
+__global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(6, 8)))
+k_render_bwd_depth(LR_BWD_SEG_PARAMS, const float* __restrict__ dL_ddepth, const float* __restrict__ depth_img)
+{
+#define LR_ITEM(...) render_bwd_item<false, true, STRICT, true>(__VA_ARGS__, dL_ddepth, depth_img)
+    LR_BWD_KERNEL_BODY(LR_ITEM)
+#undef LR_ITEM
+}
 #ifdef LR_DIAGNOSTICS
 // rounds 4-5: the lane-swap reduction (reduce8 + row_merge3), 44 staged Gaussians per round: A/B partner (bwd_red = 2)
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8), amdgpu_num_vgpr(64)))
@@ -827,7 +881,8 @@ int last_bwd_shape() { return g_last_bwd_shape; }
 void launch_render_bwd(int W, int H, int gx, int gy, const uint2* ranges, const uint32_t* point_list,
                        const GaussRec* rec, const float* bg, const float* final_T,
                        const uint32_t* n_contrib, const float* dL_dpix, char* bin_base, const GeomHeader* hdr,
-                       const uint32_t* tile_seg0, const float4* c_final, long long seg_bound, hipStream_t s)
+                       const uint32_t* tile_seg0, const float4* c_final, long long seg_bound, hipStream_t s,
+                       const float* dL_ddepth, const float* depth_img)
 {
     const int num_tiles = gx * gy;
     if (num_tiles <= 0) return;
@@ -848,8 +903,18 @@ void launch_render_bwd(int W, int H, int gx, int gy, const uint2* ranges, const 
 #endif
 #define LR_BWD_ARGS W, H, gx, num_tiles, tile_map, ranges, point_list, rec, bg, final_T, n_contrib, dL_dpix, bin_base, hdr, force_check
     // instances the caller's bound allows (bin_seg_capacity(bound) = bound / BWD_SEG + 2): an upper estimate of the lists' lengths
-    int shape = blend_shape(num_tiles, seg_bound > 2 ? (seg_bound - 2) * (long long)BWD_SEG : -1);
     const bool strict = tune_get(TUNE_STRICT) > 0;
+    if (dL_ddepth != nullptr) {
+        // depth mode: ONE shape at every image size (the 2-wave one), one workgroup per tile over its whole list -- correct for
+        // any launch size, no listed segments (seg_on = 0); the shape rule and the segment switch do not apply
+        g_last_bwd_shape = BLEND_HALF;
+        if (strict) hipLaunchKernelGGL(k_render_bwd_depth<true>, dim3(grid), dim3(128), 0, s, LR_BWD_ARGS, tile_seg0, c_final, grid, 0,
+                                       dL_ddepth, depth_img);
+        else hipLaunchKernelGGL(k_render_bwd_depth<false>, dim3(grid), dim3(128), 0, s, LR_BWD_ARGS, tile_seg0, c_final, grid, 0,
+                                dL_ddepth, depth_img);
+        return;
+    }
+    int shape = blend_shape(num_tiles, seg_bound > 2 ? (seg_bound - 2) * (long long)BWD_SEG : -1);
     // Segments (common.h BWD_SEG): on by default; lr_tune_set("bwd_seg", 0) = one workgroup walks a tile's whole list (rounds
     // 1-4: what the segment tests compare with).  The launch adds workgroups for the listed segments up to the bound the host
     // knows, capped (a workgroup strides over the list, so the cap costs nothing but balance on absurdly long lists).

@@ -174,13 +174,15 @@ FwdResult rasterize_gaussians(const at::Tensor& background, const at::Tensor& me
 // accumulate: eight optional tensors in the order of the returned tuple (means2D, colors, opacity, means3D, cov3D, sh,
 // scales, rotations); a given tensor receives `+=` in place (rows of culled Gaussians untouched) and its slot of the
 // result is None.  skip_unused: gradients of absent input representations are not materialised (None).
+// depth_image (keyword-only; the forward's depth output): depth mode -- dL_dout_depth is honoured (lr_backward_depth); without
+// it dL_dout_depth is ignored, as in the reference.
 std::vector<OptT> rasterize_gaussians_backward(
     const at::Tensor& background, const at::Tensor& means3D, const at::Tensor& radii, const OptT& colors, const OptT& scales,
     const OptT& rotations, double scale_modifier, const OptT& cov3D_precomp, const at::Tensor& viewmatrix,
     const at::Tensor& projmatrix, double tan_fovx, double tan_fovy, const at::Tensor& dL_dout_color, const OptT& dL_dout_depth,
     const OptT& sh, int64_t degree, const at::Tensor& campos, const at::Tensor& geomBuffer, int64_t R,
     const at::Tensor& binningBuffer, const at::Tensor& imageBuffer, bool debug, int64_t binning_capacity,
-    const std::vector<OptT>& accumulate, bool skip_unused)
+    const std::vector<OptT>& accumulate, bool skip_unused, const OptT& depth_image)
 {
     require_device(means3D, "means3D");
     const c10::Device dev = means3D.device();
@@ -221,10 +223,24 @@ std::vector<OptT> rasterize_gaussians_backward(
     if (P != 0) {
         const Arg m = f32(means3D, dev, "means3D"), bg = f32(background, dev, "background"), view = f32(viewmatrix, dev, "viewmatrix"),
                   proj = f32(projmatrix, dev, "projmatrix"), cam = f32(campos, dev, "campos"), shc = f32(sh, dev, "sh"),
-                  gc = f32(dL_dout_color, dev, "dL_dout_color"), gd = f32(dL_dout_depth, dev, "dL_dout_depth");
+                  gc = f32(dL_dout_color, dev, "dL_dout_color"), gd = f32(dL_dout_depth, dev, "dL_dout_depth"),
+                  di = f32(depth_image, dev, "depth_image");
         const at::Tensor radii_c = radii.contiguous();
         hipStream_t cur = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(dev.index()).stream();
         ChainScope chain(mask != 0 || t_fused_backward, dev.index(), cur);
+        if (di.p != nullptr) {
+            TORCH_CHECK(di.t.numel() == H * W, "depth_image must be the forward's depth output (1, H, W)");
+            TORCH_CHECK(!gd.p || gd.t.numel() == H * W, "dL_dout_depth must have the depth output's shape (1, H, W)");
+            const int rc = lr_backward_depth(
+                static_cast<int>(P), static_cast<int>(degree), M, static_cast<int>(R), bg.p, static_cast<int>(W), static_cast<int>(H), m.p,
+                shc.p, col.p, sc.p, static_cast<float>(scale_modifier), rot.p, cov.p, view.p, proj.p, cam.p, static_cast<float>(tan_fovx),
+                static_cast<float>(tan_fovy), radii_c.data_ptr<int>(), static_cast<char*>(geomBuffer.data_ptr()),
+                static_cast<char*>(binningBuffer.data_ptr()), static_cast<char*>(imageBuffer.data_ptr()), gc.p, gd.p, di.p, ptr[0],
+                nullptr, ptr[2], ptr[1], ptr[3], ptr[4], M ? ptr[5] : nullptr, ptr[6], ptr[7], debug ? 1 : 0,
+                static_cast<long long>(binning_capacity), mask, cur);
+            if (rc < 0) raise_for(rc, "rasterize_gaussians_backward");
+            return result;
+        }
         const int rc = lr_backward(static_cast<int>(P), static_cast<int>(degree), M, static_cast<int>(R), bg.p, static_cast<int>(W),
                                    static_cast<int>(H), m.p, shc.p, col.p, sc.p, static_cast<float>(scale_modifier), rot.p, cov.p,
                                    view.p, proj.p, cam.p, static_cast<float>(tan_fovx), static_cast<float>(tan_fovy),
@@ -273,13 +289,15 @@ FwdResult rasterize_gaussians_raw(const at::Tensor& background, const at::Tensor
 }
 
 // result / accumulate order: (means2D, xyz, features_dc, features_rest, opacity, scaling, rotation)
+// dL_dout_depth / depth_image (keyword-only): depth mode as in rasterize_gaussians_backward (lr_backward_raw_depth); the
+// gradient of the depth output is used only when both are given.
 std::vector<OptT> rasterize_gaussians_raw_backward(
     const at::Tensor& background, const at::Tensor& xyz, const at::Tensor& radii, const at::Tensor& features_dc,
     const OptT& features_rest, const at::Tensor& opacity_raw, const at::Tensor& scaling_raw, const at::Tensor& rotation_raw,
     double scale_modifier, const at::Tensor& viewmatrix, const at::Tensor& projmatrix, double tan_fovx, double tan_fovy,
     const at::Tensor& dL_dout_color, int64_t degree, const at::Tensor& campos, const at::Tensor& geomBuffer, int64_t R,
     const at::Tensor& binningBuffer, const at::Tensor& imageBuffer, bool debug, int64_t binning_capacity,
-    const std::vector<OptT>& accumulate, bool no_zero_fill)
+    const std::vector<OptT>& accumulate, bool no_zero_fill, const OptT& dL_dout_depth, const OptT& depth_image)
 {
     require_device(xyz, "xyz");
     const c10::Device dev = xyz.device();
@@ -325,10 +343,24 @@ std::vector<OptT> rasterize_gaussians_raw_backward(
         const Arg bg = f32(background, dev, "background"), x = f32(xyz, dev, "xyz"), dc = f32(features_dc, dev, "features_dc"),
                   op = f32(opacity_raw, dev, "opacity"), sc = f32(scaling_raw, dev, "scaling"), rot = f32(rotation_raw, dev, "rotation"),
                   view = f32(viewmatrix, dev, "viewmatrix"), proj = f32(projmatrix, dev, "projmatrix"), cam = f32(campos, dev, "campos"),
-                  gc = f32(dL_dout_color, dev, "dL_dout_color");
+                  gc = f32(dL_dout_color, dev, "dL_dout_color"), gd = f32(dL_dout_depth, dev, "dL_dout_depth"),
+                  di = f32(depth_image, dev, "depth_image");
         const at::Tensor radii_c = radii.contiguous();
         hipStream_t cur = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(dev.index()).stream();
         ChainScope chain((mask & ~LR_ACC_NO_ZERO_FILL) != 0, dev.index(), cur);
+        if (di.p != nullptr) {
+            TORCH_CHECK(di.t.numel() == H * W, "depth_image must be the forward's depth output (1, H, W)");
+            TORCH_CHECK(!gd.p || gd.t.numel() == H * W, "dL_dout_depth must have the depth output's shape (1, H, W)");
+            const int rc = lr_backward_raw_depth(
+                static_cast<int>(P), static_cast<int>(degree), M, static_cast<int>(R), bg.p, static_cast<int>(W), static_cast<int>(H), x.p,
+                dc.p, rest.p, op.p, sc.p, static_cast<float>(scale_modifier), rot.p, view.p, proj.p, cam.p, static_cast<float>(tan_fovx),
+                static_cast<float>(tan_fovy), radii_c.data_ptr<int>(), static_cast<char*>(geomBuffer.data_ptr()),
+                static_cast<char*>(binningBuffer.data_ptr()), static_cast<char*>(imageBuffer.data_ptr()), gc.p, gd.p, di.p, ptr[0],
+                ptr[4], ptr[1], ptr[2], nrest ? ptr[3] : nullptr, ptr[5], ptr[6], debug ? 1 : 0,
+                static_cast<long long>(binning_capacity), mask, cur);
+            if (rc < 0) raise_for(rc, "rasterize_gaussians_raw_backward");
+            return result;
+        }
         const int rc = lr_backward_raw(static_cast<int>(P), static_cast<int>(degree), M, static_cast<int>(R), bg.p, static_cast<int>(W),
                                        static_cast<int>(H), x.p, dc.p, rest.p, op.p, sc.p, static_cast<float>(scale_modifier), rot.p,
                                        view.p, proj.p, cam.p, static_cast<float>(tan_fovx), static_cast<float>(tan_fovy),
@@ -405,14 +437,14 @@ using torch::autograd::AutogradContext;
 using torch::autograd::variable_list;
 
 struct RasterizeFn : public torch::autograd::Function<RasterizeFn> {
-    static constexpr int kForwardArgs = 21;
+    static constexpr int kForwardArgs = 22;
 
     static variable_list forward(AutogradContext* ctx, const at::Tensor& means3D, const at::Tensor& means2D, const at::Tensor& sh,
                                  const at::Tensor& colors, const at::Tensor& opacities, const at::Tensor& scales,
                                  const at::Tensor& rotations, const at::Tensor& cov3D, const at::Tensor& bg,
                                  const at::Tensor& viewmatrix, const at::Tensor& projmatrix, const at::Tensor& campos,
                                  double scale_modifier, double tan_fovx, double tan_fovy, int64_t H, int64_t W, int64_t degree,
-                                 bool prefiltered, int64_t binning_capacity, bool fused_accumulate)
+                                 bool prefiltered, int64_t binning_capacity, bool fused_accumulate, bool depth_gradient)
     {
         FwdResult r = rasterize_gaussians(bg, means3D, colors, opacities, scales, rotations, scale_modifier, cov3D, viewmatrix,
                                           projmatrix, tan_fovx, tan_fovy, H, W, sh, degree, campos, prefiltered, false,
@@ -441,6 +473,15 @@ struct RasterizeFn : public torch::autograd::Function<RasterizeFn> {
         ctx->saved_data["num_rendered"] = std::get<0>(r);
         ctx->saved_data["capacity"] = binning_capacity;
         ctx->saved_data["fused"] = fused_accumulate;
+        // config.set_depth_gradient, as it was at THIS forward: the depth output is kept for the backward's depth mode
+        // and undefined output gradients stay undefined: a loss that does not use the depth output must reach the default kernels,
+        // not the depth-mode ones with a materialised zero gradient (the switch off keeps torch's default, materialised zeros)
+        // (a DETACHED alias: `depth` is an output of this node, and an output kept in saved_data would hold the node through its
+        // grad_fn -- a reference cycle nothing collects, leaking the node and its scratch buffers at every forward)
+        if (depth_gradient) {
+            ctx->saved_data["depth"] = depth.detach();
+            ctx->set_materialize_grads(false);
+        }
         ctx->mark_non_differentiable({radii, geom});
         return {color, radii, depth, geom};
     }
@@ -458,6 +499,9 @@ struct RasterizeFn : public torch::autograd::Function<RasterizeFn> {
         at::Tensor g_color = grad_out[0];
         if (!g_color.defined()) g_color = at::zeros({3, H, W}, at::TensorOptions().dtype(at::kFloat).device(dev));
         const OptT g_depth = grad_out[2].defined() ? OptT(grad_out[2]) : OptT();
+        // depth mode only when the switch was on at the forward AND a gradient reached the depth output; otherwise the
+        // default call (same kernels, same bits)
+        const OptT depth_image = (g_depth.has_value() && d.find("depth") != d.end()) ? OptT(d["depth"].toTensor()) : OptT();
         // config.set_fused_grad_accumulation: a leaf input whose .grad exists (contiguous float32, 16-byte aligned: the kernels
         // accumulate with 16-byte accesses) receives `+=` inside the kernel; its slot of the result stays undefined
         const bool fused = d["fused"].toBool();
@@ -479,7 +523,7 @@ struct RasterizeFn : public torch::autograd::Function<RasterizeFn> {
             bg, means3D, d["radii"].toTensor(), colors, scales, rotations, d["scale_modifier"].toDouble(), cov3D, viewmatrix,
             projmatrix, d["tan_fovx"].toDouble(), d["tan_fovy"].toDouble(), g_color, g_depth, sh, d["degree"].toInt(), campos,
             d["geom"].toTensor(), d["num_rendered"].toInt(), d["binning"].toTensor(), d["img"].toTensor(), false,
-            d["capacity"].toInt(), acc, true);
+            d["capacity"].toInt(), acc, true, depth_image);
         auto slot = [&](int k) { return g[k].has_value() ? *g[k] : at::Tensor(); };
         variable_list out(kForwardArgs);                       // one per forward argument; undefined = no gradient
         out[0] = slot(3); out[1] = slot(0); out[2] = slot(5); out[3] = slot(1); out[4] = slot(2); out[5] = slot(6); out[6] = slot(7);
@@ -493,10 +537,12 @@ std::vector<at::Tensor> rasterize_autograd(const at::Tensor& means3D, const at::
                                            const at::Tensor& rotations, const at::Tensor& cov3D, const at::Tensor& bg,
                                            const at::Tensor& viewmatrix, const at::Tensor& projmatrix, const at::Tensor& campos,
                                            double scale_modifier, double tan_fovx, double tan_fovy, int64_t H, int64_t W,
-                                           int64_t degree, bool prefiltered, int64_t binning_capacity, bool fused_accumulate)
+                                           int64_t degree, bool prefiltered, int64_t binning_capacity, bool fused_accumulate,
+                                           bool depth_gradient)
 {
     return RasterizeFn::apply(means3D, means2D, sh, colors, opacities, scales, rotations, cov3D, bg, viewmatrix, projmatrix, campos,
-                              scale_modifier, tan_fovx, tan_fovy, H, W, degree, prefiltered, binning_capacity, fused_accumulate);
+                              scale_modifier, tan_fovx, tan_fovy, H, W, degree, prefiltered, binning_capacity, fused_accumulate,
+                              depth_gradient);
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -541,7 +587,7 @@ std::vector<at::Tensor> rasterize_view_step(const at::Tensor& means3D, const at:
         FusedBackwardScope fused_scope(true);
         (void)rasterize_gaussians_backward(bg, means3D, std::get<3>(r), colors, scales, rotations, scale_modifier, cov3D, viewmatrix,
                                            projmatrix, tan_fovx, tan_fovy, grad_color, OptT(), sh, degree, campos, std::get<4>(r),
-                                           std::get<0>(r), std::get<5>(r), std::get<6>(r), false, binning_capacity, acc, true);
+                                           std::get<0>(r), std::get<5>(r), std::get<6>(r), false, binning_capacity, acc, true, OptT());
     }
     return { std::get<1>(r), std::get<3>(r), std::get<2>(r), std::get<4>(r) };
 }
@@ -603,9 +649,21 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
 {
     m.doc() = "luciddreamer_amd: torch <-> liblucid_raster.so (C-ABI) binding of the per-view rasterizer entry points";
     m.def("rasterize_gaussians", &rasterize_gaussians);
-    m.def("rasterize_gaussians_backward", &rasterize_gaussians_backward);
+    // the positional signatures of the two backward entry points are the reference's; the depth-mode inputs are keyword-only
+    m.def("rasterize_gaussians_backward", &rasterize_gaussians_backward, py::arg("background"), py::arg("means3D"),
+          py::arg("radii"), py::arg("colors"), py::arg("scales"), py::arg("rotations"), py::arg("scale_modifier"),
+          py::arg("cov3D_precomp"), py::arg("viewmatrix"), py::arg("projmatrix"), py::arg("tan_fovx"), py::arg("tan_fovy"),
+          py::arg("dL_dout_color"), py::arg("dL_dout_depth"), py::arg("sh"), py::arg("degree"), py::arg("campos"),
+          py::arg("geomBuffer"), py::arg("R"), py::arg("binningBuffer"), py::arg("imageBuffer"), py::arg("debug"),
+          py::arg("binning_capacity"), py::arg("accumulate"), py::arg("skip_unused"), py::kw_only(),
+          py::arg("depth_image") = py::none());
     m.def("rasterize_gaussians_raw", &rasterize_gaussians_raw);
-    m.def("rasterize_gaussians_raw_backward", &rasterize_gaussians_raw_backward);
+    m.def("rasterize_gaussians_raw_backward", &rasterize_gaussians_raw_backward, py::arg("background"), py::arg("xyz"),
+          py::arg("radii"), py::arg("features_dc"), py::arg("features_rest"), py::arg("opacity_raw"), py::arg("scaling_raw"),
+          py::arg("rotation_raw"), py::arg("scale_modifier"), py::arg("viewmatrix"), py::arg("projmatrix"), py::arg("tan_fovx"),
+          py::arg("tan_fovy"), py::arg("dL_dout_color"), py::arg("degree"), py::arg("campos"), py::arg("geomBuffer"), py::arg("R"),
+          py::arg("binningBuffer"), py::arg("imageBuffer"), py::arg("debug"), py::arg("binning_capacity"), py::arg("accumulate"),
+          py::arg("no_zero_fill"), py::kw_only(), py::arg("dL_dout_depth") = py::none(), py::arg("depth_image") = py::none());
     m.def("rasterize_autograd", &rasterize_autograd);
     m.def("last_num_rendered", [] { return g_last_num_rendered; });
     m.def("mark_visible", &mark_visible);

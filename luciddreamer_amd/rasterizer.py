@@ -93,6 +93,11 @@ class _RasterizeGaussians(torch.autograd.Function):
         ctx.leaf_inputs = dict(means3D=means3D, means2D=means2D, sh=sh, colors=colors_precomp, opacity=opacities,
                                scales=scales, rotations=rotations, cov3D=cov3Ds_precomp) \
             if config.fused_grad_accumulation() else None
+        # config.set_depth_gradient as it is at this forward: the depth image is kept for a depth-mode backward
+        # (detached: the output itself on ctx would be a reference cycle through its grad_fn, freed only by the cyclic GC)
+        ctx.depth_image = depth.detach() if config.depth_gradient() else None
+        if ctx.depth_image is not None:
+            ctx.set_materialize_grads(False)        # an unused depth output arrives as None: the default kernels
         ctx.save_for_backward(colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geom, binning, img)
         return color, radii, depth
 
@@ -114,9 +119,12 @@ class _RasterizeGaussians(torch.autograd.Function):
                         and g.data_ptr() % 16 == 0:      # the kernels accumulate with 16-byte accesses; else: dense path
                     accumulate_into[name] = g
         try:
+            # depth mode only with the switch on at the forward AND a gradient for depth; otherwise today's call
+            depth_image = ctx.depth_image if grad_depth is not None else None
             (grad_means2D, grad_colors_precomp, grad_opacities, grad_means3D, grad_cov3Ds_precomp, grad_sh,
              grad_scales, grad_rotations) = _C.rasterize_gaussians_backward(
-                *args, binning_capacity=ctx.binning_capacity, accumulate_into=accumulate_into, skip_unused=True)
+                *args, binning_capacity=ctx.binning_capacity, accumulate_into=accumulate_into, skip_unused=True,
+                depth_image=depth_image)
         except Exception:
             if rs.debug:
                 _snapshot(args, "snapshot_bw.dump")
@@ -156,7 +164,8 @@ def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales,
     def run(cap):
         return _C.rasterize_autograd(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, rs.bg,
                                      rs.viewmatrix, rs.projmatrix, rs.campos, rs.scale_modifier, rs.tanfovx, rs.tanfovy,
-                                     rs.image_height, rs.image_width, rs.sh_degree, rs.prefiltered, cap, fused)
+                                     rs.image_height, rs.image_width, rs.sh_degree, rs.prefiltered, cap, fused,
+                                     config.depth_gradient())
     ticket = -1
     if verifying:
         _C.request_early_header()
@@ -207,6 +216,9 @@ class _RasterizeGaussiansRaw(torch.autograd.Function):
         ctx.leaf_inputs = dict(xyz=xyz, means2D=means2D, features_dc=features_dc, features_rest=features_rest,
                                opacity=opacity, scaling=scaling, rotation=rotation) \
             if config.fused_grad_accumulation() else None
+        ctx.depth_image = depth.detach() if config.depth_gradient() else None       # as _RasterizeGaussians
+        if ctx.depth_image is not None:
+            ctx.set_materialize_grads(False)
         ctx.save_for_backward(xyz, features_dc, features_rest, opacity, scaling, rotation, radii, geom, binning, img)
         return color, radii, depth
 
@@ -216,6 +228,9 @@ class _RasterizeGaussiansRaw(torch.autograd.Function):
         xyz, features_dc, features_rest, opacity, scaling, rotation, radii, geom, binning, img = ctx.saved_tensors
         if grad_out_color is None:
             grad_out_color = torch.zeros((3, rs.image_height, rs.image_width), dtype=torch.float32, device=xyz.device)
+        # depth mode (config.set_depth_gradient at the forward, and a gradient for depth): lr_backward_raw_depth
+        depth = dict(dL_dout_depth=grad_depth, depth_image=ctx.depth_image) \
+            if (grad_depth is not None and ctx.depth_image is not None) else {}
         accumulate_into = None
         if ctx.leaf_inputs is not None:
             def leaf_grad(t):
@@ -239,13 +254,13 @@ class _RasterizeGaussiansRaw(torch.autograd.Function):
             g = _C.rasterize_gaussians_raw_backward(
                 rs.bg, xyz, radii, features_dc, features_rest, opacity, scaling, rotation, rs.scale_modifier, rs.viewmatrix,
                 rs.projmatrix, rs.tanfovx, rs.tanfovy, grad_out_color, rs.sh_degree, rs.campos, geom, ctx.num_rendered,
-                binning, img, False, binning_capacity=ctx.binning_capacity, no_zero_fill=True)
+                binning, img, False, binning_capacity=ctx.binning_capacity, no_zero_fill=True, **depth)
             opt.apply_armed_step(geom, [xyz, features_dc, features_rest, opacity, scaling, rotation], list(g[1:]))
             return None, g[0], None, None, None, None, None, None
         g = _C.rasterize_gaussians_raw_backward(
             rs.bg, xyz, radii, features_dc, features_rest, opacity, scaling, rotation, rs.scale_modifier, rs.viewmatrix,
             rs.projmatrix, rs.tanfovx, rs.tanfovy, grad_out_color, rs.sh_degree, rs.campos, geom, ctx.num_rendered,
-            binning, img, rs.debug, binning_capacity=ctx.binning_capacity, accumulate_into=accumulate_into)
+            binning, img, rs.debug, binning_capacity=ctx.binning_capacity, accumulate_into=accumulate_into, **depth)
         g_means2D, g_xyz, g_dc, g_rest, g_op, g_sc, g_rot = g
         return g_xyz, g_means2D, g_dc, g_rest, g_op, g_sc, g_rot, None
 
