@@ -386,6 +386,48 @@ int lr_views_train_check(const char* workspace, int P, int width, int height, lo
                          void* stream);
 
 /*
+ * The multi-view step with depth supervision (the depth-mode backward of lr_backward_depth, per view).
+ *   lr_views_accumulate_depth: the arguments of lr_views_accumulate plus dL_ddepth (HOST array of n_views DEVICE [H,W]
+ *     pointers, required; a NULL entry gives that view the colour-only backward) and optional out_depth (per-view [H,W]
+ *     device images receiving the rendered depth; NULL entries or array: not returned).  Each view with a depth gradient runs
+ *     the depth-mode backward fed with its own depth image.  Workspace (lr_views_workspace_bytes), overflow check
+ *     (lr_views_check) and chains are exactly those of lr_views_accumulate.
+ *   lr_views_train_depth_accumulate: the arguments of lr_views_train_accumulate plus depth_targets (per-view [H,W] device
+ *     depth maps; pixels whose target is not > 0, NaN included, are ignored), depth_weight (finite, >= 0) and optional
+ *     out_depth.  out_losses: device float[4 * n_views] receiving {loss, l1, ssim, depth_l1} per view, with
+ *     loss = colour loss + depth_weight * depth_l1 and depth_l1 the unweighted masked mean of lr_depth_l1_forward.  Per view,
+ *     on its stream: forward, colour loss, depth loss, depth-mode backward.  With depth_weight == 0 the backward is the
+ *     colour-only one: the gradients are bit-identical to lr_views_train_accumulate's, and depth_l1 is still reported.
+ *     Workspace from lr_views_train_depth_workspace_bytes (>= lr_views_train_workspace_bytes); overflow check with
+ *     lr_views_train_depth_check.
+ * Neither reads config-level switches: the depth arguments are the opt-in.  No host synchronisation.
+ */
+int lr_views_accumulate_depth(int n_views, const float* const* viewmatrices, const float* const* projmatrices,
+                              const float* const* cam_positions, const float* tan_fovx, const float* tan_fovy,
+                              int P, int D, int M, const float* background, int width, int height,
+                              const float* means3D, const float* shs, const float* colors_precomp, const float* opacities,
+                              const float* scales, float scale_modifier, const float* rotations, const float* cov3D_precomp,
+                              const float* const* dL_dpix, const float* const* dL_ddepth, float* const* out_color,
+                              float* const* out_depth, int* const* out_radii,
+                              float* acc_mean2D, float* acc_opacity, float* acc_color, float* acc_mean3D, float* acc_cov3D,
+                              float* acc_sh, float* acc_scale, float* acc_rot,
+                              char* workspace, size_t workspace_bytes, long long binning_capacity, int n_streams,
+                              void* stream);
+size_t lr_views_train_depth_workspace_bytes(int P, int width, int height, long long binning_capacity, int n_streams);
+int lr_views_train_depth_accumulate(int n_views, const float* const* viewmatrices, const float* const* projmatrices,
+                                    const float* const* cam_positions, const float* tan_fovx, const float* tan_fovy,
+                                    int P, int D, int M, const float* background, int width, int height,
+                                    const float* means3D, const float* shs, const float* opacities, const float* scales,
+                                    float scale_modifier, const float* rotations, const float* const* targets,
+                                    float lambda_dssim, const float* const* depth_targets, float depth_weight,
+                                    float* out_losses, float* const* out_color, float* const* out_depth,
+                                    int* const* out_radii, float* acc_mean2D, float* acc_opacity, float* acc_mean3D,
+                                    float* acc_sh, float* acc_scale, float* acc_rot, char* workspace, size_t workspace_bytes,
+                                    long long binning_capacity, int n_streams, void* stream);
+int lr_views_train_depth_check(const char* workspace, int P, int width, int height, long long binning_capacity, int n_streams,
+                               void* stream);
+
+/*
  * Row surgery of the Gaussian parameter set.  The reference changes the number of Gaussians
  * with boolean-mask indexing / torch.cat applied tensor by tensor to the six parameters and both Adam moments of
  * each (R/scene/gaussian_model.py:273-340 prune_points, _prune_optimizer, cat_tensors_to_optimizer; :342-403
@@ -462,6 +504,25 @@ int lr_l1_dssim_backward(int channels, int height, int width, const float* image
  * device scalars (autograd's grad_outputs of the two means) -- no host synchronisation to read them. */
 int lr_l1_dssim_backward_weights(int channels, int height, int width, const float* image, const float* gt, const float* w_l1,
                                  const float* w_ssim, const void* workspace, float* dL_dimage, void* stream);
+
+/*
+ * Masked depth L1, for supervising the rendered depth with a depth map (e.g. a monocular estimate):
+ *     loss = weight * mean_{H*W}( |depth - target| * [target > 0] )
+ *     d loss / d depth = weight * sign(depth - target) * [target > 0] / (H*W)      (sign(0) = 0)
+ * depth, target: [H,W] float32 device images, contiguous (a [1,H,W] depth output as is).  Pixels whose target is not > 0
+ * (no estimate, NaN) contribute nothing, to the value and to the gradient.
+ *   lr_depth_l1_forward : out_loss (device, 1 float); fills `workspace` (device, lr_depth_l1_workspace_bytes) with
+ *                         per-workgroup partial sums, reduced in a fixed order in double.  No host synchronisation.
+ *   lr_depth_l1_backward: dL_ddepth [H,W] = upstream * d loss / d depth; `upstream` is a device scalar (autograd's
+ *                         grad_output) or NULL for 1.  The gradient does not depend on the loss value: one elementwise pass,
+ *                         no workspace.
+ * Deterministic (no atomics): the value is bit-repeatable.  Return 0 or a negative LR_ERR_*.
+ */
+size_t lr_depth_l1_workspace_bytes(int height, int width);
+int lr_depth_l1_forward(int height, int width, const float* depth, const float* target, float weight, float* out_loss,
+                        void* workspace, size_t workspace_bytes, void* stream);
+int lr_depth_l1_backward(int height, int width, const float* depth, const float* target, float weight, const float* upstream,
+                         float* dL_ddepth, void* stream);
 
 /* present[P] (1 byte each) = view-space z > 0.2.  Returns 0 or a negative LR_ERR_*. */
 int lr_mark_visible(int P, const float* means3D, const float* viewmatrix, const float* projmatrix,

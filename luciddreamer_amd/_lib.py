@@ -33,7 +33,9 @@ EXPORTS = ("lr_last_error", "lr_version", "lr_geom_bytes", "lr_img_bytes", "lr_b
            "lr_views_workspace_bytes", "lr_views_accumulate", "lr_views_check",
            "lr_loss_workspace_bytes", "lr_l1_dssim_forward", "lr_l1_dssim_backward", "lr_l1_dssim_backward_weights",
            "lr_select_workspace_bytes", "lr_select_rows", "lr_pack_ply_rows", "lr_adam_step", "lr_adam_step_masked", "lr_densify_stats",
-           "lr_views_train_workspace_bytes", "lr_views_train_accumulate", "lr_views_train_check")
+           "lr_views_train_workspace_bytes", "lr_views_train_accumulate", "lr_views_train_check",
+           "lr_views_accumulate_depth", "lr_views_train_depth_workspace_bytes", "lr_views_train_depth_accumulate",
+           "lr_views_train_depth_check", "lr_depth_l1_workspace_bytes", "lr_depth_l1_forward", "lr_depth_l1_backward")
 
 
 def assert_single_copy():
@@ -133,6 +135,31 @@ def lib():
                                                 vp, ctypes.c_size_t, ll, ci, vp] # workspace, bytes, capacity, n_streams, stream
         L.lr_views_train_check.restype = ci
         L.lr_views_train_check.argtypes = [vp, ci, ci, ci, ll, ci, vp]
+        L.lr_views_accumulate_depth.restype = ci
+        L.lr_views_accumulate_depth.argtypes = [ci, vp, vp, vp, vp, vp,          # n_views, view/proj/campos arrays, tanfovx/y arrays
+                                                ci, ci, ci, vp, ci, ci,          # P D M bg W H
+                                                vp, vp, vp, vp, vp, cf, vp, vp,  # means3D shs colors opac scales mod rot cov3D
+                                                vp, vp, vp, vp, vp,              # dL_dpix[], dL_ddepth[], out_color[], out_depth[], out_radii[]
+                                                vp, vp, vp, vp, vp, vp, vp, vp,  # 8 accumulators
+                                                vp, ctypes.c_size_t, ll, ci, vp] # workspace, bytes, capacity, n_streams, stream
+        L.lr_views_train_depth_workspace_bytes.restype = ctypes.c_size_t
+        L.lr_views_train_depth_workspace_bytes.argtypes = [ci, ci, ci, ll, ci]
+        L.lr_views_train_depth_accumulate.restype = ci
+        L.lr_views_train_depth_accumulate.argtypes = [ci, vp, vp, vp, vp, vp,    # n_views, view/proj/campos arrays, tanfovx/y arrays
+                                                      ci, ci, ci, vp, ci, ci,    # P D M bg W H
+                                                      vp, vp, vp, vp, cf, vp,    # means3D shs opac scales mod rot
+                                                      vp, cf, vp, cf,            # targets[], lambda, depth_targets[], depth_weight
+                                                      vp, vp, vp, vp,            # out_losses, out_color[], out_depth[], out_radii[]
+                                                      vp, vp, vp, vp, vp, vp,    # 6 accumulators
+                                                      vp, ctypes.c_size_t, ll, ci, vp]
+        L.lr_views_train_depth_check.restype = ci
+        L.lr_views_train_depth_check.argtypes = [vp, ci, ci, ci, ll, ci, vp]
+        L.lr_depth_l1_workspace_bytes.restype = ctypes.c_size_t
+        L.lr_depth_l1_workspace_bytes.argtypes = [ci, ci]
+        L.lr_depth_l1_forward.restype = ci
+        L.lr_depth_l1_forward.argtypes = [ci, ci, vp, vp, cf, vp, vp, ctypes.c_size_t, vp]
+        L.lr_depth_l1_backward.restype = ci
+        L.lr_depth_l1_backward.argtypes = [ci, ci, vp, vp, cf, vp, vp, vp]
         L.lr_loss_workspace_bytes.restype = ctypes.c_size_t
         L.lr_loss_workspace_bytes.argtypes = [ci, ci, ci]
         L.lr_l1_dssim_forward.restype = ci

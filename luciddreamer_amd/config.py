@@ -250,27 +250,42 @@ def verify(means3D, rs, ticket) -> bool:
     return over
 
 
-def offer_grad_output(grad_output):
+def offer_grad_output(grad_output, grad_depth=None):
     """parallel.ViewStreams.run_view: the NEXT rasterizer call on this thread may run its backward right behind its forward
-    with this dL/dcolor (one call into the binding, no autograd node: rasterizer.rasterize_gaussians); None withdraws the
-    offer.  Whether it was taken: grad_output_taken()."""
+    with this dL/dcolor -- and dL/ddepth, if given: the depth-mode backward -- (one call into the binding, no autograd node:
+    rasterizer.rasterize_gaussians); None withdraws the offer.  Whether it was taken: grad_output_taken()."""
     _tls.offered_grad = grad_output
+    _tls.offered_depth = grad_depth if grad_output is not None else None
     _tls.grad_taken = False
+    _tls.taken_outputs = None
 
 
 def offered_grad_output():
     return getattr(_tls, "offered_grad", None)
 
 
-def mark_grad_output_taken():
+def offered_grad_depth():
+    return getattr(_tls, "offered_depth", None)
+
+
+def mark_grad_output_taken(outputs=None):
+    """outputs: the (color, depth) the call that took the offer returned (taken_outputs())."""
     _tls.offered_grad = None
+    _tls.offered_depth = None
     _tls.grad_taken = True
+    _tls.taken_outputs = outputs
 
 
 def grad_output_taken() -> bool:
     """True once if the offer of offer_grad_output() was taken (the view's gradients are already accumulated); clears it."""
-    taken, _tls.grad_taken, _tls.offered_grad = getattr(_tls, "grad_taken", False), False, None
+    taken, _tls.grad_taken, _tls.offered_grad, _tls.offered_depth = getattr(_tls, "grad_taken", False), False, None, None
     return taken
+
+
+def taken_outputs():
+    """(color, depth) of the rasterizer call that last took an offer on this thread (None if none did); cleared by the call."""
+    out, _tls.taken_outputs = getattr(_tls, "taken_outputs", None), None
+    return out
 
 
 def take_last_entry():

@@ -499,6 +499,15 @@ void launch_loss_forward(int C, int H, int W, const float* img, const float* gt,
                          hipStream_t s, bool defer_final = false);
 void launch_loss_backward(int C, int H, int W, const float* img, const float* gt, float lambda, const float* upstream,
                           const char* ws, float* grad, hipStream_t s, float* final_out3 = nullptr, const float* w_ssim = nullptr);
+// masked depth L1 (loss.hip).  The value, by final_mode: DEPTH_L1_VALUE out[0] = weight * mean(|depth - target| [target > 0]);
+// DEPTH_L1_FUSED (fused step, out = the view's {loss, l1, ssim, depth_l1}) out[0] += weight * mean, out[3] = mean;
+// DEPTH_L1_DEFER left to launch_depth_l1_backward(..., fused_out), which does what DEPTH_L1_FUSED does
+enum DepthL1Final { DEPTH_L1_VALUE = 0, DEPTH_L1_FUSED = 1, DEPTH_L1_DEFER = 2 };
+size_t depth_l1_workspace_bytes(int H, int W);
+void launch_depth_l1_forward(int H, int W, const float* depth, const float* target, float weight, float* out, char* ws,
+                             hipStream_t s, DepthL1Final final_mode = DEPTH_L1_VALUE);
+void launch_depth_l1_backward(int H, int W, const float* depth, const float* target, float weight, const float* upstream,
+                              const char* ws, float* grad, hipStream_t s, float* fused_out = nullptr);
 // bit positions of lr_backward's accumulate_mask (LR_ACC_* in lucid_raster.h)
 enum { ACC_MEAN2D = 0, ACC_CONIC = 1, ACC_OPACITY = 2, ACC_COLOR = 3, ACC_MEAN3D = 4, ACC_COV3D = 5, ACC_SH = 6,
        ACC_SCALE = 7, ACC_ROT = 8 };

@@ -359,6 +359,106 @@ k_ssim_bwd(int H, int W, int tiles_x, int tiles_y, Win win, float lambda, float 
     }
 }
 
+// ---- masked depth L1 (supervision of the rendered depth against a depth map, e.g. a monocular estimate) -------------------
+//     loss = weight * mean_{H*W}( |depth - target| * [target > 0] ),   d loss / d depth = weight * sign(depth - target) * [target > 0] / (H*W)
+// A target that is not > 0 (no estimate, NaN) contributes nothing: the masked pixels are SELECTED away, so a NaN target never
+// reaches the sum or the gradient.  HBM-bound (12 B per pixel over both passes); deterministic: fixed per-workgroup
+// partial sums, reduced in a fixed order in double; no atomics.
+constexpr int DL_ITEMS = 8;                          // pixels per thread
+constexpr int DL_BLOCK = LTHREADS * DL_ITEMS;        // pixels per workgroup (2048)
+
+__device__ __forceinline__ double block_sum_d(double v, double* s_tmp)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+    const int w = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) s_tmp[w] = v;
+    lds_barrier();
+    return (s_tmp[0] + s_tmp[1]) + (s_tmp[2] + s_tmp[3]);
+}
+
+__global__ void __launch_bounds__(LTHREADS)
+k_depth_l1_fwd(int n, const float* __restrict__ depth, const float* __restrict__ target, double* __restrict__ partials)
+{
+    __shared__ double s_tmp[4];
+    const int base = (int)blockIdx.x * DL_BLOCK + (int)threadIdx.x;
+    float d[DL_ITEMS], t[DL_ITEMS];
+#pragma unroll
+    for (int i = 0; i < DL_ITEMS; i++) {             // all loads first; pixel base + 256 i: coalesced
+        const int q = base + i * LTHREADS;
+        const bool ok = q < n;
+        d[i] = ok ? depth[q] : 0.f;
+        t[i] = ok ? target[q] : 0.f;
+    }
+    float sum = 0.f;
+#pragma unroll
+    for (int i = 0; i < DL_ITEMS; i++) sum += t[i] > 0.f ? fabsf(d[i] - t[i]) : 0.f;
+    const double bs = block_sum_d((double)sum, s_tmp);
+    if (threadIdx.x == 0) partials[blockIdx.x] = bs;
+}
+
+// {weight * mean, mean} of the partials, fixed order; fused step (out_losses of lr_views_train_depth_accumulate): the colour
+// loss already in out[0] gets the weighted depth term added, the unweighted mean goes to out[3]
+__device__ __forceinline__ void depth_l1_final(int n_blocks, double n_elems, float weight, const double* __restrict__ partials,
+                                               float* __restrict__ out, bool fused, double* s_a)
+{
+    double a = 0.0;
+    for (int i = threadIdx.x; i < n_blocks; i += LTHREADS) a += partials[i];
+    s_a[threadIdx.x] = a;
+    lds_barrier();
+    for (int off = LTHREADS / 2; off > 0; off >>= 1) {
+        if ((int)threadIdx.x < off) s_a[threadIdx.x] += s_a[threadIdx.x + off];
+        lds_barrier();
+    }
+    if (threadIdx.x == 0) {
+        const float mean = (float)(s_a[0] / n_elems);
+        if (fused) { if (weight != 0.f) out[0] = out[0] + weight * mean; out[3] = mean; }
+        else { out[0] = weight * mean; }
+    }
+}
+
+__global__ void __launch_bounds__(LTHREADS)
+k_depth_l1_final(int n_blocks, double n_elems, float weight, const double* __restrict__ partials, float* __restrict__ out,
+                 int fused)
+{
+    __shared__ double s_a[LTHREADS];
+    depth_l1_final(n_blocks, n_elems, weight, partials, out, fused != 0, s_a);
+}
+
+// dL/ddepth = (upstream * weight) / n * sign(depth - target) * [target > 0]: the product, divided, is what torch's autograd of
+// the definition forms (mul backward, then mean backward's division), so the gradient is bit-equal to it.  fused_out: the
+// fused step's loss value (depth_l1_final) rides in workgroup 0, one launch less per view.
+__global__ void __launch_bounds__(LTHREADS)
+k_depth_l1_bwd(int n, float weight, const float* __restrict__ upstream, const float* __restrict__ depth,
+               const float* __restrict__ target, float* __restrict__ grad, const double* __restrict__ partials, int n_blocks,
+               float* __restrict__ fused_out)
+{
+    if (fused_out != nullptr && blockIdx.x == 0) {
+        __shared__ double s_a[LTHREADS];
+        depth_l1_final(n_blocks, (double)n, weight, partials, fused_out, true, s_a);
+    }
+    const float up = upstream != nullptr ? upstream[0] : 1.0f;
+    const float k = (up * weight) / (float)n;
+    const int base = (int)blockIdx.x * DL_BLOCK + (int)threadIdx.x;
+    float d[DL_ITEMS], t[DL_ITEMS];
+#pragma unroll
+    for (int i = 0; i < DL_ITEMS; i++) {
+        const int q = base + i * LTHREADS;
+        const bool ok = q < n;
+        d[i] = ok ? depth[q] : 0.f;
+        t[i] = ok ? target[q] : 0.f;
+    }
+#pragma unroll
+    for (int i = 0; i < DL_ITEMS; i++) {
+        const int q = base + i * LTHREADS;
+        if (q < n) {
+            const float r = d[i] - t[i];
+            const float sgn = r > 0.f ? 1.f : (r < 0.f ? -1.f : 0.f);       // torch.abs backward: sign, 0 at 0
+            grad[q] = t[i] > 0.f ? sgn * k : 0.f;
+        }
+    }
+}
+
 }  // namespace
 
 size_t loss_workspace_bytes(int C, int H, int W)
@@ -393,6 +493,38 @@ void launch_loss_backward(int C, int H, int W, const float* img, const float* gt
     const float2* partials = reinterpret_cast<const float2*>(ws + align_up(3 * n * sizeof(float)));
     hipLaunchKernelGGL(k_ssim_bwd, dim3((C * tx * ty + 7) / 8 * 8), dim3(LTHREADS), 0, s, H, W, tx, ty, win, lambda, (float)(1.0 / (double)n),
                        upstream, w_ssim, img, gt, D, D + n, D + 2 * n, grad, partials, C * tx * ty, (double)n, final_out3);
+}
+
+}  // namespace lr
+
+namespace lr {
+
+size_t depth_l1_workspace_bytes(int H, int W)
+{
+    const size_t n = (size_t)H * W;
+    return align_up(((n + DL_BLOCK - 1) / DL_BLOCK) * sizeof(double));
+}
+
+void launch_depth_l1_forward(int H, int W, const float* depth, const float* target, float weight, float* out, char* ws,
+                             hipStream_t s, DepthL1Final final_mode)
+{
+    const int n = H * W;
+    const int blocks = (n + DL_BLOCK - 1) / DL_BLOCK;
+    double* partials = reinterpret_cast<double*>(ws);
+    hipLaunchKernelGGL(k_depth_l1_fwd, dim3(blocks), dim3(LTHREADS), 0, s, n, depth, target, partials);
+    // DEPTH_L1_DEFER: launch_depth_l1_backward(..., fused_out) follows on the same stream and forms the value
+    if (final_mode != DEPTH_L1_DEFER)
+        hipLaunchKernelGGL(k_depth_l1_final, dim3(1), dim3(LTHREADS), 0, s, blocks, (double)n, weight, partials, out,
+                           final_mode == DEPTH_L1_FUSED ? 1 : 0);
+}
+
+void launch_depth_l1_backward(int H, int W, const float* depth, const float* target, float weight, const float* upstream,
+                              const char* ws, float* grad, hipStream_t s, float* fused_out)
+{
+    const int n = H * W;
+    const int blocks = (n + DL_BLOCK - 1) / DL_BLOCK;
+    hipLaunchKernelGGL(k_depth_l1_bwd, dim3(blocks), dim3(LTHREADS), 0, s, n, weight, upstream, depth, target, grad,
+                       reinterpret_cast<const double*>(ws), blocks, fused_out);
 }
 
 }  // namespace lr

@@ -555,13 +555,16 @@ std::vector<at::Tensor> rasterize_autograd(const at::Tensor& means3D, const at::
 // (RasterizeFn::backward above), in the same accumulate chain.  Returns an empty vector -- nothing done -- when an input does
 // not qualify: the caller takes the autograd path.  Otherwise (color, radii, depth, geom) with num_rendered in
 // last_num_rendered(); the images carry no grad_fn.
+// grad_depth (optional, [1,H,W]): dL/ddepth as well -- the backward is the depth-mode one (lr_backward_depth) fed with this
+// forward's own depth image; as the explicit opt-in it does not read config.set_depth_gradient.
 // ------------------------------------------------------------------------------------------------------------------
 std::vector<at::Tensor> rasterize_view_step(const at::Tensor& means3D, const at::Tensor& means2D, const at::Tensor& sh,
                                             const at::Tensor& colors, const at::Tensor& opacities, const at::Tensor& scales,
                                             const at::Tensor& rotations, const at::Tensor& cov3D, const at::Tensor& bg,
                                             const at::Tensor& viewmatrix, const at::Tensor& projmatrix, const at::Tensor& campos,
                                             double scale_modifier, double tan_fovx, double tan_fovy, int64_t H, int64_t W,
-                                            int64_t degree, bool prefiltered, int64_t binning_capacity, const at::Tensor& grad_color)
+                                            int64_t degree, bool prefiltered, int64_t binning_capacity, const at::Tensor& grad_color,
+                                            const OptT& grad_depth)
 {
     require_device(means3D, "means3D");
     const c10::Device dev = means3D.device();
@@ -579,6 +582,10 @@ std::vector<at::Tensor> rasterize_view_step(const at::Tensor& means3D, const at:
         acc[k] = g;
     }
     if (!grad_color.defined() || grad_color.dim() != 3 || grad_color.size(1) != H || grad_color.size(2) != W) return {};
+    const bool depth_mode = grad_depth.has_value() && grad_depth->defined();
+    if (depth_mode)
+        TORCH_CHECK(grad_depth->numel() == H * W && grad_depth->size(-1) == W && grad_depth->size(-2) == H,
+                    "grad_depth must have the depth output's shape (1, H, W)");
     at::NoGradGuard no_grad;
     FwdResult r = rasterize_gaussians(bg, means3D, colors, opacities, scales, rotations, scale_modifier, cov3D, viewmatrix,
                                       projmatrix, tan_fovx, tan_fovy, H, W, sh, degree, campos, prefiltered, false, binning_capacity);
@@ -586,8 +593,9 @@ std::vector<at::Tensor> rasterize_view_step(const at::Tensor& means3D, const at:
     if (means3D.size(0) != 0) {
         FusedBackwardScope fused_scope(true);
         (void)rasterize_gaussians_backward(bg, means3D, std::get<3>(r), colors, scales, rotations, scale_modifier, cov3D, viewmatrix,
-                                           projmatrix, tan_fovx, tan_fovy, grad_color, OptT(), sh, degree, campos, std::get<4>(r),
-                                           std::get<0>(r), std::get<5>(r), std::get<6>(r), false, binning_capacity, acc, true, OptT());
+                                           projmatrix, tan_fovx, tan_fovy, grad_color, depth_mode ? grad_depth : OptT(), sh, degree,
+                                           campos, std::get<4>(r), std::get<0>(r), std::get<5>(r), std::get<6>(r), false,
+                                           binning_capacity, acc, true, depth_mode ? OptT(std::get<2>(r)) : OptT());
     }
     return { std::get<1>(r), std::get<3>(r), std::get<2>(r), std::get<4>(r) };
 }
@@ -667,7 +675,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
     m.def("rasterize_autograd", &rasterize_autograd);
     m.def("last_num_rendered", [] { return g_last_num_rendered; });
     m.def("mark_visible", &mark_visible);
-    m.def("rasterize_view_step", &rasterize_view_step);
+    m.def("rasterize_view_step", &rasterize_view_step, py::arg("means3D"), py::arg("means2D"), py::arg("sh"), py::arg("colors"),
+          py::arg("opacities"), py::arg("scales"), py::arg("rotations"), py::arg("cov3D"), py::arg("bg"), py::arg("viewmatrix"),
+          py::arg("projmatrix"), py::arg("campos"), py::arg("scale_modifier"), py::arg("tan_fovx"), py::arg("tan_fovy"), py::arg("H"),
+          py::arg("W"), py::arg("degree"), py::arg("prefiltered"), py::arg("binning_capacity"), py::arg("grad_color"),
+          py::arg("grad_depth") = py::none());
     m.def("adam_step_masked", &adam_step_masked);
     m.def("check", &check);
     m.def("header_post", &header_post);

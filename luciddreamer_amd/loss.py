@@ -179,3 +179,62 @@ class PairedLoss:
                 return self._fallback_ssim(img1, img2, window_size, size_average)
             raise NotImplementedError("fused ssim: float32 [..., 3, H, W] device tensors, window_size=11, size_average=True")
         return self._get(img1, img2)[1]
+
+
+_DEPTH_WS_BYTES = {}                # (H, W) -> lr_depth_l1_workspace_bytes
+
+
+def _depth_dims(depth, target):
+    if not depth.is_cuda or not target.is_cuda:
+        raise RuntimeError("luciddreamer_amd.loss.depth_l1: depth and target must be on a HIP device (no CPU path)")
+    if depth.dtype != torch.float32 or target.dtype != torch.float32:
+        raise RuntimeError("depth and target must be float32")
+    ok = lambda t: t.dim() == 2 or (t.dim() == 3 and t.shape[0] == 1)
+    if not ok(depth) or not ok(target) or depth.shape[-2:] != target.shape[-2:]:
+        raise RuntimeError(f"depth {tuple(depth.shape)} and target {tuple(target.shape)} must be [1,H,W] or [H,W] of one H, W")
+    return int(depth.shape[-2]), int(depth.shape[-1])
+
+
+class _DepthL1(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, depth, target, weight):
+        H, W = _depth_dims(depth, target)
+        d, t = depth.contiguous(), target.contiguous()
+        L = _lib.lib()
+        dev = d.device
+        n = _DEPTH_WS_BYTES.get((H, W))
+        if n is None:
+            n = _DEPTH_WS_BYTES[(H, W)] = int(L.lr_depth_l1_workspace_bytes(H, W))
+        out = torch.empty((1,), dtype=torch.float32, device=dev)
+        ws = torch.empty((n,), dtype=torch.uint8, device=dev)
+        with _lib.on_device(dev):
+            rc = L.lr_depth_l1_forward(H, W, d.data_ptr(), t.data_ptr(), float(weight), out.data_ptr(), ws.data_ptr(),
+                                       ws.numel(), torch.cuda.current_stream(dev).cuda_stream)
+        if rc < 0:
+            _lib.raise_for(rc, "depth_l1")
+        ctx.save_for_backward(d, t)
+        ctx.weight, ctx.dims, ctx.in_shape = float(weight), (H, W), depth.shape
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        d, t = ctx.saved_tensors
+        H, W = ctx.dims
+        L = _lib.lib()
+        dev = d.device
+        up = _weight(grad_out, dev)
+        grad = torch.empty_like(d)
+        with _lib.on_device(dev):
+            rc = L.lr_depth_l1_backward(H, W, d.data_ptr(), t.data_ptr(), ctx.weight, up.data_ptr(), grad.data_ptr(),
+                                        torch.cuda.current_stream(dev).cuda_stream)
+        if rc < 0:
+            _lib.raise_for(rc, "depth_l1 backward")
+        return grad.view(ctx.in_shape), None, None
+
+
+def depth_l1(depth, target, weight=1.0):
+    """weight * mean over all H*W pixels of |depth - target| where target > 0 (a target that is not > 0, NaN included,
+    contributes nothing); depth, target: [1,H,W] or [H,W] float32.  One HIP pass forward (per-workgroup partial sums, reduced in
+    a fixed order in double: bit-repeatable) and one elementwise pass backward (lr_depth_l1_forward / lr_depth_l1_backward).
+    Gradients flow to `depth` only (the target is data)."""
+    return _DepthL1.apply(depth, target, weight)

@@ -589,14 +589,15 @@ def _calling_thread_backward():
     return contextlib.nullcontext()
 
 
-def _direct_backward(out: torch.Tensor, grad_output: torch.Tensor) -> bool:
+def _direct_backward(out: torch.Tensor, grad_output: torch.Tensor, grad_depth: Optional[torch.Tensor] = None) -> bool:
     """Backward of ONE rasterizer node without the autograd engine: `out` must be the image returned by the rasterizer op,
     every differentiable input of the node a LEAF (its next function an AccumulateGrad, or none), and fused gradient
     accumulation on, so that the node's kernels add into the leaves' .grad in place.  The node is called on the calling thread
     and current stream (= the stream of its forward); a gradient it returns for a leaf it could not accumulate into (no .grad
     yet, unsuitable layout) is added the way AccumulateGrad would.  Returns False -- nothing done -- when the shape of the
     graph is anything else: the caller goes through the engine then.  Tensor hooks on the leaves are not run (as with fused
-    accumulation in general, config.set_fused_grad_accumulation)."""
+    accumulation in general, config.set_fused_grad_accumulation).  grad_depth: dL/d depth of the same node's depth output
+    (run_view checked that it is one): the node's depth-mode backward."""
     from . import config
     fn = out.grad_fn
     if fn is None or not config.fused_grad_accumulation() or "Rasterize" not in type(fn).__name__ + fn.name():
@@ -614,7 +615,7 @@ def _direct_backward(out: torch.Tensor, grad_output: torch.Tensor) -> bool:
             leaves.append(nxt.variable)
         else:
             return False
-    grads = fn(grad_output, None, None, None)                    # the compiled node's outputs: (color, radii, depth, geom)
+    grads = fn(grad_output, None, grad_depth, None)              # the compiled node's outputs: (color, radii, depth, geom)
     if not isinstance(grads, (tuple, list)):
         grads = (grads,)
     with torch.no_grad():
@@ -622,6 +623,26 @@ def _direct_backward(out: torch.Tensor, grad_output: torch.Tensor) -> bool:
             if leaf is not None and g is not None:
                 leaf.grad = g if leaf.grad is None else leaf.grad.add_(g)
     return True
+
+
+def _rasterizer_pair(out, taken):
+    """(color, depth) of what a run_view forward_fn returned with grad_depth: it must be the very pair ONE rasterizer call
+    returned -- the images of the fused step (`taken`: config.taken_outputs()) or two outputs of one rasterizer autograd node
+    (color its output 0, depth its output 2).  Anything else (a post-processed image, a depth map of another call) would have
+    its gradient applied to the wrong tensors: RuntimeError."""
+    if not (isinstance(out, (tuple, list)) and len(out) == 2 and all(isinstance(t, torch.Tensor) for t in out)):
+        raise RuntimeError("run_view(grad_depth=...): forward_fn must return (color, depth), the pair one rasterizer call returned")
+    color, depth = out
+    if taken is not None:
+        if color is taken[0] and depth is taken[1]:
+            return color, depth
+    else:
+        fn = color.grad_fn
+        if (fn is not None and depth.grad_fn is fn and "Rasterize" in type(fn).__name__ + fn.name()
+                and color.output_nr == 0 and depth.output_nr == 2):
+            return color, depth
+    raise RuntimeError("run_view(grad_depth=...): forward_fn must return the rasterizer's own (color, depth) outputs, "
+                       "unmodified -- not a post-processed image or another call's depth")
 
 
 class ViewStreams:
@@ -703,7 +724,8 @@ class ViewStreams:
             self._policy = None
             _lib.tune_set("views_in_flight", -1)
 
-    def run_view(self, forward_fn: Callable, backward_fn: Optional[Callable] = None, grad_output: Optional[torch.Tensor] = None):
+    def run_view(self, forward_fn: Callable, backward_fn: Optional[Callable] = None, grad_output: Optional[torch.Tensor] = None,
+                 grad_depth: Optional[torch.Tensor] = None):
         """forward_fn() -> the view's output tensor, issued on the next stream of the ring.  Then EITHER
         backward_fn(out): the view's backward right away (its own pass of the autograd engine), chained behind the previous
             view's by an event; OR
@@ -715,10 +737,22 @@ class ViewStreams:
             (csrc/torch_ext.cpp AccumulateChain), so the gradients are those of the per-view form.  With `direct` (default)
             and `out` the rasterizer's own output over LEAF inputs under fused gradient accumulation, there is nothing for the
             engine to do at all -- one node, gradients added in place by its kernels -- and the node is called right here, on
-            this thread (_direct_backward): ~25 us instead of the engine's ~110 us per view, no grouping needed."""
+            this thread (_direct_backward): ~25 us instead of the engine's ~110 us per view, no grouping needed.
+        grad_depth (with grad_output): dL/d depth as well -- forward_fn must then return (color, depth), the very tensors one
+            rasterizer call returned (RuntimeError otherwise), and the view's backward is the depth-mode one on every path
+            (fused step, direct node call, engine, the re-run of an overflowed view).  Needs config.set_depth_gradient(True)
+            (ValueError otherwise: the autograd paths would drop the depth gradient)."""
         from . import config
         if (backward_fn is None) == (grad_output is None):
             raise ValueError("give exactly one of backward_fn / grad_output")
+        if grad_depth is not None:
+            if grad_output is None:
+                raise ValueError("grad_depth goes with grad_output (a backward_fn forms its own loss)")
+            if not config.depth_gradient():
+                raise ValueError("run_view(grad_depth=...) needs config.set_depth_gradient(True): without it the rasterizer's "
+                                 "backward ignores the depth gradient")
+            if not isinstance(grad_depth, torch.Tensor):
+                raise ValueError("grad_depth must be a tensor (dL/d depth, shape (1, H, W))")
         s = self.streams[self._i % len(self.streams)]
         # set_stream instead of the `with torch.cuda.stream(s)` context: the context manager's save / restore per view is
         # ~10 us of host time on a path that is host bound; end_step() puts the caller's stream back
@@ -727,14 +761,20 @@ class ViewStreams:
             config.take_last_entry()
             # grad_output known up front: the rasterizer call inside forward_fn may run its backward right behind its forward
             # (one call into the binding, no autograd node -- rasterizer.rasterize_gaussians); if it did, nothing is left to do
-            config.offer_grad_output(grad_output if (grad_output is not None and self.direct) else None)
+            config.offer_grad_output(grad_output if (grad_output is not None and self.direct) else None, grad_depth)
             try:
                 out = forward_fn()
             finally:
                 taken = config.grad_output_taken()
+                taken_out = config.taken_outputs()
             entry = config.take_last_entry()                 # this view's header entry, if its forward was an async one
+            if grad_depth is not None:
+                out, out_depth = _rasterizer_pair(out, taken_out)
+                # (end_step: a lost view, run again -- its forward_fn returns the pair again)
+                redo = lambda o, g=grad_output, gd=grad_depth: torch.autograd.backward([o[0], o[1]], [g, gd])
             if taken:
-                redo = lambda o, g=grad_output: torch.autograd.backward([o], [g])     # (end_step: a lost view, run again)
+                if grad_depth is None:
+                    redo = lambda o, g=grad_output: torch.autograd.backward([o], [g])     # (end_step: a lost view, run again)
             elif backward_fn is not None:
                 if self._prev_bwd is not None:
                     s.wait_event(self._prev_bwd)
@@ -744,9 +784,14 @@ class ViewStreams:
                 ev.record(s)
                 self._prev_bwd = ev
                 redo = backward_fn
+            elif grad_depth is not None:
+                if not (self.direct and _direct_backward(out, grad_output, grad_depth)):
+                    self._deferred.append(((out, grad_output), (out_depth, grad_depth)))
+                    if len(self._deferred) >= self.group:
+                        self._flush()
             else:
                 if not (self.direct and _direct_backward(out, grad_output)):
-                    self._deferred.append((out, grad_output))
+                    self._deferred.append(((out, grad_output),))
                     if len(self._deferred) >= self.group:
                         self._flush()
                 redo = lambda o, g=grad_output: torch.autograd.backward([o], [g])     # (end_step: a lost view, run again)
@@ -762,7 +807,7 @@ class ViewStreams:
 
     def _flush(self):
         if self._deferred:
-            outs, grads = zip(*self._deferred)
+            outs, grads = zip(*[pair for view in self._deferred for pair in view])     # (output, gradient) pairs of every view
             self._deferred = []
             with _calling_thread_backward():
                 torch.autograd.backward(list(outs), list(grads))
@@ -816,21 +861,37 @@ class ViewBatch:
 
     def __init__(self, cams: Sequence, grad_colors: Optional[Sequence[torch.Tensor]], sh_degree: int, bg: torch.Tensor,
                  binning_capacity: int, n_streams: int = 2, scale_modifier: float = 1.0,
-                 targets: Optional[Sequence[torch.Tensor]] = None, lambda_dssim: float = 0.2):
+                 targets: Optional[Sequence[torch.Tensor]] = None, lambda_dssim: float = 0.2,
+                 grad_depths: Optional[Sequence[torch.Tensor]] = None,
+                 depth_targets: Optional[Sequence[torch.Tensor]] = None, depth_weight: Optional[float] = None,
+                 depths: Optional[Sequence[torch.Tensor]] = None):
         """grad_colors: fixed upstream gradients dL/dcolor per view, OR targets: ground-truth images per view, in which
         case every view's L1 + DSSIM loss against its target is formed inside the call (lr_views_train_accumulate) and
-        `self.losses` ([n,3] device tensor: loss, l1, ssim per view) is filled by run()."""
+        `self.losses` ([n,3] device tensor: loss, l1, ssim per view) is filled by run().
+        Depth supervision (the depth-mode backward of every view; the arguments are the opt-in, config.set_depth_gradient is
+        not read):
+          grad_depths (with grad_colors): fixed dL/d depth per view, [1,H,W] or [H,W] (lr_views_accumulate_depth);
+          depth_targets (with targets): depth maps per view, [1,H,W] or [H,W]; pixels whose target is not > 0 are ignored.
+            The masked depth L1 (loss.depth_l1) joins each view's loss with depth_weight (default 1.0, >= 0), and
+            `self.losses` is [n,4]: loss (= colour loss + depth_weight * depth_l1), l1, ssim, depth_l1
+            (lr_views_train_depth_accumulate).  depth_weight 0 reports depth_l1 with the colour-only gradients.
+          depths: per-view [1,H,W] or [H,W] contiguous float32 device tensors that run() fills with the rendered depth (not
+            with targets alone).
+        Arguments are checked before any device work."""
         import ctypes
         import math
-        from . import _lib
-        self._lib = _lib
-        self.L = _lib.lib()
         self.cams = list(cams)
         self.n = len(self.cams)
         if (grad_colors is None) == (targets is None):
             raise ValueError("give exactly one of grad_colors / targets")
-        assert self.n == len(grad_colors if targets is None else targets) and self.n > 0
+        if self.n == 0 or self.n != len(grad_colors if targets is None else targets):
+            raise ValueError("one grad_colors / targets entry per camera, and at least one camera")
         self.W, self.H = int(self.cams[0].image_width), int(self.cams[0].image_height)
+        self.train_depth = depth_targets is not None
+        self._check_depth_args(grad_colors, targets, grad_depths, depth_targets, depth_weight, depths)
+        from . import _lib
+        self._lib = _lib
+        self.L = _lib.lib()
         self.device = self.cams[0].world_view_transform.device
         self.degree, self.scale_modifier = int(sh_degree), float(scale_modifier)
         self.capacity, self.n_streams = int(binning_capacity), int(n_streams)
@@ -847,12 +908,49 @@ class ViewBatch:
         self.train = targets is not None
         self.lambda_dssim = float(lambda_dssim)
         self._grads = ptr_array(grad_colors if not self.train else targets)     # per-view dL/dcolor, or target images
-        self.losses = torch.zeros((self.n, 3), dtype=torch.float32, device=self.device) if self.train else None
+        self.depth_weight = (1.0 if depth_weight is None else float(depth_weight)) if self.train_depth else 0.0
+        # per-view dL/ddepth or depth targets; without either but with `depths`: NULL entries (the colour-only backward)
+        self._dgrads = ptr_array(grad_depths if grad_depths is not None else depth_targets) \
+            if (grad_depths is not None or self.train_depth) else None
+        if self._dgrads is None and depths is not None:
+            self._dgrads = (ctypes.c_void_p * self.n)()
+        self.depths = list(depths) if depths is not None else None
+        self._depths = (ctypes.c_void_p * self.n)(*[t.data_ptr() for t in self.depths]) if depths is not None else None
+        self.losses = torch.zeros((self.n, 4 if self.train_depth else 3), dtype=torch.float32, device=self.device) \
+            if self.train else None
         self._tanx = (ctypes.c_float * self.n)(*[math.tan(c.FoVx * 0.5) for c in self.cams])
         self._tany = (ctypes.c_float * self.n)(*[math.tan(c.FoVy * 0.5) for c in self.cams])
         self._keep = keep
         self._ws = None
         self._ws_key = None
+
+    def _check_depth_args(self, grad_colors, targets, grad_depths, depth_targets, depth_weight, depths):
+        import math
+        if grad_depths is not None and grad_colors is None:
+            raise ValueError("grad_depths goes with grad_colors (fixed upstream gradients); with targets give depth_targets")
+        if depth_targets is not None and targets is None:
+            raise ValueError("depth_targets goes with targets (the fused training step); with grad_colors give grad_depths")
+        if depth_weight is not None:
+            if depth_targets is None:
+                raise ValueError("depth_weight needs depth_targets")
+            w = float(depth_weight)
+            if not (math.isfinite(w) and w >= 0.0):
+                raise ValueError(f"depth_weight must be finite and >= 0, got {depth_weight}")
+        if depths is not None and targets is not None and depth_targets is None:
+            raise ValueError("depths= with targets needs depth_targets (the colour-only training step returns no depth)")
+        shape_ok = lambda t: isinstance(t, torch.Tensor) and tuple(t.shape) in ((self.H, self.W), (1, self.H, self.W))
+        for name, seq in (("grad_depths", grad_depths), ("depth_targets", depth_targets), ("depths", depths)):
+            if seq is None:
+                continue
+            seq = list(seq)
+            if len(seq) != self.n:
+                raise ValueError(f"{name}: {len(seq)} entries for {self.n} views")
+            for t in seq:
+                if not shape_ok(t):
+                    raise ValueError(f"{name}: every entry must be a [1,H,W] or [H,W] tensor with H,W = {self.H},{self.W}, "
+                                     f"got {tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__}")
+                if name == "depths" and not (t.is_cuda and t.dtype is torch.float32 and t.is_contiguous()):
+                    raise ValueError("depths: outputs must be contiguous float32 tensors on the HIP device")
 
     def run(self, means3D, opacities, scales, rotations, shs, acc: dict):
         """acc: {"means3D", "means2D", "opacity", "sh", "scales", "rotations"} -> contiguous float32 tensors that are
@@ -861,6 +959,8 @@ class ViewBatch:
         key = (P, self.capacity, self.n_streams)      # the workspace is sized per stream slot: set_streams() re-allocates
         if self._ws_key != key:
             size_fn = self.L.lr_views_train_workspace_bytes if self.train else self.L.lr_views_workspace_bytes
+            if self.train_depth:
+                size_fn = self.L.lr_views_train_depth_workspace_bytes
             nbytes = size_fn(P, self.W, self.H, self.capacity, self.n_streams)
             self._ws = torch.empty((nbytes,), dtype=torch.uint8, device=self.device)
             self._ws_key = key
@@ -872,6 +972,18 @@ class ViewBatch:
 
     def _run(self, P, M, means3D, opacities, scales, rotations, shs, acc):
         stream = torch.cuda.current_stream(self.device).cuda_stream
+        if self.train_depth:
+            rc = self.L.lr_views_train_depth_accumulate(
+                self.n, self._views, self._projs, self._campos, self._tanx, self._tany, P, self.degree, M,
+                self.bg.data_ptr(), self.W, self.H, means3D.data_ptr(), shs.data_ptr(), opacities.data_ptr(),
+                scales.data_ptr(), self.scale_modifier, rotations.data_ptr(), self._grads, self.lambda_dssim,
+                self._dgrads, self.depth_weight, self.losses.data_ptr(), None, self._depths, None,
+                acc["means2D"].data_ptr(), acc["opacity"].data_ptr(), acc["means3D"].data_ptr(), acc["sh"].data_ptr(),
+                acc["scales"].data_ptr(), acc["rotations"].data_ptr(),
+                self._ws.data_ptr(), self._ws.numel(), self.capacity, self.n_streams, stream)
+            if rc < 0:
+                self._lib.raise_for(rc, "lr_views_train_depth_accumulate")
+            return
         if self.train:
             rc = self.L.lr_views_train_accumulate(
                 self.n, self._views, self._projs, self._campos, self._tanx, self._tany, P, self.degree, M,
@@ -882,6 +994,17 @@ class ViewBatch:
                 self._ws.data_ptr(), self._ws.numel(), self.capacity, self.n_streams, stream)
             if rc < 0:
                 self._lib.raise_for(rc, "lr_views_train_accumulate")
+            return
+        if self._dgrads is not None:
+            rc = self.L.lr_views_accumulate_depth(
+                self.n, self._views, self._projs, self._campos, self._tanx, self._tany, P, self.degree, M,
+                self.bg.data_ptr(), self.W, self.H, means3D.data_ptr(), shs.data_ptr(), None, opacities.data_ptr(),
+                scales.data_ptr(), self.scale_modifier, rotations.data_ptr(), None, self._grads, self._dgrads, None,
+                self._depths, None, acc["means2D"].data_ptr(), acc["opacity"].data_ptr(), None, acc["means3D"].data_ptr(),
+                None, acc["sh"].data_ptr(), acc["scales"].data_ptr(), acc["rotations"].data_ptr(),
+                self._ws.data_ptr(), self._ws.numel(), self.capacity, self.n_streams, stream)
+            if rc < 0:
+                self._lib.raise_for(rc, "lr_views_accumulate_depth")
             return
         rc = self.L.lr_views_accumulate(
             self.n, self._views, self._projs, self._campos, self._tanx, self._tany, P, self.degree, M,
@@ -899,6 +1022,8 @@ class ViewBatch:
             return
         P = self._ws_key[0]
         check = self.L.lr_views_train_check if self.train else self.L.lr_views_check
+        if self.train_depth:
+            check = self.L.lr_views_train_depth_check
         with torch.cuda.device(self.device):
             rc = check(self._ws.data_ptr(), P, self.W, self.H, self.capacity, self.n_streams,
                        torch.cuda.current_stream(self.device).cuda_stream)

@@ -152,12 +152,14 @@ def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales,
         # the caller already holds dL/dcolor (parallel.ViewStreams.run_view): forward and backward in ONE call of the binding,
         # gradients added into the leaves' .grad by the kernels, no autograd node (csrc/torch_ext.cpp rasterize_view_step).
         # An input that is not a leaf with a suitable .grad -> empty result -> the autograd path below, offer untouched.
+        # An offered dL/ddepth selects the depth-mode backward (fed with this forward's own depth image).
         out = _C.rasterize_view_step(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, rs.bg,
                                      rs.viewmatrix, rs.projmatrix, rs.campos, rs.scale_modifier, rs.tanfovx, rs.tanfovy,
-                                     rs.image_height, rs.image_width, rs.sh_degree, rs.prefiltered, capacity, offered)
+                                     rs.image_height, rs.image_width, rs.sh_degree, rs.prefiltered, capacity, offered,
+                                     config.offered_grad_depth())
         if out:
             color, radii, depth, geom = out
-            config.mark_grad_output_taken()
+            config.mark_grad_output_taken((color, depth))
             config.note_forward(means3D, rs, _C.last_num_rendered(), geom, capacity)
             return color, radii, depth
 
