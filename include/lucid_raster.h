@@ -524,6 +524,37 @@ int lr_depth_l1_forward(int height, int width, const float* depth, const float* 
 int lr_depth_l1_backward(int height, int width, const float* depth, const float* target, float weight, const float* upstream,
                          float* dL_ddepth, void* stream);
 
+/*
+ * Video frames on the device (the per-frame post-processing of the video renderer, R/luciddreamer.py:250-265).  Every entry
+ * point takes n_frames contiguous frames of one H, W and handles them in the same launches; nothing reads back to the host.
+ *
+ *   lr_frames_to_u8 : images [n,3,H,W] float32 -> out [n,H,W,3] uint8,
+ *                     out = uint8(rint(min(max(x, 0), 1) * 255))   (float32, round half to even, no fma; NaN -> 0)
+ *                     = np.round(image.permute(1,2,0).numpy().clip(0,1) * 255.).astype(np.uint8) byte for byte.
+ *   lr_depth_colorize : depths [n,H,W] float32 -> out_rgba [n,H,W,4] uint8, R/utils/depth.py:colorize with its defaults:
+ *       v = from_render ? -(d * (d > 0)) : d;  valid = (v != invalid_val);  n = number of valid pixels
+ *       vmin, vmax = np.percentile(v[valid], q_lo), np.percentile(v[valid], q_hi) in float32, "linear" method, bit for bit
+ *                    (a NaN among the valid values gives NaN), found by a 3-pass radix select on the device (no sort);
+ *                    or read from fixed_vmin_vmax (device float[2 * n]: vmin, vmax per frame; NULL = select) -- colorize(vmin=,
+ *                    vmax=) with both limits given, taken as float32
+ *       t = vmin != vmax ? (v - vmin) / (vmax - vmin) : v * 0;  x = t * lut_n, x == lut_n -> lut_n - 1
+ *       colour = lut[trunc(x)], or row lut_n (under) for x < 0, lut_n + 1 (over) for x >= lut_n, lut_n + 2 (bad) for NaN;
+ *       invalid pixels get background[0..3].
+ *     lut: device uint8 [(lut_n + 3), 4], a matplotlib colormap's _lut with bytes=True (1 <= lut_n <= LR_VIDEO_MAX_LUT_N).
+ *     background: HOST pointer to 4 bytes (RGBA).  out_vmin_vmax: device float[2 * n] (required): the limits used per frame.
+ *     With n == 0 valid pixels (the reference raises IndexError) the frame is all background and vmin = vmax = NaN.
+ *     workspace: lr_video_workspace_bytes(n_frames, H, W) device bytes (unused, and may be NULL, with fixed_vmin_vmax).
+ *     The histograms merge with integer atomics only: the output is deterministic.
+ * Images of at most 2^31 - 2^12 pixels, 1 <= n_frames <= 65535.  Return 0 or a negative LR_ERR_*.
+ */
+#define LR_VIDEO_MAX_LUT_N 4096
+size_t lr_video_workspace_bytes(int n_frames, int height, int width);
+int lr_frames_to_u8(int n_frames, int height, int width, const float* images, unsigned char* out, void* stream);
+int lr_depth_colorize(int n_frames, int height, int width, const float* depths, int from_render, float invalid_val,
+                      float q_lo, float q_hi, const float* fixed_vmin_vmax, const unsigned char* lut, int lut_n,
+                      const unsigned char* background, unsigned char* out_rgba, float* out_vmin_vmax, void* workspace,
+                      size_t workspace_bytes, void* stream);
+
 /* present[P] (1 byte each) = view-space z > 0.2.  Returns 0 or a negative LR_ERR_*. */
 int lr_mark_visible(int P, const float* means3D, const float* viewmatrix, const float* projmatrix,
                     unsigned char* present, void* stream);

@@ -35,7 +35,8 @@ EXPORTS = ("lr_last_error", "lr_version", "lr_geom_bytes", "lr_img_bytes", "lr_b
            "lr_select_workspace_bytes", "lr_select_rows", "lr_pack_ply_rows", "lr_adam_step", "lr_adam_step_masked", "lr_densify_stats",
            "lr_views_train_workspace_bytes", "lr_views_train_accumulate", "lr_views_train_check",
            "lr_views_accumulate_depth", "lr_views_train_depth_workspace_bytes", "lr_views_train_depth_accumulate",
-           "lr_views_train_depth_check", "lr_depth_l1_workspace_bytes", "lr_depth_l1_forward", "lr_depth_l1_backward")
+           "lr_views_train_depth_check", "lr_depth_l1_workspace_bytes", "lr_depth_l1_forward", "lr_depth_l1_backward",
+           "lr_video_workspace_bytes", "lr_frames_to_u8", "lr_depth_colorize")
 
 
 def assert_single_copy():
@@ -160,6 +161,15 @@ def lib():
         L.lr_depth_l1_forward.argtypes = [ci, ci, vp, vp, cf, vp, vp, ctypes.c_size_t, vp]
         L.lr_depth_l1_backward.restype = ci
         L.lr_depth_l1_backward.argtypes = [ci, ci, vp, vp, cf, vp, vp, vp]
+        L.lr_video_workspace_bytes.restype = ctypes.c_size_t
+        L.lr_video_workspace_bytes.argtypes = [ci, ci, ci]
+        L.lr_frames_to_u8.restype = ci
+        L.lr_frames_to_u8.argtypes = [ci, ci, ci, vp, vp, vp]
+        L.lr_depth_colorize.restype = ci
+        L.lr_depth_colorize.argtypes = [ci, ci, ci, vp, ci, cf,                  # n H W depths from_render invalid_val
+                                        cf, cf, vp, vp, ci,                      # q_lo q_hi fixed_vmin_vmax lut lut_n
+                                        ctypes.c_char_p, vp, vp,                 # background (host, 4 bytes) out_rgba out_vmin_vmax
+                                        vp, ctypes.c_size_t, vp]                 # workspace bytes stream
         L.lr_loss_workspace_bytes.restype = ctypes.c_size_t
         L.lr_loss_workspace_bytes.argtypes = [ci, ci, ci]
         L.lr_l1_dssim_forward.restype = ci

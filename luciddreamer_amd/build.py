@@ -34,6 +34,8 @@ SOURCES = {
     "loss.hip": ["-fno-slp-vectorize"],
     "rows.hip": [],
     "adam.hip": [],
+    # video frames: bit-exact to numpy's float32 operations (np.round, np.percentile, colorize's normalisation): no FMA contraction
+    "video.hip": ["-ffp-contract=off"],
     "api.hip": [],
 }
 

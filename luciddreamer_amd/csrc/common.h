@@ -513,6 +513,13 @@ enum { ACC_MEAN2D = 0, ACC_CONIC = 1, ACC_OPACITY = 2, ACC_COLOR = 3, ACC_MEAN3D
        ACC_SCALE = 7, ACC_ROT = 8 };
 void launch_zero_outputs(float* const* ptrs, const unsigned long long* nfloats, int count, hipStream_t s);
 
+// video frames on the device (video.hip)
+size_t video_workspace_bytes(int n_frames);
+void launch_frames_u8(int n, int HW, const float* images, uint8_t* out, hipStream_t s);
+hipError_t launch_depth_colorize(int n, int HW, const float* depths, bool from_render, float invalid_val, float q_lo,
+                                 float q_hi, const float* fixed_vmm, const uint32_t* lut, int lut_n, uint32_t background,
+                                 uint32_t* out, float* out_vmm, void* workspace, hipStream_t s);
+
 void launch_dist2(int P, const float* points, float* out, char* workspace, hipStream_t s);
 size_t dist2_workspace_bytes(int P);
 
