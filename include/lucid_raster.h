@@ -336,6 +336,96 @@ int lr_backward_raw_depth(int P, int D, int M, int R,
                           void* stream);
 
 /*
+ * Alpha output: the accumulated opacity alpha = 1 - T_final [1,H,W] of a forward, from its image buffer (the float32 T_final
+ * the blend forward left there), written to out_alpha on `stream`.  0 where no Gaussian contributes.  Valid for lr_forward and
+ * lr_forward_raw, exact and async mode: pass the image buffer of the forward whose colour you keep (after an overflow
+ * re-render, the re-render's).  The forward's kernels are not changed by it.
+ */
+int lr_render_alpha(const char* image_buffer, int width, int height, float* out_alpha, void* stream);
+
+/*
+ * Alpha mode: lr_backward_depth / lr_backward_raw_depth with a gradient through the alpha output as well.  Each takes its
+ * depth counterpart's arguments plus dL_dalpha [1,H,W] right after depth_image; the depth pair is optional (NULL, NULL: alpha
+ * alone).  With dL_dalpha == NULL each is exactly its depth counterpart (same kernels, same bits).
+ * The derivative is that of 1 - prod_i (1 - alpha_i) over the layers the forward applied, with the colour path's conventions
+ * (the 0.99 clamp of alpha not differentiated; the alpha < 1/255 and power > 0 skips, the T < 1e-4 stop -- whose trigger is not
+ * applied -- and the sort order are constants; the fov clamp as there): d alpha_pix / d alpha_i = T_final / (1 - alpha_i).  It
+ * reaches dL_dopacity, dL_dmean2D (which feeds densification), dL_dconic and through them means3D / xyz, scales, rotations and
+ * cov3D; colours and SH get nothing from it.  Alone it runs the default backward's blend shape and list segments; with the depth
+ * pair it joins the depth-mode kernel.  No global float atomics: bit-repeatable.  Errors and the return value are those of the
+ * depth counterpart.
+ */
+int lr_backward_alpha(int P, int D, int M, int R,
+                      const float* background,
+                      int width, int height,
+                      const float* means3D,
+                      const float* shs,
+                      const float* colors_precomp,
+                      const float* scales,
+                      float scale_modifier,
+                      const float* rotations,
+                      const float* cov3D_precomp,
+                      const float* viewmatrix,
+                      const float* projmatrix,
+                      const float* campos,
+                      float tan_fovx, float tan_fovy,
+                      const int* radii,
+                      char* geom_buffer,
+                      char* binning_buffer,
+                      char* image_buffer,
+                      const float* dL_dpix,
+                      const float* dL_depths,
+                      const float* depth_image,
+                      const float* dL_dalpha,
+                      float* dL_dmean2D,
+                      float* dL_dconic,
+                      float* dL_dopacity,
+                      float* dL_dcolor,
+                      float* dL_dmean3D,
+                      float* dL_dcov3D,
+                      float* dL_dsh,
+                      float* dL_dscale,
+                      float* dL_drot,
+                      int debug,
+                      long long binning_capacity,
+                      unsigned int accumulate_mask,
+                      void* stream);
+
+int lr_backward_raw_alpha(int P, int D, int M, int R,
+                          const float* background,
+                          int width, int height,
+                          const float* xyz,
+                          const float* features_dc,
+                          const float* features_rest,
+                          const float* opacity_raw,
+                          const float* scaling_raw,
+                          float scale_modifier,
+                          const float* rotation_raw,
+                          const float* viewmatrix,
+                          const float* projmatrix,
+                          const float* campos,
+                          float tan_fovx, float tan_fovy,
+                          const int* radii,
+                          char* geom_buffer,
+                          char* binning_buffer,
+                          char* image_buffer,
+                          const float* dL_dpix,
+                          const float* dL_depths,
+                          const float* depth_image,
+                          const float* dL_dalpha,
+                          float* dL_dmean2D,
+                          float* dL_dopacity_raw,
+                          float* dL_dxyz,
+                          float* dL_dfeatures_dc,
+                          float* dL_dfeatures_rest,
+                          float* dL_dscaling_raw,
+                          float* dL_drotation_raw,
+                          int debug,
+                          long long binning_capacity,
+                          unsigned int accumulate_mask,
+                          void* stream);
+
+/*
  * Multi-view step (new; the reference renders one view per Python iteration, luciddreamer.py:291-304).
  * Runs lr_forward + lr_backward for n_views views of ONE parameter set and ACCUMULATES the gradients into the
  * acc_* buffers (same shapes as lr_backward's outputs; acc_color / acc_cov3D / acc_sh / acc_scale / acc_rot may be

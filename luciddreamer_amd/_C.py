@@ -12,6 +12,7 @@ There is no fallback: a missing extension raises on import.
 
 Beyond the reference's contract (all optional, keyword-only):
     binning_capacity : > 0 runs lr_forward in async mode (no host sync; see lucid_raster.h)
+    dL_dout_alpha    : the gradient of the alpha output (render_alpha), on both backward entry points
 """
 try:
     from . import _C_ext
@@ -44,7 +45,8 @@ def rasterize_gaussians(background, means3D, colors, opacity, scales, rotations,
 def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rotations, scale_modifier,
                                  cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color,
                                  dL_dout_depth, sh, degree, campos, geomBuffer, R, binningBuffer, imageBuffer,
-                                 debug, *, binning_capacity=0, accumulate_into=None, skip_unused=False, depth_image=None):
+                                 debug, *, binning_capacity=0, accumulate_into=None, skip_unused=False, depth_image=None,
+                                 dL_dout_alpha=None):
     """accumulate_into (optional): {name: tensor} with names among ACC_BITS; the gradient of that input is
     ADDED in place into the given contiguous float32 tensor (rows of culled Gaussians untouched) and the
     corresponding slot of the returned tuple is None.
@@ -52,12 +54,14 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
     dL_dscales / dL_drotations for the representation not in use); their slots are None.  The reference always
     returns all eight tensors, so the default keeps that.
     depth_image (optional): the forward's depth output -- depth mode (lr_backward_depth): dL_dout_depth is honoured.  Without
-    it dL_dout_depth is ignored, as in the reference."""
+    it dL_dout_depth is ignored, as in the reference.
+    dL_dout_alpha (optional, (1, H, W)): the gradient of the alpha output (render_alpha) as well -- lr_backward_alpha, alone or
+    together with depth mode."""
     acc = _NONE8 if not accumulate_into else [accumulate_into.get(k) for k in GRAD_ORDER]
     return tuple(_C_ext.rasterize_gaussians_backward(
         background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix, projmatrix,
         tan_fovx, tan_fovy, dL_dout_color, dL_dout_depth, sh, degree, campos, geomBuffer, R, binningBuffer, imageBuffer,
-        debug, binning_capacity, acc, skip_unused, depth_image=depth_image))
+        debug, binning_capacity, acc, skip_unused, depth_image=depth_image, dL_dout_alpha=dL_dout_alpha))
 
 
 def rasterize_gaussians_raw(background, xyz, features_dc, features_rest, opacity_raw, scaling_raw, rotation_raw,
@@ -77,11 +81,12 @@ def rasterize_gaussians_raw_backward(background, xyz, radii, features_dc, featur
                                      rotation_raw, scale_modifier, viewmatrix, projmatrix, tan_fovx, tan_fovy,
                                      dL_dout_color, degree, campos, geomBuffer, R, binningBuffer, imageBuffer, debug, *,
                                      binning_capacity=0, accumulate_into=None, no_zero_fill=False, dL_dout_depth=None,
-                                     depth_image=None):
+                                     depth_image=None, dL_dout_alpha=None):
     """Gradients w.r.t. the stored tensors: (means2D, xyz, features_dc, features_rest, opacity, scaling, rotation).
     accumulate_into: {"means2D","xyz","opacity","scaling","rotation": tensor, "features": (dc_grad, rest_grad)} adds
     in place (slot returned as None).
-    dL_dout_depth + depth_image (the forward's depth output): depth mode (lr_backward_raw_depth)."""
+    dL_dout_depth + depth_image (the forward's depth output): depth mode (lr_backward_raw_depth).
+    dL_dout_alpha: the gradient of the alpha output as well (lr_backward_raw_alpha)."""
     acc = _NONE8
     if accumulate_into:
         f = accumulate_into.get("features") or (None, None)
@@ -90,7 +95,8 @@ def rasterize_gaussians_raw_backward(background, xyz, radii, features_dc, featur
     return tuple(_C_ext.rasterize_gaussians_raw_backward(
         background, xyz, radii, features_dc, features_rest, opacity_raw, scaling_raw, rotation_raw, scale_modifier, viewmatrix,
         projmatrix, tan_fovx, tan_fovy, dL_dout_color, degree, campos, geomBuffer, R, binningBuffer, imageBuffer, debug,
-        binning_capacity, acc, bool(no_zero_fill), dL_dout_depth=dL_dout_depth, depth_image=depth_image))
+        binning_capacity, acc, bool(no_zero_fill), dL_dout_depth=dL_dout_depth, depth_image=depth_image,
+        dL_dout_alpha=dL_dout_alpha))
 
 
 # one Adam step whose gradients are valid only in the rows of the Gaussians one view visited (lr_adam_step_masked)
@@ -100,6 +106,9 @@ check = _C_ext.check
 # the operator with its autograd node compiled (csrc/torch_ext.cpp RasterizeFn); returns (color, radii, depth, geom), the
 # call's num_rendered is read with last_num_rendered()
 rasterize_autograd = _C_ext.rasterize_autograd
+# the alpha output 1 - T_final (1, H, W) of a forward, from its image buffer (lr_render_alpha); no autograd.  (With alpha=True
+# rasterize_autograd returns it as a fifth, differentiable output.)
+render_alpha = _C_ext.render_alpha
 # forward + backward of one view in one call for a caller that holds dL/dcolor up front; [] = an input does not qualify
 rasterize_view_step = _C_ext.rasterize_view_step
 last_num_rendered = _C_ext.last_num_rendered

@@ -27,7 +27,8 @@ _lib = None
 _lock = threading.Lock()
 
 EXPORTS = ("lr_last_error", "lr_version", "lr_geom_bytes", "lr_img_bytes", "lr_binning_bytes", "lr_forward",
-           "lr_backward", "lr_forward_raw", "lr_backward_raw", "lr_backward_depth", "lr_backward_raw_depth", "lr_mark_visible", "lr_check", "lr_dist2_workspace_bytes", "lr_dist2",
+           "lr_backward", "lr_forward_raw", "lr_backward_raw", "lr_backward_depth", "lr_backward_raw_depth",
+           "lr_backward_alpha", "lr_backward_raw_alpha", "lr_render_alpha", "lr_mark_visible", "lr_check", "lr_dist2_workspace_bytes", "lr_dist2",
            "lr_profile_enable", "lr_profile_stage_name", "lr_profile_read", "lr_tune_set", "lr_last_launch_shapes", "lr_request_early_header",
            "lr_take_early_ticket", "lr_forward_ticket", "lr_backward_wait_event", "lr_step_begin", "lr_step_end", "lr_step_abort",
            "lr_views_workspace_bytes", "lr_views_accumulate", "lr_views_check",
@@ -106,6 +107,8 @@ def lib():
                                       vp, vp, vp, vp,                            # geom binning img dL_dpix
                                       vp, vp, vp, vp, vp, vp, vp,                # 7 gradient outputs
                                       ci, ll, ctypes.c_uint, vp]                 # debug capacity accumulate_mask stream
+        L.lr_render_alpha.restype = ci
+        L.lr_render_alpha.argtypes = [vp, ci, ci, vp, vp]                        # image_buffer W H out_alpha stream
         L.lr_mark_visible.restype = ci
         L.lr_mark_visible.argtypes = [ci, vp, vp, vp, vp, vp]
         L.lr_check.restype = ci

@@ -437,14 +437,18 @@ void launch_render_fwd(int W, int H, int gx, int gy, const uint2* ranges, const 
                        uint32_t* n_contrib, float* out_color, float* out_depth, uint8_t* quad_hits,
                        GeomHeader* hdr, uint2* seg_list, float4* ckpt, uint32_t* tile_seg0, float4* c_final,
                        long long inst_hint, hipStream_t s);
+// alpha [n] = 1 - final_T [n]: the accumulated opacity of the forward that left final_T (lr_render_alpha)
+void launch_render_alpha(const float* final_T, long long n, float* alpha, hipStream_t s);
 // seg_bound: upper bound of GeomHeader::n_seg known to the host (bin_seg_capacity of the instance bound of the call)
 // dL_ddepth != nullptr: depth mode (lr_backward_depth) -- the depth-mode kernels differentiate the forward's depth image
 // depth_img [H*W] for the upstream gradient dL_ddepth [H*W] as well, and write dL/dz of every instance to its slot's free float
+// dL_dalpha != nullptr: alpha mode (lr_backward_alpha) -- the gradient of the accumulated opacity 1 - final_T [H*W] as well;
+// alone it keeps the default shape and segments, with depth mode it joins the depth-mode kernel
 void launch_render_bwd(int W, int H, int gx, int gy, const uint2* ranges, const uint32_t* point_list,
                        const GaussRec* rec, const float* bg, const float* final_T,
                        const uint32_t* n_contrib, const float* dL_dpix, char* bin_base, const GeomHeader* hdr,
                        const uint32_t* tile_seg0, const float4* c_final, long long seg_bound, hipStream_t s,
-                       const float* dL_ddepth = nullptr, const float* depth_img = nullptr);
+                       const float* dL_ddepth = nullptr, const float* depth_img = nullptr, const float* dL_dalpha = nullptr);
 // ---- Adam, element-wise (adam.hip and the step fused into the per-Gaussian backward, gauss_bwd.hip) -----------------------
 // torch's single-tensor Adam (torch/optim/adam.py _single_tensor_adam; no weight decay, amsgrad or maximize) with the roundings
 // of torch's own kernels: lerp = fma(w, b - a, a), addcmul = fma(value * t1, t2, self), addcdiv = fma(value, t1 / t2, self);

@@ -3,7 +3,8 @@
 // Replaces BACKWARD::render / renderCUDA (RAST/cuda_rasterizer/backward.cu:399-586).  The
 // per-pixel recursion is the reference's (back-to-front, T un-blended by division, colour
 // recursion through accum_rec, background term, 0.99 clamp not differentiated, depth gradient
-// ignored -- except in the depth-mode kernels k_render_bwd_depth below, lr_backward_depth).  The kernel is VALU-issue bound; the design removes wave-instructions:
+// ignored -- except in the depth-mode kernels k_render_bwd_depth below, lr_backward_depth; the alpha-mode kernels
+// k_render_bwd*_alpha, lr_backward_alpha, add the gradient of the accumulated opacity).  The kernel is VALU-issue bound; the design removes wave-instructions:
 //
 //   * same two-level loop as the forward: per 64 staged Gaussians one lane each looks up the outcome of the forward's
 //     exact quadrant test (box_hit, kept per list position in the binning buffer) -> 64-bit candidate mask; only
@@ -248,14 +249,21 @@ __device__ __forceinline__ void bwd_pixel(BwdPix& p, const float qA, const float
 // Gaussian has z > 0.2 (in_frustum), so a pixel with acc > 0.5 has a nonzero depth, exactly the forward's decision.
 // (Not the reference's commented-out depth terms, backward.cu:457-464, 539-554: they differentiate p_proj.z / p_proj.w and
 // the un-normalised D, which is not the quantity the forward outputs.)
-template <bool QUAD, bool MERGE, bool STRICT, bool DEPTH = false>
+// ALPHA (k_render_bwd_alpha, k_render_bwd_tile_alpha, k_render_bwd_depth_alpha; lr_backward_alpha): the derivative of the
+// accumulated opacity 1 - T_final for g = dL_dalpha.  Coverage is a colour channel with value 1 and background 0, the same as
+// a channel with value 0 and background 1 taken with weight -g; with value 0 it adds nothing to any layer's difference d, so
+// the whole of it is the start value of A: bg.dL - g at the list's end (and for a pixel that stopped before the segment),
+// and at a segment start where the pixel is still blending the background share seen from there, -g T_final / T_ck -- both
+// numbers the segment already has.  No instruction per layer; the segments and every shape of the default backward stay.
+template <bool QUAD, bool MERGE, bool STRICT, bool DEPTH = false, bool ALPHA = false>
 __device__ __forceinline__ void render_bwd_item(const int tile, const int seg, const uint32_t ck_slot,
              const float4* __restrict__ c_final, int W, int H, int gx, const uint2* __restrict__ ranges,
              const uint32_t* __restrict__ point_list, const GaussRec* __restrict__ rec,
              const float* __restrict__ bg, const float* __restrict__ final_Ts,
              const uint32_t* __restrict__ n_contrib, const float* __restrict__ dL_dpix,
              char* __restrict__ bin_base, const GeomHeader* __restrict__ hdr, int force_check,
-             const float* __restrict__ dL_ddepth = nullptr, const float* __restrict__ depth_img = nullptr)
+             const float* __restrict__ dL_ddepth = nullptr, const float* __restrict__ depth_img = nullptr,
+             const float* __restrict__ dL_dalpha = nullptr)
 {
     static_assert(!DEPTH || MERGE, "depth mode uses the merged reduction");
     constexpr int BATCH = QUAD ? LR_QBATCH_BWD : BATCH2;
@@ -320,6 +328,13 @@ __device__ __forceinline__ void render_bwd_item(const int tile, const int seg, c
         depth_pixel(PA, insA, pixA);
         depth_pixel(PB, insB, pixB);
     }
+    float gaA = 0.f, gaB = 0.f;                                     // ALPHA: dL/dalpha of the two pixels
+    if constexpr (ALPHA) {
+        gaA = insA ? dL_dalpha[pixA] : 0.f;
+        gaB = insB ? dL_dalpha[pixB] : 0.f;
+        PA.A -= gaA;                                                // the coverage channel's background term (see above)
+        PB.A -= gaB;
+    }
     if (seg_hi < total) {
         // The recursion starts in the middle of the list.  A pixel the forward was still blending at position seg_hi
         // (last > seg_hi: it stopped later, or never) takes the forward's own T there and the colour still to come behind it --
@@ -328,13 +343,19 @@ __device__ __forceinline__ void render_bwd_item(const int tile, const int seg, c
         const int qA = QUAD ? w : 2 * w;                         // quadrant of pixel A (pixel index of the checkpoint: quadrant * 64 + lane)
         if (PA.last > (uint32_t)seg_hi) {
             const float4 c = ck[qA * 64 + l], f = c_final[pixA];       // {T, colour so far} there; the pixel's final colour
+            if constexpr (ALPHA)                                        // PA.T is still the final T here
+                PA.A = ((f.x - c.y) * PA.dLr + (f.y - c.z) * PA.dLg + (f.z - c.w) * PA.dLb - gaA * PA.T) * __builtin_amdgcn_rcpf(c.x);
             PA.T = c.x;
-            PA.A = ((f.x - c.y) * PA.dLr + (f.y - c.z) * PA.dLg + (f.z - c.w) * PA.dLb) * __builtin_amdgcn_rcpf(c.x);
+            if constexpr (!ALPHA)
+                PA.A = ((f.x - c.y) * PA.dLr + (f.y - c.z) * PA.dLg + (f.z - c.w) * PA.dLb) * __builtin_amdgcn_rcpf(c.x);
         }
         if (!QUAD && PB.last > (uint32_t)seg_hi) {
             const float4 c = ck[(qA + 1) * 64 + l], f = c_final[pixB];
+            if constexpr (ALPHA)
+                PB.A = ((f.x - c.y) * PB.dLr + (f.y - c.z) * PB.dLg + (f.z - c.w) * PB.dLb - gaB * PB.T) * __builtin_amdgcn_rcpf(c.x);
             PB.T = c.x;
-            PB.A = ((f.x - c.y) * PB.dLr + (f.y - c.z) * PB.dLg + (f.z - c.w) * PB.dLb) * __builtin_amdgcn_rcpf(c.x);
+            if constexpr (!ALPHA)
+                PB.A = ((f.x - c.y) * PB.dLr + (f.y - c.z) * PB.dLg + (f.z - c.w) * PB.dLb) * __builtin_amdgcn_rcpf(c.x);
         }
     }
     const uint32_t lastL = wave_max_u32(PA.last), lastR = QUAD ? 0u : wave_max_u32(PB.last);   // per quadrant
@@ -502,13 +523,15 @@ __device__ __forceinline__ void render_bwd_item(const int tile, const int seg, c
 // test (2.33 of 4 at C3).  The two rows of quadrants have their own dy, so the lane keeps the moments of the upper and the
 // lower pixel pair apart (D, D dx, D dx^2 each) and applies the dy factors to each pair before the reduction.  Single-wave
 // workgroups: 8160 of them at 1080p, no partner wave to wait for at the batch barriers.
-template <int BATCH, bool STRICT, bool LDSRED = false>
+// ALPHA: as render_bwd_item (the start values of A only).
+template <int BATCH, bool STRICT, bool LDSRED = false, bool ALPHA = false>
 __device__ __forceinline__ void render_bwd_tile(const int tile, const int seg, const uint32_t ck_slot,
                   const float4* __restrict__ c_final, int W, int H, int gx, const uint2* __restrict__ ranges,
                   const uint32_t* __restrict__ point_list, const GaussRec* __restrict__ rec,
                   const float* __restrict__ bg, const float* __restrict__ final_Ts,
                   const uint32_t* __restrict__ n_contrib, const float* __restrict__ dL_dpix,
-                  char* __restrict__ bin_base, const GeomHeader* __restrict__ hdr, int force_check)
+                  char* __restrict__ bin_base, const GeomHeader* __restrict__ hdr, int force_check,
+                  const float* __restrict__ dL_dalpha = nullptr)
 {
     __shared__ float4 s_q0[BATCH];      // as k_render_bwd
     __shared__ float4 s_q1[BATCH];
@@ -549,10 +572,18 @@ __device__ __forceinline__ void render_bwd_tile(const int tile, const int seg, c
         p.dLg = ins ? dL_dpix[N + pix] : 0.f;
         p.dLb = ins ? dL_dpix[2 * N + pix] : 0.f;
         p.A = bg0 * p.dLr + bg1 * p.dLg + bg2 * p.dLb;
+        float ga = 0.f;
+        if constexpr (ALPHA) {
+            ga = ins ? dL_dalpha[pix] : 0.f;
+            p.A -= ga;
+        }
         if (seg_hi < total && p.last > (uint32_t)seg_hi) {          // as render_bwd_item: the forward's state at the segment's deep end
             const float4 c = ck[q * 64 + l], f = c_final[pix];
+            if constexpr (ALPHA)
+                p.A = ((f.x - c.y) * p.dLr + (f.y - c.z) * p.dLg + (f.z - c.w) * p.dLb - ga * p.T) * __builtin_amdgcn_rcpf(c.x);
             p.T = c.x;
-            p.A = ((f.x - c.y) * p.dLr + (f.y - c.z) * p.dLg + (f.z - c.w) * p.dLb) * __builtin_amdgcn_rcpf(c.x);
+            if constexpr (!ALPHA)
+                p.A = ((f.x - c.y) * p.dLr + (f.y - c.z) * p.dLg + (f.z - c.w) * p.dLb) * __builtin_amdgcn_rcpf(c.x);
         }
     };
     load_pixel(P0, pxL, pyT, 0); load_pixel(P1, pxR, pyT, 1); load_pixel(P2, pxL, pyB, 2); load_pixel(P3, pxR, pyB, 3);
@@ -781,6 +812,35 @@ k_render_bwd_depth(LR_BWD_SEG_PARAMS, const float* __restrict__ dL_ddepth, const
     LR_BWD_KERNEL_BODY(LR_ITEM)
 #undef LR_ITEM
 }
+// Alpha mode (lr_backward_alpha: a gradient through the accumulated opacity 1 - T_final): the default kernels with the ALPHA
+// start values of A (render_bwd_item).  Nothing changes per layer, so each keeps the shape, launch bounds and list segments of
+// its default counterpart; own symbols, so that the default kernels keep their names and instruction streams.
+template <bool QUAD, bool STRICT>
+__global__ void __launch_bounds__(QUAD ? 256 : 128) __attribute__((amdgpu_waves_per_eu(QUAD ? 4 : 7, 8)))
+k_render_bwd_alpha(LR_BWD_SEG_PARAMS, const float* __restrict__ dL_dalpha)
+{
+#define LR_ITEM(...) render_bwd_item<QUAD, true, STRICT, false, true>(__VA_ARGS__, nullptr, nullptr, dL_dalpha)
+    LR_BWD_KERNEL_BODY(LR_ITEM)
+#undef LR_ITEM
+}
+template <bool STRICT>
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8), amdgpu_num_vgpr(64)))
+k_render_bwd_tile_alpha(LR_BWD_SEG_PARAMS, const float* __restrict__ dL_dalpha)
+{
+#define LR_ITEM(...) render_bwd_tile<30, STRICT, true, true>(__VA_ARGS__, dL_dalpha)
+    LR_BWD_KERNEL_BODY_ONE(LR_ITEM)
+#undef LR_ITEM
+}
+// depth + alpha: k_render_bwd_depth with the ALPHA start values (whole lists, as depth mode)
+template <bool STRICT>
+__global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(6, 8)))
+k_render_bwd_depth_alpha(LR_BWD_SEG_PARAMS, const float* __restrict__ dL_ddepth, const float* __restrict__ depth_img,
+                         const float* __restrict__ dL_dalpha)
+{
+#define LR_ITEM(...) render_bwd_item<false, true, STRICT, true, true>(__VA_ARGS__, dL_ddepth, depth_img, dL_dalpha)
+    LR_BWD_KERNEL_BODY(LR_ITEM)
+#undef LR_ITEM
+}
 #ifdef LR_DIAGNOSTICS
 // rounds 4-5: the lane-swap reduction (reduce8 + row_merge3), 44 staged Gaussians per round: A/B partner (bwd_red = 2)
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8), amdgpu_num_vgpr(64)))
@@ -882,7 +942,7 @@ void launch_render_bwd(int W, int H, int gx, int gy, const uint2* ranges, const 
                        const GaussRec* rec, const float* bg, const float* final_T,
                        const uint32_t* n_contrib, const float* dL_dpix, char* bin_base, const GeomHeader* hdr,
                        const uint32_t* tile_seg0, const float4* c_final, long long seg_bound, hipStream_t s,
-                       const float* dL_ddepth, const float* depth_img)
+                       const float* dL_ddepth, const float* depth_img, const float* dL_dalpha)
 {
     const int num_tiles = gx * gy;
     if (num_tiles <= 0) return;
@@ -908,6 +968,13 @@ void launch_render_bwd(int W, int H, int gx, int gy, const uint2* ranges, const 
         // depth mode: ONE shape at every image size (the 2-wave one), one workgroup per tile over its whole list -- correct for
         // any launch size, no listed segments (seg_on = 0); the shape rule and the segment switch do not apply
         g_last_bwd_shape = BLEND_HALF;
+        if (dL_dalpha != nullptr) {                 // depth + alpha
+            if (strict) hipLaunchKernelGGL(k_render_bwd_depth_alpha<true>, dim3(grid), dim3(128), 0, s, LR_BWD_ARGS, tile_seg0, c_final,
+                                           grid, 0, dL_ddepth, depth_img, dL_dalpha);
+            else hipLaunchKernelGGL(k_render_bwd_depth_alpha<false>, dim3(grid), dim3(128), 0, s, LR_BWD_ARGS, tile_seg0, c_final,
+                                    grid, 0, dL_ddepth, depth_img, dL_dalpha);
+            return;
+        }
         if (strict) hipLaunchKernelGGL(k_render_bwd_depth<true>, dim3(grid), dim3(128), 0, s, LR_BWD_ARGS, tile_seg0, c_final, grid, 0,
                                        dL_ddepth, depth_img);
         else hipLaunchKernelGGL(k_render_bwd_depth<false>, dim3(grid), dim3(128), 0, s, LR_BWD_ARGS, tile_seg0, c_final, grid, 0,
@@ -928,7 +995,20 @@ void launch_render_bwd(int W, int H, int gx, int gy, const uint2* ranges, const 
     const int extra = seg_on ? (int)(seg_bound < 1 ? 1024 : seg_bound > cap ? cap : seg_bound) : 0;
     const dim3 g(grid + extra);
 #define LR_SEG_ARGS LR_BWD_ARGS, tile_seg0, c_final, grid, seg_on
-    if (shape == BLEND_TILE) {
+    if (dL_dalpha != nullptr) {
+        // alpha mode: the shape and the segment set the default backward takes for this view (the diagnostics-only variants,
+        // bwd_red 0 / 2 / 3, fall back to the default alpha kernel of the shape)
+        if (shape == BLEND_TILE) {
+            if (strict) hipLaunchKernelGGL(k_render_bwd_tile_alpha<true>, g, dim3(64), 0, s, LR_SEG_ARGS, dL_dalpha);
+            else hipLaunchKernelGGL(k_render_bwd_tile_alpha<false>, g, dim3(64), 0, s, LR_SEG_ARGS, dL_dalpha);
+        } else if (shape == BLEND_QUAD) {
+            if (strict) hipLaunchKernelGGL((k_render_bwd_alpha<true, true>), g, dim3(256), 0, s, LR_SEG_ARGS, dL_dalpha);
+            else hipLaunchKernelGGL((k_render_bwd_alpha<true, false>), g, dim3(256), 0, s, LR_SEG_ARGS, dL_dalpha);
+        } else {
+            if (strict) hipLaunchKernelGGL((k_render_bwd_alpha<false, true>), g, dim3(128), pad, s, LR_SEG_ARGS, dL_dalpha);
+            else hipLaunchKernelGGL((k_render_bwd_alpha<false, false>), g, dim3(128), pad, s, LR_SEG_ARGS, dL_dalpha);
+        }
+    } else if (shape == BLEND_TILE) {
         if (strict) hipLaunchKernelGGL(k_render_bwd_tile<true>, g, dim3(64), 0, s, LR_SEG_ARGS);
 #ifdef LR_DIAGNOSTICS
         else if (red == 2) hipLaunchKernelGGL(k_render_bwd_tile_swap, g, dim3(64), 0, s, LR_SEG_ARGS);

@@ -468,4 +468,37 @@ void launch_render_fwd(int W, int H, int gx, int gy, const uint2* ranges, const 
 #undef LR_FWD
 }
 
+// The alpha output (lr_render_alpha): 1 - T_final of every pixel, from the final_T the blend forward left in the image state --
+// a pass of its own, so that the blend-forward kernels stay as they are.  Four pixels per lane when both arrays are 16-byte
+// aligned (final_T always is, ImgLayout), else one.
+__global__ void __launch_bounds__(256) k_render_alpha(const float* __restrict__ final_T, long long n, float* __restrict__ alpha)
+{
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) alpha[i] = 1.0f - final_T[i];
+}
+__global__ void __launch_bounds__(256) k_render_alpha4(const float4* __restrict__ final_T, long long n4, float4* __restrict__ alpha)
+{
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i < n4) {
+        const float4 t = final_T[i];
+        alpha[i] = make_float4(1.0f - t.x, 1.0f - t.y, 1.0f - t.z, 1.0f - t.w);
+    }
+}
+
+void launch_render_alpha(const float* final_T, long long n, float* alpha, hipStream_t s)
+{
+    if (n <= 0) return;
+    long long done = 0;
+    if ((reinterpret_cast<uintptr_t>(alpha) & 15u) == 0 && (reinterpret_cast<uintptr_t>(final_T) & 15u) == 0) {
+        const long long n4 = n / 4;
+        if (n4 > 0)
+            hipLaunchKernelGGL(k_render_alpha4, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s,
+                               reinterpret_cast<const float4*>(final_T), n4, reinterpret_cast<float4*>(alpha));
+        done = 4 * n4;
+    }
+    if (done < n)
+        hipLaunchKernelGGL(k_render_alpha, dim3((unsigned)((n - done + 255) / 256)), dim3(256), 0, s, final_T + done, n - done,
+                           alpha + done);
+}
+
 }  // namespace lr

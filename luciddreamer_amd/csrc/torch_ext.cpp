@@ -176,13 +176,15 @@ FwdResult rasterize_gaussians(const at::Tensor& background, const at::Tensor& me
 // result is None.  skip_unused: gradients of absent input representations are not materialised (None).
 // depth_image (keyword-only; the forward's depth output): depth mode -- dL_dout_depth is honoured (lr_backward_depth); without
 // it dL_dout_depth is ignored, as in the reference.
+// dL_dout_alpha (keyword-only, [1,H,W]): the gradient of the alpha output (render_alpha) as well -- lr_backward_alpha, alone or
+// with depth mode.
 std::vector<OptT> rasterize_gaussians_backward(
     const at::Tensor& background, const at::Tensor& means3D, const at::Tensor& radii, const OptT& colors, const OptT& scales,
     const OptT& rotations, double scale_modifier, const OptT& cov3D_precomp, const at::Tensor& viewmatrix,
     const at::Tensor& projmatrix, double tan_fovx, double tan_fovy, const at::Tensor& dL_dout_color, const OptT& dL_dout_depth,
     const OptT& sh, int64_t degree, const at::Tensor& campos, const at::Tensor& geomBuffer, int64_t R,
     const at::Tensor& binningBuffer, const at::Tensor& imageBuffer, bool debug, int64_t binning_capacity,
-    const std::vector<OptT>& accumulate, bool skip_unused, const OptT& depth_image)
+    const std::vector<OptT>& accumulate, bool skip_unused, const OptT& depth_image, const OptT& dL_dout_alpha)
 {
     require_device(means3D, "means3D");
     const c10::Device dev = means3D.device();
@@ -224,10 +226,24 @@ std::vector<OptT> rasterize_gaussians_backward(
         const Arg m = f32(means3D, dev, "means3D"), bg = f32(background, dev, "background"), view = f32(viewmatrix, dev, "viewmatrix"),
                   proj = f32(projmatrix, dev, "projmatrix"), cam = f32(campos, dev, "campos"), shc = f32(sh, dev, "sh"),
                   gc = f32(dL_dout_color, dev, "dL_dout_color"), gd = f32(dL_dout_depth, dev, "dL_dout_depth"),
-                  di = f32(depth_image, dev, "depth_image");
+                  di = f32(depth_image, dev, "depth_image"), ga = f32(dL_dout_alpha, dev, "dL_dout_alpha");
         const at::Tensor radii_c = radii.contiguous();
         hipStream_t cur = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(dev.index()).stream();
         ChainScope chain(mask != 0 || t_fused_backward, dev.index(), cur);
+        if (ga.p != nullptr) {
+            TORCH_CHECK(ga.t.numel() == H * W, "dL_dout_alpha must have the alpha output's shape (1, H, W)");
+            TORCH_CHECK(!di.p || di.t.numel() == H * W, "depth_image must be the forward's depth output (1, H, W)");
+            TORCH_CHECK(!di.p || !gd.p || gd.t.numel() == H * W, "dL_dout_depth must have the depth output's shape (1, H, W)");
+            const int rc = lr_backward_alpha(
+                static_cast<int>(P), static_cast<int>(degree), M, static_cast<int>(R), bg.p, static_cast<int>(W), static_cast<int>(H), m.p,
+                shc.p, col.p, sc.p, static_cast<float>(scale_modifier), rot.p, cov.p, view.p, proj.p, cam.p, static_cast<float>(tan_fovx),
+                static_cast<float>(tan_fovy), radii_c.data_ptr<int>(), static_cast<char*>(geomBuffer.data_ptr()),
+                static_cast<char*>(binningBuffer.data_ptr()), static_cast<char*>(imageBuffer.data_ptr()), gc.p, di.p ? gd.p : nullptr,
+                di.p, ga.p, ptr[0], nullptr, ptr[2], ptr[1], ptr[3], ptr[4], M ? ptr[5] : nullptr, ptr[6], ptr[7], debug ? 1 : 0,
+                static_cast<long long>(binning_capacity), mask, cur);
+            if (rc < 0) raise_for(rc, "rasterize_gaussians_backward");
+            return result;
+        }
         if (di.p != nullptr) {
             TORCH_CHECK(di.t.numel() == H * W, "depth_image must be the forward's depth output (1, H, W)");
             TORCH_CHECK(!gd.p || gd.t.numel() == H * W, "dL_dout_depth must have the depth output's shape (1, H, W)");
@@ -290,14 +306,15 @@ FwdResult rasterize_gaussians_raw(const at::Tensor& background, const at::Tensor
 
 // result / accumulate order: (means2D, xyz, features_dc, features_rest, opacity, scaling, rotation)
 // dL_dout_depth / depth_image (keyword-only): depth mode as in rasterize_gaussians_backward (lr_backward_raw_depth); the
-// gradient of the depth output is used only when both are given.
+// gradient of the depth output is used only when both are given.  dL_dout_alpha (keyword-only): lr_backward_raw_alpha.
 std::vector<OptT> rasterize_gaussians_raw_backward(
     const at::Tensor& background, const at::Tensor& xyz, const at::Tensor& radii, const at::Tensor& features_dc,
     const OptT& features_rest, const at::Tensor& opacity_raw, const at::Tensor& scaling_raw, const at::Tensor& rotation_raw,
     double scale_modifier, const at::Tensor& viewmatrix, const at::Tensor& projmatrix, double tan_fovx, double tan_fovy,
     const at::Tensor& dL_dout_color, int64_t degree, const at::Tensor& campos, const at::Tensor& geomBuffer, int64_t R,
     const at::Tensor& binningBuffer, const at::Tensor& imageBuffer, bool debug, int64_t binning_capacity,
-    const std::vector<OptT>& accumulate, bool no_zero_fill, const OptT& dL_dout_depth, const OptT& depth_image)
+    const std::vector<OptT>& accumulate, bool no_zero_fill, const OptT& dL_dout_depth, const OptT& depth_image,
+    const OptT& dL_dout_alpha)
 {
     require_device(xyz, "xyz");
     const c10::Device dev = xyz.device();
@@ -344,10 +361,24 @@ std::vector<OptT> rasterize_gaussians_raw_backward(
                   op = f32(opacity_raw, dev, "opacity"), sc = f32(scaling_raw, dev, "scaling"), rot = f32(rotation_raw, dev, "rotation"),
                   view = f32(viewmatrix, dev, "viewmatrix"), proj = f32(projmatrix, dev, "projmatrix"), cam = f32(campos, dev, "campos"),
                   gc = f32(dL_dout_color, dev, "dL_dout_color"), gd = f32(dL_dout_depth, dev, "dL_dout_depth"),
-                  di = f32(depth_image, dev, "depth_image");
+                  di = f32(depth_image, dev, "depth_image"), ga = f32(dL_dout_alpha, dev, "dL_dout_alpha");
         const at::Tensor radii_c = radii.contiguous();
         hipStream_t cur = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(dev.index()).stream();
         ChainScope chain((mask & ~LR_ACC_NO_ZERO_FILL) != 0, dev.index(), cur);
+        if (ga.p != nullptr) {
+            TORCH_CHECK(ga.t.numel() == H * W, "dL_dout_alpha must have the alpha output's shape (1, H, W)");
+            TORCH_CHECK(!di.p || di.t.numel() == H * W, "depth_image must be the forward's depth output (1, H, W)");
+            TORCH_CHECK(!di.p || !gd.p || gd.t.numel() == H * W, "dL_dout_depth must have the depth output's shape (1, H, W)");
+            const int rc = lr_backward_raw_alpha(
+                static_cast<int>(P), static_cast<int>(degree), M, static_cast<int>(R), bg.p, static_cast<int>(W), static_cast<int>(H), x.p,
+                dc.p, rest.p, op.p, sc.p, static_cast<float>(scale_modifier), rot.p, view.p, proj.p, cam.p, static_cast<float>(tan_fovx),
+                static_cast<float>(tan_fovy), radii_c.data_ptr<int>(), static_cast<char*>(geomBuffer.data_ptr()),
+                static_cast<char*>(binningBuffer.data_ptr()), static_cast<char*>(imageBuffer.data_ptr()), gc.p, di.p ? gd.p : nullptr,
+                di.p, ga.p, ptr[0], ptr[4], ptr[1], ptr[2], nrest ? ptr[3] : nullptr, ptr[5], ptr[6], debug ? 1 : 0,
+                static_cast<long long>(binning_capacity), mask, cur);
+            if (rc < 0) raise_for(rc, "rasterize_gaussians_raw_backward");
+            return result;
+        }
         if (di.p != nullptr) {
             TORCH_CHECK(di.t.numel() == H * W, "depth_image must be the forward's depth output (1, H, W)");
             TORCH_CHECK(!gd.p || gd.t.numel() == H * W, "dL_dout_depth must have the depth output's shape (1, H, W)");
@@ -419,6 +450,25 @@ void adam_step_masked(const std::vector<at::Tensor>& params, const std::vector<a
     if (rc < 0) raise_for(rc, "adam_step_masked");
 }
 
+// The alpha output of a forward (lr_render_alpha): 1 - T_final [1,H,W] from the forward's image buffer, on the current stream.
+// An empty buffer (P == 0: nothing was rendered, rasterize_points.cu:68-82) gives zeros.
+at::Tensor render_alpha(const at::Tensor& imageBuffer, int64_t H, int64_t W)
+{
+    const c10::Device dev = imageBuffer.device();
+    auto fopt = at::TensorOptions().dtype(at::kFloat).device(dev);
+    if (imageBuffer.numel() == 0) return at::zeros({1, H, W}, fopt);
+    require_device(imageBuffer, "imageBuffer");
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
+    TORCH_CHECK(imageBuffer.is_contiguous() && static_cast<size_t>(imageBuffer.numel()) >=
+                    lr_img_bytes(static_cast<int>(W), static_cast<int>(H)),
+                "imageBuffer is not the image state of an (H, W) forward");
+    at::Tensor alpha = at::empty({1, H, W}, fopt);
+    const int rc = lr_render_alpha(static_cast<const char*>(imageBuffer.data_ptr()), static_cast<int>(W), static_cast<int>(H),
+                                   alpha.data_ptr<float>(), c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(dev.index()).stream());
+    if (rc < 0) raise_for(rc, "render_alpha");
+    return alpha;
+}
+
 // ------------------------------------------------------------------------------------------------------------------
 // The autograd node of the drop-in operator in C++ (RAST/depth_diff_gaussian_rasterization_min/__init__.py:44-156 is a
 // Python torch.autograd.Function).  With the Python node a 1080p view cost ~230 us of host time against ~190 us of GPU
@@ -429,7 +479,8 @@ void adam_step_masked(const std::vector<at::Tensor>& params, const std::vector<a
 // forward arguments: the eight differentiable inputs in the reference's order (means3D, means2D, sh, colors_precomp,
 // opacities, scales, rotations, cov3Ds_precomp; absent ones as empty tensors), the four tensors of the settings tuple,
 // then its scalars, the async-mode binning capacity and the fused-accumulation switch (config.py).
-// returns (color, radii, depth, geom); num_rendered of the call is left in a thread-local (last_num_rendered()).
+// returns (color, radii, depth, geom), and with `alpha` the alpha output 1 - T_final as a fifth tensor; num_rendered of the
+// call is left in a thread-local (last_num_rendered()).
 // ------------------------------------------------------------------------------------------------------------------
 thread_local int64_t g_last_num_rendered = 0;
 
@@ -437,14 +488,15 @@ using torch::autograd::AutogradContext;
 using torch::autograd::variable_list;
 
 struct RasterizeFn : public torch::autograd::Function<RasterizeFn> {
-    static constexpr int kForwardArgs = 22;
+    static constexpr int kForwardArgs = 23;
 
     static variable_list forward(AutogradContext* ctx, const at::Tensor& means3D, const at::Tensor& means2D, const at::Tensor& sh,
                                  const at::Tensor& colors, const at::Tensor& opacities, const at::Tensor& scales,
                                  const at::Tensor& rotations, const at::Tensor& cov3D, const at::Tensor& bg,
                                  const at::Tensor& viewmatrix, const at::Tensor& projmatrix, const at::Tensor& campos,
                                  double scale_modifier, double tan_fovx, double tan_fovy, int64_t H, int64_t W, int64_t degree,
-                                 bool prefiltered, int64_t binning_capacity, bool fused_accumulate, bool depth_gradient)
+                                 bool prefiltered, int64_t binning_capacity, bool fused_accumulate, bool depth_gradient,
+                                 bool alpha)
     {
         FwdResult r = rasterize_gaussians(bg, means3D, colors, opacities, scales, rotations, scale_modifier, cov3D, viewmatrix,
                                           projmatrix, tan_fovx, tan_fovy, H, W, sh, degree, campos, prefiltered, false,
@@ -483,7 +535,14 @@ struct RasterizeFn : public torch::autograd::Function<RasterizeFn> {
             ctx->set_materialize_grads(false);
         }
         ctx->mark_non_differentiable({radii, geom});
-        return {color, radii, depth, geom};
+        if (!alpha) return {color, radii, depth, geom};
+        // the alpha output (a fifth output): its backward needs the forward's final T only, which the image buffer holds -- the
+        // alpha tensor itself is not kept (an output in saved_data is the reference cycle described above).  Undefined output
+        // gradients stay undefined, so that an unused alpha output reaches the default kernels (the other outputs' undefined
+        // gradients are handled in backward as torch's materialised zeros would be: a zero colour gradient, no depth gradient)
+        ctx->set_materialize_grads(false);
+        const at::Tensor a = render_alpha(std::get<6>(r), H, W);
+        return {color, radii, depth, geom, a};
     }
 
     static variable_list backward(AutogradContext* ctx, variable_list grad_out)
@@ -502,6 +561,8 @@ struct RasterizeFn : public torch::autograd::Function<RasterizeFn> {
         // depth mode only when the switch was on at the forward AND a gradient reached the depth output; otherwise the
         // default call (same kernels, same bits)
         const OptT depth_image = (g_depth.has_value() && d.find("depth") != d.end()) ? OptT(d["depth"].toTensor()) : OptT();
+        // alpha mode only when the node has an alpha output and a gradient reached it (lr_backward_alpha)
+        const OptT g_alpha = (grad_out.size() > 4 && grad_out[4].defined()) ? OptT(grad_out[4]) : OptT();
         // config.set_fused_grad_accumulation: a leaf input whose .grad exists (contiguous float32, 16-byte aligned: the kernels
         // accumulate with 16-byte accesses) receives `+=` inside the kernel; its slot of the result stays undefined
         const bool fused = d["fused"].toBool();
@@ -523,7 +584,7 @@ struct RasterizeFn : public torch::autograd::Function<RasterizeFn> {
             bg, means3D, d["radii"].toTensor(), colors, scales, rotations, d["scale_modifier"].toDouble(), cov3D, viewmatrix,
             projmatrix, d["tan_fovx"].toDouble(), d["tan_fovy"].toDouble(), g_color, g_depth, sh, d["degree"].toInt(), campos,
             d["geom"].toTensor(), d["num_rendered"].toInt(), d["binning"].toTensor(), d["img"].toTensor(), false,
-            d["capacity"].toInt(), acc, true, depth_image);
+            d["capacity"].toInt(), acc, true, depth_image, g_alpha);
         auto slot = [&](int k) { return g[k].has_value() ? *g[k] : at::Tensor(); };
         variable_list out(kForwardArgs);                       // one per forward argument; undefined = no gradient
         out[0] = slot(3); out[1] = slot(0); out[2] = slot(5); out[3] = slot(1); out[4] = slot(2); out[5] = slot(6); out[6] = slot(7);
@@ -538,11 +599,11 @@ std::vector<at::Tensor> rasterize_autograd(const at::Tensor& means3D, const at::
                                            const at::Tensor& viewmatrix, const at::Tensor& projmatrix, const at::Tensor& campos,
                                            double scale_modifier, double tan_fovx, double tan_fovy, int64_t H, int64_t W,
                                            int64_t degree, bool prefiltered, int64_t binning_capacity, bool fused_accumulate,
-                                           bool depth_gradient)
+                                           bool depth_gradient, bool alpha)
 {
     return RasterizeFn::apply(means3D, means2D, sh, colors, opacities, scales, rotations, cov3D, bg, viewmatrix, projmatrix, campos,
                               scale_modifier, tan_fovx, tan_fovy, H, W, degree, prefiltered, binning_capacity, fused_accumulate,
-                              depth_gradient);
+                              depth_gradient, alpha);
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -595,7 +656,7 @@ std::vector<at::Tensor> rasterize_view_step(const at::Tensor& means3D, const at:
         (void)rasterize_gaussians_backward(bg, means3D, std::get<3>(r), colors, scales, rotations, scale_modifier, cov3D, viewmatrix,
                                            projmatrix, tan_fovx, tan_fovy, grad_color, depth_mode ? grad_depth : OptT(), sh, degree,
                                            campos, std::get<4>(r), std::get<0>(r), std::get<5>(r), std::get<6>(r), false,
-                                           binning_capacity, acc, true, depth_mode ? OptT(std::get<2>(r)) : OptT());
+                                           binning_capacity, acc, true, depth_mode ? OptT(std::get<2>(r)) : OptT(), OptT());
     }
     return { std::get<1>(r), std::get<3>(r), std::get<2>(r), std::get<4>(r) };
 }
@@ -664,15 +725,21 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
           py::arg("dL_dout_color"), py::arg("dL_dout_depth"), py::arg("sh"), py::arg("degree"), py::arg("campos"),
           py::arg("geomBuffer"), py::arg("R"), py::arg("binningBuffer"), py::arg("imageBuffer"), py::arg("debug"),
           py::arg("binning_capacity"), py::arg("accumulate"), py::arg("skip_unused"), py::kw_only(),
-          py::arg("depth_image") = py::none());
+          py::arg("depth_image") = py::none(), py::arg("dL_dout_alpha") = py::none());
     m.def("rasterize_gaussians_raw", &rasterize_gaussians_raw);
     m.def("rasterize_gaussians_raw_backward", &rasterize_gaussians_raw_backward, py::arg("background"), py::arg("xyz"),
           py::arg("radii"), py::arg("features_dc"), py::arg("features_rest"), py::arg("opacity_raw"), py::arg("scaling_raw"),
           py::arg("rotation_raw"), py::arg("scale_modifier"), py::arg("viewmatrix"), py::arg("projmatrix"), py::arg("tan_fovx"),
           py::arg("tan_fovy"), py::arg("dL_dout_color"), py::arg("degree"), py::arg("campos"), py::arg("geomBuffer"), py::arg("R"),
           py::arg("binningBuffer"), py::arg("imageBuffer"), py::arg("debug"), py::arg("binning_capacity"), py::arg("accumulate"),
-          py::arg("no_zero_fill"), py::kw_only(), py::arg("dL_dout_depth") = py::none(), py::arg("depth_image") = py::none());
-    m.def("rasterize_autograd", &rasterize_autograd);
+          py::arg("no_zero_fill"), py::kw_only(), py::arg("dL_dout_depth") = py::none(), py::arg("depth_image") = py::none(),
+          py::arg("dL_dout_alpha") = py::none());
+    m.def("rasterize_autograd", &rasterize_autograd, py::arg("means3D"), py::arg("means2D"), py::arg("sh"), py::arg("colors"),
+          py::arg("opacities"), py::arg("scales"), py::arg("rotations"), py::arg("cov3D"), py::arg("bg"), py::arg("viewmatrix"),
+          py::arg("projmatrix"), py::arg("campos"), py::arg("scale_modifier"), py::arg("tan_fovx"), py::arg("tan_fovy"), py::arg("H"),
+          py::arg("W"), py::arg("degree"), py::arg("prefiltered"), py::arg("binning_capacity"), py::arg("fused_accumulate"),
+          py::arg("depth_gradient"), py::arg("alpha") = false);
+    m.def("render_alpha", &render_alpha);
     m.def("last_num_rendered", [] { return g_last_num_rendered; });
     m.def("mark_visible", &mark_visible);
     m.def("rasterize_view_step", &rasterize_view_step, py::arg("means3D"), py::arg("means2D"), py::arg("sh"), py::arg("colors"),

@@ -249,10 +249,16 @@ def install(gaussian_renderer=None, loss=None, gaussian_model=None, *, render=Tr
     if render and gaussian_renderer is not None:
         orig_render = gaussian_renderer.render
 
-        def render_(viewpoint_camera, pc, opt, bg_color, scaling_modifier=1.0, override_color=None, render_only=False):
+        def render_(viewpoint_camera, pc, opt, bg_color, scaling_modifier=1.0, override_color=None, render_only=False,
+                    return_alpha=False):
+            # return_alpha: the result gains "alpha" (gaussian_renderer.render); the reference's own render has no such
+            # keyword, so an alpha-requesting call it would take goes to this package's render of the same contract
             if not _raw_ok(pc, opt, override_color):
+                if return_alpha:
+                    return gr.render(viewpoint_camera, pc, opt, bg_color, scaling_modifier, override_color, render_only,
+                                     return_alpha=True)
                 return orig_render(viewpoint_camera, pc, opt, bg_color, scaling_modifier, override_color, render_only)
-            out = gr.render_raw(viewpoint_camera, pc, opt, bg_color, scaling_modifier, render_only)
+            out = gr.render_raw(viewpoint_camera, pc, opt, bg_color, scaling_modifier, render_only, return_alpha=return_alpha)
             if not render_only:
                 # carries the radii for the fused densification statistics below, and keeps the caller's own
                 # `max_radii2D[filter] = torch.max(max_radii2D[filter], radii[filter])` on the device (_VisFilter above)

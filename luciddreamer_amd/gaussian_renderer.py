@@ -19,8 +19,9 @@ DEFAULT_OPT = SimpleNamespace(debug=False, compute_cov3D_python=False, convert_S
 
 
 def render(viewpoint_camera, pc, opt=DEFAULT_OPT, bg_color=None, scaling_modifier=1.0, override_color=None,
-           render_only=False):
-    """Returns {"render", "viewspace_points", "visibility_filter", "radii", "depth"} (or render/depth only)."""
+           render_only=False, return_alpha=False):
+    """Returns {"render", "viewspace_points", "visibility_filter", "radii", "depth"} (or render/depth only); with
+    return_alpha the dict gains "alpha", the accumulated opacity 1 - T_final (1, H, W), differentiable."""
     xyz = pc.get_xyz
     if bg_color is None:
         bg_color = torch.zeros(3, dtype=torch.float32, device=xyz.device)
@@ -62,20 +63,29 @@ def render(viewpoint_camera, pc, opt=DEFAULT_OPT, bg_color=None, scaling_modifie
     else:
         colors_precomp = override_color
 
-    rendered_image, radii, depth = rasterizer(
+    out = rasterizer(
         means3D=xyz, means2D=screenspace_points, shs=shs, colors_precomp=colors_precomp,
-        opacities=pc.get_opacity, scales=scales, rotations=rotations, cov3D_precomp=cov3D_precomp)
-    if render_only:
-        return {"render": rendered_image, "depth": depth}
-    return {"render": rendered_image, "viewspace_points": screenspace_points, "visibility_filter": radii > 0,
-            "radii": radii, "depth": depth}
+        opacities=pc.get_opacity, scales=scales, rotations=rotations, cov3D_precomp=cov3D_precomp, return_alpha=return_alpha)
+    return _result(out, screenspace_points, render_only)
 
 
-def render_raw(viewpoint_camera, pc, opt=DEFAULT_OPT, bg_color=None, scaling_modifier=1.0, render_only=False):
+def _result(out, screenspace_points, render_only):
+    rendered_image, radii, depth = out[:3]
+    res = {"render": rendered_image, "depth": depth} if render_only else \
+        {"render": rendered_image, "viewspace_points": screenspace_points, "visibility_filter": radii > 0, "radii": radii,
+         "depth": depth}
+    if len(out) > 3:
+        res["alpha"] = out[3]
+    return res
+
+
+def render_raw(viewpoint_camera, pc, opt=DEFAULT_OPT, bg_color=None, scaling_modifier=1.0, render_only=False,
+               return_alpha=False):
     """render() for the common training configuration (SH colours, scale/rotation covariance), reading the STORED
     parameters of `pc` (`_xyz, _features_dc, _features_rest, _opacity, _scaling, _rotation`,
     /root/reference/scene/gaussian_model.py:47-52) instead of the activated getters: the activations and the
-    dc|rest concatenation happen inside the rasterizer kernels.  Same return dict as render()."""
+    dc|rest concatenation happen inside the rasterizer kernels.  Same return dict as render() (return_alpha
+    included)."""
     xyz = pc._xyz
     if bg_color is None:
         bg_color = torch.zeros(3, dtype=torch.float32, device=xyz.device)
@@ -90,12 +100,9 @@ def render_raw(viewpoint_camera, pc, opt=DEFAULT_OPT, bg_color=None, scaling_mod
         bg=bg_color, scale_modifier=scaling_modifier, viewmatrix=viewpoint_camera.world_view_transform,
         projmatrix=viewpoint_camera.full_proj_transform, sh_degree=pc.active_sh_degree,
         campos=viewpoint_camera.camera_center, prefiltered=False, debug=bool(getattr(opt, "debug", False)))
-    rendered_image, radii, depth = rasterize_gaussians_raw(xyz, screenspace_points, pc._features_dc, pc._features_rest,
-                                                           pc._opacity, pc._scaling, pc._rotation, rs)
-    if render_only:
-        return {"render": rendered_image, "depth": depth}
-    return {"render": rendered_image, "viewspace_points": screenspace_points, "visibility_filter": radii > 0,
-            "radii": radii, "depth": depth}
+    out = rasterize_gaussians_raw(xyz, screenspace_points, pc._features_dc, pc._features_rest, pc._opacity, pc._scaling,
+                                  pc._rotation, rs, return_alpha=return_alpha)
+    return _result(out, screenspace_points, render_only)
 
 
 class GaussianCloud:

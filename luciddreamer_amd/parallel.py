@@ -615,7 +615,10 @@ def _direct_backward(out: torch.Tensor, grad_output: torch.Tensor, grad_depth: O
             leaves.append(nxt.variable)
         else:
             return False
-    grads = fn(grad_output, None, grad_depth, None)              # the compiled node's outputs: (color, radii, depth, geom)
+    # the compiled node's outputs: (color, radii, depth, geom), and alpha after them when the call asked for it
+    # (return_alpha): no gradient reaches that one here, exactly as in the engine's pass over (out, grad_output)
+    n_out = len(fn._input_metadata)
+    grads = fn(grad_output, None, grad_depth, *([None] * (n_out - 3)))
     if not isinstance(grads, (tuple, list)):
         grads = (grads,)
     with torch.no_grad():

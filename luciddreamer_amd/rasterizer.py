@@ -5,6 +5,9 @@
     GaussianRasterizer              nn.Module; forward(...) -> (color, radii, depth); markVisible (:172-221)
     rasterize_gaussians             functional entry                                (:21-42)
 
+Beyond the reference: return_alpha=True (GaussianRasterizer.forward, rasterize_gaussians, rasterize_gaussians_raw) returns
+(color, radii, depth, alpha) -- alpha (1, H, W) = 1 - T_final, the accumulated opacity, differentiable (lr_backward_alpha).
+
 Error behaviour mirrored: plain `Exception` for bad SH/colour or scale/rotation/covariance
 combinations (:192-196); with settings.debug the inputs of a failing call are dumped to
 snapshot_fw.dump / snapshot_bw.dump before re-raising (:83-90, :133-140).
@@ -57,7 +60,7 @@ class _RasterizeGaussians(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                raster_settings):
+                raster_settings, return_alpha=False):
         rs = raster_settings
         args = (rs.bg, means3D, colors_precomp, opacities, scales, rotations, rs.scale_modifier, cov3Ds_precomp,
                 rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, rs.image_height, rs.image_width, sh,
@@ -99,10 +102,15 @@ class _RasterizeGaussians(torch.autograd.Function):
         if ctx.depth_image is not None:
             ctx.set_materialize_grads(False)        # an unused depth output arrives as None: the default kernels
         ctx.save_for_backward(colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geom, binning, img)
-        return color, radii, depth
+        if not return_alpha:
+            return color, radii, depth
+        # the alpha output, from the image state of the forward returned above (after a re-render, the re-render's); the
+        # backward needs that state's final T only -- the alpha tensor itself is not kept (see depth_image above)
+        ctx.set_materialize_grads(False)            # an unused alpha output arrives as None: the default kernels
+        return color, radii, depth, _C.render_alpha(img, rs.image_height, rs.image_width)
 
     @staticmethod
-    def backward(ctx, grad_out_color, grad_radii, grad_depth):
+    def backward(ctx, grad_out_color, grad_radii, grad_depth, grad_alpha=None):
         rs = ctx.raster_settings
         colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geom, binning, img = ctx.saved_tensors
         if grad_out_color is None:
@@ -124,7 +132,7 @@ class _RasterizeGaussians(torch.autograd.Function):
             (grad_means2D, grad_colors_precomp, grad_opacities, grad_means3D, grad_cov3Ds_precomp, grad_sh,
              grad_scales, grad_rotations) = _C.rasterize_gaussians_backward(
                 *args, binning_capacity=ctx.binning_capacity, accumulate_into=accumulate_into, skip_unused=True,
-                depth_image=depth_image)
+                depth_image=depth_image, dL_dout_alpha=grad_alpha)
         except Exception:
             if rs.debug:
                 _snapshot(args, "snapshot_bw.dump")
@@ -132,23 +140,26 @@ class _RasterizeGaussians(torch.autograd.Function):
             raise
         # order of the forward inputs (RAST/.../__init__.py:144-154); gradients of absent inputs are None-able
         return (grad_means3D, grad_means2D, grad_sh, grad_colors_precomp, grad_opacities, grad_scales, grad_rotations,
-                grad_cov3Ds_precomp, None)
+                grad_cov3Ds_precomp, None, None)
 
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                        raster_settings):
+                        raster_settings, return_alpha=False):
     """The operator.  Its autograd node is compiled (csrc/torch_ext.cpp RasterizeFn: forward and backward run without the
     interpreter -- the Python node below cost more host time per 1080p view than the GPU needs for it); with settings.debug
-    the Python node runs instead, because it is the one that writes the reference's snapshot_fw.dump / snapshot_bw.dump."""
+    the Python node runs instead, because it is the one that writes the reference's snapshot_fw.dump / snapshot_bw.dump.
+    return_alpha: (color, radii, depth, alpha) -- alpha = 1 - T_final (1, H, W), differentiable; a gradient reaching it runs the
+    alpha-mode backward (lr_backward_alpha), an unused alpha output the default one."""
     rs = raster_settings
     if rs.debug:
         return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
-                                         cov3Ds_precomp, rs)
+                                         cov3Ds_precomp, rs, bool(return_alpha))
     capacity = config.capacity_for(means3D, rs)
     verifying = config.verifying(capacity)
     fused = config.fused_grad_accumulation()
     offered = config.offered_grad_output()
-    if offered is not None and fused and not verifying:
+    # (an alpha-requesting call never takes the direct route: its backward would not see a gradient of alpha)
+    if offered is not None and fused and not verifying and not return_alpha:
         # the caller already holds dL/dcolor (parallel.ViewStreams.run_view): forward and backward in ONE call of the binding,
         # gradients added into the leaves' .grad by the kernels, no autograd node (csrc/torch_ext.cpp rasterize_view_step).
         # An input that is not a leaf with a suitable .grad -> empty result -> the autograd path below, offer untouched.
@@ -167,12 +178,12 @@ def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales,
         return _C.rasterize_autograd(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, rs.bg,
                                      rs.viewmatrix, rs.projmatrix, rs.campos, rs.scale_modifier, rs.tanfovx, rs.tanfovy,
                                      rs.image_height, rs.image_width, rs.sh_degree, rs.prefiltered, cap, fused,
-                                     config.depth_gradient())
+                                     config.depth_gradient(), bool(return_alpha))
     ticket = -1
     if verifying:
         _C.request_early_header()
     try:
-        color, radii, depth, geom = run(capacity)
+        out = run(capacity)
     finally:
         if verifying:
             ticket = _take_ticket()
@@ -180,9 +191,11 @@ def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales,
     # rendered again in exact mode -- what is returned is always a complete image (the first node is simply dropped)
     if verifying and config.verify(means3D, rs, ticket):
         capacity = 0
-        color, radii, depth, geom = run(0)
-    config.note_forward(means3D, rs, _C.last_num_rendered(), geom, capacity)
-    return color, radii, depth
+        out = run(0)
+    config.note_forward(means3D, rs, _C.last_num_rendered(), out[3], capacity)
+    if return_alpha:
+        return out[0], out[1], out[2], out[4]
+    return out[0], out[1], out[2]
 
 
 class _RasterizeGaussiansRaw(torch.autograd.Function):
@@ -190,7 +203,7 @@ class _RasterizeGaussiansRaw(torch.autograd.Function):
     exp / normalize / sigmoid / cat and their autograd nodes (R/scene/gaussian_model.py:97-117)."""
 
     @staticmethod
-    def forward(ctx, xyz, means2D, features_dc, features_rest, opacity, scaling, rotation, raster_settings):
+    def forward(ctx, xyz, means2D, features_dc, features_rest, opacity, scaling, rotation, raster_settings, return_alpha=False):
         rs = raster_settings
         capacity = config.capacity_for(xyz, rs)
         verifying = config.verifying(capacity)
@@ -222,10 +235,13 @@ class _RasterizeGaussiansRaw(torch.autograd.Function):
         if ctx.depth_image is not None:
             ctx.set_materialize_grads(False)
         ctx.save_for_backward(xyz, features_dc, features_rest, opacity, scaling, rotation, radii, geom, binning, img)
-        return color, radii, depth
+        if not return_alpha:
+            return color, radii, depth
+        ctx.set_materialize_grads(False)                # as _RasterizeGaussians
+        return color, radii, depth, _C.render_alpha(img, rs.image_height, rs.image_width)
 
     @staticmethod
-    def backward(ctx, grad_out_color, grad_radii, grad_depth):
+    def backward(ctx, grad_out_color, grad_radii, grad_depth, grad_alpha=None):
         rs = ctx.raster_settings
         xyz, features_dc, features_rest, opacity, scaling, rotation, radii, geom, binning, img = ctx.saved_tensors
         if grad_out_color is None:
@@ -233,6 +249,8 @@ class _RasterizeGaussiansRaw(torch.autograd.Function):
         # depth mode (config.set_depth_gradient at the forward, and a gradient for depth): lr_backward_raw_depth
         depth = dict(dL_dout_depth=grad_depth, depth_image=ctx.depth_image) \
             if (grad_depth is not None and ctx.depth_image is not None) else {}
+        if grad_alpha is not None:                      # alpha mode: lr_backward_raw_alpha (with or without depth mode)
+            depth["dL_dout_alpha"] = grad_alpha
         accumulate_into = None
         if ctx.leaf_inputs is not None:
             def leaf_grad(t):
@@ -258,19 +276,21 @@ class _RasterizeGaussiansRaw(torch.autograd.Function):
                 rs.projmatrix, rs.tanfovx, rs.tanfovy, grad_out_color, rs.sh_degree, rs.campos, geom, ctx.num_rendered,
                 binning, img, False, binning_capacity=ctx.binning_capacity, no_zero_fill=True, **depth)
             opt.apply_armed_step(geom, [xyz, features_dc, features_rest, opacity, scaling, rotation], list(g[1:]))
-            return None, g[0], None, None, None, None, None, None
+            return None, g[0], None, None, None, None, None, None, None
         g = _C.rasterize_gaussians_raw_backward(
             rs.bg, xyz, radii, features_dc, features_rest, opacity, scaling, rotation, rs.scale_modifier, rs.viewmatrix,
             rs.projmatrix, rs.tanfovx, rs.tanfovy, grad_out_color, rs.sh_degree, rs.campos, geom, ctx.num_rendered,
             binning, img, rs.debug, binning_capacity=ctx.binning_capacity, accumulate_into=accumulate_into, **depth)
         g_means2D, g_xyz, g_dc, g_rest, g_op, g_sc, g_rot = g
-        return g_xyz, g_means2D, g_dc, g_rest, g_op, g_sc, g_rot, None
+        return g_xyz, g_means2D, g_dc, g_rest, g_op, g_sc, g_rot, None, None
 
 
-def rasterize_gaussians_raw(xyz, means2D, features_dc, features_rest, opacity, scaling, rotation, raster_settings):
-    """(color, radii, depth) from the stored GaussianModel parameters (pre-activation), see _RasterizeGaussiansRaw."""
+def rasterize_gaussians_raw(xyz, means2D, features_dc, features_rest, opacity, scaling, rotation, raster_settings,
+                            return_alpha=False):
+    """(color, radii, depth) from the stored GaussianModel parameters (pre-activation), see _RasterizeGaussiansRaw;
+    return_alpha: (color, radii, depth, alpha) as rasterize_gaussians."""
     return _RasterizeGaussiansRaw.apply(xyz, means2D, features_dc, features_rest, opacity, scaling, rotation,
-                                        raster_settings)
+                                        raster_settings, bool(return_alpha))
 
 
 _EMPTY = torch.Tensor([])           # never written: one instance serves every call (three constructions per call were ~6 us)
@@ -288,7 +308,8 @@ class GaussianRasterizer(nn.Module):
             return _C.mark_visible(positions, rs.viewmatrix, rs.projmatrix)
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
-                cov3D_precomp=None):
+                cov3D_precomp=None, return_alpha=False):
+        """(color, radii, depth), or with return_alpha=True (color, radii, depth, alpha): alpha (1, H, W) = 1 - T_final."""
         rs = self.raster_settings
         if (shs is None) == (colors_precomp is None):
             raise Exception('Please provide excatly one of either SHs or precomputed colors!')
@@ -303,5 +324,8 @@ class GaussianRasterizer(nn.Module):
         scales = empty if scales is None else scales
         rotations = empty if rotations is None else rotations
         cov3D_precomp = empty if cov3D_precomp is None else cov3D_precomp
+        if return_alpha:
+            return rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
+                                       cov3D_precomp, rs, return_alpha=True)
         return rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
                                    cov3D_precomp, rs)
