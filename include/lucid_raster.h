@@ -346,7 +346,8 @@ int lr_render_alpha(const char* image_buffer, int width, int height, float* out_
 /*
  * Alpha mode: lr_backward_depth / lr_backward_raw_depth with a gradient through the alpha output as well.  Each takes its
  * depth counterpart's arguments plus dL_dalpha [1,H,W] right after depth_image; the depth pair is optional (NULL, NULL: alpha
- * alone).  With dL_dalpha == NULL each is exactly its depth counterpart (same kernels, same bits).
+ * alone).  With dL_dalpha == NULL each is exactly its depth counterpart (same kernels, same bits).  These two are the general
+ * per-view backward entries: the other four are these with NULLs.
  * The derivative is that of 1 - prod_i (1 - alpha_i) over the layers the forward applied, with the colour path's conventions
  * (the 0.99 clamp of alpha not differentiated; the alpha < 1/255 and power > 0 skips, the T < 1e-4 stop -- whose trigger is not
  * applied -- and the sort order are constants; the fov clamp as there): d alpha_pix / d alpha_i = T_final / (1 - alpha_i).  It

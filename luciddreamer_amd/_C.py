@@ -53,10 +53,10 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
     skip_unused: do not materialise gradients of inputs that are absent (dL_dcolors when SHs are used, dL_dcov3D /
     dL_dscales / dL_drotations for the representation not in use); their slots are None.  The reference always
     returns all eight tensors, so the default keeps that.
-    depth_image (optional): the forward's depth output -- depth mode (lr_backward_depth): dL_dout_depth is honoured.  Without
-    it dL_dout_depth is ignored, as in the reference.
-    dL_dout_alpha (optional, (1, H, W)): the gradient of the alpha output (render_alpha) as well -- lr_backward_alpha, alone or
-    together with depth mode."""
+    depth_image (optional): the forward's depth output -- depth mode: dL_dout_depth is honoured.  Without it dL_dout_depth
+    is ignored, as in the reference.
+    dL_dout_alpha (optional, (1, H, W)): the gradient of the alpha output (render_alpha) as well, alone or together with depth
+    mode.  Every mode, the default included, is one call of lr_backward_alpha with NULL for what is absent."""
     acc = _NONE8 if not accumulate_into else [accumulate_into.get(k) for k in GRAD_ORDER]
     return tuple(_C_ext.rasterize_gaussians_backward(
         background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix, projmatrix,
@@ -85,8 +85,8 @@ def rasterize_gaussians_raw_backward(background, xyz, radii, features_dc, featur
     """Gradients w.r.t. the stored tensors: (means2D, xyz, features_dc, features_rest, opacity, scaling, rotation).
     accumulate_into: {"means2D","xyz","opacity","scaling","rotation": tensor, "features": (dc_grad, rest_grad)} adds
     in place (slot returned as None).
-    dL_dout_depth + depth_image (the forward's depth output): depth mode (lr_backward_raw_depth).
-    dL_dout_alpha: the gradient of the alpha output as well (lr_backward_raw_alpha)."""
+    dL_dout_depth + depth_image (the forward's depth output): depth mode.
+    dL_dout_alpha: the gradient of the alpha output as well.  Every mode is one call of lr_backward_raw_alpha."""
     acc = _NONE8
     if accumulate_into:
         f = accumulate_into.get("features") or (None, None)

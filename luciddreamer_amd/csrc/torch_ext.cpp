@@ -171,13 +171,47 @@ FwdResult rasterize_gaussians(const at::Tensor& background, const at::Tensor& me
     return FwdResult(rc, out_color, out_depth, radii, geom.t, binning.t, img.t);
 }
 
+// One gradient output of a backward binding: `acc` (a caller tensor, if given) receives `+=` in place -- its LR_ACC_* `bit` is set
+// in `mask` and its result slot stays None --; otherwise a new tensor of `shape`, fully written by the library (culled rows = 0,
+// cf. rasterize_points.cu:154-162) and returned in `*slot` (a null `slot` only for an empty tensor, whose pointer is null)
+float* grad_output(const at::Tensor* acc, const std::vector<int64_t>& shape, int bit, const c10::Device& dev, unsigned int& mask,
+                   OptT* slot)
+{
+    at::Tensor t;
+    if (acc) {
+        int64_t n = 1;
+        for (int64_t d : shape) n *= d;
+        TORCH_CHECK(acc->scalar_type() == at::kFloat && acc->is_contiguous() && acc->device() == dev && acc->numel() == n,
+                    "accumulate tensors must be contiguous float32 of the gradient's size on ", dev);
+        mask |= 1u << bit;
+        t = *acc;
+    } else {
+        t = at::empty(shape, at::TensorOptions().dtype(at::kFloat).device(dev));
+        if (slot) *slot = t;
+    }
+    return t.numel() ? t.data_ptr<float>() : nullptr;
+}
+const at::Tensor* given(const std::vector<OptT>& accumulate, int k)
+{
+    return (!accumulate.empty() && accumulate[k].has_value() && accumulate[k]->defined()) ? &*accumulate[k] : nullptr;
+}
+
+// The optional images of the depth and alpha modes.  Both backward bindings always call the general entry (lr_backward_alpha /
+// lr_backward_raw_alpha) and leave the mode to the library: depth mode iff depth_image and dL_dout_depth are both given (so
+// dL_dout_depth goes in only with depth_image), alpha mode iff dL_dout_alpha is; with neither, the default backward, bit for bit.
+void check_mode_images(int64_t H, int64_t W, const Arg& gd, const Arg& di, const Arg& ga)
+{
+    TORCH_CHECK(!ga.p || ga.t.numel() == H * W, "dL_dout_alpha must have the alpha output's shape (1, H, W)");
+    TORCH_CHECK(!di.p || di.t.numel() == H * W, "depth_image must be the forward's depth output (1, H, W)");
+    TORCH_CHECK(!di.p || !gd.p || gd.t.numel() == H * W, "dL_dout_depth must have the depth output's shape (1, H, W)");
+}
+
 // accumulate: eight optional tensors in the order of the returned tuple (means2D, colors, opacity, means3D, cov3D, sh,
 // scales, rotations); a given tensor receives `+=` in place (rows of culled Gaussians untouched) and its slot of the
 // result is None.  skip_unused: gradients of absent input representations are not materialised (None).
-// depth_image (keyword-only; the forward's depth output): depth mode -- dL_dout_depth is honoured (lr_backward_depth); without
-// it dL_dout_depth is ignored, as in the reference.
-// dL_dout_alpha (keyword-only, [1,H,W]): the gradient of the alpha output (render_alpha) as well -- lr_backward_alpha, alone or
-// with depth mode.
+// depth_image (keyword-only; the forward's depth output): with it dL_dout_depth is honoured (depth mode); without it
+// dL_dout_depth is ignored, as in the reference.  dL_dout_alpha (keyword-only, [1,H,W]): the gradient of the alpha output
+// (render_alpha) as well, alone or with depth mode.
 std::vector<OptT> rasterize_gaussians_backward(
     const at::Tensor& background, const at::Tensor& means3D, const at::Tensor& radii, const OptT& colors, const OptT& scales,
     const OptT& rotations, double scale_modifier, const OptT& cov3D_precomp, const at::Tensor& viewmatrix,
@@ -193,7 +227,6 @@ std::vector<OptT> rasterize_gaussians_backward(
     const int M = sh_coeffs(sh);
     TORCH_CHECK(accumulate.empty() || accumulate.size() == 8, "accumulate: eight entries or none");
     c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
-    auto fopt = at::TensorOptions().dtype(at::kFloat).device(dev);
     // order of the result tuple (rasterize_points.cu:199) and the LR_ACC_* bit of each entry
     static const int kBit[8] = { 0, 3, 2, 4, 5, 6, 7, 8 };
     const std::vector<int64_t> shapes[8] = { { P, 3 }, { P, 3 }, { P, 1 }, { P, 3 }, { P, 6 }, { P, M, 3 }, { P, 3 }, { P, 4 } };
@@ -201,70 +234,27 @@ std::vector<OptT> rasterize_gaussians_backward(
               cov = f32(cov3D_precomp, dev, "cov3D_precomp");
     const bool unused[8] = { false, skip_unused && !col.p, false, false, skip_unused && !cov.p, false, skip_unused && !sc.p,
                              skip_unused && !sc.p };
-    at::Tensor out[8];
     float* ptr[8];
     unsigned int mask = 0;
     std::vector<OptT> result(8);
-    for (int k = 0; k < 8; k++) {
-        ptr[k] = nullptr;
-        if (unused[k]) continue;
-        if (!accumulate.empty() && accumulate[k].has_value() && accumulate[k]->defined()) {
-            const at::Tensor& t = *accumulate[k];
-            int64_t n = 1;
-            for (int64_t d : shapes[k]) n *= d;
-            TORCH_CHECK(t.scalar_type() == at::kFloat && t.is_contiguous() && t.device() == dev && t.numel() == n,
-                        "accumulate tensors must be contiguous float32 of the gradient's size on ", dev);
-            mask |= 1u << kBit[k];
-            out[k] = t;
-        } else {
-            out[k] = at::empty(shapes[k], fopt);     // fully written by the library (culled rows = 0), cf. :154-162
-            result[k] = out[k];
-        }
-        ptr[k] = out[k].numel() ? out[k].data_ptr<float>() : nullptr;
-    }
+    for (int k = 0; k < 8; k++)
+        ptr[k] = unused[k] ? nullptr : grad_output(given(accumulate, k), shapes[k], kBit[k], dev, mask, &result[k]);
     if (P != 0) {
         const Arg m = f32(means3D, dev, "means3D"), bg = f32(background, dev, "background"), view = f32(viewmatrix, dev, "viewmatrix"),
                   proj = f32(projmatrix, dev, "projmatrix"), cam = f32(campos, dev, "campos"), shc = f32(sh, dev, "sh"),
                   gc = f32(dL_dout_color, dev, "dL_dout_color"), gd = f32(dL_dout_depth, dev, "dL_dout_depth"),
                   di = f32(depth_image, dev, "depth_image"), ga = f32(dL_dout_alpha, dev, "dL_dout_alpha");
+        check_mode_images(H, W, gd, di, ga);
         const at::Tensor radii_c = radii.contiguous();
         hipStream_t cur = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(dev.index()).stream();
         ChainScope chain(mask != 0 || t_fused_backward, dev.index(), cur);
-        if (ga.p != nullptr) {
-            TORCH_CHECK(ga.t.numel() == H * W, "dL_dout_alpha must have the alpha output's shape (1, H, W)");
-            TORCH_CHECK(!di.p || di.t.numel() == H * W, "depth_image must be the forward's depth output (1, H, W)");
-            TORCH_CHECK(!di.p || !gd.p || gd.t.numel() == H * W, "dL_dout_depth must have the depth output's shape (1, H, W)");
-            const int rc = lr_backward_alpha(
-                static_cast<int>(P), static_cast<int>(degree), M, static_cast<int>(R), bg.p, static_cast<int>(W), static_cast<int>(H), m.p,
-                shc.p, col.p, sc.p, static_cast<float>(scale_modifier), rot.p, cov.p, view.p, proj.p, cam.p, static_cast<float>(tan_fovx),
-                static_cast<float>(tan_fovy), radii_c.data_ptr<int>(), static_cast<char*>(geomBuffer.data_ptr()),
-                static_cast<char*>(binningBuffer.data_ptr()), static_cast<char*>(imageBuffer.data_ptr()), gc.p, di.p ? gd.p : nullptr,
-                di.p, ga.p, ptr[0], nullptr, ptr[2], ptr[1], ptr[3], ptr[4], M ? ptr[5] : nullptr, ptr[6], ptr[7], debug ? 1 : 0,
-                static_cast<long long>(binning_capacity), mask, cur);
-            if (rc < 0) raise_for(rc, "rasterize_gaussians_backward");
-            return result;
-        }
-        if (di.p != nullptr) {
-            TORCH_CHECK(di.t.numel() == H * W, "depth_image must be the forward's depth output (1, H, W)");
-            TORCH_CHECK(!gd.p || gd.t.numel() == H * W, "dL_dout_depth must have the depth output's shape (1, H, W)");
-            const int rc = lr_backward_depth(
-                static_cast<int>(P), static_cast<int>(degree), M, static_cast<int>(R), bg.p, static_cast<int>(W), static_cast<int>(H), m.p,
-                shc.p, col.p, sc.p, static_cast<float>(scale_modifier), rot.p, cov.p, view.p, proj.p, cam.p, static_cast<float>(tan_fovx),
-                static_cast<float>(tan_fovy), radii_c.data_ptr<int>(), static_cast<char*>(geomBuffer.data_ptr()),
-                static_cast<char*>(binningBuffer.data_ptr()), static_cast<char*>(imageBuffer.data_ptr()), gc.p, gd.p, di.p, ptr[0],
-                nullptr, ptr[2], ptr[1], ptr[3], ptr[4], M ? ptr[5] : nullptr, ptr[6], ptr[7], debug ? 1 : 0,
-                static_cast<long long>(binning_capacity), mask, cur);
-            if (rc < 0) raise_for(rc, "rasterize_gaussians_backward");
-            return result;
-        }
-        const int rc = lr_backward(static_cast<int>(P), static_cast<int>(degree), M, static_cast<int>(R), bg.p, static_cast<int>(W),
-                                   static_cast<int>(H), m.p, shc.p, col.p, sc.p, static_cast<float>(scale_modifier), rot.p, cov.p,
-                                   view.p, proj.p, cam.p, static_cast<float>(tan_fovx), static_cast<float>(tan_fovy),
-                                   radii_c.data_ptr<int>(), static_cast<char*>(geomBuffer.data_ptr()),
-                                   static_cast<char*>(binningBuffer.data_ptr()), static_cast<char*>(imageBuffer.data_ptr()), gc.p, gd.p,
-                                   ptr[0], nullptr, ptr[2], ptr[1], ptr[3], ptr[4], M ? ptr[5] : nullptr, ptr[6], ptr[7],
-                                   debug ? 1 : 0, static_cast<long long>(binning_capacity), mask,
-                                   c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(dev.index()).stream());
+        const int rc = lr_backward_alpha(
+            static_cast<int>(P), static_cast<int>(degree), M, static_cast<int>(R), bg.p, static_cast<int>(W), static_cast<int>(H), m.p,
+            shc.p, col.p, sc.p, static_cast<float>(scale_modifier), rot.p, cov.p, view.p, proj.p, cam.p, static_cast<float>(tan_fovx),
+            static_cast<float>(tan_fovy), radii_c.data_ptr<int>(), static_cast<char*>(geomBuffer.data_ptr()),
+            static_cast<char*>(binningBuffer.data_ptr()), static_cast<char*>(imageBuffer.data_ptr()), gc.p, di.p ? gd.p : nullptr,
+            di.p, ga.p, ptr[0], nullptr, ptr[2], ptr[1], ptr[3], ptr[4], M ? ptr[5] : nullptr, ptr[6], ptr[7], debug ? 1 : 0,
+            static_cast<long long>(binning_capacity), mask, cur);
         if (rc < 0) raise_for(rc, "rasterize_gaussians_backward");
     }
     return result;
@@ -305,8 +295,8 @@ FwdResult rasterize_gaussians_raw(const at::Tensor& background, const at::Tensor
 }
 
 // result / accumulate order: (means2D, xyz, features_dc, features_rest, opacity, scaling, rotation)
-// dL_dout_depth / depth_image (keyword-only): depth mode as in rasterize_gaussians_backward (lr_backward_raw_depth); the
-// gradient of the depth output is used only when both are given.  dL_dout_alpha (keyword-only): lr_backward_raw_alpha.
+// dL_dout_depth / depth_image / dL_dout_alpha (keyword-only): as in rasterize_gaussians_backward; the gradient of the depth
+// output is used only when depth_image is given as well.
 std::vector<OptT> rasterize_gaussians_raw_backward(
     const at::Tensor& background, const at::Tensor& xyz, const at::Tensor& radii, const at::Tensor& features_dc,
     const OptT& features_rest, const at::Tensor& opacity_raw, const at::Tensor& scaling_raw, const at::Tensor& rotation_raw,
@@ -325,33 +315,17 @@ std::vector<OptT> rasterize_gaussians_raw_backward(
     const int64_t nrest = rest.p ? features_rest->size(1) : 0;
     const int M = 1 + static_cast<int>(nrest);
     TORCH_CHECK(accumulate.empty() || accumulate.size() == 7, "accumulate: seven entries or none");
-    auto fopt = at::TensorOptions().dtype(at::kFloat).device(dev);
     static const int kBit[7] = { 0, 4, 6, 6, 2, 7, 8 };                 // features_dc and features_rest share LR_ACC_SH
     const std::vector<int64_t> shapes[7] = { { P, 3 }, { P, 3 }, { P, 1, 3 }, { P, nrest, 3 }, { P, 1 }, { P, 3 }, { P, 4 } };
-    const bool have_acc = !accumulate.empty();
-    const bool feat_acc = have_acc && accumulate[2].has_value() && accumulate[2]->defined() &&
-                          (nrest == 0 || (accumulate[3].has_value() && accumulate[3]->defined()));
-    at::Tensor out[7];
+    const bool feat_acc = given(accumulate, 2) && (nrest == 0 || given(accumulate, 3));
     float* ptr[7];
     unsigned int mask = 0;
     std::vector<OptT> result(7);
     for (int k = 0; k < 7; k++) {
         const bool is_feat = (k == 2 || k == 3);
-        const bool acc = have_acc && (is_feat ? feat_acc : (accumulate[k].has_value() && accumulate[k]->defined())) &&
-                         !(k == 3 && nrest == 0);
-        if (acc) {
-            const at::Tensor& t = *accumulate[k];
-            int64_t n = 1;
-            for (int64_t d : shapes[k]) n *= d;
-            TORCH_CHECK(t.scalar_type() == at::kFloat && t.is_contiguous() && t.device() == dev && t.numel() == n,
-                        "accumulate tensors must be contiguous float32 of the gradient's size on ", dev);
-            mask |= 1u << kBit[k];
-            out[k] = t;
-        } else {
-            out[k] = at::empty(shapes[k], fopt);
-            if (!(is_feat && feat_acc)) result[k] = out[k];
-        }
-        ptr[k] = out[k].numel() ? out[k].data_ptr<float>() : nullptr;
+        const bool acc = (is_feat ? feat_acc : given(accumulate, k) != nullptr) && !(k == 3 && nrest == 0);
+        ptr[k] = grad_output(acc ? given(accumulate, k) : nullptr, shapes[k], kBit[k], dev, mask,
+                             (is_feat && feat_acc) ? nullptr : &result[k]);
     }
     // no_zero_fill: rows of Gaussians the view did not visit stay unwritten in the write-mode outputs (means2D excepted): for the
     // masked optimizer step (adam_step_masked below), which does not read them
@@ -362,44 +336,17 @@ std::vector<OptT> rasterize_gaussians_raw_backward(
                   view = f32(viewmatrix, dev, "viewmatrix"), proj = f32(projmatrix, dev, "projmatrix"), cam = f32(campos, dev, "campos"),
                   gc = f32(dL_dout_color, dev, "dL_dout_color"), gd = f32(dL_dout_depth, dev, "dL_dout_depth"),
                   di = f32(depth_image, dev, "depth_image"), ga = f32(dL_dout_alpha, dev, "dL_dout_alpha");
+        check_mode_images(H, W, gd, di, ga);
         const at::Tensor radii_c = radii.contiguous();
         hipStream_t cur = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(dev.index()).stream();
         ChainScope chain((mask & ~LR_ACC_NO_ZERO_FILL) != 0, dev.index(), cur);
-        if (ga.p != nullptr) {
-            TORCH_CHECK(ga.t.numel() == H * W, "dL_dout_alpha must have the alpha output's shape (1, H, W)");
-            TORCH_CHECK(!di.p || di.t.numel() == H * W, "depth_image must be the forward's depth output (1, H, W)");
-            TORCH_CHECK(!di.p || !gd.p || gd.t.numel() == H * W, "dL_dout_depth must have the depth output's shape (1, H, W)");
-            const int rc = lr_backward_raw_alpha(
-                static_cast<int>(P), static_cast<int>(degree), M, static_cast<int>(R), bg.p, static_cast<int>(W), static_cast<int>(H), x.p,
-                dc.p, rest.p, op.p, sc.p, static_cast<float>(scale_modifier), rot.p, view.p, proj.p, cam.p, static_cast<float>(tan_fovx),
-                static_cast<float>(tan_fovy), radii_c.data_ptr<int>(), static_cast<char*>(geomBuffer.data_ptr()),
-                static_cast<char*>(binningBuffer.data_ptr()), static_cast<char*>(imageBuffer.data_ptr()), gc.p, di.p ? gd.p : nullptr,
-                di.p, ga.p, ptr[0], ptr[4], ptr[1], ptr[2], nrest ? ptr[3] : nullptr, ptr[5], ptr[6], debug ? 1 : 0,
-                static_cast<long long>(binning_capacity), mask, cur);
-            if (rc < 0) raise_for(rc, "rasterize_gaussians_raw_backward");
-            return result;
-        }
-        if (di.p != nullptr) {
-            TORCH_CHECK(di.t.numel() == H * W, "depth_image must be the forward's depth output (1, H, W)");
-            TORCH_CHECK(!gd.p || gd.t.numel() == H * W, "dL_dout_depth must have the depth output's shape (1, H, W)");
-            const int rc = lr_backward_raw_depth(
-                static_cast<int>(P), static_cast<int>(degree), M, static_cast<int>(R), bg.p, static_cast<int>(W), static_cast<int>(H), x.p,
-                dc.p, rest.p, op.p, sc.p, static_cast<float>(scale_modifier), rot.p, view.p, proj.p, cam.p, static_cast<float>(tan_fovx),
-                static_cast<float>(tan_fovy), radii_c.data_ptr<int>(), static_cast<char*>(geomBuffer.data_ptr()),
-                static_cast<char*>(binningBuffer.data_ptr()), static_cast<char*>(imageBuffer.data_ptr()), gc.p, gd.p, di.p, ptr[0],
-                ptr[4], ptr[1], ptr[2], nrest ? ptr[3] : nullptr, ptr[5], ptr[6], debug ? 1 : 0,
-                static_cast<long long>(binning_capacity), mask, cur);
-            if (rc < 0) raise_for(rc, "rasterize_gaussians_raw_backward");
-            return result;
-        }
-        const int rc = lr_backward_raw(static_cast<int>(P), static_cast<int>(degree), M, static_cast<int>(R), bg.p, static_cast<int>(W),
-                                       static_cast<int>(H), x.p, dc.p, rest.p, op.p, sc.p, static_cast<float>(scale_modifier), rot.p,
-                                       view.p, proj.p, cam.p, static_cast<float>(tan_fovx), static_cast<float>(tan_fovy),
-                                       radii_c.data_ptr<int>(), static_cast<char*>(geomBuffer.data_ptr()),
-                                       static_cast<char*>(binningBuffer.data_ptr()), static_cast<char*>(imageBuffer.data_ptr()), gc.p,
-                                       ptr[0], ptr[4], ptr[1], ptr[2], nrest ? ptr[3] : nullptr, ptr[5], ptr[6], debug ? 1 : 0,
-                                       static_cast<long long>(binning_capacity), mask,
-                                       c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(dev.index()).stream());
+        const int rc = lr_backward_raw_alpha(
+            static_cast<int>(P), static_cast<int>(degree), M, static_cast<int>(R), bg.p, static_cast<int>(W), static_cast<int>(H), x.p,
+            dc.p, rest.p, op.p, sc.p, static_cast<float>(scale_modifier), rot.p, view.p, proj.p, cam.p, static_cast<float>(tan_fovx),
+            static_cast<float>(tan_fovy), radii_c.data_ptr<int>(), static_cast<char*>(geomBuffer.data_ptr()),
+            static_cast<char*>(binningBuffer.data_ptr()), static_cast<char*>(imageBuffer.data_ptr()), gc.p, di.p ? gd.p : nullptr,
+            di.p, ga.p, ptr[0], ptr[4], ptr[1], ptr[2], nrest ? ptr[3] : nullptr, ptr[5], ptr[6], debug ? 1 : 0,
+            static_cast<long long>(binning_capacity), mask, cur);
         if (rc < 0) raise_for(rc, "rasterize_gaussians_raw_backward");
     }
     return result;
@@ -557,11 +504,10 @@ struct RasterizeFn : public torch::autograd::Function<RasterizeFn> {
         const c10::Device dev = means3D.device();
         at::Tensor g_color = grad_out[0];
         if (!g_color.defined()) g_color = at::zeros({3, H, W}, at::TensorOptions().dtype(at::kFloat).device(dev));
+        // the output gradients that arrived and the depth image kept when the switch was on at the forward: the binding picks
+        // the mode from them (depth mode needs both depth ones)
         const OptT g_depth = grad_out[2].defined() ? OptT(grad_out[2]) : OptT();
-        // depth mode only when the switch was on at the forward AND a gradient reached the depth output; otherwise the
-        // default call (same kernels, same bits)
-        const OptT depth_image = (g_depth.has_value() && d.find("depth") != d.end()) ? OptT(d["depth"].toTensor()) : OptT();
-        // alpha mode only when the node has an alpha output and a gradient reached it (lr_backward_alpha)
+        const OptT depth_image = d.find("depth") != d.end() ? OptT(d["depth"].toTensor()) : OptT();
         const OptT g_alpha = (grad_out.size() > 4 && grad_out[4].defined()) ? OptT(grad_out[4]) : OptT();
         // config.set_fused_grad_accumulation: a leaf input whose .grad exists (contiguous float32, 16-byte aligned: the kernels
         // accumulate with 16-byte accesses) receives `+=` inside the kernel; its slot of the result stays undefined
@@ -616,8 +562,8 @@ std::vector<at::Tensor> rasterize_autograd(const at::Tensor& means3D, const at::
 // (RasterizeFn::backward above), in the same accumulate chain.  Returns an empty vector -- nothing done -- when an input does
 // not qualify: the caller takes the autograd path.  Otherwise (color, radii, depth, geom) with num_rendered in
 // last_num_rendered(); the images carry no grad_fn.
-// grad_depth (optional, [1,H,W]): dL/ddepth as well -- the backward is the depth-mode one (lr_backward_depth) fed with this
-// forward's own depth image; as the explicit opt-in it does not read config.set_depth_gradient.
+// grad_depth (optional, [1,H,W]): dL/ddepth as well -- the backward, always given this forward's own depth image, is then the
+// depth-mode one; as the explicit opt-in it does not read config.set_depth_gradient.
 // ------------------------------------------------------------------------------------------------------------------
 std::vector<at::Tensor> rasterize_view_step(const at::Tensor& means3D, const at::Tensor& means2D, const at::Tensor& sh,
                                             const at::Tensor& colors, const at::Tensor& opacities, const at::Tensor& scales,
@@ -643,8 +589,7 @@ std::vector<at::Tensor> rasterize_view_step(const at::Tensor& means3D, const at:
         acc[k] = g;
     }
     if (!grad_color.defined() || grad_color.dim() != 3 || grad_color.size(1) != H || grad_color.size(2) != W) return {};
-    const bool depth_mode = grad_depth.has_value() && grad_depth->defined();
-    if (depth_mode)
+    if (grad_depth.has_value() && grad_depth->defined())
         TORCH_CHECK(grad_depth->numel() == H * W && grad_depth->size(-1) == W && grad_depth->size(-2) == H,
                     "grad_depth must have the depth output's shape (1, H, W)");
     at::NoGradGuard no_grad;
@@ -654,9 +599,9 @@ std::vector<at::Tensor> rasterize_view_step(const at::Tensor& means3D, const at:
     if (means3D.size(0) != 0) {
         FusedBackwardScope fused_scope(true);
         (void)rasterize_gaussians_backward(bg, means3D, std::get<3>(r), colors, scales, rotations, scale_modifier, cov3D, viewmatrix,
-                                           projmatrix, tan_fovx, tan_fovy, grad_color, depth_mode ? grad_depth : OptT(), sh, degree,
-                                           campos, std::get<4>(r), std::get<0>(r), std::get<5>(r), std::get<6>(r), false,
-                                           binning_capacity, acc, true, depth_mode ? OptT(std::get<2>(r)) : OptT(), OptT());
+                                           projmatrix, tan_fovx, tan_fovy, grad_color, grad_depth, sh, degree, campos,
+                                           std::get<4>(r), std::get<0>(r), std::get<5>(r), std::get<6>(r), false,
+                                           binning_capacity, acc, true, std::get<2>(r), OptT());
     }
     return { std::get<1>(r), std::get<3>(r), std::get<2>(r), std::get<4>(r) };
 }

@@ -853,10 +853,10 @@ class ViewStreams:
 
 
 class ViewBatch:
-    """One C call per step for a fixed list of views (lr_views_accumulate): forward + backward of every view,
-    gradients accumulated in place, views alternated over internal HIP streams.  The per-view upstream
-    gradients dL/dcolor are given up front (a training loop that needs the rendered image to form its loss uses
-    the autograd op, optionally with ViewStreams, instead).
+    """One C call per step for a fixed list of views (lr_views_accumulate_depth, which with NULL depth gradients is
+    lr_views_accumulate): forward + backward of every view, gradients accumulated in place, views alternated over internal
+    HIP streams.  The per-view upstream gradients dL/dcolor are given up front (a training loop that needs the rendered
+    image to form its loss uses the autograd op, optionally with ViewStreams, instead).
 
     cams: objects with world_view_transform, full_proj_transform, camera_center (device tensors), FoVx, FoVy,
           image_width, image_height (e.g. cameras.MiniCam); all views share one resolution.
@@ -912,11 +912,9 @@ class ViewBatch:
         self.lambda_dssim = float(lambda_dssim)
         self._grads = ptr_array(grad_colors if not self.train else targets)     # per-view dL/dcolor, or target images
         self.depth_weight = (1.0 if depth_weight is None else float(depth_weight)) if self.train_depth else 0.0
-        # per-view dL/ddepth or depth targets; without either but with `depths`: NULL entries (the colour-only backward)
-        self._dgrads = ptr_array(grad_depths if grad_depths is not None else depth_targets) \
-            if (grad_depths is not None or self.train_depth) else None
-        if self._dgrads is None and depths is not None:
-            self._dgrads = (ctypes.c_void_p * self.n)()
+        # per-view dL/ddepth or depth targets; without either: NULL entries (lr_views_accumulate_depth's colour-only backward)
+        depth_in = grad_depths if grad_depths is not None else depth_targets
+        self._dgrads = ptr_array(depth_in) if depth_in is not None else (ctypes.c_void_p * self.n)()
         self.depths = list(depths) if depths is not None else None
         self._depths = (ctypes.c_void_p * self.n)(*[t.data_ptr() for t in self.depths]) if depths is not None else None
         self.losses = torch.zeros((self.n, 4 if self.train_depth else 3), dtype=torch.float32, device=self.device) \
@@ -926,6 +924,11 @@ class ViewBatch:
         self._keep = keep
         self._ws = None
         self._ws_key = None
+        L = self.L
+        self._ws_bytes, self._ws_check = (
+            (L.lr_views_train_depth_workspace_bytes, L.lr_views_train_depth_check) if self.train_depth else
+            (L.lr_views_train_workspace_bytes, L.lr_views_train_check) if self.train else
+            (L.lr_views_workspace_bytes, L.lr_views_check))
 
     def _check_depth_args(self, grad_colors, targets, grad_depths, depth_targets, depth_weight, depths):
         import math
@@ -961,10 +964,7 @@ class ViewBatch:
         P, M = int(means3D.shape[0]), int(shs.shape[1])
         key = (P, self.capacity, self.n_streams)      # the workspace is sized per stream slot: set_streams() re-allocates
         if self._ws_key != key:
-            size_fn = self.L.lr_views_train_workspace_bytes if self.train else self.L.lr_views_workspace_bytes
-            if self.train_depth:
-                size_fn = self.L.lr_views_train_depth_workspace_bytes
-            nbytes = size_fn(P, self.W, self.H, self.capacity, self.n_streams)
+            nbytes = self._ws_bytes(P, self.W, self.H, self.capacity, self.n_streams)
             self._ws = torch.empty((nbytes,), dtype=torch.uint8, device=self.device)
             self._ws_key = key
         for t in (means3D, opacities, scales, rotations, shs, *acc.values()):
@@ -998,38 +998,24 @@ class ViewBatch:
             if rc < 0:
                 self._lib.raise_for(rc, "lr_views_train_accumulate")
             return
-        if self._dgrads is not None:
-            rc = self.L.lr_views_accumulate_depth(
-                self.n, self._views, self._projs, self._campos, self._tanx, self._tany, P, self.degree, M,
-                self.bg.data_ptr(), self.W, self.H, means3D.data_ptr(), shs.data_ptr(), None, opacities.data_ptr(),
-                scales.data_ptr(), self.scale_modifier, rotations.data_ptr(), None, self._grads, self._dgrads, None,
-                self._depths, None, acc["means2D"].data_ptr(), acc["opacity"].data_ptr(), None, acc["means3D"].data_ptr(),
-                None, acc["sh"].data_ptr(), acc["scales"].data_ptr(), acc["rotations"].data_ptr(),
-                self._ws.data_ptr(), self._ws.numel(), self.capacity, self.n_streams, stream)
-            if rc < 0:
-                self._lib.raise_for(rc, "lr_views_accumulate_depth")
-            return
-        rc = self.L.lr_views_accumulate(
+        rc = self.L.lr_views_accumulate_depth(
             self.n, self._views, self._projs, self._campos, self._tanx, self._tany, P, self.degree, M,
             self.bg.data_ptr(), self.W, self.H, means3D.data_ptr(), shs.data_ptr(), None, opacities.data_ptr(),
-            scales.data_ptr(), self.scale_modifier, rotations.data_ptr(), None, self._grads, None, None,
-            acc["means2D"].data_ptr(), acc["opacity"].data_ptr(), None, acc["means3D"].data_ptr(), None,
-            acc["sh"].data_ptr(), acc["scales"].data_ptr(), acc["rotations"].data_ptr(),
+            scales.data_ptr(), self.scale_modifier, rotations.data_ptr(), None, self._grads, self._dgrads, None,
+            self._depths, None, acc["means2D"].data_ptr(), acc["opacity"].data_ptr(), None, acc["means3D"].data_ptr(),
+            None, acc["sh"].data_ptr(), acc["scales"].data_ptr(), acc["rotations"].data_ptr(),
             self._ws.data_ptr(), self._ws.numel(), self.capacity, self.n_streams, stream)
         if rc < 0:
-            self._lib.raise_for(rc, "lr_views_accumulate")
+            self._lib.raise_for(rc, "lr_views_accumulate_depth")
 
     def check(self):
         """Synchronise and raise if any view of the previous run() overflowed the binning capacity."""
         if self._ws is None:
             return
         P = self._ws_key[0]
-        check = self.L.lr_views_train_check if self.train else self.L.lr_views_check
-        if self.train_depth:
-            check = self.L.lr_views_train_depth_check
         with torch.cuda.device(self.device):
-            rc = check(self._ws.data_ptr(), P, self.W, self.H, self.capacity, self.n_streams,
-                       torch.cuda.current_stream(self.device).cuda_stream)
+            rc = self._ws_check(self._ws.data_ptr(), P, self.W, self.H, self.capacity, self.n_streams,
+                                torch.cuda.current_stream(self.device).cuda_stream)
         if rc < 0:
             self._lib.raise_for(rc, "lr_views_check")
 

@@ -127,12 +127,11 @@ class _RasterizeGaussians(torch.autograd.Function):
                         and g.data_ptr() % 16 == 0:      # the kernels accumulate with 16-byte accesses; else: dense path
                     accumulate_into[name] = g
         try:
-            # depth mode only with the switch on at the forward AND a gradient for depth; otherwise today's call
-            depth_image = ctx.depth_image if grad_depth is not None else None
+            # the binding picks the mode: depth mode needs the kept depth image (switch on at the forward) and grad_depth
             (grad_means2D, grad_colors_precomp, grad_opacities, grad_means3D, grad_cov3Ds_precomp, grad_sh,
              grad_scales, grad_rotations) = _C.rasterize_gaussians_backward(
                 *args, binning_capacity=ctx.binning_capacity, accumulate_into=accumulate_into, skip_unused=True,
-                depth_image=depth_image, dL_dout_alpha=grad_alpha)
+                depth_image=ctx.depth_image, dL_dout_alpha=grad_alpha)
         except Exception:
             if rs.debug:
                 _snapshot(args, "snapshot_bw.dump")
@@ -246,11 +245,8 @@ class _RasterizeGaussiansRaw(torch.autograd.Function):
         xyz, features_dc, features_rest, opacity, scaling, rotation, radii, geom, binning, img = ctx.saved_tensors
         if grad_out_color is None:
             grad_out_color = torch.zeros((3, rs.image_height, rs.image_width), dtype=torch.float32, device=xyz.device)
-        # depth mode (config.set_depth_gradient at the forward, and a gradient for depth): lr_backward_raw_depth
-        depth = dict(dL_dout_depth=grad_depth, depth_image=ctx.depth_image) \
-            if (grad_depth is not None and ctx.depth_image is not None) else {}
-        if grad_alpha is not None:                      # alpha mode: lr_backward_raw_alpha (with or without depth mode)
-            depth["dL_dout_alpha"] = grad_alpha
+        # what arrived, as _RasterizeGaussians.backward: the binding picks the depth / alpha mode from it
+        modes = dict(dL_dout_depth=grad_depth, depth_image=ctx.depth_image, dL_dout_alpha=grad_alpha)
         accumulate_into = None
         if ctx.leaf_inputs is not None:
             def leaf_grad(t):
@@ -274,13 +270,13 @@ class _RasterizeGaussiansRaw(torch.autograd.Function):
             g = _C.rasterize_gaussians_raw_backward(
                 rs.bg, xyz, radii, features_dc, features_rest, opacity, scaling, rotation, rs.scale_modifier, rs.viewmatrix,
                 rs.projmatrix, rs.tanfovx, rs.tanfovy, grad_out_color, rs.sh_degree, rs.campos, geom, ctx.num_rendered,
-                binning, img, False, binning_capacity=ctx.binning_capacity, no_zero_fill=True, **depth)
+                binning, img, False, binning_capacity=ctx.binning_capacity, no_zero_fill=True, **modes)
             opt.apply_armed_step(geom, [xyz, features_dc, features_rest, opacity, scaling, rotation], list(g[1:]))
             return None, g[0], None, None, None, None, None, None, None
         g = _C.rasterize_gaussians_raw_backward(
             rs.bg, xyz, radii, features_dc, features_rest, opacity, scaling, rotation, rs.scale_modifier, rs.viewmatrix,
             rs.projmatrix, rs.tanfovx, rs.tanfovy, grad_out_color, rs.sh_degree, rs.campos, geom, ctx.num_rendered,
-            binning, img, rs.debug, binning_capacity=ctx.binning_capacity, accumulate_into=accumulate_into, **depth)
+            binning, img, rs.debug, binning_capacity=ctx.binning_capacity, accumulate_into=accumulate_into, **modes)
         g_means2D, g_xyz, g_dc, g_rest, g_op, g_sc, g_rot = g
         return g_xyz, g_means2D, g_dc, g_rest, g_op, g_sc, g_rot, None, None
 

@@ -1,7 +1,7 @@
 """Differentiable alpha output (return_alpha, lr_render_alpha / lr_backward_alpha): the contract's CPU side.
 
-tests/alpha_grad_oracle.py restates the render loop with alpha = 1 - T_final as an output.  These tests check that
-restatement against tests/depth_grad_oracle.py (same colour, depth and radii), against the coverage render and against float64
+tests/grad_oracle.py restates the render loop with alpha = 1 - T_final as an output (alpha=True).  These tests check that
+output against the same render without it (same colour, depth and radii), against the coverage render and against float64
 central differences, the per-layer closed form d alpha_pix / d alpha_i = T_final / (1 - alpha_i), the blend backward's
 recursion for the coverage channel (the start values of A the alpha-mode kernels use, whole lists and segment starts), and
 that the new C-ABI entry points are declared and exported."""
@@ -13,7 +13,7 @@ import numpy as np
 import torch
 
 from luciddreamer_amd import cameras, synthetic
-from tests import alpha_grad_oracle, depth_grad_oracle, helpers as hp
+from tests import grad_oracle, helpers as hp
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -32,22 +32,23 @@ def _params(cloud, opacity=None):
     return p
 
 
-def _render(mod, cam, p, degree, bg, **kw):
+def _render(cam, p, degree, bg, **kw):
     tfx, tfy = hp.tan_fov(cam)
-    return mod.render(p["means3D"], p["opacities"], cam.world_view_transform, cam.full_proj_transform, cam.camera_center,
-                      tfx, tfy, cam.image_height, cam.image_width, bg, scales=p["scales"], rotations=p["rotations"],
-                      shs=p["shs"], degree=degree, means2D=p["means2D"], **kw)
+    return grad_oracle.render(p["means3D"], p["opacities"], cam.world_view_transform, cam.full_proj_transform,
+                              cam.camera_center, tfx, tfy, cam.image_height, cam.image_width, bg, scales=p["scales"],
+                              rotations=p["rotations"], shs=p["shs"], degree=degree, means2D=p["means2D"], **kw)
 
 
 def test_colour_depth_radii_are_depth_oracle_s_and_alpha_is_coverage():
-    """Colour, depth and radii bit-equal to depth_grad_oracle; alpha in [0, 1], 0 where nothing is drawn, equal to 1 - T_final
-    -- which is also the coverage render (colours 1, background 0) -- and its colour gradients those of depth_grad_oracle."""
+    """Colour, depth and radii bit-equal to the depth oracle's (the same render without alpha=True), and so are the colour
+    gradients; alpha in [0, 1], 0 where nothing is drawn, equal to 1 - T_final -- which is also the coverage render (colours 1,
+    background 0)."""
     cam, cloud = _scene(300, 64, 48, 3)
     bg = torch.tensor([0.1, 0.2, 0.3], dtype=torch.float64)
     gc = torch.randn(3, 48, 64, generator=torch.Generator().manual_seed(1), dtype=torch.float64)
     p0, p1 = _params(cloud), _params(cloud)
-    c0, d0, r0 = _render(depth_grad_oracle, cam, p0, 3, bg)
-    c1, d1, a1, r1 = _render(alpha_grad_oracle, cam, p1, 3, bg)
+    c0, d0, r0 = _render(cam, p0, 3, bg)
+    c1, d1, a1, r1 = _render(cam, p1, 3, bg, alpha=True)
     assert torch.equal(c0, c1) and torch.equal(d0, d1) and torch.equal(r0, r1)
     (c0 * gc).sum().backward()
     (c1 * gc).sum().backward()
@@ -59,13 +60,13 @@ def test_colour_depth_radii_are_depth_oracle_s_and_alpha_is_coverage():
     # the coverage channel: colours 1, background 0
     tfx, tfy = hp.tan_fov(cam)
     q = _params(cloud)
-    cov_img, _, _ = depth_grad_oracle.render(q["means3D"], q["opacities"], cam.world_view_transform, cam.full_proj_transform,
-                                             cam.camera_center, tfx, tfy, 48, 64, torch.zeros(3, dtype=torch.float64),
-                                             scales=q["scales"], rotations=q["rotations"],
-                                             colors_precomp=torch.ones(300, 3, dtype=torch.float64))
+    cov_img, _, _ = grad_oracle.render(q["means3D"], q["opacities"], cam.world_view_transform, cam.full_proj_transform,
+                                       cam.camera_center, tfx, tfy, 48, 64, torch.zeros(3, dtype=torch.float64),
+                                       scales=q["scales"], rotations=q["rotations"],
+                                       colors_precomp=torch.ones(300, 3, dtype=torch.float64))
     assert float((cov_img[0:1].detach() - a1).abs().max()) <= 1e-12
     # 1 - T_final per pixel, from the applied layers
-    _, _, a2, _, layers = _render(alpha_grad_oracle, cam, _params(cloud), 3, bg, with_layers=True)
+    _, _, a2, _, layers = _render(cam, _params(cloud), 3, bg, alpha=True, with_layers=True)
     for t in layers:
         ys, xs = t["pix"]
         inside = (ys < 48) & (xs < 64)
@@ -83,7 +84,7 @@ def test_alpha_gradient_matches_central_differences():
     bg = torch.zeros(3, dtype=torch.float64)
     ga = torch.randn(1, H, W, generator=torch.Generator().manual_seed(2), dtype=torch.float64)
     p = _params(cloud, op)
-    _, _, alpha, radii = _render(alpha_grad_oracle, cam, p, 0, bg)
+    _, _, alpha, radii = _render(cam, p, 0, bg, alpha=True)
     assert int((radii > 0).sum()) >= 5 and float((alpha > 0).double().mean()) > 0.2
     (alpha * ga).sum().backward()
 
@@ -91,7 +92,7 @@ def test_alpha_gradient_matches_central_differences():
         q = {k: v.detach().clone() for k, v in p.items()}
         q[name].view(-1)[flat_index] += delta
         with torch.no_grad():
-            _, _, a, _ = _render(alpha_grad_oracle, cam, q, 0, bg)
+            _, _, a, _ = _render(cam, q, 0, bg, alpha=True)
         return float((a * ga).sum())
 
     eps = 1e-6
@@ -118,14 +119,14 @@ def test_per_layer_closed_form():
     cloud = dict(cloud)
     cloud["scales"] = cloud["scales"] * 4.0
     bg = torch.zeros(3, dtype=torch.float64)
-    _, _, alpha0, _, layers = _render(alpha_grad_oracle, cam, _params(cloud, op), 0, bg, with_layers=True)
+    _, _, alpha0, _, layers = _render(cam, _params(cloud, op), 0, bg, alpha=True, with_layers=True)
     checked = 0
     for t in layers:
         n_applied = t["contrib"].sum(dim=1)
         for k in torch.nonzero(n_applied >= 3).flatten()[:3].tolist():
             y, x = int(t["pix"][0][k]), int(t["pix"][1][k])
             p = _params(cloud, op)
-            _, _, alpha, _ = _render(alpha_grad_oracle, cam, p, 0, bg)
+            _, _, alpha, _ = _render(cam, p, 0, bg, alpha=True)
             alpha[0, y, x].backward()
             expect = torch.zeros(P, dtype=torch.float64)
             for j in torch.nonzero(t["contrib"][k]).flatten().tolist():

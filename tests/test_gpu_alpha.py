@@ -1,6 +1,6 @@
 """Differentiable alpha output on the GPU (return_alpha -> lr_render_alpha, lr_backward_alpha / lr_backward_raw_alpha).
 
-The forward's alpha against the float64 restatement tests/alpha_grad_oracle.py, gradients of losses on alpha (alone, and with
+The forward's alpha against the float64 restatement tests/grad_oracle.py, gradients of losses on alpha (alone, and with
 colour and depth mode) against its autograd, on every blend-backward shape and variant that reaches the alpha-mode kernels, a
 C3-size consistency check (list segments against whole lists, against the two-render workaround, linearity), the bit guarantees,
 memory, and ViewStreams.run_view with an alpha-requesting forward."""
@@ -12,7 +12,7 @@ import torch
 import torch.nn as nn
 
 from luciddreamer_amd import _lib, cameras, config, synthetic
-from tests import alpha_grad_oracle, helpers as hp
+from tests import grad_oracle, helpers as hp
 
 pytestmark = pytest.mark.gpu
 
@@ -84,9 +84,10 @@ def _oracle(cloud, cam, degree, bg, gc=None, gd=None, ga=None, colors_precomp=No
     shs = leaf(cloud["shs"]) if colors_precomp is None else None
     m2 = torch.zeros_like(m3, requires_grad=True)
     tfx, tfy = hp.tan_fov(cam)
-    col, dep, alpha, radii = alpha_grad_oracle.render(
+    col, dep, alpha, radii = grad_oracle.render(
         m3, op, cam.world_view_transform, cam.full_proj_transform, cam.camera_center, tfx, tfy, cam.image_height,
-        cam.image_width, bg, scales=sc, rotations=rot, cov3D_precomp=cov, shs=shs, degree=degree, colors_precomp=cols, means2D=m2)
+        cam.image_width, bg, scales=sc, rotations=rot, cov3D_precomp=cov, shs=shs, degree=degree, colors_precomp=cols, means2D=m2,
+        alpha=True)
     res = dict(color=col.detach(), depth=dep.detach(), alpha=alpha.detach(), radii=radii)
     loss = None
     for t, g in ((col, gc), (dep, gd), (alpha, ga)):

@@ -1,6 +1,6 @@
 """Differentiable depth output on the GPU (config.set_depth_gradient -> lr_backward_depth / lr_backward_raw_depth).
 
-Gradients of losses on `depth` against the float64 restatement tests/depth_grad_oracle.py (sizes bounded by that Python
+Gradients of losses on `depth` against the float64 restatement tests/grad_oracle.py (sizes bounded by that Python
 oracle), the variants that reach the depth-mode kernels (strict parity, the Python debug node, fused accumulation, the raw
 path, the armed optimizer step), the switch's bit-identity guarantees, repeatability, and a C3-size consistency check."""
 from types import SimpleNamespace
@@ -11,7 +11,7 @@ import torch
 import torch.nn as nn
 
 from luciddreamer_amd import cameras, config, synthetic
-from tests import depth_grad_oracle, helpers as hp
+from tests import grad_oracle, helpers as hp
 
 pytestmark = pytest.mark.gpu
 
@@ -50,9 +50,9 @@ def _oracle(cloud, cam, degree, bg, gc, gd, colors_precomp=None, cov3D_precomp=N
     shs = leaf(cloud["shs"]) if colors_precomp is None else None
     m2 = torch.zeros_like(m3, requires_grad=True)
     tfx, tfy = hp.tan_fov(cam)
-    col, dep, _ = depth_grad_oracle.render(m3, op, cam.world_view_transform, cam.full_proj_transform, cam.camera_center, tfx, tfy,
-                                           cam.image_height, cam.image_width, bg, scales=sc, rotations=rot, cov3D_precomp=cov,
-                                           shs=shs, degree=degree, colors_precomp=cols, means2D=m2)
+    col, dep, _ = grad_oracle.render(m3, op, cam.world_view_transform, cam.full_proj_transform, cam.camera_center, tfx, tfy,
+                                     cam.image_height, cam.image_width, bg, scales=sc, rotations=rot, cov3D_precomp=cov,
+                                     shs=shs, degree=degree, colors_precomp=cols, means2D=m2)
     ((col * gc.double()).sum() + (dep * gd.double()).sum()).backward()
     P = m3.shape[0]
     z = lambda t, shape: np.zeros(shape) if (t is None or t.grad is None) else t.grad.numpy()
