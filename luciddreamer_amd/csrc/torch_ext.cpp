@@ -139,6 +139,22 @@ FwdResult empty_forward(const c10::Device& dev, int64_t H, int64_t W)
                      at::empty({0}, b), at::empty({0}, b), at::empty({0}, b));
 }
 
+// The outputs and scratch of one forward (rasterize_points.cu:68-70): the images are fully written by the library, no zero fill
+struct FwdOutputs {
+    at::Tensor color, depth, radii;
+    Scratch geom, binning, img;
+    FwdOutputs(const c10::Device& dev, int64_t P, int64_t H, int64_t W)
+        : color(at::empty({3, H, W}, at::TensorOptions().dtype(at::kFloat).device(dev))), depth(at::empty({1, H, W}, color.options())),
+          radii(at::empty({P}, color.options().dtype(at::kInt))), geom(dev), binning(dev), img(dev) {}
+    // rc of lr_forward / lr_forward_raw: num_rendered, LR_NUM_RENDERED_ON_DEVICE (async mode) or an error
+    FwdResult result(int rc, const char* what)
+    {
+        if (rc < 0 && rc != LR_NUM_RENDERED_ON_DEVICE) raise_for(rc, what);
+        if (!binning.t.defined()) binning.t = at::empty({0}, at::TensorOptions().dtype(at::kByte).device(binning.dev));
+        return FwdResult(rc, color, depth, radii, geom.t, binning.t, img.t);
+    }
+};
+
 FwdResult rasterize_gaussians(const at::Tensor& background, const at::Tensor& means3D, const OptT& colors, const at::Tensor& opacity,
                               const OptT& scales, const OptT& rotations, double scale_modifier, const OptT& cov3D_precomp,
                               const at::Tensor& viewmatrix, const at::Tensor& projmatrix, double tan_fovx, double tan_fovy,
@@ -151,24 +167,18 @@ FwdResult rasterize_gaussians(const at::Tensor& background, const at::Tensor& me
     const int64_t P = means3D.size(0), H = image_height, W = image_width;
     if (P == 0) return empty_forward(dev, H, W);
     c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
-    auto fopt = at::TensorOptions().dtype(at::kFloat).device(dev);
-    at::Tensor out_color = at::empty({3, H, W}, fopt);          // fully written by the library: no zero fill (:68-70)
-    at::Tensor out_depth = at::empty({1, H, W}, fopt);
-    at::Tensor radii = at::empty({P}, fopt.dtype(at::kInt));
+    FwdOutputs out(dev, P, H, W);
     const Arg m = f32(means3D, dev, "means3D"), bg = f32(background, dev, "background"), col = f32(colors, dev, "colors_precomp"),
               op = f32(opacity, dev, "opacities"), sc = f32(scales, dev, "scales"), rot = f32(rotations, dev, "rotations"),
               cov = f32(cov3D_precomp, dev, "cov3D_precomp"), view = f32(viewmatrix, dev, "viewmatrix"),
               proj = f32(projmatrix, dev, "projmatrix"), cam = f32(campos, dev, "campos"), shc = f32(sh, dev, "sh");
-    Scratch geom(dev), binning(dev), img(dev);
-    const int rc = lr_forward(scratch_alloc, &geom, scratch_alloc, &binning, scratch_alloc, &img, static_cast<int>(P),
+    const int rc = lr_forward(scratch_alloc, &out.geom, scratch_alloc, &out.binning, scratch_alloc, &out.img, static_cast<int>(P),
                               static_cast<int>(degree), sh_coeffs(sh), bg.p, static_cast<int>(W), static_cast<int>(H), m.p, shc.p,
                               col.p, op.p, sc.p, static_cast<float>(scale_modifier), rot.p, cov.p, view.p, proj.p, cam.p,
                               static_cast<float>(tan_fovx), static_cast<float>(tan_fovy), prefiltered ? 1 : 0,
-                              out_color.data_ptr<float>(), out_depth.data_ptr<float>(), radii.data_ptr<int>(), debug ? 1 : 0,
+                              out.color.data_ptr<float>(), out.depth.data_ptr<float>(), out.radii.data_ptr<int>(), debug ? 1 : 0,
                               static_cast<long long>(binning_capacity), c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(dev.index()).stream());
-    if (rc < 0 && rc != LR_NUM_RENDERED_ON_DEVICE) raise_for(rc, "rasterize_gaussians");
-    if (!binning.t.defined()) binning.t = at::empty({0}, at::TensorOptions().dtype(at::kByte).device(dev));
-    return FwdResult(rc, out_color, out_depth, radii, geom.t, binning.t, img.t);
+    return out.result(rc, "rasterize_gaussians");
 }
 
 // One gradient output of a backward binding: `acc` (a caller tensor, if given) receives `+=` in place -- its LR_ACC_* `bit` is set
@@ -276,22 +286,17 @@ FwdResult rasterize_gaussians_raw(const at::Tensor& background, const at::Tensor
     c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
     const Arg rest = f32(features_rest, dev, "features_rest");
     const int M = 1 + (rest.p ? static_cast<int>(features_rest->size(1)) : 0);
-    auto fopt = at::TensorOptions().dtype(at::kFloat).device(dev);
-    at::Tensor out_color = at::empty({3, H, W}, fopt), out_depth = at::empty({1, H, W}, fopt);
-    at::Tensor radii = at::empty({P}, fopt.dtype(at::kInt));
+    FwdOutputs out(dev, P, H, W);
     const Arg bg = f32(background, dev, "background"), x = f32(xyz, dev, "xyz"), dc = f32(features_dc, dev, "features_dc"),
               op = f32(opacity_raw, dev, "opacity"), sc = f32(scaling_raw, dev, "scaling"), rot = f32(rotation_raw, dev, "rotation"),
               view = f32(viewmatrix, dev, "viewmatrix"), proj = f32(projmatrix, dev, "projmatrix"), cam = f32(campos, dev, "campos");
-    Scratch geom(dev), binning(dev), img(dev);
-    const int rc = lr_forward_raw(scratch_alloc, &geom, scratch_alloc, &binning, scratch_alloc, &img, static_cast<int>(P),
+    const int rc = lr_forward_raw(scratch_alloc, &out.geom, scratch_alloc, &out.binning, scratch_alloc, &out.img, static_cast<int>(P),
                                   static_cast<int>(degree), M, bg.p, static_cast<int>(W), static_cast<int>(H), x.p, dc.p, rest.p, op.p,
                                   sc.p, static_cast<float>(scale_modifier), rot.p, view.p, proj.p, cam.p, static_cast<float>(tan_fovx),
-                                  static_cast<float>(tan_fovy), out_color.data_ptr<float>(), out_depth.data_ptr<float>(),
-                                  radii.data_ptr<int>(), debug ? 1 : 0, static_cast<long long>(binning_capacity),
+                                  static_cast<float>(tan_fovy), out.color.data_ptr<float>(), out.depth.data_ptr<float>(),
+                                  out.radii.data_ptr<int>(), debug ? 1 : 0, static_cast<long long>(binning_capacity),
                                   c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(dev.index()).stream());
-    if (rc < 0 && rc != LR_NUM_RENDERED_ON_DEVICE) raise_for(rc, "rasterize_gaussians_raw");
-    if (!binning.t.defined()) binning.t = at::empty({0}, at::TensorOptions().dtype(at::kByte).device(dev));
-    return FwdResult(rc, out_color, out_depth, radii, geom.t, binning.t, img.t);
+    return out.result(rc, "rasterize_gaussians_raw");
 }
 
 // result / accumulate order: (means2D, xyz, features_dc, features_rest, opacity, scaling, rotation)
@@ -431,6 +436,19 @@ at::Tensor render_alpha(const at::Tensor& imageBuffer, int64_t H, int64_t W)
 // ------------------------------------------------------------------------------------------------------------------
 thread_local int64_t g_last_num_rendered = 0;
 
+// Fused gradient accumulation (config.set_fused_grad_accumulation): the .grad of `t` if the backward kernels may add into it in
+// place -- `t` a non-empty leaf that requires a gradient, its .grad contiguous float32 on `dev` and 16-byte aligned (the kernels
+// accumulate with 16-byte accesses) --, else none.  rasterizer.py _fusable_grad is the same rule.
+OptT fusable_grad(const at::Tensor& t, const c10::Device& dev)
+{
+    if (!t.defined() || t.numel() == 0 || !t.requires_grad() || !t.is_leaf()) return OptT();
+    const at::Tensor& g = t.grad();
+    if (!g.defined() || !g.is_contiguous() || g.scalar_type() != at::kFloat || g.device() != dev ||
+        reinterpret_cast<uintptr_t>(g.data_ptr()) % 16 != 0)
+        return OptT();
+    return OptT(g);
+}
+
 using torch::autograd::AutogradContext;
 using torch::autograd::variable_list;
 
@@ -509,22 +527,14 @@ struct RasterizeFn : public torch::autograd::Function<RasterizeFn> {
         const OptT g_depth = grad_out[2].defined() ? OptT(grad_out[2]) : OptT();
         const OptT depth_image = d.find("depth") != d.end() ? OptT(d["depth"].toTensor()) : OptT();
         const OptT g_alpha = (grad_out.size() > 4 && grad_out[4].defined()) ? OptT(grad_out[4]) : OptT();
-        // config.set_fused_grad_accumulation: a leaf input whose .grad exists (contiguous float32, 16-byte aligned: the kernels
-        // accumulate with 16-byte accesses) receives `+=` inside the kernel; its slot of the result stays undefined
+        // config.set_fused_grad_accumulation: a leaf input with a fusable .grad receives `+=` inside the kernel; its slot of the
+        // result stays undefined
         const bool fused = d["fused"].toBool();
-        auto leaf_grad = [&](const at::Tensor& t) -> OptT {
-            if (!fused || !t.defined() || t.numel() == 0 || !t.requires_grad() || !t.is_leaf()) return OptT();
-            const at::Tensor& g = t.grad();
-            if (!g.defined() || !g.is_contiguous() || g.scalar_type() != at::kFloat || g.device() != dev ||
-                reinterpret_cast<uintptr_t>(g.data_ptr()) % 16 != 0)
-                return OptT();
-            return OptT(g);
-        };
         // order of rasterize_gaussians_backward's result: means2D, colors, opacity, means3D, cov3D, sh, scales, rotations
         std::vector<OptT> acc;
         if (fused)
-            acc = { leaf_grad(means2D), leaf_grad(colors), leaf_grad(opacities), leaf_grad(means3D), leaf_grad(cov3D), leaf_grad(sh),
-                    leaf_grad(scales), leaf_grad(rotations) };
+            acc = { fusable_grad(means2D, dev), fusable_grad(colors, dev), fusable_grad(opacities, dev), fusable_grad(means3D, dev),
+                    fusable_grad(cov3D, dev), fusable_grad(sh, dev), fusable_grad(scales, dev), fusable_grad(rotations, dev) };
         FusedBackwardScope fused_scope(fused);
         const std::vector<OptT> g = rasterize_gaussians_backward(
             bg, means3D, d["radii"].toTensor(), colors, scales, rotations, d["scale_modifier"].toDouble(), cov3D, viewmatrix,
@@ -557,8 +567,8 @@ std::vector<at::Tensor> rasterize_autograd(const at::Tensor& means3D, const at::
 // with grad_output: a fixed upstream gradient, a loss formed elsewhere): no autograd node is built and nothing returns to the
 // interpreter between the two halves -- the node, its saved variables and the call of its backward were ~100 us of a view's
 // ~135 us of host time at 1080p, against ~35 us for the ten launches themselves (profiles/r06i_host_profile_dropin.txt).
-// Every differentiable input that requires a gradient must be a LEAF whose .grad exists (contiguous float32, 16-byte
-// aligned): the kernels add into it in place, exactly what the compiled node does under fused gradient accumulation
+// Every differentiable input that requires a gradient must be a leaf with a fusable .grad (fusable_grad above) of its own
+// size: the kernels add into it in place, exactly what the compiled node does under fused gradient accumulation
 // (RasterizeFn::backward above), in the same accumulate chain.  Returns an empty vector -- nothing done -- when an input does
 // not qualify: the caller takes the autograd path.  Otherwise (color, radii, depth, geom) with num_rendered in
 // last_num_rendered(); the images carry no grad_fn.
@@ -581,12 +591,8 @@ std::vector<at::Tensor> rasterize_view_step(const at::Tensor& means3D, const at:
     for (int k = 0; k < 8; k++) {
         const at::Tensor& t = *in[k];
         if (!t.defined() || t.numel() == 0 || !t.requires_grad()) continue;          // no gradient wanted: written to a scratch tensor
-        if (!t.is_leaf()) return {};
-        const at::Tensor& g = t.grad();
-        if (!g.defined() || !g.is_contiguous() || g.scalar_type() != at::kFloat || g.device() != dev || g.numel() != t.numel() ||
-            reinterpret_cast<uintptr_t>(g.data_ptr()) % 16 != 0)
-            return {};
-        acc[k] = g;
+        acc[k] = fusable_grad(t, dev);
+        if (!acc[k] || acc[k]->numel() != t.numel()) return {};       // (a .grad can be resized in place: resize_)
     }
     if (!grad_color.defined() || grad_color.dim() != 3 || grad_color.size(1) != H || grad_color.size(2) != W) return {};
     if (grad_depth.has_value() && grad_depth->defined())

@@ -18,34 +18,30 @@ from .sh import colors_from_shs
 DEFAULT_OPT = SimpleNamespace(debug=False, compute_cov3D_python=False, convert_SHs_python=False)
 
 
-def render(viewpoint_camera, pc, opt=DEFAULT_OPT, bg_color=None, scaling_modifier=1.0, override_color=None,
-           render_only=False, return_alpha=False):
-    """Returns {"render", "viewspace_points", "visibility_filter", "radii", "depth"} (or render/depth only); with
-    return_alpha the dict gains "alpha", the accumulated opacity 1 - T_final (1, H, W), differentiable."""
-    xyz = pc.get_xyz
+def _view_setup(viewpoint_camera, pc, xyz, opt, bg_color, scaling_modifier):
+    """(screenspace_points, settings) of one camera for render / render_raw: the screen-space points are a zero tensor whose
+    gradient is the screen-space (NDC-scaled) mean gradient used by densification."""
     if bg_color is None:
         bg_color = torch.zeros(3, dtype=torch.float32, device=xyz.device)
-    # zero tensor whose gradient is the screen-space (NDC-scaled) mean gradient used by densification
     screenspace_points = torch.zeros_like(xyz, dtype=xyz.dtype, requires_grad=True) + 0
     try:
         screenspace_points.retain_grad()
     except Exception:
         pass
+    return screenspace_points, GaussianRasterizationSettings(
+        image_height=int(viewpoint_camera.image_height), image_width=int(viewpoint_camera.image_width),
+        tanfovx=math.tan(viewpoint_camera.FoVx * 0.5), tanfovy=math.tan(viewpoint_camera.FoVy * 0.5),
+        bg=bg_color, scale_modifier=scaling_modifier, viewmatrix=viewpoint_camera.world_view_transform,
+        projmatrix=viewpoint_camera.full_proj_transform, sh_degree=pc.active_sh_degree,
+        campos=viewpoint_camera.camera_center, prefiltered=False, debug=bool(getattr(opt, "debug", False)))
 
-    raster_settings = GaussianRasterizationSettings(
-        image_height=int(viewpoint_camera.image_height),
-        image_width=int(viewpoint_camera.image_width),
-        tanfovx=math.tan(viewpoint_camera.FoVx * 0.5),
-        tanfovy=math.tan(viewpoint_camera.FoVy * 0.5),
-        bg=bg_color,
-        scale_modifier=scaling_modifier,
-        viewmatrix=viewpoint_camera.world_view_transform,
-        projmatrix=viewpoint_camera.full_proj_transform,
-        sh_degree=pc.active_sh_degree,
-        campos=viewpoint_camera.camera_center,
-        prefiltered=False,
-        debug=bool(getattr(opt, "debug", False)),
-    )
+
+def render(viewpoint_camera, pc, opt=DEFAULT_OPT, bg_color=None, scaling_modifier=1.0, override_color=None,
+           render_only=False, return_alpha=False):
+    """Returns {"render", "viewspace_points", "visibility_filter", "radii", "depth"} (or render/depth only); with
+    return_alpha the dict gains "alpha", the accumulated opacity 1 - T_final (1, H, W), differentiable."""
+    xyz = pc.get_xyz
+    screenspace_points, raster_settings = _view_setup(viewpoint_camera, pc, xyz, opt, bg_color, scaling_modifier)
     rasterizer = GaussianRasterizer(raster_settings=raster_settings)
 
     scales = rotations = cov3D_precomp = None
@@ -87,19 +83,7 @@ def render_raw(viewpoint_camera, pc, opt=DEFAULT_OPT, bg_color=None, scaling_mod
     dc|rest concatenation happen inside the rasterizer kernels.  Same return dict as render() (return_alpha
     included)."""
     xyz = pc._xyz
-    if bg_color is None:
-        bg_color = torch.zeros(3, dtype=torch.float32, device=xyz.device)
-    screenspace_points = torch.zeros_like(xyz, dtype=xyz.dtype, requires_grad=True) + 0
-    try:
-        screenspace_points.retain_grad()
-    except Exception:
-        pass
-    rs = GaussianRasterizationSettings(
-        image_height=int(viewpoint_camera.image_height), image_width=int(viewpoint_camera.image_width),
-        tanfovx=math.tan(viewpoint_camera.FoVx * 0.5), tanfovy=math.tan(viewpoint_camera.FoVy * 0.5),
-        bg=bg_color, scale_modifier=scaling_modifier, viewmatrix=viewpoint_camera.world_view_transform,
-        projmatrix=viewpoint_camera.full_proj_transform, sh_degree=pc.active_sh_degree,
-        campos=viewpoint_camera.camera_center, prefiltered=False, debug=bool(getattr(opt, "debug", False)))
+    screenspace_points, rs = _view_setup(viewpoint_camera, pc, xyz, opt, bg_color, scaling_modifier)
     out = rasterize_gaussians_raw(xyz, screenspace_points, pc._features_dc, pc._features_rest, pc._opacity, pc._scaling,
                                   pc._rotation, rs, return_alpha=return_alpha)
     return _result(out, screenspace_points, render_only)

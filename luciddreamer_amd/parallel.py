@@ -771,14 +771,7 @@ class ViewStreams:
                 taken = config.grad_output_taken()
                 taken_out = config.taken_outputs()
             entry = config.take_last_entry()                 # this view's header entry, if its forward was an async one
-            if grad_depth is not None:
-                out, out_depth = _rasterizer_pair(out, taken_out)
-                # (end_step: a lost view, run again -- its forward_fn returns the pair again)
-                redo = lambda o, g=grad_output, gd=grad_depth: torch.autograd.backward([o[0], o[1]], [g, gd])
-            if taken:
-                if grad_depth is None:
-                    redo = lambda o, g=grad_output: torch.autograd.backward([o], [g])     # (end_step: a lost view, run again)
-            elif backward_fn is not None:
+            if backward_fn is not None:
                 if self._prev_bwd is not None:
                     s.wait_event(self._prev_bwd)
                 with _calling_thread_backward():
@@ -787,17 +780,20 @@ class ViewStreams:
                 ev.record(s)
                 self._prev_bwd = ev
                 redo = backward_fn
-            elif grad_depth is not None:
-                if not (self.direct and _direct_backward(out, grad_output, grad_depth)):
-                    self._deferred.append(((out, grad_output), (out_depth, grad_depth)))
-                    if len(self._deferred) >= self.group:
-                        self._flush()
             else:
-                if not (self.direct and _direct_backward(out, grad_output)):
-                    self._deferred.append(((out, grad_output),))
+                # the view's (output, gradient) pairs: the image, and with grad_depth the depth output of the same call
+                if grad_depth is None:
+                    pairs = ((out, grad_output),)
+                else:
+                    color, depth = _rasterizer_pair(out, taken_out)
+                    pairs = ((color, grad_output), (depth, grad_depth))
+                if not (taken or (self.direct and _direct_backward(pairs[0][0], grad_output, grad_depth))):
+                    self._deferred.append(pairs)
                     if len(self._deferred) >= self.group:
                         self._flush()
-                redo = lambda o, g=grad_output: torch.autograd.backward([o], [g])     # (end_step: a lost view, run again)
+                # (end_step: a lost view, run again -- its forward_fn returns the image, or the pair, again)
+                grads = [g for _, g in pairs]
+                redo = lambda o, grads=grads: torch.autograd.backward([o] if len(grads) == 1 else [o[0], o[1]], grads)
             if entry is not None:
                 self._views.append((entry, forward_fn, redo))
         except BaseException:

@@ -51,6 +51,41 @@ def _take_ticket():
     return ticket
 
 
+def _forward(means3D, rs, capacity, run, node=False):
+    """The forward of every entry point: run(capacity) under the overflow policy; returns (run's result, capacity used).
+    capacity: config.capacity_for(means3D, rs), taken by the caller (rasterize_gaussians picks its route by it).
+    node: run returns the compiled node's outputs (color, radii, depth, geom[, alpha]) with num_rendered in
+    last_num_rendered(), else the binding's (num_rendered, color, depth, radii, geom, binning, img)."""
+    verifying = config.verifying(capacity)
+    ticket = -1
+    if verifying:
+        _C.request_early_header()
+    try:
+        out = run(capacity)
+    finally:
+        if verifying:
+            ticket = _take_ticket()
+    # policy "verify" (config.py): the whole forward is enqueued; wait for the copy of the header the library posted after the
+    # scan, and if the view needs more instances than its buffer holds render it again in exact mode -- what is returned is
+    # always a complete image (a first autograd node is simply dropped)
+    if verifying and config.verify(means3D, rs, ticket):
+        capacity = 0
+        out = run(0)
+    num_rendered, geom = (_C.last_num_rendered(), out[3]) if node else (out[0], out[4])
+    config.note_forward(means3D, rs, num_rendered, geom, capacity)
+    return out, capacity
+
+
+def _fusable_grad(t, device):
+    """t.grad if a backward kernel may add into it in place (config.set_fused_grad_accumulation), else None: t a non-empty
+    leaf that requires grad, its .grad contiguous float32 on `device` and 16-byte aligned (the kernels accumulate with
+    16-byte accesses).  csrc/torch_ext.cpp fusable_grad is the same rule."""
+    g = t.grad if (t.is_leaf and t.requires_grad and t.numel() != 0) else None
+    if g is not None and g.is_contiguous() and g.dtype == torch.float32 and g.device == device and g.data_ptr() % 16 == 0:
+        return g
+    return None
+
+
 def _snapshot(args, path):
     torch.save(tuple(a.detach().cpu().clone() if isinstance(a, torch.Tensor) else a for a in args), path)
 
@@ -66,29 +101,14 @@ class _RasterizeGaussians(torch.autograd.Function):
                 rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, rs.image_height, rs.image_width, sh,
                 rs.sh_degree, rs.campos, rs.prefiltered, rs.debug)
         capacity = config.capacity_for(means3D, rs)
-        verifying = config.verifying(capacity)
         try:
-            ticket = -1
-            if verifying:
-                _C.request_early_header()
-            try:
-                num_rendered, color, depth, radii, geom, binning, img = _C.rasterize_gaussians(
-                    *args, binning_capacity=capacity)
-            finally:
-                if verifying:
-                    ticket = _take_ticket()
-            # policy "verify": every kernel of the forward is enqueued; wait for the copy of the header the library posted
-            # after the scan, and if the view needs more instances than the buffer holds render it again in exact mode --
-            # what is returned is always a complete image
-            if verifying and config.verify(means3D, rs, ticket):
-                capacity = 0
-                num_rendered, color, depth, radii, geom, binning, img = _C.rasterize_gaussians(*args, binning_capacity=0)
+            (num_rendered, color, depth, radii, geom, binning, img), capacity = _forward(
+                means3D, rs, capacity, lambda cap: _C.rasterize_gaussians(*args, binning_capacity=cap))
         except Exception:
             if rs.debug:
                 _snapshot(args, "snapshot_fw.dump")
                 print("\nAn error occured in forward. Please forward snapshot_fw.dump for debugging.")
             raise
-        config.note_forward(means3D, rs, num_rendered, geom, capacity)
         ctx.raster_settings = rs
         ctx.num_rendered = num_rendered
         ctx.binning_capacity = capacity
@@ -119,13 +139,8 @@ class _RasterizeGaussians(torch.autograd.Function):
                 rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, grad_out_color, grad_depth, sh, rs.sh_degree,
                 rs.campos, geom, ctx.num_rendered, binning, img, rs.debug)
         accumulate_into = None
-        if ctx.leaf_inputs is not None:
-            accumulate_into = {}
-            for name, t in ctx.leaf_inputs.items():
-                g = t.grad if (t.is_leaf and t.requires_grad and t.numel() != 0) else None
-                if g is not None and g.is_contiguous() and g.dtype == torch.float32 and g.device == means3D.device \
-                        and g.data_ptr() % 16 == 0:      # the kernels accumulate with 16-byte accesses; else: dense path
-                    accumulate_into[name] = g
+        if ctx.leaf_inputs is not None:                 # an input without a fusable .grad (None): the dense path
+            accumulate_into = {name: _fusable_grad(t, means3D.device) for name, t in ctx.leaf_inputs.items()}
         try:
             # the binding picks the mode: depth mode needs the kept depth image (switch on at the forward) and grad_depth
             (grad_means2D, grad_colors_precomp, grad_opacities, grad_means3D, grad_cov3Ds_precomp, grad_sh,
@@ -154,11 +169,10 @@ def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales,
         return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
                                          cov3Ds_precomp, rs, bool(return_alpha))
     capacity = config.capacity_for(means3D, rs)
-    verifying = config.verifying(capacity)
     fused = config.fused_grad_accumulation()
     offered = config.offered_grad_output()
     # (an alpha-requesting call never takes the direct route: its backward would not see a gradient of alpha)
-    if offered is not None and fused and not verifying and not return_alpha:
+    if offered is not None and fused and not return_alpha and not config.verifying(capacity):
         # the caller already holds dL/dcolor (parallel.ViewStreams.run_view): forward and backward in ONE call of the binding,
         # gradients added into the leaves' .grad by the kernels, no autograd node (csrc/torch_ext.cpp rasterize_view_step).
         # An input that is not a leaf with a suitable .grad -> empty result -> the autograd path below, offer untouched.
@@ -178,20 +192,7 @@ def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales,
                                      rs.viewmatrix, rs.projmatrix, rs.campos, rs.scale_modifier, rs.tanfovx, rs.tanfovy,
                                      rs.image_height, rs.image_width, rs.sh_degree, rs.prefiltered, cap, fused,
                                      config.depth_gradient(), bool(return_alpha))
-    ticket = -1
-    if verifying:
-        _C.request_early_header()
-    try:
-        out = run(capacity)
-    finally:
-        if verifying:
-            ticket = _take_ticket()
-    # policy "verify" (config.py): the whole forward is enqueued; if the view needs more instances than its buffer holds it is
-    # rendered again in exact mode -- what is returned is always a complete image (the first node is simply dropped)
-    if verifying and config.verify(means3D, rs, ticket):
-        capacity = 0
-        out = run(0)
-    config.note_forward(means3D, rs, _C.last_num_rendered(), out[3], capacity)
+    out, _ = _forward(means3D, rs, capacity, run, node=True)
     if return_alpha:
         return out[0], out[1], out[2], out[4]
     return out[0], out[1], out[2]
@@ -204,26 +205,13 @@ class _RasterizeGaussiansRaw(torch.autograd.Function):
     @staticmethod
     def forward(ctx, xyz, means2D, features_dc, features_rest, opacity, scaling, rotation, raster_settings, return_alpha=False):
         rs = raster_settings
-        capacity = config.capacity_for(xyz, rs)
-        verifying = config.verifying(capacity)
 
         def run(cap):
             return _C.rasterize_gaussians_raw(
                 rs.bg, xyz, features_dc, features_rest, opacity, scaling, rotation, rs.scale_modifier, rs.viewmatrix,
                 rs.projmatrix, rs.tanfovx, rs.tanfovy, rs.image_height, rs.image_width, rs.sh_degree, rs.campos, rs.debug,
                 binning_capacity=cap)
-        ticket = -1
-        if verifying:
-            _C.request_early_header()
-        try:
-            num_rendered, color, depth, radii, geom, binning, img = run(capacity)
-        finally:
-            if verifying:
-                ticket = _take_ticket()
-        if verifying and config.verify(xyz, rs, ticket):       # overflowed: an exact-mode render instead
-            capacity = 0
-            num_rendered, color, depth, radii, geom, binning, img = run(0)
-        config.note_forward(xyz, rs, num_rendered, geom, capacity)
+        (num_rendered, color, depth, radii, geom, binning, img), capacity = _forward(xyz, rs, config.capacity_for(xyz, rs), run)
         ctx.raster_settings = rs
         ctx.num_rendered = num_rendered
         ctx.binning_capacity = capacity
@@ -249,14 +237,9 @@ class _RasterizeGaussiansRaw(torch.autograd.Function):
         modes = dict(dL_dout_depth=grad_depth, depth_image=ctx.depth_image, dL_dout_alpha=grad_alpha)
         accumulate_into = None
         if ctx.leaf_inputs is not None:
-            def leaf_grad(t):
-                g = t.grad if (t.is_leaf and t.requires_grad and t.numel() != 0) else None
-                ok = g is not None and g.is_contiguous() and g.dtype == torch.float32 and g.device == xyz.device \
-                    and g.data_ptr() % 16 == 0
-                return g if ok else None
             li = ctx.leaf_inputs
-            accumulate_into = {k: leaf_grad(li[k]) for k in ("xyz", "means2D", "opacity", "scaling", "rotation")}
-            g_dc, g_rest = leaf_grad(li["features_dc"]), leaf_grad(li["features_rest"])
+            accumulate_into = {k: _fusable_grad(li[k], xyz.device) for k in ("xyz", "means2D", "opacity", "scaling", "rotation")}
+            g_dc, g_rest = _fusable_grad(li["features_dc"], xyz.device), _fusable_grad(li["features_rest"], xyz.device)
             if g_dc is not None and (g_rest is not None or features_rest.numel() == 0):
                 accumulate_into["features"] = (g_dc, g_rest)
         # an armed FusedAdam over exactly these six tensors (optim.FusedAdam.arm_fused_backward): the gradients go to tensors
