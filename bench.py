@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- views/s forward+backward of the MI355X Gaussian-splat rasterizer (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3|c2|c3box|c4shape|c5shape] [--views V] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3|c2|c3box|c4shape|c5shape] [--views V] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -26,13 +26,19 @@ Workloads (BASELINE.json configs):
 
 Prints ONE JSON line (rank 0): the result record without the descriptions of how its figures were produced
 (printed_record; `--details FILE` writes the whole record).  `value` is the headline entry point (one lr_views_accumulate call per step, async mode,
-3 streams).  In the default run (N = 1, workload c3) the same process also times, with the same K and W,
+3 streams).  A plain run does only what that figure needs: it sets up, warms up, times the K steps, writes `--dump-outputs`
+and prints the line; the figures below are null in it.  With `--full` the same process goes on, after the timed steps, to
+  * `sustained`: the same step again for >= --sustain-seconds;
+  * `roofline`: the dominant kernel (HIP-event timed inside the library on the launch stream, single stream), with two live
+    rocprofv3 byte-counter passes over a child run at N = 1 on the default workload;
+and at N = 1 on the default workload c3 also times, with the same K and W,
   * `entry_points`: the drop-in autograd operator (`drop_in_views_per_s`), the same in the reference's exact mode with a
     host round trip per view (`exact_mode_views_per_s`) and the views step with the fused L1+DSSIM loss inside
     (`views_loss_views_per_s`);
+  * `f_rows`: the loss, Adam, prune and distCUDA2 kernels on their own;
   * `other_workloads`: the dense C3-box and C4-shape lines (their 20 %-of-roofline figures, driver-timed).
-`roofline` describes the dominant kernel (HIP-event timed inside the library on the launch stream, single stream);
-`cpu_baseline` is the CPU oracle ("port" of the reference semantics) on this box's host cores, one view at a time.
+`cpu_baseline` (with `parity`, N = 1) is the CPU oracle ("port" of the reference semantics) on the host's cores, one view at
+a time, and the HIP path's accuracy against it.
 """
 import argparse
 import json
@@ -422,7 +428,7 @@ def live_pmc_counters(timeout_s=90):
         return {}, "this run is itself being profiled"
     out = tempfile.mkdtemp(prefix="lr_pmc_", dir="/tmp")
     env = dict(os.environ, TMPDIR="/tmp")
-    child = [sys.executable, os.path.abspath(__file__), "--views", "4", "--steps", "1", "--warmup", "1", "--no-cpu-baseline",
+    child = [sys.executable, os.path.abspath(__file__), "--views", "4", "--steps", "1", "--warmup", "1", "--full", "--no-cpu-baseline",
              "--no-extras", "--sustain-seconds", "0"]
     acc = {}
     try:
@@ -446,7 +452,7 @@ def live_pmc_counters(timeout_s=90):
         shutil.rmtree(out, ignore_errors=True)
     return ({k: {c: v[0] / v[1] for c, v in cs.items()} for k, cs in acc.items()},
             "rocprofv3 --kernel-trace --pmc FETCH_SIZE / WRITE_SIZE, one pass each, run by this bench.py on this box "
-            "(child: bench.py --views 4 --steps 1 --warmup 1 --no-extras)")
+            "(child: bench.py --views 4 --steps 1 --warmup 1 --full --no-extras)")
 
 
 def profiled_stages(wl, api, exact, steps, world, dev, args, views_in_flight):
@@ -768,10 +774,15 @@ def main():
     ap.add_argument("--views", type=int, default=None, help="views per rank per step")
     ap.add_argument("--gaussians", type=int, default=None, help="override the Gaussian count (debug)")
     ap.add_argument("--exact", action="store_true", help="reference-style host sync per view instead of async mode")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the entry_points / other_workloads legs (and the live PMC passes)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, everything else the bench measures and checks: sustained, roofline (with the "
+                         "live PMC passes), entry_points, f_rows, cpu_baseline and parity, other_workloads.  Without it a run "
+                         "sets up, warms up, times the K steps, writes --dump-outputs and prints the line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the cpu_baseline / parity leg")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="--full: skip the entry_points / f_rows / other_workloads legs (and the live PMC passes)")
     ap.add_argument("--no-live-pmc", action="store_true",
-                    help="do not run the two rocprofv3 byte-counter passes; roofline.traffic then comes from profiles/pmc_c3.json")
+                    help="--full: do not run the two rocprofv3 byte-counter passes; roofline.traffic then comes from profiles/pmc_c3.json")
     ap.add_argument("--resolution", default=None, help="WxH override (the metric uses 1920x1080)")
     ap.add_argument("--sh-degree", type=int, default=3, choices=[0, 1, 2, 3], help="active SH degree (diagnostics; the metric uses 3)")
     ap.add_argument("--api", default="views", choices=["views", "autograd", "views-loss"],
@@ -789,7 +800,7 @@ def main():
                          "(parallel.sparse_rows_all_reduce); sharded-adam = a training step, reduce-scatter + Adam on the rank's "
                          "shard + all-gather of the parameters (extra work: not the metric)")
     ap.add_argument("--sustain-seconds", type=float, default=1.0,
-                    help="after the K contract steps, time the same step for at least this long (reported as `sustained`)")
+                    help="--full: after the K contract steps, time the same step for at least this long (reported as `sustained`)")
     ap.add_argument("--no-fused-accumulate", action="store_true",
                     help="let autograd accumulate dense per-view gradients instead of the in-kernel accumulation")
     ap.add_argument("--details", default=None, metavar="FILE",
@@ -848,16 +859,17 @@ def main():
         exchange_bytes = mean("bytes_sent")
         exchange_detail = {"rows_sent_per_step": mean("sent_rows"), "bytes_all_to_all": mean("bytes_all_to_all"),
                            "bytes_all_gather": mean("bytes_all_gather"), "dense_ring_allreduce_bytes": mean("dense_equivalent_bytes")}
+    # everything below up to the result line is --full only: a plain run goes from the timed steps (and the dump) to the line
     # the contract's K steps are 0.1 s of GPU time at C3; the same step again for >= sustain-seconds as a cross-check
     sustained = None
-    if args.sustain_seconds > 0:
+    if args.full and args.sustain_seconds > 0:
         n_sus = max(args.steps, int(math.ceil(args.sustain_seconds / max(ms_per_step * 1e-3, 1e-6))))
         dt_sus, _ = timed(step_fn, n_sus, world, dev)
         wl.finish()
         sustained = {"views_per_s": round(wl.total_views * n_sus / dt_sus, 2), "steps": n_sus, "seconds": round(dt_sus, 3)}
-    roofline = roofline_leg(wl, args.api, args.exact, args.steps, world, dev, value, args)
+    roofline = roofline_leg(wl, args.api, args.exact, args.steps, world, dev, value, args) if args.full else None
 
-    extras = rank == 0 and world == 1 and not args.no_extras and args.workload == "c3" and args.api == "views" \
+    extras = args.full and rank == 0 and world == 1 and not args.no_extras and args.workload == "c3" and args.api == "views" \
         and not args.exact and args.gaussians is None and args.views is None and res is None
     entry_points, other = None, None
     if extras:
@@ -907,7 +919,7 @@ def main():
                                 "only, one stream, default configuration (the video renderer's loop)")
     f_rows = measure_f_rows(dev) if extras else None
     cpu_baseline, parity = None, None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu_baseline, parity = run_cpu_baseline(wl)
     if extras:
         other = {}
