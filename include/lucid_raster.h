@@ -519,6 +519,53 @@ int lr_views_train_depth_check(const char* workspace, int P, int width, int heig
                                void* stream);
 
 /*
+ * The multi-view step with mask supervision (LucidDreamer's frames have holes: pixels the projected cloud left empty are exact
+ * zeros).  m is a per-view content mask [H,W] in [0, 1] (1: content, 0: hole) and A = 1 - T_final the alpha output.
+ *   lr_views_accumulate_alpha: the arguments of lr_views_accumulate_depth plus dL_dalpha (HOST array of n_views DEVICE [H,W]
+ *     pointers, required; a NULL entry gives that view no alpha gradient) and optional out_alpha (per-view [H,W] device images
+ *     receiving A, lr_render_alpha's values; NULL entries or array: not returned).  Here dL_ddepth may be NULL as a whole.  Each
+ *     view with an alpha gradient runs the alpha-mode backward of lr_backward_alpha (depth + alpha with a depth gradient too),
+ *     in the blend shape the view would take without it.  Workspace (lr_views_workspace_bytes), overflow check (lr_views_check)
+ *     and chains are exactly those of lr_views_accumulate.
+ *   lr_views_train_mask_accumulate: the arguments of lr_views_train_depth_accumulate plus masks (per-view [H,W], required) and
+ *     alpha_weight (finite, >= 0); depth_targets may be NULL (no depth term; depth_weight is then ignored) and out_alpha is
+ *     optional.  Per view, on its stream: forward, masked colour loss (lr_masked_l1_dssim_forward), depth L1 (if any), alpha hole
+ *     term (lr_alpha_hole_forward, from the forward's T_final), backward.  out_losses: device float[5 * n_views] receiving
+ *     {loss, l1, ssim, depth_l1, alpha_hole} per view, loss = Lc + depth_weight * depth_l1 + alpha_weight * alpha_hole, where l1
+ *     and ssim are those of the masked pair and depth_l1 (0 without depth targets), alpha_hole are unweighted.  With
+ *     alpha_weight == 0 the view gets no alpha gradient: its backward is the colour-only or depth-mode one (the bits of
+ *     lr_views_train_accumulate / lr_views_train_depth_accumulate for all-ones masks), and alpha_hole is still reported.
+ *     Workspace from lr_views_train_mask_workspace_bytes (>= lr_views_train_depth_workspace_bytes); overflow check with
+ *     lr_views_train_mask_check.
+ * Neither reads config-level switches: the new arguments are the opt-in.  No host synchronisation.
+ */
+int lr_views_accumulate_alpha(int n_views, const float* const* viewmatrices, const float* const* projmatrices,
+                              const float* const* cam_positions, const float* tan_fovx, const float* tan_fovy,
+                              int P, int D, int M, const float* background, int width, int height,
+                              const float* means3D, const float* shs, const float* colors_precomp, const float* opacities,
+                              const float* scales, float scale_modifier, const float* rotations, const float* cov3D_precomp,
+                              const float* const* dL_dpix, const float* const* dL_ddepth, const float* const* dL_dalpha,
+                              float* const* out_color, float* const* out_depth, float* const* out_alpha, int* const* out_radii,
+                              float* acc_mean2D, float* acc_opacity, float* acc_color, float* acc_mean3D, float* acc_cov3D,
+                              float* acc_sh, float* acc_scale, float* acc_rot,
+                              char* workspace, size_t workspace_bytes, long long binning_capacity, int n_streams,
+                              void* stream);
+size_t lr_views_train_mask_workspace_bytes(int P, int width, int height, long long binning_capacity, int n_streams);
+int lr_views_train_mask_accumulate(int n_views, const float* const* viewmatrices, const float* const* projmatrices,
+                                   const float* const* cam_positions, const float* tan_fovx, const float* tan_fovy,
+                                   int P, int D, int M, const float* background, int width, int height,
+                                   const float* means3D, const float* shs, const float* opacities, const float* scales,
+                                   float scale_modifier, const float* rotations, const float* const* targets,
+                                   float lambda_dssim, const float* const* masks, float alpha_weight,
+                                   const float* const* depth_targets, float depth_weight, float* out_losses,
+                                   float* const* out_color, float* const* out_depth, float* const* out_alpha,
+                                   int* const* out_radii, float* acc_mean2D, float* acc_opacity, float* acc_mean3D,
+                                   float* acc_sh, float* acc_scale, float* acc_rot, char* workspace, size_t workspace_bytes,
+                                   long long binning_capacity, int n_streams, void* stream);
+int lr_views_train_mask_check(const char* workspace, int P, int width, int height, long long binning_capacity, int n_streams,
+                              void* stream);
+
+/*
  * Row surgery of the Gaussian parameter set.  The reference changes the number of Gaussians
  * with boolean-mask indexing / torch.cat applied tensor by tensor to the six parameters and both Adam moments of
  * each (R/scene/gaussian_model.py:273-340 prune_points, _prune_optimizer, cat_tensors_to_optimizer; :342-403
@@ -614,6 +661,30 @@ int lr_depth_l1_forward(int height, int width, const float* depth, const float* 
                         void* workspace, size_t workspace_bytes, void* stream);
 int lr_depth_l1_backward(int height, int width, const float* depth, const float* target, float weight, const float* upstream,
                          float* dL_ddepth, void* stream);
+
+/*
+ * Mask supervision of one view (the single-view building blocks of lr_views_train_mask_accumulate).  mask: [H,W] float32
+ * device image in [0, 1], 1 where the target frame has content, 0 in its holes; shared by the channels of image / gt.
+ *   lr_masked_l1_dssim_forward / _backward: lr_l1_dssim_forward / _backward of the masked pair (mask * image, mask * gt) --
+ *     loss = l1_dssim(m I, m G, lambda), dL_dimage = upstream * m * (d l1_dssim / dI')|_{I' = m I} -- with the same workspace
+ *     (lr_loss_workspace_bytes), window, zero padding and mean over C*H*W.  Every product by m is exact for m == 1: an all-ones
+ *     mask gives the bits of lr_l1_dssim_*.
+ *   lr_alpha_hole_forward : out_loss (device, 1 float) = weight * mean_{H*W}( alpha * (1 - mask) ), alpha [H,W] (1 - T_final,
+ *                           e.g. lr_render_alpha's output); per-workgroup partial sums in `workspace` (lr_alpha_hole_workspace_bytes),
+ *                           reduced in a fixed order in double: bit-repeatable.
+ *   lr_alpha_hole_backward: dL_dalpha [H,W] = upstream * weight * (1 - mask) / (H*W); `upstream` a device scalar or NULL for 1.
+ *                           One elementwise pass, no workspace; it does not depend on alpha.
+ * Deterministic (no atomics), no host synchronisation.  Return 0 or a negative LR_ERR_*.
+ */
+int lr_masked_l1_dssim_forward(int channels, int height, int width, const float* image, const float* gt, const float* mask,
+                               float lambda_dssim, float* out_loss3, void* workspace, size_t workspace_bytes, void* stream);
+int lr_masked_l1_dssim_backward(int channels, int height, int width, const float* image, const float* gt, const float* mask,
+                                float lambda_dssim, const float* upstream, const void* workspace, float* dL_dimage, void* stream);
+size_t lr_alpha_hole_workspace_bytes(int height, int width);
+int lr_alpha_hole_forward(int height, int width, const float* alpha, const float* mask, float weight, float* out_loss,
+                          void* workspace, size_t workspace_bytes, void* stream);
+int lr_alpha_hole_backward(int height, int width, const float* mask, float weight, const float* upstream, float* dL_dalpha,
+                           void* stream);
 
 /*
  * Video frames on the device (the per-frame post-processing of the video renderer, R/luciddreamer.py:250-265).  Every entry

@@ -37,7 +37,10 @@ EXPORTS = ("lr_last_error", "lr_version", "lr_geom_bytes", "lr_img_bytes", "lr_b
            "lr_views_train_workspace_bytes", "lr_views_train_accumulate", "lr_views_train_check",
            "lr_views_accumulate_depth", "lr_views_train_depth_workspace_bytes", "lr_views_train_depth_accumulate",
            "lr_views_train_depth_check", "lr_depth_l1_workspace_bytes", "lr_depth_l1_forward", "lr_depth_l1_backward",
-           "lr_video_workspace_bytes", "lr_frames_to_u8", "lr_depth_colorize")
+           "lr_video_workspace_bytes", "lr_frames_to_u8", "lr_depth_colorize",
+           "lr_masked_l1_dssim_forward", "lr_masked_l1_dssim_backward", "lr_alpha_hole_workspace_bytes", "lr_alpha_hole_forward",
+           "lr_alpha_hole_backward", "lr_views_accumulate_alpha", "lr_views_train_mask_workspace_bytes",
+           "lr_views_train_mask_accumulate", "lr_views_train_mask_check")
 
 
 def assert_single_copy():
@@ -164,6 +167,36 @@ def lib():
         L.lr_depth_l1_forward.argtypes = [ci, ci, vp, vp, cf, vp, vp, ctypes.c_size_t, vp]
         L.lr_depth_l1_backward.restype = ci
         L.lr_depth_l1_backward.argtypes = [ci, ci, vp, vp, cf, vp, vp, vp]
+        L.lr_views_accumulate_alpha.restype = ci
+        L.lr_views_accumulate_alpha.argtypes = [ci, vp, vp, vp, vp, vp,          # n_views, view/proj/campos arrays, tanfovx/y arrays
+                                                ci, ci, ci, vp, ci, ci,          # P D M bg W H
+                                                vp, vp, vp, vp, vp, cf, vp, vp,  # means3D shs colors opac scales mod rot cov3D
+                                                vp, vp, vp,                      # dL_dpix[], dL_ddepth[], dL_dalpha[]
+                                                vp, vp, vp, vp,                  # out_color[], out_depth[], out_alpha[], out_radii[]
+                                                vp, vp, vp, vp, vp, vp, vp, vp,  # 8 accumulators
+                                                vp, ctypes.c_size_t, ll, ci, vp] # workspace, bytes, capacity, n_streams, stream
+        L.lr_views_train_mask_workspace_bytes.restype = ctypes.c_size_t
+        L.lr_views_train_mask_workspace_bytes.argtypes = [ci, ci, ci, ll, ci]
+        L.lr_views_train_mask_accumulate.restype = ci
+        L.lr_views_train_mask_accumulate.argtypes = [ci, vp, vp, vp, vp, vp,     # n_views, view/proj/campos arrays, tanfovx/y arrays
+                                                     ci, ci, ci, vp, ci, ci,     # P D M bg W H
+                                                     vp, vp, vp, vp, cf, vp,     # means3D shs opac scales mod rot
+                                                     vp, cf, vp, cf, vp, cf,     # targets[], lambda, masks[], alpha_weight, depth_targets[], depth_weight
+                                                     vp, vp, vp, vp, vp,         # out_losses, out_color[], out_depth[], out_alpha[], out_radii[]
+                                                     vp, vp, vp, vp, vp, vp,     # 6 accumulators
+                                                     vp, ctypes.c_size_t, ll, ci, vp]
+        L.lr_views_train_mask_check.restype = ci
+        L.lr_views_train_mask_check.argtypes = [vp, ci, ci, ci, ll, ci, vp]
+        L.lr_masked_l1_dssim_forward.restype = ci
+        L.lr_masked_l1_dssim_forward.argtypes = [ci, ci, ci, vp, vp, vp, cf, vp, vp, ctypes.c_size_t, vp]
+        L.lr_masked_l1_dssim_backward.restype = ci
+        L.lr_masked_l1_dssim_backward.argtypes = [ci, ci, ci, vp, vp, vp, cf, vp, vp, vp, vp]
+        L.lr_alpha_hole_workspace_bytes.restype = ctypes.c_size_t
+        L.lr_alpha_hole_workspace_bytes.argtypes = [ci, ci]
+        L.lr_alpha_hole_forward.restype = ci
+        L.lr_alpha_hole_forward.argtypes = [ci, ci, vp, vp, cf, vp, vp, ctypes.c_size_t, vp]
+        L.lr_alpha_hole_backward.restype = ci
+        L.lr_alpha_hole_backward.argtypes = [ci, ci, vp, cf, vp, vp, vp]
         L.lr_video_workspace_bytes.restype = ctypes.c_size_t
         L.lr_video_workspace_bytes.argtypes = [ci, ci, ci]
         L.lr_frames_to_u8.restype = ci

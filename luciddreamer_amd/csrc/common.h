@@ -499,10 +499,12 @@ int launch_adam_masked(int n_tensors, float* const* params, const float* const* 
 size_t loss_workspace_bytes(int C, int H, int W);
 // defer_final: leave {loss, l1, ssim} to the launch_loss_backward(..., final_out3) that follows on the same stream
 // (workgroup 0 of the backward kernel sums the partials: one launch less per view in the fused step)
+// mask != nullptr: the masked pair (mask [H,W] shared by the C channels): the loss of (m img, m gt), dL/dimg = m dL/d(m img)
 void launch_loss_forward(int C, int H, int W, const float* img, const float* gt, float lambda, float* out3, char* ws,
-                         hipStream_t s, bool defer_final = false);
+                         hipStream_t s, bool defer_final = false, const float* mask = nullptr);
 void launch_loss_backward(int C, int H, int W, const float* img, const float* gt, float lambda, const float* upstream,
-                          const char* ws, float* grad, hipStream_t s, float* final_out3 = nullptr, const float* w_ssim = nullptr);
+                          const char* ws, float* grad, hipStream_t s, float* final_out3 = nullptr, const float* w_ssim = nullptr,
+                          const float* mask = nullptr);
 // masked depth L1 (loss.hip).  The value, by final_mode: DEPTH_L1_VALUE out[0] = weight * mean(|depth - target| [target > 0]);
 // DEPTH_L1_FUSED (fused step, out = the view's {loss, l1, ssim, depth_l1}) out[0] += weight * mean, out[3] = mean;
 // DEPTH_L1_DEFER left to launch_depth_l1_backward(..., fused_out), which does what DEPTH_L1_FUSED does
@@ -512,6 +514,16 @@ void launch_depth_l1_forward(int H, int W, const float* depth, const float* targ
                              hipStream_t s, DepthL1Final final_mode = DEPTH_L1_VALUE);
 void launch_depth_l1_backward(int H, int W, const float* depth, const float* target, float weight, const float* upstream,
                               const char* ws, float* grad, hipStream_t s, float* fused_out = nullptr);
+// alpha hole term (loss.hip): weight * mean(A (1 - m)) with A the alpha image, or 1 - src when from_T (src = the blend forward's
+// final_T; alpha_out, if given, receives that A).  final_mode as the depth L1's, the fused value going to out[4]
+// ({loss, l1, ssim, depth_l1, alpha_hole}; fused_no_depth: out[3] = 0 as well, a step without a depth term); the backward
+// writes dL/dA = upstream * weight * (1 - m) / (H*W).
+size_t alpha_hole_workspace_bytes(int H, int W);
+void launch_alpha_hole_forward(int H, int W, const float* src, bool from_T, const float* mask, float weight, float* out, char* ws,
+                               hipStream_t s, DepthL1Final final_mode = DEPTH_L1_VALUE, float* alpha_out = nullptr,
+                               bool fused_no_depth = false);
+void launch_alpha_hole_backward(int H, int W, const float* mask, float weight, const float* upstream, const char* ws,
+                                float* grad, hipStream_t s, float* fused_out = nullptr, bool fused_no_depth = false);
 // bit positions of lr_backward's accumulate_mask (LR_ACC_* in lucid_raster.h)
 enum { ACC_MEAN2D = 0, ACC_CONIC = 1, ACC_OPACITY = 2, ACC_COLOR = 3, ACC_MEAN3D = 4, ACC_COV3D = 5, ACC_SH = 6,
        ACC_SCALE = 7, ACC_ROT = 8 };

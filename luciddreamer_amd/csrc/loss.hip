@@ -15,6 +15,9 @@
 //                dL/dI(q) = -lambda/n * [ W*D1 + 2 I(q) W*D2 + G(q) W*D3 ](q) + (1-lambda)/n * sign(I-G)(q),
 //                again separable through LDS, times the upstream scalar (device pointer, no host sync).
 // HBM-bound by construction: ~60 B per pixel-channel over both passes; no atomics, deterministic.
+// k_ssim_fwd_masked / k_ssim_bwd_masked (lr_masked_l1_dssim_*): the same bodies (loss_ssim_*_body.h) on the masked pair
+// (m I, m G), m a content mask [H,W]; 4 B more per pixel-channel and pass.  Below them: the masked depth L1 and the alpha hole
+// term, elementwise passes with fixed-order double reductions.
 #include "common.h"
 #include <cmath>
 
@@ -62,146 +65,24 @@ __device__ __forceinline__ float block_sum(float v, float* s_tmp)
     return s_tmp[0] + s_tmp[1] + s_tmp[2] + s_tmp[3];
 }
 
+
 __global__ void __launch_bounds__(LTHREADS)
 k_ssim_fwd(int H, int W, int tiles_x, int tiles_y, Win win, const float* __restrict__ img, const float* __restrict__ gt,
            float* __restrict__ D1, float* __restrict__ D2, float* __restrict__ D3, float2* __restrict__ partials,
            int n_blocks)
 {
-    // One LDS buffer, two tenants: the staged halo regions of I and G, then -- once every thread holds its horizontal
-    // sums in registers -- the five horizontal maps.  28 KB instead of 42 KB per workgroup: 5 workgroups per CU, not 3
-    // (the kernel is a chain of memory and LDS round trips; what it lacks is waves to hide them).
-    __shared__ float s_raw[5 * LR_IN * (LT + 1)];
-    float (*s_i)[LR_IN + 1] = reinterpret_cast<float (*)[LR_IN + 1]>(s_raw);
-    float (*s_g)[LR_IN + 1] = reinterpret_cast<float (*)[LR_IN + 1]>(s_raw + LR_IN * (LR_IN + 1));
-    float (*s_h)[LR_IN][LT + 1] = reinterpret_cast<float (*)[LR_IN][LT + 1]>(s_raw);     // I, G, I^2, G^2, I*G
-    static_assert(2 * LR_IN * (LR_IN + 1) <= 5 * LR_IN * (LT + 1), "the halo regions must fit under the horizontal maps");
-    __shared__ float s_tmp[4];
+    constexpr bool MASKED = false;
+    const float* const mask = nullptr;
+#include "loss_ssim_fwd_body.h"
+}
 
-    const int lb = xcd_band_block(n_blocks);
-    if (lb < 0) return;
-    const int tile = lb % (tiles_x * tiles_y), ch = lb / (tiles_x * tiles_y);
-    const int x0 = (tile % tiles_x) * LT, y0 = (tile / tiles_x) * LT;
-    const size_t plane = (size_t)ch * H * W;
-    const int tid = threadIdx.x;
-
-    // stage the halo region: ALL global loads of the thread are issued before the first LDS store (the workgroup's run
-    // time is a chain of memory round trips at 3-5 waves per SIMD; a rolled loop pays one round trip per iteration).
-    // Element p = tid + 256 i of the 42x42 region: (row, column) advance by (6, 4) per step with one carry -- one
-    // integer division per thread instead of two per element (index arithmetic was a third of the kernel's instructions).
-    float l1_part = 0.f;
-    {
-        const float* __restrict__ ip = img + plane;
-        const float* __restrict__ gp = gt + plane;
-        float ra[NSTAGE], rb[NSTAGE];
-        int li[NSTAGE];                                       // LDS index, -1: nothing to store
-        bool inner[NSTAGE];
-        int ly = tid / LR_IN, lx = tid - ly * LR_IN;
-#pragma unroll
-        for (int i = 0; i < NSTAGE; i++) {
-            const int y = y0 + ly - HALO, x = x0 + lx - HALO;
-            const bool in_region = tid + i * LTHREADS < LR_IN * LR_IN;
-            const bool ok = in_region && (unsigned)y < (unsigned)H && (unsigned)x < (unsigned)W;
-            const int q = ok ? y * W + x : 0;
-            const float a = ip[q], b = gp[q];
-            ra[i] = ok ? a : 0.f; rb[i] = ok ? b : 0.f;
-            li[i] = in_region ? ly * (LR_IN + 1) + lx : -1;
-            inner[i] = in_region && (unsigned)(ly - HALO) < (unsigned)LT && (unsigned)(lx - HALO) < (unsigned)LT;
-            lx += LTHREADS % LR_IN; ly += LTHREADS / LR_IN;
-            if (lx >= LR_IN) { lx -= LR_IN; ly += 1; }
-        }
-#pragma unroll
-        for (int i = 0; i < NSTAGE; i++) {
-            if (li[i] >= 0) {
-                (&s_i[0][0])[li[i]] = ra[i]; (&s_g[0][0])[li[i]] = rb[i];
-                if (inner[i]) l1_part += fabsf(ra[i] - rb[i]);                          // outside the image = 0
-            }
-        }
-    }
-    lds_barrier();
-
-    // horizontal pass: item = (row, group of 4 adjacent output columns); 336 items = up to two per thread, kept in
-    // registers until every thread has read its inputs (the maps overwrite the halo regions)
-    constexpr int HITEMS = LR_IN * (LT / 4), HROUNDS = (HITEMS + LTHREADS - 1) / LTHREADS;
-    float hs[HROUNDS][5][4];
-#pragma unroll
-    for (int r = 0; r < HROUNDS; r++) {
-        const int it = tid + r * LTHREADS;
-        if (it < HITEMS) {
-            const int row = it / (LT / 4), c0 = (it % (LT / 4)) * 4;
-            float a[14], b[14];
-#pragma unroll
-            for (int k = 0; k < 14; k++) { a[k] = s_i[row][c0 + k]; b[k] = s_g[row][c0 + k]; }
-#pragma unroll
-            for (int o = 0; o < 4; o++) {
-                float m1 = 0.f, m2 = 0.f, e11 = 0.f, e22 = 0.f, e12 = 0.f;
-#pragma unroll
-                for (int k = 0; k < 11; k++) {
-                    const float w = win.w[k], u = a[o + k], v = b[o + k];
-                    m1 += w * u; m2 += w * v; e11 += w * (u * u); e22 += w * (v * v); e12 += w * (u * v);
-                }
-                hs[r][0][o] = m1; hs[r][1][o] = m2; hs[r][2][o] = e11; hs[r][3][o] = e22; hs[r][4][o] = e12;
-            }
-        }
-    }
-    lds_barrier();
-#pragma unroll
-    for (int r = 0; r < HROUNDS; r++) {
-        const int it = tid + r * LTHREADS;
-        if (it < HITEMS) {
-            const int row = it / (LT / 4), c0 = (it % (LT / 4)) * 4;
-#pragma unroll
-            for (int m = 0; m < 5; m++)
-#pragma unroll
-                for (int o = 0; o < 4; o++) s_h[m][row][c0 + o] = hs[r][m][o];
-        }
-    }
-    lds_barrier();
-
-    // vertical pass: thread = (column, group of 4 adjacent output rows)
-    const int col = tid % LT, r0 = (tid / LT) * 4;
-    float acc[5][4];
-#pragma unroll
-    for (int m = 0; m < 5; m++) {
-        float v[14];
-#pragma unroll
-        for (int k = 0; k < 14; k++) v[k] = s_h[m][r0 + k][col];
-#pragma unroll
-        for (int o = 0; o < 4; o++) {
-            float s = 0.f;
-#pragma unroll
-            for (int k = 0; k < 11; k++) s += win.w[k] * v[o + k];
-            acc[m][o] = s;
-        }
-    }
-    const float C1 = 0.01f * 0.01f, C2 = 0.03f * 0.03f;
-    float ssim_part = 0.f;
-    float* __restrict__ d1p = D1 + plane;
-    float* __restrict__ d2p = D2 + plane;
-    float* __restrict__ d3p = D3 + plane;
-#pragma unroll
-    for (int o = 0; o < 4; o++) {
-        const int y = y0 + r0 + o, x = x0 + col;
-        if (y < H && x < W) {
-            const float mu1 = acc[0][o], mu2 = acc[1][o];
-            const float mu1_sq = mu1 * mu1, mu2_sq = mu2 * mu2, mu12 = mu1 * mu2;
-            const float s1 = acc[2][o] - mu1_sq, s2 = acc[3][o] - mu2_sq, s12 = acc[4][o] - mu12;
-            const float A1 = 2.f * mu12 + C1, A2 = 2.f * s12 + C2, B1 = mu1_sq + mu2_sq + C1, B2 = s1 + s2 + C2;
-            // two v_rcp_f32 (1 ulp) instead of three IEEE divisions: B1 >= C1, B2 >= C2 up to rounding, no special cases
-            const float iB1 = __builtin_amdgcn_rcpf(B1), iB2 = __builtin_amdgcn_rcpf(B2);
-            const float inv = iB1 * iB2;
-            const float S = A1 * A2 * inv;
-            ssim_part += S;
-            // partial derivatives of S w.r.t. the window sums of I, I^2 and I*G (those of G, G^2 are not needed)
-            const float dA1 = A2 * inv, dA2 = A1 * inv, dB1 = -S * iB1, dB2 = -S * iB2;
-            const int q = y * W + x;
-            d1p[q] = dA1 * 2.f * mu2 + dB1 * 2.f * mu1 - dB2 * 2.f * mu1 - dA2 * 2.f * mu2;
-            d2p[q] = dB2;
-            d3p[q] = 2.f * dA2;
-        }
-    }
-    const float st = block_sum(ssim_part, s_tmp);
-    const float lt = block_sum(l1_part, s_tmp);
-    if (tid == 0) partials[lb] = make_float2(st, lt);
+__global__ void __launch_bounds__(LTHREADS)
+k_ssim_fwd_masked(int H, int W, int tiles_x, int tiles_y, Win win, const float* __restrict__ img, const float* __restrict__ gt,
+                  const float* __restrict__ mask, float* __restrict__ D1, float* __restrict__ D2, float* __restrict__ D3,
+                  float2* __restrict__ partials, int n_blocks)
+{
+    constexpr bool MASKED = true;
+#include "loss_ssim_fwd_body.h"
 }
 
 // {loss, l1, ssim} from the per-workgroup partials, fixed order, one workgroup of LTHREADS threads
@@ -231,132 +112,27 @@ k_loss_final(int n_blocks, double n_elems, float lambda, const float2* __restric
     loss_final(n_blocks, n_elems, lambda, partials, out, s_a, s_b);
 }
 
+
 __global__ void __launch_bounds__(LTHREADS)
 k_ssim_bwd(int H, int W, int tiles_x, int tiles_y, Win win, float lambda, float inv_n, const float* __restrict__ upstream,
            const float* __restrict__ w_ssim, const float* __restrict__ img, const float* __restrict__ gt, const float* __restrict__ D1,
            const float* __restrict__ D2, const float* __restrict__ D3, float* __restrict__ grad,
            const float2* __restrict__ partials, int n_blocks, double n_elems, float* __restrict__ out3)
 {
-    // as in k_ssim_fwd: the three horizontal maps take over the LDS of the staged halo regions (22 KB instead of 38 KB)
-    __shared__ float s_raw[3 * LR_IN * (LR_IN + 1)];
-    static_assert(sizeof(float) * 3 * LR_IN * (LR_IN + 1) >= sizeof(double) * 2 * LTHREADS, "scratch of the final sum");
-    // fused step (views_core): the loss value's final sum rides in workgroup 0 instead of a launch of its own
-    if (out3 != nullptr && blockIdx.x == 0) {
-        double* s_a = reinterpret_cast<double*>(s_raw);
-        loss_final(n_blocks, n_elems, lambda, partials, out3, s_a, s_a + LTHREADS);
-        lds_barrier();
-    }
-    float (*s_d)[LR_IN][LR_IN + 1] = reinterpret_cast<float (*)[LR_IN][LR_IN + 1]>(s_raw);
-    float (*s_h)[LR_IN][LT + 1] = reinterpret_cast<float (*)[LR_IN][LT + 1]>(s_raw);
-    const int lb = xcd_band_block(n_blocks);
-    if (lb < 0) return;
-    const int tile = lb % (tiles_x * tiles_y), ch = lb / (tiles_x * tiles_y);
-    const int x0 = (tile % tiles_x) * LT, y0 = (tile / tiles_x) * LT;
-    const size_t plane = (size_t)ch * H * W;
-    const int tid = threadIdx.x;
+    constexpr bool MASKED = false;
+    const float* const mask = nullptr;
+#include "loss_ssim_bwd_body.h"
+}
 
-    // the pixel's own I and G (needed only in the last lines) are requested first, together with the halo loads: as the
-    // kernel's final dependent loads they cost every workgroup one more memory round trip
-    const int col = tid % LT, r0 = (tid / LT) * 4;
-    const float* __restrict__ ip = img + plane;
-    const float* __restrict__ gp = gt + plane;
-    float own_i[4], own_g[4];
-#pragma unroll
-    for (int o = 0; o < 4; o++) {
-        const int y = y0 + r0 + o, x = x0 + col;
-        const int q = (y < H && x < W) ? y * W + x : 0;
-        own_i[o] = ip[q]; own_g[o] = gp[q];
-    }
-    {
-        const float* __restrict__ p1 = D1 + plane;
-        const float* __restrict__ p2 = D2 + plane;
-        const float* __restrict__ p3 = D3 + plane;
-        float r1[NSTAGE], r2[NSTAGE], r3[NSTAGE];
-        int li[NSTAGE];
-        int ly = tid / LR_IN, lx = tid - ly * LR_IN;           // element tid + 256 i: (row, column) += (6, 4) with carry
-#pragma unroll
-        for (int i = 0; i < NSTAGE; i++) {                   // all loads first (see k_ssim_fwd)
-            const int y = y0 + ly - HALO, x = x0 + lx - HALO;
-            const bool in_region = tid + i * LTHREADS < LR_IN * LR_IN;
-            const bool ok = in_region && (unsigned)y < (unsigned)H && (unsigned)x < (unsigned)W;
-            const int q = ok ? y * W + x : 0;
-            const float a = p1[q], b = p2[q], c = p3[q];
-            r1[i] = ok ? a : 0.f; r2[i] = ok ? b : 0.f; r3[i] = ok ? c : 0.f;
-            li[i] = in_region ? ly * (LR_IN + 1) + lx : -1;
-            lx += LTHREADS % LR_IN; ly += LTHREADS / LR_IN;
-            if (lx >= LR_IN) { lx -= LR_IN; ly += 1; }
-        }
-#pragma unroll
-        for (int i = 0; i < NSTAGE; i++)
-            if (li[i] >= 0) { (&s_d[0][0][0])[li[i]] = r1[i]; (&s_d[1][0][0])[li[i]] = r2[i]; (&s_d[2][0][0])[li[i]] = r3[i]; }
-    }
-    lds_barrier();
-    constexpr int HITEMS = LR_IN * (LT / 4), HROUNDS = (HITEMS + LTHREADS - 1) / LTHREADS;
-    float hs[HROUNDS][3][4];
-#pragma unroll
-    for (int r = 0; r < HROUNDS; r++) {
-        const int it = tid + r * LTHREADS;
-        if (it < HITEMS) {
-            const int row = it / (LT / 4), c0 = (it % (LT / 4)) * 4;
-#pragma unroll
-            for (int m = 0; m < 3; m++) {
-                float v[14];
-#pragma unroll
-                for (int k = 0; k < 14; k++) v[k] = s_d[m][row][c0 + k];
-#pragma unroll
-                for (int o = 0; o < 4; o++) {
-                    float sum = 0.f;
-#pragma unroll
-                    for (int k = 0; k < 11; k++) sum += win.w[k] * v[o + k];
-                    hs[r][m][o] = sum;
-                }
-            }
-        }
-    }
-    lds_barrier();
-#pragma unroll
-    for (int r = 0; r < HROUNDS; r++) {
-        const int it = tid + r * LTHREADS;
-        if (it < HITEMS) {
-            const int row = it / (LT / 4), c0 = (it % (LT / 4)) * 4;
-#pragma unroll
-            for (int m = 0; m < 3; m++)
-#pragma unroll
-                for (int o = 0; o < 4; o++) s_h[m][row][c0 + o] = hs[r][m][o];
-        }
-    }
-    lds_barrier();
-    float acc[3][4];
-#pragma unroll
-    for (int m = 0; m < 3; m++) {
-        float v[14];
-#pragma unroll
-        for (int k = 0; k < 14; k++) v[k] = s_h[m][r0 + k][col];
-#pragma unroll
-        for (int o = 0; o < 4; o++) {
-            float s = 0.f;
-#pragma unroll
-            for (int k = 0; k < 11; k++) s += win.w[k] * v[o + k];
-            acc[m][o] = s;
-        }
-    }
-    const float up = upstream != nullptr ? upstream[0] : 1.0f;
-    // two-weight form (lr_l1_dssim_backward_weights): upstream = dL/d l1, w_ssim = dL/d ssim, both device scalars -- the
-    // caller composed the two means itself, with whatever weights
-    const float k_ssim = w_ssim != nullptr ? inv_n * w_ssim[0] : -lambda * inv_n * up;
-    const float k_l1 = w_ssim != nullptr ? inv_n * up : (1.0f - lambda) * inv_n * up;
-    float* __restrict__ gradp = grad + plane;
-#pragma unroll
-    for (int o = 0; o < 4; o++) {
-        const int y = y0 + r0 + o, x = x0 + col;
-        if (y < H && x < W) {
-            const int q = y * W + x;
-            const float a = own_i[o], b = own_g[o];
-            const float d = a - b;
-            const float sgn = d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f);          // torch.abs backward: sign, 0 at 0
-            gradp[q] = k_ssim * (acc[0][o] + 2.f * a * acc[1][o] + b * acc[2][o]) + k_l1 * sgn;
-        }
-    }
+__global__ void __launch_bounds__(LTHREADS)
+k_ssim_bwd_masked(int H, int W, int tiles_x, int tiles_y, Win win, float lambda, float inv_n, const float* __restrict__ upstream,
+                  const float* __restrict__ w_ssim, const float* __restrict__ img, const float* __restrict__ gt,
+                  const float* __restrict__ mask, const float* __restrict__ D1, const float* __restrict__ D2,
+                  const float* __restrict__ D3, float* __restrict__ grad, const float2* __restrict__ partials, int n_blocks,
+                  double n_elems, float* __restrict__ out3)
+{
+    constexpr bool MASKED = true;
+#include "loss_ssim_bwd_body.h"
 }
 
 // ---- masked depth L1 (supervision of the rendered depth against a depth map, e.g. a monocular estimate) -------------------
@@ -459,6 +235,103 @@ k_depth_l1_bwd(int n, float weight, const float* __restrict__ upstream, const fl
     }
 }
 
+// ---- alpha hole term (coverage where the target frame has no content) -----------------------------------------------------
+//     loss = weight * mean_{H*W}( A * (1 - m) ),   d loss / d A = weight * (1 - m) / (H*W)
+// A = 1 - T_final, the alpha output; m [H,W] the content mask in [0, 1].  The forward reads A -- or T_final itself, from_T, and
+// forms A = 1 - T_final as lr_render_alpha does, writing it to alpha_out when the caller keeps the alpha image.  Partials,
+// fixed-order double reduction and the DEFER / FUSED finalisation as k_depth_l1_*; the fused value goes to out[4].
+__global__ void __launch_bounds__(LTHREADS)
+k_alpha_hole_fwd(int n, const float* __restrict__ src, int from_T, const float* __restrict__ mask, double* __restrict__ partials,
+                 float* __restrict__ alpha_out)
+{
+    __shared__ double s_tmp[4];
+    const int base = (int)blockIdx.x * DL_BLOCK + (int)threadIdx.x;
+    float a[DL_ITEMS], m[DL_ITEMS];
+#pragma unroll
+    for (int i = 0; i < DL_ITEMS; i++) {             // all loads first; pixel base + 256 i: coalesced
+        const int q = base + i * LTHREADS;
+        const bool ok = q < n;
+        a[i] = ok ? src[q] : (from_T ? 1.f : 0.f);
+        m[i] = ok ? mask[q] : 1.f;
+    }
+    if (from_T) {
+#pragma unroll
+        for (int i = 0; i < DL_ITEMS; i++) a[i] = 1.0f - a[i];
+        if (alpha_out != nullptr) {
+#pragma unroll
+            for (int i = 0; i < DL_ITEMS; i++) {
+                const int q = base + i * LTHREADS;
+                if (q < n) alpha_out[q] = a[i];
+            }
+        }
+    }
+    float sum = 0.f;
+#pragma unroll
+    for (int i = 0; i < DL_ITEMS; i++) sum += a[i] * (1.0f - m[i]);
+    const double bs = block_sum_d((double)sum, s_tmp);
+    if (threadIdx.x == 0) partials[blockIdx.x] = bs;
+}
+
+// as depth_l1_final, with the fused step's unweighted mean in out[4] (out_losses of lr_views_train_mask_accumulate);
+// fused 2: a step without a depth term, whose depth_l1 out[3] is reported as 0
+__device__ __forceinline__ void alpha_hole_final(int n_blocks, double n_elems, float weight, const double* __restrict__ partials,
+                                                 float* __restrict__ out, int fused, double* s_a)
+{
+    double a = 0.0;
+    for (int i = threadIdx.x; i < n_blocks; i += LTHREADS) a += partials[i];
+    s_a[threadIdx.x] = a;
+    lds_barrier();
+    for (int off = LTHREADS / 2; off > 0; off >>= 1) {
+        if ((int)threadIdx.x < off) s_a[threadIdx.x] += s_a[threadIdx.x + off];
+        lds_barrier();
+    }
+    if (threadIdx.x == 0) {
+        const float mean = (float)(s_a[0] / n_elems);
+        if (fused) {
+            if (weight != 0.f) out[0] = out[0] + weight * mean;
+            out[4] = mean;
+            if (fused == 2) out[3] = 0.f;
+        } else {
+            out[0] = weight * mean;
+        }
+    }
+}
+
+__global__ void __launch_bounds__(LTHREADS)
+k_alpha_hole_final(int n_blocks, double n_elems, float weight, const double* __restrict__ partials, float* __restrict__ out,
+                   int fused)
+{
+    __shared__ double s_a[LTHREADS];
+    alpha_hole_final(n_blocks, n_elems, weight, partials, out, fused, s_a);
+}
+
+// dL/dA = (upstream * weight) / n * (1 - m): torch's autograd of the definition (mul, mean backward's division, then the
+// product with 1 - m), bit for bit.  It does not depend on A.  fused_out: the fused step's value rides in workgroup 0.
+__global__ void __launch_bounds__(LTHREADS)
+k_alpha_hole_bwd(int n, float weight, const float* __restrict__ upstream, const float* __restrict__ mask,
+                 float* __restrict__ grad, const double* __restrict__ partials, int n_blocks, float* __restrict__ fused_out,
+                 int fused)
+{
+    if (fused_out != nullptr && blockIdx.x == 0) {
+        __shared__ double s_a[LTHREADS];
+        alpha_hole_final(n_blocks, (double)n, weight, partials, fused_out, fused, s_a);
+    }
+    const float up = upstream != nullptr ? upstream[0] : 1.0f;
+    const float k = (up * weight) / (float)n;
+    const int base = (int)blockIdx.x * DL_BLOCK + (int)threadIdx.x;
+    float m[DL_ITEMS];
+#pragma unroll
+    for (int i = 0; i < DL_ITEMS; i++) {
+        const int q = base + i * LTHREADS;
+        m[i] = q < n ? mask[q] : 1.f;
+    }
+#pragma unroll
+    for (int i = 0; i < DL_ITEMS; i++) {
+        const int q = base + i * LTHREADS;
+        if (q < n) grad[q] = k * (1.0f - m[i]);
+    }
+}
+
 }  // namespace
 
 size_t loss_workspace_bytes(int C, int H, int W)
@@ -469,7 +342,7 @@ size_t loss_workspace_bytes(int C, int H, int W)
 }
 
 void launch_loss_forward(int C, int H, int W, const float* img, const float* gt, float lambda, float* out3, char* ws,
-                         hipStream_t s, bool defer_final)
+                         hipStream_t s, bool defer_final, const float* mask)
 {
     static const Win win = make_window();
     const size_t n = (size_t)C * H * W;
@@ -477,22 +350,32 @@ void launch_loss_forward(int C, int H, int W, const float* img, const float* gt,
     const int blocks = C * tx * ty;
     float* D = reinterpret_cast<float*>(ws);
     float2* partials = reinterpret_cast<float2*>(ws + align_up(3 * n * sizeof(float)));
-    hipLaunchKernelGGL(k_ssim_fwd, dim3((blocks + 7) / 8 * 8), dim3(LTHREADS), 0, s, H, W, tx, ty, win, img, gt, D, D + n, D + 2 * n,
-                       partials, blocks);
+    if (mask != nullptr)
+        hipLaunchKernelGGL(k_ssim_fwd_masked, dim3((blocks + 7) / 8 * 8), dim3(LTHREADS), 0, s, H, W, tx, ty, win, img, gt, mask, D,
+                           D + n, D + 2 * n, partials, blocks);
+    else
+        hipLaunchKernelGGL(k_ssim_fwd, dim3((blocks + 7) / 8 * 8), dim3(LTHREADS), 0, s, H, W, tx, ty, win, img, gt, D, D + n,
+                           D + 2 * n, partials, blocks);
     if (!defer_final)      // otherwise launch_loss_backward(..., final_out3) follows on the same stream and forms the value
         hipLaunchKernelGGL(k_loss_final, dim3(1), dim3(LTHREADS), 0, s, blocks, (double)n, lambda, partials, out3);
 }
 
 void launch_loss_backward(int C, int H, int W, const float* img, const float* gt, float lambda, const float* upstream,
-                          const char* ws, float* grad, hipStream_t s, float* final_out3, const float* w_ssim)
+                          const char* ws, float* grad, hipStream_t s, float* final_out3, const float* w_ssim, const float* mask)
 {
     static const Win win = make_window();
     const size_t n = (size_t)C * H * W;
     const int tx = (W + LT - 1) / LT, ty = (H + LT - 1) / LT;
     const float* D = reinterpret_cast<const float*>(ws);
     const float2* partials = reinterpret_cast<const float2*>(ws + align_up(3 * n * sizeof(float)));
-    hipLaunchKernelGGL(k_ssim_bwd, dim3((C * tx * ty + 7) / 8 * 8), dim3(LTHREADS), 0, s, H, W, tx, ty, win, lambda, (float)(1.0 / (double)n),
-                       upstream, w_ssim, img, gt, D, D + n, D + 2 * n, grad, partials, C * tx * ty, (double)n, final_out3);
+    if (mask != nullptr)
+        hipLaunchKernelGGL(k_ssim_bwd_masked, dim3((C * tx * ty + 7) / 8 * 8), dim3(LTHREADS), 0, s, H, W, tx, ty, win, lambda,
+                           (float)(1.0 / (double)n), upstream, w_ssim, img, gt, mask, D, D + n, D + 2 * n, grad, partials, C * tx * ty,
+                           (double)n, final_out3);
+    else
+        hipLaunchKernelGGL(k_ssim_bwd, dim3((C * tx * ty + 7) / 8 * 8), dim3(LTHREADS), 0, s, H, W, tx, ty, win, lambda,
+                           (float)(1.0 / (double)n), upstream, w_ssim, img, gt, D, D + n, D + 2 * n, grad, partials, C * tx * ty,
+                           (double)n, final_out3);
 }
 
 }  // namespace lr
@@ -525,6 +408,35 @@ void launch_depth_l1_backward(int H, int W, const float* depth, const float* tar
     const int blocks = (n + DL_BLOCK - 1) / DL_BLOCK;
     hipLaunchKernelGGL(k_depth_l1_bwd, dim3(blocks), dim3(LTHREADS), 0, s, n, weight, upstream, depth, target, grad,
                        reinterpret_cast<const double*>(ws), blocks, fused_out);
+}
+
+}  // namespace lr
+
+namespace lr {
+
+size_t alpha_hole_workspace_bytes(int H, int W) { return depth_l1_workspace_bytes(H, W); }
+
+void launch_alpha_hole_forward(int H, int W, const float* src, bool from_T, const float* mask, float weight, float* out, char* ws,
+                               hipStream_t s, DepthL1Final final_mode, float* alpha_out, bool fused_no_depth)
+{
+    const int n = H * W;
+    const int blocks = (n + DL_BLOCK - 1) / DL_BLOCK;
+    double* partials = reinterpret_cast<double*>(ws);
+    hipLaunchKernelGGL(k_alpha_hole_fwd, dim3(blocks), dim3(LTHREADS), 0, s, n, src, from_T ? 1 : 0, mask, partials,
+                       from_T ? alpha_out : nullptr);
+    // DEPTH_L1_DEFER: launch_alpha_hole_backward(..., fused_out) follows on the same stream and forms the value
+    if (final_mode != DEPTH_L1_DEFER)
+        hipLaunchKernelGGL(k_alpha_hole_final, dim3(1), dim3(LTHREADS), 0, s, blocks, (double)n, weight, partials, out,
+                           final_mode == DEPTH_L1_FUSED ? (fused_no_depth ? 2 : 1) : 0);
+}
+
+void launch_alpha_hole_backward(int H, int W, const float* mask, float weight, const float* upstream, const char* ws,
+                                float* grad, hipStream_t s, float* fused_out, bool fused_no_depth)
+{
+    const int n = H * W;
+    const int blocks = (n + DL_BLOCK - 1) / DL_BLOCK;
+    hipLaunchKernelGGL(k_alpha_hole_bwd, dim3(blocks), dim3(LTHREADS), 0, s, n, weight, upstream, mask, grad,
+                       reinterpret_cast<const double*>(ws), blocks, fused_out, fused_no_depth ? 2 : 1);
 }
 
 }  // namespace lr

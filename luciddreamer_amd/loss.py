@@ -238,3 +238,122 @@ def depth_l1(depth, target, weight=1.0):
     a fixed order in double: bit-repeatable) and one elementwise pass backward (lr_depth_l1_forward / lr_depth_l1_backward).
     Gradients flow to `depth` only (the target is data)."""
     return _DepthL1.apply(depth, target, weight)
+
+
+# ---- mask supervision (INTEGRATION.md 2e): a colour loss only where the frame has content, a penalty on alpha in its holes ----
+def content_mask(gt):
+    """float32 [1,H,W] mask of the pixels of a target frame [C,H,W] where any channel is non-zero: LucidDreamer's `maskj`
+    rebuilt from the frame (generate_pcd sets every pixel the projected cloud left empty to exact zero).  A genuinely black
+    content pixel counts as a hole.  A one-time step during setup: a torch expression."""
+    if gt.dim() != 3:
+        raise RuntimeError(f"content_mask: gt must be [C,H,W], got {tuple(gt.shape)}")
+    return (gt != 0).any(dim=0, keepdim=True).to(torch.float32)
+
+
+def _mask_hw(mask, H, W, dev):
+    if not mask.is_cuda or mask.device != dev or mask.dtype != torch.float32:
+        raise RuntimeError("mask must be a float32 tensor on the device of the image")
+    if tuple(mask.shape) not in ((H, W), (1, H, W)):
+        raise RuntimeError(f"mask {tuple(mask.shape)} must be [1,H,W] or [H,W] with H,W = {H},{W}")
+    return mask.contiguous()
+
+
+class _MaskedL1DSSIM(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, image, gt, mask, lambda_dssim):
+        if not image.is_cuda or not gt.is_cuda:
+            raise RuntimeError("luciddreamer_amd.loss: image and gt must be on a HIP device (no CPU path)")
+        if image.shape != gt.shape or image.dim() < 2 or image.dtype != torch.float32 or gt.dtype != torch.float32:
+            raise RuntimeError("image and gt must be float32 tensors of the same [..., H, W] shape")
+        x, g = image.contiguous(), gt.contiguous()
+        H, W = int(x.shape[-2]), int(x.shape[-1])
+        C = x.numel() // (H * W)
+        m = _mask_hw(mask, H, W, x.device)
+        L = _lib.lib()
+        dev = x.device
+        out3 = torch.empty((3,), dtype=torch.float32, device=dev)
+        ws = torch.empty((_ws_bytes(L, C, H, W),), dtype=torch.uint8, device=dev)
+        with _lib.on_device(dev):
+            rc = L.lr_masked_l1_dssim_forward(C, H, W, x.data_ptr(), g.data_ptr(), m.data_ptr(), float(lambda_dssim),
+                                              out3.data_ptr(), ws.data_ptr(), ws.numel(), torch.cuda.current_stream(dev).cuda_stream)
+        if rc < 0:
+            _lib.raise_for(rc, "masked_l1_dssim")
+        ctx.save_for_backward(x, g, m, ws)
+        ctx.lam, ctx.dims, ctx.in_shape = float(lambda_dssim), (C, H, W), image.shape
+        return out3[0]
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        x, g, m, ws = ctx.saved_tensors
+        C, H, W = ctx.dims
+        L = _lib.lib()
+        dev = x.device
+        up = _weight(grad_out, dev)
+        grad = torch.empty_like(x)
+        with _lib.on_device(dev):
+            rc = L.lr_masked_l1_dssim_backward(C, H, W, x.data_ptr(), g.data_ptr(), m.data_ptr(), ctx.lam, up.data_ptr(),
+                                               ws.data_ptr(), grad.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+        if rc < 0:
+            _lib.raise_for(rc, "masked_l1_dssim backward")
+        return grad.view(ctx.in_shape), None, None, None
+
+
+def masked_l1_dssim(image, gt, mask, lambda_dssim=0.2):
+    """l1_dssim_loss(mask * image, mask * gt, lambda_dssim): the fused L1 + DSSIM of the masked pair (mean over all C*H*W);
+    image, gt [C,H,W], mask [1,H,W] or [H,W] in [0, 1] (content_mask), shared by the channels.  The gradient flows to `image`:
+    mask * dL/d(mask * image).  An all-ones mask gives l1_dssim_loss's bits.  HIP in both directions, no host synchronisation
+    (lr_masked_l1_dssim_forward / _backward)."""
+    return _MaskedL1DSSIM.apply(image, gt, mask, lambda_dssim)
+
+
+_ALPHA_WS_BYTES = {}                # (H, W) -> lr_alpha_hole_workspace_bytes
+
+
+class _AlphaHole(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, alpha, mask, weight):
+        if not alpha.is_cuda or alpha.dtype != torch.float32:
+            raise RuntimeError("luciddreamer_amd.loss.alpha_hole: alpha must be a float32 tensor on a HIP device (no CPU path)")
+        if not (alpha.dim() == 2 or (alpha.dim() == 3 and alpha.shape[0] == 1)):
+            raise RuntimeError(f"alpha {tuple(alpha.shape)} must be [1,H,W] or [H,W]")
+        H, W = int(alpha.shape[-2]), int(alpha.shape[-1])
+        a = alpha.contiguous()
+        m = _mask_hw(mask, H, W, a.device)
+        L = _lib.lib()
+        dev = a.device
+        n = _ALPHA_WS_BYTES.get((H, W))
+        if n is None:
+            n = _ALPHA_WS_BYTES[(H, W)] = int(L.lr_alpha_hole_workspace_bytes(H, W))
+        out = torch.empty((1,), dtype=torch.float32, device=dev)
+        ws = torch.empty((n,), dtype=torch.uint8, device=dev)
+        with _lib.on_device(dev):
+            rc = L.lr_alpha_hole_forward(H, W, a.data_ptr(), m.data_ptr(), float(weight), out.data_ptr(), ws.data_ptr(),
+                                         ws.numel(), torch.cuda.current_stream(dev).cuda_stream)
+        if rc < 0:
+            _lib.raise_for(rc, "alpha_hole")
+        ctx.save_for_backward(m)
+        ctx.weight, ctx.dims, ctx.in_shape = float(weight), (H, W), alpha.shape
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        m, = ctx.saved_tensors
+        H, W = ctx.dims
+        L = _lib.lib()
+        dev = m.device
+        up = _weight(grad_out, dev)
+        grad = torch.empty(ctx.in_shape, dtype=torch.float32, device=dev)
+        with _lib.on_device(dev):
+            rc = L.lr_alpha_hole_backward(H, W, m.data_ptr(), ctx.weight, up.data_ptr(), grad.data_ptr(),
+                                          torch.cuda.current_stream(dev).cuda_stream)
+        if rc < 0:
+            _lib.raise_for(rc, "alpha_hole backward")
+        return grad, None, None
+
+
+def alpha_hole(alpha, mask, weight=1.0):
+    """weight * mean over all H*W pixels of alpha * (1 - mask): the penalty on coverage in the target frame's holes; alpha
+    [1,H,W] or [H,W] (the rasterizer's return_alpha output), mask as masked_l1_dssim's.  One HIP pass forward (per-workgroup
+    partial sums, reduced in a fixed order in double: bit-repeatable) and one elementwise pass backward, weight * (1 - mask) /
+    (H*W), bit-equal to torch autograd of the definition (lr_alpha_hole_forward / _backward)."""
+    return _AlphaHole.apply(alpha, mask, weight)

@@ -850,7 +850,7 @@ class ViewStreams:
 
 class ViewBatch:
     """One C call per step for a fixed list of views (lr_views_accumulate_depth, which with NULL depth gradients is
-    lr_views_accumulate): forward + backward of every view, gradients accumulated in place, views alternated over internal
+    lr_views_accumulate; lr_views_accumulate_alpha with grad_alphas): forward + backward of every view, gradients accumulated in place, views alternated over internal
     HIP streams.  The per-view upstream gradients dL/dcolor are given up front (a training loop that needs the rendered
     image to form its loss uses the autograd op, optionally with ViewStreams, instead).
 
@@ -863,7 +863,9 @@ class ViewBatch:
                  targets: Optional[Sequence[torch.Tensor]] = None, lambda_dssim: float = 0.2,
                  grad_depths: Optional[Sequence[torch.Tensor]] = None,
                  depth_targets: Optional[Sequence[torch.Tensor]] = None, depth_weight: Optional[float] = None,
-                 depths: Optional[Sequence[torch.Tensor]] = None):
+                 depths: Optional[Sequence[torch.Tensor]] = None,
+                 grad_alphas: Optional[Sequence[torch.Tensor]] = None, masks: Optional[Sequence[torch.Tensor]] = None,
+                 alpha_weight: Optional[float] = None, alphas: Optional[Sequence[torch.Tensor]] = None):
         """grad_colors: fixed upstream gradients dL/dcolor per view, OR targets: ground-truth images per view, in which
         case every view's L1 + DSSIM loss against its target is formed inside the call (lr_views_train_accumulate) and
         `self.losses` ([n,3] device tensor: loss, l1, ssim per view) is filled by run().
@@ -876,6 +878,16 @@ class ViewBatch:
             (lr_views_train_depth_accumulate).  depth_weight 0 reports depth_l1 with the colour-only gradients.
           depths: per-view [1,H,W] or [H,W] contiguous float32 device tensors that run() fills with the rendered depth (not
             with targets alone).
+        Mask supervision (the alpha output A = 1 - T_final; the arguments are the opt-in):
+          grad_alphas (with grad_colors): fixed dL/d alpha per view, [1,H,W] or [H,W]: the alpha-mode backward of every view
+            (lr_views_accumulate_alpha; with grad_depths too, the depth + alpha one);
+          masks (with targets): content masks per view, [1,H,W] or [H,W] in [0, 1] (loss.content_mask).  Each view's loss is
+            masked_l1_dssim(image, target, mask) + depth_weight * depth_l1 (with depth_targets) + alpha_weight *
+            alpha_hole(A, mask), alpha_weight default 1.0, >= 0; `self.losses` is [n,5]: loss, l1, ssim (of the masked pair),
+            depth_l1 (0 without depth_targets), alpha_hole (lr_views_train_mask_accumulate).  alpha_weight 0 reports
+            alpha_hole with the gradients of the step without it.
+          alphas: per-view [1,H,W] or [H,W] contiguous float32 device tensors that run() fills with A (with grad_alphas or
+            masks only).
         Arguments are checked before any device work."""
         import ctypes
         import math
@@ -887,7 +899,11 @@ class ViewBatch:
             raise ValueError("one grad_colors / targets entry per camera, and at least one camera")
         self.W, self.H = int(self.cams[0].image_width), int(self.cams[0].image_height)
         self.train_depth = depth_targets is not None
-        self._check_depth_args(grad_colors, targets, grad_depths, depth_targets, depth_weight, depths)
+        self._check_depth_args(grad_colors, targets, grad_depths, depth_targets, depth_weight, depths,
+                               allow_depths=masks is not None)
+        self.train_mask = masks is not None
+        self.alpha_mode = grad_alphas is not None
+        self._check_alpha_args(grad_colors, targets, grad_alphas, masks, alpha_weight, alphas)
         from . import _lib
         self._lib = _lib
         self.L = _lib.lib()
@@ -913,8 +929,14 @@ class ViewBatch:
         self._dgrads = ptr_array(depth_in) if depth_in is not None else (ctypes.c_void_p * self.n)()
         self.depths = list(depths) if depths is not None else None
         self._depths = (ctypes.c_void_p * self.n)(*[t.data_ptr() for t in self.depths]) if depths is not None else None
-        self.losses = torch.zeros((self.n, 4 if self.train_depth else 3), dtype=torch.float32, device=self.device) \
-            if self.train else None
+        # per-view dL/dalpha or content masks; alpha outputs
+        self.alpha_weight = (1.0 if alpha_weight is None else float(alpha_weight)) if self.train_mask else 0.0
+        alpha_in = grad_alphas if grad_alphas is not None else masks
+        self._agrads = ptr_array(alpha_in) if alpha_in is not None else None
+        self.alphas = list(alphas) if alphas is not None else None
+        self._alphas = (ctypes.c_void_p * self.n)(*[t.data_ptr() for t in self.alphas]) if alphas is not None else None
+        n_losses = 5 if self.train_mask else 4 if self.train_depth else 3
+        self.losses = torch.zeros((self.n, n_losses), dtype=torch.float32, device=self.device) if self.train else None
         self._tanx = (ctypes.c_float * self.n)(*[math.tan(c.FoVx * 0.5) for c in self.cams])
         self._tany = (ctypes.c_float * self.n)(*[math.tan(c.FoVy * 0.5) for c in self.cams])
         self._keep = keep
@@ -922,11 +944,12 @@ class ViewBatch:
         self._ws_key = None
         L = self.L
         self._ws_bytes, self._ws_check = (
+            (L.lr_views_train_mask_workspace_bytes, L.lr_views_train_mask_check) if self.train_mask else
             (L.lr_views_train_depth_workspace_bytes, L.lr_views_train_depth_check) if self.train_depth else
             (L.lr_views_train_workspace_bytes, L.lr_views_train_check) if self.train else
             (L.lr_views_workspace_bytes, L.lr_views_check))
 
-    def _check_depth_args(self, grad_colors, targets, grad_depths, depth_targets, depth_weight, depths):
+    def _check_depth_args(self, grad_colors, targets, grad_depths, depth_targets, depth_weight, depths, allow_depths=False):
         import math
         if grad_depths is not None and grad_colors is None:
             raise ValueError("grad_depths goes with grad_colors (fixed upstream gradients); with targets give depth_targets")
@@ -938,7 +961,7 @@ class ViewBatch:
             w = float(depth_weight)
             if not (math.isfinite(w) and w >= 0.0):
                 raise ValueError(f"depth_weight must be finite and >= 0, got {depth_weight}")
-        if depths is not None and targets is not None and depth_targets is None:
+        if depths is not None and targets is not None and depth_targets is None and not allow_depths:
             raise ValueError("depths= with targets needs depth_targets (the colour-only training step returns no depth)")
         shape_ok = lambda t: isinstance(t, torch.Tensor) and tuple(t.shape) in ((self.H, self.W), (1, self.H, self.W))
         for name, seq in (("grad_depths", grad_depths), ("depth_targets", depth_targets), ("depths", depths)):
@@ -953,6 +976,36 @@ class ViewBatch:
                                      f"got {tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__}")
                 if name == "depths" and not (t.is_cuda and t.dtype is torch.float32 and t.is_contiguous()):
                     raise ValueError("depths: outputs must be contiguous float32 tensors on the HIP device")
+
+    def _check_alpha_args(self, grad_colors, targets, grad_alphas, masks, alpha_weight, alphas):
+        import math
+        if grad_alphas is not None and grad_colors is None:
+            raise ValueError("grad_alphas goes with grad_colors (fixed upstream gradients); with targets give masks")
+        if masks is not None and targets is None:
+            raise ValueError("masks goes with targets (the fused training step); with grad_colors give grad_alphas")
+        if alpha_weight is not None:
+            if masks is None:
+                raise ValueError("alpha_weight needs masks")
+            w = float(alpha_weight)
+            if not (math.isfinite(w) and w >= 0.0):
+                raise ValueError(f"alpha_weight must be finite and >= 0, got {alpha_weight}")
+        if alphas is not None and grad_alphas is None and masks is None:
+            raise ValueError("alphas= needs grad_alphas or masks (a step without them renders no alpha)")
+        shape_ok = lambda t: isinstance(t, torch.Tensor) and tuple(t.shape) in ((self.H, self.W), (1, self.H, self.W))
+        for name, seq in (("grad_alphas", grad_alphas), ("masks", masks), ("alphas", alphas)):
+            if seq is None:
+                continue
+            seq = list(seq)
+            if len(seq) != self.n:
+                raise ValueError(f"{name}: {len(seq)} entries for {self.n} views")
+            for t in seq:
+                if not shape_ok(t):
+                    raise ValueError(f"{name}: every entry must be a [1,H,W] or [H,W] tensor with H,W = {self.H},{self.W}, "
+                                     f"got {tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__}")
+                if name == "alphas" and not (t.is_cuda and t.dtype is torch.float32 and t.is_contiguous()):
+                    raise ValueError("alphas: outputs must be contiguous float32 tensors on the HIP device")
+                if name == "masks" and t.dtype is not torch.float32:
+                    raise ValueError("masks: float32 tensors (loss.content_mask)")
 
     def run(self, means3D, opacities, scales, rotations, shs, acc: dict):
         """acc: {"means3D", "means2D", "opacity", "sh", "scales", "rotations"} -> contiguous float32 tensors that are
@@ -971,6 +1024,19 @@ class ViewBatch:
 
     def _run(self, P, M, means3D, opacities, scales, rotations, shs, acc):
         stream = torch.cuda.current_stream(self.device).cuda_stream
+        if self.train_mask:
+            rc = self.L.lr_views_train_mask_accumulate(
+                self.n, self._views, self._projs, self._campos, self._tanx, self._tany, P, self.degree, M,
+                self.bg.data_ptr(), self.W, self.H, means3D.data_ptr(), shs.data_ptr(), opacities.data_ptr(),
+                scales.data_ptr(), self.scale_modifier, rotations.data_ptr(), self._grads, self.lambda_dssim,
+                self._agrads, self.alpha_weight, self._dgrads if self.train_depth else None, self.depth_weight,
+                self.losses.data_ptr(), None, self._depths, self._alphas, None,
+                acc["means2D"].data_ptr(), acc["opacity"].data_ptr(), acc["means3D"].data_ptr(), acc["sh"].data_ptr(),
+                acc["scales"].data_ptr(), acc["rotations"].data_ptr(),
+                self._ws.data_ptr(), self._ws.numel(), self.capacity, self.n_streams, stream)
+            if rc < 0:
+                self._lib.raise_for(rc, "lr_views_train_mask_accumulate")
+            return
         if self.train_depth:
             rc = self.L.lr_views_train_depth_accumulate(
                 self.n, self._views, self._projs, self._campos, self._tanx, self._tany, P, self.degree, M,
@@ -993,6 +1059,17 @@ class ViewBatch:
                 self._ws.data_ptr(), self._ws.numel(), self.capacity, self.n_streams, stream)
             if rc < 0:
                 self._lib.raise_for(rc, "lr_views_train_accumulate")
+            return
+        if self.alpha_mode:
+            rc = self.L.lr_views_accumulate_alpha(
+                self.n, self._views, self._projs, self._campos, self._tanx, self._tany, P, self.degree, M,
+                self.bg.data_ptr(), self.W, self.H, means3D.data_ptr(), shs.data_ptr(), None, opacities.data_ptr(),
+                scales.data_ptr(), self.scale_modifier, rotations.data_ptr(), None, self._grads, self._dgrads, self._agrads,
+                None, self._depths, self._alphas, None, acc["means2D"].data_ptr(), acc["opacity"].data_ptr(), None,
+                acc["means3D"].data_ptr(), None, acc["sh"].data_ptr(), acc["scales"].data_ptr(), acc["rotations"].data_ptr(),
+                self._ws.data_ptr(), self._ws.numel(), self.capacity, self.n_streams, stream)
+            if rc < 0:
+                self._lib.raise_for(rc, "lr_views_accumulate_alpha")
             return
         rc = self.L.lr_views_accumulate_depth(
             self.n, self._views, self._projs, self._campos, self._tanx, self._tany, P, self.degree, M,
