@@ -86,6 +86,7 @@ def train(args, log=print):
     # no host round trip per forward ("Host sync"); instance counts drift while the cloud is
     # optimised, so the capacity is taken over the views of the path, with generous headroom
     config.set_async(not args.exact, headroom=1.5, warm_calls=len(cams))     # overflowed views are re-rendered (default policy)
+    config.set_antialiasing(args.antialiasing)     # opacity compensation for the 2D dilation; render the result with it on too
     losses = []
     gen = torch.Generator().manual_seed(0)
     torch.cuda.synchronize()
@@ -109,13 +110,14 @@ def train(args, log=print):
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     config.set_async(True)              # back to the library defaults
+    config.set_antialiasing(False)
     log(f"{args.iters} iterations in {dt:.2f} s = {dt / args.iters * 1e3:.3f} ms/iteration")
     return losses, dt
 
 
 def default_args(**kw):
     d = dict(gaussians=200_000, iters=300, resolution="512x512", views=12, lambda_dssim=0.2, log=50, densify_from=100,
-             densify_every=100, densify_until=10_000, exact=False, torch_adam=False)
+             densify_every=100, densify_until=10_000, exact=False, torch_adam=False, antialiasing=False)
     d.update(kw)
     return SimpleNamespace(**d)
 

@@ -793,6 +793,22 @@ void lr_backward_wait_event(void* event);
  * diagnostics build (-DLR_DIAGNOSTICS, `python -m luciddreamer_amd.build --diagnostics`; lr_version() then says "+diagnostics");
  * the product library rejects them with LR_ERR_INVALID_ARG and reads no environment variable. */
 int lr_tune_set(const char* name, int value);
+/* Anti-aliasing (the `antialiasing` switch of the upstream 3DGS rasterizer, the 2D Mip filter of Mip-Splatting).  Preprocess
+ * dilates every screen-space covariance {a0, b, c0} by h = 0.3 on its diagonal; with the setting on it also multiplies the
+ * opacity it stores for the blend by
+ *     coef = sqrt(max(0.000025, det0 / det)),   det0 = a0 c0 - b b,   det = (a0 + h)(c0 + h) - b b,
+ * so that a splat smaller than a pixel is dimmed by as much as the dilation spreads it.  Radii, tile rectangles, conics and
+ * depths do not move; colour, depth, alpha and every gradient follow from the scaled opacity (the backward adds the
+ * coefficient's derivative with respect to the covariance to dL/dmeans3D, dL/dscales, dL/drotations or dL/dcov3D).
+ * A PROCESS-WIDE setting (not per thread: an autograd engine runs backwards on threads other than the forward's), 0 = off by
+ * default, and then no output differs by a bit from a library without it.  Unlike lr_tune_set it changes results.  Every entry
+ * point reads it once when it starts: lr_forward[_raw], every lr_backward*, and every view of the lr_views_* family.
+ * CONTRACT: a view's backward must run under the setting its forward ran under -- the geom buffer holds the scaled opacity and
+ * nothing records which kind it is; the gradients of a mixed pair are silently wrong.  (luciddreamer_amd's autograd functions
+ * remember the forward's setting and raise instead.)  Do not toggle it while an lr_views_* call is running.
+ * lr_set_antialiasing returns the previous value. */
+int lr_set_antialiasing(int on);
+int lr_get_antialiasing(void);
 /* Kernel shapes of the process's last blend launches (either pointer may be NULL): forward 0 quadrant kernel, 1 with
  * candidate pairs, 2 one wave per tile; backward 0 two waves per tile, 1 four, 2 one; -1 = none yet.  For tests that must
  * know WHICH kernels a configuration ran (e.g. that the headline's step ran the one-wave-per-tile pair). */

@@ -40,7 +40,7 @@ EXPORTS = ("lr_last_error", "lr_version", "lr_geom_bytes", "lr_img_bytes", "lr_b
            "lr_video_workspace_bytes", "lr_frames_to_u8", "lr_depth_colorize",
            "lr_masked_l1_dssim_forward", "lr_masked_l1_dssim_backward", "lr_alpha_hole_workspace_bytes", "lr_alpha_hole_forward",
            "lr_alpha_hole_backward", "lr_views_accumulate_alpha", "lr_views_train_mask_workspace_bytes",
-           "lr_views_train_mask_accumulate", "lr_views_train_mask_check")
+           "lr_views_train_mask_accumulate", "lr_views_train_mask_check", "lr_set_antialiasing", "lr_get_antialiasing")
 
 
 def assert_single_copy():
@@ -235,6 +235,10 @@ def lib():
         L.lr_forward_ticket.argtypes = []
         L.lr_tune_set.restype = ci
         L.lr_tune_set.argtypes = [ctypes.c_char_p, ci]
+        L.lr_set_antialiasing.restype = ci
+        L.lr_set_antialiasing.argtypes = [ci]
+        L.lr_get_antialiasing.restype = ci
+        L.lr_get_antialiasing.argtypes = []
         L.lr_last_launch_shapes.restype = ci
         L.lr_last_launch_shapes.argtypes = [ctypes.POINTER(ci), ctypes.POINTER(ci)]
         L.lr_profile_enable.restype = ci

@@ -163,12 +163,44 @@ def depth_gradient() -> bool:
     return _depth_gradient
 
 
+def set_antialiasing(enabled: bool):
+    """Anti-aliased splatting (off by default; process-wide; lr_set_antialiasing).  Preprocess dilates every screen-space
+    covariance by 0.3 px^2 and leaves the opacity as it was, so a splat smaller than a pixel deposits more energy than it holds:
+    thin structures fatten and brighten when the camera recedes.  With the switch on the opacity the blend sees is
+    opacity * sqrt(max(0.000025, det(cov2D) / det(cov2D + 0.3 I))) -- the `antialiasing` option of the upstream 3DGS rasterizer
+    (the 2D Mip filter of Mip-Splatting).  Radii, tile rectangles and conics do not move; colour, depth, alpha and all gradients
+    follow, the coefficient's own derivative reaching means3D and scales / rotations (or cov3D_precomp).  Every path honours it:
+    both operators, render / render_raw, ViewStreams, ViewBatch, render_video_frames, the drop-in.  The setting lives in the
+    library, not in this module, so that backwards run by the autograd engine's threads see it.  A view's backward must run
+    under the setting of its forward: the autograd nodes remember it and raise RuntimeError otherwise.  A model trained with
+    the switch on should be rendered with it on.  INTEGRATION.md 2f."""
+    from . import _lib
+    _lib.lib().lr_set_antialiasing(1 if enabled else 0)
+
+
+def antialiasing() -> bool:
+    from . import _lib
+    return _lib.lib().lr_get_antialiasing() != 0
+
+
+def require_antialiasing(at_forward: bool):
+    """Called by a backward before it launches anything: raises when the switch is not what it was at the node's forward."""
+    now = antialiasing()
+    if now != bool(at_forward):
+        raise RuntimeError(f"luciddreamer_amd: anti-aliasing was {'on' if at_forward else 'off'} at this view's forward and is "
+                           f"{'on' if now else 'off'} at its backward (config.set_antialiasing): a view's backward must run "
+                           "under the setting of its forward")
+
+
 def is_async() -> bool:
     return _async
 
 
 def reset():
     drain()
+    from . import _lib
+    if _lib._lib is not None:             # (a process that never loaded the library has nothing to turn off)
+        set_antialiasing(False)
     _hwm.clear()
     _seen.clear()
 

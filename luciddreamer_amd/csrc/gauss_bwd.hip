@@ -119,7 +119,10 @@ __device__ __forceinline__ float row_sum(float v)
 // DEPTH (k_gauss_bwd_depth): g2.y is the Gaussian's dL/d(view depth) from the depth-mode blend backward; it reaches the mean
 // through z = view[2] x + view[6] y + view[10] z + view[14] (column-major view matrix, auxiliary.h:58-66) -- in the raw path
 // the same term is dL/dxyz.
-template <bool RAW, bool DEPTH = false>
+// AA (the view's forward ran anti-aliased, common.h aa_coef): the record's opacity is opacity * coef(a0, b, c0), so g1.y is
+// dL/d(record opacity): dL/dopacity = g coef, and dL/drho = g rec_opacity / (2 rho) above the floor reaches the 2D covariance
+// next to the conic's terms.  rec_opacity: the record's opacity (non-raw: read from the geom buffer by the caller; raw: recomputed).
+template <bool RAW, bool DEPTH = false, bool AA = false>
 __device__ __forceinline__ void
 gauss_backward_one(const int idx, const ViewParams& vp, const float* __restrict__ means3D, const float* __restrict__ scales,
             const float* __restrict__ rotations, const bool have_sh, const V3 dL_ddir,
@@ -127,7 +130,7 @@ gauss_backward_one(const int idx, const ViewParams& vp, const float* __restrict_
             float* __restrict__ dL_dmean2D, float* __restrict__ dL_dconic, float* __restrict__ dL_dopacity,
             float* __restrict__ dL_dcolor, float* __restrict__ dL_dmean3D, float* __restrict__ dL_dcov3D,
             float* __restrict__ dL_dscale, float* __restrict__ dL_drot,
-            uint32_t accum_mask, float* __restrict__ acc16)
+            uint32_t accum_mask, float* __restrict__ acc16, const float rec_opacity = 0.f)
 {
     const size_t i = (size_t)idx;
     const float* __restrict__ V = vp.view;
@@ -199,10 +202,25 @@ gauss_backward_one(const int idx, const ViewParams& vp, const float* __restrict_
         const float denom = a * c - b * b;
         float dL_da = 0, dL_db = 0, dL_dc = 0;
         const float denom2inv = 1.0f / ((denom * denom) + 0.0000001f);
+        AACoef aa = { 0.f, 1.f, 1.f };
+        float aa_drho = 0.f;
+        if constexpr (AA) {
+            aa = aa_coef(cov2D.c[0][0], b, cov2D.c[1][1], denom);
+            const float rec_op = RAW ? act_opacity(vp.opacity_raw[i]) * aa.coef : rec_opacity;
+            aa_drho = aa.rho > AA_RHO_FLOOR ? o_op * rec_op / (2.f * aa.rho) : 0.f;      // o_op is still dL/d(record opacity)
+            o_op *= aa.coef;
+        }
         if (denom2inv != 0) {
             dL_da = denom2inv * (-c * c * gca + 2 * b * c * gcb + (denom - a * c) * gcc);
             dL_dc = denom2inv * (-a * a * gcc + 2 * a * b * gcb + (denom - a * c) * gca);
             dL_db = denom2inv * 2 * (b * c * gca - (denom + 2 * b * b) * gcb + a * b * gcc);
+            if constexpr (AA) {
+                // rho = det0 / det, det0 = a0 c0 - b b, det = (a0 + h)(c0 + h) - b b; b is the one scalar dL_db refers to
+                const float k = aa_drho / (denom * denom);
+                dL_da += k * (cov2D.c[1][1] * denom - aa.det0 * c);
+                dL_dc += k * (cov2D.c[0][0] * denom - aa.det0 * a);
+                dL_db += k * (-2.f * b * (denom - aa.det0));
+            }
             o_cov[0] = (T.c[0][0] * T.c[0][0] * dL_da + T.c[0][0] * T.c[1][0] * dL_db + T.c[1][0] * T.c[1][0] * dL_dc);
             o_cov[3] = (T.c[0][1] * T.c[0][1] * dL_da + T.c[0][1] * T.c[1][1] * dL_db + T.c[1][1] * T.c[1][1] * dL_dc);
             o_cov[5] = (T.c[0][2] * T.c[0][2] * dL_da + T.c[0][2] * T.c[1][2] * dL_db + T.c[1][2] * T.c[1][2] * dL_dc);
@@ -369,7 +387,8 @@ __device__ __forceinline__ float wave_sum(float v)
             float* __restrict__ dL_dsh, float* __restrict__ dL_dscale, float* __restrict__ dL_drot,                             \
             uint32_t accum_mask, float* __restrict__ acc16
 
-template <bool RAW>
+// AA: the anti-aliased instantiations (gauss_backward_one); <RAW, false> is the kernel as it was
+template <bool RAW, bool AA>
 __global__ void __launch_bounds__(GB_THREADS) __attribute__((amdgpu_waves_per_eu(LR_GB_WAVES, 8)))
 k_gauss_bwd(LR_GB_PARAMS)
 {
@@ -377,7 +396,7 @@ k_gauss_bwd(LR_GB_PARAMS)
 #include "gauss_bwd_body.h"
 }
 // depth mode (lr_backward_depth / lr_backward_raw_depth): its own entry point, so that k_gauss_bwd keeps its instruction stream
-template <bool RAW>
+template <bool RAW, bool AA>
 __global__ void __launch_bounds__(GB_THREADS) __attribute__((amdgpu_waves_per_eu(LR_GB_WAVES, 8)))
 k_gauss_bwd_depth(LR_GB_PARAMS)
 {
@@ -440,30 +459,25 @@ void launch_gauss_bwd(const ViewParams& vp, const float* means3D, const float* s
                       const char* bin_base, const GeomHeader* hdr,
                       float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor,
                       float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot,
-                      uint32_t accum_mask, float* acc16, hipStream_t s, bool depth)
+                      uint32_t accum_mask, float* acc16, hipStream_t s, bool depth, bool antialiasing)
 {
     (void)colors_precomp;
     if (vp.P <= 0) return;
     const int groups = std::min((vp.P + GB_THREADS - 1) / GB_THREADS, GB_MAX_GROUPS);
-    if (depth) {
-        if (vp.raw)
-            hipLaunchKernelGGL(k_gauss_bwd_depth<true>, dim3(groups), dim3(GB_THREADS), 0, s, vp, means3D, scales, rotations, shs,
-                               cov3D_precomp, vis_list, clamped, offsets, bin_base, hdr, dL_dmean2D, dL_dconic,
-                               dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, accum_mask, acc16);
-        else
-            hipLaunchKernelGGL(k_gauss_bwd_depth<false>, dim3(groups), dim3(GB_THREADS), 0, s, vp, means3D, scales, rotations, shs,
-                               cov3D_precomp, vis_list, clamped, offsets, bin_base, hdr, dL_dmean2D, dL_dconic,
-                               dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, accum_mask, acc16);
-        return;
+#define LR_GB(KERNEL_, RAW_, AA_) hipLaunchKernelGGL((KERNEL_<RAW_, AA_>), dim3(groups), dim3(GB_THREADS), 0, s, vp, means3D, scales,  \
+                               rotations, shs, cov3D_precomp, vis_list, clamped, offsets, bin_base, hdr, dL_dmean2D, dL_dconic,     \
+                               dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, accum_mask, acc16)
+    switch ((vp.raw ? 1 : 0) | (antialiasing ? 2 : 0) | (depth ? 4 : 0)) {
+        case 0: LR_GB(k_gauss_bwd, false, false); break;
+        case 1: LR_GB(k_gauss_bwd, true, false); break;
+        case 2: LR_GB(k_gauss_bwd, false, true); break;
+        case 3: LR_GB(k_gauss_bwd, true, true); break;
+        case 4: LR_GB(k_gauss_bwd_depth, false, false); break;
+        case 5: LR_GB(k_gauss_bwd_depth, true, false); break;
+        case 6: LR_GB(k_gauss_bwd_depth, false, true); break;
+        default: LR_GB(k_gauss_bwd_depth, true, true); break;
     }
-    if (vp.raw)
-        hipLaunchKernelGGL(k_gauss_bwd<true>, dim3(groups), dim3(GB_THREADS), 0, s, vp, means3D, scales, rotations, shs,
-                           cov3D_precomp, vis_list, clamped, offsets, bin_base, hdr, dL_dmean2D, dL_dconic,
-                           dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, accum_mask, acc16);
-    else
-        hipLaunchKernelGGL(k_gauss_bwd<false>, dim3(groups), dim3(GB_THREADS), 0, s, vp, means3D, scales, rotations, shs,
-                           cov3D_precomp, vis_list, clamped, offsets, bin_base, hdr, dL_dmean2D, dL_dconic,
-                           dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, accum_mask, acc16);
+#undef LR_GB
 }
 
 namespace {

@@ -1,7 +1,8 @@
 // gauss_bwd_body.h -- the body of the per-Gaussian backward kernels k_gauss_bwd and k_gauss_bwd_depth (gauss_bwd.hip),
-// included INSIDE each of them with `RAW` (template parameter) and `DEPTH` (constexpr bool) in scope.  Textual inclusion, not an
+// included INSIDE each of them with `RAW`, `AA` (template parameters) and `DEPTH` (constexpr bool) in scope.  Textual inclusion, not an
 // inlined __device__ function: the function form changed k_gauss_bwd's instruction stream (operand order of its slot sums), and
 // the default kernel must stay instruction for instruction what it was.  DEPTH: the slots' dL/d(view depth) float is summed too.
+// AA && !RAW: the record's opacity (opacity * coef, what the blend saw) is read from the geom buffer, whose first bytes are `hdr`.
 // NOT a stand-alone header (no include guard on purpose).
     constexpr uint32_t SERIAL_MAX = 24;      // instances summed by the owning lane; more -> whole wave helps
     constexpr int BST = 17;                  // LDS row stride (floats) of the per-Gaussian basis rows: odd -> no conflicts
@@ -24,6 +25,12 @@
         const bool live = t < n;
         const int idx = live ? (int)vis_list[t] : 0;
         s_idx[lane] = (uint32_t)idx;
+        float rec_opacity = 0.f;
+        if constexpr (AA && !RAW) {
+            // geom_layout (common.h): the records follow the 256-byte header
+            const GaussRec* __restrict__ rec = reinterpret_cast<const GaussRec*>(reinterpret_cast<const char*>(hdr) + align_up(sizeof(GeomHeader)));
+            if (live) rec_opacity = rec[idx].opacity;
+        }
         // first instance slot and instance count from the rank-ordered `offsets` (dense reads: neighbouring lanes read
         // neighbouring words) instead of goff[idx] / tiles_touched[idx] -- two more 64-byte lines per visible Gaussian for
         // 4 useful bytes each when ~9 % of the Gaussians are visible
@@ -158,8 +165,8 @@
             if (live) dL_ddir = { s_ddir[0][lane], s_ddir[1][lane], s_ddir[2][lane] };
         }
         if (live)
-            gauss_backward_one<RAW, DEPTH>(idx, vp, means3D, scales, rotations, have_sh, dL_ddir, cov3D_precomp, g0, g1, g2,
+            gauss_backward_one<RAW, DEPTH, AA>(idx, vp, means3D, scales, rotations, have_sh, dL_ddir, cov3D_precomp, g0, g1, g2,
                                dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dscale,
-                               dL_drot, accum_mask, acc16);
+                               dL_drot, accum_mask, acc16, rec_opacity);
         lds_barrier();                     // the LDS planes are rewritten by the next round
     }

@@ -144,7 +144,8 @@ __device__ __forceinline__ void tile_rect(float px, float py, int radius, int gx
 constexpr int PP_THREADS = 128;                 // Gaussians per workgroup (measured: 64 -> 0.047, 128 -> 0.039, 256 -> 0.042, 512 -> 0.042 ms on C3)
 constexpr int PP_WAVES = PP_THREADS / 64;
 
-template <bool RAW>
+// AA (lr_set_antialiasing): the record's opacity is opacity * aa_coef(...).coef (common.h); nothing else differs
+template <bool RAW, bool AA>
 __global__ void __launch_bounds__(PP_THREADS)
 k_preprocess(ViewParams vp, const float* __restrict__ means3D, const float* __restrict__ scales,
              const float* __restrict__ rotations, const float* __restrict__ opacities,
@@ -288,6 +289,7 @@ k_preprocess(ViewParams vp, const float* __restrict__ means3D, const float* __re
         GaussRec g;
         g.x = pix; g.y = piy; g.ca = con_a; g.cb = con_b;
         g.cc = con_c; g.opacity = RAW ? act_opacity(opacities[idx]) : opacities[idx]; g.r = rgb.x; g.g = rgb.y;
+        if constexpr (AA) g.opacity = g.opacity * aa_coef(cov.c[0][0], cb, cov.c[1][1], det).coef;
         g.b = rgb.z; g.depth = vz; g.qmax = cull_qmax(g.opacity); g.pad1 = 0.f;
         float4* dst = reinterpret_cast<float4*>(rec + idx);
         dst[0] = make_float4(g.x, g.y, g.ca, g.cb);
@@ -359,10 +361,10 @@ constexpr int PL_POOL = 512;
 constexpr int PL_WAVES = PL_THREADS / 64;
 constexpr int PL_ROUNDS = PL_POOL / PL_THREADS;
 
-struct Projected { float pix, piy, con_a, con_b, con_c, vz; int radius; };
+struct Projected { float pix, piy, con_a, con_b, con_c, vz; int radius; float coef; };   // coef: anti-aliased kernels only
 
 // forward.cu:196-232 for one Gaussian that passed the near plane.  false: culled (det == 0 or empty tile rectangle).
-template <bool RAW>
+template <bool RAW, bool AA>
 __device__ __forceinline__ bool project_gaussian(const ViewParams& vp, int idx, const float* __restrict__ means3D,
                                                  const float* __restrict__ scales, const float* __restrict__ rotations,
                                                  const float* __restrict__ cov3D_precomp, Projected& out)
@@ -424,6 +426,7 @@ __device__ __forceinline__ bool project_gaussian(const ViewParams& vp, int idx, 
     if (det == 0.0f) return false;
     const float det_inv = 1.f / det;
     out.con_a = cc * det_inv; out.con_b = -cb * det_inv; out.con_c = ca * det_inv;
+    if constexpr (AA) out.coef = aa_coef(cov.c[0][0], cb, cov.c[1][1], det).coef;
 
     const float mid = 0.5f * (ca + cc);                    // forward.cu:229-232
     const float lambda1 = mid + sqrtf(fmaxf(0.1f, mid * mid - det));
@@ -441,7 +444,7 @@ __device__ __forceinline__ bool project_gaussian(const ViewParams& vp, int idx, 
 
 // forward.cu:236-255 for a survivor: colour and record.  Returns the tile rectangle (origin, width, area) and the cull
 // threshold for the exact tile count that follows.
-template <bool RAW>
+template <bool RAW, bool AA>
 __device__ __forceinline__ void colour_and_record(const ViewParams& vp, int idx, const Projected& pj,
                                                   const float* __restrict__ means3D, const float* __restrict__ opacities,
                                                   const float* __restrict__ shs, const float* __restrict__ colors_precomp,
@@ -471,7 +474,8 @@ __device__ __forceinline__ void colour_and_record(const ViewParams& vp, int idx,
     }
     clamped[idx] = cbits;
 
-    const float opacity = RAW ? act_opacity(opacities[idx]) : opacities[idx];
+    float opacity = RAW ? act_opacity(opacities[idx]) : opacities[idx];
+    if constexpr (AA) opacity = opacity * pj.coef;
     qmax = cull_qmax(opacity);
     float4* dst = reinterpret_cast<float4*>(rec + idx);
     dst[0] = make_float4(pj.pix, pj.piy, pj.con_a, pj.con_b);
@@ -480,7 +484,8 @@ __device__ __forceinline__ void colour_and_record(const ViewParams& vp, int idx,
 }
 
 // 5 workgroups per CU (29.7 KB of LDS each; 80 VGPRs, no scratch); the split SH loader of raw mode needs 126 registers
-template <bool RAW>
+// AA: one more parked plane (the coefficient of phase 2 for phase 3a), 31.7 KB: five workgroups still fit the CU's 160 KB
+template <bool RAW, bool AA>
 __global__ void __launch_bounds__(PL_THREADS) __attribute__((amdgpu_waves_per_eu(RAW ? 4 : 5, 8)))
 k_preprocess_pool(ViewParams vp, const float* __restrict__ means3D, const float* __restrict__ scales,
                   const float* __restrict__ rotations, const float* __restrict__ opacities,
@@ -494,6 +499,7 @@ k_preprocess_pool(ViewParams vp, const float* __restrict__ means3D, const float*
     __shared__ int s_radius[PL_POOL];                        // results of the whole pool (0 for everything culled)
     __shared__ uint32_t s_tiles[PL_POOL];
     __shared__ float s_mid[6][PL_POOL];                      // parked survivors of phase 2: pix, piy, conic a b c, vz (3b: qmax)
+    __shared__ float s_coef[AA ? PL_POOL : 1];               // ... their anti-aliasing coefficient (AA kernels only)
     __shared__ uint32_t s_mid_id[PL_POOL];                   // ... and their pool-local ids
     __shared__ uint32_t s_tests[PL_POOL];                    // tile tests per survivor -> inclusive prefix
     __shared__ uint2 s_rect[PL_POOL];                        // tile rectangle of a survivor: min x | min y << 16, width
@@ -542,7 +548,7 @@ k_preprocess_pool(ViewParams vp, const float* __restrict__ means3D, const float*
         uint32_t loc = 0;
         if (i < n_near) {
             loc = s_near[i];
-            ok = project_gaussian<RAW>(vp, base + (int)loc, means3D, scales, rotations, cov3D_precomp, pj);
+            ok = project_gaussian<RAW, AA>(vp, base + (int)loc, means3D, scales, rotations, cov3D_precomp, pj);
         }
         const uint64_t mk = __ballot(ok);
         uint32_t wbase = 0;
@@ -552,6 +558,7 @@ k_preprocess_pool(ViewParams vp, const float* __restrict__ means3D, const float*
             const uint32_t slot = wbase + (uint32_t)__popcll(mk & ((1ull << l) - 1ull));
             s_mid[0][slot] = pj.pix; s_mid[1][slot] = pj.piy; s_mid[2][slot] = pj.con_a; s_mid[3][slot] = pj.con_b;
             s_mid[4][slot] = pj.con_c; s_mid[5][slot] = pj.vz;
+            if constexpr (AA) s_coef[slot] = pj.coef;
             s_mid_id[slot] = loc; s_radius[loc] = pj.radius;
         }
     }
@@ -567,10 +574,11 @@ k_preprocess_pool(ViewParams vp, const float* __restrict__ means3D, const float*
             Projected pj;
             pj.pix = s_mid[0][i]; pj.piy = s_mid[1][i]; pj.con_a = s_mid[2][i]; pj.con_b = s_mid[3][i];
             pj.con_c = s_mid[4][i]; pj.vz = s_mid[5][i];
+            if constexpr (AA) pj.coef = s_coef[i];
             const uint32_t loc = s_mid_id[i];
             pj.radius = s_radius[loc];
             int minx, miny, width; uint32_t area; float qmax;
-            colour_and_record<RAW>(vp, base + (int)loc, pj, means3D, opacities, shs, colors_precomp, rec, clamped,
+            colour_and_record<RAW, AA>(vp, base + (int)loc, pj, means3D, opacities, shs, colors_precomp, rec, clamped,
                                    minx, miny, width, area, qmax);
             my_ref += area;
             // rectangles of more than CULL_MAX_TILES tiles are emitted unculled (common.h): nothing to test
@@ -673,7 +681,8 @@ void launch_preprocess(const ViewParams& vp, const float* means3D, const float* 
                        const float* opacities, const float* shs, const float* cov3D_precomp,
                        const float* colors_precomp, bool prefiltered, int* radii, GaussRec* rec,
                        uint8_t* clamped, uint32_t* tiles_touched, uint4* hitrec, uint32_t* depth_key,
-                       GeomHeader* hdr, uint32_t binning_capacity, uint32_t* chunk_sums, bool sparse_view_hint, hipStream_t s)
+                       GeomHeader* hdr, uint32_t binning_capacity, uint32_t* chunk_sums, bool sparse_view_hint, hipStream_t s,
+                       bool antialiasing)
 {
     static_assert(SCAN_TILE % PP_THREADS == 0, "a preprocess workgroup must lie inside one compaction chunk");
     static_assert(SCAN_TILE % PL_POOL == 0, "a preprocess pool must lie inside one compaction chunk");
@@ -683,27 +692,32 @@ void launch_preprocess(const ViewParams& vp, const float* means3D, const float* 
     // fraction of the last forward whose counts reached the host).  lr_tune_set("preprocess", 0 / 1) forces one (A/B runs).
     const int forced = tune_get(TUNE_PREPROCESS);
     const bool pooled = forced >= 0 ? forced != 0 : (sparse_view_hint && vp.P >= 400000);
+    const int variant = (vp.raw ? 1 : 0) | (antialiasing ? 2 : 0);
     if (pooled && depth_key == nullptr && vp.gx <= 65535 && vp.gy <= 65535) {
         dim3 grid((vp.P + PL_POOL - 1) / PL_POOL), block(PL_THREADS);
-        if (vp.raw)
-            hipLaunchKernelGGL(k_preprocess_pool<true>, grid, block, 0, s, vp, means3D, scales, rotations, opacities, shs,
-                               cov3D_precomp, colors_precomp, prefiltered ? 1 : 0, radii, rec, clamped, tiles_touched, hitrec,
-                               hdr, binning_capacity, chunk_sums);
-        else
-            hipLaunchKernelGGL(k_preprocess_pool<false>, grid, block, 0, s, vp, means3D, scales, rotations, opacities, shs,
-                               cov3D_precomp, colors_precomp, prefiltered ? 1 : 0, radii, rec, clamped, tiles_touched, hitrec,
-                               hdr, binning_capacity, chunk_sums);
+#define LR_PP_POOL(RAW_, AA_) hipLaunchKernelGGL((k_preprocess_pool<RAW_, AA_>), grid, block, 0, s, vp, means3D, scales, rotations, \
+                               opacities, shs, cov3D_precomp, colors_precomp, prefiltered ? 1 : 0, radii, rec, clamped,            \
+                               tiles_touched, hitrec, hdr, binning_capacity, chunk_sums)
+        switch (variant) {
+            case 0: LR_PP_POOL(false, false); break;
+            case 1: LR_PP_POOL(true, false); break;
+            case 2: LR_PP_POOL(false, true); break;
+            default: LR_PP_POOL(true, true); break;
+        }
+#undef LR_PP_POOL
         return;
     }
     dim3 grid((vp.P + PP_THREADS - 1) / PP_THREADS), block(PP_THREADS);
-    if (vp.raw)
-        hipLaunchKernelGGL(k_preprocess<true>, grid, block, 0, s, vp, means3D, scales, rotations, opacities, shs,
-                           cov3D_precomp, colors_precomp, prefiltered ? 1 : 0, radii, rec, clamped, tiles_touched,
-                           hitrec, depth_key, hdr, binning_capacity, chunk_sums);
-    else
-        hipLaunchKernelGGL(k_preprocess<false>, grid, block, 0, s, vp, means3D, scales, rotations, opacities, shs,
-                           cov3D_precomp, colors_precomp, prefiltered ? 1 : 0, radii, rec, clamped, tiles_touched,
-                           hitrec, depth_key, hdr, binning_capacity, chunk_sums);
+#define LR_PP(RAW_, AA_) hipLaunchKernelGGL((k_preprocess<RAW_, AA_>), grid, block, 0, s, vp, means3D, scales, rotations, opacities, \
+                           shs, cov3D_precomp, colors_precomp, prefiltered ? 1 : 0, radii, rec, clamped, tiles_touched, hitrec,    \
+                           depth_key, hdr, binning_capacity, chunk_sums)
+    switch (variant) {
+        case 0: LR_PP(false, false); break;
+        case 1: LR_PP(true, false); break;
+        case 2: LR_PP(false, true); break;
+        default: LR_PP(true, true); break;
+    }
+#undef LR_PP
 }
 
 void launch_mark_visible(int P, const float* means3D, const float* view, const float* proj, uint8_t* present,

@@ -463,6 +463,8 @@ struct RasterizeFn : public torch::autograd::Function<RasterizeFn> {
                                  bool prefiltered, int64_t binning_capacity, bool fused_accumulate, bool depth_gradient,
                                  bool alpha)
     {
+        // lr_set_antialiasing as this forward finds it: the geom buffer will hold opacities scaled under it (backward checks)
+        const int64_t antialiasing = lr_get_antialiasing();
         FwdResult r = rasterize_gaussians(bg, means3D, colors, opacities, scales, rotations, scale_modifier, cov3D, viewmatrix,
                                           projmatrix, tan_fovx, tan_fovy, H, W, sh, degree, campos, prefiltered, false,
                                           binning_capacity);
@@ -490,6 +492,7 @@ struct RasterizeFn : public torch::autograd::Function<RasterizeFn> {
         ctx->saved_data["num_rendered"] = std::get<0>(r);
         ctx->saved_data["capacity"] = binning_capacity;
         ctx->saved_data["fused"] = fused_accumulate;
+        ctx->saved_data["antialiasing"] = antialiasing;
         // config.set_depth_gradient, as it was at THIS forward: the depth output is kept for the backward's depth mode
         // and undefined output gradients stay undefined: a loss that does not use the depth output must reach the default kernels,
         // not the depth-mode ones with a materialised zero gradient (the switch off keeps torch's default, materialised zeros)
@@ -512,6 +515,12 @@ struct RasterizeFn : public torch::autograd::Function<RasterizeFn> {
 
     static variable_list backward(AutogradContext* ctx, variable_list grad_out)
     {
+        // before anything is launched or written: the gradients of a forward / backward pair under different settings would be
+        // silently wrong (lucid_raster.h lr_set_antialiasing)
+        TORCH_CHECK(lr_get_antialiasing() == ctx->saved_data["antialiasing"].toInt(),
+                    "luciddreamer_amd: anti-aliasing was ", ctx->saved_data["antialiasing"].toInt() ? "on" : "off",
+                    " at this view's forward and is ", lr_get_antialiasing() ? "on" : "off",
+                    " at its backward (config.set_antialiasing): a view's backward must run under the setting of its forward");
         const variable_list in = ctx->get_saved_variables();
         const at::Tensor &means3D = in[0], &sh = in[1], &colors = in[2], &scales = in[3], &rotations = in[4], &cov3D = in[5];
         auto& d = ctx->saved_data;

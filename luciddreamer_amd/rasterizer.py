@@ -101,6 +101,7 @@ class _RasterizeGaussians(torch.autograd.Function):
                 rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, rs.image_height, rs.image_width, sh,
                 rs.sh_degree, rs.campos, rs.prefiltered, rs.debug)
         capacity = config.capacity_for(means3D, rs)
+        ctx.antialiasing = config.antialiasing()        # as this forward finds it: backward checks (config.set_antialiasing)
         try:
             (num_rendered, color, depth, radii, geom, binning, img), capacity = _forward(
                 means3D, rs, capacity, lambda cap: _C.rasterize_gaussians(*args, binning_capacity=cap))
@@ -131,6 +132,7 @@ class _RasterizeGaussians(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_out_color, grad_radii, grad_depth, grad_alpha=None):
+        config.require_antialiasing(ctx.antialiasing)   # before anything is launched or written
         rs = ctx.raster_settings
         colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geom, binning, img = ctx.saved_tensors
         if grad_out_color is None:
@@ -205,6 +207,7 @@ class _RasterizeGaussiansRaw(torch.autograd.Function):
     @staticmethod
     def forward(ctx, xyz, means2D, features_dc, features_rest, opacity, scaling, rotation, raster_settings, return_alpha=False):
         rs = raster_settings
+        ctx.antialiasing = config.antialiasing()        # as _RasterizeGaussians
 
         def run(cap):
             return _C.rasterize_gaussians_raw(
@@ -229,6 +232,7 @@ class _RasterizeGaussiansRaw(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_out_color, grad_radii, grad_depth, grad_alpha=None):
+        config.require_antialiasing(ctx.antialiasing)   # before anything is launched or written
         rs = ctx.raster_settings
         xyz, features_dc, features_rest, opacity, scaling, rotation, radii, geom, binning, img = ctx.saved_tensors
         if grad_out_color is None:
