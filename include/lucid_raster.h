@@ -821,6 +821,12 @@ int lr_profile_read(double* ms_per_stage, long long* calls_per_stage, int n_stag
  * points [P,3] -> out [P].  workspace: lr_dist2_workspace_bytes(P) device bytes. */
 size_t lr_dist2_workspace_bytes(int P);
 int lr_dist2(int P, const float* points, float* out, char* workspace, void* stream);
+/* For tests of the Morton stage: byte offsets inside `workspace` of what lr_dist2 leaves there once its work on the stream is
+ * done -- offsets[0] the sorted 30-bit Morton keys (uint32 [P]), [1] the order (original index of every sorted position,
+ * uint32 [P]), [2] the points in that order (float4 [P]: x, y, z, the original index's bits), [3] the boxes (float [ceil(P/256)][8]:
+ * min xyz, unused, max xyz, unused; box b covers sorted positions 256 b .. 256 b + 255).  Pure host function; the layout is an
+ * implementation detail and may change with the library version. */
+int lr_dist2_workspace_layout(int P, size_t offsets[4]);
 
 #ifdef __cplusplus
 }

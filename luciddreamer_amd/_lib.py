@@ -29,6 +29,7 @@ _lock = threading.Lock()
 EXPORTS = ("lr_last_error", "lr_version", "lr_geom_bytes", "lr_img_bytes", "lr_binning_bytes", "lr_forward",
            "lr_backward", "lr_forward_raw", "lr_backward_raw", "lr_backward_depth", "lr_backward_raw_depth",
            "lr_backward_alpha", "lr_backward_raw_alpha", "lr_render_alpha", "lr_mark_visible", "lr_check", "lr_dist2_workspace_bytes", "lr_dist2",
+           "lr_dist2_workspace_layout",
            "lr_profile_enable", "lr_profile_stage_name", "lr_profile_read", "lr_tune_set", "lr_last_launch_shapes", "lr_request_early_header",
            "lr_take_early_ticket", "lr_forward_ticket", "lr_backward_wait_event", "lr_step_begin", "lr_step_end", "lr_step_abort",
            "lr_views_workspace_bytes", "lr_views_accumulate", "lr_views_check",
@@ -120,6 +121,8 @@ def lib():
         L.lr_dist2_workspace_bytes.argtypes = [ci]
         L.lr_dist2.restype = ci
         L.lr_dist2.argtypes = [ci, vp, vp, vp, vp]
+        L.lr_dist2_workspace_layout.restype = ci
+        L.lr_dist2_workspace_layout.argtypes = [ci, ctypes.POINTER(ctypes.c_size_t)]
         L.lr_views_workspace_bytes.restype = ctypes.c_size_t
         L.lr_views_workspace_bytes.argtypes = [ci, ci, ci, ll, ci]
         L.lr_views_accumulate.restype = ci

@@ -176,7 +176,8 @@ void radix_sort_pairs(uint32_t* key_a, uint32_t* key_b, uint32_t* val_a, uint32_
     const SortPlan plan = sort_plan(n_bound);
     uint32_t* totals = hist + (size_t)SORT_MAX_BLOCKS * RADIX_SIZE;
     bool first = true;
-    for (int shift = 0; shift < end_bit; shift += RADIX_BITS) {
+    for (int pass = 0; pass < radix_sort_passes(end_bit); pass++) {
+        const int shift = pass * RADIX_BITS;
         const int bits = (end_bit - shift) < RADIX_BITS ? (end_bit - shift) : RADIX_BITS;
         const uint32_t mask = (1u << bits) - 1u;
         hipLaunchKernelGGL(k_radix_hist, dim3(plan.nblocks), dim3(SORT_THREADS), 0, s, kin, n_dev, plan.chunk,

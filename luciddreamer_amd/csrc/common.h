@@ -391,6 +391,7 @@ void launch_mark_visible(int P, const float* means3D, const float* view, const f
 // Stable LSD radix sort of (key,val) u32 pairs on bits [0,end_bit).  n_dev: device count (may be
 // smaller than n_bound; blocks beyond it idle).  vals_in == nullptr means val = index (iota).
 // Returns which buffers hold the result via *keys_out / *vals_out.
+inline int radix_sort_passes(int end_bit) { return (end_bit + RADIX_BITS - 1) / RADIX_BITS; }   // the result is in the _a buffers after an even number
 void radix_sort_pairs(uint32_t* key_a, uint32_t* key_b, uint32_t* val_a, uint32_t* val_b, bool vals_iota,
                       const uint32_t* n_dev, long long n_bound, int end_bit, uint32_t* hist,
                       uint32_t** keys_out, uint32_t** vals_out, hipStream_t s);
@@ -563,5 +564,6 @@ hipError_t launch_depth_colorize(int n, int HW, const float* depths, bool from_r
 
 void launch_dist2(int P, const float* points, float* out, char* workspace, hipStream_t s);
 size_t dist2_workspace_bytes(int P);
+void dist2_workspace_layout(int P, size_t offsets[4]);
 
 }  // namespace lr

@@ -20,6 +20,7 @@ namespace lr {
 namespace {
 
 constexpr int BOX = 256;   // points per box (one workgroup); the reference uses 1024
+constexpr int MORTON_BITS = 30;
 
 struct KnnLayout { size_t aabb, codes_a, codes_b, idx_a, idx_b, hist, sorted_pts, boxes, nP, total; };
 inline KnnLayout knn_layout(int P)
@@ -205,6 +206,18 @@ k_box_knn(int P, const float4* __restrict__ sorted, const float* __restrict__ bo
 
 size_t dist2_workspace_bytes(int P) { return knn_layout(P).total; }
 
+// Where the Morton stage leaves its results inside the workspace (tests read them back): sorted keys, order, sorted_pts, boxes.
+// radix_sort_pairs swaps its ping-pong buffers once per pass, so the pass count says which pair holds the result.
+void dist2_workspace_layout(int P, size_t offsets[4])
+{
+    const KnnLayout L = knn_layout(P);
+    const bool in_a = radix_sort_passes(MORTON_BITS) % 2 == 0;
+    offsets[0] = in_a ? L.codes_a : L.codes_b;
+    offsets[1] = in_a ? L.idx_a : L.idx_b;
+    offsets[2] = L.sorted_pts;
+    offsets[3] = L.boxes;
+}
+
 void launch_dist2(int P, const float* points, float* out, char* ws, hipStream_t s)
 {
     const KnnLayout L = knn_layout(P);
@@ -224,7 +237,7 @@ void launch_dist2(int P, const float* points, float* out, char* ws, hipStream_t 
     hipLaunchKernelGGL(k_aabb, dim3(rb), dim3(256), 0, s, P, points, aabb);
     hipLaunchKernelGGL(k_morton, dim3((P + 255) / 256), dim3(256), 0, s, P, points, aabb, codes_a);
     uint32_t *ks, *order;
-    radix_sort_pairs(codes_a, codes_b, idx_a, idx_b, /*iota*/ true, nP, P, 30, hist, &ks, &order, s);
+    radix_sort_pairs(codes_a, codes_b, idx_a, idx_b, /*iota*/ true, nP, P, MORTON_BITS, hist, &ks, &order, s);
     hipLaunchKernelGGL(k_box_minmax, dim3(nbox), dim3(BOX), 0, s, P, points, order, sorted, boxes);
     hipLaunchKernelGGL(k_box_knn, dim3(nbox), dim3(BOX), 0, s, P, sorted, boxes, out);
 }

@@ -235,3 +235,57 @@ def dist2(points, backend=None):
     if P:
         (backend or lib()).dist2(P, _ptr(pts), _ptr(out))
     return out
+
+
+def _knn_fn(name, argtypes):
+    f = getattr(lib().L, name)
+    f.restype, f.argtypes = None, argtypes
+    return f
+
+
+def _rows(rows, P):
+    """(nq, int32 index array or None) of a subset call; rows=None means every row."""
+    if rows is None:
+        return P, None
+    q = np.ascontiguousarray(np.asarray(rows, dtype=np.int32))
+    if q.ndim != 1 or (q.size and (q.min() < 0 or q.max() >= P)):
+        raise ValueError("rows must be a 1-D array of indices into points")
+    return q.size, q
+
+
+def dist2_subset(points, rows):
+    """oracle_dist2's loop for the query rows `rows` only (restatement backend): out[q] belongs to points[rows[q]]."""
+    pts = _f32(points)
+    nq, q = _rows(rows, pts.shape[0])
+    out = np.zeros((nq,), np.float32)
+    if nq:
+        vp, ci = ctypes.c_void_p, ctypes.c_int
+        _knn_fn("oracle_dist2_subset", [ci, vp, ci, vp, vp])(pts.shape[0], _ptr(pts), nq, _ptr(q), _ptr(out))
+    return out
+
+
+def dist2_f64(points, rows=None):
+    """The plain high-precision reference: differences, squares, sums and the mean in float64 on the float32 inputs
+    (oracle_dist2_f64); all rows, or the rows listed.  Returns float64."""
+    pts = _f32(points)
+    nq, q = _rows(rows, pts.shape[0])
+    out = np.zeros((nq,), np.float64)
+    if nq:
+        vp, ci = ctypes.c_void_p, ctypes.c_int
+        _knn_fn("oracle_dist2_f64", [ci, vp, ci, vp, vp])(pts.shape[0], _ptr(pts), nq, None if q is None else _ptr(q), _ptr(out))
+    return out
+
+
+def dist2_fma(points, variant, rows=None):
+    """oracle_dist2 with the squared distance formed by fmaf in one of the two association orders a contracting compiler may
+    choose (oracle_dist2_fma, variant 1 or 2)."""
+    if variant not in (1, 2):
+        raise ValueError("variant must be 1 or 2")
+    pts = _f32(points)
+    nq, q = _rows(rows, pts.shape[0])
+    out = np.zeros((nq,), np.float32)
+    if nq:
+        vp, ci = ctypes.c_void_p, ctypes.c_int
+        _knn_fn("oracle_dist2_fma", [ci, vp, ci, vp, ci, vp])(pts.shape[0], _ptr(pts), nq, None if q is None else _ptr(q),
+                                                             variant, _ptr(out))
+    return out
