@@ -428,142 +428,109 @@ int lr_backward_raw_alpha(int P, int D, int M, int R,
 
 /*
  * Multi-view step (new; the reference renders one view per Python iteration, luciddreamer.py:291-304).
- * Runs lr_forward + lr_backward for n_views views of ONE parameter set and ACCUMULATES the gradients into the
- * acc_* buffers (same shapes as lr_backward's outputs; acc_color / acc_cov3D / acc_sh / acc_scale / acc_rot may be
- * NULL when the corresponding input is absent).  Everything is enqueued from C in one call: views alternate over
- * up to 4 chains (forward of view i+1 overlaps the backward of view i; the accumulating kernels are chained by
- * events): the chain that ends with the last view runs on `stream` itself, the others on streams of the library
- * which are forked from / joined to `stream` with events -- no host synchronisation; everything the call
- * enqueued is ordered before whatever is enqueued on `stream` after it.
- * Async mode only (binning_capacity > 0); an overflow of any view is latched per slot and reported by
- * lr_views_check (which synchronises).  Per-view arrays are HOST arrays of length n_views holding DEVICE
- * pointers (viewmatrices, projmatrices, cam_positions, dL_dpix [3,H,W], optional out_color [3,H,W] and
- * out_radii [P], entries or whole arrays may be NULL) or floats (tan_fovx, tan_fovy).
- * workspace: lr_views_workspace_bytes(P, W, H, binning_capacity, n_streams) device bytes, 256-byte aligned.
+ * lr_views_accumulate runs lr_forward + the backward for n_views views of ONE parameter set and ACCUMULATES the gradients
+ * into the acc_* buffers.  Everything is enqueued from C in one call: views alternate over up to 4 chains (forward of view
+ * i+1 overlaps the backward of view i; the accumulating kernels are chained by events): the chain that ends with the last
+ * view runs on `stream` itself, the others on streams of the library which are forked from / joined to `stream` with events
+ * -- no host synchronisation; everything the call enqueued is ordered before whatever is enqueued on `stream` after it.
+ * Async mode only (binning_capacity > 0); an overflow of any view is latched per slot and reported by lr_views_check (which
+ * synchronises).  No config-level switch is read: which pointers are non-NULL selects the mode.
+ *
+ * Per-view arrays are HOST arrays of length n_views holding DEVICE pointers, or floats (tan_fovx, tan_fovy).  The driver of the
+ * backward is EITHER fixed upstream gradients OR per-view targets (the fused training step); giving both is
+ * LR_ERR_INVALID_ARG, as are depth_targets or masks without targets, and targets together with colors_precomp,
+ * cov3D_precomp, acc_color or acc_cov3D.
+ *   Fixed gradients: dL_dpix [3,H,W] per view, required.  dL_ddepth / dL_dalpha [H,W] per view, optional arrays: a view with
+ *     a depth gradient runs the depth-mode backward of lr_backward_depth fed with its own depth image, one with an alpha
+ *     gradient the alpha-mode backward of lr_backward_alpha (depth + alpha with both), in the blend shape the view would
+ *     take without it; a NULL entry gives that view the backward without that term.
+ *   Fused training step (render -> loss -> backward per view, on the view's stream: the per-iteration body of the training
+ *     loop, R/luciddreamer.py:296-304; gradients of sum_v loss_v; SH colours and scale/rotation covariances only):
+ *     targets [3,H,W] per view, every entry required; loss = (1 - lambda_dssim) l1 + lambda_dssim (1 - ssim) as
+ *       lr_l1_dssim_forward; out_losses (device, required) receives {loss, l1, ssim} per view.
+ *     depth_targets [H,W] per view (optional array, no NULL entries; pixels whose target is not > 0, NaN included, are
+ *       ignored) with depth_weight (finite, >= 0): loss += depth_weight * depth_l1, depth_l1 the unweighted masked mean of
+ *       lr_depth_l1_forward; out_losses holds {loss, l1, ssim, depth_l1} per view.  With depth_weight == 0 the backward is the
+ *       colour-only one (the bits of the step without depth_targets) and depth_l1 is still reported.
+ *     masks [H,W] in [0, 1] per view (optional array, no NULL entries; 1: content, 0: hole -- LucidDreamer's frames have holes:
+ *       pixels the projected cloud left empty are exact zeros) with alpha_weight (finite, >= 0): the colour loss is that of the
+ *       masked pair (lr_masked_l1_dssim_forward) and loss += alpha_weight * alpha_hole (lr_alpha_hole_forward on A = 1 -
+ *       T_final of the view's forward); out_losses holds {loss, l1, ssim, depth_l1, alpha_hole} per view (depth_l1 = 0 without
+ *       depth_targets, whose depth_weight is then ignored).  With alpha_weight == 0 the view gets no alpha gradient (for
+ *       all-ones masks: the bits of the step without masks) and alpha_hole is still reported.
+ * Workspace: lr_views_workspace_bytes(P, W, H, binning_capacity, n_streams, parts) device bytes, 256-byte aligned, with
+ * `parts` the LR_VIEWS_* flags of what the step's slots hold besides a view's scratch: 0 for fixed gradients, LR_VIEWS_LOSS
+ * with targets, | LR_VIEWS_DEPTH_LOSS with depth_targets, | LR_VIEWS_MASK_LOSS with masks (a mask step's slot always has the
+ * depth part too: LOSS|MASK and LOSS|DEPTH|MASK are one layout).  DEPTH or MASK without LOSS, or unknown bits, are invalid:
+ * the size query returns 0 and lr_views_check LR_ERR_INVALID_ARG.  lr_views_check takes the values the step was run with.
+ * (The positional lr_views_* entry points of library versions up to 0.5, one family per mode, are gone.)
  */
-size_t lr_views_workspace_bytes(int P, int width, int height, long long binning_capacity, int n_streams);
-int lr_views_accumulate(int n_views, const float* const* viewmatrices, const float* const* projmatrices,
-                        const float* const* cam_positions, const float* tan_fovx, const float* tan_fovy,
-                        int P, int D, int M, const float* background, int width, int height,
-                        const float* means3D, const float* shs, const float* colors_precomp, const float* opacities,
-                        const float* scales, float scale_modifier, const float* rotations, const float* cov3D_precomp,
-                        const float* const* dL_dpix, float* const* out_color, int* const* out_radii,
-                        float* acc_mean2D, float* acc_opacity, float* acc_color, float* acc_mean3D, float* acc_cov3D,
-                        float* acc_sh, float* acc_scale, float* acc_rot,
-                        char* workspace, size_t workspace_bytes, long long binning_capacity, int n_streams,
-                        void* stream);
+#define LR_VIEWS_LOSS        1u   /* slot holds the colour-loss workspace and dL/dcolor image   */
+#define LR_VIEWS_DEPTH_LOSS  2u   /* ... and the depth gradient image + depth-L1 workspace      */
+#define LR_VIEWS_MASK_LOSS   4u   /* ... and the alpha gradient image + alpha-hole workspace    */
+
+typedef struct lr_views_args {
+    size_t struct_bytes;                     /* = sizeof(lr_views_args); anything else is LR_ERR_INVALID_ARG */
+    /* the views: n_views and per-view camera data (all required) */
+    int n_views;
+    const float* const* viewmatrices;
+    const float* const* projmatrices;
+    const float* const* cam_positions;
+    const float* tan_fovx;
+    const float* tan_fovy;
+    /* the scene, as in lr_forward (shs or colors_precomp; scales + rotations or cov3D_precomp) */
+    int P, D, M;
+    const float* background;
+    int width, height;
+    const float* means3D;
+    const float* shs;
+    const float* colors_precomp;
+    const float* opacities;
+    const float* scales;
+    const float* rotations;
+    const float* cov3D_precomp;
+    float scale_modifier;
+    /* fixed upstream gradients per view (see above) */
+    const float* const* dL_dpix;
+    const float* const* dL_ddepth;
+    const float* const* dL_dalpha;
+    /* the fused training step (see above); out_losses: device float[(3, 4 or 5) * n_views] */
+    const float* const* targets;
+    float lambda_dssim;
+    const float* const* depth_targets;
+    float depth_weight;
+    const float* const* masks;
+    float alpha_weight;
+    float* out_losses;
+    /* optional per-view outputs, fully written: colour [3,H,W], depth [H,W], alpha A = 1 - T_final [H,W] (lr_render_alpha's
+     * values), radii [P]; NULL entries or arrays: not returned */
+    float* const* out_color;
+    float* const* out_depth;
+    float* const* out_alpha;
+    int* const* out_radii;
+    /* the accumulators, shaped like lr_backward's outputs; acc_mean2D, acc_opacity and acc_mean3D are required, the others
+     * may be NULL when the corresponding input is absent */
+    float* acc_mean2D;
+    float* acc_opacity;
+    float* acc_color;
+    float* acc_mean3D;
+    float* acc_cov3D;
+    float* acc_sh;
+    float* acc_scale;
+    float* acc_rot;
+    /* workspace (lr_views_workspace_bytes for the same P, width, height, binning_capacity, n_streams and the step's parts),
+     * number of chains (clamped to 1..4) and the caller's HIP stream */
+    char* workspace;
+    size_t workspace_bytes;
+    long long binning_capacity;
+    int n_streams;
+    void* stream;
+} lr_views_args;
+
+int lr_views_accumulate(const lr_views_args* a);
+size_t lr_views_workspace_bytes(int P, int width, int height, long long binning_capacity, int n_streams, unsigned parts);
 int lr_views_check(const char* workspace, int P, int width, int height, long long binning_capacity, int n_streams,
-                   void* stream);
-
-/*
- * The same multi-view step with the photometric loss inside (render -> L1 + DSSIM against a target -> backward, per
- * view, on the view's stream): the per-iteration body of the training loop, R/luciddreamer.py:296-304, for n_views
- * views of one parameter set.  targets[v]: [3,H,W] device images; out_losses: device float[3 * n_views] receiving
- * {loss, l1, ssim} per view; gradients of sum_v loss_v are accumulated into the acc_* buffers (SH colours and
- * scale/rotation covariances only).  Workspace from lr_views_train_workspace_bytes; overflow check with
- * lr_views_train_check.  No host synchronisation.
- */
-size_t lr_views_train_workspace_bytes(int P, int width, int height, long long binning_capacity, int n_streams);
-int lr_views_train_accumulate(int n_views, const float* const* viewmatrices, const float* const* projmatrices,
-                              const float* const* cam_positions, const float* tan_fovx, const float* tan_fovy,
-                              int P, int D, int M, const float* background, int width, int height,
-                              const float* means3D, const float* shs, const float* opacities, const float* scales,
-                              float scale_modifier, const float* rotations, const float* const* targets,
-                              float lambda_dssim, float* out_losses, float* const* out_color, int* const* out_radii,
-                              float* acc_mean2D, float* acc_opacity, float* acc_mean3D, float* acc_sh, float* acc_scale,
-                              float* acc_rot, char* workspace, size_t workspace_bytes, long long binning_capacity,
-                              int n_streams, void* stream);
-int lr_views_train_check(const char* workspace, int P, int width, int height, long long binning_capacity, int n_streams,
-                         void* stream);
-
-/*
- * The multi-view step with depth supervision (the depth-mode backward of lr_backward_depth, per view).
- *   lr_views_accumulate_depth: the arguments of lr_views_accumulate plus dL_ddepth (HOST array of n_views DEVICE [H,W]
- *     pointers, required; a NULL entry gives that view the colour-only backward) and optional out_depth (per-view [H,W]
- *     device images receiving the rendered depth; NULL entries or array: not returned).  Each view with a depth gradient runs
- *     the depth-mode backward fed with its own depth image.  Workspace (lr_views_workspace_bytes), overflow check
- *     (lr_views_check) and chains are exactly those of lr_views_accumulate.
- *   lr_views_train_depth_accumulate: the arguments of lr_views_train_accumulate plus depth_targets (per-view [H,W] device
- *     depth maps; pixels whose target is not > 0, NaN included, are ignored), depth_weight (finite, >= 0) and optional
- *     out_depth.  out_losses: device float[4 * n_views] receiving {loss, l1, ssim, depth_l1} per view, with
- *     loss = colour loss + depth_weight * depth_l1 and depth_l1 the unweighted masked mean of lr_depth_l1_forward.  Per view,
- *     on its stream: forward, colour loss, depth loss, depth-mode backward.  With depth_weight == 0 the backward is the
- *     colour-only one: the gradients are bit-identical to lr_views_train_accumulate's, and depth_l1 is still reported.
- *     Workspace from lr_views_train_depth_workspace_bytes (>= lr_views_train_workspace_bytes); overflow check with
- *     lr_views_train_depth_check.
- * Neither reads config-level switches: the depth arguments are the opt-in.  No host synchronisation.
- */
-int lr_views_accumulate_depth(int n_views, const float* const* viewmatrices, const float* const* projmatrices,
-                              const float* const* cam_positions, const float* tan_fovx, const float* tan_fovy,
-                              int P, int D, int M, const float* background, int width, int height,
-                              const float* means3D, const float* shs, const float* colors_precomp, const float* opacities,
-                              const float* scales, float scale_modifier, const float* rotations, const float* cov3D_precomp,
-                              const float* const* dL_dpix, const float* const* dL_ddepth, float* const* out_color,
-                              float* const* out_depth, int* const* out_radii,
-                              float* acc_mean2D, float* acc_opacity, float* acc_color, float* acc_mean3D, float* acc_cov3D,
-                              float* acc_sh, float* acc_scale, float* acc_rot,
-                              char* workspace, size_t workspace_bytes, long long binning_capacity, int n_streams,
-                              void* stream);
-size_t lr_views_train_depth_workspace_bytes(int P, int width, int height, long long binning_capacity, int n_streams);
-int lr_views_train_depth_accumulate(int n_views, const float* const* viewmatrices, const float* const* projmatrices,
-                                    const float* const* cam_positions, const float* tan_fovx, const float* tan_fovy,
-                                    int P, int D, int M, const float* background, int width, int height,
-                                    const float* means3D, const float* shs, const float* opacities, const float* scales,
-                                    float scale_modifier, const float* rotations, const float* const* targets,
-                                    float lambda_dssim, const float* const* depth_targets, float depth_weight,
-                                    float* out_losses, float* const* out_color, float* const* out_depth,
-                                    int* const* out_radii, float* acc_mean2D, float* acc_opacity, float* acc_mean3D,
-                                    float* acc_sh, float* acc_scale, float* acc_rot, char* workspace, size_t workspace_bytes,
-                                    long long binning_capacity, int n_streams, void* stream);
-int lr_views_train_depth_check(const char* workspace, int P, int width, int height, long long binning_capacity, int n_streams,
-                               void* stream);
-
-/*
- * The multi-view step with mask supervision (LucidDreamer's frames have holes: pixels the projected cloud left empty are exact
- * zeros).  m is a per-view content mask [H,W] in [0, 1] (1: content, 0: hole) and A = 1 - T_final the alpha output.
- *   lr_views_accumulate_alpha: the arguments of lr_views_accumulate_depth plus dL_dalpha (HOST array of n_views DEVICE [H,W]
- *     pointers, required; a NULL entry gives that view no alpha gradient) and optional out_alpha (per-view [H,W] device images
- *     receiving A, lr_render_alpha's values; NULL entries or array: not returned).  Here dL_ddepth may be NULL as a whole.  Each
- *     view with an alpha gradient runs the alpha-mode backward of lr_backward_alpha (depth + alpha with a depth gradient too),
- *     in the blend shape the view would take without it.  Workspace (lr_views_workspace_bytes), overflow check (lr_views_check)
- *     and chains are exactly those of lr_views_accumulate.
- *   lr_views_train_mask_accumulate: the arguments of lr_views_train_depth_accumulate plus masks (per-view [H,W], required) and
- *     alpha_weight (finite, >= 0); depth_targets may be NULL (no depth term; depth_weight is then ignored) and out_alpha is
- *     optional.  Per view, on its stream: forward, masked colour loss (lr_masked_l1_dssim_forward), depth L1 (if any), alpha hole
- *     term (lr_alpha_hole_forward, from the forward's T_final), backward.  out_losses: device float[5 * n_views] receiving
- *     {loss, l1, ssim, depth_l1, alpha_hole} per view, loss = Lc + depth_weight * depth_l1 + alpha_weight * alpha_hole, where l1
- *     and ssim are those of the masked pair and depth_l1 (0 without depth targets), alpha_hole are unweighted.  With
- *     alpha_weight == 0 the view gets no alpha gradient: its backward is the colour-only or depth-mode one (the bits of
- *     lr_views_train_accumulate / lr_views_train_depth_accumulate for all-ones masks), and alpha_hole is still reported.
- *     Workspace from lr_views_train_mask_workspace_bytes (>= lr_views_train_depth_workspace_bytes); overflow check with
- *     lr_views_train_mask_check.
- * Neither reads config-level switches: the new arguments are the opt-in.  No host synchronisation.
- */
-int lr_views_accumulate_alpha(int n_views, const float* const* viewmatrices, const float* const* projmatrices,
-                              const float* const* cam_positions, const float* tan_fovx, const float* tan_fovy,
-                              int P, int D, int M, const float* background, int width, int height,
-                              const float* means3D, const float* shs, const float* colors_precomp, const float* opacities,
-                              const float* scales, float scale_modifier, const float* rotations, const float* cov3D_precomp,
-                              const float* const* dL_dpix, const float* const* dL_ddepth, const float* const* dL_dalpha,
-                              float* const* out_color, float* const* out_depth, float* const* out_alpha, int* const* out_radii,
-                              float* acc_mean2D, float* acc_opacity, float* acc_color, float* acc_mean3D, float* acc_cov3D,
-                              float* acc_sh, float* acc_scale, float* acc_rot,
-                              char* workspace, size_t workspace_bytes, long long binning_capacity, int n_streams,
-                              void* stream);
-size_t lr_views_train_mask_workspace_bytes(int P, int width, int height, long long binning_capacity, int n_streams);
-int lr_views_train_mask_accumulate(int n_views, const float* const* viewmatrices, const float* const* projmatrices,
-                                   const float* const* cam_positions, const float* tan_fovx, const float* tan_fovy,
-                                   int P, int D, int M, const float* background, int width, int height,
-                                   const float* means3D, const float* shs, const float* opacities, const float* scales,
-                                   float scale_modifier, const float* rotations, const float* const* targets,
-                                   float lambda_dssim, const float* const* masks, float alpha_weight,
-                                   const float* const* depth_targets, float depth_weight, float* out_losses,
-                                   float* const* out_color, float* const* out_depth, float* const* out_alpha,
-                                   int* const* out_radii, float* acc_mean2D, float* acc_opacity, float* acc_mean3D,
-                                   float* acc_sh, float* acc_scale, float* acc_rot, char* workspace, size_t workspace_bytes,
-                                   long long binning_capacity, int n_streams, void* stream);
-int lr_views_train_mask_check(const char* workspace, int P, int width, int height, long long binning_capacity, int n_streams,
-                              void* stream);
+                   unsigned parts, void* stream);
 
 /*
  * Row surgery of the Gaussian parameter set.  The reference changes the number of Gaussians
@@ -663,7 +630,7 @@ int lr_depth_l1_backward(int height, int width, const float* depth, const float*
                          float* dL_ddepth, void* stream);
 
 /*
- * Mask supervision of one view (the single-view building blocks of lr_views_train_mask_accumulate).  mask: [H,W] float32
+ * Mask supervision of one view (the single-view building blocks of lr_views_accumulate with masks).  mask: [H,W] float32
  * device image in [0, 1], 1 where the target frame has content, 0 in its holes; shared by the channels of image / gt.
  *   lr_masked_l1_dssim_forward / _backward: lr_l1_dssim_forward / _backward of the masked pair (mask * image, mask * gt) --
  *     loss = l1_dssim(m I, m G, lambda), dL_dimage = upstream * m * (d l1_dssim / dI')|_{I' = m I} -- with the same workspace

@@ -35,13 +35,42 @@ EXPORTS = ("lr_last_error", "lr_version", "lr_geom_bytes", "lr_img_bytes", "lr_b
            "lr_views_workspace_bytes", "lr_views_accumulate", "lr_views_check",
            "lr_loss_workspace_bytes", "lr_l1_dssim_forward", "lr_l1_dssim_backward", "lr_l1_dssim_backward_weights",
            "lr_select_workspace_bytes", "lr_select_rows", "lr_pack_ply_rows", "lr_adam_step", "lr_adam_step_masked", "lr_densify_stats",
-           "lr_views_train_workspace_bytes", "lr_views_train_accumulate", "lr_views_train_check",
-           "lr_views_accumulate_depth", "lr_views_train_depth_workspace_bytes", "lr_views_train_depth_accumulate",
-           "lr_views_train_depth_check", "lr_depth_l1_workspace_bytes", "lr_depth_l1_forward", "lr_depth_l1_backward",
+           "lr_depth_l1_workspace_bytes", "lr_depth_l1_forward", "lr_depth_l1_backward",
            "lr_video_workspace_bytes", "lr_frames_to_u8", "lr_depth_colorize",
            "lr_masked_l1_dssim_forward", "lr_masked_l1_dssim_backward", "lr_alpha_hole_workspace_bytes", "lr_alpha_hole_forward",
-           "lr_alpha_hole_backward", "lr_views_accumulate_alpha", "lr_views_train_mask_workspace_bytes",
-           "lr_views_train_mask_accumulate", "lr_views_train_mask_check", "lr_set_antialiasing", "lr_get_antialiasing")
+           "lr_alpha_hole_backward", "lr_set_antialiasing", "lr_get_antialiasing")
+
+# lr_views_workspace_bytes / lr_views_check `parts`: what a step's workspace slots hold besides a view's scratch
+LR_VIEWS_LOSS, LR_VIEWS_DEPTH_LOSS, LR_VIEWS_MASK_LOSS = 1, 2, 4
+
+
+class ViewsArgs(ctypes.Structure):
+    """lr_views_args of include/lucid_raster.h, field for field (tests/test_views_args_cpu.py compares the offsets with the
+    host compiler's).  `[]` marks HOST arrays of n_views entries."""
+    _vp, _ci, _cf = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
+    _fields_ = [("struct_bytes", ctypes.c_size_t),
+                # the views
+                ("n_views", _ci), ("viewmatrices", _vp), ("projmatrices", _vp), ("cam_positions", _vp),      # [] [] []
+                ("tan_fovx", _vp), ("tan_fovy", _vp),                                                       # float[] float[]
+                # the scene
+                ("P", _ci), ("D", _ci), ("M", _ci), ("background", _vp), ("width", _ci), ("height", _ci),
+                ("means3D", _vp), ("shs", _vp), ("colors_precomp", _vp), ("opacities", _vp), ("scales", _vp),
+                ("rotations", _vp), ("cov3D_precomp", _vp), ("scale_modifier", _cf),
+                # fixed upstream gradients
+                ("dL_dpix", _vp), ("dL_ddepth", _vp), ("dL_dalpha", _vp),                                    # [] [] []
+                # the fused training step
+                ("targets", _vp), ("lambda_dssim", _cf), ("depth_targets", _vp), ("depth_weight", _cf),      # [] . [] .
+                ("masks", _vp), ("alpha_weight", _cf), ("out_losses", _vp),                                  # [] . device
+                # optional per-view outputs
+                ("out_color", _vp), ("out_depth", _vp), ("out_alpha", _vp), ("out_radii", _vp),              # [] [] [] []
+                # the accumulators
+                ("acc_mean2D", _vp), ("acc_opacity", _vp), ("acc_color", _vp), ("acc_mean3D", _vp),
+                ("acc_cov3D", _vp), ("acc_sh", _vp), ("acc_scale", _vp), ("acc_rot", _vp),
+                ("workspace", _vp), ("workspace_bytes", ctypes.c_size_t), ("binning_capacity", ctypes.c_longlong),
+                ("n_streams", _ci), ("stream", _vp)]
+
+    def __init__(self, **fields):
+        super().__init__(struct_bytes=ctypes.sizeof(ViewsArgs), **fields)
 
 
 def assert_single_copy():
@@ -124,72 +153,17 @@ def lib():
         L.lr_dist2_workspace_layout.restype = ci
         L.lr_dist2_workspace_layout.argtypes = [ci, ctypes.POINTER(ctypes.c_size_t)]
         L.lr_views_workspace_bytes.restype = ctypes.c_size_t
-        L.lr_views_workspace_bytes.argtypes = [ci, ci, ci, ll, ci]
+        L.lr_views_workspace_bytes.argtypes = [ci, ci, ci, ll, ci, ctypes.c_uint]     # P W H capacity n_streams parts
         L.lr_views_accumulate.restype = ci
-        L.lr_views_accumulate.argtypes = [ci, vp, vp, vp, vp, vp,                # n_views, view/proj/campos arrays, tanfovx/y arrays
-                                          ci, ci, ci, vp, ci, ci,                # P D M bg W H
-                                          vp, vp, vp, vp, vp, cf, vp, vp,        # means3D shs colors opac scales mod rot cov3D
-                                          vp, vp, vp,                            # dL_dpix[], out_color[], out_radii[]
-                                          vp, vp, vp, vp, vp, vp, vp, vp,        # 8 accumulators
-                                          vp, ctypes.c_size_t, ll, ci, vp]       # workspace, bytes, capacity, n_streams, stream
+        L.lr_views_accumulate.argtypes = [ctypes.POINTER(ViewsArgs)]
         L.lr_views_check.restype = ci
-        L.lr_views_check.argtypes = [vp, ci, ci, ci, ll, ci, vp]
-        L.lr_views_train_workspace_bytes.restype = ctypes.c_size_t
-        L.lr_views_train_workspace_bytes.argtypes = [ci, ci, ci, ll, ci]
-        L.lr_views_train_accumulate.restype = ci
-        L.lr_views_train_accumulate.argtypes = [ci, vp, vp, vp, vp, vp,          # n_views, view/proj/campos arrays, tanfovx/y arrays
-                                                ci, ci, ci, vp, ci, ci,          # P D M bg W H
-                                                vp, vp, vp, vp, cf, vp,          # means3D shs opac scales mod rot
-                                                vp, cf, vp, vp, vp,              # targets[], lambda, out_losses, out_color[], out_radii[]
-                                                vp, vp, vp, vp, vp, vp,          # 6 accumulators
-                                                vp, ctypes.c_size_t, ll, ci, vp] # workspace, bytes, capacity, n_streams, stream
-        L.lr_views_train_check.restype = ci
-        L.lr_views_train_check.argtypes = [vp, ci, ci, ci, ll, ci, vp]
-        L.lr_views_accumulate_depth.restype = ci
-        L.lr_views_accumulate_depth.argtypes = [ci, vp, vp, vp, vp, vp,          # n_views, view/proj/campos arrays, tanfovx/y arrays
-                                                ci, ci, ci, vp, ci, ci,          # P D M bg W H
-                                                vp, vp, vp, vp, vp, cf, vp, vp,  # means3D shs colors opac scales mod rot cov3D
-                                                vp, vp, vp, vp, vp,              # dL_dpix[], dL_ddepth[], out_color[], out_depth[], out_radii[]
-                                                vp, vp, vp, vp, vp, vp, vp, vp,  # 8 accumulators
-                                                vp, ctypes.c_size_t, ll, ci, vp] # workspace, bytes, capacity, n_streams, stream
-        L.lr_views_train_depth_workspace_bytes.restype = ctypes.c_size_t
-        L.lr_views_train_depth_workspace_bytes.argtypes = [ci, ci, ci, ll, ci]
-        L.lr_views_train_depth_accumulate.restype = ci
-        L.lr_views_train_depth_accumulate.argtypes = [ci, vp, vp, vp, vp, vp,    # n_views, view/proj/campos arrays, tanfovx/y arrays
-                                                      ci, ci, ci, vp, ci, ci,    # P D M bg W H
-                                                      vp, vp, vp, vp, cf, vp,    # means3D shs opac scales mod rot
-                                                      vp, cf, vp, cf,            # targets[], lambda, depth_targets[], depth_weight
-                                                      vp, vp, vp, vp,            # out_losses, out_color[], out_depth[], out_radii[]
-                                                      vp, vp, vp, vp, vp, vp,    # 6 accumulators
-                                                      vp, ctypes.c_size_t, ll, ci, vp]
-        L.lr_views_train_depth_check.restype = ci
-        L.lr_views_train_depth_check.argtypes = [vp, ci, ci, ci, ll, ci, vp]
+        L.lr_views_check.argtypes = [vp, ci, ci, ci, ll, ci, ctypes.c_uint, vp]      # workspace, then as above, stream
         L.lr_depth_l1_workspace_bytes.restype = ctypes.c_size_t
         L.lr_depth_l1_workspace_bytes.argtypes = [ci, ci]
         L.lr_depth_l1_forward.restype = ci
         L.lr_depth_l1_forward.argtypes = [ci, ci, vp, vp, cf, vp, vp, ctypes.c_size_t, vp]
         L.lr_depth_l1_backward.restype = ci
         L.lr_depth_l1_backward.argtypes = [ci, ci, vp, vp, cf, vp, vp, vp]
-        L.lr_views_accumulate_alpha.restype = ci
-        L.lr_views_accumulate_alpha.argtypes = [ci, vp, vp, vp, vp, vp,          # n_views, view/proj/campos arrays, tanfovx/y arrays
-                                                ci, ci, ci, vp, ci, ci,          # P D M bg W H
-                                                vp, vp, vp, vp, vp, cf, vp, vp,  # means3D shs colors opac scales mod rot cov3D
-                                                vp, vp, vp,                      # dL_dpix[], dL_ddepth[], dL_dalpha[]
-                                                vp, vp, vp, vp,                  # out_color[], out_depth[], out_alpha[], out_radii[]
-                                                vp, vp, vp, vp, vp, vp, vp, vp,  # 8 accumulators
-                                                vp, ctypes.c_size_t, ll, ci, vp] # workspace, bytes, capacity, n_streams, stream
-        L.lr_views_train_mask_workspace_bytes.restype = ctypes.c_size_t
-        L.lr_views_train_mask_workspace_bytes.argtypes = [ci, ci, ci, ll, ci]
-        L.lr_views_train_mask_accumulate.restype = ci
-        L.lr_views_train_mask_accumulate.argtypes = [ci, vp, vp, vp, vp, vp,     # n_views, view/proj/campos arrays, tanfovx/y arrays
-                                                     ci, ci, ci, vp, ci, ci,     # P D M bg W H
-                                                     vp, vp, vp, vp, cf, vp,     # means3D shs opac scales mod rot
-                                                     vp, cf, vp, cf, vp, cf,     # targets[], lambda, masks[], alpha_weight, depth_targets[], depth_weight
-                                                     vp, vp, vp, vp, vp,         # out_losses, out_color[], out_depth[], out_alpha[], out_radii[]
-                                                     vp, vp, vp, vp, vp, vp,     # 6 accumulators
-                                                     vp, ctypes.c_size_t, ll, ci, vp]
-        L.lr_views_train_mask_check.restype = ci
-        L.lr_views_train_mask_check.argtypes = [vp, ci, ci, ci, ll, ci, vp]
         L.lr_masked_l1_dssim_forward.restype = ci
         L.lr_masked_l1_dssim_forward.argtypes = [ci, ci, ci, vp, vp, vp, cf, vp, vp, ctypes.c_size_t, vp]
         L.lr_masked_l1_dssim_backward.restype = ci

@@ -173,7 +173,7 @@ k_depth_l1_fwd(int n, const float* __restrict__ depth, const float* __restrict__
     if (threadIdx.x == 0) partials[blockIdx.x] = bs;
 }
 
-// {weight * mean, mean} of the partials, fixed order; fused step (out_losses of lr_views_train_depth_accumulate): the colour
+// {weight * mean, mean} of the partials, fixed order; fused step (out_losses of lr_views_accumulate with depth_targets): the colour
 // loss already in out[0] gets the weighted depth term added, the unweighted mean goes to out[3]
 __device__ __forceinline__ void depth_l1_final(int n_blocks, double n_elems, float weight, const double* __restrict__ partials,
                                                float* __restrict__ out, bool fused, double* s_a)
@@ -272,7 +272,7 @@ k_alpha_hole_fwd(int n, const float* __restrict__ src, int from_T, const float* 
     if (threadIdx.x == 0) partials[blockIdx.x] = bs;
 }
 
-// as depth_l1_final, with the fused step's unweighted mean in out[4] (out_losses of lr_views_train_mask_accumulate);
+// as depth_l1_final, with the fused step's unweighted mean in out[4] (out_losses of lr_views_accumulate with masks);
 // fused 2: a step without a depth term, whose depth_l1 out[3] is reported as 0
 __device__ __forceinline__ void alpha_hole_final(int n_blocks, double n_elems, float weight, const double* __restrict__ partials,
                                                  float* __restrict__ out, int fused, double* s_a)

@@ -849,10 +849,10 @@ class ViewStreams:
 
 
 class ViewBatch:
-    """One C call per step for a fixed list of views (lr_views_accumulate_depth, which with NULL depth gradients is
-    lr_views_accumulate; lr_views_accumulate_alpha with grad_alphas): forward + backward of every view, gradients accumulated in place, views alternated over internal
-    HIP streams.  The per-view upstream gradients dL/dcolor are given up front (a training loop that needs the rendered
-    image to form its loss uses the autograd op, optionally with ViewStreams, instead).
+    """One C call per step for a fixed list of views (lr_views_accumulate): forward + backward of every view, gradients
+    accumulated in place, views alternated over internal HIP streams.  The per-view upstream gradients dL/dcolor are given up
+    front (a training loop that needs the rendered image to form its loss uses the autograd op, optionally with ViewStreams,
+    instead).
 
     cams: objects with world_view_transform, full_proj_transform, camera_center (device tensors), FoVx, FoVy,
           image_width, image_height (e.g. cameras.MiniCam); all views share one resolution.
@@ -867,25 +867,25 @@ class ViewBatch:
                  grad_alphas: Optional[Sequence[torch.Tensor]] = None, masks: Optional[Sequence[torch.Tensor]] = None,
                  alpha_weight: Optional[float] = None, alphas: Optional[Sequence[torch.Tensor]] = None):
         """grad_colors: fixed upstream gradients dL/dcolor per view, OR targets: ground-truth images per view, in which
-        case every view's L1 + DSSIM loss against its target is formed inside the call (lr_views_train_accumulate) and
+        case every view's L1 + DSSIM loss against its target is formed inside the call (lr_views_accumulate with targets) and
         `self.losses` ([n,3] device tensor: loss, l1, ssim per view) is filled by run().
         Depth supervision (the depth-mode backward of every view; the arguments are the opt-in, config.set_depth_gradient is
         not read):
-          grad_depths (with grad_colors): fixed dL/d depth per view, [1,H,W] or [H,W] (lr_views_accumulate_depth);
+          grad_depths (with grad_colors): fixed dL/d depth per view, [1,H,W] or [H,W];
           depth_targets (with targets): depth maps per view, [1,H,W] or [H,W]; pixels whose target is not > 0 are ignored.
             The masked depth L1 (loss.depth_l1) joins each view's loss with depth_weight (default 1.0, >= 0), and
-            `self.losses` is [n,4]: loss (= colour loss + depth_weight * depth_l1), l1, ssim, depth_l1
-            (lr_views_train_depth_accumulate).  depth_weight 0 reports depth_l1 with the colour-only gradients.
+            `self.losses` is [n,4]: loss (= colour loss + depth_weight * depth_l1), l1, ssim, depth_l1.  depth_weight 0
+            reports depth_l1 with the colour-only gradients.
           depths: per-view [1,H,W] or [H,W] contiguous float32 device tensors that run() fills with the rendered depth (not
             with targets alone).
         Mask supervision (the alpha output A = 1 - T_final; the arguments are the opt-in):
           grad_alphas (with grad_colors): fixed dL/d alpha per view, [1,H,W] or [H,W]: the alpha-mode backward of every view
-            (lr_views_accumulate_alpha; with grad_depths too, the depth + alpha one);
+            (with grad_depths too, the depth + alpha one);
           masks (with targets): content masks per view, [1,H,W] or [H,W] in [0, 1] (loss.content_mask).  Each view's loss is
             masked_l1_dssim(image, target, mask) + depth_weight * depth_l1 (with depth_targets) + alpha_weight *
             alpha_hole(A, mask), alpha_weight default 1.0, >= 0; `self.losses` is [n,5]: loss, l1, ssim (of the masked pair),
-            depth_l1 (0 without depth_targets), alpha_hole (lr_views_train_mask_accumulate).  alpha_weight 0 reports
-            alpha_hole with the gradients of the step without it.
+            depth_l1 (0 without depth_targets), alpha_hole.  alpha_weight 0 reports alpha_hole with the gradients of the
+            step without it.
           alphas: per-view [1,H,W] or [H,W] contiguous float32 device tensors that run() fills with A (with grad_alphas or
             masks only).
         Arguments are checked before any device work."""
@@ -898,188 +898,142 @@ class ViewBatch:
         if self.n == 0 or self.n != len(grad_colors if targets is None else targets):
             raise ValueError("one grad_colors / targets entry per camera, and at least one camera")
         self.W, self.H = int(self.cams[0].image_width), int(self.cams[0].image_height)
-        self.train_depth = depth_targets is not None
-        self._check_depth_args(grad_colors, targets, grad_depths, depth_targets, depth_weight, depths,
-                               allow_depths=masks is not None)
-        self.train_mask = masks is not None
-        self.alpha_mode = grad_alphas is not None
-        self._check_alpha_args(grad_colors, targets, grad_alphas, masks, alpha_weight, alphas)
+        self._check_optional_args(grad_colors, targets, grad_depths, depth_targets, depth_weight, depths, grad_alphas, masks,
+                                  alpha_weight, alphas)
         from . import _lib
         self._lib = _lib
         self.L = _lib.lib()
         self.device = self.cams[0].world_view_transform.device
-        self.degree, self.scale_modifier = int(sh_degree), float(scale_modifier)
         self.capacity, self.n_streams = int(binning_capacity), int(n_streams)
         self.bg = bg.to(self.device).contiguous()
-        keep = []
-
-        def ptr_array(tensors):
-            ts = [t.to(self.device).contiguous() for t in tensors]
-            keep.extend(ts)
-            return (ctypes.c_void_p * self.n)(*[t.data_ptr() for t in ts])
-        self._views = ptr_array([c.world_view_transform for c in self.cams])
-        self._projs = ptr_array([c.full_proj_transform for c in self.cams])
-        self._campos = ptr_array([c.camera_center for c in self.cams])
         self.train = targets is not None
-        self.lambda_dssim = float(lambda_dssim)
-        self._grads = ptr_array(grad_colors if not self.train else targets)     # per-view dL/dcolor, or target images
-        self.depth_weight = (1.0 if depth_weight is None else float(depth_weight)) if self.train_depth else 0.0
-        # per-view dL/ddepth or depth targets; without either: NULL entries (lr_views_accumulate_depth's colour-only backward)
-        depth_in = grad_depths if grad_depths is not None else depth_targets
-        self._dgrads = ptr_array(depth_in) if depth_in is not None else (ctypes.c_void_p * self.n)()
         self.depths = list(depths) if depths is not None else None
-        self._depths = (ctypes.c_void_p * self.n)(*[t.data_ptr() for t in self.depths]) if depths is not None else None
-        # per-view dL/dalpha or content masks; alpha outputs
-        self.alpha_weight = (1.0 if alpha_weight is None else float(alpha_weight)) if self.train_mask else 0.0
-        alpha_in = grad_alphas if grad_alphas is not None else masks
-        self._agrads = ptr_array(alpha_in) if alpha_in is not None else None
         self.alphas = list(alphas) if alphas is not None else None
-        self._alphas = (ctypes.c_void_p * self.n)(*[t.data_ptr() for t in self.alphas]) if alphas is not None else None
-        n_losses = 5 if self.train_mask else 4 if self.train_depth else 3
+        n_losses = 5 if masks is not None else 4 if depth_targets is not None else 3
         self.losses = torch.zeros((self.n, n_losses), dtype=torch.float32, device=self.device) if self.train else None
-        self._tanx = (ctypes.c_float * self.n)(*[math.tan(c.FoVx * 0.5) for c in self.cams])
-        self._tany = (ctypes.c_float * self.n)(*[math.tan(c.FoVy * 0.5) for c in self.cams])
-        self._keep = keep
+        # what a workspace slot holds besides a view's scratch (lr_views_workspace_bytes, lr_views_check)
+        self.parts = ((_lib.LR_VIEWS_LOSS if self.train else 0) | (_lib.LR_VIEWS_DEPTH_LOSS if depth_targets is not None else 0) |
+                      (_lib.LR_VIEWS_MASK_LOSS if masks is not None else 0))
+        self._keep = []                     # what the host arrays below point to, and the arrays themselves
+
+        def host_array(values, ctype=ctypes.c_void_p):
+            arr = (ctype * self.n)(*values)
+            self._keep.append(arr)
+            return ctypes.addressof(arr)
+
+        def inputs(tensors):                # HOST array of the device pointers of per-view inputs; None stays NULL
+            if tensors is None:
+                return None
+            ts = [t.to(self.device).contiguous() for t in tensors]
+            self._keep.extend(ts)
+            return host_array(t.data_ptr() for t in ts)
+
+        def outputs(tensors):               # ... of the caller's own tensors (checked above: on the device, contiguous)
+            return None if tensors is None else host_array(t.data_ptr() for t in tensors)
+        # everything that is fixed for the batch; run() adds the parameters, the accumulators and the workspace
+        self._args = _lib.ViewsArgs(
+            n_views=self.n, viewmatrices=inputs([c.world_view_transform for c in self.cams]),
+            projmatrices=inputs([c.full_proj_transform for c in self.cams]),
+            cam_positions=inputs([c.camera_center for c in self.cams]),
+            tan_fovx=host_array((math.tan(c.FoVx * 0.5) for c in self.cams), ctypes.c_float),
+            tan_fovy=host_array((math.tan(c.FoVy * 0.5) for c in self.cams), ctypes.c_float),
+            D=int(sh_degree), background=self.bg.data_ptr(), width=self.W, height=self.H, scale_modifier=float(scale_modifier),
+            dL_dpix=inputs(grad_colors), dL_ddepth=inputs(grad_depths), dL_dalpha=inputs(grad_alphas),
+            targets=inputs(targets), lambda_dssim=float(lambda_dssim),
+            depth_targets=inputs(depth_targets), depth_weight=1.0 if depth_weight is None else float(depth_weight),
+            masks=inputs(masks), alpha_weight=1.0 if alpha_weight is None else float(alpha_weight),
+            out_losses=self.losses.data_ptr() if self.train else None,
+            out_depth=outputs(self.depths), out_alpha=outputs(self.alphas), binning_capacity=self.capacity)
         self._ws = None
         self._ws_key = None
-        L = self.L
-        self._ws_bytes, self._ws_check = (
-            (L.lr_views_train_mask_workspace_bytes, L.lr_views_train_mask_check) if self.train_mask else
-            (L.lr_views_train_depth_workspace_bytes, L.lr_views_train_depth_check) if self.train_depth else
-            (L.lr_views_train_workspace_bytes, L.lr_views_train_check) if self.train else
-            (L.lr_views_workspace_bytes, L.lr_views_check))
 
-    def _check_depth_args(self, grad_colors, targets, grad_depths, depth_targets, depth_weight, depths, allow_depths=False):
+    def _check_optional_args(self, grad_colors, targets, grad_depths, depth_targets, depth_weight, depths, grad_alphas, masks,
+                             alpha_weight, alphas):
+        """Depth supervision, then mask supervision: the same rules over each one's (fixed gradients, training input, weight,
+        output) and its table of per-view images."""
         import math
-        if grad_depths is not None and grad_colors is None:
-            raise ValueError("grad_depths goes with grad_colors (fixed upstream gradients); with targets give depth_targets")
-        if depth_targets is not None and targets is None:
-            raise ValueError("depth_targets goes with targets (the fused training step); with grad_colors give grad_depths")
-        if depth_weight is not None:
-            if depth_targets is None:
-                raise ValueError("depth_weight needs depth_targets")
-            w = float(depth_weight)
-            if not (math.isfinite(w) and w >= 0.0):
-                raise ValueError(f"depth_weight must be finite and >= 0, got {depth_weight}")
-        if depths is not None and targets is not None and depth_targets is None and not allow_depths:
-            raise ValueError("depths= with targets needs depth_targets (the colour-only training step returns no depth)")
-        shape_ok = lambda t: isinstance(t, torch.Tensor) and tuple(t.shape) in ((self.H, self.W), (1, self.H, self.W))
-        for name, seq in (("grad_depths", grad_depths), ("depth_targets", depth_targets), ("depths", depths)):
-            if seq is None:
-                continue
-            seq = list(seq)
-            if len(seq) != self.n:
-                raise ValueError(f"{name}: {len(seq)} entries for {self.n} views")
-            for t in seq:
-                if not shape_ok(t):
-                    raise ValueError(f"{name}: every entry must be a [1,H,W] or [H,W] tensor with H,W = {self.H},{self.W}, "
-                                     f"got {tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__}")
-                if name == "depths" and not (t.is_cuda and t.dtype is torch.float32 and t.is_contiguous()):
-                    raise ValueError("depths: outputs must be contiguous float32 tensors on the HIP device")
+        fixed, train = grad_colors is not None, targets is not None
+        for (g_name, grads, t_name, train_in, w_name, weight, no_output, images) in (
+                ("grad_depths", grad_depths, "depth_targets", depth_targets, "depth_weight", depth_weight,
+                 "depths= with targets needs depth_targets (the colour-only training step returns no depth)"
+                 if depths is not None and train and depth_targets is None and masks is None else None,
+                 (("grad_depths", grad_depths, None), ("depth_targets", depth_targets, None), ("depths", depths, "output"))),
+                ("grad_alphas", grad_alphas, "masks", masks, "alpha_weight", alpha_weight,
+                 "alphas= needs grad_alphas or masks (a step without them renders no alpha)"
+                 if alphas is not None and grad_alphas is None and masks is None else None,
+                 (("grad_alphas", grad_alphas, None), ("masks", masks, "float32"), ("alphas", alphas, "output")))):
+            if grads is not None and not fixed:
+                raise ValueError(f"{g_name} goes with grad_colors (fixed upstream gradients); with targets give {t_name}")
+            if train_in is not None and not train:
+                raise ValueError(f"{t_name} goes with targets (the fused training step); with grad_colors give {g_name}")
+            if weight is not None:
+                if train_in is None:
+                    raise ValueError(f"{w_name} needs {t_name}")
+                if not (math.isfinite(float(weight)) and float(weight) >= 0.0):
+                    raise ValueError(f"{w_name} must be finite and >= 0, got {weight}")
+            if no_output:
+                raise ValueError(no_output)
+            # per-view [1,H,W] or [H,W] images, one per view; rule "output": run() writes it in place; "float32": read as it is
+            for name, seq, rule in images:
+                if seq is None:
+                    continue
+                seq = list(seq)
+                if len(seq) != self.n:
+                    raise ValueError(f"{name}: {len(seq)} entries for {self.n} views")
+                for t in seq:
+                    if not (isinstance(t, torch.Tensor) and tuple(t.shape) in ((self.H, self.W), (1, self.H, self.W))):
+                        raise ValueError(f"{name}: every entry must be a [1,H,W] or [H,W] tensor with H,W = {self.H},{self.W}, "
+                                         f"got {tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__}")
+                    if rule == "output" and not (t.is_cuda and t.dtype is torch.float32 and t.is_contiguous()):
+                        raise ValueError(f"{name}: outputs must be contiguous float32 tensors on the HIP device")
+                    if rule == "float32" and t.dtype is not torch.float32:
+                        raise ValueError(f"{name}: float32 tensors (loss.content_mask)")
 
-    def _check_alpha_args(self, grad_colors, targets, grad_alphas, masks, alpha_weight, alphas):
-        import math
-        if grad_alphas is not None and grad_colors is None:
-            raise ValueError("grad_alphas goes with grad_colors (fixed upstream gradients); with targets give masks")
-        if masks is not None and targets is None:
-            raise ValueError("masks goes with targets (the fused training step); with grad_colors give grad_alphas")
-        if alpha_weight is not None:
-            if masks is None:
-                raise ValueError("alpha_weight needs masks")
-            w = float(alpha_weight)
-            if not (math.isfinite(w) and w >= 0.0):
-                raise ValueError(f"alpha_weight must be finite and >= 0, got {alpha_weight}")
-        if alphas is not None and grad_alphas is None and masks is None:
-            raise ValueError("alphas= needs grad_alphas or masks (a step without them renders no alpha)")
-        shape_ok = lambda t: isinstance(t, torch.Tensor) and tuple(t.shape) in ((self.H, self.W), (1, self.H, self.W))
-        for name, seq in (("grad_alphas", grad_alphas), ("masks", masks), ("alphas", alphas)):
-            if seq is None:
-                continue
-            seq = list(seq)
-            if len(seq) != self.n:
-                raise ValueError(f"{name}: {len(seq)} entries for {self.n} views")
-            for t in seq:
-                if not shape_ok(t):
-                    raise ValueError(f"{name}: every entry must be a [1,H,W] or [H,W] tensor with H,W = {self.H},{self.W}, "
-                                     f"got {tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__}")
-                if name == "alphas" and not (t.is_cuda and t.dtype is torch.float32 and t.is_contiguous()):
-                    raise ValueError("alphas: outputs must be contiguous float32 tensors on the HIP device")
-                if name == "masks" and t.dtype is not torch.float32:
-                    raise ValueError("masks: float32 tensors (loss.content_mask)")
+    @property
+    def workspace(self) -> Optional[torch.Tensor]:
+        """The workspace tensor run() uses (allocated by it, or adopted by use_workspace); None before the first run()."""
+        return self._ws
+
+    def workspace_bytes(self, P: int) -> int:
+        """Bytes of the workspace of a run() with P Gaussians at the current capacity and n_streams."""
+        return int(self.L.lr_views_workspace_bytes(int(P), self.W, self.H, self.capacity, self.n_streams, self.parts))
+
+    def use_workspace(self, tensor: torch.Tensor, P: int):
+        """Adopt the caller's uint8 device buffer as the workspace of runs with P Gaussians at the current capacity and
+        n_streams (its contents may be anything); ValueError if it is smaller than workspace_bytes(P)."""
+        if not (tensor.is_cuda and tensor.dtype is torch.uint8 and tensor.is_contiguous()):
+            raise ValueError("use_workspace: a contiguous uint8 tensor on the HIP device")
+        if tensor.numel() < self.workspace_bytes(P):
+            raise ValueError(f"use_workspace: {tensor.numel()} bytes, {self.workspace_bytes(P)} needed")
+        self._ws, self._ws_key = tensor, (int(P), self.capacity, self.n_streams)
+
+    def release_workspace(self):
+        """Drop the workspace (the next run() allocates one); check() has nothing to look at until then."""
+        self._ws = self._ws_key = None
 
     def run(self, means3D, opacities, scales, rotations, shs, acc: dict):
         """acc: {"means3D", "means2D", "opacity", "sh", "scales", "rotations"} -> contiguous float32 tensors that are
         accumulated into (e.g. the .grad views of a FlatGrads bucket)."""
-        P, M = int(means3D.shape[0]), int(shs.shape[1])
+        P = int(means3D.shape[0])
         key = (P, self.capacity, self.n_streams)      # the workspace is sized per stream slot: set_streams() re-allocates
         if self._ws_key != key:
-            nbytes = self._ws_bytes(P, self.W, self.H, self.capacity, self.n_streams)
-            self._ws = torch.empty((nbytes,), dtype=torch.uint8, device=self.device)
+            self._ws = torch.empty((self.workspace_bytes(P),), dtype=torch.uint8, device=self.device)
             self._ws_key = key
         for t in (means3D, opacities, scales, rotations, shs, *acc.values()):
             if not (t.is_cuda and t.dtype is torch.float32 and t.is_contiguous()):
                 raise RuntimeError("ViewBatch.run needs contiguous float32 tensors on the HIP device")
+        a = self._args
+        a.P, a.M = P, int(shs.shape[1])
+        a.means3D, a.shs, a.opacities = means3D.data_ptr(), shs.data_ptr(), opacities.data_ptr()
+        a.scales, a.rotations = scales.data_ptr(), rotations.data_ptr()
+        a.acc_mean2D, a.acc_opacity, a.acc_mean3D = acc["means2D"].data_ptr(), acc["opacity"].data_ptr(), acc["means3D"].data_ptr()
+        a.acc_sh, a.acc_scale, a.acc_rot = acc["sh"].data_ptr(), acc["scales"].data_ptr(), acc["rotations"].data_ptr()
+        a.workspace, a.workspace_bytes, a.n_streams = self._ws.data_ptr(), self._ws.numel(), self.n_streams
+        a.stream = torch.cuda.current_stream(self.device).cuda_stream
         with torch.cuda.device(self.device):
-            self._run(P, M, means3D, opacities, scales, rotations, shs, acc)
-
-    def _run(self, P, M, means3D, opacities, scales, rotations, shs, acc):
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        if self.train_mask:
-            rc = self.L.lr_views_train_mask_accumulate(
-                self.n, self._views, self._projs, self._campos, self._tanx, self._tany, P, self.degree, M,
-                self.bg.data_ptr(), self.W, self.H, means3D.data_ptr(), shs.data_ptr(), opacities.data_ptr(),
-                scales.data_ptr(), self.scale_modifier, rotations.data_ptr(), self._grads, self.lambda_dssim,
-                self._agrads, self.alpha_weight, self._dgrads if self.train_depth else None, self.depth_weight,
-                self.losses.data_ptr(), None, self._depths, self._alphas, None,
-                acc["means2D"].data_ptr(), acc["opacity"].data_ptr(), acc["means3D"].data_ptr(), acc["sh"].data_ptr(),
-                acc["scales"].data_ptr(), acc["rotations"].data_ptr(),
-                self._ws.data_ptr(), self._ws.numel(), self.capacity, self.n_streams, stream)
-            if rc < 0:
-                self._lib.raise_for(rc, "lr_views_train_mask_accumulate")
-            return
-        if self.train_depth:
-            rc = self.L.lr_views_train_depth_accumulate(
-                self.n, self._views, self._projs, self._campos, self._tanx, self._tany, P, self.degree, M,
-                self.bg.data_ptr(), self.W, self.H, means3D.data_ptr(), shs.data_ptr(), opacities.data_ptr(),
-                scales.data_ptr(), self.scale_modifier, rotations.data_ptr(), self._grads, self.lambda_dssim,
-                self._dgrads, self.depth_weight, self.losses.data_ptr(), None, self._depths, None,
-                acc["means2D"].data_ptr(), acc["opacity"].data_ptr(), acc["means3D"].data_ptr(), acc["sh"].data_ptr(),
-                acc["scales"].data_ptr(), acc["rotations"].data_ptr(),
-                self._ws.data_ptr(), self._ws.numel(), self.capacity, self.n_streams, stream)
-            if rc < 0:
-                self._lib.raise_for(rc, "lr_views_train_depth_accumulate")
-            return
-        if self.train:
-            rc = self.L.lr_views_train_accumulate(
-                self.n, self._views, self._projs, self._campos, self._tanx, self._tany, P, self.degree, M,
-                self.bg.data_ptr(), self.W, self.H, means3D.data_ptr(), shs.data_ptr(), opacities.data_ptr(),
-                scales.data_ptr(), self.scale_modifier, rotations.data_ptr(), self._grads, self.lambda_dssim,
-                self.losses.data_ptr(), None, None, acc["means2D"].data_ptr(), acc["opacity"].data_ptr(),
-                acc["means3D"].data_ptr(), acc["sh"].data_ptr(), acc["scales"].data_ptr(), acc["rotations"].data_ptr(),
-                self._ws.data_ptr(), self._ws.numel(), self.capacity, self.n_streams, stream)
-            if rc < 0:
-                self._lib.raise_for(rc, "lr_views_train_accumulate")
-            return
-        if self.alpha_mode:
-            rc = self.L.lr_views_accumulate_alpha(
-                self.n, self._views, self._projs, self._campos, self._tanx, self._tany, P, self.degree, M,
-                self.bg.data_ptr(), self.W, self.H, means3D.data_ptr(), shs.data_ptr(), None, opacities.data_ptr(),
-                scales.data_ptr(), self.scale_modifier, rotations.data_ptr(), None, self._grads, self._dgrads, self._agrads,
-                None, self._depths, self._alphas, None, acc["means2D"].data_ptr(), acc["opacity"].data_ptr(), None,
-                acc["means3D"].data_ptr(), None, acc["sh"].data_ptr(), acc["scales"].data_ptr(), acc["rotations"].data_ptr(),
-                self._ws.data_ptr(), self._ws.numel(), self.capacity, self.n_streams, stream)
-            if rc < 0:
-                self._lib.raise_for(rc, "lr_views_accumulate_alpha")
-            return
-        rc = self.L.lr_views_accumulate_depth(
-            self.n, self._views, self._projs, self._campos, self._tanx, self._tany, P, self.degree, M,
-            self.bg.data_ptr(), self.W, self.H, means3D.data_ptr(), shs.data_ptr(), None, opacities.data_ptr(),
-            scales.data_ptr(), self.scale_modifier, rotations.data_ptr(), None, self._grads, self._dgrads, None,
-            self._depths, None, acc["means2D"].data_ptr(), acc["opacity"].data_ptr(), None, acc["means3D"].data_ptr(),
-            None, acc["sh"].data_ptr(), acc["scales"].data_ptr(), acc["rotations"].data_ptr(),
-            self._ws.data_ptr(), self._ws.numel(), self.capacity, self.n_streams, stream)
+            rc = self.L.lr_views_accumulate(a)
         if rc < 0:
-            self._lib.raise_for(rc, "lr_views_accumulate_depth")
+            self._lib.raise_for(rc, "lr_views_accumulate")
 
     def check(self):
         """Synchronise and raise if any view of the previous run() overflowed the binning capacity."""
@@ -1087,8 +1041,8 @@ class ViewBatch:
             return
         P = self._ws_key[0]
         with torch.cuda.device(self.device):
-            rc = self._ws_check(self._ws.data_ptr(), P, self.W, self.H, self.capacity, self.n_streams,
-                                torch.cuda.current_stream(self.device).cuda_stream)
+            rc = self.L.lr_views_check(self._ws.data_ptr(), P, self.W, self.H, self.capacity, self.n_streams, self.parts,
+                                       torch.cuda.current_stream(self.device).cuda_stream)
         if rc < 0:
             self._lib.raise_for(rc, "lr_views_check")
 

@@ -1,5 +1,5 @@
 """References of the mask supervision losses (luciddreamer_amd.loss.masked_l1_dssim / alpha_hole, and the fused multi-view step
-lr_views_train_mask_accumulate):
+lr_views_accumulate with masks):
 
     Lc = l1_dssim(m * I, m * G, lambda)          dLc/dI = m * (d l1_dssim / dI')|_{I' = m I}
     La = weight * mean_{H*W}( A * (1 - m) )      dLa/dA = weight * (1 - m) / (H*W)

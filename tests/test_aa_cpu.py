@@ -171,7 +171,7 @@ def test_library_exports_the_setting_and_round_trips():
         assert L.lr_set_antialiasing(0) == 1 and L.lr_get_antialiasing() == 0
     finally:
         L.lr_set_antialiasing(0)
-    assert b" 0.5" in L.lr_version()
+    assert b" 0.6" in L.lr_version()
     with pytest.raises(RuntimeError):
         _lib.tune_set("antialiasing", 1)              # not a tuning knob: it changes results
 

@@ -1,5 +1,5 @@
 """Depth supervision in the multi-view step on the GPU: the masked depth L1 kernels (lr_depth_l1_*), ViewBatch with
-grad_depths (lr_views_accumulate_depth) and with depth_targets (lr_views_train_depth_accumulate), ViewStreams.run_view with
+grad_depths (lr_views_accumulate with dL_ddepth) and with depth_targets (the same call with targets), ViewStreams.run_view with
 grad_depth on its fused, direct and engine paths and through the re-run of an overflowed view, and a C3-size step."""
 import numpy as np
 import pytest
@@ -353,8 +353,8 @@ def test_run_view_recovers_an_overflowed_view_with_its_depth_share(hip_device, d
 
 # ---- 6. C3 size -----------------------------------------------------------------------------------------------------------
 def test_c3_size_views_accumulate_depth(hip_device, depth_on):
-    """Three 1080p views of the 1 M cloud in ONE lr_views_accumulate_depth call: finite, equal to the sum of three single-view
-    depth-mode backward passes, and with zero depth gradients equal to lr_views_accumulate."""
+    """Three 1080p views of the 1 M cloud in ONE lr_views_accumulate call with dL_ddepth: finite, equal to the sum of three
+    single-view depth-mode backward passes, and with zero depth gradients equal to the call without them."""
     from luciddreamer_amd import _C, parallel
     P, W, H = 1_000_000, 1920, 1080
     c = {k: v.to(hip_device) for k, v in synthetic.make_cloud(P, "band", 0).items()}

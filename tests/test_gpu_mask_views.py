@@ -1,6 +1,6 @@
 """Mask supervision in the multi-view step on the GPU: the masked L1 + DSSIM kernels (lr_masked_l1_dssim_*) against the float64
 oracle and, for an all-ones mask, against lr_l1_dssim_* bit for bit; the alpha hole term (lr_alpha_hole_*); ViewBatch with
-grad_alphas (lr_views_accumulate_alpha) and with masks (lr_views_train_mask_accumulate) against the autograd route, the same bits
+grad_alphas (lr_views_accumulate with dL_dalpha) and with masks (the same call with masks) against the autograd route, the same bits
 for every number of chains, and a C3-size step."""
 import numpy as np
 import pytest
@@ -337,7 +337,7 @@ def test_view_batch_with_masks_same_bits_for_every_number_of_chains(hip_device, 
 
 # ---- 5. C3 size ---------------------------------------------------------------------------------------------------------------
 def test_c3_size_views_train_mask(hip_device):
-    """Three 1080p views of the 1 M cloud in ONE lr_views_train_mask_accumulate call: finite, and equal to the sum of three
+    """Three 1080p views of the 1 M cloud in ONE lr_views_accumulate call with masks: finite, and equal to the sum of three
     single-view calls."""
     from luciddreamer_amd import _C, parallel
     P, W, H = 1_000_000, 1920, 1080

@@ -586,16 +586,16 @@ def test_view_batch_with_fewer_views_than_streams(hip_device):
            "scales": torch.zeros(8_000, 3, device=hip_device), "rotations": torch.zeros(8_000, 4, device=hip_device)}
     batch = parallel.ViewBatch(cams, [g], 3, torch.zeros(3, device=hip_device), binning_capacity=100_000, n_streams=3)
     P = 8_000
-    nbytes = batch.L.lr_views_workspace_bytes(P, 128, 96, 100_000, 3)
-    batch._ws = torch.full((nbytes,), 0xFF, dtype=torch.uint8, device=hip_device)      # worst-case stale contents
-    batch._ws_key = (P, 100_000)
+    stale = torch.full((batch.workspace_bytes(P),), 0xFF, dtype=torch.uint8, device=hip_device)     # worst-case stale contents
+    batch.use_workspace(stale, P)
     batch.run(cloud["means3D"], cloud["opacities"], cloud["scales"], cloud["rotations"], cloud["shs"], acc)
+    assert batch.workspace.data_ptr() == stale.data_ptr()               # run() kept the planted buffer
     batch.check()
     assert float(acc["means3D"].abs().max()) > 0
 
 
 def test_view_batch_with_fused_loss_equals_autograd(hip_device):
-    """ViewBatch(targets=...) (lr_views_train_accumulate: render -> L1+DSSIM -> backward per view inside one C call)
+    """ViewBatch(targets=...) (lr_views_accumulate with targets: render -> L1+DSSIM -> backward per view inside one C call)
     == the autograd op followed by luciddreamer_amd.loss.l1_dssim_loss, summed over the views."""
     from depth_diff_gaussian_rasterization_min import GaussianRasterizationSettings, GaussianRasterizer
     from luciddreamer_amd import parallel

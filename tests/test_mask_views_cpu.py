@@ -15,8 +15,13 @@ from tests import mask_loss_ref
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("lr_masked_l1_dssim_forward", "lr_masked_l1_dssim_backward", "lr_alpha_hole_workspace_bytes", "lr_alpha_hole_forward",
-       "lr_alpha_hole_backward", "lr_views_accumulate_alpha", "lr_views_train_mask_workspace_bytes",
-       "lr_views_train_mask_accumulate", "lr_views_train_mask_check")
+       "lr_alpha_hole_backward", "lr_views_workspace_bytes", "lr_views_accumulate", "lr_views_check")
+# the multi-view step is ONE entry point over lr_views_args with three LR_VIEWS_* flags; the positional per-mode forms are gone
+FLAGS = {"LR_VIEWS_LOSS": 1, "LR_VIEWS_DEPTH_LOSS": 2, "LR_VIEWS_MASK_LOSS": 4}
+RETIRED = ("lr_views_accumulate_alpha", "lr_views_train_mask_workspace_bytes", "lr_views_train_mask_accumulate",
+           "lr_views_train_mask_check", "lr_views_accumulate_depth", "lr_views_train_depth_workspace_bytes",
+           "lr_views_train_depth_accumulate", "lr_views_train_depth_check", "lr_views_train_workspace_bytes",
+           "lr_views_train_accumulate", "lr_views_train_check")
 
 
 @pytest.fixture(scope="module")
@@ -25,9 +30,13 @@ def built_lib():
     return build.build()
 
 
-def _declared():
+def _header():
     text = open(os.path.join(ROOT, "include", "lucid_raster.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    return re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+
+
+def _declared():
+    text = _header()
     return set(re.findall(r"^(?:int|size_t) (lr_[a-z0-9_]+)\(", text, flags=re.M))
 
 
@@ -35,6 +44,12 @@ def test_header_declares_the_mask_entry_points():
     names = _declared()
     for n in NEW:
         assert n in names, n
+    text = _header()
+    assert re.search(r"typedef struct lr_views_args \{.*?\} lr_views_args;", text, flags=re.S)
+    for flag, value in FLAGS.items():
+        assert re.search(rf"^#define {flag}\s+{value}u\s*$", text, flags=re.M), flag
+    for n in RETIRED:
+        assert n not in names and not re.search(rf"\b{n}\b", text), n
 
 
 def test_library_exports_the_mask_entry_points(built_lib):
@@ -43,20 +58,30 @@ def test_library_exports_the_mask_entry_points(built_lib):
     for n in NEW:
         assert hasattr(L, n), n
         assert n in _lib.EXPORTS, n
+    for n in RETIRED:
+        assert not hasattr(L, n), n
+        assert n not in _lib.EXPORTS, n
+    assert (_lib.LR_VIEWS_LOSS, _lib.LR_VIEWS_DEPTH_LOSS, _lib.LR_VIEWS_MASK_LOSS) == tuple(FLAGS.values())
 
 
 def test_mask_workspace_sizes_are_pure_host_functions(built_lib):
     from luciddreamer_amd import _lib
     L = _lib.lib()
+    LOSS, DEPTH, MASK = _lib.LR_VIEWS_LOSS, _lib.LR_VIEWS_DEPTH_LOSS, _lib.LR_VIEWS_MASK_LOSS
     for P, W, H, cap in ((1, 16, 16, 1000), (25_000, 256, 160, 400_000), (1_000_000, 1920, 1080, 30_000_000)):
         for n in (1, 2, 3, 4):
-            dep = L.lr_views_train_depth_workspace_bytes(P, W, H, cap, n)
-            msk = L.lr_views_train_mask_workspace_bytes(P, W, H, cap, n)
+            dep = L.lr_views_workspace_bytes(P, W, H, cap, n, LOSS | DEPTH)
+            msk = L.lr_views_workspace_bytes(P, W, H, cap, n, LOSS | MASK)
             # the slot grows by the alpha gradient image (and the hole term's partials) behind the train-depth slot
             assert msk >= dep + n * W * H * 4, (P, W, H, n)
             assert msk % 256 == 0
             # the existing layouts are unchanged
-            assert L.lr_views_workspace_bytes(P, W, H, cap, n) <= L.lr_views_train_workspace_bytes(P, W, H, cap, n) <= dep
+            assert 0 <= L.lr_views_workspace_bytes(P, W, H, cap, n, 0) <= L.lr_views_workspace_bytes(P, W, H, cap, n, LOSS) <= dep
+            # a mask step's slot always has the depth part
+            assert L.lr_views_workspace_bytes(P, W, H, cap, n, LOSS | DEPTH | MASK) == msk
+            # the mask or depth part without the colour loss, or an unknown bit, is no layout
+            for bad in (MASK, DEPTH, DEPTH | MASK, LOSS | 8, 1 << 31):
+                assert L.lr_views_workspace_bytes(P, W, H, cap, n, bad) == 0, bad
     for H, W in ((16, 16), (257, 511), (512, 512), (1080, 1920)):
         b = L.lr_alpha_hole_workspace_bytes(H, W)
         assert b >= math.ceil(H * W / 2048) * 8 and b % 256 == 0

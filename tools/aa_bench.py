@@ -95,7 +95,7 @@ def run(name, args, dev):
                 batch.run(c["means3D"], c["opacities"], c["scales"], c["rotations"], c["shs"], acc)
             vms = _time(views, args.steps, max(2, args.warmup // 2))
             batch.check()
-            batch._ws = None
+            batch.release_workspace()
             res["on" if on else "off"] = dict(one_view=one, views30=dict(step_ms=round(vms, 3),
                                                                         views_per_s=round(len(cams) / vms * 1e3, 1)))
         finally:

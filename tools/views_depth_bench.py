@@ -4,8 +4,8 @@
 
 For each workload (bench.py's C3 and LD-512 clouds, --views views of the rotate360 path, ONE ViewBatch call per step over
 --streams chains, async mode with the capacity bench.py would give) four steps are timed with HIP events (median of --steps after
---warmup): `default` (grad_colors, lr_views_accumulate) against `depth` (grad_colors + grad_depths, lr_views_accumulate_depth),
-and `train` (targets, lr_views_train_accumulate) against `train_depth` (targets + depth_targets, lr_views_train_depth_accumulate).
+--warmup): `default` (lr_views_accumulate with grad_colors) against `depth` (with grad_colors + grad_depths),
+and `train` (with targets) against `train_depth` (with targets + depth_targets).
 Then lr_depth_l1_forward + lr_depth_l1_backward alone at 1080p and 512x512 (median of 200 timed pairs).  Prints ONE JSON line.
 """
 import argparse
@@ -83,7 +83,7 @@ def run(name, args, dev):
         ms = _time(step, args.steps, args.warmup)
         b.check()
         res[mode] = {"step_ms": round(ms, 3), "views_per_s": round(V / ms * 1e3, 1)}
-        b._ws = None                                   # one workspace at a time
+        b.release_workspace()                           # one workspace at a time
     res["depth_over_default"] = round(res["depth"]["step_ms"] / res["default"]["step_ms"], 3)
     res["train_depth_over_train"] = round(res["train_depth"]["step_ms"] / res["train"]["step_ms"], 3)
     return res

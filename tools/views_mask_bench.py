@@ -4,9 +4,9 @@
 
 For each workload (bench.py's C3 and LD-512 clouds, --views views of the rotate360 path, ONE ViewBatch call per step over
 --streams chains, async mode with the capacity bench.py would give) four steps are timed with HIP events (median of --steps after
---warmup): `default` (grad_colors, lr_views_accumulate) against `alpha` (grad_colors + grad_alphas, lr_views_accumulate_alpha),
-and `train` (targets, lr_views_train_accumulate) against `train_mask` (targets + masks, alpha_weight 0.5,
-lr_views_train_mask_accumulate; the masks are LucidDreamer-like, with holes).  Then, at 1080p and 512x512 (median of 200 timed
+--warmup): `default` (lr_views_accumulate with grad_colors) against `alpha` (with grad_colors + grad_alphas),
+and `train` (with targets) against `train_mask` (with targets + masks, alpha_weight 0.5; the masks are LucidDreamer-like, with
+holes).  Then, at 1080p and 512x512 (median of 200 timed
 calls each): lr_l1_dssim_forward + backward against lr_masked_l1_dssim_forward + backward, and lr_alpha_hole_forward +
 lr_alpha_hole_backward.  Prints ONE JSON line.
 """
@@ -84,7 +84,7 @@ def run(name, args, dev):
         ms = _time(step, args.steps, args.warmup)
         b.check()
         res[mode] = {"step_ms": round(ms, 3), "views_per_s": round(V / ms * 1e3, 1)}
-        b._ws = None                                   # one workspace at a time
+        b.release_workspace()                           # one workspace at a time
     res["alpha_over_default"] = round(res["alpha"]["step_ms"] / res["default"]["step_ms"], 3)
     res["train_mask_over_train"] = round(res["train_mask"]["step_ms"] / res["train"]["step_ms"], 3)
     return res
