@@ -12,6 +12,7 @@ Targets are renders of a hidden "ground truth" cloud from a look-around camera p
 a perturbed subset of it.  Prints the loss every `--log` iterations and the time per iteration.
 
     python examples/train_loop.py [--gaussians 200000] [--iters 300] [--resolution 512x512]
+                                  [--absgrad --densify-grad-threshold 0.0008]
 """
 import argparse
 import math
@@ -87,6 +88,7 @@ def train(args, log=print):
     # optimised, so the capacity is taken over the views of the path, with generous headroom
     config.set_async(not args.exact, headroom=1.5, warm_calls=len(cams))     # overflowed views are re-rendered (default policy)
     config.set_antialiasing(args.antialiasing)     # opacity compensation for the 2D dilation; render the result with it on too
+    config.set_absgrad(args.absgrad)               # AbsGS: the backward attaches viewspace_points.absgrad, the statistics use it
     losses = []
     gen = torch.Generator().manual_seed(0)
     torch.cuda.synchronize()
@@ -101,7 +103,7 @@ def train(args, log=print):
             if it < args.densify_until:                                                   # :308-318
                 densify.add_densification_stats(model, pkg["viewspace_points"], radii)   # :310-311 + stats, one kernel
                 if it >= args.densify_from and it % args.densify_every == 0:
-                    densify.densify_and_prune(model, 0.0002, 0.005, 5.0, 20)
+                    densify.densify_and_prune(model, args.densify_grad_threshold, 0.005, 5.0, 20)
             model.optimizer.step()                                                        # :322-324
             model.optimizer.zero_grad(set_to_none=True)
         if it % args.log == 0 or it == 1:
@@ -111,22 +113,32 @@ def train(args, log=print):
     dt = time.perf_counter() - t0
     config.set_async(True)              # back to the library defaults
     config.set_antialiasing(False)
+    config.set_absgrad(False)
     log(f"{args.iters} iterations in {dt:.2f} s = {dt / args.iters * 1e3:.3f} ms/iteration")
     return losses, dt
 
 
 def default_args(**kw):
     d = dict(gaussians=200_000, iters=300, resolution="512x512", views=12, lambda_dssim=0.2, log=50, densify_from=100,
-             densify_every=100, densify_until=10_000, exact=False, torch_adam=False, antialiasing=False)
+             densify_every=100, densify_until=10_000, exact=False, torch_adam=False, antialiasing=False, absgrad=False,
+             densify_grad_threshold=0.0002)
     d.update(kw)
     return SimpleNamespace(**d)
+
+
+HELP = {
+    "absgrad": "densify by the absolute view-space gradient (AbsGS, config.set_absgrad): per-pixel pulls on a Gaussian are summed "
+               "by magnitude, so large Gaussians over blurry regions get split; raise --densify-grad-threshold with it",
+    "densify_grad_threshold": "clone / split threshold on the accumulated view-space gradient norm (reference: 0.0002).  Summed "
+                              "magnitudes are larger than the signed norm: with --absgrad use about 4x (0.0008)",
+}
 
 
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     for k, v in vars(default_args()).items():
         if isinstance(v, bool):
-            ap.add_argument("--" + k.replace("_", "-"), action="store_true")
+            ap.add_argument("--" + k.replace("_", "-"), action="store_true", help=HELP.get(k))
         else:
-            ap.add_argument("--" + k.replace("_", "-"), type=type(v), default=v)
+            ap.add_argument("--" + k.replace("_", "-"), type=type(v), default=v, help=HELP.get(k))
     train(ap.parse_args())

@@ -427,6 +427,96 @@ int lr_backward_raw_alpha(int P, int D, int M, int R,
                           void* stream);
 
 /*
+ * Absgrad mode (AbsGS; gsplat's `absgrad`): lr_backward_alpha / lr_backward_raw_alpha with one more output, dL_dmean2D_abs
+ * [P,3] right after dL_dmean2D.  Each takes its alpha counterpart's arguments; dL_depths / depth_image and dL_dalpha stay
+ * optional (NULL), dL_dmean2D_abs is required (LR_ERR_INVALID_ARG when NULL) and 16-byte aligned.
+ * Definition.  Let L be the scalar the call differentiates: sum dL_dpix . colour, plus the depth and alpha terms when their
+ * gradients are given.  For pixel p and Gaussian i let g[p,i] in R^2 be the part of dL/dmeans2D_i[:2] that flows through pixel p,
+ * in the NDC scale of dL_dmean2D (0.5 W, 0.5 H; backward.cu:473-474), so that sum_p g[p,i] = dL_dmean2D[i, :2].  Then
+ *     dL_dmean2D_abs[i] = ( sum_p |g[p,i].x|,  sum_p |g[p,i].y|,  0 ).
+ * Every convention of the signed path holds: the power > 0 and alpha < 1/255 skips, nothing behind a pixel's last contributor,
+ * the 0.99 clamp not differentiated, strict mode (lr_tune_set("strict")) and anti-aliasing.  Rows with radii <= 0 are exact zeros.
+ * dL_dmean2D_abs >= |dL_dmean2D| componentwise, with equality only where the per-pixel pulls do not cancel: a large Gaussian over
+ * a blurry region has a near-zero signed gradient and a large absolute one, which is what a densification rule wants to see.
+ * The tensor is always WRITTEN: zero-filled by the call (also under LR_ACC_NO_ZERO_FILL, like dL_dmean2D), never accumulated
+ * (no bit of accumulate_mask refers to it), not part of the armed fused step.  Every other output is what the alpha counterpart
+ * gives for the same arguments up to the rounding of another reduction order: the blend backward runs the 2-wave shape over
+ * whole lists at every image size, as depth mode does.  No global float atomics: bit-repeatable.  lr_views_accumulate does not
+ * produce it.  Errors and the return value are those of the alpha counterpart.
+ */
+int lr_backward_absgrad(int P, int D, int M, int R,
+                        const float* background,
+                        int width, int height,
+                        const float* means3D,
+                        const float* shs,
+                        const float* colors_precomp,
+                        const float* scales,
+                        float scale_modifier,
+                        const float* rotations,
+                        const float* cov3D_precomp,
+                        const float* viewmatrix,
+                        const float* projmatrix,
+                        const float* campos,
+                        float tan_fovx, float tan_fovy,
+                        const int* radii,
+                        char* geom_buffer,
+                        char* binning_buffer,
+                        char* image_buffer,
+                        const float* dL_dpix,
+                        const float* dL_depths,
+                        const float* depth_image,
+                        const float* dL_dalpha,
+                        float* dL_dmean2D,
+                        float* dL_dmean2D_abs,
+                        float* dL_dconic,
+                        float* dL_dopacity,
+                        float* dL_dcolor,
+                        float* dL_dmean3D,
+                        float* dL_dcov3D,
+                        float* dL_dsh,
+                        float* dL_dscale,
+                        float* dL_drot,
+                        int debug,
+                        long long binning_capacity,
+                        unsigned int accumulate_mask,
+                        void* stream);
+
+int lr_backward_raw_absgrad(int P, int D, int M, int R,
+                            const float* background,
+                            int width, int height,
+                            const float* xyz,
+                            const float* features_dc,
+                            const float* features_rest,
+                            const float* opacity_raw,
+                            const float* scaling_raw,
+                            float scale_modifier,
+                            const float* rotation_raw,
+                            const float* viewmatrix,
+                            const float* projmatrix,
+                            const float* campos,
+                            float tan_fovx, float tan_fovy,
+                            const int* radii,
+                            char* geom_buffer,
+                            char* binning_buffer,
+                            char* image_buffer,
+                            const float* dL_dpix,
+                            const float* dL_depths,
+                            const float* depth_image,
+                            const float* dL_dalpha,
+                            float* dL_dmean2D,
+                            float* dL_dmean2D_abs,
+                            float* dL_dopacity_raw,
+                            float* dL_dxyz,
+                            float* dL_dfeatures_dc,
+                            float* dL_dfeatures_rest,
+                            float* dL_dscaling_raw,
+                            float* dL_drotation_raw,
+                            int debug,
+                            long long binning_capacity,
+                            unsigned int accumulate_mask,
+                            void* stream);
+
+/*
  * Multi-view step (new; the reference renders one view per Python iteration, luciddreamer.py:291-304).
  * lr_views_accumulate runs lr_forward + the backward for n_views views of ONE parameter set and ACCUMULATES the gradients
  * into the acc_* buffers.  Everything is enqueued from C in one call: views alternate over up to 4 chains (forward of view

@@ -13,6 +13,7 @@ There is no fallback: a missing extension raises on import.
 Beyond the reference's contract (all optional, keyword-only):
     binning_capacity : > 0 runs lr_forward in async mode (no host sync; see lucid_raster.h)
     dL_dout_alpha    : the gradient of the alpha output (render_alpha), on both backward entry points
+    absgrad          : absgrad mode (lr_backward_absgrad / lr_backward_raw_absgrad), on both backward entry points
 """
 try:
     from . import _C_ext
@@ -46,7 +47,7 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
                                  cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color,
                                  dL_dout_depth, sh, degree, campos, geomBuffer, R, binningBuffer, imageBuffer,
                                  debug, *, binning_capacity=0, accumulate_into=None, skip_unused=False, depth_image=None,
-                                 dL_dout_alpha=None):
+                                 dL_dout_alpha=None, absgrad=False):
     """accumulate_into (optional): {name: tensor} with names among ACC_BITS; the gradient of that input is
     ADDED in place into the given contiguous float32 tensor (rows of culled Gaussians untouched) and the
     corresponding slot of the returned tuple is None.
@@ -56,12 +57,13 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
     depth_image (optional): the forward's depth output -- depth mode: dL_dout_depth is honoured.  Without it dL_dout_depth
     is ignored, as in the reference.
     dL_dout_alpha (optional, (1, H, W)): the gradient of the alpha output (render_alpha) as well, alone or together with depth
-    mode.  Every mode, the default included, is one call of lr_backward_alpha with NULL for what is absent."""
+    mode.  Every mode, the default included, is one call of lr_backward_alpha with NULL for what is absent.
+    absgrad: one call of lr_backward_absgrad instead; the result gains a ninth entry, dL_dmean2D_abs [P,3] (always a new tensor)."""
     acc = _NONE8 if not accumulate_into else [accumulate_into.get(k) for k in GRAD_ORDER]
     return tuple(_C_ext.rasterize_gaussians_backward(
         background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix, projmatrix,
         tan_fovx, tan_fovy, dL_dout_color, dL_dout_depth, sh, degree, campos, geomBuffer, R, binningBuffer, imageBuffer,
-        debug, binning_capacity, acc, skip_unused, depth_image=depth_image, dL_dout_alpha=dL_dout_alpha))
+        debug, binning_capacity, acc, skip_unused, depth_image=depth_image, dL_dout_alpha=dL_dout_alpha, absgrad=bool(absgrad)))
 
 
 def rasterize_gaussians_raw(background, xyz, features_dc, features_rest, opacity_raw, scaling_raw, rotation_raw,
@@ -81,12 +83,13 @@ def rasterize_gaussians_raw_backward(background, xyz, radii, features_dc, featur
                                      rotation_raw, scale_modifier, viewmatrix, projmatrix, tan_fovx, tan_fovy,
                                      dL_dout_color, degree, campos, geomBuffer, R, binningBuffer, imageBuffer, debug, *,
                                      binning_capacity=0, accumulate_into=None, no_zero_fill=False, dL_dout_depth=None,
-                                     depth_image=None, dL_dout_alpha=None):
+                                     depth_image=None, dL_dout_alpha=None, absgrad=False):
     """Gradients w.r.t. the stored tensors: (means2D, xyz, features_dc, features_rest, opacity, scaling, rotation).
     accumulate_into: {"means2D","xyz","opacity","scaling","rotation": tensor, "features": (dc_grad, rest_grad)} adds
     in place (slot returned as None).
     dL_dout_depth + depth_image (the forward's depth output): depth mode.
-    dL_dout_alpha: the gradient of the alpha output as well.  Every mode is one call of lr_backward_raw_alpha."""
+    dL_dout_alpha: the gradient of the alpha output as well.  Every mode is one call of lr_backward_raw_alpha.
+    absgrad: one call of lr_backward_raw_absgrad instead; the result gains an eighth entry, dL_dmean2D_abs [P,3]."""
     acc = _NONE8
     if accumulate_into:
         f = accumulate_into.get("features") or (None, None)
@@ -96,7 +99,7 @@ def rasterize_gaussians_raw_backward(background, xyz, radii, features_dc, featur
         background, xyz, radii, features_dc, features_rest, opacity_raw, scaling_raw, rotation_raw, scale_modifier, viewmatrix,
         projmatrix, tan_fovx, tan_fovy, dL_dout_color, degree, campos, geomBuffer, R, binningBuffer, imageBuffer, debug,
         binning_capacity, acc, bool(no_zero_fill), dL_dout_depth=dL_dout_depth, depth_image=depth_image,
-        dL_dout_alpha=dL_dout_alpha))
+        dL_dout_alpha=dL_dout_alpha, absgrad=bool(absgrad)))
 
 
 # one Adam step whose gradients are valid only in the rows of the Gaussians one view visited (lr_adam_step_masked)

@@ -28,7 +28,7 @@ _lock = threading.Lock()
 
 EXPORTS = ("lr_last_error", "lr_version", "lr_geom_bytes", "lr_img_bytes", "lr_binning_bytes", "lr_forward",
            "lr_backward", "lr_forward_raw", "lr_backward_raw", "lr_backward_depth", "lr_backward_raw_depth",
-           "lr_backward_alpha", "lr_backward_raw_alpha", "lr_render_alpha", "lr_mark_visible", "lr_check", "lr_dist2_workspace_bytes", "lr_dist2",
+           "lr_backward_alpha", "lr_backward_raw_alpha", "lr_backward_absgrad", "lr_backward_raw_absgrad", "lr_render_alpha", "lr_mark_visible", "lr_check", "lr_dist2_workspace_bytes", "lr_dist2",
            "lr_dist2_workspace_layout",
            "lr_profile_enable", "lr_profile_stage_name", "lr_profile_read", "lr_tune_set", "lr_last_launch_shapes", "lr_request_early_header",
            "lr_take_early_ticket", "lr_forward_ticket", "lr_backward_wait_event", "lr_step_begin", "lr_step_end", "lr_step_abort",
@@ -140,6 +140,22 @@ def lib():
                                       vp, vp, vp, vp,                            # geom binning img dL_dpix
                                       vp, vp, vp, vp, vp, vp, vp,                # 7 gradient outputs
                                       ci, ll, ctypes.c_uint, vp]                 # debug capacity accumulate_mask stream
+        L.lr_backward_absgrad.restype = ci
+        L.lr_backward_absgrad.argtypes = [ci, ci, ci, ci, vp, ci, ci,            # P D M R bg W H
+                                          vp, vp, vp, vp, cf, vp, vp,            # means3D shs colors scales mod rot cov3D
+                                          vp, vp, vp, cf, cf, vp,                # view proj campos tanx tany radii
+                                          vp, vp, vp, vp, vp, vp, vp,            # geom binning img dL_dpix dL_ddepth depth_image dL_dalpha
+                                          vp, vp,                                # dL_dmean2D dL_dmean2D_abs
+                                          vp, vp, vp, vp, vp, vp, vp, vp,        # the other 8 gradient outputs
+                                          ci, ll, ctypes.c_uint, vp]             # debug capacity accumulate_mask stream
+        L.lr_backward_raw_absgrad.restype = ci
+        L.lr_backward_raw_absgrad.argtypes = [ci, ci, ci, ci, vp, ci, ci,        # P D M R bg W H
+                                              vp, vp, vp, vp, vp, cf, vp,        # xyz f_dc f_rest opacity scaling mod rotation
+                                              vp, vp, vp, cf, cf, vp,            # view proj campos tanx tany radii
+                                              vp, vp, vp, vp, vp, vp, vp,        # geom binning img dL_dpix dL_ddepth depth_image dL_dalpha
+                                              vp, vp,                            # dL_dmean2D dL_dmean2D_abs
+                                              vp, vp, vp, vp, vp, vp,            # the other 6 gradient outputs
+                                              ci, ll, ctypes.c_uint, vp]         # debug capacity accumulate_mask stream
         L.lr_render_alpha.restype = ci
         L.lr_render_alpha.argtypes = [vp, ci, ci, vp, vp]                        # image_buffer W H out_alpha stream
         L.lr_mark_visible.restype = ci

@@ -36,6 +36,7 @@ import warnings
 _async = os.environ.get("LUCID_RASTER_EXACT", "0") != "1"
 _fused_accumulate = False
 _depth_gradient = False       # set_depth_gradient
+_absgrad = False              # set_absgrad
 _headroom = 1.3
 _hwm = {}            # (device, P, H, W) -> largest instance count observed
 _pending = []        # "drop" / "raise": [[ticket of lr_header_post, key, policy]]
@@ -163,6 +164,26 @@ def depth_gradient() -> bool:
     return _depth_gradient
 
 
+def set_absgrad(enabled: bool):
+    """Absolute view-space gradient for densification (AbsGS; gsplat's `absgrad=True`; off by default; process-wide).  The
+    quantity densification goes by, the norm of dL/dmeans2D[:, :2], is a signed sum over the pixels a Gaussian covers: a large
+    Gaussian over a blurry region is pulled in opposite directions by the pixels on its two sides, the pulls cancel, and it is
+    never split.  When the switch is on at a FORWARD of either operator (render / render_raw, GaussianRasterizer, the drop-in),
+    that view's backward runs the absgrad kernels (lr_backward_absgrad / lr_backward_raw_absgrad) and attaches
+    `means2D.absgrad` [P,3] to the means2D tensor the caller passed: per Gaussian (sum_p |g_p.x|, sum_p |g_p.y|, 0) over the
+    per-pixel shares g_p of dL/dmeans2D -- replaced at every backward, never accumulated; with the switch off the attribute is
+    never set.  densify.add_densification_stats then feeds that tensor instead of .grad to the unchanged statistics kernel.
+    Every gradient is what it is with the switch off (up to the rounding of another reduction order).  Summed magnitudes are
+    larger than the signed norm: raise the densification threshold (gsplat suggests about 4x: 0.0008 for the usual 0.0002).
+    The multi-view step (ViewBatch, ChunkedViewStep) does not produce it.  INTEGRATION.md 2g."""
+    global _absgrad
+    _absgrad = bool(enabled)
+
+
+def absgrad() -> bool:
+    return _absgrad
+
+
 def set_antialiasing(enabled: bool):
     """Anti-aliased splatting (off by default; process-wide; lr_set_antialiasing).  Preprocess dilates every screen-space
     covariance by 0.3 px^2 and leaves the opacity as it was, so a splat smaller than a pixel deposits more energy than it holds:
@@ -197,7 +218,9 @@ def is_async() -> bool:
 
 
 def reset():
+    global _absgrad
     drain()
+    _absgrad = False
     from . import _lib
     if _lib._lib is not None:             # (a process that never loaded the library has nothing to turn off)
         set_antialiasing(False)

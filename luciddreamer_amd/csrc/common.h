@@ -471,7 +471,10 @@ void launch_render_bwd(int W, int H, int gx, int gy, const uint2* ranges, const 
                        const GaussRec* rec, const float* bg, const float* final_T,
                        const uint32_t* n_contrib, const float* dL_dpix, char* bin_base, const GeomHeader* hdr,
                        const uint32_t* tile_seg0, const float4* c_final, long long seg_bound, hipStream_t s,
-                       const float* dL_ddepth = nullptr, const float* depth_img = nullptr, const float* dL_dalpha = nullptr);
+                       const float* dL_ddepth = nullptr, const float* depth_img = nullptr, const float* dL_dalpha = nullptr,
+                       bool absgrad = false);
+// absgrad: absgrad mode (lr_backward_absgrad) -- the k_render_bwd_abs kernels (2-wave shape, whole lists, with the depth / alpha
+// terms the pointers ask for), which also leave each instance's sums of |per-pixel dL/dmean2D| in its slot's last two floats
 // ---- Adam, element-wise (adam.hip and the step fused into the per-Gaussian backward, gauss_bwd.hip) -----------------------
 // torch's single-tensor Adam (torch/optim/adam.py _single_tensor_adam; no weight decay, amsgrad or maximize) with the roundings
 // of torch's own kernels: lerp = fma(w, b - a, a), addcmul = fma(value * t1, t2, self), addcdiv = fma(value, t1 / t2, self);
@@ -492,7 +495,10 @@ void launch_gauss_bwd(const ViewParams& vp, const float* means3D, const float* s
                       const char* bin_base, const GeomHeader* hdr,
                       float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor,
                       float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot,
-                      uint32_t accum_mask, float* acc16, hipStream_t s, bool depth = false, bool antialiasing = false);
+                      uint32_t accum_mask, float* acc16, hipStream_t s, bool depth = false, bool antialiasing = false,
+                      float* dL_dmean2D_abs = nullptr);
+// dL_dmean2D_abs != nullptr [P,3]: the k_gauss_bwd_abs kernels, which also sum the slots' two absgrad floats per Gaussian and
+// WRITE {x, y, 0} to the rows of visible Gaussians (never accumulated; the caller zero-fills the tensor)
 // antialiasing: the view's forward ran under lr_set_antialiasing(1) -- the <RAW, AA = true> kernels chain the record's opacity
 // gradient through aa_coef to the opacity and to the 2D covariance (the non-raw ones read the record's opacity from the geom
 // buffer, which starts at `hdr`)

@@ -392,7 +392,8 @@ template <bool RAW, bool AA>
 __global__ void __launch_bounds__(GB_THREADS) __attribute__((amdgpu_waves_per_eu(LR_GB_WAVES, 8)))
 k_gauss_bwd(LR_GB_PARAMS)
 {
-    constexpr bool DEPTH = false;
+    constexpr bool DEPTH = false, ABSG = false;
+    constexpr float* dL_dmean2D_abs = nullptr;
 #include "gauss_bwd_body.h"
 }
 // depth mode (lr_backward_depth / lr_backward_raw_depth): its own entry point, so that k_gauss_bwd keeps its instruction stream
@@ -400,7 +401,16 @@ template <bool RAW, bool AA>
 __global__ void __launch_bounds__(GB_THREADS) __attribute__((amdgpu_waves_per_eu(LR_GB_WAVES, 8)))
 k_gauss_bwd_depth(LR_GB_PARAMS)
 {
-    constexpr bool DEPTH = true;
+    constexpr bool DEPTH = true, ABSG = false;
+    constexpr float* dL_dmean2D_abs = nullptr;
+#include "gauss_bwd_body.h"
+}
+// absgrad mode (lr_backward_absgrad / lr_backward_raw_absgrad), with or without the depth term: own entry points again
+template <bool RAW, bool AA, bool DEPTH>
+__global__ void __launch_bounds__(GB_THREADS) __attribute__((amdgpu_waves_per_eu(LR_GB_WAVES, 8)))
+k_gauss_bwd_abs(LR_GB_PARAMS, float* __restrict__ dL_dmean2D_abs)
+{
+    constexpr bool ABSG = true;
 #include "gauss_bwd_body.h"
 }
 #undef LR_GB_PARAMS
@@ -459,11 +469,29 @@ void launch_gauss_bwd(const ViewParams& vp, const float* means3D, const float* s
                       const char* bin_base, const GeomHeader* hdr,
                       float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor,
                       float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot,
-                      uint32_t accum_mask, float* acc16, hipStream_t s, bool depth, bool antialiasing)
+                      uint32_t accum_mask, float* acc16, hipStream_t s, bool depth, bool antialiasing, float* dL_dmean2D_abs)
 {
     (void)colors_precomp;
     if (vp.P <= 0) return;
     const int groups = std::min((vp.P + GB_THREADS - 1) / GB_THREADS, GB_MAX_GROUPS);
+    if (dL_dmean2D_abs != nullptr) {
+#define LR_GBA(RAW_, AA_, DEPTH_) hipLaunchKernelGGL((k_gauss_bwd_abs<RAW_, AA_, DEPTH_>), dim3(groups), dim3(GB_THREADS), 0, s, vp,   \
+                               means3D, scales, rotations, shs, cov3D_precomp, vis_list, clamped, offsets, bin_base, hdr, dL_dmean2D,  \
+                               dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, accum_mask, acc16, \
+                               dL_dmean2D_abs)
+        switch ((vp.raw ? 1 : 0) | (antialiasing ? 2 : 0) | (depth ? 4 : 0)) {
+            case 0: LR_GBA(false, false, false); break;
+            case 1: LR_GBA(true, false, false); break;
+            case 2: LR_GBA(false, true, false); break;
+            case 3: LR_GBA(true, true, false); break;
+            case 4: LR_GBA(false, false, true); break;
+            case 5: LR_GBA(true, false, true); break;
+            case 6: LR_GBA(false, true, true); break;
+            default: LR_GBA(true, true, true); break;
+        }
+#undef LR_GBA
+        return;
+    }
 #define LR_GB(KERNEL_, RAW_, AA_) hipLaunchKernelGGL((KERNEL_<RAW_, AA_>), dim3(groups), dim3(GB_THREADS), 0, s, vp, means3D, scales,  \
                                rotations, shs, cov3D_precomp, vis_list, clamped, offsets, bin_base, hdr, dL_dmean2D, dL_dconic,     \
                                dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, accum_mask, acc16)

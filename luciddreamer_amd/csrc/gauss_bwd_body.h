@@ -2,6 +2,8 @@
 // included INSIDE each of them with `RAW`, `AA` (template parameters) and `DEPTH` (constexpr bool) in scope.  Textual inclusion, not an
 // inlined __device__ function: the function form changed k_gauss_bwd's instruction stream (operand order of its slot sums), and
 // the default kernel must stay instruction for instruction what it was.  DEPTH: the slots' dL/d(view depth) float is summed too.
+// ABSG (k_gauss_bwd_abs; constexpr bool, with `dL_dmean2D_abs` in scope): the slots' two absgrad floats (g2.z, g2.w: the blend
+// backward's sums of |per-pixel dL/dmean2D|) are summed too and written -- never accumulated -- to dL_dmean2D_abs [P,3] as {x, y, 0}.
 // AA && !RAW: the record's opacity (opacity * coef, what the blend saw) is read from the geom buffer, whose first bytes are `hdr`.
 // NOT a stand-alone header (no include guard on purpose).
     constexpr uint32_t SERIAL_MAX = 24;      // instances summed by the owning lane; more -> whole wave helps
@@ -68,6 +70,7 @@
             p1.x = wave_sum(p1.x); p1.y = wave_sum(p1.y); p1.z = wave_sum(p1.z); p1.w = wave_sum(p1.w);
             p2.x = wave_sum(p2.x);
             if constexpr (DEPTH) p2.y = wave_sum(p2.y);
+            if constexpr (ABSG) { p2.z = wave_sum(p2.z); p2.w = wave_sum(p2.w); }
             if (lane == src) { g0 = p0; g1 = p1; g2 = p2; }
         }
         // ---- spherical harmonics: rows are 3*M floats per Gaussian.  One lane per Gaussian would make every
@@ -168,5 +171,11 @@
             gauss_backward_one<RAW, DEPTH, AA>(idx, vp, means3D, scales, rotations, have_sh, dL_ddir, cov3D_precomp, g0, g1, g2,
                                dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dscale,
                                dL_drot, accum_mask, acc16, rec_opacity);
+        if constexpr (ABSG) {
+            if (live) {
+                float* __restrict__ pa = dL_dmean2D_abs + 3 * (size_t)idx;
+                pa[0] = g2.z; pa[1] = g2.w; pa[2] = 0.f;
+            }
+        }
         lds_barrier();                     // the LDS planes are rewritten by the next round
     }

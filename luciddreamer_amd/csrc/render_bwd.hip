@@ -195,12 +195,17 @@ struct BwdPix {
 // C3 view; most of a dense one do have stopped pixels) walks its candidates through the copy of the loop without it.
 // DEPTH (depth-mode kernels only): the layer's view depth z enters the recursion as a fourth "colour" with weight p.gz (A
 // carries the coverage term, see render_bwd_item), and the lane sums the direct term w * gz = alpha T gz into *sZ.
-template <bool FIRSTM, bool FIRSTC, bool CHECK_LAST, bool STRICT = false, bool DEPTH = false>
+// ABSG (absgrad kernels only, k_render_bwd_abs): the pixel's own share of dL/dmean2D, dop (kA dx + bdy) and dop (qB dx + cdy) up
+// to the factors the flush applies, is summed by ABSOLUTE value into *sAx / *sAy (the |.| is a source modifier of the add).
+// kA = 2 qA (the conic's a in strict mode), bdy = qB dy, cdy = 2 qC dy (c dy in strict mode): formed once per candidate and lane.
+template <bool FIRSTM, bool FIRSTC, bool CHECK_LAST, bool STRICT = false, bool DEPTH = false, bool ABSG = false>
 __device__ __forceinline__ void bwd_pixel(BwdPix& p, const float qA, const float qB, const float qC, const float r0, const float r1,
                                           const float gx,
                                           const float op, const float cr, const float cg, const float cb, const uint32_t pos,
                                           float& sD, float& sMx, float& sMxx, float& sR, float& sG, float& sB,
-                                          const float z = 0.f, float* sZ = nullptr)
+                                          const float z = 0.f, float* sZ = nullptr,
+                                          const float kA = 0.f, const float bdy = 0.f, const float cdy = 0.f,
+                                          float* sAx = nullptr, float* sAy = nullptr)
 {
     const float dx = gx - p.pxf;
     float power;                                                           // (log2(e) x) the reference's power
@@ -231,6 +236,11 @@ __device__ __forceinline__ void bwd_pixel(BwdPix& p, const float qA, const float
         if (FIRSTC) *sZ = dchan * p.gz;
         else *sZ += dchan * p.gz;
     }
+    if constexpr (ABSG) {
+        const float ax = dop * __builtin_fmaf(kA, dx, bdy), ay = dop * __builtin_fmaf(qB, dx, cdy);
+        if (FIRSTM) { *sAx = __builtin_fabsf(ax); *sAy = __builtin_fabsf(ay); }
+        else { *sAx += __builtin_fabsf(ax); *sAy += __builtin_fabsf(ay); }
+    }
 }
 
 // MERGE: row_merge3 + one plain store per candidate into the wave's own accumulator copy (the default); false = the round-2
@@ -255,7 +265,12 @@ __device__ __forceinline__ void bwd_pixel(BwdPix& p, const float qA, const float
 // the whole of it is the start value of A: bg.dL - g at the list's end (and for a pixel that stopped before the segment),
 // and at a segment start where the pixel is still blending the background share seen from there, -g T_final / T_ck -- both
 // numbers the segment already has.  No instruction per layer; the segments and every shape of the default backward stay.
-template <bool QUAD, bool MERGE, bool STRICT, bool DEPTH = false, bool ALPHA = false>
+// ABSG (k_render_bwd_abs; lr_backward_absgrad; 2-wave shape, whole lists as depth mode): the AbsGS statistic.  For pixel p the
+// share of dL/dmean2D of the instance is g[p] = -dop (a dx + b dy, c dy + b dx) x the NDC scale -- the signed sums above are its
+// sum over p --; bwd_pixel sums |g[p].x| and |g[p].y| per lane (with the staged, scaled conic), a row sum per 16-lane row goes to
+// four more accumulator columns per term (as the depth term), and the flush applies what is uniform per instance (ln 2 back from
+// the log2 e staging, the NDC scale) and stores the two sums in the slot's last free floats (slot[2].z / .w, read by k_gauss_bwd_abs).
+template <bool QUAD, bool MERGE, bool STRICT, bool DEPTH = false, bool ALPHA = false, bool ABSG = false>
 __device__ __forceinline__ void render_bwd_item(const int tile, const int seg, const uint32_t ck_slot,
              const float4* __restrict__ c_final, int W, int H, int gx, const uint2* __restrict__ ranges,
              const uint32_t* __restrict__ point_list, const GaussRec* __restrict__ rec,
@@ -266,6 +281,7 @@ __device__ __forceinline__ void render_bwd_item(const int tile, const int seg, c
              const float* __restrict__ dL_dalpha = nullptr)
 {
     static_assert(!DEPTH || MERGE, "depth mode uses the merged reduction");
+    static_assert(!ABSG || (MERGE && !QUAD), "the absgrad mode is built on the 2-wave shape with the merged reduction");
     constexpr int BATCH = QUAD ? LR_QBATCH_BWD : BATCH2;
     __shared__ float4 s_q0[BATCH];      // x, y, Ap = -0.5 conic a, Bp = -conic b      (common.h gauss_power; x log2 e)
     __shared__ float4 s_q1[BATCH];      // Cp = -0.5 conic c (x log2 e), opacity, -, -   (16-byte stride like s_q0 / s_q2: the
@@ -279,7 +295,8 @@ __device__ __forceinline__ void render_bwd_item(const int tile, const int seg, c
     // into ONE copy with LDS float atomics -- two operands, so the sum does not depend on which wave comes first.)
     constexpr int NWAVES = QUAD ? 4 : 2;
     constexpr int NACC = (QUAD || MERGE) ? NWAVES : 1;
-    constexpr int NCOL = DEPTH ? 16 : 12;   // DEPTH: columns 12-15 = the dL/dz partial of each 16-lane row
+    constexpr int COL_ABS = DEPTH ? 16 : 12;        // ABSG: four columns (one per 16-lane row) of sum |g.x|, then four of sum |g.y|
+    constexpr int NCOL = COL_ABS + (ABSG ? 8 : 0);  // DEPTH: columns 12-15 = the dL/dz partial of each 16-lane row
     __shared__ float s_acc[BATCH][NACC][NCOL];
     __shared__ uint32_t s_wlast[NWAVES];
 
@@ -449,8 +466,17 @@ __device__ __forceinline__ void render_bwd_item(const int tile, const int seg, c
                 gauss_row<STRICT>(a.w, b.x, dys, r0, r1);                                       // common.h gauss_power
                 // (sZ's address only in depth mode: taken in the default kernels as well, it renamed their registers)
                 float sD = 0.f, sMx = 0.f, sMxx = 0.f, sR = 0.f, sG = 0.f, sB = 0.f, sZ = 0.f;
+                if constexpr (!ABSG) {
                 if (QUAD || ((maskL >> k) & 1ull)) bwd_pixel<true, true, CHECK, STRICT, DEPTH>(PA, a.z, a.w, b.x, r0, r1, a.x, b.y, c.x, c.y, c.z, pos, sD, sMx, sMxx, sR, sG, sB, c.w, DEPTH ? &sZ : nullptr);
                 if (!QUAD && ((maskR >> k) & 1ull)) bwd_pixel<false, false, CHECK, STRICT, DEPTH>(PB, a.z, a.w, b.x, r0, r1, a.x, b.y, c.x, c.y, c.z, pos, sD, sMx, sMxx, sR, sG, sB, c.w, DEPTH ? &sZ : nullptr);
+                }
+                // (the two |.| sums and their addresses exist in the absgrad kernels only: see sZ above)
+                float sAx = 0.f, sAy = 0.f;
+                if constexpr (ABSG) {
+                    const float kA = STRICT ? a.z : 2.0f * a.z, bdy = a.w * dys, cdy = (STRICT ? b.x : 2.0f * b.x) * dys;
+                    if ((maskL >> k) & 1ull) bwd_pixel<true, true, CHECK, STRICT, DEPTH, true>(PA, a.z, a.w, b.x, r0, r1, a.x, b.y, c.x, c.y, c.z, pos, sD, sMx, sMxx, sR, sG, sB, c.w, DEPTH ? &sZ : nullptr, kA, bdy, cdy, &sAx, &sAy);
+                    if ((maskR >> k) & 1ull) bwd_pixel<false, false, CHECK, STRICT, DEPTH, true>(PB, a.z, a.w, b.x, r0, r1, a.x, b.y, c.x, c.y, c.z, pos, sD, sMx, sMxx, sR, sG, sB, c.w, DEPTH ? &sZ : nullptr, kA, bdy, cdy, &sAx, &sAy);
+                }
                 // both pixels of a lane share dy, so the dy factors are applied to the lane's sums
                 const float sMy = dys * sD, sMxy = dys * sMx;
                 const float sMyy = dys * sMy;
@@ -464,6 +490,11 @@ __device__ __forceinline__ void render_bwd_item(const int tile, const int seg, c
                     if constexpr (DEPTH) {                    // the tenth term: a row sum, lane 12 of each row writes its column
                         const float rz = row_sum(sZ);
                         if (l16 == 12) (&s_acc[0][0][0])[jo + w * NCOL + 12 + row] = rz;
+                    }
+                    if constexpr (ABSG) {                     // two more row sums: lanes 13 / 14 of each row write their columns
+                        const float rx = row_sum(sAx), ry = row_sum(sAy);
+                        if (l16 == 13) (&s_acc[0][0][0])[jo + w * NCOL + COL_ABS + row] = rx;
+                        if (l16 == 14) (&s_acc[0][0][0])[jo + w * NCOL + COL_ABS + 4 + row] = ry;
                     }
                 } else {
                     ra = row_sum(ra); rb = row_sum(rb);
@@ -488,7 +519,7 @@ __device__ __forceinline__ void render_bwd_item(const int tile, const int seg, c
             // every instance owns one 48-byte slot: plain stores, no atomics, and the per-Gaussian sum in
             // k_gauss_bwd runs in a fixed order (the slot is written even when nothing contributed).  The factors that
             // are constant per Gaussian (opacity, conic entries, -0.5, the NDC scale of backward.cu:473-474) go in here.
-            float a9[NCOL];                            // sums of D dx, D dy, D dx^2, D dx dy, D dy^2, D, dr, dg, db (x4), [dz (x4)]
+            float a9[NCOL];                            // sums of D dx, D dy, D dx^2, D dx dy, D dy^2, D, dr, dg, db (x4), [dz (x4)], [|g.x| (x4), |g.y| (x4)]
 #pragma unroll
             for (int k = 0; k < NCOL; k++) {
                 float v = s_acc[tid][0][k];
@@ -508,8 +539,14 @@ __device__ __forceinline__ void render_bwd_item(const int tile, const int seg, c
             slot[0] = make_float4((-ca * sx - cb * sy) * ddelx_dx, (-cc * sy - cb * sx) * ddely_dy, h * a9[2], h * a9[3]);
             slot[1] = make_float4(h * a9[4], dopac, a9[6], a9[7]);
             float dz = 0.f;
-            if constexpr (DEPTH) dz = (a9[NCOL - 4] + a9[NCOL - 3]) + (a9[NCOL - 2] + a9[NCOL - 1]);
-            slot[2] = make_float4(db, dz, 0.f, 0.f);
+            if constexpr (DEPTH) dz = (a9[12] + a9[13]) + (a9[14] + a9[15]);
+            float gax = 0.f, gay = 0.f;
+            if constexpr (ABSG) {                      // the rows in fixed order, then ln 2 (scaled staging) and the NDC scale
+                const float k = STRICT ? 1.0f : LN2;
+                gax = ((a9[COL_ABS] + a9[COL_ABS + 1]) + (a9[COL_ABS + 2] + a9[COL_ABS + 3])) * (k * ddelx_dx);
+                gay = ((a9[COL_ABS + 4] + a9[COL_ABS + 5]) + (a9[COL_ABS + 6] + a9[COL_ABS + 7])) * (k * ddely_dy);
+            }
+            slot[2] = make_float4(db, dz, gax, gay);
         }
     }
 }
@@ -841,6 +878,18 @@ k_render_bwd_depth_alpha(LR_BWD_SEG_PARAMS, const float* __restrict__ dL_ddepth,
     LR_BWD_KERNEL_BODY(LR_ITEM)
 #undef LR_ITEM
 }
+// Absgrad mode (lr_backward_absgrad): the 2-wave shape with the two |.| sums of render_bwd_item<ABSG>, one workgroup per tile over
+// its whole list at every image size, as depth mode (seg_on = 0); with or without the depth terms and the ALPHA start values.
+// Own entry points: the kernels above keep their names and instruction streams.
+template <bool STRICT, bool DEPTH, bool ALPHA>
+__global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(5, 8)))
+k_render_bwd_abs(LR_BWD_SEG_PARAMS, const float* __restrict__ dL_ddepth, const float* __restrict__ depth_img,
+                 const float* __restrict__ dL_dalpha)
+{
+#define LR_ITEM(...) render_bwd_item<false, true, STRICT, DEPTH, ALPHA, true>(__VA_ARGS__, dL_ddepth, depth_img, dL_dalpha)
+    LR_BWD_KERNEL_BODY(LR_ITEM)
+#undef LR_ITEM
+}
 #ifdef LR_DIAGNOSTICS
 // rounds 4-5: the lane-swap reduction (reduce8 + row_merge3), 44 staged Gaussians per round: A/B partner (bwd_red = 2)
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8), amdgpu_num_vgpr(64)))
@@ -942,7 +991,7 @@ void launch_render_bwd(int W, int H, int gx, int gy, const uint2* ranges, const 
                        const GaussRec* rec, const float* bg, const float* final_T,
                        const uint32_t* n_contrib, const float* dL_dpix, char* bin_base, const GeomHeader* hdr,
                        const uint32_t* tile_seg0, const float4* c_final, long long seg_bound, hipStream_t s,
-                       const float* dL_ddepth, const float* depth_img, const float* dL_dalpha)
+                       const float* dL_ddepth, const float* depth_img, const float* dL_dalpha, bool absgrad)
 {
     const int num_tiles = gx * gy;
     if (num_tiles <= 0) return;
@@ -964,6 +1013,24 @@ void launch_render_bwd(int W, int H, int gx, int gy, const uint2* ranges, const 
 #define LR_BWD_ARGS W, H, gx, num_tiles, tile_map, ranges, point_list, rec, bg, final_T, n_contrib, dL_dpix, bin_base, hdr, force_check
     // instances the caller's bound allows (bin_seg_capacity(bound) = bound / BWD_SEG + 2): an upper estimate of the lists' lengths
     const bool strict = tune_get(TUNE_STRICT) > 0;
+    if (absgrad) {
+        // absgrad mode: as depth mode ONE shape at every image size, one workgroup per tile over its whole list (seg_on = 0)
+        g_last_bwd_shape = BLEND_HALF;
+#define LR_ABS(S_, D_, A_) hipLaunchKernelGGL((k_render_bwd_abs<S_, D_, A_>), dim3(grid), dim3(128), 0, s, LR_BWD_ARGS, tile_seg0,   \
+                                              c_final, grid, 0, dL_ddepth, depth_img, dL_dalpha)
+        switch ((strict ? 1 : 0) | (dL_ddepth != nullptr ? 2 : 0) | (dL_dalpha != nullptr ? 4 : 0)) {
+            case 0: LR_ABS(false, false, false); break;
+            case 1: LR_ABS(true, false, false); break;
+            case 2: LR_ABS(false, true, false); break;
+            case 3: LR_ABS(true, true, false); break;
+            case 4: LR_ABS(false, false, true); break;
+            case 5: LR_ABS(true, false, true); break;
+            case 6: LR_ABS(false, true, true); break;
+            default: LR_ABS(true, true, true); break;
+        }
+#undef LR_ABS
+        return;
+    }
     if (dL_ddepth != nullptr) {
         // depth mode: ONE shape at every image size (the 2-wave one), one workgroup per tile over its whole list -- correct for
         // any launch size, no listed segments (seg_on = 0); the shape rule and the segment switch do not apply

@@ -222,13 +222,15 @@ void check_mode_images(int64_t H, int64_t W, const Arg& gd, const Arg& di, const
 // depth_image (keyword-only; the forward's depth output): with it dL_dout_depth is honoured (depth mode); without it
 // dL_dout_depth is ignored, as in the reference.  dL_dout_alpha (keyword-only, [1,H,W]): the gradient of the alpha output
 // (render_alpha) as well, alone or with depth mode.
+// absgrad (keyword-only): absgrad mode (lr_backward_absgrad) -- a ninth entry of the result, dL_dmean2D_abs [P,3]: per Gaussian
+// the sums over pixels of |per-pixel dL/dmeans2D| (x, y, 0); always a new tensor, never accumulated.
 std::vector<OptT> rasterize_gaussians_backward(
     const at::Tensor& background, const at::Tensor& means3D, const at::Tensor& radii, const OptT& colors, const OptT& scales,
     const OptT& rotations, double scale_modifier, const OptT& cov3D_precomp, const at::Tensor& viewmatrix,
     const at::Tensor& projmatrix, double tan_fovx, double tan_fovy, const at::Tensor& dL_dout_color, const OptT& dL_dout_depth,
     const OptT& sh, int64_t degree, const at::Tensor& campos, const at::Tensor& geomBuffer, int64_t R,
     const at::Tensor& binningBuffer, const at::Tensor& imageBuffer, bool debug, int64_t binning_capacity,
-    const std::vector<OptT>& accumulate, bool skip_unused, const OptT& depth_image, const OptT& dL_dout_alpha)
+    const std::vector<OptT>& accumulate, bool skip_unused, const OptT& depth_image, const OptT& dL_dout_alpha, bool absgrad)
 {
     require_device(means3D, "means3D");
     const c10::Device dev = means3D.device();
@@ -249,6 +251,11 @@ std::vector<OptT> rasterize_gaussians_backward(
     std::vector<OptT> result(8);
     for (int k = 0; k < 8; k++)
         ptr[k] = unused[k] ? nullptr : grad_output(given(accumulate, k), shapes[k], kBit[k], dev, mask, &result[k]);
+    at::Tensor abs2d;
+    if (absgrad) {
+        abs2d = at::empty({P, 3}, at::TensorOptions().dtype(at::kFloat).device(dev));
+        result.push_back(abs2d);
+    }
     if (P != 0) {
         const Arg m = f32(means3D, dev, "means3D"), bg = f32(background, dev, "background"), view = f32(viewmatrix, dev, "viewmatrix"),
                   proj = f32(projmatrix, dev, "projmatrix"), cam = f32(campos, dev, "campos"), shc = f32(sh, dev, "sh"),
@@ -258,7 +265,14 @@ std::vector<OptT> rasterize_gaussians_backward(
         const at::Tensor radii_c = radii.contiguous();
         hipStream_t cur = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(dev.index()).stream();
         ChainScope chain(mask != 0 || t_fused_backward, dev.index(), cur);
-        const int rc = lr_backward_alpha(
+        const int rc = absgrad ? lr_backward_absgrad(
+            static_cast<int>(P), static_cast<int>(degree), M, static_cast<int>(R), bg.p, static_cast<int>(W), static_cast<int>(H), m.p,
+            shc.p, col.p, sc.p, static_cast<float>(scale_modifier), rot.p, cov.p, view.p, proj.p, cam.p, static_cast<float>(tan_fovx),
+            static_cast<float>(tan_fovy), radii_c.data_ptr<int>(), static_cast<char*>(geomBuffer.data_ptr()),
+            static_cast<char*>(binningBuffer.data_ptr()), static_cast<char*>(imageBuffer.data_ptr()), gc.p, di.p ? gd.p : nullptr,
+            di.p, ga.p, ptr[0], abs2d.data_ptr<float>(), nullptr, ptr[2], ptr[1], ptr[3], ptr[4], M ? ptr[5] : nullptr, ptr[6], ptr[7],
+            debug ? 1 : 0, static_cast<long long>(binning_capacity), mask, cur)
+                              : lr_backward_alpha(
             static_cast<int>(P), static_cast<int>(degree), M, static_cast<int>(R), bg.p, static_cast<int>(W), static_cast<int>(H), m.p,
             shc.p, col.p, sc.p, static_cast<float>(scale_modifier), rot.p, cov.p, view.p, proj.p, cam.p, static_cast<float>(tan_fovx),
             static_cast<float>(tan_fovy), radii_c.data_ptr<int>(), static_cast<char*>(geomBuffer.data_ptr()),
@@ -301,7 +315,8 @@ FwdResult rasterize_gaussians_raw(const at::Tensor& background, const at::Tensor
 
 // result / accumulate order: (means2D, xyz, features_dc, features_rest, opacity, scaling, rotation)
 // dL_dout_depth / depth_image / dL_dout_alpha (keyword-only): as in rasterize_gaussians_backward; the gradient of the depth
-// output is used only when depth_image is given as well.
+// output is used only when depth_image is given as well.  absgrad: dL_dmean2D_abs [P,3] as an eighth entry of the result
+// (lr_backward_raw_absgrad), as in rasterize_gaussians_backward.
 std::vector<OptT> rasterize_gaussians_raw_backward(
     const at::Tensor& background, const at::Tensor& xyz, const at::Tensor& radii, const at::Tensor& features_dc,
     const OptT& features_rest, const at::Tensor& opacity_raw, const at::Tensor& scaling_raw, const at::Tensor& rotation_raw,
@@ -309,7 +324,7 @@ std::vector<OptT> rasterize_gaussians_raw_backward(
     const at::Tensor& dL_dout_color, int64_t degree, const at::Tensor& campos, const at::Tensor& geomBuffer, int64_t R,
     const at::Tensor& binningBuffer, const at::Tensor& imageBuffer, bool debug, int64_t binning_capacity,
     const std::vector<OptT>& accumulate, bool no_zero_fill, const OptT& dL_dout_depth, const OptT& depth_image,
-    const OptT& dL_dout_alpha)
+    const OptT& dL_dout_alpha, bool absgrad)
 {
     require_device(xyz, "xyz");
     const c10::Device dev = xyz.device();
@@ -335,6 +350,11 @@ std::vector<OptT> rasterize_gaussians_raw_backward(
     // no_zero_fill: rows of Gaussians the view did not visit stay unwritten in the write-mode outputs (means2D excepted): for the
     // masked optimizer step (adam_step_masked below), which does not read them
     if (no_zero_fill) mask |= LR_ACC_NO_ZERO_FILL;
+    at::Tensor abs2d;
+    if (absgrad) {
+        abs2d = at::empty({P, 3}, at::TensorOptions().dtype(at::kFloat).device(dev));
+        result.push_back(abs2d);
+    }
     if (P != 0) {
         const Arg bg = f32(background, dev, "background"), x = f32(xyz, dev, "xyz"), dc = f32(features_dc, dev, "features_dc"),
                   op = f32(opacity_raw, dev, "opacity"), sc = f32(scaling_raw, dev, "scaling"), rot = f32(rotation_raw, dev, "rotation"),
@@ -345,7 +365,14 @@ std::vector<OptT> rasterize_gaussians_raw_backward(
         const at::Tensor radii_c = radii.contiguous();
         hipStream_t cur = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(dev.index()).stream();
         ChainScope chain((mask & ~LR_ACC_NO_ZERO_FILL) != 0, dev.index(), cur);
-        const int rc = lr_backward_raw_alpha(
+        const int rc = absgrad ? lr_backward_raw_absgrad(
+            static_cast<int>(P), static_cast<int>(degree), M, static_cast<int>(R), bg.p, static_cast<int>(W), static_cast<int>(H), x.p,
+            dc.p, rest.p, op.p, sc.p, static_cast<float>(scale_modifier), rot.p, view.p, proj.p, cam.p, static_cast<float>(tan_fovx),
+            static_cast<float>(tan_fovy), radii_c.data_ptr<int>(), static_cast<char*>(geomBuffer.data_ptr()),
+            static_cast<char*>(binningBuffer.data_ptr()), static_cast<char*>(imageBuffer.data_ptr()), gc.p, di.p ? gd.p : nullptr,
+            di.p, ga.p, ptr[0], abs2d.data_ptr<float>(), ptr[4], ptr[1], ptr[2], nrest ? ptr[3] : nullptr, ptr[5], ptr[6],
+            debug ? 1 : 0, static_cast<long long>(binning_capacity), mask, cur)
+                              : lr_backward_raw_alpha(
             static_cast<int>(P), static_cast<int>(degree), M, static_cast<int>(R), bg.p, static_cast<int>(W), static_cast<int>(H), x.p,
             dc.p, rest.p, op.p, sc.p, static_cast<float>(scale_modifier), rot.p, view.p, proj.p, cam.p, static_cast<float>(tan_fovx),
             static_cast<float>(tan_fovy), radii_c.data_ptr<int>(), static_cast<char*>(geomBuffer.data_ptr()),
@@ -453,7 +480,7 @@ using torch::autograd::AutogradContext;
 using torch::autograd::variable_list;
 
 struct RasterizeFn : public torch::autograd::Function<RasterizeFn> {
-    static constexpr int kForwardArgs = 23;
+    static constexpr int kForwardArgs = 24;
 
     static variable_list forward(AutogradContext* ctx, const at::Tensor& means3D, const at::Tensor& means2D, const at::Tensor& sh,
                                  const at::Tensor& colors, const at::Tensor& opacities, const at::Tensor& scales,
@@ -461,7 +488,7 @@ struct RasterizeFn : public torch::autograd::Function<RasterizeFn> {
                                  const at::Tensor& viewmatrix, const at::Tensor& projmatrix, const at::Tensor& campos,
                                  double scale_modifier, double tan_fovx, double tan_fovy, int64_t H, int64_t W, int64_t degree,
                                  bool prefiltered, int64_t binning_capacity, bool fused_accumulate, bool depth_gradient,
-                                 bool alpha)
+                                 bool alpha, bool absgrad)
     {
         // lr_set_antialiasing as this forward finds it: the geom buffer will hold opacities scaled under it (backward checks)
         const int64_t antialiasing = lr_get_antialiasing();
@@ -493,6 +520,7 @@ struct RasterizeFn : public torch::autograd::Function<RasterizeFn> {
         ctx->saved_data["capacity"] = binning_capacity;
         ctx->saved_data["fused"] = fused_accumulate;
         ctx->saved_data["antialiasing"] = antialiasing;
+        ctx->saved_data["absgrad"] = absgrad;            // config.set_absgrad, as it was at THIS forward
         // config.set_depth_gradient, as it was at THIS forward: the depth output is kept for the backward's depth mode
         // and undefined output gradients stay undefined: a loss that does not use the depth output must reach the default kernels,
         // not the depth-mode ones with a materialised zero gradient (the switch off keeps torch's default, materialised zeros)
@@ -549,7 +577,13 @@ struct RasterizeFn : public torch::autograd::Function<RasterizeFn> {
             bg, means3D, d["radii"].toTensor(), colors, scales, rotations, d["scale_modifier"].toDouble(), cov3D, viewmatrix,
             projmatrix, d["tan_fovx"].toDouble(), d["tan_fovy"].toDouble(), g_color, g_depth, sh, d["degree"].toInt(), campos,
             d["geom"].toTensor(), d["num_rendered"].toInt(), d["binning"].toTensor(), d["img"].toTensor(), false,
-            d["capacity"].toInt(), acc, true, depth_image, g_alpha);
+            d["capacity"].toInt(), acc, true, depth_image, g_alpha, d["absgrad"].toBool());
+        if (d["absgrad"].toBool()) {
+            // gsplat's convention: the statistic travels as an attribute of the means2D tensor the caller passed (its Python
+            // object, as long as the caller holds it), replaced at every backward.  The one step of this node that needs the GIL.
+            py::gil_scoped_acquire gil;
+            py::setattr(py::cast(means2D), "absgrad", py::cast(*g[8]));
+        }
         auto slot = [&](int k) { return g[k].has_value() ? *g[k] : at::Tensor(); };
         variable_list out(kForwardArgs);                       // one per forward argument; undefined = no gradient
         out[0] = slot(3); out[1] = slot(0); out[2] = slot(5); out[3] = slot(1); out[4] = slot(2); out[5] = slot(6); out[6] = slot(7);
@@ -564,11 +598,11 @@ std::vector<at::Tensor> rasterize_autograd(const at::Tensor& means3D, const at::
                                            const at::Tensor& viewmatrix, const at::Tensor& projmatrix, const at::Tensor& campos,
                                            double scale_modifier, double tan_fovx, double tan_fovy, int64_t H, int64_t W,
                                            int64_t degree, bool prefiltered, int64_t binning_capacity, bool fused_accumulate,
-                                           bool depth_gradient, bool alpha)
+                                           bool depth_gradient, bool alpha, bool absgrad)
 {
     return RasterizeFn::apply(means3D, means2D, sh, colors, opacities, scales, rotations, cov3D, bg, viewmatrix, projmatrix, campos,
                               scale_modifier, tan_fovx, tan_fovy, H, W, degree, prefiltered, binning_capacity, fused_accumulate,
-                              depth_gradient, alpha);
+                              depth_gradient, alpha, absgrad);
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -583,6 +617,7 @@ std::vector<at::Tensor> rasterize_autograd(const at::Tensor& means3D, const at::
 // last_num_rendered(); the images carry no grad_fn.
 // grad_depth (optional, [1,H,W]): dL/ddepth as well -- the backward, always given this forward's own depth image, is then the
 // depth-mode one; as the explicit opt-in it does not read config.set_depth_gradient.
+// absgrad: the absgrad-mode backward; dL_dmean2D_abs [P,3] is returned as a fifth tensor (the caller attaches it to means2D).
 // ------------------------------------------------------------------------------------------------------------------
 std::vector<at::Tensor> rasterize_view_step(const at::Tensor& means3D, const at::Tensor& means2D, const at::Tensor& sh,
                                             const at::Tensor& colors, const at::Tensor& opacities, const at::Tensor& scales,
@@ -590,7 +625,7 @@ std::vector<at::Tensor> rasterize_view_step(const at::Tensor& means3D, const at:
                                             const at::Tensor& viewmatrix, const at::Tensor& projmatrix, const at::Tensor& campos,
                                             double scale_modifier, double tan_fovx, double tan_fovy, int64_t H, int64_t W,
                                             int64_t degree, bool prefiltered, int64_t binning_capacity, const at::Tensor& grad_color,
-                                            const OptT& grad_depth)
+                                            const OptT& grad_depth, bool absgrad)
 {
     require_device(means3D, "means3D");
     const c10::Device dev = means3D.device();
@@ -611,13 +646,18 @@ std::vector<at::Tensor> rasterize_view_step(const at::Tensor& means3D, const at:
     FwdResult r = rasterize_gaussians(bg, means3D, colors, opacities, scales, rotations, scale_modifier, cov3D, viewmatrix,
                                       projmatrix, tan_fovx, tan_fovy, H, W, sh, degree, campos, prefiltered, false, binning_capacity);
     g_last_num_rendered = std::get<0>(r);
+    at::Tensor abs2d;
     if (means3D.size(0) != 0) {
         FusedBackwardScope fused_scope(true);
-        (void)rasterize_gaussians_backward(bg, means3D, std::get<3>(r), colors, scales, rotations, scale_modifier, cov3D, viewmatrix,
-                                           projmatrix, tan_fovx, tan_fovy, grad_color, grad_depth, sh, degree, campos,
-                                           std::get<4>(r), std::get<0>(r), std::get<5>(r), std::get<6>(r), false,
-                                           binning_capacity, acc, true, std::get<2>(r), OptT());
+        const std::vector<OptT> g = rasterize_gaussians_backward(
+            bg, means3D, std::get<3>(r), colors, scales, rotations, scale_modifier, cov3D, viewmatrix, projmatrix, tan_fovx, tan_fovy,
+            grad_color, grad_depth, sh, degree, campos, std::get<4>(r), std::get<0>(r), std::get<5>(r), std::get<6>(r), false,
+            binning_capacity, acc, true, std::get<2>(r), OptT(), absgrad);
+        if (absgrad) abs2d = *g[8];
+    } else if (absgrad) {
+        abs2d = at::zeros({0, 3}, at::TensorOptions().dtype(at::kFloat).device(dev));
     }
+    if (absgrad) return { std::get<1>(r), std::get<3>(r), std::get<2>(r), std::get<4>(r), abs2d };
     return { std::get<1>(r), std::get<3>(r), std::get<2>(r), std::get<4>(r) };
 }
 
@@ -685,7 +725,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
           py::arg("dL_dout_color"), py::arg("dL_dout_depth"), py::arg("sh"), py::arg("degree"), py::arg("campos"),
           py::arg("geomBuffer"), py::arg("R"), py::arg("binningBuffer"), py::arg("imageBuffer"), py::arg("debug"),
           py::arg("binning_capacity"), py::arg("accumulate"), py::arg("skip_unused"), py::kw_only(),
-          py::arg("depth_image") = py::none(), py::arg("dL_dout_alpha") = py::none());
+          py::arg("depth_image") = py::none(), py::arg("dL_dout_alpha") = py::none(), py::arg("absgrad") = false);
     m.def("rasterize_gaussians_raw", &rasterize_gaussians_raw);
     m.def("rasterize_gaussians_raw_backward", &rasterize_gaussians_raw_backward, py::arg("background"), py::arg("xyz"),
           py::arg("radii"), py::arg("features_dc"), py::arg("features_rest"), py::arg("opacity_raw"), py::arg("scaling_raw"),
@@ -693,12 +733,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
           py::arg("tan_fovy"), py::arg("dL_dout_color"), py::arg("degree"), py::arg("campos"), py::arg("geomBuffer"), py::arg("R"),
           py::arg("binningBuffer"), py::arg("imageBuffer"), py::arg("debug"), py::arg("binning_capacity"), py::arg("accumulate"),
           py::arg("no_zero_fill"), py::kw_only(), py::arg("dL_dout_depth") = py::none(), py::arg("depth_image") = py::none(),
-          py::arg("dL_dout_alpha") = py::none());
+          py::arg("dL_dout_alpha") = py::none(), py::arg("absgrad") = false);
     m.def("rasterize_autograd", &rasterize_autograd, py::arg("means3D"), py::arg("means2D"), py::arg("sh"), py::arg("colors"),
           py::arg("opacities"), py::arg("scales"), py::arg("rotations"), py::arg("cov3D"), py::arg("bg"), py::arg("viewmatrix"),
           py::arg("projmatrix"), py::arg("campos"), py::arg("scale_modifier"), py::arg("tan_fovx"), py::arg("tan_fovy"), py::arg("H"),
           py::arg("W"), py::arg("degree"), py::arg("prefiltered"), py::arg("binning_capacity"), py::arg("fused_accumulate"),
-          py::arg("depth_gradient"), py::arg("alpha") = false);
+          py::arg("depth_gradient"), py::arg("alpha") = false, py::arg("absgrad") = false);
     m.def("render_alpha", &render_alpha);
     m.def("last_num_rendered", [] { return g_last_num_rendered; });
     m.def("mark_visible", &mark_visible);
@@ -706,7 +746,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
           py::arg("opacities"), py::arg("scales"), py::arg("rotations"), py::arg("cov3D"), py::arg("bg"), py::arg("viewmatrix"),
           py::arg("projmatrix"), py::arg("campos"), py::arg("scale_modifier"), py::arg("tan_fovx"), py::arg("tan_fovy"), py::arg("H"),
           py::arg("W"), py::arg("degree"), py::arg("prefiltered"), py::arg("binning_capacity"), py::arg("grad_color"),
-          py::arg("grad_depth") = py::none());
+          py::arg("grad_depth") = py::none(), py::arg("absgrad") = false);
     m.def("adam_step_masked", &adam_step_masked);
     m.def("check", &check);
     m.def("header_post", &header_post);

@@ -29,6 +29,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
+from . import config
 
 GROUP_ATTR = {"xyz": "_xyz", "f_dc": "_features_dc", "f_rest": "_features_rest", "opacity": "_opacity",
               "scaling": "_scaling", "rotation": "_rotation"}
@@ -223,8 +224,16 @@ def _bind(model, st):
 def add_densification_stats(model, viewspace_point_tensor, radii):
     """The per-iteration bookkeeping of the training loop in one kernel (R/luciddreamer.py:310-311 +
     GaussianModel.add_densification_stats, gaussian_model.py:405-407): for Gaussians with radii > 0,
-    max_radii2D = max(max_radii2D, radii); xyz_gradient_accum += |viewspace grad[:, :2]|; denom += 1."""
+    max_radii2D = max(max_radii2D, radii); xyz_gradient_accum += |viewspace grad[:, :2]|; denom += 1.
+    With config.set_absgrad(True) the statistic is AbsGS's: the norm of viewspace_point_tensor.absgrad[:, :2] (the rasterizer's
+    backward attached it) takes the place of the norm of .grad[:, :2]; same kernel."""
     g = viewspace_point_tensor.grad
+    if config.absgrad():
+        g = getattr(viewspace_point_tensor, "absgrad", None)
+        if g is None:
+            raise RuntimeError("add_densification_stats: config.set_absgrad(True) is on but the viewspace tensor carries no "
+                               ".absgrad -- it is attached by the backward of a view rendered with the switch on (render / "
+                               "render_raw / GaussianRasterizer); the multi-view step does not produce it")
     P = int(radii.shape[0])
     ok = lambda t, n: t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n
     if g is None or not (ok(g, 3 * P) and ok(model.xyz_gradient_accum, P) and ok(model.denom, P) and ok(model.max_radii2D, P)) \

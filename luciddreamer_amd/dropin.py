@@ -32,6 +32,8 @@ import types
 
 import torch
 
+from . import config
+
 
 class _Handle:
     def __init__(self):
@@ -312,6 +314,12 @@ def install(gaussian_renderer=None, loss=None, gaussian_model=None, *, render=Tr
         def add_densification_stats(self, viewspace_point_tensor, update_filter):
             radii = getattr(update_filter, "_lr_radii", None)
             g = viewspace_point_tensor.grad
+            if config.absgrad():
+                # AbsGS (config.set_absgrad): the reference's own method knows only .grad -- never fall back to it silently
+                if radii is None:
+                    raise RuntimeError("luciddreamer_amd.install: config.set_absgrad(True) needs the replaced render (render=True): "
+                                       "the reference's add_densification_stats would use the signed gradient")
+                return dz.add_densification_stats(self, viewspace_point_tensor, radii)
             ok = lambda t: torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
             if radii is None or g is None or not (ok(g) and ok(self.xyz_gradient_accum) and ok(self.denom) and ok(self.max_radii2D)):
                 return add(self, viewspace_point_tensor, update_filter)

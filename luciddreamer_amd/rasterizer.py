@@ -7,6 +7,8 @@
 
 Beyond the reference: return_alpha=True (GaussianRasterizer.forward, rasterize_gaussians, rasterize_gaussians_raw) returns
 (color, radii, depth, alpha) -- alpha (1, H, W) = 1 - T_final, the accumulated opacity, differentiable (lr_backward_alpha).
+config.set_absgrad(True): the backward of a view attaches `means2D.absgrad` [P,3] (AbsGS; lr_backward_absgrad) to the means2D
+tensor the caller passed.
 
 Error behaviour mirrored: plain `Exception` for bad SH/colour or scale/rotation/covariance
 combinations (:192-196); with settings.debug the inputs of a failing call are dumped to
@@ -102,6 +104,7 @@ class _RasterizeGaussians(torch.autograd.Function):
                 rs.sh_degree, rs.campos, rs.prefiltered, rs.debug)
         capacity = config.capacity_for(means3D, rs)
         ctx.antialiasing = config.antialiasing()        # as this forward finds it: backward checks (config.set_antialiasing)
+        ctx.absgrad_to = means2D if config.absgrad() else None      # config.set_absgrad as it is at this forward
         try:
             (num_rendered, color, depth, radii, geom, binning, img), capacity = _forward(
                 means3D, rs, capacity, lambda cap: _C.rasterize_gaussians(*args, binning_capacity=cap))
@@ -145,10 +148,13 @@ class _RasterizeGaussians(torch.autograd.Function):
             accumulate_into = {name: _fusable_grad(t, means3D.device) for name, t in ctx.leaf_inputs.items()}
         try:
             # the binding picks the mode: depth mode needs the kept depth image (switch on at the forward) and grad_depth
-            (grad_means2D, grad_colors_precomp, grad_opacities, grad_means3D, grad_cov3Ds_precomp, grad_sh,
-             grad_scales, grad_rotations) = _C.rasterize_gaussians_backward(
+            g = _C.rasterize_gaussians_backward(
                 *args, binning_capacity=ctx.binning_capacity, accumulate_into=accumulate_into, skip_unused=True,
-                depth_image=ctx.depth_image, dL_dout_alpha=grad_alpha)
+                depth_image=ctx.depth_image, dL_dout_alpha=grad_alpha, absgrad=ctx.absgrad_to is not None)
+            (grad_means2D, grad_colors_precomp, grad_opacities, grad_means3D, grad_cov3Ds_precomp, grad_sh,
+             grad_scales, grad_rotations) = g[:8]
+            if ctx.absgrad_to is not None:              # gsplat's convention; replaced at every backward
+                ctx.absgrad_to.absgrad = g[8]
         except Exception:
             if rs.debug:
                 _snapshot(args, "snapshot_bw.dump")
@@ -173,6 +179,7 @@ def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales,
     capacity = config.capacity_for(means3D, rs)
     fused = config.fused_grad_accumulation()
     offered = config.offered_grad_output()
+    absgrad = config.absgrad()
     # (an alpha-requesting call never takes the direct route: its backward would not see a gradient of alpha)
     if offered is not None and fused and not return_alpha and not config.verifying(capacity):
         # the caller already holds dL/dcolor (parallel.ViewStreams.run_view): forward and backward in ONE call of the binding,
@@ -182,9 +189,11 @@ def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales,
         out = _C.rasterize_view_step(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, rs.bg,
                                      rs.viewmatrix, rs.projmatrix, rs.campos, rs.scale_modifier, rs.tanfovx, rs.tanfovy,
                                      rs.image_height, rs.image_width, rs.sh_degree, rs.prefiltered, capacity, offered,
-                                     config.offered_grad_depth())
+                                     config.offered_grad_depth(), absgrad)
         if out:
-            color, radii, depth, geom = out
+            color, radii, depth, geom = out[:4]
+            if absgrad:                                 # the backward has run: as the nodes do at theirs
+                means2D.absgrad = out[4]
             config.mark_grad_output_taken((color, depth))
             config.note_forward(means3D, rs, _C.last_num_rendered(), geom, capacity)
             return color, radii, depth
@@ -193,7 +202,7 @@ def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales,
         return _C.rasterize_autograd(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, rs.bg,
                                      rs.viewmatrix, rs.projmatrix, rs.campos, rs.scale_modifier, rs.tanfovx, rs.tanfovy,
                                      rs.image_height, rs.image_width, rs.sh_degree, rs.prefiltered, cap, fused,
-                                     config.depth_gradient(), bool(return_alpha))
+                                     config.depth_gradient(), bool(return_alpha), absgrad)
     out, _ = _forward(means3D, rs, capacity, run, node=True)
     if return_alpha:
         return out[0], out[1], out[2], out[4]
@@ -208,6 +217,7 @@ class _RasterizeGaussiansRaw(torch.autograd.Function):
     def forward(ctx, xyz, means2D, features_dc, features_rest, opacity, scaling, rotation, raster_settings, return_alpha=False):
         rs = raster_settings
         ctx.antialiasing = config.antialiasing()        # as _RasterizeGaussians
+        ctx.absgrad_to = means2D if config.absgrad() else None
 
         def run(cap):
             return _C.rasterize_gaussians_raw(
@@ -238,7 +248,8 @@ class _RasterizeGaussiansRaw(torch.autograd.Function):
         if grad_out_color is None:
             grad_out_color = torch.zeros((3, rs.image_height, rs.image_width), dtype=torch.float32, device=xyz.device)
         # what arrived, as _RasterizeGaussians.backward: the binding picks the depth / alpha mode from it
-        modes = dict(dL_dout_depth=grad_depth, depth_image=ctx.depth_image, dL_dout_alpha=grad_alpha)
+        modes = dict(dL_dout_depth=grad_depth, depth_image=ctx.depth_image, dL_dout_alpha=grad_alpha,
+                     absgrad=ctx.absgrad_to is not None)
         accumulate_into = None
         if ctx.leaf_inputs is not None:
             li = ctx.leaf_inputs
@@ -258,13 +269,17 @@ class _RasterizeGaussiansRaw(torch.autograd.Function):
                 rs.bg, xyz, radii, features_dc, features_rest, opacity, scaling, rotation, rs.scale_modifier, rs.viewmatrix,
                 rs.projmatrix, rs.tanfovx, rs.tanfovy, grad_out_color, rs.sh_degree, rs.campos, geom, ctx.num_rendered,
                 binning, img, False, binning_capacity=ctx.binning_capacity, no_zero_fill=True, **modes)
-            opt.apply_armed_step(geom, [xyz, features_dc, features_rest, opacity, scaling, rotation], list(g[1:]))
+            if ctx.absgrad_to is not None:              # written in full also here (zero-filled like means2D): not part of the step
+                ctx.absgrad_to.absgrad = g[7]
+            opt.apply_armed_step(geom, [xyz, features_dc, features_rest, opacity, scaling, rotation], list(g[1:7]))
             return None, g[0], None, None, None, None, None, None, None
         g = _C.rasterize_gaussians_raw_backward(
             rs.bg, xyz, radii, features_dc, features_rest, opacity, scaling, rotation, rs.scale_modifier, rs.viewmatrix,
             rs.projmatrix, rs.tanfovx, rs.tanfovy, grad_out_color, rs.sh_degree, rs.campos, geom, ctx.num_rendered,
             binning, img, rs.debug, binning_capacity=ctx.binning_capacity, accumulate_into=accumulate_into, **modes)
-        g_means2D, g_xyz, g_dc, g_rest, g_op, g_sc, g_rot = g
+        if ctx.absgrad_to is not None:
+            ctx.absgrad_to.absgrad = g[7]
+        g_means2D, g_xyz, g_dc, g_rest, g_op, g_sc, g_rot = g[:7]
         return g_xyz, g_means2D, g_dc, g_rest, g_op, g_sc, g_rot, None, None
 
 

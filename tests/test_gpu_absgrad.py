@@ -1,0 +1,271 @@
+"""Absolute view-space gradient on the GPU (config.set_absgrad -> lr_backward_absgrad / lr_backward_raw_absgrad) against the
+float64 per-pixel reference (tests/absgrad_ref.py) on the seeded cases of tests/absgrad_cases.py, through the binding (one C-ABI
+call each) and through the operators.
+
+Tolerance: the project's GRAD_RTOL (helpers.compare_grads: max|g - g_ref| <= 1e-4 max|g_ref|), the bar of the signed gradients
+-- a sum of non-negative terms has no cancellation, so nothing wider is needed.  Rows of Gaussians that touch a pixel the CPU
+oracle flags as threshold-fragile may be left out, at most 1 row in 50 of the visible rows; tests/test_absgrad_cpu.py checks
+that the committed seeds stay inside that cap on the oracle alone."""
+import numpy as np
+import pytest
+import torch
+
+from luciddreamer_amd import _C, config, gaussian_renderer as gr
+from tests import absgrad_cases as cases
+from tests import absgrad_ref as ref
+from tests import helpers as hp
+
+pytestmark = pytest.mark.gpu
+
+SIGNED = ("means2D", "opacity", "means3D", "sh", "scales", "rotations")
+EMPTY = torch.Tensor([])
+
+
+class _Modes:
+    """The process-wide switches a case needs, restored on exit."""
+
+    def __init__(self, case, absgrad=True, depth=False):
+        self.case, self.absgrad, self.depth = case, absgrad, depth
+
+    def __enter__(self):
+        config.set_absgrad(self.absgrad)
+        config.set_depth_gradient(self.depth)
+        config.set_strict_parity(self.case["strict"])
+        config.set_antialiasing(self.case["antialiasing"])
+
+    def __exit__(self, *exc):
+        config.set_absgrad(False)
+        config.set_depth_gradient(False)
+        config.set_strict_parity(False)
+        config.set_antialiasing(False)
+        return False
+
+
+def _view(case, dev):
+    cam = case["cam"].to(dev)
+    tfx, tfy = cases.tan_fov(case["cam"])
+    t = lambda x: None if x is None else x.to(dev)
+    return cam, tfx, tfy, t(case["g_color"]), t(case["g_depth"]), t(case["g_alpha"])
+
+
+def run_cabi(case, dev, raw=False):
+    """Forward + absgrad backward through the binding: {"abs": (P,3), signed gradients by helpers' names, "radii"} as numpy."""
+    cam, tfx, tfy, gc, gd, ga = _view(case, dev)
+    cloud = case["cloud"]
+    H, W = cam.image_height, cam.image_width
+    bg = case["bg"].to(dev)
+    n = lambda t: t.detach().cpu().numpy()
+    with _Modes(case):
+        if not raw:
+            c = {k: v.to(dev) for k, v in cloud.items()}
+            fwd = _C.rasterize_gaussians(bg, c["means3D"], EMPTY, c["opacities"], c["scales"], c["rotations"], 1.0, EMPTY,
+                                         cam.world_view_transform, cam.full_proj_transform, tfx, tfy, H, W, c["shs"], cases.DEGREE,
+                                         cam.camera_center, False, False)
+            R, _, depth, radii, geom, binning, img = fwd
+            g = _C.rasterize_gaussians_backward(bg, c["means3D"], radii, EMPTY, c["scales"], c["rotations"], 1.0, EMPTY,
+                                                cam.world_view_transform, cam.full_proj_transform, tfx, tfy, gc, gd, c["shs"],
+                                                cases.DEGREE, cam.camera_center, geom, R, binning, img, False,
+                                                depth_image=depth if gd is not None else None, dL_dout_alpha=ga, absgrad=True)
+            assert len(g) == 9
+            out = dict(zip(_C.GRAD_ORDER, g[:8]))
+            out = {k: n(out[k]) for k in SIGNED}
+            out["abs"] = n(g[8])
+        else:
+            pc = gr.GaussianCloud(cloud["means3D"].to(dev), cloud["scales"].to(dev), cloud["rotations"].to(dev),
+                                  cloud["opacities"].to(dev), cloud["shs"].to(dev), active_sh_degree=cases.DEGREE, requires_grad=False)
+            p = (pc._xyz, pc._features_dc, pc._features_rest, pc._opacity, pc._scaling, pc._rotation)
+            fwd = _C.rasterize_gaussians_raw(bg, *p, 1.0, cam.world_view_transform, cam.full_proj_transform, tfx, tfy, H, W,
+                                             cases.DEGREE, cam.camera_center, False)
+            R, _, depth, radii, geom, binning, img = fwd
+            g = _C.rasterize_gaussians_raw_backward(bg, p[0], radii, *p[1:], 1.0, cam.world_view_transform, cam.full_proj_transform,
+                                                    tfx, tfy, gc, cases.DEGREE, cam.camera_center, geom, R, binning, img, False,
+                                                    dL_dout_depth=gd, depth_image=depth if gd is not None else None,
+                                                    dL_dout_alpha=ga, absgrad=True)
+            assert len(g) == 8
+            out = dict(means2D=n(g[0]), means3D=n(g[1]), abs=n(g[7]))
+        out["radii"] = n(radii)
+    return out
+
+
+def run_op(case, dev, debug=False, absgrad=True, backwards=1):
+    """Through GaussianRasterizer (debug: the Python node, else the compiled one): (means2D tensor, signed gradients)."""
+    from depth_diff_gaussian_rasterization_min import GaussianRasterizationSettings, GaussianRasterizer
+    cam, tfx, tfy, gc, gd, ga = _view(case, dev)
+    d = lambda t: t.detach().to(dev).requires_grad_(True)
+    cloud = case["cloud"]
+    leaves = dict(means3D=d(cloud["means3D"]), opacity=d(cloud["opacities"]), scales=d(cloud["scales"]),
+                  rotations=d(cloud["rotations"]), sh=d(cloud["shs"]))
+    leaves["means2D"] = torch.zeros_like(leaves["means3D"], requires_grad=True)
+    rs = GaussianRasterizationSettings(
+        image_height=cam.image_height, image_width=cam.image_width, tanfovx=tfx, tanfovy=tfy, bg=case["bg"].to(dev),
+        scale_modifier=1.0, viewmatrix=cam.world_view_transform, projmatrix=cam.full_proj_transform, sh_degree=cases.DEGREE,
+        campos=cam.camera_center, prefiltered=False, debug=debug)
+    with _Modes(case, absgrad=absgrad, depth=gd is not None):
+        config.set_async(False)
+        try:
+            out = GaussianRasterizer(rs)(means3D=leaves["means3D"], means2D=leaves["means2D"], opacities=leaves["opacity"],
+                                         shs=leaves["sh"], scales=leaves["scales"], rotations=leaves["rotations"],
+                                         return_alpha=ga is not None)
+            loss = (out[0] * gc).sum()
+            if gd is not None:
+                loss = loss + (out[2] * gd).sum()
+            if ga is not None:
+                loss = loss + (out[3] * ga).sum()
+            seen = []
+            for k in range(backwards):
+                loss.backward(retain_graph=k + 1 < backwards)
+                seen.append(getattr(leaves["means2D"], "absgrad", None))
+        finally:
+            config.set_async(True)
+    grads = {k: v.grad.detach().cpu().numpy() for k, v in leaves.items()}
+    return leaves["means2D"], grads, seen
+
+
+def check_abs(name, a):
+    """a: (P,3) from the GPU.  The bar of the module docstring; culled rows and column 2 exact zeros."""
+    r = ref.reference(name)
+    rows, visible = ref.fragile_rows(name)
+    assert len(rows) <= cases.FRAGILE_ROW_CAP * visible
+    a = np.asarray(a, dtype=np.float64)
+    assert a.shape == (r["radii"].shape[0], 3)
+    assert (a[:, 2] == 0).all()
+    assert (a[r["radii"] <= 0] == 0).all()
+    assert (a >= 0).all()
+    xy = a[:, :2].copy()
+    xy[list(rows)] = r["abs"][list(rows)]
+    fig = hp.compare_grads({"abs": xy}, {"abs": r["abs"]}, names=["abs"])
+    print(f"[absgrad] {name}: max|a - a_ref| = {fig['abs'][0]:.3e}, max|a_ref| = {fig['abs'][1]:.3e}, rows left out {len(rows)}")
+
+
+def check_signed(name, grads, names):
+    r = ref.reference(name)
+    rows = list(ref.fragile_rows(name)[0])
+    got = {}
+    for k in names:
+        g = np.asarray(grads[k], dtype=np.float64).reshape(r["grads"][k].shape).copy()
+        g[rows] = r["grads"][k][rows]
+        got[k] = g
+    hp.compare_grads(got, r["grads"], names=list(names))
+
+
+@pytest.mark.parametrize("name", cases.NAMES)
+def test_cabi_against_reference(hip_device, name):
+    case = cases.make(name)
+    out = run_cabi(case, hip_device)
+    assert np.array_equal(out["radii"] > 0, ref.reference(name)["radii"] > 0)
+    check_abs(name, out["abs"])
+    # the signed outputs of the same call; with anti-aliasing the prescaled reference covers means2D only (the coefficient's own
+    # chain to the other inputs is tests/test_gpu_aa.py's subject)
+    check_signed(name, out, ("means2D",) if case["antialiasing"] else SIGNED)
+    again = run_cabi(case, hip_device)
+    for k in ("abs",) + SIGNED:
+        assert np.array_equal(out[k], again[k]), k                    # bit-repeatable
+
+
+@pytest.mark.parametrize("name", cases.NAMES)
+def test_raw_entry_agrees(hip_device, name):
+    case = cases.make(name)
+    a, b = run_cabi(case, hip_device), run_cabi(case, hip_device, raw=True)
+    check_abs(name, b["abs"])
+    hp.compare_grads({"abs": b["abs"], "means2D": b["means2D"]}, {"abs": a["abs"], "means2D": a["means2D"]}, names=["abs", "means2D"])
+
+
+@pytest.mark.parametrize("name", cases.NAMES)
+def test_operator_nodes(hip_device, name):
+    case = cases.make(name)
+    m2c, gc_, _ = run_op(case, hip_device, debug=False)
+    m2p, gp_, _ = run_op(case, hip_device, debug=True)
+    check_abs(name, m2c.absgrad.cpu().numpy())
+    check_signed(name, gc_, ("means2D",) if case["antialiasing"] else SIGNED)
+    assert torch.equal(m2c.absgrad, m2p.absgrad)                      # the Python node and the compiled node: identical bits
+    for k in SIGNED:
+        assert np.array_equal(gc_[k], gp_[k]), k
+
+
+@pytest.mark.parametrize("debug", [False, True])
+def test_absgrad_attribute_lifecycle(hip_device, debug):
+    case = cases.make("partial")
+    m2, _, seen = run_op(case, hip_device, debug=debug, absgrad=False)
+    assert seen == [None] and not hasattr(m2, "absgrad")              # switch off: never set
+    m2, _, seen = run_op(case, hip_device, debug=debug, backwards=2)
+    assert seen[0] is not None and seen[1] is not None
+    assert seen[0] is not seen[1] and seen[0].data_ptr() != seen[1].data_ptr()     # replaced by the second backward ...
+    assert torch.equal(seen[0], seen[1])                              # ... by the same values: never accumulated
+    assert m2.absgrad is seen[1] and tuple(m2.absgrad.shape) == (m2.shape[0], 3)
+
+
+def test_view_step_route(hip_device):
+    """rasterize_view_step (forward + backward in one call of the binding) under the switch: the same bits as the node."""
+    case = cases.make("partial")
+    cam, tfx, tfy, gc, _, _ = _view(case, hip_device)
+    cloud = case["cloud"]
+    d = lambda t: t.detach().to(hip_device).requires_grad_(True)
+    t = [d(cloud["means3D"]), torch.zeros(cloud["means3D"].shape, device=hip_device, requires_grad=True), d(cloud["shs"]),
+         d(cloud["opacities"]), d(cloud["scales"]), d(cloud["rotations"])]
+    for x in t:
+        x.grad = torch.zeros_like(x)
+    out = _C.rasterize_view_step(t[0], t[1], t[2], EMPTY.to(hip_device), t[3], t[4], t[5], EMPTY.to(hip_device), case["bg"].to(hip_device),
+                                 cam.world_view_transform, cam.full_proj_transform, cam.camera_center, 1.0, tfx, tfy,
+                                 cam.image_height, cam.image_width, cases.DEGREE, False, 0, gc, None, True)
+    assert len(out) == 5
+    m2, _, _ = run_op(case, hip_device)
+    assert torch.equal(out[4], m2.absgrad)
+
+
+def _model(case, dev):
+    from tests.test_gpu_densify import Model
+    cloud = case["cloud"]
+    P = cloud["means3D"].shape[0]
+    pc = gr.GaussianCloud(cloud["means3D"], cloud["scales"], cloud["rotations"], cloud["opacities"], cloud["shs"],
+                          active_sh_degree=cases.DEGREE)
+    m = Model(P, dev, n_rest=cases.SH_COEFFS - 1, with_adam_state=False)
+    for a in ("_xyz", "_features_dc", "_features_rest", "_opacity", "_scaling", "_rotation"):
+        getattr(m, a).data.copy_(getattr(pc, a).data)
+    m.active_sh_degree = cases.DEGREE
+    m.xyz_gradient_accum = torch.zeros(P, 1, device=dev)
+    m.denom = torch.zeros(P, 1, device=dev)
+    m.max_radii2D = torch.zeros(P, device=dev)
+    return m
+
+
+def _train_view(case, m, dev, absgrad):
+    from luciddreamer_amd import densify
+    cam, _, _, gc, _, _ = _view(case, dev)
+    with _Modes(case, absgrad=absgrad):
+        out = gr.render_raw(cam, m, bg_color=case["bg"].to(dev))
+        (out["render"] * gc).sum().backward()
+        densify.add_densification_stats(m, out["viewspace_points"], out["radii"])
+    return out
+
+
+def test_densification_stats(hip_device):
+    name = "partial"
+    case, r = cases.make(name), ref.reference(name)
+    m = _model(case, hip_device)
+    out = _train_view(case, m, hip_device, True)
+    vis = r["radii"] > 0
+    want = np.where(vis, np.linalg.norm(r["abs"], axis=1), 0.0)
+    got = m.xyz_gradient_accum[:, 0].cpu().numpy().astype(np.float64)
+    rows = list(ref.fragile_rows(name)[0])
+    got[rows] = want[rows]
+    hp.compare_grads({"accum": got}, {"accum": want}, names=["accum"])
+    assert np.array_equal(m.denom[:, 0].cpu().numpy(), vis.astype(np.float32))          # as before
+    radii = out["radii"].cpu().numpy()
+    assert np.array_equal(m.max_radii2D.cpu().numpy(), np.maximum(radii, 0).astype(np.float32))
+    # and the switch off: the signed norm, from .grad
+    m0 = _model(case, hip_device)
+    _train_view(case, m0, hip_device, False)
+    want0 = np.where(vis, np.linalg.norm(r["grads"]["means2D"][:, :2], axis=1), 0.0)
+    hp.compare_grads({"accum": m0.xyz_gradient_accum[:, 0].cpu().numpy().astype(np.float64)}, {"accum": want0}, names=["accum"])
+
+
+@pytest.mark.parametrize("absgrad", [True, False])
+def test_densify_rule_on_the_cancellation_case(hip_device, absgrad):
+    """The reference's rule at the reference's threshold (densify_grad_threshold = 0.0002): a broad Gaussian whose per-pixel
+    pulls cancel is selected with the switch on and is not with it off."""
+    from luciddreamer_amd import densify
+    case = cases.make("cancel")
+    m = _model(case, hip_device)
+    _train_view(case, m, hip_device, absgrad)
+    densify.densify_and_prune(m, 0.0002, 0.005, 10.0, None)
+    assert m._xyz.shape[0] == (2 if absgrad else 1)
