@@ -127,7 +127,7 @@ int lr_forward(lr_alloc_fn geom_alloc, void* geom_user,
  * lr_check on the view's geom buffer and, with debug != 0, by lr_backward itself.  Larger values only cost idle workgroups;
  * R = LR_NUM_RENDERED_ON_DEVICE with capacity 0 ("unknown") selects kernels that are correct for any launch size.
  * dL_depths is accepted and ignored, exactly as the reference does
- * (RAST/cuda_rasterizer/backward.cu:457-464, 539-554 are commented out); lr_backward_depth below honours it.
+ * (RAST/cuda_rasterizer/backward.cu:457-464, 539-554 are commented out); lr_view_backward below honours it.
  * accumulate_mask: bit k set (LR_ACC_*) => that output is ACCUMULATED into (rows of visible Gaussians are
  * added to the existing contents, rows of culled Gaussians are not touched); bit clear => the output is
  * fully written (zero rows for culled Gaussians), no pre-fill needed.  0 reproduces the reference contract.
@@ -176,83 +176,78 @@ int lr_backward(int P, int D, int M, int R,
                 void* stream);
 
 /*
- * Raw-parameter fast path (no counterpart in the reference's native code).
- * The reference's Python caller materialises the activated parameters for every view before calling the
- * rasterizer -- exp(scaling), normalize(rotation), sigmoid(opacity) and torch.cat(features_dc, features_rest)
- * (R/scene/gaussian_model.py:97-117, R/gaussian_renderer/__init__.py:53-80): a 192 B/Gaussian copy plus four
- * elementwise kernels forward, and their autograd counterparts backward.  These two entry points take the STORED
- * GaussianModel tensors instead and apply the activations (forward) and their derivatives (backward) inside the
- * per-Gaussian kernels:
- *   xyz [P,3]; features_dc [P,1,3]; features_rest [P,M-1,3] (NULL iff M == 1); opacity_raw [P,1] (pre-sigmoid);
- *   scaling_raw [P,3] (pre-exp); rotation_raw [P,4] (pre-normalisation, torch.nn.functional.normalize eps 1e-12).
- * M = 1 + number of rest coefficients; D as in lr_forward.  colors_precomp / cov3D_precomp / prefiltered do not
- * exist in this mode.  Everything else (scratch buffers, binning_capacity, stream, return value, errors) is as in
- * lr_forward / lr_backward; the scratch buffers of a raw forward must be used with lr_backward_raw.
- * Gradients are with respect to the stored tensors: dL_dopacity_raw [P], dL_dxyz [P,3], dL_dfeatures_dc [P,3],
- * dL_dfeatures_rest [P,M-1,3], dL_dscaling_raw [P,3], dL_drotation_raw [P,4]; dL_dmean2D [P,3] as in lr_backward.
- * accumulate_mask uses the LR_ACC_* bits of the corresponding lr_backward outputs (LR_ACC_SH covers both feature
- * tensors).
+ * The per-view entries proper: lr_view_forward / lr_view_backward take one argument struct each.  lr_forward / lr_backward above
+ * are thin wrappers that fill these structs (activated parameters, no depth / alpha / absgrad mode); everything they document --
+ * exact and async mode, R / binning_capacity, accumulate_mask, the 16-byte alignment of the gradient outputs, which outputs may be
+ * NULL -- holds here.  No switch selects a mode: which pointers are non-NULL does.  (The positional lr_forward_raw and
+ * lr_backward_{raw,depth,alpha,absgrad}* entry points of library versions up to 0.6.1, two per mode, are gone.)
+ *
+ * lr_view: the scene and camera of one view, shared by its forward and its backward.
+ *   raw == 0: the ACTIVATED parameters, field for field the arguments of lr_forward; sh_rest must be NULL; `opacities` is read by
+ *     the forward only.
+ *   raw != 0: the raw-parameter fast path (no counterpart in the reference's native code).  The reference's
+ *     Python caller materialises the activated parameters for every view before calling the rasterizer -- exp(scaling),
+ *     normalize(rotation), sigmoid(opacity) and torch.cat(features_dc, features_rest) (R/scene/gaussian_model.py:97-117,
+ *     R/gaussian_renderer/__init__.py:53-80): a 192 B/Gaussian copy plus four elementwise kernels forward, and their autograd
+ *     counterparts backward.  In this mode the fields hold the STORED GaussianModel tensors and the per-Gaussian kernels apply the
+ *     activations (forward) and their derivatives (backward):
+ *       means3D = xyz [P,3]; shs = features_dc [P,1,3]; sh_rest = features_rest [P,M-1,3] (NULL iff M == 1);
+ *       opacities = opacity_raw [P,1] (pre-sigmoid; also read by the backward); scales = scaling_raw [P,3] (pre-exp);
+ *       rotations = rotation_raw [P,4] (pre-normalisation, torch.nn.functional.normalize eps 1e-12).
+ *     M = 1 + number of rest coefficients (>= 1); D as in lr_forward.  colors_precomp, cov3D_precomp and prefiltered do not exist
+ *     in this mode (LR_ERR_INVALID_ARG when given).  The scratch buffers of a raw forward must be used with a raw backward.
  */
-int lr_forward_raw(lr_alloc_fn geom_alloc, void* geom_user,
-                   lr_alloc_fn binning_alloc, void* binning_user,
-                   lr_alloc_fn img_alloc, void* img_user,
-                   int P, int D, int M,
-                   const float* background,
-                   int width, int height,
-                   const float* xyz,
-                   const float* features_dc,
-                   const float* features_rest,
-                   const float* opacity_raw,
-                   const float* scaling_raw,
-                   float scale_modifier,
-                   const float* rotation_raw,
-                   const float* viewmatrix,
-                   const float* projmatrix,
-                   const float* cam_pos,
-                   float tan_fovx, float tan_fovy,
-                   float* out_color,
-                   float* out_depth,
-                   int* radii,
-                   int debug,
-                   long long binning_capacity,
-                   void* stream);
+typedef struct lr_view {
+    /* sizes and the parameter representation (see above) */
+    int P, D, M;
+    int raw;
+    /* the image */
+    const float* background;
+    int width, height;
+    /* the scene: shs or colors_precomp; scales + rotations or cov3D_precomp */
+    const float* means3D;
+    const float* shs;
+    const float* sh_rest;
+    const float* colors_precomp;
+    const float* opacities;
+    const float* scales;
+    float scale_modifier;
+    const float* rotations;
+    const float* cov3D_precomp;
+    /* the camera */
+    const float* viewmatrix;
+    const float* projmatrix;
+    const float* campos;
+    float tan_fovx, tan_fovy;
+} lr_view;
 
-int lr_backward_raw(int P, int D, int M, int R,
-                    const float* background,
-                    int width, int height,
-                    const float* xyz,
-                    const float* features_dc,
-                    const float* features_rest,
-                    const float* opacity_raw,
-                    const float* scaling_raw,
-                    float scale_modifier,
-                    const float* rotation_raw,
-                    const float* viewmatrix,
-                    const float* projmatrix,
-                    const float* campos,
-                    float tan_fovx, float tan_fovy,
-                    const int* radii,
-                    char* geom_buffer,
-                    char* binning_buffer,
-                    char* image_buffer,
-                    const float* dL_dpix,
-                    float* dL_dmean2D,
-                    float* dL_dopacity_raw,
-                    float* dL_dxyz,
-                    float* dL_dfeatures_dc,
-                    float* dL_dfeatures_rest,
-                    float* dL_dscaling_raw,
-                    float* dL_drotation_raw,
-                    int debug,
-                    long long binning_capacity,
-                    unsigned int accumulate_mask,
-                    void* stream);
+typedef struct lr_forward_args {
+    size_t struct_bytes;                     /* = sizeof(lr_forward_args); anything else is LR_ERR_INVALID_ARG */
+    lr_view view;
+    /* scratch allocators, as in lr_forward */
+    lr_alloc_fn geom_alloc;    void* geom_user;
+    lr_alloc_fn binning_alloc; void* binning_user;
+    lr_alloc_fn img_alloc;     void* img_user;
+    int prefiltered;                         /* must be 0 in raw mode */
+    /* outputs, fully written: colour [3,H,W], depth [1,H,W], radii [P] */
+    float* out_color;
+    float* out_depth;
+    int* radii;
+    int debug;
+    long long binning_capacity;              /* 0: exact mode, > 0: async mode */
+    void* stream;
+} lr_forward_args;
 
 /*
- * Depth mode: lr_backward / lr_backward_raw with a gradient through the depth output.  Each takes its counterpart's
- * arguments plus the forward's depth image `depth_image` [1,H,W] (out_depth of the same view); lr_backward_raw_depth also
- * takes dL_depths, right after dL_dpix.  Here dL_depths [1,H,W] is HONOURED; with dL_depths == NULL the call is exactly
- * its counterpart (same kernels, same bits).  lr_backward / lr_backward_raw do not change and still ignore dL_depths.
+ * lr_backward_args.  The outputs are lr_backward's; in raw mode they are gradients with respect to the stored tensors:
+ * dL_dopacity = dL_dopacity_raw [P], dL_dmean3D = dL_dxyz [P,3], dL_dsh = dL_dfeatures_dc [P,3], dL_dsh_rest = dL_dfeatures_rest
+ * [P,M-1,3] (required iff M > 1; NULL in activated mode), dL_dscale = dL_dscaling_raw [P,3], dL_drot = dL_drotation_raw [P,4],
+ * dL_dmean2D [P,3] as in lr_backward; dL_dconic, dL_dcolor and dL_dcov3D are NULL.  accumulate_mask uses the LR_ACC_* bits of the
+ * lr_backward outputs (LR_ACC_SH covers both feature tensors).
+ *
+ * Depth mode iff dL_depths and depth_image are both given: dL_depths [1,H,W] is HONOURED, with `depth_image` [1,H,W] the forward's
+ * depth output (out_depth of the same view).  dL_depths without depth_image is LR_ERR_INVALID_ARG (lr_backward, the reference's
+ * mirror, passes neither and so ignores its dL_depths); depth_image alone changes nothing (same kernels, same bits).
  * The derivative is that of what the forward outputs, depth = D / acc where acc > 0.5 and 0 elsewhere, with
  * D = sum z_i w_i, acc = 1e-6 + sum w_i, w_i = alpha_i T_i and z_i the view-space depth of Gaussian i; for an upstream g
  * and a pixel with depth != 0 (gz = g / acc, ga = -g depth / acc; pixels whose depth is 0 contribute nothing):
@@ -264,172 +259,18 @@ int lr_backward_raw(int P, int D, int M, int R,
  * alpha < 1/255 and power > 0 skips, the sort order and the acc > 0.5 mask are constants; the fov clamp is treated as there.
  * acc is taken as 1e-6 + (1 - final T) (equal to the forward's float sum up to rounding).  The blend backward walks every
  * tile's whole list in this mode (no list segments); no global float atomics: the result is bit-repeatable.  An async view
- * that overflowed its binning buffer writes nothing, as in lr_backward.  accumulate_mask, errors and the return value are
- * those of the counterpart; dL_depths without depth_image is LR_ERR_INVALID_ARG.
- */
-int lr_backward_depth(int P, int D, int M, int R,
-                      const float* background,
-                      int width, int height,
-                      const float* means3D,
-                      const float* shs,
-                      const float* colors_precomp,
-                      const float* scales,
-                      float scale_modifier,
-                      const float* rotations,
-                      const float* cov3D_precomp,
-                      const float* viewmatrix,
-                      const float* projmatrix,
-                      const float* campos,
-                      float tan_fovx, float tan_fovy,
-                      const int* radii,
-                      char* geom_buffer,
-                      char* binning_buffer,
-                      char* image_buffer,
-                      const float* dL_dpix,
-                      const float* dL_depths,
-                      const float* depth_image,
-                      float* dL_dmean2D,
-                      float* dL_dconic,
-                      float* dL_dopacity,
-                      float* dL_dcolor,
-                      float* dL_dmean3D,
-                      float* dL_dcov3D,
-                      float* dL_dsh,
-                      float* dL_dscale,
-                      float* dL_drot,
-                      int debug,
-                      long long binning_capacity,
-                      unsigned int accumulate_mask,
-                      void* stream);
-
-int lr_backward_raw_depth(int P, int D, int M, int R,
-                          const float* background,
-                          int width, int height,
-                          const float* xyz,
-                          const float* features_dc,
-                          const float* features_rest,
-                          const float* opacity_raw,
-                          const float* scaling_raw,
-                          float scale_modifier,
-                          const float* rotation_raw,
-                          const float* viewmatrix,
-                          const float* projmatrix,
-                          const float* campos,
-                          float tan_fovx, float tan_fovy,
-                          const int* radii,
-                          char* geom_buffer,
-                          char* binning_buffer,
-                          char* image_buffer,
-                          const float* dL_dpix,
-                          const float* dL_depths,
-                          const float* depth_image,
-                          float* dL_dmean2D,
-                          float* dL_dopacity_raw,
-                          float* dL_dxyz,
-                          float* dL_dfeatures_dc,
-                          float* dL_dfeatures_rest,
-                          float* dL_dscaling_raw,
-                          float* dL_drotation_raw,
-                          int debug,
-                          long long binning_capacity,
-                          unsigned int accumulate_mask,
-                          void* stream);
-
-/*
- * Alpha output: the accumulated opacity alpha = 1 - T_final [1,H,W] of a forward, from its image buffer (the float32 T_final
- * the blend forward left there), written to out_alpha on `stream`.  0 where no Gaussian contributes.  Valid for lr_forward and
- * lr_forward_raw, exact and async mode: pass the image buffer of the forward whose colour you keep (after an overflow
- * re-render, the re-render's).  The forward's kernels are not changed by it.
- */
-int lr_render_alpha(const char* image_buffer, int width, int height, float* out_alpha, void* stream);
-
-/*
- * Alpha mode: lr_backward_depth / lr_backward_raw_depth with a gradient through the alpha output as well.  Each takes its
- * depth counterpart's arguments plus dL_dalpha [1,H,W] right after depth_image; the depth pair is optional (NULL, NULL: alpha
- * alone).  With dL_dalpha == NULL each is exactly its depth counterpart (same kernels, same bits).  These two are the general
- * per-view backward entries: the other four are these with NULLs.
- * The derivative is that of 1 - prod_i (1 - alpha_i) over the layers the forward applied, with the colour path's conventions
+ * that overflowed its binning buffer writes nothing, as in lr_backward.
+ *
+ * Alpha mode iff dL_dalpha [1,H,W] is given: the gradient through the alpha output (lr_render_alpha) as well, alone or with depth
+ * mode.  The derivative is that of 1 - prod_i (1 - alpha_i) over the layers the forward applied, with the colour path's conventions
  * (the 0.99 clamp of alpha not differentiated; the alpha < 1/255 and power > 0 skips, the T < 1e-4 stop -- whose trigger is not
  * applied -- and the sort order are constants; the fov clamp as there): d alpha_pix / d alpha_i = T_final / (1 - alpha_i).  It
  * reaches dL_dopacity, dL_dmean2D (which feeds densification), dL_dconic and through them means3D / xyz, scales, rotations and
  * cov3D; colours and SH get nothing from it.  Alone it runs the default backward's blend shape and list segments; with the depth
- * pair it joins the depth-mode kernel.  No global float atomics: bit-repeatable.  Errors and the return value are those of the
- * depth counterpart.
- */
-int lr_backward_alpha(int P, int D, int M, int R,
-                      const float* background,
-                      int width, int height,
-                      const float* means3D,
-                      const float* shs,
-                      const float* colors_precomp,
-                      const float* scales,
-                      float scale_modifier,
-                      const float* rotations,
-                      const float* cov3D_precomp,
-                      const float* viewmatrix,
-                      const float* projmatrix,
-                      const float* campos,
-                      float tan_fovx, float tan_fovy,
-                      const int* radii,
-                      char* geom_buffer,
-                      char* binning_buffer,
-                      char* image_buffer,
-                      const float* dL_dpix,
-                      const float* dL_depths,
-                      const float* depth_image,
-                      const float* dL_dalpha,
-                      float* dL_dmean2D,
-                      float* dL_dconic,
-                      float* dL_dopacity,
-                      float* dL_dcolor,
-                      float* dL_dmean3D,
-                      float* dL_dcov3D,
-                      float* dL_dsh,
-                      float* dL_dscale,
-                      float* dL_drot,
-                      int debug,
-                      long long binning_capacity,
-                      unsigned int accumulate_mask,
-                      void* stream);
-
-int lr_backward_raw_alpha(int P, int D, int M, int R,
-                          const float* background,
-                          int width, int height,
-                          const float* xyz,
-                          const float* features_dc,
-                          const float* features_rest,
-                          const float* opacity_raw,
-                          const float* scaling_raw,
-                          float scale_modifier,
-                          const float* rotation_raw,
-                          const float* viewmatrix,
-                          const float* projmatrix,
-                          const float* campos,
-                          float tan_fovx, float tan_fovy,
-                          const int* radii,
-                          char* geom_buffer,
-                          char* binning_buffer,
-                          char* image_buffer,
-                          const float* dL_dpix,
-                          const float* dL_depths,
-                          const float* depth_image,
-                          const float* dL_dalpha,
-                          float* dL_dmean2D,
-                          float* dL_dopacity_raw,
-                          float* dL_dxyz,
-                          float* dL_dfeatures_dc,
-                          float* dL_dfeatures_rest,
-                          float* dL_dscaling_raw,
-                          float* dL_drotation_raw,
-                          int debug,
-                          long long binning_capacity,
-                          unsigned int accumulate_mask,
-                          void* stream);
-
-/*
- * Absgrad mode (AbsGS; gsplat's `absgrad`): lr_backward_alpha / lr_backward_raw_alpha with one more output, dL_dmean2D_abs
- * [P,3] right after dL_dmean2D.  Each takes its alpha counterpart's arguments; dL_depths / depth_image and dL_dalpha stay
- * optional (NULL), dL_dmean2D_abs is required (LR_ERR_INVALID_ARG when NULL) and 16-byte aligned.
+ * pair it joins the depth-mode kernel.  No global float atomics: bit-repeatable.
+ *
+ * Absgrad mode (AbsGS; gsplat's `absgrad`) iff dL_dmean2D_abs [P,3] is given (16-byte aligned; NULL simply means the mode is off --
+ * the "dL_dmean2D_abs is required" check of the retired absgrad entries went with them).
  * Definition.  Let L be the scalar the call differentiates: sum dL_dpix . colour, plus the depth and alpha terms when their
  * gradients are given.  For pixel p and Gaussian i let g[p,i] in R^2 be the part of dL/dmeans2D_i[:2] that flows through pixel p,
  * in the NDC scale of dL_dmean2D (0.5 W, 0.5 H; backward.cu:473-474), so that sum_p g[p,i] = dL_dmean2D[i, :2].  Then
@@ -439,82 +280,55 @@ int lr_backward_raw_alpha(int P, int D, int M, int R,
  * dL_dmean2D_abs >= |dL_dmean2D| componentwise, with equality only where the per-pixel pulls do not cancel: a large Gaussian over
  * a blurry region has a near-zero signed gradient and a large absolute one, which is what a densification rule wants to see.
  * The tensor is always WRITTEN: zero-filled by the call (also under LR_ACC_NO_ZERO_FILL, like dL_dmean2D), never accumulated
- * (no bit of accumulate_mask refers to it), not part of the armed fused step.  Every other output is what the alpha counterpart
+ * (no bit of accumulate_mask refers to it), not part of the armed fused step.  Every other output is what the call without it
  * gives for the same arguments up to the rounding of another reduction order: the blend backward runs the 2-wave shape over
  * whole lists at every image size, as depth mode does.  No global float atomics: bit-repeatable.  lr_views_accumulate does not
- * produce it.  Errors and the return value are those of the alpha counterpart.
+ * produce it.
  */
-int lr_backward_absgrad(int P, int D, int M, int R,
-                        const float* background,
-                        int width, int height,
-                        const float* means3D,
-                        const float* shs,
-                        const float* colors_precomp,
-                        const float* scales,
-                        float scale_modifier,
-                        const float* rotations,
-                        const float* cov3D_precomp,
-                        const float* viewmatrix,
-                        const float* projmatrix,
-                        const float* campos,
-                        float tan_fovx, float tan_fovy,
-                        const int* radii,
-                        char* geom_buffer,
-                        char* binning_buffer,
-                        char* image_buffer,
-                        const float* dL_dpix,
-                        const float* dL_depths,
-                        const float* depth_image,
-                        const float* dL_dalpha,
-                        float* dL_dmean2D,
-                        float* dL_dmean2D_abs,
-                        float* dL_dconic,
-                        float* dL_dopacity,
-                        float* dL_dcolor,
-                        float* dL_dmean3D,
-                        float* dL_dcov3D,
-                        float* dL_dsh,
-                        float* dL_dscale,
-                        float* dL_drot,
-                        int debug,
-                        long long binning_capacity,
-                        unsigned int accumulate_mask,
-                        void* stream);
+typedef struct lr_backward_args {
+    size_t struct_bytes;                     /* = sizeof(lr_backward_args); anything else is LR_ERR_INVALID_ARG */
+    lr_view view;
+    /* what the view's forward returned / wrote: num_rendered, radii [P] and the three scratch buffers */
+    int R;
+    const int* radii;
+    char* geom_buffer;
+    char* binning_buffer;
+    char* image_buffer;
+    /* upstream gradients: dL_dpix [3,H,W] required; the others select depth and alpha mode (see above) */
+    const float* dL_dpix;
+    const float* dL_depths;
+    const float* depth_image;
+    const float* dL_dalpha;
+    /* gradient outputs (see above and lr_backward) */
+    float* dL_dmean2D;
+    float* dL_dmean2D_abs;
+    float* dL_dconic;
+    float* dL_dopacity;
+    float* dL_dcolor;
+    float* dL_dmean3D;
+    float* dL_dcov3D;
+    float* dL_dsh;
+    float* dL_dsh_rest;
+    float* dL_dscale;
+    float* dL_drot;
+    int debug;
+    long long binning_capacity;              /* the value the forward was given */
+    unsigned int accumulate_mask;
+    void* stream;
+} lr_backward_args;
 
-int lr_backward_raw_absgrad(int P, int D, int M, int R,
-                            const float* background,
-                            int width, int height,
-                            const float* xyz,
-                            const float* features_dc,
-                            const float* features_rest,
-                            const float* opacity_raw,
-                            const float* scaling_raw,
-                            float scale_modifier,
-                            const float* rotation_raw,
-                            const float* viewmatrix,
-                            const float* projmatrix,
-                            const float* campos,
-                            float tan_fovx, float tan_fovy,
-                            const int* radii,
-                            char* geom_buffer,
-                            char* binning_buffer,
-                            char* image_buffer,
-                            const float* dL_dpix,
-                            const float* dL_depths,
-                            const float* depth_image,
-                            const float* dL_dalpha,
-                            float* dL_dmean2D,
-                            float* dL_dmean2D_abs,
-                            float* dL_dopacity_raw,
-                            float* dL_dxyz,
-                            float* dL_dfeatures_dc,
-                            float* dL_dfeatures_rest,
-                            float* dL_dscaling_raw,
-                            float* dL_drotation_raw,
-                            int debug,
-                            long long binning_capacity,
-                            unsigned int accumulate_mask,
-                            void* stream);
+/* Return values and errors are lr_forward's / lr_backward's.  A NULL pointer or a struct_bytes other than the struct's size is
+ * LR_ERR_INVALID_ARG, checked before anything else. */
+int lr_view_forward(const lr_forward_args* a);
+int lr_view_backward(const lr_backward_args* a);
+
+/*
+ * Alpha output: the accumulated opacity alpha = 1 - T_final [1,H,W] of a forward, from its image buffer (the float32 T_final
+ * the blend forward left there), written to out_alpha on `stream`.  0 where no Gaussian contributes.  Valid for activated and
+ * raw forwards, exact and async mode: pass the image buffer of the forward whose colour you keep (after an overflow
+ * re-render, the re-render's).  The forward's kernels are not changed by it.
+ */
+int lr_render_alpha(const char* image_buffer, int width, int height, float* out_alpha, void* stream);
 
 /*
  * Multi-view step (new; the reference renders one view per Python iteration, luciddreamer.py:291-304).
@@ -531,8 +345,8 @@ int lr_backward_raw_absgrad(int P, int D, int M, int R,
  * LR_ERR_INVALID_ARG, as are depth_targets or masks without targets, and targets together with colors_precomp,
  * cov3D_precomp, acc_color or acc_cov3D.
  *   Fixed gradients: dL_dpix [3,H,W] per view, required.  dL_ddepth / dL_dalpha [H,W] per view, optional arrays: a view with
- *     a depth gradient runs the depth-mode backward of lr_backward_depth fed with its own depth image, one with an alpha
- *     gradient the alpha-mode backward of lr_backward_alpha (depth + alpha with both), in the blend shape the view would
+ *     a depth gradient runs the depth-mode backward of lr_view_backward fed with its own depth image, one with an alpha
+ *     gradient its alpha-mode backward (depth + alpha with both), in the blend shape the view would
  *     take without it; a NULL entry gives that view the backward without that term.
  *   Fused training step (render -> loss -> backward per view, on the view's stream: the per-iteration body of the training
  *     loop, R/luciddreamer.py:296-304; gradients of sum_v loss_v; SH colours and scale/rotation covariances only):
@@ -788,7 +602,7 @@ int lr_check(const char* geom_buffer, long long* num_rendered, void* stream);
  * out8) returns 1 and fills out8 once the copy has completed (the ticket is then released), 0 if it has not and
  * block == 0, a negative LR_ERR_* on a bad ticket.  The device current at lr_header_post must be the buffer's. */
 long long lr_header_post(const char* geom_buffer, void* stream);
-/* "Verify in the forward": lr_request_early_header() makes the next async-mode lr_forward / lr_forward_raw on the calling
+/* "Verify in the forward": lr_request_early_header() makes the next async-mode lr_forward / lr_view_forward on the calling
  * thread post such a ticket itself as soon as the view's counts are final -- after the compaction scan, with the binning and
  * blend kernels enqueued behind it -- and lr_take_early_ticket() hands it out (-1: none, e.g. exact mode or P == 0).  A caller
  * that polls it with block = 1 right after lr_forward returns waits only for the preprocess and scan kernels (the host has
@@ -799,17 +613,7 @@ void lr_request_early_header(void);
 long long lr_take_early_ticket(void);
 int lr_header_poll(long long ticket, int block, unsigned int* out8);
 
-/* Optional per-stage timing with HIP events recorded on the call's stream (bench.py roofline leg).
- * lr_profile_enable(1) clears and starts recording, (0) stops; returns the number of stages.
- * lr_profile_read waits for the recorded events and returns, per stage, the summed elapsed
- * milliseconds and the number of recorded calls.  Stage names: lr_profile_stage_name(i).
- * The stages "preprocess", "render_fwd", "render_bwd", "gauss_bwd" are exactly one kernel launch each. */
-/* Diagnostics: switch a kernel variant at run time (benchmark tooling measures two variants alternately in one process).
- * Knobs: "bwd_red" (reduction variant of the blend backward), "blend_quad", "tile_map", "preprocess", "gauss_bwd", "tsort",
- * "walk_own" (instances of a Gaussian the binning walks on its own lane), "hit_mask" (0: binning without preprocess's tile masks);
- * value -1 restores the library's own rule.  Results are identical up to float summation order whatever the setting.
- * Not part of the reference interface (it has no equivalent). */
-/* Ticket of the header of the LAST async-mode (binning_capacity > 0) lr_forward / lr_forward_raw on the calling thread, for
+/* Ticket of the header of the LAST async-mode (binning_capacity > 0) lr_forward / lr_view_forward on the calling thread, for
  * lr_header_poll -- or -1 (no such forward yet, exact mode, P == 0).  Costs nothing: async-mode forwards leave their header in
  * a ring of host-visible slots written by the scan kernel itself (no copy, no event; the poll spins on the slot's tag), which
  * is what a caller that keeps several views in flight checks its views with (luciddreamer_amd/config.py).  The slot of a
@@ -817,7 +621,7 @@ int lr_header_poll(long long ticket, int block, unsigned int* out8);
 long long lr_forward_ticket(void);
 /* A STEP of several views issued through the per-view entry points (what lr_views_accumulate is for callers that need the
  * rendered image between forward and backward).  Between lr_step_begin and lr_step_end on a device, every accumulate-mode
- * lr_backward / lr_backward_raw whose accumulate_mask covers mean2D, opacity, mean3D, scale and rotation (and that uses neither
+ * lr_backward / lr_view_backward whose accumulate_mask covers mean2D, opacity, mean3D, scale and rotation (and that uses neither
  * colors_precomp nor cov3D_precomp) adds those five rows into ONE interleaved 64-byte row per Gaussian owned by the library
  * instead of five scattered 12-16 byte read-modify-writes; lr_step_end(stream) adds the touched rows into the five tensors
  * the step's calls named (calls that name other tensors, or another P, accumulate directly as before).  The calls of a step
@@ -829,12 +633,17 @@ int lr_step_end(void* stream);
  * came).  The tensors named by its views may be gone by then; nothing is written through the remembered pointers. */
 int lr_step_abort(void);
 /* Accumulate-mode backward passes of different views on different streams add into the SAME gradient tensors and must not
- * overlap there.  `event` (a hipEvent_t, or NULL) is consumed by the next lr_backward / lr_backward_raw on the calling thread:
+ * overlap there.  `event` (a hipEvent_t, or NULL) is consumed by the next lr_backward / lr_view_backward on the calling thread:
  * its stream waits for the event after the blend backward (which writes only the call's own scratch) and before the kernels
  * that touch the outputs -- so a caller that records an event after each backward and passes it to the next one chains the
  * accumulations while the blend backward of one view still overlaps the per-Gaussian backward of the previous one
  * (csrc/torch_ext.cpp does this for the autograd operator; lr_views_accumulate does it internally). */
 void lr_backward_wait_event(void* event);
+/* Diagnostics: switch a kernel variant at run time (benchmark tooling measures two variants alternately in one process).
+ * Knobs: "bwd_red" (reduction variant of the blend backward), "blend_quad", "tile_map", "preprocess", "gauss_bwd", "tsort",
+ * "walk_own" (instances of a Gaussian the binning walks on its own lane), "hit_mask" (0: binning without preprocess's tile masks);
+ * value -1 restores the library's own rule.  Results are identical up to float summation order whatever the setting.
+ * Not part of the reference interface (it has no equivalent). */
 /* Test hook: force one of the SHIPPED code paths that the library otherwise picks by rule (value -1 = the rule again).
  * Results never depend on it beyond float rounding between kernel shapes; the parity suite runs every path through it.
  *   "strict" 1           the blend in the reference's own float operations (luciddreamer_amd.config.set_strict_parity)
@@ -859,7 +668,7 @@ int lr_tune_set(const char* name, int value);
  * coefficient's derivative with respect to the covariance to dL/dmeans3D, dL/dscales, dL/drotations or dL/dcov3D).
  * A PROCESS-WIDE setting (not per thread: an autograd engine runs backwards on threads other than the forward's), 0 = off by
  * default, and then no output differs by a bit from a library without it.  Unlike lr_tune_set it changes results.  Every entry
- * point reads it once when it starts: lr_forward[_raw], every lr_backward*, and every view of the lr_views_* family.
+ * point reads it once when it starts: lr_forward, lr_backward, lr_view_forward, lr_view_backward, and every view of the lr_views_* family.
  * CONTRACT: a view's backward must run under the setting its forward ran under -- the geom buffer holds the scaled opacity and
  * nothing records which kind it is; the gradients of a mixed pair are silently wrong.  (luciddreamer_amd's autograd functions
  * remember the forward's setting and raise instead.)  Do not toggle it while an lr_views_* call is running.
@@ -870,6 +679,11 @@ int lr_get_antialiasing(void);
  * candidate pairs, 2 one wave per tile; backward 0 two waves per tile, 1 four, 2 one; -1 = none yet.  For tests that must
  * know WHICH kernels a configuration ran (e.g. that the headline's step ran the one-wave-per-tile pair). */
 int lr_last_launch_shapes(int* forward_shape, int* backward_shape);
+/* Optional per-stage timing with HIP events recorded on the call's stream (bench.py roofline leg).
+ * lr_profile_enable(1) clears and starts recording, (0) stops; returns the number of stages.
+ * lr_profile_read waits for the recorded events and returns, per stage, the summed elapsed
+ * milliseconds and the number of recorded calls.  Stage names: lr_profile_stage_name(i).
+ * The stages "preprocess", "render_fwd", "render_bwd", "gauss_bwd" are exactly one kernel launch each. */
 int lr_profile_enable(int on);
 const char* lr_profile_stage_name(int stage);
 int lr_profile_read(double* ms_per_stage, long long* calls_per_stage, int n_stages);

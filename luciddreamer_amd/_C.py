@@ -13,7 +13,7 @@ There is no fallback: a missing extension raises on import.
 Beyond the reference's contract (all optional, keyword-only):
     binning_capacity : > 0 runs lr_forward in async mode (no host sync; see lucid_raster.h)
     dL_dout_alpha    : the gradient of the alpha output (render_alpha), on both backward entry points
-    absgrad          : absgrad mode (lr_backward_absgrad / lr_backward_raw_absgrad), on both backward entry points
+    absgrad          : absgrad mode (lr_view_backward with dL_dmean2D_abs), on both backward entry points
 """
 try:
     from . import _C_ext
@@ -57,8 +57,8 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
     depth_image (optional): the forward's depth output -- depth mode: dL_dout_depth is honoured.  Without it dL_dout_depth
     is ignored, as in the reference.
     dL_dout_alpha (optional, (1, H, W)): the gradient of the alpha output (render_alpha) as well, alone or together with depth
-    mode.  Every mode, the default included, is one call of lr_backward_alpha with NULL for what is absent.
-    absgrad: one call of lr_backward_absgrad instead; the result gains a ninth entry, dL_dmean2D_abs [P,3] (always a new tensor)."""
+    mode.  Every mode, the default included, is one call of lr_view_backward with NULL for what is absent.
+    absgrad: lr_view_backward with dL_dmean2D_abs as well; the result gains a ninth entry, dL_dmean2D_abs [P,3] (always a new tensor)."""
     acc = _NONE8 if not accumulate_into else [accumulate_into.get(k) for k in GRAD_ORDER]
     return tuple(_C_ext.rasterize_gaussians_backward(
         background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix, projmatrix,
@@ -69,7 +69,7 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
 def rasterize_gaussians_raw(background, xyz, features_dc, features_rest, opacity_raw, scaling_raw, rotation_raw,
                             scale_modifier, viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width,
                             degree, campos, debug, *, binning_capacity=0):
-    """Forward on the STORED GaussianModel tensors (lr_forward_raw): exp / normalize / sigmoid and
+    """Forward on the STORED GaussianModel tensors (lr_view_forward with raw = 1): exp / normalize / sigmoid and
     the features_dc|features_rest split are handled inside the kernels.  Returns the tuple of rasterize_gaussians."""
     if opacity_raw is None:
         raise RuntimeError("rasterize_gaussians_raw: raw mode needs features_dc, features_rest (M > 1), opacity, "
@@ -88,8 +88,8 @@ def rasterize_gaussians_raw_backward(background, xyz, radii, features_dc, featur
     accumulate_into: {"means2D","xyz","opacity","scaling","rotation": tensor, "features": (dc_grad, rest_grad)} adds
     in place (slot returned as None).
     dL_dout_depth + depth_image (the forward's depth output): depth mode.
-    dL_dout_alpha: the gradient of the alpha output as well.  Every mode is one call of lr_backward_raw_alpha.
-    absgrad: one call of lr_backward_raw_absgrad instead; the result gains an eighth entry, dL_dmean2D_abs [P,3]."""
+    dL_dout_alpha: the gradient of the alpha output as well.  Every mode is one call of lr_view_backward with raw = 1.
+    absgrad: dL_dmean2D_abs given as well; the result gains an eighth entry, dL_dmean2D_abs [P,3]."""
     acc = _NONE8
     if accumulate_into:
         f = accumulate_into.get("features") or (None, None)

@@ -27,8 +27,8 @@ _lib = None
 _lock = threading.Lock()
 
 EXPORTS = ("lr_last_error", "lr_version", "lr_geom_bytes", "lr_img_bytes", "lr_binning_bytes", "lr_forward",
-           "lr_backward", "lr_forward_raw", "lr_backward_raw", "lr_backward_depth", "lr_backward_raw_depth",
-           "lr_backward_alpha", "lr_backward_raw_alpha", "lr_backward_absgrad", "lr_backward_raw_absgrad", "lr_render_alpha", "lr_mark_visible", "lr_check", "lr_dist2_workspace_bytes", "lr_dist2",
+           "lr_backward", "lr_view_forward", "lr_view_backward", "lr_render_alpha", "lr_mark_visible", "lr_check",
+           "lr_dist2_workspace_bytes", "lr_dist2",
            "lr_dist2_workspace_layout",
            "lr_profile_enable", "lr_profile_stage_name", "lr_profile_read", "lr_tune_set", "lr_last_launch_shapes", "lr_request_early_header",
            "lr_take_early_ticket", "lr_forward_ticket", "lr_backward_wait_event", "lr_step_begin", "lr_step_end", "lr_step_abort",
@@ -71,6 +71,44 @@ class ViewsArgs(ctypes.Structure):
 
     def __init__(self, **fields):
         super().__init__(struct_bytes=ctypes.sizeof(ViewsArgs), **fields)
+
+
+class View(ctypes.Structure):
+    """lr_view: the scene and camera of one view (raw != 0: the stored GaussianModel tensors; see the header)."""
+    _vp, _ci, _cf = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
+    _fields_ = [("P", _ci), ("D", _ci), ("M", _ci), ("raw", _ci),
+                ("background", _vp), ("width", _ci), ("height", _ci),
+                ("means3D", _vp), ("shs", _vp), ("sh_rest", _vp), ("colors_precomp", _vp), ("opacities", _vp), ("scales", _vp),
+                ("scale_modifier", _cf), ("rotations", _vp), ("cov3D_precomp", _vp),
+                ("viewmatrix", _vp), ("projmatrix", _vp), ("campos", _vp), ("tan_fovx", _cf), ("tan_fovy", _cf)]
+
+
+class ForwardArgs(ctypes.Structure):
+    """lr_forward_args, field for field (tests/test_view_args_cpu.py compares the offsets with the host compiler's)."""
+    _vp, _ci = ctypes.c_void_p, ctypes.c_int
+    _fields_ = [("struct_bytes", ctypes.c_size_t), ("view", View),
+                ("geom_alloc", ALLOC_FN), ("geom_user", _vp), ("binning_alloc", ALLOC_FN), ("binning_user", _vp),
+                ("img_alloc", ALLOC_FN), ("img_user", _vp), ("prefiltered", _ci),
+                ("out_color", _vp), ("out_depth", _vp), ("radii", _vp),
+                ("debug", _ci), ("binning_capacity", ctypes.c_longlong), ("stream", _vp)]
+
+    def __init__(self, **fields):
+        super().__init__(struct_bytes=ctypes.sizeof(ForwardArgs), **fields)
+
+
+class BackwardArgs(ctypes.Structure):
+    """lr_backward_args, field for field.  Which optional pointers are given selects the depth / alpha / absgrad mode."""
+    _vp, _ci = ctypes.c_void_p, ctypes.c_int
+    _fields_ = [("struct_bytes", ctypes.c_size_t), ("view", View),
+                ("R", _ci), ("radii", _vp), ("geom_buffer", _vp), ("binning_buffer", _vp), ("image_buffer", _vp),
+                ("dL_dpix", _vp), ("dL_depths", _vp), ("depth_image", _vp), ("dL_dalpha", _vp),
+                ("dL_dmean2D", _vp), ("dL_dmean2D_abs", _vp), ("dL_dconic", _vp), ("dL_dopacity", _vp), ("dL_dcolor", _vp),
+                ("dL_dmean3D", _vp), ("dL_dcov3D", _vp), ("dL_dsh", _vp), ("dL_dsh_rest", _vp), ("dL_dscale", _vp),
+                ("dL_drot", _vp),
+                ("debug", _ci), ("binning_capacity", ctypes.c_longlong), ("accumulate_mask", ctypes.c_uint), ("stream", _vp)]
+
+    def __init__(self, **fields):
+        super().__init__(struct_bytes=ctypes.sizeof(BackwardArgs), **fields)
 
 
 def assert_single_copy():
@@ -127,35 +165,10 @@ def lib():
                                   vp, vp, vp, vp, vp,                            # geom binning img dL_dpix dL_ddepth
                                   vp, vp, vp, vp, vp, vp, vp, vp, vp,            # 9 gradient outputs
                                   ci, ll, ctypes.c_uint, vp]                     # debug capacity accumulate_mask stream
-        L.lr_forward_raw.restype = ci
-        L.lr_forward_raw.argtypes = [ALLOC_FN, vp, ALLOC_FN, vp, ALLOC_FN, vp,  # allocators
-                                     ci, ci, ci, vp, ci, ci,                     # P D M bg W H
-                                     vp, vp, vp, vp, vp, cf, vp,                 # xyz f_dc f_rest opacity scaling mod rotation
-                                     vp, vp, vp, cf, cf,                         # view proj campos tanx tany
-                                     vp, vp, vp, ci, ll, vp]                     # out_color out_depth radii debug capacity stream
-        L.lr_backward_raw.restype = ci
-        L.lr_backward_raw.argtypes = [ci, ci, ci, ci, vp, ci, ci,                # P D M R bg W H
-                                      vp, vp, vp, vp, vp, cf, vp,                # xyz f_dc f_rest opacity scaling mod rotation
-                                      vp, vp, vp, cf, cf, vp,                    # view proj campos tanx tany radii
-                                      vp, vp, vp, vp,                            # geom binning img dL_dpix
-                                      vp, vp, vp, vp, vp, vp, vp,                # 7 gradient outputs
-                                      ci, ll, ctypes.c_uint, vp]                 # debug capacity accumulate_mask stream
-        L.lr_backward_absgrad.restype = ci
-        L.lr_backward_absgrad.argtypes = [ci, ci, ci, ci, vp, ci, ci,            # P D M R bg W H
-                                          vp, vp, vp, vp, cf, vp, vp,            # means3D shs colors scales mod rot cov3D
-                                          vp, vp, vp, cf, cf, vp,                # view proj campos tanx tany radii
-                                          vp, vp, vp, vp, vp, vp, vp,            # geom binning img dL_dpix dL_ddepth depth_image dL_dalpha
-                                          vp, vp,                                # dL_dmean2D dL_dmean2D_abs
-                                          vp, vp, vp, vp, vp, vp, vp, vp,        # the other 8 gradient outputs
-                                          ci, ll, ctypes.c_uint, vp]             # debug capacity accumulate_mask stream
-        L.lr_backward_raw_absgrad.restype = ci
-        L.lr_backward_raw_absgrad.argtypes = [ci, ci, ci, ci, vp, ci, ci,        # P D M R bg W H
-                                              vp, vp, vp, vp, vp, cf, vp,        # xyz f_dc f_rest opacity scaling mod rotation
-                                              vp, vp, vp, cf, cf, vp,            # view proj campos tanx tany radii
-                                              vp, vp, vp, vp, vp, vp, vp,        # geom binning img dL_dpix dL_ddepth depth_image dL_dalpha
-                                              vp, vp,                            # dL_dmean2D dL_dmean2D_abs
-                                              vp, vp, vp, vp, vp, vp,            # the other 6 gradient outputs
-                                              ci, ll, ctypes.c_uint, vp]         # debug capacity accumulate_mask stream
+        L.lr_view_forward.restype = ci
+        L.lr_view_forward.argtypes = [ctypes.POINTER(ForwardArgs)]
+        L.lr_view_backward.restype = ci
+        L.lr_view_backward.argtypes = [ctypes.POINTER(BackwardArgs)]
         L.lr_render_alpha.restype = ci
         L.lr_render_alpha.argtypes = [vp, ci, ci, vp, vp]                        # image_buffer W H out_alpha stream
         L.lr_mark_visible.restype = ci

@@ -151,7 +151,7 @@ def set_depth_gradient(enabled: bool):
     """Differentiable depth output (off by default; process-wide).  The reference's backward drops the gradient of its depth
     output (a loss on `depth` gives exactly zero parameter gradient), and so does this rasterizer unless this switch is on.
     When it is on at a FORWARD, that forward keeps its depth image on the autograd node, and a backward that then receives a
-    gradient for `depth` runs the depth-mode kernels (lr_backward_depth / lr_backward_raw_depth): the true derivative of the
+    gradient for `depth` runs the depth-mode kernels (lr_view_backward with dL_depths and depth_image): the true derivative of the
     forward's depth = D / acc (0 where acc <= 0.5), reaching means3D directly and means2D, conics, opacities, scales and
     rotations through alpha -- means2D.grad, which feeds densification, included.  A backward without a depth gradient is
     today's, same kernels and bits.  Read at forward time and recorded on the node: flipping it between a forward and its
@@ -169,7 +169,7 @@ def set_absgrad(enabled: bool):
     quantity densification goes by, the norm of dL/dmeans2D[:, :2], is a signed sum over the pixels a Gaussian covers: a large
     Gaussian over a blurry region is pulled in opposite directions by the pixels on its two sides, the pulls cancel, and it is
     never split.  When the switch is on at a FORWARD of either operator (render / render_raw, GaussianRasterizer, the drop-in),
-    that view's backward runs the absgrad kernels (lr_backward_absgrad / lr_backward_raw_absgrad) and attaches
+    that view's backward runs the absgrad kernels (lr_view_backward with dL_dmean2D_abs) and attaches
     `means2D.absgrad` [P,3] to the means2D tensor the caller passed: per Gaussian (sum_p |g_p.x|, sum_p |g_p.y|, 0) over the
     per-pixel shares g_p of dL/dmeans2D -- replaced at every backward, never accumulated; with the switch off the attribute is
     never set.  densify.add_densification_stats then feeds that tensor instead of .grad to the unchanged statistics kernel.

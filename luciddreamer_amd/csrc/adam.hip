@@ -79,7 +79,7 @@ k_adam(AdamTensors T, float w1, float beta2, float w2, float bc2_sqrt, float eps
 
 // The same step where a Gaussian's gradient rows are only VALID if the view visited it (launch_adam_masked): element e of tensor
 // t belongs to Gaussian e / row_len[t]; tiles_touched == 0 -> gradient zero, the gradient array is not read (the backward left
-// those rows unwritten: no zero-fill pass, no read of zeros -- lr_backward_raw with LR_ACC_NO_ZERO_FILL).  RL: the row length as
+// those rows unwritten: no zero-fill pass, no read of zeros -- lr_view_backward with raw = 1 with LR_ACC_NO_ZERO_FILL).  RL: the row length as
 // a compile-time constant (1, 3, 4, 45 = the GaussianModel tensors at SH degree 3; 0 = the run-time value): element -> Gaussian
 // is a division per float4 group, and by a run-time divisor it costs more than the group's memory traffic.
 struct AdamMasked { AdamTensors T; unsigned int row_len[ADAM_MAX_TENSORS]; };

@@ -26,7 +26,7 @@ static_assert(sizeof(GaussRec) == 48, "GaussRec must be 48 bytes");
 struct __attribute__((aligned(16))) GradRec {
     float dmx, dmy, dca, dcb;       // dL/dmean2D.xy (NDC-scaled), dL/dconic a, b
     float dcc, dop, dr, dg;         // dL/dconic c, dL/dopacity, dL/dcolour r, g
-    float db, pad0, pad1, pad2;     // pad0: dL/d(view depth) in depth mode (lr_backward_depth), else 0
+    float db, pad0, pad1, pad2;     // pad0: dL/d(view depth) in depth mode (lr_view_backward with dL_depths and depth_image), else 0
 };
 static_assert(sizeof(GradRec) == 48, "GradRec must be 48 bytes");
 
@@ -355,7 +355,7 @@ struct ViewParams {
     float tan_fovx, tan_fovy, focal_x, focal_y, scale_modifier;
     int W, H, gx, gy, P, D, M;
     int hit_origin_limit;         // HIT_ORIGIN_LIMIT; 0 (lr_tune_set("hit_mask", 0), tests) = no masks: every rectangle walked from its record
-    // raw-parameter mode (lr_forward_raw / lr_backward_raw): scales, rotations and opacities are the STORED
+    // raw-parameter mode (lr_view_forward / lr_view_backward with raw = 1): scales, rotations and opacities are the STORED
     // GaussianModel parameters (pre exp / normalize / sigmoid, R/scene/gaussian_model.py:97-117) and the SH
     // coefficients come as two arrays, `shs` = features_dc [P,1,3] and `sh_rest` = features_rest [P,M-1,3]
     // (no torch.cat copy).  The activations and their derivatives are applied inside the per-Gaussian kernels.
@@ -463,9 +463,9 @@ void launch_render_fwd(int W, int H, int gx, int gy, const uint2* ranges, const 
 // alpha [n] = 1 - final_T [n]: the accumulated opacity of the forward that left final_T (lr_render_alpha)
 void launch_render_alpha(const float* final_T, long long n, float* alpha, hipStream_t s);
 // seg_bound: upper bound of GeomHeader::n_seg known to the host (bin_seg_capacity of the instance bound of the call)
-// dL_ddepth != nullptr: depth mode (lr_backward_depth) -- the depth-mode kernels differentiate the forward's depth image
+// dL_ddepth != nullptr: depth mode (lr_view_backward with dL_depths and depth_image) -- the depth-mode kernels differentiate the forward's depth image
 // depth_img [H*W] for the upstream gradient dL_ddepth [H*W] as well, and write dL/dz of every instance to its slot's free float
-// dL_dalpha != nullptr: alpha mode (lr_backward_alpha) -- the gradient of the accumulated opacity 1 - final_T [H*W] as well;
+// dL_dalpha != nullptr: alpha mode (lr_view_backward with dL_dalpha) -- the gradient of the accumulated opacity 1 - final_T [H*W] as well;
 // alone it keeps the default shape and segments, with depth mode it joins the depth-mode kernel
 void launch_render_bwd(int W, int H, int gx, int gy, const uint2* ranges, const uint32_t* point_list,
                        const GaussRec* rec, const float* bg, const float* final_T,
@@ -473,7 +473,7 @@ void launch_render_bwd(int W, int H, int gx, int gy, const uint2* ranges, const 
                        const uint32_t* tile_seg0, const float4* c_final, long long seg_bound, hipStream_t s,
                        const float* dL_ddepth = nullptr, const float* depth_img = nullptr, const float* dL_dalpha = nullptr,
                        bool absgrad = false);
-// absgrad: absgrad mode (lr_backward_absgrad) -- the k_render_bwd_abs kernels (2-wave shape, whole lists, with the depth / alpha
+// absgrad: absgrad mode (lr_view_backward with dL_dmean2D_abs) -- the k_render_bwd_abs kernels (2-wave shape, whole lists, with the depth / alpha
 // terms the pointers ask for), which also leave each instance's sums of |per-pixel dL/dmean2D| in its slot's last two floats
 // ---- Adam, element-wise (adam.hip and the step fused into the per-Gaussian backward, gauss_bwd.hip) -----------------------
 // torch's single-tensor Adam (torch/optim/adam.py _single_tensor_adam; no weight decay, amsgrad or maximize) with the roundings
@@ -520,7 +520,7 @@ void launch_densify_stats(int P, const int* radii, const float* dL_dmean2D, floa
 int launch_adam(int n_tensors, float* const* params, const float* const* grads, float* const* exp_avg,
                 float* const* exp_avg_sq, const unsigned long long* numel, const double* lr, double beta1, double beta2,
                 double eps, int step, hipStream_t s);
-// ... where the gradient of a Gaussian's rows is only VALID if the view visited it (tiles_touched != 0: lr_backward_raw with
+// ... where the gradient of a Gaussian's rows is only VALID if the view visited it (tiles_touched != 0: lr_view_backward with raw = 1 with
 // LR_ACC_NO_ZERO_FILL left the other rows unwritten) and is taken as zero otherwise -- or for every row, when the view
 // overflowed its binning buffer and the backward skipped it.  row_len[t]: floats per Gaussian of tensor t.
 int launch_adam_masked(int n_tensors, float* const* params, const float* const* grads, float* const* exp_avg,

@@ -114,7 +114,7 @@ __device__ __forceinline__ float row_sum(float v)
 
 // Backward of ONE visible Gaussian, everything except the spherical-harmonics rows (those are handled 16 lanes per
 // Gaussian by the caller, which passes the resulting dL/d(view direction) in `dL_ddir` when `have_sh`).
-// RAW (lr_backward_raw) is a template parameter, not a run-time branch: with `if (vp.raw)` blocks in this function
+// RAW (lr_view_backward with raw = 1) is a template parameter, not a run-time branch: with `if (vp.raw)` blocks in this function
 // ROCm 7.2 hipcc produced wrong dL/dcov3D in the NON-raw path (verified on hardware by removing either block).
 // DEPTH (k_gauss_bwd_depth): g2.y is the Gaussian's dL/d(view depth) from the depth-mode blend backward; it reaches the mean
 // through z = view[2] x + view[6] y + view[10] z + view[14] (column-major view matrix, auxiliary.h:58-66) -- in the raw path
@@ -396,7 +396,7 @@ k_gauss_bwd(LR_GB_PARAMS)
     constexpr float* dL_dmean2D_abs = nullptr;
 #include "gauss_bwd_body.h"
 }
-// depth mode (lr_backward_depth / lr_backward_raw_depth): its own entry point, so that k_gauss_bwd keeps its instruction stream
+// depth mode (lr_view_backward with dL_depths and depth_image): its own entry point, so that k_gauss_bwd keeps its instruction stream
 template <bool RAW, bool AA>
 __global__ void __launch_bounds__(GB_THREADS) __attribute__((amdgpu_waves_per_eu(LR_GB_WAVES, 8)))
 k_gauss_bwd_depth(LR_GB_PARAMS)
@@ -405,7 +405,7 @@ k_gauss_bwd_depth(LR_GB_PARAMS)
     constexpr float* dL_dmean2D_abs = nullptr;
 #include "gauss_bwd_body.h"
 }
-// absgrad mode (lr_backward_absgrad / lr_backward_raw_absgrad), with or without the depth term: own entry points again
+// absgrad mode (lr_view_backward with dL_dmean2D_abs), with or without the depth term: own entry points again
 template <bool RAW, bool AA, bool DEPTH>
 __global__ void __launch_bounds__(GB_THREADS) __attribute__((amdgpu_waves_per_eu(LR_GB_WAVES, 8)))
 k_gauss_bwd_abs(LR_GB_PARAMS, float* __restrict__ dL_dmean2D_abs)

@@ -139,7 +139,7 @@ __device__ __forceinline__ void tile_rect(float px, float py, int radius, int gx
     maxy = min(gy, max(0, (int)((py + radius + TILE_Y - 1) / TILE_Y)));
 }
 
-// RAW (lr_forward_raw) is a template parameter so that the standard path keeps its register budget (100 VGPRs,
+// RAW (lr_view_forward with raw = 1) is a template parameter so that the standard path keeps its register budget (100 VGPRs,
 // 4 waves/SIMD; the split SH loader of raw mode needs 130)
 constexpr int PP_THREADS = 128;                 // Gaussians per workgroup (measured: 64 -> 0.047, 128 -> 0.039, 256 -> 0.042, 512 -> 0.042 ms on C3)
 constexpr int PP_WAVES = PP_THREADS / 64;

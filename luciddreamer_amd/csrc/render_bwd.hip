@@ -3,8 +3,8 @@
 // Replaces BACKWARD::render / renderCUDA (RAST/cuda_rasterizer/backward.cu:399-586).  The
 // per-pixel recursion is the reference's (back-to-front, T un-blended by division, colour
 // recursion through accum_rec, background term, 0.99 clamp not differentiated, depth gradient
-// ignored -- except in the depth-mode kernels k_render_bwd_depth below, lr_backward_depth; the alpha-mode kernels
-// k_render_bwd*_alpha, lr_backward_alpha, add the gradient of the accumulated opacity).  The kernel is VALU-issue bound; the design removes wave-instructions:
+// ignored -- except in the depth-mode kernels k_render_bwd_depth below, lr_view_backward with dL_depths and depth_image; the alpha-mode kernels
+// k_render_bwd*_alpha, lr_view_backward with dL_dalpha, add the gradient of the accumulated opacity).  The kernel is VALU-issue bound; the design removes wave-instructions:
 //
 //   * same two-level loop as the forward: per 64 staged Gaussians one lane each looks up the outcome of the forward's
 //     exact quadrant test (box_hit, kept per list position in the binning buffer) -> 64-bit candidate mask; only
@@ -259,13 +259,13 @@ __device__ __forceinline__ void bwd_pixel(BwdPix& p, const float qA, const float
 // Gaussian has z > 0.2 (in_frustum), so a pixel with acc > 0.5 has a nonzero depth, exactly the forward's decision.
 // (Not the reference's commented-out depth terms, backward.cu:457-464, 539-554: they differentiate p_proj.z / p_proj.w and
 // the un-normalised D, which is not the quantity the forward outputs.)
-// ALPHA (k_render_bwd_alpha, k_render_bwd_tile_alpha, k_render_bwd_depth_alpha; lr_backward_alpha): the derivative of the
+// ALPHA (k_render_bwd_alpha, k_render_bwd_tile_alpha, k_render_bwd_depth_alpha; lr_view_backward with dL_dalpha): the derivative of the
 // accumulated opacity 1 - T_final for g = dL_dalpha.  Coverage is a colour channel with value 1 and background 0, the same as
 // a channel with value 0 and background 1 taken with weight -g; with value 0 it adds nothing to any layer's difference d, so
 // the whole of it is the start value of A: bg.dL - g at the list's end (and for a pixel that stopped before the segment),
 // and at a segment start where the pixel is still blending the background share seen from there, -g T_final / T_ck -- both
 // numbers the segment already has.  No instruction per layer; the segments and every shape of the default backward stay.
-// ABSG (k_render_bwd_abs; lr_backward_absgrad; 2-wave shape, whole lists as depth mode): the AbsGS statistic.  For pixel p the
+// ABSG (k_render_bwd_abs; lr_view_backward with dL_dmean2D_abs; 2-wave shape, whole lists as depth mode): the AbsGS statistic.  For pixel p the
 // share of dL/dmean2D of the instance is g[p] = -dop (a dx + b dy, c dy + b dx) x the NDC scale -- the signed sums above are its
 // sum over p --; bwd_pixel sums |g[p].x| and |g[p].y| per lane (with the staged, scaled conic), a row sum per 16-lane row goes to
 // four more accumulator columns per term (as the depth term), and the flush applies what is uniform per instance (ln 2 back from
@@ -837,7 +837,7 @@ k_render_bwd_tile(LR_BWD_SEG_PARAMS)
     LR_BWD_KERNEL_BODY_ONE(LR_ITEM)
 #undef LR_ITEM
 }
-// Depth mode (lr_backward_depth): the 2-wave shape with the depth terms, one workgroup per tile walking its whole list (seg_on = 0:
+// Depth mode (lr_view_backward with dL_depths and depth_image): the 2-wave shape with the depth terms, one workgroup per tile walking its whole list (seg_on = 0:
 // the segment checkpoints hold no depth so far, and the forward is not changed to write one).  Its own entry points, so that the
 // default kernels keep their names and instruction streams.  The two per-pixel registers and the tenth sum fit the 72-register
 // budget of k_render_bwd (72 VGPRs, no spills: 7 waves per SIMD; asked for at least 6).
@@ -849,7 +849,7 @@ k_render_bwd_depth(LR_BWD_SEG_PARAMS, const float* __restrict__ dL_ddepth, const
     LR_BWD_KERNEL_BODY(LR_ITEM)
 #undef LR_ITEM
 }
-// Alpha mode (lr_backward_alpha: a gradient through the accumulated opacity 1 - T_final): the default kernels with the ALPHA
+// Alpha mode (lr_view_backward with dL_dalpha: a gradient through the accumulated opacity 1 - T_final): the default kernels with the ALPHA
 // start values of A (render_bwd_item).  Nothing changes per layer, so each keeps the shape, launch bounds and list segments of
 // its default counterpart; own symbols, so that the default kernels keep their names and instruction streams.
 template <bool QUAD, bool STRICT>
@@ -878,7 +878,7 @@ k_render_bwd_depth_alpha(LR_BWD_SEG_PARAMS, const float* __restrict__ dL_ddepth,
     LR_BWD_KERNEL_BODY(LR_ITEM)
 #undef LR_ITEM
 }
-// Absgrad mode (lr_backward_absgrad): the 2-wave shape with the two |.| sums of render_bwd_item<ABSG>, one workgroup per tile over
+// Absgrad mode (lr_view_backward with dL_dmean2D_abs): the 2-wave shape with the two |.| sums of render_bwd_item<ABSG>, one workgroup per tile over
 // its whole list at every image size, as depth mode (seg_on = 0); with or without the depth terms and the ALPHA start values.
 // Own entry points: the kernels above keep their names and instruction streams.
 template <bool STRICT, bool DEPTH, bool ALPHA>

@@ -146,9 +146,22 @@ struct FwdOutputs {
     FwdOutputs(const c10::Device& dev, int64_t P, int64_t H, int64_t W)
         : color(at::empty({3, H, W}, at::TensorOptions().dtype(at::kFloat).device(dev))), depth(at::empty({1, H, W}, color.options())),
           radii(at::empty({P}, color.options().dtype(at::kInt))), geom(dev), binning(dev), img(dev) {}
-    // rc of lr_forward / lr_forward_raw: num_rendered, LR_NUM_RENDERED_ON_DEVICE (async mode) or an error
-    FwdResult result(int rc, const char* what)
+    // runs lr_view_forward on `view` into these outputs, on the device's current stream; rc: num_rendered,
+    // LR_NUM_RENDERED_ON_DEVICE (async mode) or an error
+    FwdResult run(const lr_view& view, bool prefiltered, bool debug, int64_t binning_capacity, const char* what)
     {
+        lr_forward_args a = {};
+        a.struct_bytes = sizeof(a);
+        a.view = view;
+        a.geom_alloc = scratch_alloc; a.geom_user = &geom;
+        a.binning_alloc = scratch_alloc; a.binning_user = &binning;
+        a.img_alloc = scratch_alloc; a.img_user = &img;
+        a.prefiltered = prefiltered ? 1 : 0;
+        a.out_color = color.data_ptr<float>(); a.out_depth = depth.data_ptr<float>(); a.radii = radii.data_ptr<int>();
+        a.debug = debug ? 1 : 0;
+        a.binning_capacity = static_cast<long long>(binning_capacity);
+        a.stream = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(geom.dev.index()).stream();
+        const int rc = lr_view_forward(&a);
         if (rc < 0 && rc != LR_NUM_RENDERED_ON_DEVICE) raise_for(rc, what);
         if (!binning.t.defined()) binning.t = at::empty({0}, at::TensorOptions().dtype(at::kByte).device(binning.dev));
         return FwdResult(rc, color, depth, radii, geom.t, binning.t, img.t);
@@ -172,13 +185,10 @@ FwdResult rasterize_gaussians(const at::Tensor& background, const at::Tensor& me
               op = f32(opacity, dev, "opacities"), sc = f32(scales, dev, "scales"), rot = f32(rotations, dev, "rotations"),
               cov = f32(cov3D_precomp, dev, "cov3D_precomp"), view = f32(viewmatrix, dev, "viewmatrix"),
               proj = f32(projmatrix, dev, "projmatrix"), cam = f32(campos, dev, "campos"), shc = f32(sh, dev, "sh");
-    const int rc = lr_forward(scratch_alloc, &out.geom, scratch_alloc, &out.binning, scratch_alloc, &out.img, static_cast<int>(P),
-                              static_cast<int>(degree), sh_coeffs(sh), bg.p, static_cast<int>(W), static_cast<int>(H), m.p, shc.p,
-                              col.p, op.p, sc.p, static_cast<float>(scale_modifier), rot.p, cov.p, view.p, proj.p, cam.p,
-                              static_cast<float>(tan_fovx), static_cast<float>(tan_fovy), prefiltered ? 1 : 0,
-                              out.color.data_ptr<float>(), out.depth.data_ptr<float>(), out.radii.data_ptr<int>(), debug ? 1 : 0,
-                              static_cast<long long>(binning_capacity), c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(dev.index()).stream());
-    return out.result(rc, "rasterize_gaussians");
+    const lr_view v = { static_cast<int>(P), static_cast<int>(degree), sh_coeffs(sh), 0, bg.p, static_cast<int>(W), static_cast<int>(H),
+                        m.p, shc.p, nullptr, col.p, op.p, sc.p, static_cast<float>(scale_modifier), rot.p, cov.p, view.p, proj.p, cam.p,
+                        static_cast<float>(tan_fovx), static_cast<float>(tan_fovy) };
+    return out.run(v, prefiltered, debug, binning_capacity, "rasterize_gaussians");
 }
 
 // One gradient output of a backward binding: `acc` (a caller tensor, if given) receives `+=` in place -- its LR_ACC_* `bit` is set
@@ -206,8 +216,8 @@ const at::Tensor* given(const std::vector<OptT>& accumulate, int k)
     return (!accumulate.empty() && accumulate[k].has_value() && accumulate[k]->defined()) ? &*accumulate[k] : nullptr;
 }
 
-// The optional images of the depth and alpha modes.  Both backward bindings always call the general entry (lr_backward_alpha /
-// lr_backward_raw_alpha) and leave the mode to the library: depth mode iff depth_image and dL_dout_depth are both given (so
+// The optional images of the depth and alpha modes.  Both backward bindings leave the mode to the library (lr_view_backward):
+// depth mode iff depth_image and dL_dout_depth are both given (so
 // dL_dout_depth goes in only with depth_image), alpha mode iff dL_dout_alpha is; with neither, the default backward, bit for bit.
 void check_mode_images(int64_t H, int64_t W, const Arg& gd, const Arg& di, const Arg& ga)
 {
@@ -216,13 +226,35 @@ void check_mode_images(int64_t H, int64_t W, const Arg& gd, const Arg& di, const
     TORCH_CHECK(!di.p || !gd.p || gd.t.numel() == H * W, "dL_dout_depth must have the depth output's shape (1, H, W)");
 }
 
+// What the two backward bindings share of lr_backward_args: the view, the forward's state, the upstream gradients (checked by
+// check_mode_images), absgrad's output, R and binning_capacity; the other gradient outputs, debug, the mask and the stream are
+// the binding's
+lr_backward_args backward_args(const lr_view& view, int64_t R, int64_t binning_capacity, const at::Tensor& radii_c,
+                               const at::Tensor& geomBuffer, const at::Tensor& binningBuffer, const at::Tensor& imageBuffer,
+                               const Arg& gc, const Arg& gd, const Arg& di, const Arg& ga, const at::Tensor& abs2d)
+{
+    check_mode_images(view.height, view.width, gd, di, ga);
+    lr_backward_args a = {};
+    a.struct_bytes = sizeof(a);
+    a.view = view;
+    a.R = static_cast<int>(R);
+    a.radii = radii_c.data_ptr<int>();
+    a.geom_buffer = static_cast<char*>(geomBuffer.data_ptr());
+    a.binning_buffer = static_cast<char*>(binningBuffer.data_ptr());
+    a.image_buffer = static_cast<char*>(imageBuffer.data_ptr());
+    a.dL_dpix = gc.p; a.dL_depths = di.p ? gd.p : nullptr; a.depth_image = di.p; a.dL_dalpha = ga.p;
+    a.dL_dmean2D_abs = abs2d.defined() ? abs2d.data_ptr<float>() : nullptr;
+    a.binning_capacity = static_cast<long long>(binning_capacity);
+    return a;
+}
+
 // accumulate: eight optional tensors in the order of the returned tuple (means2D, colors, opacity, means3D, cov3D, sh,
 // scales, rotations); a given tensor receives `+=` in place (rows of culled Gaussians untouched) and its slot of the
 // result is None.  skip_unused: gradients of absent input representations are not materialised (None).
 // depth_image (keyword-only; the forward's depth output): with it dL_dout_depth is honoured (depth mode); without it
 // dL_dout_depth is ignored, as in the reference.  dL_dout_alpha (keyword-only, [1,H,W]): the gradient of the alpha output
 // (render_alpha) as well, alone or with depth mode.
-// absgrad (keyword-only): absgrad mode (lr_backward_absgrad) -- a ninth entry of the result, dL_dmean2D_abs [P,3]: per Gaussian
+// absgrad (keyword-only): absgrad mode (lr_backward_args::dL_dmean2D_abs) -- a ninth entry of the result, dL_dmean2D_abs [P,3]: per Gaussian
 // the sums over pixels of |per-pixel dL/dmeans2D| (x, y, 0); always a new tensor, never accumulated.
 std::vector<OptT> rasterize_gaussians_backward(
     const at::Tensor& background, const at::Tensor& means3D, const at::Tensor& radii, const OptT& colors, const OptT& scales,
@@ -261,24 +293,18 @@ std::vector<OptT> rasterize_gaussians_backward(
                   proj = f32(projmatrix, dev, "projmatrix"), cam = f32(campos, dev, "campos"), shc = f32(sh, dev, "sh"),
                   gc = f32(dL_dout_color, dev, "dL_dout_color"), gd = f32(dL_dout_depth, dev, "dL_dout_depth"),
                   di = f32(depth_image, dev, "depth_image"), ga = f32(dL_dout_alpha, dev, "dL_dout_alpha");
-        check_mode_images(H, W, gd, di, ga);
         const at::Tensor radii_c = radii.contiguous();
         hipStream_t cur = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(dev.index()).stream();
+        const lr_view v = { static_cast<int>(P), static_cast<int>(degree), M, 0, bg.p, static_cast<int>(W), static_cast<int>(H), m.p,
+                            shc.p, nullptr, col.p, nullptr, sc.p, static_cast<float>(scale_modifier), rot.p, cov.p, view.p, proj.p,
+                            cam.p, static_cast<float>(tan_fovx), static_cast<float>(tan_fovy) };
+        lr_backward_args a = backward_args(v, R, binning_capacity, radii_c, geomBuffer, binningBuffer, imageBuffer, gc, gd, di, ga,
+                                           abs2d);
+        a.debug = debug ? 1 : 0; a.accumulate_mask = mask; a.stream = cur;
+        a.dL_dmean2D = ptr[0]; a.dL_dopacity = ptr[2]; a.dL_dcolor = ptr[1]; a.dL_dmean3D = ptr[3]; a.dL_dcov3D = ptr[4];
+        a.dL_dsh = M ? ptr[5] : nullptr; a.dL_dscale = ptr[6]; a.dL_drot = ptr[7];
         ChainScope chain(mask != 0 || t_fused_backward, dev.index(), cur);
-        const int rc = absgrad ? lr_backward_absgrad(
-            static_cast<int>(P), static_cast<int>(degree), M, static_cast<int>(R), bg.p, static_cast<int>(W), static_cast<int>(H), m.p,
-            shc.p, col.p, sc.p, static_cast<float>(scale_modifier), rot.p, cov.p, view.p, proj.p, cam.p, static_cast<float>(tan_fovx),
-            static_cast<float>(tan_fovy), radii_c.data_ptr<int>(), static_cast<char*>(geomBuffer.data_ptr()),
-            static_cast<char*>(binningBuffer.data_ptr()), static_cast<char*>(imageBuffer.data_ptr()), gc.p, di.p ? gd.p : nullptr,
-            di.p, ga.p, ptr[0], abs2d.data_ptr<float>(), nullptr, ptr[2], ptr[1], ptr[3], ptr[4], M ? ptr[5] : nullptr, ptr[6], ptr[7],
-            debug ? 1 : 0, static_cast<long long>(binning_capacity), mask, cur)
-                              : lr_backward_alpha(
-            static_cast<int>(P), static_cast<int>(degree), M, static_cast<int>(R), bg.p, static_cast<int>(W), static_cast<int>(H), m.p,
-            shc.p, col.p, sc.p, static_cast<float>(scale_modifier), rot.p, cov.p, view.p, proj.p, cam.p, static_cast<float>(tan_fovx),
-            static_cast<float>(tan_fovy), radii_c.data_ptr<int>(), static_cast<char*>(geomBuffer.data_ptr()),
-            static_cast<char*>(binningBuffer.data_ptr()), static_cast<char*>(imageBuffer.data_ptr()), gc.p, di.p ? gd.p : nullptr,
-            di.p, ga.p, ptr[0], nullptr, ptr[2], ptr[1], ptr[3], ptr[4], M ? ptr[5] : nullptr, ptr[6], ptr[7], debug ? 1 : 0,
-            static_cast<long long>(binning_capacity), mask, cur);
+        const int rc = lr_view_backward(&a);
         if (rc < 0) raise_for(rc, "rasterize_gaussians_backward");
     }
     return result;
@@ -304,19 +330,16 @@ FwdResult rasterize_gaussians_raw(const at::Tensor& background, const at::Tensor
     const Arg bg = f32(background, dev, "background"), x = f32(xyz, dev, "xyz"), dc = f32(features_dc, dev, "features_dc"),
               op = f32(opacity_raw, dev, "opacity"), sc = f32(scaling_raw, dev, "scaling"), rot = f32(rotation_raw, dev, "rotation"),
               view = f32(viewmatrix, dev, "viewmatrix"), proj = f32(projmatrix, dev, "projmatrix"), cam = f32(campos, dev, "campos");
-    const int rc = lr_forward_raw(scratch_alloc, &out.geom, scratch_alloc, &out.binning, scratch_alloc, &out.img, static_cast<int>(P),
-                                  static_cast<int>(degree), M, bg.p, static_cast<int>(W), static_cast<int>(H), x.p, dc.p, rest.p, op.p,
-                                  sc.p, static_cast<float>(scale_modifier), rot.p, view.p, proj.p, cam.p, static_cast<float>(tan_fovx),
-                                  static_cast<float>(tan_fovy), out.color.data_ptr<float>(), out.depth.data_ptr<float>(),
-                                  out.radii.data_ptr<int>(), debug ? 1 : 0, static_cast<long long>(binning_capacity),
-                                  c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(dev.index()).stream());
-    return out.result(rc, "rasterize_gaussians_raw");
+    const lr_view v = { static_cast<int>(P), static_cast<int>(degree), M, 1, bg.p, static_cast<int>(W), static_cast<int>(H), x.p, dc.p,
+                        rest.p, nullptr, op.p, sc.p, static_cast<float>(scale_modifier), rot.p, nullptr, view.p, proj.p, cam.p,
+                        static_cast<float>(tan_fovx), static_cast<float>(tan_fovy) };
+    return out.run(v, false, debug, binning_capacity, "rasterize_gaussians_raw");
 }
 
 // result / accumulate order: (means2D, xyz, features_dc, features_rest, opacity, scaling, rotation)
 // dL_dout_depth / depth_image / dL_dout_alpha (keyword-only): as in rasterize_gaussians_backward; the gradient of the depth
 // output is used only when depth_image is given as well.  absgrad: dL_dmean2D_abs [P,3] as an eighth entry of the result
-// (lr_backward_raw_absgrad), as in rasterize_gaussians_backward.
+// as in rasterize_gaussians_backward.
 std::vector<OptT> rasterize_gaussians_raw_backward(
     const at::Tensor& background, const at::Tensor& xyz, const at::Tensor& radii, const at::Tensor& features_dc,
     const OptT& features_rest, const at::Tensor& opacity_raw, const at::Tensor& scaling_raw, const at::Tensor& rotation_raw,
@@ -361,24 +384,18 @@ std::vector<OptT> rasterize_gaussians_raw_backward(
                   view = f32(viewmatrix, dev, "viewmatrix"), proj = f32(projmatrix, dev, "projmatrix"), cam = f32(campos, dev, "campos"),
                   gc = f32(dL_dout_color, dev, "dL_dout_color"), gd = f32(dL_dout_depth, dev, "dL_dout_depth"),
                   di = f32(depth_image, dev, "depth_image"), ga = f32(dL_dout_alpha, dev, "dL_dout_alpha");
-        check_mode_images(H, W, gd, di, ga);
         const at::Tensor radii_c = radii.contiguous();
         hipStream_t cur = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(dev.index()).stream();
+        const lr_view v = { static_cast<int>(P), static_cast<int>(degree), M, 1, bg.p, static_cast<int>(W), static_cast<int>(H), x.p,
+                            dc.p, rest.p, nullptr, op.p, sc.p, static_cast<float>(scale_modifier), rot.p, nullptr, view.p, proj.p,
+                            cam.p, static_cast<float>(tan_fovx), static_cast<float>(tan_fovy) };
+        lr_backward_args a = backward_args(v, R, binning_capacity, radii_c, geomBuffer, binningBuffer, imageBuffer, gc, gd, di, ga,
+                                           abs2d);
+        a.debug = debug ? 1 : 0; a.accumulate_mask = mask; a.stream = cur;
+        a.dL_dmean2D = ptr[0]; a.dL_dopacity = ptr[4]; a.dL_dmean3D = ptr[1]; a.dL_dsh = ptr[2];
+        a.dL_dsh_rest = nrest ? ptr[3] : nullptr; a.dL_dscale = ptr[5]; a.dL_drot = ptr[6];
         ChainScope chain((mask & ~LR_ACC_NO_ZERO_FILL) != 0, dev.index(), cur);
-        const int rc = absgrad ? lr_backward_raw_absgrad(
-            static_cast<int>(P), static_cast<int>(degree), M, static_cast<int>(R), bg.p, static_cast<int>(W), static_cast<int>(H), x.p,
-            dc.p, rest.p, op.p, sc.p, static_cast<float>(scale_modifier), rot.p, view.p, proj.p, cam.p, static_cast<float>(tan_fovx),
-            static_cast<float>(tan_fovy), radii_c.data_ptr<int>(), static_cast<char*>(geomBuffer.data_ptr()),
-            static_cast<char*>(binningBuffer.data_ptr()), static_cast<char*>(imageBuffer.data_ptr()), gc.p, di.p ? gd.p : nullptr,
-            di.p, ga.p, ptr[0], abs2d.data_ptr<float>(), ptr[4], ptr[1], ptr[2], nrest ? ptr[3] : nullptr, ptr[5], ptr[6],
-            debug ? 1 : 0, static_cast<long long>(binning_capacity), mask, cur)
-                              : lr_backward_raw_alpha(
-            static_cast<int>(P), static_cast<int>(degree), M, static_cast<int>(R), bg.p, static_cast<int>(W), static_cast<int>(H), x.p,
-            dc.p, rest.p, op.p, sc.p, static_cast<float>(scale_modifier), rot.p, view.p, proj.p, cam.p, static_cast<float>(tan_fovx),
-            static_cast<float>(tan_fovy), radii_c.data_ptr<int>(), static_cast<char*>(geomBuffer.data_ptr()),
-            static_cast<char*>(binningBuffer.data_ptr()), static_cast<char*>(imageBuffer.data_ptr()), gc.p, di.p ? gd.p : nullptr,
-            di.p, ga.p, ptr[0], ptr[4], ptr[1], ptr[2], nrest ? ptr[3] : nullptr, ptr[5], ptr[6], debug ? 1 : 0,
-            static_cast<long long>(binning_capacity), mask, cur);
+        const int rc = lr_view_backward(&a);
         if (rc < 0) raise_for(rc, "rasterize_gaussians_raw_backward");
     }
     return result;

@@ -12,7 +12,8 @@ import torch
 
 from . import _lib
 
-# Group names of GaussianModel.training_setup (R/scene/gaussian_model.py:155-162) in the tensor order of lr_backward_raw_adam
+# Group names of GaussianModel.training_setup (R/scene/gaussian_model.py:155-162) in the tensor order of the raw backward's outputs
+# (lr_view_backward with raw = 1) as lr_adam_step_masked takes them
 FUSED_ORDER = ("xyz", "f_dc", "f_rest", "opacity", "scaling", "rotation")
 _armed = None                # the FusedAdam whose step the NEXT raw-mode rasterizer backward takes (arm_fused_backward)
 
@@ -37,7 +38,7 @@ class FusedAdam(torch.optim.Optimizer):
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps))
         self._fused_pending = None       # the parameters an armed backward has already stepped, until step() has checked the iteration
 
-    # ---- the step taken by the backward pass (lr_backward_raw_adam) ------------------------------------------
+    # ---- the step taken by the backward pass (a raw lr_view_backward under LR_ACC_NO_ZERO_FILL + lr_adam_step_masked) -----
     def _fused_groups(self):
         by_name = {g.get("name"): g for g in self.param_groups}
         if any(n not in by_name or len(by_name[n]["params"]) != 1 for n in FUSED_ORDER):

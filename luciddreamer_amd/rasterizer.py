@@ -6,8 +6,8 @@
     rasterize_gaussians             functional entry                                (:21-42)
 
 Beyond the reference: return_alpha=True (GaussianRasterizer.forward, rasterize_gaussians, rasterize_gaussians_raw) returns
-(color, radii, depth, alpha) -- alpha (1, H, W) = 1 - T_final, the accumulated opacity, differentiable (lr_backward_alpha).
-config.set_absgrad(True): the backward of a view attaches `means2D.absgrad` [P,3] (AbsGS; lr_backward_absgrad) to the means2D
+(color, radii, depth, alpha) -- alpha (1, H, W) = 1 - T_final, the accumulated opacity, differentiable (lr_view_backward with dL_dalpha).
+config.set_absgrad(True): the backward of a view attaches `means2D.absgrad` [P,3] (AbsGS; lr_view_backward with dL_dmean2D_abs) to the means2D
 tensor the caller passed.
 
 Error behaviour mirrored: plain `Exception` for bad SH/colour or scale/rotation/covariance
@@ -171,7 +171,7 @@ def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales,
     interpreter -- the Python node below cost more host time per 1080p view than the GPU needs for it); with settings.debug
     the Python node runs instead, because it is the one that writes the reference's snapshot_fw.dump / snapshot_bw.dump.
     return_alpha: (color, radii, depth, alpha) -- alpha = 1 - T_final (1, H, W), differentiable; a gradient reaching it runs the
-    alpha-mode backward (lr_backward_alpha), an unused alpha output the default one."""
+    alpha-mode backward (lr_view_backward with dL_dalpha), an unused alpha output the default one."""
     rs = raster_settings
     if rs.debug:
         return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,

@@ -1,6 +1,6 @@
 """Float64 reference of the absgrad output (test helper, not collected).
 
-lr_backward_absgrad returns, per Gaussian i, (sum_p |g[p,i].x|, sum_p |g[p,i].y|, 0): g[p,i] the part of dL/dmeans2D_i[:2] that
+lr_view_backward with dL_dmean2D_abs returns, per Gaussian i, (sum_p |g[p,i].x|, sum_p |g[p,i].y|, 0): g[p,i] the part of dL/dmeans2D_i[:2] that
 flows through pixel p, in the NDC scale of dL_dmean2D.  tests/grad_oracle.render takes means2D as a virtual screen-space offset
 in NDC units, so the gradient of a scalar with respect to it IS dL_dmean2D; here every pixel's share of L is back-propagated on
 its own (one autograd.grad per pixel) and the magnitudes are summed.  The signed sum of the same per-pixel gradients is returned

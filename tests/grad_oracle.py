@@ -1,14 +1,14 @@
 """Float64 PyTorch restatement of oracle/torch_oracle.render with DIFFERENTIABLE depth and alpha outputs (test helper, not
 collected).
 
-The depth-mode backward (lr_backward_depth, config.set_depth_gradient) returns the true derivative of the forward's depth
+The depth-mode backward (lr_view_backward with dL_depths and depth_image, config.set_depth_gradient) returns the true derivative of the forward's depth
 output depth = D / acc (0 where acc <= 0.5) with the colour path's conventions -- the 0.99 clamp of alpha and the fov clamp
 treated as in torch_oracle (its docstring, points i and ii), the skips, the T < 1e-4 stop, the sort order and the acc > 0.5
 mask constant.  torch_oracle reproduces the reference, whose depth carries no gradient (point iii: two detach() calls, on the
 per-Gaussian view depth and on the depth image); this restatement of its render loop drops exactly those two, so that
 autograd through it is the contract of the depth mode.  The sort key stays detached.
 
-The alpha output (return_alpha, lr_render_alpha) is 1 - T_final per pixel; its backward (lr_backward_alpha) is the true
+The alpha output (return_alpha, lr_render_alpha) is 1 - T_final per pixel; its backward (lr_view_backward with dL_dalpha) is the true
 derivative of 1 - prod_i (1 - alpha_i) over the layers the forward applied, with the same conventions (the T < 1e-4 stop's
 trigger is not applied).
 """

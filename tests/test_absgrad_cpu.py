@@ -1,4 +1,4 @@
-"""Absolute view-space gradient (AbsGS; config.set_absgrad, lr_backward_absgrad / lr_backward_raw_absgrad): the contract's CPU
+"""Absolute view-space gradient (AbsGS; config.set_absgrad, lr_backward_args::dL_dmean2D_abs): the contract's CPU
 side -- the float64 reference checks itself, the seeded cases are fit for the GPU comparisons, the switch and the exports."""
 import os
 import re
@@ -78,16 +78,19 @@ def test_exports_and_header():
     L = _lib.lib()
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     header = open(os.path.join(root, "include", "lucid_raster.h")).read()
-    for name in ("lr_backward_absgrad", "lr_backward_raw_absgrad"):
-        assert name in _lib.EXPORTS
-        getattr(L, name)
-        m = re.search(r"int " + name + r"\((.*?)\);", header, re.S)
-        assert m, name
-        args = [a.strip() for a in m.group(1).split(",")]
-        i = args.index("float* dL_dmean2D")
-        assert args[i + 1] == "float* dL_dmean2D_abs"                    # right after dL_dmean2D
-        alpha = re.search(r"int " + name.replace("absgrad", "alpha") + r"\((.*?)\);", header, re.S)
-        assert [a for a in args if a != "float* dL_dmean2D_abs"] == [a.strip() for a in alpha.group(1).split(",")]
+    assert "lr_view_backward" in _lib.EXPORTS
+    getattr(L, "lr_view_backward")
+    assert re.search(r"^int\s+lr_view_backward\s*\(const lr_backward_args\*", header, re.M)
+    # the statistic is a member of the one backward struct (activated and raw mode alike), right after dL_dmean2D
+    m = re.search(r"typedef struct lr_backward_args \{(.*?)\} lr_backward_args;", header, re.S)
+    assert m
+    members = [x.strip() for x in re.sub(r"/\*.*?\*/", "", m.group(1), flags=re.S).split(";") if x.strip()]
+    i = members.index("float* dL_dmean2D")
+    assert members[i + 1] == "float* dL_dmean2D_abs"                     # right after dL_dmean2D
+    names = [f[0] for f in _lib.BackwardArgs._fields_]
+    assert names[names.index("dL_dmean2D") + 1] == "dL_dmean2D_abs"      # ... and in the ctypes mirror
+    # a call without it is the call of the other modes: every other member is what they take
+    assert [re.split(r"[ *]+", x)[-1] for x in members if x != "float* dL_dmean2D_abs"] == [n for n in names if n != "dL_dmean2D_abs"]
 
 
 def test_stats_need_the_attribute():

@@ -1,4 +1,4 @@
-"""Differentiable alpha output (return_alpha, lr_render_alpha / lr_backward_alpha): the contract's CPU side.
+"""Differentiable alpha output (return_alpha, lr_render_alpha / lr_view_backward with dL_dalpha): the contract's CPU side.
 
 tests/grad_oracle.py restates the render loop with alpha = 1 - T_final as an output (alpha=True).  These tests check that
 output against the same render without it (same colour, depth and radii), against the coverage render and against float64
@@ -191,18 +191,19 @@ def test_coverage_recursion_matches_autograd_whole_lists_and_segment_starts():
 def test_header_declares_and_library_exports_the_alpha_entry_points():
     text = open(os.path.join(ROOT, "include", "lucid_raster.h")).read()
     text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    for name in ("lr_backward_alpha", "lr_backward_raw_alpha"):
-        m = re.search(r"^int\s+" + name + r"\s*\(([^;]*)\);", text, flags=re.M)
-        assert m, name
-        args = m.group(1)
-        assert re.search(r"const float\* depth_image,\s*const float\* dL_dalpha,", args), name
+    assert re.search(r"^int\s+lr_view_backward\s*\(const lr_backward_args\*[^;]*\);", text, flags=re.M)
+    m = re.search(r"typedef struct lr_backward_args \{(.*?)\} lr_backward_args;", text, flags=re.S)
+    assert m                                            # one struct for activated and raw mode
+    assert re.search(r"const float\* depth_image;\s*const float\* dL_dalpha;", m.group(1))
     m = re.search(r"^int\s+lr_render_alpha\s*\(([^;]*)\);", text, flags=re.M)
     assert m and "float* out_alpha" in m.group(1)
     from luciddreamer_amd import _lib, build
     L = ctypes.CDLL(build.build())
-    for name in ("lr_backward_alpha", "lr_backward_raw_alpha", "lr_render_alpha"):
+    for name in ("lr_view_backward", "lr_render_alpha"):
         assert hasattr(L, name), name
         assert name in _lib.EXPORTS, name
+    names = [f[0] for f in _lib.BackwardArgs._fields_]
+    assert names[names.index("depth_image") + 1] == "dL_dalpha"
 
 
 def test_public_signatures_take_return_alpha():

@@ -1,4 +1,4 @@
-"""Differentiable depth output (config.set_depth_gradient, lr_backward_depth): the contract's CPU side.
+"""Differentiable depth output (config.set_depth_gradient, lr_view_backward with dL_depths and depth_image): the contract's CPU side.
 
 tests/grad_oracle.py restates oracle/torch_oracle.render without the two detach() calls on depth; these tests check that
 restatement against torch_oracle (colour gradients unchanged) and against float64 central differences (the depth gradient is
@@ -101,8 +101,12 @@ def test_depth_gradient_switch_defaults_to_off():
 def test_header_declares_the_depth_entry_points():
     text = open(os.path.join(ROOT, "include", "lucid_raster.h")).read()
     text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    for name in ("lr_backward_depth", "lr_backward_raw_depth"):
-        m = re.search(r"^int\s+" + name + r"\s*\(([^;]*)\);", text, flags=re.M)
-        assert m, name
-        args = m.group(1)
-        assert "const float* dL_depths" in args and "const float* depth_image" in args, name
+    assert re.search(r"^int\s+lr_view_backward\s*\(const lr_backward_args\*[^;]*\);", text, flags=re.M)
+    m = re.search(r"typedef struct lr_backward_args \{(.*?)\} lr_backward_args;", text, flags=re.S)
+    assert m
+    args = m.group(1)                                   # one struct for activated and raw mode
+    assert "const float* dL_depths;" in args and "const float* depth_image;" in args
+    from luciddreamer_amd import _lib
+    names = [f[0] for f in _lib.BackwardArgs._fields_]
+    assert "dL_depths" in names and "depth_image" in names
+    assert "lr_view_backward" in _lib.EXPORTS

@@ -1,4 +1,4 @@
-"""Absolute view-space gradient on the GPU (config.set_absgrad -> lr_backward_absgrad / lr_backward_raw_absgrad) against the
+"""Absolute view-space gradient on the GPU (config.set_absgrad -> lr_view_backward with dL_dmean2D_abs) against the
 float64 per-pixel reference (tests/absgrad_ref.py) on the seeded cases of tests/absgrad_cases.py, through the binding (one C-ABI
 call each) and through the operators.
 

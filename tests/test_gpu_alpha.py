@@ -1,4 +1,4 @@
-"""Differentiable alpha output on the GPU (return_alpha -> lr_render_alpha, lr_backward_alpha / lr_backward_raw_alpha).
+"""Differentiable alpha output on the GPU (return_alpha -> lr_render_alpha, lr_view_backward with dL_dalpha).
 
 The forward's alpha against the float64 restatement tests/grad_oracle.py, gradients of losses on alpha (alone, and with
 colour and depth mode) against its autograd, on every blend-backward shape and variant that reaches the alpha-mode kernels, a
@@ -285,7 +285,7 @@ def test_fused_accumulation_adds_the_alpha_gradient(hip_device):
 
 @pytest.mark.parametrize("with_depth", [False, True], ids=["color_alpha", "color_depth_alpha"])
 def test_raw_path_matches_activated_path(hip_device, with_depth):
-    """render_raw (the raw node, lr_backward_raw_alpha) = render on the activated tensors followed by autograd through
+    """render_raw (the raw node, lr_view_backward with raw = 1 and dL_dalpha) = render on the activated tensors followed by autograd through
     exp / normalize / sigmoid, for a loss on colour, alpha (and depth)."""
     from luciddreamer_amd.gaussian_renderer import GaussianCloud, render, render_raw
     W, H = 256, 160

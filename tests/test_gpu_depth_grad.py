@@ -1,4 +1,4 @@
-"""Differentiable depth output on the GPU (config.set_depth_gradient -> lr_backward_depth / lr_backward_raw_depth).
+"""Differentiable depth output on the GPU (config.set_depth_gradient -> lr_view_backward with dL_depths and depth_image).
 
 Gradients of losses on `depth` against the float64 restatement tests/grad_oracle.py (sizes bounded by that Python
 oracle), the variants that reach the depth-mode kernels (strict parity, the Python debug node, fused accumulation, the raw
@@ -156,7 +156,7 @@ def test_fused_accumulation_adds_the_depth_gradient(hip_device, depth_on):
 
 
 def test_raw_path_matches_activated_path(hip_device, depth_on):
-    """render_raw (the raw node, lr_backward_raw_depth) = render on the activated tensors followed by autograd through
+    """render_raw (the raw node, lr_view_backward with raw = 1, dL_depths and depth_image) = render on the activated tensors followed by autograd through
     exp / normalize / sigmoid, for a colour + depth loss."""
     from luciddreamer_amd.gaussian_renderer import GaussianCloud, render, render_raw
     W, H = 256, 160

@@ -160,7 +160,7 @@ def _adam_for(cloud):
 @pytest.mark.parametrize("W,H", [(320, 192), (1280, 720)])
 def test_step_taken_by_the_backward_gives_the_bits_of_backward_plus_step(hip_device, W, H):
     """Same cloud twice, same views, same upstream gradients.  A: raw-mode backward writes the gradients, FusedAdam.step()
-    applies them (lr_backward_raw + lr_adam_step).  B: the optimizer is armed, the backward writes only the rows of the Gaussians
+    applies them (lr_view_backward with raw = 1 + lr_adam_step).  B: the optimizer is armed, the backward writes only the rows of the Gaussians
     the view touches into tensors autograd never sees (LR_ACC_NO_ZERO_FILL) and step() takes every other gradient as zero without
     reading it (lr_adam_step_masked).  After every iteration all six parameter tensors and both moments must be the SAME BITS, and so must
     the screen-space gradients the densification statistics read -- over views that see a fraction of the band cloud (most

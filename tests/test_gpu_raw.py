@@ -1,4 +1,4 @@
-"""raw-parameter fast path (lr_forward_raw / lr_backward_raw).
+"""raw-parameter fast path (lr_view_forward / lr_view_backward with raw = 1).
 
 The stored GaussianModel tensors (log-scales, logit-opacities, unnormalised quaternions, SH split in
 features_dc | features_rest; /root/reference/scene/gaussian_model.py:47-52, 97-117) go straight into the

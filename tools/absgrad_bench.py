@@ -1,4 +1,4 @@
-"""Cost of the absgrad-mode backward (config.set_absgrad -> lr_backward_absgrad) against the default and the depth-mode backward.
+"""Cost of the absgrad-mode backward (config.set_absgrad -> lr_view_backward with dL_dmean2D_abs) against the default and the depth-mode backward.
 
     python tools/absgrad_bench.py [--iters 25] [--warmup 5] [--workloads c3,ld512]
 

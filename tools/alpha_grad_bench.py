@@ -1,4 +1,4 @@
-"""Cost of the alpha output (return_alpha -> lr_render_alpha, lr_backward_alpha) against the default backward and against the
+"""Cost of the alpha output (return_alpha -> lr_render_alpha, lr_view_backward with dL_dalpha) against the default backward and against the
 two-render workaround.
 
     python tools/alpha_grad_bench.py [--iters 25] [--warmup 5] [--workloads c3,ld512]

@@ -1,4 +1,4 @@
-"""Cost of the depth-mode backward (config.set_depth_gradient -> lr_backward_depth) against the default backward.
+"""Cost of the depth-mode backward (config.set_depth_gradient -> lr_view_backward with dL_depths and depth_image) against the default backward.
 
     python tools/depth_grad_bench.py [--iters 25] [--warmup 5] [--workloads c3,ld512]
 
