@@ -13,6 +13,11 @@ a perturbed subset of it.  Prints the loss every `--log` iterations and the time
 
     python examples/train_loop.py [--gaussians 200000] [--iters 300] [--resolution 512x512]
                                   [--absgrad --densify-grad-threshold 0.0008]
+                                  [--multi-view 4 [--absgrad]]
+
+--multi-view K: the loop body is ONE multi-view step (parallel.ViewBatch: forward, L1 + DSSIM loss and backward of K views in one
+C call, gradients summed) followed by Adam; the densification statistics are formed inside the step, per view
+(densify_stats="grad", or "absgrad" with --absgrad), and densify_and_prune runs on them.
 """
 import argparse
 import math
@@ -80,7 +85,90 @@ def build(args, dev):
     return model, cams, targets
 
 
+def _capacity(model, cams, bg):
+    """Binning capacity of a multi-view step: twice the largest exact-mode instance count over the path, + 4096 (the cloud
+    moves between two densifications; an overflow is reported by ViewBatch.check, never silent)."""
+    from depth_diff_gaussian_rasterization_min import GaussianRasterizationSettings, GaussianRasterizer
+    from luciddreamer_amd import _C
+    config.set_async(False)
+    try:
+        n = []
+        with torch.no_grad():
+            for c in cams:
+                rs = GaussianRasterizationSettings(c.image_height, c.image_width, math.tan(c.FoVx * 0.5), math.tan(c.FoVy * 0.5),
+                                                   bg, 1.0, c.world_view_transform, c.full_proj_transform, 3, c.camera_center,
+                                                   False, False)
+                GaussianRasterizer(rs)(means3D=model.get_xyz, means2D=torch.zeros_like(model.get_xyz), opacities=model.get_opacity,
+                                       shs=model.get_features.contiguous(), scales=model.get_scaling, rotations=model.get_rotation)
+                n.append(int(_C.last_num_rendered()))
+    finally:
+        config.set_async(True)
+        config.reset()
+    return 2 * max(n) + 4096
+
+
+def train_multi_view(args, log=print):
+    """One ViewBatch step of K views with targets per iteration, then Adam; densification on the step's own statistics."""
+    from luciddreamer_amd import parallel
+    dev = torch.device("cuda:0")
+    model, cams, targets = build(args, dev)
+    bg = torch.zeros(3, device=dev)
+    K = min(int(args.multi_view), len(cams))
+    mode = "absgrad" if args.absgrad else "grad"
+    config.set_antialiasing(args.antialiasing)
+    groups = [list(range(i, i + K)) for i in range(0, len(cams) - K + 1, K)]      # consecutive views of the path
+    batches, cap = {}, _capacity(model, cams, bg)
+
+    def batch_for(gi, with_stats):
+        key = (gi, with_stats)
+        if key not in batches:
+            batches[key] = parallel.ViewBatch([cams[i] for i in groups[gi]], None, 3, bg, cap, n_streams=min(3, K),
+                                              targets=[targets[i] for i in groups[gi]], lambda_dssim=args.lambda_dssim,
+                                              densify_stats=mode if with_stats else None)
+        return batches[key]
+    losses = []
+    gen = torch.Generator().manual_seed(0)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for it in range(1, args.iters + 1):
+        gi = int(torch.randint(0, len(groups), (1,), generator=gen))
+        with_stats = it < args.densify_until
+        batch = batch_for(gi, with_stats)
+        # the step takes activated parameters and accumulates their gradients; autograd carries them to the stored ones
+        act = {"means3D": model.get_xyz, "opacities": model.get_opacity, "scales": model.get_scaling,
+               "rotations": model.get_rotation, "shs": model.get_features}
+        P = act["means3D"].shape[0]
+        acc = {"means3D": torch.zeros(P, 3, device=dev), "means2D": torch.zeros(P, 3, device=dev),
+               "opacity": torch.zeros(P, 1, device=dev), "sh": torch.zeros(P, 16, 3, device=dev),
+               "scales": torch.zeros(P, 3, device=dev), "rotations": torch.zeros(P, 4, device=dev)}
+        d = {k: v.detach().contiguous() for k, v in act.items()}
+        batch.run(d["means3D"], d["opacities"], d["scales"], d["rotations"], d["shs"], acc,
+                  stats=densify.view_batch_stats(model) if with_stats else None)
+        torch.autograd.backward([act["means3D"], act["opacities"], act["scales"], act["rotations"], act["shs"]],
+                                [acc["means3D"], acc["opacity"], acc["scales"], acc["rotations"], acc["sh"]])
+        with torch.no_grad():
+            densified = with_stats and it >= args.densify_from and it % args.densify_every == 0
+            if densified:
+                batch.check()                      # an overflowed view would have contributed nothing
+                densify.densify_and_prune(model, args.densify_grad_threshold, 0.005, 5.0, 20)
+            model.optimizer.step()
+            model.optimizer.zero_grad(set_to_none=True)
+            if densified:                          # another P: another capacity, and the batches are rebuilt on it
+                batches, cap = {}, _capacity(model, cams, bg)
+        if it % args.log == 0 or it == 1:
+            batch.check()
+            losses.append((it, float(batch.losses[:, 0].mean().item()), int(model._xyz.shape[0])))
+            log(f"iter {it:5d}  loss {losses[-1][1]:.5f}  gaussians {losses[-1][2]}")
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    config.set_antialiasing(False)
+    log(f"{args.iters} iterations of {K} views in {dt:.2f} s = {dt / args.iters * 1e3:.3f} ms/iteration")
+    return losses, dt
+
+
 def train(args, log=print):
+    if getattr(args, "multi_view", 0) > 0:
+        return train_multi_view(args, log)
     dev = torch.device("cuda:0")
     model, cams, targets = build(args, dev)
     bg = torch.zeros(3, device=dev)
@@ -121,12 +209,14 @@ def train(args, log=print):
 def default_args(**kw):
     d = dict(gaussians=200_000, iters=300, resolution="512x512", views=12, lambda_dssim=0.2, log=50, densify_from=100,
              densify_every=100, densify_until=10_000, exact=False, torch_adam=False, antialiasing=False, absgrad=False,
-             densify_grad_threshold=0.0002)
+             densify_grad_threshold=0.0002, multi_view=0)
     d.update(kw)
     return SimpleNamespace(**d)
 
 
 HELP = {
+    "multi_view": "K > 0: one multi-view step of K views per iteration (parallel.ViewBatch with targets) instead of one view; the "
+                  "densification statistics come from the step itself (with --absgrad: the absolute gradient's)",
     "absgrad": "densify by the absolute view-space gradient (AbsGS, config.set_absgrad): per-pixel pulls on a Gaussian are summed "
                "by magnitude, so large Gaussians over blurry regions get split; raise --densify-grad-threshold with it",
     "densify_grad_threshold": "clone / split threshold on the accumulated view-space gradient norm (reference: 0.0002).  Summed "

@@ -283,7 +283,7 @@ typedef struct lr_forward_args {
  * (no bit of accumulate_mask refers to it), not part of the armed fused step.  Every other output is what the call without it
  * gives for the same arguments up to the rounding of another reduction order: the blend backward runs the 2-wave shape over
  * whole lists at every image size, as depth mode does.  No global float atomics: bit-repeatable.  lr_views_accumulate does not
- * produce it.
+ * hand out the tensor; it accumulates the norm of each view's into its densification statistics (stat_absgrad, below).
  */
 typedef struct lr_backward_args {
     size_t struct_bytes;                     /* = sizeof(lr_backward_args); anything else is LR_ERR_INVALID_ARG */
@@ -367,6 +367,23 @@ int lr_render_alpha(const char* image_buffer, int width, int height, float* out_
  * with targets, | LR_VIEWS_DEPTH_LOSS with depth_targets, | LR_VIEWS_MASK_LOSS with masks (a mask step's slot always has the
  * depth part too: LOSS|MASK and LOSS|DEPTH|MASK are one layout).  DEPTH or MASK without LOSS, or unknown bits, are invalid:
  * the size query returns 0 and lr_views_check LR_ERR_INVALID_ARG.  lr_views_check takes the values the step was run with.
+ * Densification statistics (0.6.3): with stat_grad_accum, stat_denom and stat_max_radii [P] given -- all three or none, anything
+ * else is LR_ERR_INVALID_ARG, as is stat_absgrad != 0 without them; 4-byte aligned, accumulated into, no accumulate-mask bit
+ * refers to them, no extra workspace -- the call leaves them as if, for every view v of the step in order,
+ *     lr_densify_stats(P, radii_v, G_v, stat_grad_accum, stat_denom, stat_max_radii)
+ * had run with the view's own gradient G_v, which the step never materialises: per Gaussian with radii_v > 0,
+ * stat_grad_accum += |G_v.xy|, stat_denom += 1, stat_max_radii = max(stat_max_radii, radii_v) -- the reference's rule, the norm
+ * PER VIEW and then the sum (R/scene/gaussian_model.py:405-407), which acc_mean2D (the signed sum over the views) cannot give.
+ *   stat_absgrad == 0: G_v is the dL_dmean2D lr_view_backward would write for that view alone, with every term the view has in
+ *     the step (colour, depth, alpha; fixed gradients or fused loss).  The step's other outputs keep their bits.
+ *   stat_absgrad != 0: G_v is that call's dL_dmean2D_abs (Absgrad mode above); as there, every view's blend backward then runs
+ *     the absgrad kernel shape and the step's gradients agree with the step without it up to the rounding of the reduction order.
+ * The visibility rule is radii_v > 0, not "owns a tile instance": a Gaussian whose tiles were all culled still counts in
+ * stat_denom and stat_max_radii, with a norm of 0.  A view that overflowed its binning buffer contributes nothing to the three
+ * tensors, as its backward writes nothing (the overflow stays latched for lr_views_check).  No global float atomics: the
+ * accumulations are chained in view order, so the statistics are bit-repeatable and the same bits for every n_streams.
+ * stat_denom and stat_max_radii equal the per-view route exactly, stat_grad_accum up to float rounding (the sum over the step's
+ * views is formed first, then added).
  * (The positional lr_views_* entry points of library versions up to 0.5, one family per mode, are gone.)
  */
 #define LR_VIEWS_LOSS        1u   /* slot holds the colour-loss workspace and dL/dcolor image   */
@@ -422,6 +439,11 @@ typedef struct lr_views_args {
     float* acc_sh;
     float* acc_scale;
     float* acc_rot;
+    /* densification statistics (see above): all three or none; accumulated into */
+    float* stat_grad_accum;                  /* [P] (a [P,1] tensor as is) */
+    float* stat_denom;                       /* [P] */
+    float* stat_max_radii;                   /* [P] */
+    int    stat_absgrad;                     /* 0: norm of the signed per-view gradient; != 0: of the absolute one */
     /* workspace (lr_views_workspace_bytes for the same P, width, height, binning_capacity, n_streams and the step's parts),
      * number of chains (clamped to 1..4) and the caller's HIP stream */
     char* workspace;

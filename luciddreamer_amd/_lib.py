@@ -66,6 +66,8 @@ class ViewsArgs(ctypes.Structure):
                 # the accumulators
                 ("acc_mean2D", _vp), ("acc_opacity", _vp), ("acc_color", _vp), ("acc_mean3D", _vp),
                 ("acc_cov3D", _vp), ("acc_sh", _vp), ("acc_scale", _vp), ("acc_rot", _vp),
+                # densification statistics [P]: all three or none; stat_absgrad selects the absolute gradient's norm
+                ("stat_grad_accum", _vp), ("stat_denom", _vp), ("stat_max_radii", _vp), ("stat_absgrad", _ci),
                 ("workspace", _vp), ("workspace_bytes", ctypes.c_size_t), ("binning_capacity", ctypes.c_longlong),
                 ("n_streams", _ci), ("stream", _vp)]
 

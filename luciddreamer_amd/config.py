@@ -175,7 +175,8 @@ def set_absgrad(enabled: bool):
     never set.  densify.add_densification_stats then feeds that tensor instead of .grad to the unchanged statistics kernel.
     Every gradient is what it is with the switch off (up to the rounding of another reduction order).  Summed magnitudes are
     larger than the signed norm: raise the densification threshold (gsplat suggests about 4x: 0.0008 for the usual 0.0002).
-    The multi-view step (ViewBatch, ChunkedViewStep) does not produce it.  INTEGRATION.md 2g."""
+    The multi-view step (ViewBatch, ChunkedViewStep) does not read this switch: its own densify_stats="absgrad" argument makes
+    it accumulate the same statistic per view.  INTEGRATION.md 2g."""
     global _absgrad
     _absgrad = bool(enabled)
 

@@ -496,7 +496,10 @@ void launch_gauss_bwd(const ViewParams& vp, const float* means3D, const float* s
                       float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor,
                       float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot,
                       uint32_t accum_mask, float* acc16, hipStream_t s, bool depth = false, bool antialiasing = false,
-                      float* dL_dmean2D_abs = nullptr);
+                      float* dL_dmean2D_abs = nullptr, float* stat_accum = nullptr, bool stat_abs = false);
+// stat_accum != nullptr [P] (lr_views_accumulate's stat_grad_accum; activated parameters, dL_dmean2D_abs NULL): the k_gauss_bwd_stats
+// kernels, which also accumulate the norm of the view's own dL/dmean2D -- stat_abs: of its absgrad pair, after the absgrad blend
+// backward -- into float 13 of the acc16 row, or without acc16 into stat_accum itself
 // dL_dmean2D_abs != nullptr [P,3]: the k_gauss_bwd_abs kernels, which also sum the slots' two absgrad floats per Gaussian and
 // WRITE {x, y, 0} to the rows of visible Gaussians (never accumulated; the caller zero-fills the tensor)
 // antialiasing: the view's forward ran under lr_set_antialiasing(1) -- the <RAW, AA = true> kernels chain the record's opacity
@@ -506,8 +509,9 @@ void launch_gauss_bwd(const ViewParams& vp, const float* means3D, const float* s
 // depth-mode blend backward) to dL/dmean3D through z = view[2] x + view[6] y + view[10] z + view[14]
 // acc16 [P][16]: per-step interleaved accumulator of the five small gradient rows (gauss_bwd.hip); added to the caller's
 // tensors once per step
+// stat_accum != nullptr [P]: float 13 of the rows (the step's sum of per-view gradient norms) is added to it as well
 void launch_uninterleave_add(int P, const float* acc16, float* mean2D, float* opacity, float* mean3D, float* scale, float* rot,
-                             hipStream_t s);
+                             hipStream_t s, float* stat_accum = nullptr);
 // row surgery of the parameter set (rows.hip)
 size_t select_workspace_bytes(int P);
 int launch_select_rows(int P, const uint8_t* mask, int n_tensors, const void* const* src, void* const* dst,
@@ -516,6 +520,9 @@ void launch_pack_ply(int P, int n_rest, const float* xyz, const float* f_dc, con
                      const float* scaling, const float* rotation, float* out, hipStream_t s);
 void launch_densify_stats(int P, const int* radii, const float* dL_dmean2D, float* accum, float* denom, float* max_radii,
                           hipStream_t s);
+// one view of a multi-view step with statistics: denom += 1 and max_radii = max(max_radii, radii) for radii > 0 -- whether or not
+// the Gaussian owns a tile instance -- unless the view overflowed its binning buffer (hdr->overflow)
+void launch_views_stats_visit(int P, const int* radii, const GeomHeader* hdr, float* denom, float* max_radii, hipStream_t s);
 // one-launch Adam step over several tensors (adam.hip)
 int launch_adam(int n_tensors, float* const* params, const float* const* grads, float* const* exp_avg,
                 float* const* exp_avg_sq, const unsigned long long* numel, const double* lr, double beta1, double beta2,

@@ -122,7 +122,10 @@ __device__ __forceinline__ float row_sum(float v)
 // AA (the view's forward ran anti-aliased, common.h aa_coef): the record's opacity is opacity * coef(a0, b, c0), so g1.y is
 // dL/d(record opacity): dL/dopacity = g coef, and dL/drho = g rec_opacity / (2 rho) above the floor reaches the 2D covariance
 // next to the conic's terms.  rec_opacity: the record's opacity (non-raw: read from the geom buffer by the caller; raw: recomputed).
-template <bool RAW, bool DEPTH = false, bool AA = false>
+// STATS (k_gauss_bwd_stats: lr_views_accumulate with the stat_* members): stat_norm, the norm of THIS view's screen-space gradient
+// (signed or absolute: the caller's choice), is summed as well -- into float 13 of the acc16 row, which travels with the row
+// anyway, or without acc16 straight into stat_accum [P] (the caller's xyz_gradient_accum; views are chained, so no atomics).
+template <bool RAW, bool DEPTH = false, bool AA = false, bool STATS = false>
 __device__ __forceinline__ void
 gauss_backward_one(const int idx, const ViewParams& vp, const float* __restrict__ means3D, const float* __restrict__ scales,
             const float* __restrict__ rotations, const bool have_sh, const V3 dL_ddir,
@@ -130,7 +133,8 @@ gauss_backward_one(const int idx, const ViewParams& vp, const float* __restrict_
             float* __restrict__ dL_dmean2D, float* __restrict__ dL_dconic, float* __restrict__ dL_dopacity,
             float* __restrict__ dL_dcolor, float* __restrict__ dL_dmean3D, float* __restrict__ dL_dcov3D,
             float* __restrict__ dL_dscale, float* __restrict__ dL_drot,
-            uint32_t accum_mask, float* __restrict__ acc16, const float rec_opacity = 0.f)
+            uint32_t accum_mask, float* __restrict__ acc16, const float rec_opacity = 0.f, const float stat_norm = 0.f,
+            float* __restrict__ stat_accum = nullptr)
 {
     const size_t i = (size_t)idx;
     const float* __restrict__ V = vp.view;
@@ -327,9 +331,11 @@ gauss_backward_one(const int idx, const ViewParams& vp, const float* __restrict_
         r1.x += o_m3d[1]; r1.y += o_m3d[2]; r1.z += o_scale[0]; r1.w += o_scale[1];
         r2.x += o_scale[2]; r2.y += o_rot[0]; r2.z += o_rot[1]; r2.w += o_rot[2];
         r3.x += o_rot[3];
+        if constexpr (STATS) r3.y += stat_norm;
         row[0] = r0; row[1] = r1; row[2] = r2; row[3] = r3;
         return;
     }
+    if constexpr (STATS) stat_accum[i] += stat_norm;
     // ---- store (or accumulate) the rows of this visible Gaussian ----
 #define LR_OUT(bit, ptr, val) do { float* p__ = (ptr); *p__ = ((accum_mask >> (bit)) & 1u) ? (*p__ + (val)) : (val); } while (0)
     LR_OUT(ACC_MEAN2D, dL_dmean2D + 3 * i, o_m2d[0]); LR_OUT(ACC_MEAN2D, dL_dmean2D + 3 * i + 1, o_m2d[1]);
@@ -392,8 +398,9 @@ template <bool RAW, bool AA>
 __global__ void __launch_bounds__(GB_THREADS) __attribute__((amdgpu_waves_per_eu(LR_GB_WAVES, 8)))
 k_gauss_bwd(LR_GB_PARAMS)
 {
-    constexpr bool DEPTH = false, ABSG = false;
+    constexpr bool DEPTH = false, ABSG = false, STATS = false;
     constexpr float* dL_dmean2D_abs = nullptr;
+    constexpr float* stat_accum = nullptr;
 #include "gauss_bwd_body.h"
 }
 // depth mode (lr_view_backward with dL_depths and depth_image): its own entry point, so that k_gauss_bwd keeps its instruction stream
@@ -401,8 +408,9 @@ template <bool RAW, bool AA>
 __global__ void __launch_bounds__(GB_THREADS) __attribute__((amdgpu_waves_per_eu(LR_GB_WAVES, 8)))
 k_gauss_bwd_depth(LR_GB_PARAMS)
 {
-    constexpr bool DEPTH = true, ABSG = false;
+    constexpr bool DEPTH = true, ABSG = false, STATS = false;
     constexpr float* dL_dmean2D_abs = nullptr;
+    constexpr float* stat_accum = nullptr;
 #include "gauss_bwd_body.h"
 }
 // absgrad mode (lr_view_backward with dL_dmean2D_abs), with or without the depth term: own entry points again
@@ -410,7 +418,19 @@ template <bool RAW, bool AA, bool DEPTH>
 __global__ void __launch_bounds__(GB_THREADS) __attribute__((amdgpu_waves_per_eu(LR_GB_WAVES, 8)))
 k_gauss_bwd_abs(LR_GB_PARAMS, float* __restrict__ dL_dmean2D_abs)
 {
-    constexpr bool ABSG = true;
+    constexpr bool ABSG = true, STATS = false;
+    constexpr float* stat_accum = nullptr;
+#include "gauss_bwd_body.h"
+}
+// statistics mode (lr_views_accumulate with the stat_* members; activated parameters only, as that step's views are): the norm of
+// the view's own screen-space gradient -- ABSG: of the slots' two absgrad sums, which are then not written anywhere -- joins the
+// accumulation (gauss_backward_one<STATS>).  Own entry points once more: the kernels above keep their instruction streams.
+template <bool AA, bool DEPTH, bool ABSG>
+__global__ void __launch_bounds__(GB_THREADS) __attribute__((amdgpu_waves_per_eu(LR_GB_WAVES, 8)))
+k_gauss_bwd_stats(LR_GB_PARAMS, float* __restrict__ stat_accum)
+{
+    constexpr bool RAW = false, STATS = true;
+    constexpr float* dL_dmean2D_abs = nullptr;
 #include "gauss_bwd_body.h"
 }
 #undef LR_GB_PARAMS
@@ -469,11 +489,30 @@ void launch_gauss_bwd(const ViewParams& vp, const float* means3D, const float* s
                       const char* bin_base, const GeomHeader* hdr,
                       float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor,
                       float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot,
-                      uint32_t accum_mask, float* acc16, hipStream_t s, bool depth, bool antialiasing, float* dL_dmean2D_abs)
+                      uint32_t accum_mask, float* acc16, hipStream_t s, bool depth, bool antialiasing, float* dL_dmean2D_abs,
+                      float* stat_accum, bool stat_abs)
 {
     (void)colors_precomp;
     if (vp.P <= 0) return;
     const int groups = std::min((vp.P + GB_THREADS - 1) / GB_THREADS, GB_MAX_GROUPS);
+    if (stat_accum != nullptr) {
+#define LR_GBS(AA_, DEPTH_, ABSG_) hipLaunchKernelGGL((k_gauss_bwd_stats<AA_, DEPTH_, ABSG_>), dim3(groups), dim3(GB_THREADS), 0, s, vp, \
+                               means3D, scales, rotations, shs, cov3D_precomp, vis_list, clamped, offsets, bin_base, hdr, dL_dmean2D,  \
+                               dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, accum_mask, acc16, \
+                               stat_accum)
+        switch ((antialiasing ? 1 : 0) | (depth ? 2 : 0) | (stat_abs ? 4 : 0)) {
+            case 0: LR_GBS(false, false, false); break;
+            case 1: LR_GBS(true, false, false); break;
+            case 2: LR_GBS(false, true, false); break;
+            case 3: LR_GBS(true, true, false); break;
+            case 4: LR_GBS(false, false, true); break;
+            case 5: LR_GBS(true, false, true); break;
+            case 6: LR_GBS(false, true, true); break;
+            default: LR_GBS(true, true, true); break;
+        }
+#undef LR_GBS
+        return;
+    }
     if (dL_dmean2D_abs != nullptr) {
 #define LR_GBA(RAW_, AA_, DEPTH_) hipLaunchKernelGGL((k_gauss_bwd_abs<RAW_, AA_, DEPTH_>), dim3(groups), dim3(GB_THREADS), 0, s, vp,   \
                                means3D, scales, rotations, shs, cov3D_precomp, vis_list, clamped, offsets, bin_base, hdr, dL_dmean2D,  \
@@ -510,19 +549,23 @@ void launch_gauss_bwd(const ViewParams& vp, const float* means3D, const float* s
 
 namespace {
 // acc16 [P][16] -> the caller's accumulators (lr_views_accumulate, once per step): rows that no view touched are all
-// zero and are skipped (nothing read or written on the caller's side)
+// zero and are skipped (nothing read or written on the caller's side).  STATS: float 13 of the row, the step's sum of per-view
+// gradient norms (gauss_backward_one<STATS>), goes to stat_accum [P] with them.
+template <bool STATS>
 __global__ void __launch_bounds__(256)
 k_uninterleave_add(int P, const float* __restrict__ acc16, float* __restrict__ mean2D, float* __restrict__ opacity,
-                   float* __restrict__ mean3D, float* __restrict__ scale, float* __restrict__ rot)
+                   float* __restrict__ mean3D, float* __restrict__ scale, float* __restrict__ rot, float* __restrict__ stat_accum)
 {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= P) return;
     const float4* row = reinterpret_cast<const float4*>(acc16 + 16 * (size_t)i);
     const float4 r0 = row[0], r1 = row[1], r2 = row[2], r3 = row[3];
     const bool any = r0.x != 0.f || r0.y != 0.f || r0.z != 0.f || r0.w != 0.f || r1.x != 0.f || r1.y != 0.f || r1.z != 0.f ||
-                     r1.w != 0.f || r2.x != 0.f || r2.y != 0.f || r2.z != 0.f || r2.w != 0.f || r3.x != 0.f;
+                     r1.w != 0.f || r2.x != 0.f || r2.y != 0.f || r2.z != 0.f || r2.w != 0.f || r3.x != 0.f ||
+                     (STATS && r3.y != 0.f);
     if (!any) return;
     const size_t k = (size_t)i;
+    if constexpr (STATS) stat_accum[k] += r3.y;
     mean2D[3 * k] += r0.x; mean2D[3 * k + 1] += r0.y;
     opacity[k] += r0.z;
     mean3D[3 * k] += r0.w; mean3D[3 * k + 1] += r1.x; mean3D[3 * k + 2] += r1.y;
@@ -537,10 +580,15 @@ k_uninterleave_add(int P, const float* __restrict__ acc16, float* __restrict__ m
 }  // namespace
 
 void launch_uninterleave_add(int P, const float* acc16, float* mean2D, float* opacity, float* mean3D, float* scale, float* rot,
-                             hipStream_t s)
+                             hipStream_t s, float* stat_accum)
 {
     if (P <= 0) return;
-    hipLaunchKernelGGL(k_uninterleave_add, dim3((P + 255) / 256), dim3(256), 0, s, P, acc16, mean2D, opacity, mean3D, scale, rot);
+    if (stat_accum != nullptr)
+        hipLaunchKernelGGL(k_uninterleave_add<true>, dim3((P + 255) / 256), dim3(256), 0, s, P, acc16, mean2D, opacity, mean3D, scale,
+                           rot, stat_accum);
+    else
+        hipLaunchKernelGGL(k_uninterleave_add<false>, dim3((P + 255) / 256), dim3(256), 0, s, P, acc16, mean2D, opacity, mean3D, scale,
+                           rot, stat_accum);
 }
 
 }  // namespace lr

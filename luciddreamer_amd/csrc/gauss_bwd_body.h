@@ -5,6 +5,8 @@
 // ABSG (k_gauss_bwd_abs; constexpr bool, with `dL_dmean2D_abs` in scope): the slots' two absgrad floats (g2.z, g2.w: the blend
 // backward's sums of |per-pixel dL/dmean2D|) are summed too and written -- never accumulated -- to dL_dmean2D_abs [P,3] as {x, y, 0}.
 // AA && !RAW: the record's opacity (opacity * coef, what the blend saw) is read from the geom buffer, whose first bytes are `hdr`.
+// STATS (k_gauss_bwd_stats; constexpr bool, with `stat_accum` in scope): the norm of the view's own dL/dmean2D -- with ABSG of the two
+// absgrad sums instead, which are then NOT written to dL_dmean2D_abs -- is handed to gauss_backward_one<STATS>, which accumulates it.
 // NOT a stand-alone header (no include guard on purpose).
     constexpr uint32_t SERIAL_MAX = 24;      // instances summed by the owning lane; more -> whole wave helps
     constexpr int BST = 17;                  // LDS row stride (floats) of the per-Gaussian basis rows: odd -> no conflicts
@@ -167,11 +169,13 @@
             }
             if (live) dL_ddir = { s_ddir[0][lane], s_ddir[1][lane], s_ddir[2][lane] };
         }
+        float stat_norm = 0.f;
+        if constexpr (STATS) stat_norm = ABSG ? sqrtf(g2.z * g2.z + g2.w * g2.w) : sqrtf(g0.x * g0.x + g0.y * g0.y);
         if (live)
-            gauss_backward_one<RAW, DEPTH, AA>(idx, vp, means3D, scales, rotations, have_sh, dL_ddir, cov3D_precomp, g0, g1, g2,
+            gauss_backward_one<RAW, DEPTH, AA, STATS>(idx, vp, means3D, scales, rotations, have_sh, dL_ddir, cov3D_precomp, g0, g1, g2,
                                dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dscale,
-                               dL_drot, accum_mask, acc16, rec_opacity);
-        if constexpr (ABSG) {
+                               dL_drot, accum_mask, acc16, rec_opacity, stat_norm, stat_accum);
+        if constexpr (ABSG && !STATS) {
             if (live) {
                 float* __restrict__ pa = dL_dmean2D_abs + 3 * (size_t)idx;
                 pa[0] = g2.z; pa[1] = g2.w; pa[2] = 0.f;

@@ -162,7 +162,31 @@ k_densify_stats(int P, const int* __restrict__ radii, const float* __restrict__ 
     denom[i] += 1.0f;
 }
 
+// The visit half of the same statistics for one view of a multi-view step (lr_views_accumulate with the stat_* members): the
+// gradient-norm half is accumulated by the per-Gaussian backward, which only walks the Gaussians that own a tile instance; the
+// rule here is radii > 0, which a Gaussian can satisfy without owning one (tiles are culled exactly).  4 bytes read per
+// Gaussian, two read-modify-writes per visible one.  A view that overflowed its binning buffer contributes nothing, as in its backward.
+__global__ void __launch_bounds__(RS_THREADS)
+k_views_stats_visit(int P, const int* __restrict__ radii, const GeomHeader* __restrict__ hdr, float* __restrict__ denom,
+                    float* __restrict__ max_radii)
+{
+    if (hdr->overflow != 0u) return;
+    const int i = blockIdx.x * RS_THREADS + threadIdx.x;
+    if (i >= P) return;
+    const int r = radii[i];
+    if (r <= 0) return;
+    max_radii[i] = fmaxf(max_radii[i], (float)r);
+    denom[i] += 1.0f;
+}
+
 }  // namespace
+
+void launch_views_stats_visit(int P, const int* radii, const GeomHeader* hdr, float* denom, float* max_radii, hipStream_t s)
+{
+    if (P <= 0) return;
+    hipLaunchKernelGGL(k_views_stats_visit, dim3((P + RS_THREADS - 1) / RS_THREADS), dim3(RS_THREADS), 0, s, P, radii, hdr, denom,
+                       max_radii);
+}
 
 void launch_densify_stats(int P, const int* radii, const float* dL_dmean2D, float* accum, float* denom, float* max_radii,
                           hipStream_t s)

@@ -233,7 +233,8 @@ def add_densification_stats(model, viewspace_point_tensor, radii):
         if g is None:
             raise RuntimeError("add_densification_stats: config.set_absgrad(True) is on but the viewspace tensor carries no "
                                ".absgrad -- it is attached by the backward of a view rendered with the switch on (render / "
-                               "render_raw / GaussianRasterizer); the multi-view step does not produce it")
+                               "render_raw / GaussianRasterizer); the multi-view step accumulates its norm itself "
+                               "(parallel.ViewBatch(densify_stats=\"absgrad\"))")
     P = int(radii.shape[0])
     ok = lambda t, n: t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n
     if g is None or not (ok(g, 3 * P) and ok(model.xyz_gradient_accum, P) and ok(model.denom, P) and ok(model.max_radii2D, P)) \
@@ -246,6 +247,24 @@ def add_densification_stats(model, viewspace_point_tensor, radii):
                                 model.max_radii2D.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
     if rc < 0:
         _lib.raise_for(rc, "lr_densify_stats")
+
+
+def view_batch_stats(model):
+    """The model's three statistics as parallel.ViewBatch.run(stats=...) takes them ({"xyz_gradient_accum", "denom",
+    "max_radii2D"}): the step accumulates into the tensors the model holds -- views of its row store once one is bound, and
+    otherwise adopted by the store at the next densify / prune (_sync_stats_into_store), so densify_and_prune sees the step's
+    statistics either way.  A model whose statistics are missing, have another row count or are not float32 gets fresh zero
+    tensors of the reference's shapes ([P,1], [P,1], [P]) first."""
+    P, dev = int(model._xyz.shape[0]), model._xyz.device
+    out = {}
+    for a in STAT_ATTRS:
+        t = getattr(model, a, None)
+        if not (isinstance(t, torch.Tensor) and t.shape[0] == P and t.numel() == P and t.dtype == torch.float32 and
+                t.device == dev and t.is_contiguous()):
+            t = torch.zeros((P,) if a == "max_radii2D" else (P, 1), dtype=torch.float32, device=dev)
+            setattr(model, a, t)
+        out[a] = t
+    return out
 
 
 def _no_fused_step_pending(model):

@@ -417,9 +417,9 @@ class ChunkedViewStep:
     ORDER = ("means3D", "scales", "rotations", "opacity", "sh")
 
     def __init__(self, cams, grad_colors, named_params, sh_degree, bg, binning_capacity, n_streams=2, chunks=None,
-                 targets=None, lambda_dssim=0.2, grads: Optional[FlatGrads] = None):
+                 targets=None, lambda_dssim=0.2, grads: Optional[FlatGrads] = None, densify_stats: Optional[str] = None):
         """grads: a bucket built by the caller over the parameters in ORDER (ShardedAdam.make_buckets pads it for the
-        reduce-scatter); default: a fresh FlatGrads."""
+        reduce-scatter); default: a fresh FlatGrads.  densify_stats: ViewBatch's, for every group; run() then takes stats=."""
         self.named = {k: named_params[k] for k in self.ORDER}
         self.grads = grads if grads is not None else FlatGrads([self.named[k] for k in self.ORDER])
         n = len(cams)
@@ -432,25 +432,29 @@ class ChunkedViewStep:
             sl = slice(bounds[i], bounds[i + 1])
             self.batches.append(ViewBatch(cams[sl], None if grad_colors is None else grad_colors[sl], sh_degree, bg,
                                           binning_capacity, n_streams=n_streams,
-                                          targets=None if targets is None else targets[sl], lambda_dssim=lambda_dssim))
+                                          targets=None if targets is None else targets[sl], lambda_dssim=lambda_dssim,
+                                          densify_stats=densify_stats))
 
     def _acc(self, bucket, means2D_acc):
         d = {k: v for k, v in zip(self.ORDER, bucket.views)}
         d["means2D"] = means2D_acc
         return d
 
-    def run(self, means2D_acc, reduce: bool = True):
+    def run(self, means2D_acc, reduce: bool = True, stats: Optional[dict] = None):
         """Zeroes the buckets, renders every group forward+backward into its bucket, all-reduces (overlapped) and leaves
         the sum over all ranks and views in self.grads (the parameters' .grad).  means2D_acc [P,3] accumulates the
         screen-space gradients of THIS rank's views (densification statistics are reduced separately).
         reduce=False: no collective here -- self.grads holds THIS rank's sum and the exchange is the optimizer's
-        (ShardedAdam: reduce-scatter, sharded Adam, all-gather)."""
+        (ShardedAdam: reduce-scatter, sharded Adam, all-gather).
+        stats (with densify_stats): ViewBatch.run's, accumulated into by THIS rank's views (all_reduce_densification_stats
+        exchanges them)."""
         p = self.named
         works = []
         for b in self.buckets:
             b.zero_()
         for batch, bucket in zip(self.batches, self.buckets):
-            batch.run(p["means3D"], p["opacity"], p["scales"], p["rotations"], p["sh"], self._acc(bucket, means2D_acc))
+            batch.run(p["means3D"], p["opacity"], p["scales"], p["rotations"], p["sh"], self._acc(bucket, means2D_acc),
+                      stats=stats)
             if world_size() > 1 and reduce:
                 works.append(dist.all_reduce(bucket.flat, op=dist.ReduceOp.SUM, async_op=True))
         for w in works:
@@ -865,7 +869,8 @@ class ViewBatch:
                  depth_targets: Optional[Sequence[torch.Tensor]] = None, depth_weight: Optional[float] = None,
                  depths: Optional[Sequence[torch.Tensor]] = None,
                  grad_alphas: Optional[Sequence[torch.Tensor]] = None, masks: Optional[Sequence[torch.Tensor]] = None,
-                 alpha_weight: Optional[float] = None, alphas: Optional[Sequence[torch.Tensor]] = None):
+                 alpha_weight: Optional[float] = None, alphas: Optional[Sequence[torch.Tensor]] = None,
+                 densify_stats: Optional[str] = None):
         """grad_colors: fixed upstream gradients dL/dcolor per view, OR targets: ground-truth images per view, in which
         case every view's L1 + DSSIM loss against its target is formed inside the call (lr_views_accumulate with targets) and
         `self.losses` ([n,3] device tensor: loss, l1, ssim per view) is filled by run().
@@ -888,6 +893,13 @@ class ViewBatch:
             step without it.
           alphas: per-view [1,H,W] or [H,W] contiguous float32 device tensors that run() fills with A (with grad_alphas or
             masks only).
+        Densification statistics (the argument is the opt-in, config.set_absgrad is not read):
+          densify_stats "grad" or "absgrad": run() then takes stats = {"xyz_gradient_accum", "denom", "max_radii2D"} (contiguous
+            float32 device tensors with P rows, e.g. densify.view_batch_stats(model)) and leaves them as if
+            densify.add_densification_stats had run after every view of the step with that view's own screen-space gradient
+            ("absgrad": its absolute one, AbsGS) and radii: the norm per view, then the sum -- which `acc["means2D"]`, the signed
+            sum over the views, cannot give.  "grad" leaves the step's gradients bit for bit; "absgrad" runs every view's blend
+            backward in the absgrad kernel shape (gradients equal up to the rounding of the reduction order).
         Arguments are checked before any device work."""
         import ctypes
         import math
@@ -897,6 +909,9 @@ class ViewBatch:
             raise ValueError("give exactly one of grad_colors / targets")
         if self.n == 0 or self.n != len(grad_colors if targets is None else targets):
             raise ValueError("one grad_colors / targets entry per camera, and at least one camera")
+        if densify_stats not in (None, "grad", "absgrad"):
+            raise ValueError(f'densify_stats must be None, "grad" or "absgrad", got {densify_stats!r}')
+        self.densify_stats = densify_stats
         self.W, self.H = int(self.cams[0].image_width), int(self.cams[0].image_height)
         self._check_optional_args(grad_colors, targets, grad_depths, depth_targets, depth_weight, depths, grad_alphas, masks,
                                   alpha_weight, alphas)
@@ -943,7 +958,8 @@ class ViewBatch:
             depth_targets=inputs(depth_targets), depth_weight=1.0 if depth_weight is None else float(depth_weight),
             masks=inputs(masks), alpha_weight=1.0 if alpha_weight is None else float(alpha_weight),
             out_losses=self.losses.data_ptr() if self.train else None,
-            out_depth=outputs(self.depths), out_alpha=outputs(self.alphas), binning_capacity=self.capacity)
+            out_depth=outputs(self.depths), out_alpha=outputs(self.alphas), binning_capacity=self.capacity,
+            stat_absgrad=1 if densify_stats == "absgrad" else 0)
         self._ws = None
         self._ws_key = None
 
@@ -1011,10 +1027,33 @@ class ViewBatch:
         """Drop the workspace (the next run() allocates one); check() has nothing to look at until then."""
         self._ws = self._ws_key = None
 
-    def run(self, means3D, opacities, scales, rotations, shs, acc: dict):
+    STAT_KEYS = ("xyz_gradient_accum", "denom", "max_radii2D")
+
+    def _check_stats(self, stats, P):
+        if stats is None:
+            if self.densify_stats is not None:
+                raise ValueError(f'ViewBatch(densify_stats="{self.densify_stats}"): run() needs stats= (densify.view_batch_stats)')
+            return
+        if self.densify_stats is None:
+            raise ValueError('run(stats=...) needs ViewBatch(densify_stats="grad" or "absgrad")')
+        if not isinstance(stats, dict) or set(stats) != set(self.STAT_KEYS):
+            raise ValueError(f"stats: a dict with exactly the keys {self.STAT_KEYS}")
+        for k in self.STAT_KEYS:
+            t = stats[k]
+            if not (isinstance(t, torch.Tensor) and t.dtype is torch.float32 and t.is_contiguous() and t.dim() in (1, 2) and
+                    t.shape[0] == P and t.numel() == P):
+                raise ValueError(f"stats[{k!r}]: a contiguous float32 tensor of shape [{P}] or [{P},1], got "
+                                 f"{(tuple(t.shape), t.dtype) if isinstance(t, torch.Tensor) else type(t).__name__}")
+            if not t.is_cuda:
+                raise ValueError(f"stats[{k!r}] must be on the HIP device")
+
+    def run(self, means3D, opacities, scales, rotations, shs, acc: dict, stats: Optional[dict] = None):
         """acc: {"means3D", "means2D", "opacity", "sh", "scales", "rotations"} -> contiguous float32 tensors that are
-        accumulated into (e.g. the .grad views of a FlatGrads bucket)."""
+        accumulated into (e.g. the .grad views of a FlatGrads bucket).
+        stats (with densify_stats, and only then): {"xyz_gradient_accum", "denom", "max_radii2D"} -> contiguous float32 device
+        tensors with P rows, accumulated into by every view of the step (see __init__)."""
         P = int(means3D.shape[0])
+        self._check_stats(stats, P)
         key = (P, self.capacity, self.n_streams)      # the workspace is sized per stream slot: set_streams() re-allocates
         if self._ws_key != key:
             self._ws = torch.empty((self.workspace_bytes(P),), dtype=torch.uint8, device=self.device)
@@ -1028,6 +1067,9 @@ class ViewBatch:
         a.scales, a.rotations = scales.data_ptr(), rotations.data_ptr()
         a.acc_mean2D, a.acc_opacity, a.acc_mean3D = acc["means2D"].data_ptr(), acc["opacity"].data_ptr(), acc["means3D"].data_ptr()
         a.acc_sh, a.acc_scale, a.acc_rot = acc["sh"].data_ptr(), acc["scales"].data_ptr(), acc["rotations"].data_ptr()
+        if stats is not None:
+            a.stat_grad_accum, a.stat_denom = stats["xyz_gradient_accum"].data_ptr(), stats["denom"].data_ptr()
+            a.stat_max_radii = stats["max_radii2D"].data_ptr()
         a.workspace, a.workspace_bytes, a.n_streams = self._ws.data_ptr(), self._ws.numel(), self.n_streams
         a.stream = torch.cuda.current_stream(self.device).cuda_stream
         with torch.cuda.device(self.device):
