@@ -424,7 +424,8 @@ typedef struct lr_views_args {
     float alpha_weight;
     float* out_losses;
     /* optional per-view outputs, fully written: colour [3,H,W], depth [H,W], alpha A = 1 - T_final [H,W] (lr_render_alpha's
-     * values), radii [P]; NULL entries or arrays: not returned */
+     * values), radii [P]; NULL entries or arrays: not returned (a view whose depth is neither returned nor read by the step --
+     * depth_targets, dL_ddepth -- is blended without the depth channel: same colour, alpha, radii and gradients to the bit) */
     float* const* out_color;
     float* const* out_depth;
     float* const* out_alpha;

@@ -460,6 +460,7 @@ void launch_render_fwd(int W, int H, int gx, int gy, const uint2* ranges, const 
                        uint32_t* n_contrib, float* out_color, float* out_depth, uint8_t* quad_hits,
                        GeomHeader* hdr, uint2* seg_list, float4* ckpt, uint32_t* tile_seg0, float4* c_final,
                        long long inst_hint, hipStream_t s);
+// out_depth == nullptr: the depth-free kernels (no depth channel in the per-pixel state, no depth image); everything else to the bit
 // alpha [n] = 1 - final_T [n]: the accumulated opacity of the forward that left final_T (lr_render_alpha)
 void launch_render_alpha(const float* final_T, long long n, float* alpha, hipStream_t s);
 // seg_bound: upper bound of GeomHeader::n_seg known to the host (bin_seg_capacity of the instance bound of the call)

@@ -42,13 +42,21 @@ constexpr int BATCH = 256;          // staged Gaussians per round = threads per 
 // the list length for a pixel that never stopped.  The positions between the reference's value and this one hold only
 // Gaussians this pixel skipped (alpha < 1/255 or power > 0), which the backward skips again by the same test on the same
 // arithmetic, so the gradients are identical -- and the common step loses the two instructions that tracked it.
-struct PixState { float T, Cr, Cg, Cb, D, acc; uint32_t last; };
+// DEPTH = false (launch_render_fwd without out_depth: a view whose depth image nobody reads): no D and acc, and the two
+// instructions per step that carried them are gone; every other field goes through the same operations.
+template <bool DEPTH> struct PixState { float T, Cr, Cg, Cb, D, acc; uint32_t last; };
+template <> struct PixState<false> { float T, Cr, Cg, Cb; uint32_t last; };
+template <bool DEPTH> __device__ __forceinline__ PixState<DEPTH> pix_start()
+{
+    if constexpr (DEPTH) return PixState<true>{ 1.0f, 0.f, 0.f, 0.f, 0.f, 0.000001f, 0u };
+    else return PixState<false>{ 1.0f, 0.f, 0.f, 0.f, 0u };
+}
 
 // One candidate for the 64 pixels of the wave.  The per-pixel predicates live in wave-uniform 64-bit lane masks
 // (v_cmp writes them to an SGPR pair; they are combined on the scalar unit and fed back to v_cndmask through
 // inverse_ballot at no VALU cost); `done` is the mask of finished pixels.
-template <bool STRICT>
-__device__ __forceinline__ void fwd_pixel(PixState& p, uint64_t& done, const float qA, const float qB, const float qC,
+template <bool STRICT, bool DEPTH>
+__device__ __forceinline__ void fwd_pixel(PixState<DEPTH>& p, uint64_t& done, const float qA, const float qB, const float qC,
                                           const float r0, const float r1,
                                           const float dx, const float op, const float cr, const float cg, const float cb,
                                           const float depth, const uint32_t pos0)
@@ -64,7 +72,8 @@ __device__ __forceinline__ void fwd_pixel(PixState& p, uint64_t& done, const flo
     const bool use = __builtin_amdgcn_inverse_ballot_w64(pass & ~low_T);
     done |= stop;
     const float wgt = use ? alpha * p.T : 0.f;
-    p.Cr += cr * wgt; p.Cg += cg * wgt; p.Cb += cb * wgt; p.D += depth * wgt; p.acc += wgt;
+    p.Cr += cr * wgt; p.Cg += cg * wgt; p.Cb += cb * wgt;
+    if constexpr (DEPTH) { p.D += depth * wgt; p.acc += wgt; }
     p.T = use ? test_T : p.T;
     if (stop != 0ull) {                                                 // rare: a pixel stops at most once
         asm volatile("");                                               // keep it a scalar branch (no selects in the common path)
@@ -75,7 +84,8 @@ __device__ __forceinline__ void fwd_pixel(PixState& p, uint64_t& done, const flo
 // The same step with the candidate's alpha already formed, and branch-free: for the PAIR loop below, where two candidates'
 // alphas are evaluated side by side and only these few dependent instructions per candidate remain in sequence.  `enable`:
 // all ones, or zero for the second half of an odd pair (the step is then the identity).
-__device__ __forceinline__ void fwd_step(PixState& p, uint64_t& done, const float alpha, const float power, const uint64_t enable,
+template <bool DEPTH>
+__device__ __forceinline__ void fwd_step(PixState<DEPTH>& p, uint64_t& done, const float alpha, const float power, const uint64_t enable,
                                          const float cr, const float cg, const float cb, const float depth, const uint32_t pos0)
 {
     const float test_T = p.T * (1.0f - alpha);
@@ -85,7 +95,8 @@ __device__ __forceinline__ void fwd_step(PixState& p, uint64_t& done, const floa
     const bool use = __builtin_amdgcn_inverse_ballot_w64(pass & ~low_T);
     done |= stop;
     const float wgt = use ? alpha * p.T : 0.f;
-    p.Cr += cr * wgt; p.Cg += cg * wgt; p.Cb += cb * wgt; p.D += depth * wgt; p.acc += wgt;
+    p.Cr += cr * wgt; p.Cg += cg * wgt; p.Cb += cb * wgt;
+    if constexpr (DEPTH) { p.D += depth * wgt; p.acc += wgt; }
     p.T = use ? test_T : p.T;
     p.last = __builtin_amdgcn_inverse_ballot_w64(stop) ? pos0 : p.last;
 }
@@ -96,7 +107,7 @@ __device__ __forceinline__ void fwd_step(PixState& p, uint64_t& done, const floa
 // Same operations per pixel and candidate in the same order: bit-identical images.  Per tile: only lists of PAIR_MIN_LIST and more
 // (measured, forward alone: dense 512^2, 1 700 per tile, 180 -> 173 us; one layer of pixel-sized splats, 320 per tile, 53.7 -> 55.1).
 constexpr int PAIR_MIN_LIST = 1024;
-template <bool STRICT, bool PAIR>
+template <bool STRICT, bool PAIR, bool DEPTH>
 __global__ void __launch_bounds__(THREADS)
 k_render_fwd(int W, int H, int gx, int num_tiles, int tile_map, const uint2* __restrict__ ranges,
              const uint32_t* __restrict__ point_list, const uint32_t* __restrict__ list_gid,
@@ -126,7 +137,7 @@ k_render_fwd(int W, int H, int gx, int num_tiles, int tile_map, const uint2* __r
     const uint2 range = ranges[tile];
     const int total = (int)(range.y - range.x);
 
-    PixState A = { 1.0f, 0.f, 0.f, 0.f, 0.f, 0.000001f, 0u };
+    PixState<DEPTH> A = pix_start<DEPTH>();
     uint64_t done = __builtin_amdgcn_ballot_w64(!inside);             // lane mask of finished pixels (all 64 lanes are live)
     bool wave_done = done == ~0ull;
 
@@ -223,7 +234,7 @@ k_render_fwd(int W, int H, int gx, int num_tiles, int tile_map, const uint2* __r
                 const float dy = a.y - pyf;
                 float r0, r1;
                 gauss_row<STRICT>(a.w, b.x, dy, r0, r1);                                        // common.h gauss_power
-                fwd_pixel<STRICT>(A, done, a.z, a.w, b.x, r0, r1, a.x - pxf, b.y, c.x, c.y, c.z, b.z, pos0);
+                fwd_pixel<STRICT, DEPTH>(A, done, a.z, a.w, b.x, r0, r1, a.x - pxf, b.y, c.x, c.y, c.z, b.z, pos0);
             }
             if (done == ~0ull) { wave_done = true; break; }             // all 64 pixels are finished
         }
@@ -241,7 +252,7 @@ k_render_fwd(int W, int H, int gx, int num_tiles, int tile_map, const uint2* __r
         // a segmented tile: the final colour once more, where the backward's later segments find it (they subtract a
         // checkpoint's colour-so-far from it: the colour still to come behind that position, background included)
         if (n_seg > 0) c_final[pix] = make_float4(fr, fg, fb, 0.f);
-        out_depth[pix] = (A.acc > 0.5f) ? A.D / A.acc : 0.0f;         // forward.cu:384-388
+        if constexpr (DEPTH) out_depth[pix] = (A.acc > 0.5f) ? A.D / A.acc : 0.0f;         // forward.cu:384-388
     }
 }
 
@@ -263,7 +274,7 @@ k_render_fwd(int W, int H, int gx, int num_tiles, int tile_map, const uint2* __r
 // quadrants at C3); no barriers, no partner waves to wait for, 3 KB of LDS.  Same operations per pixel and candidate in the
 // same order as the quadrant kernel: the same bits (tests/test_gpu_variants.py).
 constexpr int TSTAGE = 64;
-template <bool STRICT>
+template <bool STRICT, bool DEPTH>
 __device__ __forceinline__ void
 render_fwd_tile(int W, int H, int gx, int num_tiles, int tile_map, const uint2* __restrict__ ranges,
                   const uint32_t* __restrict__ point_list, const uint32_t* __restrict__ list_gid,
@@ -288,12 +299,12 @@ render_fwd_tile(int W, int H, int gx, int num_tiles, int tile_map, const uint2* 
     const uint2 range = ranges[tile];
     const int total = (int)(range.y - range.x);
 
-    PixState A[4];
+    PixState<DEPTH> A[4];
     uint64_t done[4];
     bool inside[4];
 #pragma unroll
     for (int q = 0; q < 4; q++) {
-        A[q] = PixState{ 1.0f, 0.f, 0.f, 0.f, 0.f, 0.000001f, 0u };
+        A[q] = pix_start<DEPTH>();
         inside[q] = pxl + (q & 1) * 8 < W && pyt + (q >> 1) * 8 < H;
         done[q] = __builtin_amdgcn_ballot_w64(!inside[q]);
     }
@@ -373,7 +384,7 @@ render_fwd_tile(int W, int H, int gx, int num_tiles, int tile_map, const uint2* 
                 for (int col = 0; col < 2; col++) {
                     const int q = 2 * row + col;
                     if ((m[q] & bit) == 0ull) continue;
-                    fwd_pixel<STRICT>(A[q], done[q], fa.z, fa.w, fb.x, r0, r1, fa.x - pxf[col], fb.y, fc.x, fc.y, fc.z, fb.z, pos0);
+                    fwd_pixel<STRICT, DEPTH>(A[q], done[q], fa.z, fa.w, fb.x, r0, r1, fa.x - pxf[col], fb.y, fc.x, fc.y, fc.z, fb.z, pos0);
                     if (done[q] == ~0ull) {                            // the quadrant is finished: its later candidates are nobody's
                         m[q] = 0ull;
                         mask &= (m[0] | m[1]) | (m[2] | m[3]);
@@ -396,7 +407,7 @@ render_fwd_tile(int W, int H, int gx, int num_tiles, int tile_map, const uint2* 
         out_color[N + pix] = fg;
         out_color[2 * N + pix] = fb;
         if (n_seg > 0) c_final[pix] = make_float4(fr, fg, fb, 0.f);
-        out_depth[pix] = (A[q].acc > 0.5f) ? A[q].D / A[q].acc : 0.0f;         // forward.cu:384-388
+        if constexpr (DEPTH) out_depth[pix] = (A[q].acc > 0.5f) ? A[q].D / A[q].acc : 0.0f;         // forward.cu:384-388
     }
 }
 #define LR_FWD_TILE_PARAMS int W, int H, int gx, int num_tiles, int tile_map, const uint2* __restrict__ ranges,                 \
@@ -412,11 +423,11 @@ render_fwd_tile(int W, int H, int gx, int num_tiles, int tile_map, const uint2* 
 // (round 6; with the compiler's own budget, 66-72 registers and 7 waves per SIMD, the last 992 waves waited for the first 7168:
 // lone view C3 62.3 -> 59.0 us, C2 101 -> 92 us, dense 1080p 366 -> 342 us, three views in flight equal;
 // profiles/r06h_ab_fwdtile8.json).  The quadrant boxes formed per round are what made room (render_fwd_tile).
-template <bool STRICT>
+template <bool STRICT, bool DEPTH>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8), amdgpu_num_vgpr(64)))
 k_render_fwd_tile(LR_FWD_TILE_PARAMS)
 {
-    render_fwd_tile<STRICT>(LR_FWD_TILE_PASS);
+    render_fwd_tile<STRICT, DEPTH>(LR_FWD_TILE_PASS);
 }
 
 }  // namespace
@@ -454,12 +465,17 @@ void launch_render_fwd(int W, int H, int gx, int gy, const uint2* ranges, const 
     note_fwd_shape(tile_shape ? 2 : pair ? 1 : 0);
 #define LR_FWD_ARGS W, H, gx, num_tiles, tile_map, ranges, point_list, list_gid, rec, bg, final_T, n_contrib, out_color, out_depth, \
                     quad_hits, hdr, seg_list, ckpt, tile_seg0, c_final
+    // out_depth == nullptr: the depth-free instantiations (DEPTH = false never touches the pointer)
+    const bool depth = out_depth != nullptr;
     if (tile_shape) {
-        if (strict) hipLaunchKernelGGL((k_render_fwd_tile<true>), dim3(grid), dim3(64), 0, s, LR_FWD_ARGS);
-        else hipLaunchKernelGGL((k_render_fwd_tile<false>), dim3(grid), dim3(64), 0, s, LR_FWD_ARGS);
+#define LR_FWD_TILE(S, DP) hipLaunchKernelGGL((k_render_fwd_tile<S, DP>), dim3(grid), dim3(64), 0, s, LR_FWD_ARGS)
+        if (depth) { if (strict) LR_FWD_TILE(true, true); else LR_FWD_TILE(false, true); }
+        else { if (strict) LR_FWD_TILE(true, false); else LR_FWD_TILE(false, false); }
+#undef LR_FWD_TILE
         return;
     }
-#define LR_FWD(S, PR) hipLaunchKernelGGL((k_render_fwd<S, PR>), dim3(grid), dim3(THREADS), 0, s, LR_FWD_ARGS)
+#define LR_FWD(S, PR) do { if (depth) hipLaunchKernelGGL((k_render_fwd<S, PR, true>), dim3(grid), dim3(THREADS), 0, s, LR_FWD_ARGS); \
+                           else hipLaunchKernelGGL((k_render_fwd<S, PR, false>), dim3(grid), dim3(THREADS), 0, s, LR_FWD_ARGS); } while (0)
 #ifdef LR_DIAGNOSTICS
     if (pair) { if (strict) LR_FWD(true, true); else LR_FWD(false, true); return; }
 #endif
