@@ -7,6 +7,7 @@ piece of this repository on the MI355X:
     densify           densify_and_prune / prune through one row-selection kernel, Adam state intact     8f-4
     FusedAdam         torch.optim.Adam's arithmetic in one launch per step                              (8e: the step after the all-reduce)
     distCUDA2         initial scales from the 3-nearest-neighbour distance                              8f-1
+    MCMCStrategy      --mcmc: relocation, capped growth and position noise instead of densify_and_prune   DESIGN.md 4b-MCMC
 
 Targets are renders of a hidden "ground truth" cloud from a look-around camera path; the trained cloud starts from
 a perturbed subset of it.  Prints the loss every `--log` iterations and the time per iteration.
@@ -14,10 +15,16 @@ a perturbed subset of it.  Prints the loss every `--log` iterations and the time
     python examples/train_loop.py [--gaussians 200000] [--iters 300] [--resolution 512x512]
                                   [--absgrad --densify-grad-threshold 0.0008]
                                   [--multi-view 4 [--absgrad]]
+                                  [--mcmc --cap-max 150000]
 
 --multi-view K: the loop body is ONE multi-view step (parallel.ViewBatch: forward, L1 + DSSIM loss and backward of K views in one
 C call, gradients summed) followed by Adam; the densification statistics are formed inside the step, per view
 (densify_stats="grad", or "absgrad" with --absgrad), and densify_and_prune runs on them.
+
+--mcmc --cap-max N: in either loop the MCMC strategy (luciddreamer_amd.mcmc.MCMCStrategy) takes the place of the densify_and_prune
+calls: the regularisers' gradients are added before the optimizer's step, and after it dead Gaussians are relocated and the set
+grows by 5 % -- never beyond N -- on the --densify-from / --densify-every / --densify-until schedule, with the position noise
+every iteration.  No gradient threshold and no densification statistics are involved.
 """
 import argparse
 import math
@@ -29,7 +36,7 @@ from types import SimpleNamespace
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from luciddreamer_amd import cameras, config, densify, synthetic           # noqa: E402
+from luciddreamer_amd import cameras, config, densify, mcmc, synthetic     # noqa: E402
 from luciddreamer_amd.gaussian_renderer import GaussianCloud, render_raw   # noqa: E402
 from luciddreamer_amd.loss import l1_dssim_loss                            # noqa: E402
 from luciddreamer_amd.optim import FusedAdam                               # noqa: E402
@@ -80,9 +87,20 @@ def build(args, dev):
     shs = torch.zeros(idx.numel(), 16, 3, device=dev)
     shs[:, 0] = gt_cloud["shs"][idx, 0]
     model = TrainableCloud(xyz, scales, rots, torch.full((idx.numel(), 1), 0.1, device=dev), shs)
-    model.training_setup({"xyz": 1.6e-4, "f_dc": 2.5e-3, "f_rest": 2.5e-3 / 20, "opacity": 0.05, "scaling": 5e-3, "rotation": 1e-3},
+    model.training_setup({"xyz": LR_XYZ, "f_dc": 2.5e-3, "f_rest": 2.5e-3 / 20, "opacity": 0.05, "scaling": 5e-3, "rotation": 1e-3},
                          torch_adam=args.torch_adam)
     return model, cams, targets
+
+
+LR_XYZ = 1.6e-4                # the position learning rate of build(): the noise is scaled by it
+
+
+def _mcmc_strategy(args, model):
+    """--mcmc: the strategy on the loop's densification schedule (--cap-max 0: 1.5 x the initial count)."""
+    if not getattr(args, "mcmc", False):
+        return None
+    cap = int(args.cap_max) if int(args.cap_max) > 0 else int(1.5 * model._xyz.shape[0])
+    return mcmc.MCMCStrategy(cap, refine_start=args.densify_from, refine_stop=args.densify_until, refine_every=args.densify_every)
 
 
 def _capacity(model, cams, bg):
@@ -128,11 +146,12 @@ def train_multi_view(args, log=print):
         return batches[key]
     losses = []
     gen = torch.Generator().manual_seed(0)
+    strategy = _mcmc_strategy(args, model)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for it in range(1, args.iters + 1):
         gi = int(torch.randint(0, len(groups), (1,), generator=gen))
-        with_stats = it < args.densify_until
+        with_stats = strategy is None and it < args.densify_until
         batch = batch_for(gi, with_stats)
         # the step takes activated parameters and accumulates their gradients; autograd carries them to the stored ones
         act = {"means3D": model.get_xyz, "opacities": model.get_opacity, "scales": model.get_scaling,
@@ -151,8 +170,12 @@ def train_multi_view(args, log=print):
             if densified:
                 batch.check()                      # an overflowed view would have contributed nothing
                 densify.densify_and_prune(model, args.densify_grad_threshold, 0.005, 5.0, 20)
+            if strategy is not None:
+                strategy.add_regularizer_grads(model)
             model.optimizer.step()
             model.optimizer.zero_grad(set_to_none=True)
+            if strategy is not None:               # relocated Gaussians sit elsewhere, added ones change P
+                densified = any(strategy.step(model, it, LR_XYZ))
             if densified:                          # another P: another capacity, and the batches are rebuilt on it
                 batches, cap = {}, _capacity(model, cams, bg)
         if it % args.log == 0 or it == 1:
@@ -179,6 +202,7 @@ def train(args, log=print):
     config.set_absgrad(args.absgrad)               # AbsGS: the backward attaches viewspace_points.absgrad, the statistics use it
     losses = []
     gen = torch.Generator().manual_seed(0)
+    strategy = _mcmc_strategy(args, model)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for it in range(1, args.iters + 1):
@@ -188,12 +212,16 @@ def train(args, log=print):
         loss.backward()                                                                   # :304
         with torch.no_grad():
             vis, radii = pkg["visibility_filter"], pkg["radii"]
-            if it < args.densify_until:                                                   # :308-318
+            if strategy is not None:
+                strategy.add_regularizer_grads(model)
+            elif it < args.densify_until:                                                 # :308-318
                 densify.add_densification_stats(model, pkg["viewspace_points"], radii)   # :310-311 + stats, one kernel
                 if it >= args.densify_from and it % args.densify_every == 0:
                     densify.densify_and_prune(model, args.densify_grad_threshold, 0.005, 5.0, 20)
             model.optimizer.step()                                                        # :322-324
             model.optimizer.zero_grad(set_to_none=True)
+            if strategy is not None:
+                strategy.step(model, it, LR_XYZ)
         if it % args.log == 0 or it == 1:
             losses.append((it, float(loss.item()), int(model._xyz.shape[0])))
             log(f"iter {it:5d}  loss {losses[-1][1]:.5f}  gaussians {losses[-1][2]}")
@@ -209,12 +237,15 @@ def train(args, log=print):
 def default_args(**kw):
     d = dict(gaussians=200_000, iters=300, resolution="512x512", views=12, lambda_dssim=0.2, log=50, densify_from=100,
              densify_every=100, densify_until=10_000, exact=False, torch_adam=False, antialiasing=False, absgrad=False,
-             densify_grad_threshold=0.0002, multi_view=0)
+             densify_grad_threshold=0.0002, multi_view=0, mcmc=False, cap_max=0)
     d.update(kw)
     return SimpleNamespace(**d)
 
 
 HELP = {
+    "mcmc": "MCMC densification (luciddreamer_amd.mcmc.MCMCStrategy) instead of densify_and_prune: dead Gaussians are relocated, "
+            "the set grows 5 % per refinement up to --cap-max, a position noise follows every step; no gradient threshold",
+    "cap_max": "with --mcmc: the largest number of Gaussians (0: 1.5 x the initial count)",
     "multi_view": "K > 0: one multi-view step of K views per iteration (parallel.ViewBatch with targets) instead of one view; the "
                   "densification statistics come from the step itself (with --absgrad: the absolute gradient's)",
     "absgrad": "densify by the absolute view-space gradient (AbsGS, config.set_absgrad): per-pixel pulls on a Gaussian are summed "

@@ -515,6 +515,65 @@ int lr_adam_step_masked(int n_tensors, float* const* params, const float* const*
                         double beta1, double beta2, double eps, int step, const char* geom_buffer, int P, void* stream);
 
 /*
+ * MCMC densification (Kheradmand et al., "3D Gaussian Splatting as Markov Chain Monte Carlo", 2024): the per-row work of a
+ * strategy with a fixed budget of Gaussians -- dead ones are relocated onto live ones, the set grows by a fixed rate up to a cap,
+ * and a small position noise is added after every optimizer step (luciddreamer_amd/mcmc.py drives it).
+ * All tensors are the STORED GaussianModel parameters: xyz [P,3], features_dc [P,1,3], features_rest [P,M-1,3], logit opacity
+ * [P,1], log scaling [P,3], unnormalised rotation quaternion [P,4] in (r,x,y,z) order; float32, contiguous, device.
+ *
+ *   lr_mcmc_relocate: n pairs (dst[j], src[j]), device int32.  With c[i] the number of j with src[j] == i and
+ *     N_i = min(c[i] + 1, n_max), every source i with c[i] > 0 -- o = sigmoid(opacity[i]) clamped to at most 1 - 2^-24 and
+ *     s = exp(scaling[i]), both the values BEFORE the call -- gets
+ *         o' = 1 - (1 - o)^(1/N_i)                                        (evaluated as -expm1(log1p(-o) / N_i))
+ *         s' = s o / den,  den = sum_{m=1..N_i} sum_{k=0..m-1} C(m-1,k) (-1)^k / sqrt(k+1) o'^(k+1)    (in double)
+ *     and logit(clamp(o', min_opacity, 1 - 1.1920929e-7)) and log(s') are stored in row i and in every dst[j] with src[j] == i;
+ *     each such dst[j] also receives row i's xyz, features_dc, features_rest and rotation unchanged.  Both Adam moments of all
+ *     six tensors (exp_avg / exp_avg_sq, in the order xyz, features_dc, features_rest, opacity, scaling, rotation; a NULL entry
+ *     means there is no such tensor) are set to zero at every touched source row AND every destination row: a destination's
+ *     moments belong to a Gaussian that no longer exists.  Rows that are neither are left bit-identical.  Deterministic: the
+ *     only atomics are integer counts, and the result is bit-repeatable.
+ *     The caller guarantees what the library cannot see without reading the device: {dst} and {src} are disjoint, dst has no
+ *     duplicates (src may repeat), and every index is in [0, P_rows) -- P_rows is the number of rows the tensors can address,
+ *     so for growth dst may lie behind the live rows of a capacity buffer.  Checked on the host (LR_ERR_INVALID_ARG): struct_bytes,
+ *     n >= 0, P_rows >= 1, M >= 1, n_max in [1, 51], the index arrays, the six parameters (features_rest only for M > 1) and
+ *     a workspace of lr_mcmc_workspace_bytes(P_rows, n) bytes.  n == 0 succeeds and launches nothing.  No host synchronisation.
+ *   lr_mcmc_noise: xyz[i] += Sigma_i xi_i g(o_i) scaler, Sigma = R diag(s^2) R^T with R the rotation of the normalised
+ *     quaternion (the covariance the preprocess builds, no scale modifier), xi = noise [P,3] standard-normal draws and
+ *     g(o) = 1 / (1 + exp(-100 ((1 - o) - 0.995))), which leaves all but nearly transparent Gaussians where they are.
+ *     56 bytes read and 12 written per Gaussian.
+ *   lr_mcmc_reg_grad: adds the gradient of opacity_reg * mean(sigmoid(opacity)) + scale_reg * mean(exp(scaling)) to existing
+ *     gradient buffers: dL_dopacity[i] += opacity_reg / P * o (1 - o), dL_dscale[i,c] += scale_reg / (3 P) * exp(scaling[i,c]).
+ */
+typedef struct lr_mcmc_relocate_args {
+    size_t struct_bytes;                     /* = sizeof(lr_mcmc_relocate_args); anything else is LR_ERR_INVALID_ARG */
+    int n;                                   /* number of pairs */
+    const int* dst;                          /* [n] device: rows that are overwritten */
+    const int* src;                          /* [n] device: rows they become copies of */
+    int P_rows;                              /* rows the tensors can address (every index is below it) */
+    int M;                                   /* SH coefficients per Gaussian: features_rest has M - 1 rows of three */
+    float* xyz;
+    float* features_dc;
+    float* features_rest;                    /* NULL when M == 1 */
+    float* opacity;
+    float* scaling;
+    float* rotation;
+    float* exp_avg[6];                       /* xyz, features_dc, features_rest, opacity, scaling, rotation; NULL = none */
+    float* exp_avg_sq[6];
+    float min_opacity;                       /* lower clamp of the new opacities */
+    int n_max;                               /* cap of N_i, 1..51 (51: the published implementations' table size) */
+    void* workspace;                         /* lr_mcmc_workspace_bytes(P_rows, n) device bytes, 256-byte aligned */
+    size_t workspace_bytes;
+    void* stream;
+} lr_mcmc_relocate_args;
+
+int lr_mcmc_relocate(const lr_mcmc_relocate_args* a);
+size_t lr_mcmc_workspace_bytes(int P_rows, int n);
+int lr_mcmc_noise(int P, float* xyz, const float* raw_scale, const float* raw_rotation, const float* raw_opacity,
+                  const float* noise, float scaler, void* stream);
+int lr_mcmc_reg_grad(int P, const float* raw_opacity, const float* raw_scale, float opacity_reg, float scale_reg,
+                     float* dL_dopacity, float* dL_dscale, void* stream);
+
+/*
  * Fused photometric loss of the training loop:
  *     loss = (1 - lambda) * mean|image - gt| + lambda * (1 - mean(SSIM_map(image, gt)))
  * replacing l1_loss + ssim of R/utils/loss.py:18-69 as composed in R/luciddreamer.py:301-304 (11x11 window = outer

@@ -11,3 +11,11 @@ def install(*args, **kwargs):
 def uninstall(handle):
     from .dropin import uninstall as _uninstall
     return _uninstall(handle)
+
+
+def __getattr__(name):
+    """`luciddreamer_amd.mcmc` (MCMCStrategy: relocation, capped growth, position noise) without importing torch with the package."""
+    if name == "mcmc":
+        import importlib
+        return importlib.import_module(".mcmc", __name__)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

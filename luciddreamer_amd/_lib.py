@@ -38,7 +38,8 @@ EXPORTS = ("lr_last_error", "lr_version", "lr_geom_bytes", "lr_img_bytes", "lr_b
            "lr_depth_l1_workspace_bytes", "lr_depth_l1_forward", "lr_depth_l1_backward",
            "lr_video_workspace_bytes", "lr_frames_to_u8", "lr_depth_colorize",
            "lr_masked_l1_dssim_forward", "lr_masked_l1_dssim_backward", "lr_alpha_hole_workspace_bytes", "lr_alpha_hole_forward",
-           "lr_alpha_hole_backward", "lr_set_antialiasing", "lr_get_antialiasing")
+           "lr_alpha_hole_backward", "lr_set_antialiasing", "lr_get_antialiasing",
+           "lr_mcmc_workspace_bytes", "lr_mcmc_relocate", "lr_mcmc_noise", "lr_mcmc_reg_grad")
 
 # lr_views_workspace_bytes / lr_views_check `parts`: what a step's workspace slots hold besides a view's scratch
 LR_VIEWS_LOSS, LR_VIEWS_DEPTH_LOSS, LR_VIEWS_MASK_LOSS = 1, 2, 4
@@ -111,6 +112,19 @@ class BackwardArgs(ctypes.Structure):
 
     def __init__(self, **fields):
         super().__init__(struct_bytes=ctypes.sizeof(BackwardArgs), **fields)
+
+
+class McmcRelocateArgs(ctypes.Structure):
+    """lr_mcmc_relocate_args, field for field (tests/test_mcmc_cpu.py compares the offsets with the host compiler's)."""
+    _vp, _ci = ctypes.c_void_p, ctypes.c_int
+    _fields_ = [("struct_bytes", ctypes.c_size_t), ("n", _ci), ("dst", _vp), ("src", _vp), ("P_rows", _ci), ("M", _ci),
+                ("xyz", _vp), ("features_dc", _vp), ("features_rest", _vp), ("opacity", _vp), ("scaling", _vp), ("rotation", _vp),
+                ("exp_avg", _vp * 6), ("exp_avg_sq", _vp * 6),
+                ("min_opacity", ctypes.c_float), ("n_max", _ci),
+                ("workspace", _vp), ("workspace_bytes", ctypes.c_size_t), ("stream", _vp)]
+
+    def __init__(self, **fields):
+        super().__init__(struct_bytes=ctypes.sizeof(McmcRelocateArgs), **fields)
 
 
 def assert_single_copy():
@@ -233,6 +247,14 @@ def lib():
         L.lr_adam_step.restype = ci
         cd = ctypes.c_double
         L.lr_adam_step.argtypes = [ci, vp, vp, vp, vp, vp, vp, cd, cd, cd, ci, vp]
+        L.lr_mcmc_workspace_bytes.restype = ctypes.c_size_t
+        L.lr_mcmc_workspace_bytes.argtypes = [ci, ci]
+        L.lr_mcmc_relocate.restype = ci
+        L.lr_mcmc_relocate.argtypes = [ctypes.POINTER(McmcRelocateArgs)]
+        L.lr_mcmc_noise.restype = ci
+        L.lr_mcmc_noise.argtypes = [ci, vp, vp, vp, vp, vp, cf, vp]              # P xyz scale rotation opacity noise scaler stream
+        L.lr_mcmc_reg_grad.restype = ci
+        L.lr_mcmc_reg_grad.argtypes = [ci, vp, vp, cf, cf, vp, vp, vp]           # P opacity scale w_opacity w_scale dL_do dL_ds stream
         L.lr_step_begin.restype = ci
         L.lr_step_begin.argtypes = []
         L.lr_step_end.restype = ci

@@ -34,6 +34,7 @@ SOURCES = {
     "loss.hip": ["-fno-slp-vectorize"],
     "rows.hip": [],
     "adam.hip": [],
+    "mcmc.hip": [],             # MCMC densification: relocation / growth, position noise, regulariser gradients
     # video frames: bit-exact to numpy's float32 operations (np.round, np.percentile, colorize's normalisation): no FMA contraction
     "video.hip": ["-ffp-contract=off"],
     "api.hip": [],

@@ -535,6 +535,19 @@ int launch_adam_masked(int n_tensors, float* const* params, const float* const* 
                        float* const* exp_avg_sq, const unsigned long long* numel, const unsigned int* row_len, const double* lr,
                        double beta1, double beta2, double eps, int step, const uint32_t* tiles_touched, const GeomHeader* hdr,
                        hipStream_t s);
+// MCMC densification (mcmc.hip): relocation / growth over (dst, src) row pairs, position noise, regulariser gradients.
+// params / exp_avg / exp_avg_sq: xyz, f_dc, f_rest, opacity, scaling, rotation (a NULL moment = no such tensor); n_rest: rows of
+// three floats per Gaussian in f_rest; ws: mcmc_workspace_bytes(P_rows, n) device bytes.
+constexpr int MCMC_N_MAX = 51;                                           // largest split count the binomial table covers
+constexpr size_t MCMC_TABLE_DOUBLES = (size_t)MCMC_N_MAX * MCMC_N_MAX + MCMC_N_MAX;
+size_t mcmc_workspace_bytes(int P_rows, int n);
+hipError_t launch_mcmc_relocate(int n, const int* dst, const int* src, int P_rows, int n_rest, float* const params[6],
+                                float* const exp_avg[6], float* const exp_avg_sq[6], float min_opacity, int n_max, char* ws,
+                                hipStream_t s);
+void launch_mcmc_noise(int P, float* xyz, const float* raw_scale, const float* raw_rotation, const float* raw_opacity,
+                       const float* noise, float scaler, hipStream_t s);
+void launch_mcmc_reg_grad(int P, const float* raw_opacity, const float* raw_scale, float opacity_reg, float scale_reg,
+                          float* dL_dopacity, float* dL_dscale, hipStream_t s);
 // fused L1 + DSSIM loss (loss.hip)
 size_t loss_workspace_bytes(int C, int H, int W);
 // defer_final: leave {loss, l1, ssim} to the launch_loss_backward(..., final_out3) that follows on the same stream
