@@ -16,10 +16,17 @@ a perturbed subset of it.  Prints the loss every `--log` iterations and the time
                                   [--absgrad --densify-grad-threshold 0.0008]
                                   [--multi-view 4 [--absgrad]]
                                   [--mcmc --cap-max 150000]
+                                  [--multi-view 4 --depth-weight 0.1 [--depth-loss pearson]]
 
 --multi-view K: the loop body is ONE multi-view step (parallel.ViewBatch: forward, L1 + DSSIM loss and backward of K views in one
 C call, gradients summed) followed by Adam; the densification statistics are formed inside the step, per view
 (densify_stats="grad", or "absgrad" with --absgrad), and densify_and_prune runs on them.
+
+--multi-view K --depth-weight W: the step also supervises every view's rendered depth with the hidden cloud's depth map
+(ViewBatch(depth_targets=, depth_weight=W)).  --depth-loss l1 compares absolute values (loss.depth_l1); --depth-loss pearson
+compares by correlation (loss.depth_pearson), and the example then CORRUPTS every view's depth target by a per-view random scale
+a in [0.5, 2] and shift b in [-1, 1] -- what a monocular estimate does to it -- which that term does not see and an L1 term
+would be pulled apart by.
 
 --mcmc --cap-max N: in either loop the MCMC strategy (luciddreamer_amd.mcmc.MCMCStrategy) takes the place of the densify_and_prune
 calls: the regularisers' gradients are added before the optimizer's step, and after it dead Gaussians are relocated and the set
@@ -92,6 +99,24 @@ def build(args, dev):
     return model, cams, targets
 
 
+def depth_targets_for(args, dev):
+    """--depth-weight: the hidden cloud's depth per view (0 where it covers nothing: no target there); with --depth-loss pearson
+    every view's map is corrupted by its own scale a in [0.5, 2] and shift b in [-1, 1], as estimated depth is."""
+    W, H = (int(v) for v in args.resolution.split("x"))
+    gt_cloud = {k: v.to(dev) for k, v in synthetic.make_cloud(args.gaussians, "box", 0).items()}
+    gt = GaussianCloud(gt_cloud["means3D"], gt_cloud["scales"], gt_cloud["rotations"], gt_cloud["opacities"], gt_cloud["shs"],
+                       requires_grad=False)
+    cams = [c.to(dev) for c in cameras.lookaround_path(W, H, n_views=args.views)]
+    with torch.no_grad():
+        depths = [render_raw(c, gt, render_only=True)["depth"].reshape(1, H, W).contiguous() for c in cams]
+    if args.depth_loss == "pearson":
+        g = torch.Generator(device="cpu").manual_seed(2)
+        for i, d in enumerate(depths):
+            a, b = 0.5 + 1.5 * float(torch.rand(1, generator=g)), -1.0 + 2.0 * float(torch.rand(1, generator=g))
+            depths[i] = torch.where(d > 0, (a * d + b).clamp_min(1e-3), d)       # a pixel with a target keeps one
+    return depths
+
+
 LR_XYZ = 1.6e-4                # the position learning rate of build(): the noise is scaled by it
 
 
@@ -136,13 +161,17 @@ def train_multi_view(args, log=print):
     config.set_antialiasing(args.antialiasing)
     groups = [list(range(i, i + K)) for i in range(0, len(cams) - K + 1, K)]      # consecutive views of the path
     batches, cap = {}, _capacity(model, cams, bg)
+    depth_weight = float(getattr(args, "depth_weight", 0.0))
+    dts = depth_targets_for(args, dev) if depth_weight > 0 else None
 
     def batch_for(gi, with_stats):
         key = (gi, with_stats)
         if key not in batches:
+            depth = {} if dts is None else dict(depth_targets=[dts[i] for i in groups[gi]], depth_weight=depth_weight,
+                                                depth_loss=args.depth_loss)
             batches[key] = parallel.ViewBatch([cams[i] for i in groups[gi]], None, 3, bg, cap, n_streams=min(3, K),
                                               targets=[targets[i] for i in groups[gi]], lambda_dssim=args.lambda_dssim,
-                                              densify_stats=mode if with_stats else None)
+                                              densify_stats=mode if with_stats else None, **depth)
         return batches[key]
     losses = []
     gen = torch.Generator().manual_seed(0)
@@ -237,7 +266,7 @@ def train(args, log=print):
 def default_args(**kw):
     d = dict(gaussians=200_000, iters=300, resolution="512x512", views=12, lambda_dssim=0.2, log=50, densify_from=100,
              densify_every=100, densify_until=10_000, exact=False, torch_adam=False, antialiasing=False, absgrad=False,
-             densify_grad_threshold=0.0002, multi_view=0, mcmc=False, cap_max=0)
+             densify_grad_threshold=0.0002, multi_view=0, mcmc=False, cap_max=0, depth_weight=0.0, depth_loss="l1")
     d.update(kw)
     return SimpleNamespace(**d)
 
@@ -250,16 +279,26 @@ HELP = {
                   "densification statistics come from the step itself (with --absgrad: the absolute gradient's)",
     "absgrad": "densify by the absolute view-space gradient (AbsGS, config.set_absgrad): per-pixel pulls on a Gaussian are summed "
                "by magnitude, so large Gaussians over blurry regions get split; raise --densify-grad-threshold with it",
+    "depth_weight": "with --multi-view: > 0 adds depth supervision against the hidden cloud's depth maps with this weight",
+    "depth_loss": "the depth term of --depth-weight: l1 (absolute values, loss.depth_l1) or pearson (1 - correlation, "
+                  "loss.depth_pearson; the targets are then corrupted by a per-view scale in [0.5, 2] and shift in [-1, 1])",
     "densify_grad_threshold": "clone / split threshold on the accumulated view-space gradient norm (reference: 0.0002).  Summed "
                               "magnitudes are larger than the signed norm: with --absgrad use about 4x (0.0008)",
 }
 
 
-if __name__ == "__main__":
+CHOICES = {"depth_loss": ("l1", "pearson")}
+
+
+def make_parser():
     ap = argparse.ArgumentParser()
     for k, v in vars(default_args()).items():
         if isinstance(v, bool):
             ap.add_argument("--" + k.replace("_", "-"), action="store_true", help=HELP.get(k))
         else:
-            ap.add_argument("--" + k.replace("_", "-"), type=type(v), default=v, help=HELP.get(k))
-    train(ap.parse_args())
+            ap.add_argument("--" + k.replace("_", "-"), type=type(v), default=v, help=HELP.get(k), choices=CHOICES.get(k))
+    return ap
+
+
+if __name__ == "__main__":
+    train(make_parser().parse_args())

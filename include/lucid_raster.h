@@ -356,6 +356,12 @@ int lr_render_alpha(const char* image_buffer, int width, int height, float* out_
  *       ignored) with depth_weight (finite, >= 0): loss += depth_weight * depth_l1, depth_l1 the unweighted masked mean of
  *       lr_depth_l1_forward; out_losses holds {loss, l1, ssim, depth_l1} per view.  With depth_weight == 0 the backward is the
  *       colour-only one (the bits of the step without depth_targets) and depth_l1 is still reported.
+ *       depth_loss selects the depth term: LR_DEPTH_LOSS_L1 (0) the above, to the bit what the step computed before the member
+ *       existed; LR_DEPTH_LOSS_PEARSON (1) the scale- and shift-invariant term of lr_depth_pearson_forward, loss += depth_weight *
+ *       (1 - rho), with 1 - rho in the depth_l1 column of out_losses (same 4 or 5 columns) and the same depth_weight == 0 rule.
+ *       A view whose term is degenerate (see there) reports 0 and gets a zero depth gradient: the colour-only gradients.  Any
+ *       other value, or a non-zero value without depth_targets, is LR_ERR_INVALID_ARG.  Masks and the densification
+ *       statistics compose with it unchanged.  It costs three launches per view where the L1 term has two.
  *     masks [H,W] in [0, 1] per view (optional array, no NULL entries; 1: content, 0: hole -- LucidDreamer's frames have holes:
  *       pixels the projected cloud left empty are exact zeros) with alpha_weight (finite, >= 0): the colour loss is that of the
  *       masked pair (lr_masked_l1_dssim_forward) and loss += alpha_weight * alpha_hole (lr_alpha_hole_forward on A = 1 -
@@ -365,7 +371,9 @@ int lr_render_alpha(const char* image_buffer, int width, int height, float* out_
  * Workspace: lr_views_workspace_bytes(P, W, H, binning_capacity, n_streams, parts) device bytes, 256-byte aligned, with
  * `parts` the LR_VIEWS_* flags of what the step's slots hold besides a view's scratch: 0 for fixed gradients, LR_VIEWS_LOSS
  * with targets, | LR_VIEWS_DEPTH_LOSS with depth_targets, | LR_VIEWS_MASK_LOSS with masks (a mask step's slot always has the
- * depth part too: LOSS|MASK and LOSS|DEPTH|MASK are one layout).  DEPTH or MASK without LOSS, or unknown bits, are invalid:
+ * depth part too: LOSS|MASK and LOSS|DEPTH|MASK are one layout), | LR_VIEWS_DEPTH_PEARSON with depth_loss ==
+ * LR_DEPTH_LOSS_PEARSON (the slot's depth-loss workspace is then the larger one of lr_depth_pearson_workspace_bytes; valid only
+ * together with LOSS and DEPTH or MASK; every other parts value keeps its sizes).  DEPTH or MASK without LOSS, or unknown bits, are invalid:
  * the size query returns 0 and lr_views_check LR_ERR_INVALID_ARG.  lr_views_check takes the values the step was run with.
  * Densification statistics (0.6.3): with stat_grad_accum, stat_denom and stat_max_radii [P] given -- all three or none, anything
  * else is LR_ERR_INVALID_ARG, as is stat_absgrad != 0 without them; 4-byte aligned, accumulated into, no accumulate-mask bit
@@ -389,6 +397,11 @@ int lr_render_alpha(const char* image_buffer, int width, int height, float* out_
 #define LR_VIEWS_LOSS        1u   /* slot holds the colour-loss workspace and dL/dcolor image   */
 #define LR_VIEWS_DEPTH_LOSS  2u   /* ... and the depth gradient image + depth-L1 workspace      */
 #define LR_VIEWS_MASK_LOSS   4u   /* ... and the alpha gradient image + alpha-hole workspace    */
+#define LR_VIEWS_DEPTH_PEARSON 16u /* the depth-loss workspace holds the Pearson term's (8u is not a flag) */
+
+/* lr_views_args::depth_loss */
+#define LR_DEPTH_LOSS_L1      0   /* masked depth L1 (lr_depth_l1_*) */
+#define LR_DEPTH_LOSS_PEARSON 1   /* 1 - Pearson correlation (lr_depth_pearson_*) */
 
 typedef struct lr_views_args {
     size_t struct_bytes;                     /* = sizeof(lr_views_args); anything else is LR_ERR_INVALID_ARG */
@@ -452,6 +465,10 @@ typedef struct lr_views_args {
     long long binning_capacity;
     int n_streams;
     void* stream;
+    /* the depth term of the fused training step (LR_DEPTH_LOSS_*; see above).  The LAST member on purpose: sizeof grows with
+     * it, so a caller built against the header without it is rejected by the struct_bytes check instead of having whatever
+     * sat in a padding hole read as a mode */
+    int depth_loss;
 } lr_views_args;
 
 int lr_views_accumulate(const lr_views_args* a);
@@ -614,6 +631,39 @@ int lr_depth_l1_forward(int height, int width, const float* depth, const float* 
                         void* workspace, size_t workspace_bytes, void* stream);
 int lr_depth_l1_backward(int height, int width, const float* depth, const float* target, float weight, const float* upstream,
                          float* dL_ddepth, void* stream);
+
+/*
+ * Pearson depth loss: scale- and shift-invariant supervision of the rendered depth by an ESTIMATED depth map (a monocular
+ * estimate is right about ordering and relative structure, wrong about scale and offset, differently in every frame; the
+ * correlation is invariant to target -> a * target + b, a > 0).  depth, target: [H,W] float32 device images, contiguous.
+ * The valid set is M = {i : target_i > 0}, exactly lr_depth_l1_*'s: NaN targets and targets <= 0 are excluded, selected away,
+ * never multiplied; m = |M|.  All sums run over M, in double:
+ *     Sd = sum d, St = sum t, Sdd = sum d^2, Stt = sum t^2, Sdt = sum d t
+ *     mu_d = Sd / m, mu_t = St / m
+ *     Sxx = Sdd - Sd^2 / m, Syy = Stt - St^2 / m, Sxy = Sdt - Sd St / m
+ *     rho = Sxy / sqrt(Sxx Syy), clamped to [-1, 1]
+ *     term = 1 - rho, loss = weight * term
+ *     for i in M: d loss / d d_i = -weight * ( (t_i - mu_t) / sqrt(Sxx Syy) - rho (d_i - mu_d) / Sxx ), and 0 outside M
+ * Degenerate inputs -- m < 2, Sxx <= 1e-12 Sdd or Syy <= 1e-12 Stt (sums that are not finite count as such) -- have no
+ * correlation: term = 0, loss = 0, rho = 0 and the gradient is exactly zero everywhere; no NaN or Inf reaches an accumulator.
+ * (1e-12 is four orders of magnitude above the double-precision cancellation error of the one-pass variance.)
+ * Every pixel's d and t are converted to double before any product or sum is formed; per-lane, per-workgroup and final sums are
+ * double, in a fixed order, no atomics: the value is bit-repeatable from call to call.
+ *   lr_depth_pearson_forward : out (device, 2 floats) = {loss, rho}; fills `workspace` (device, lr_depth_pearson_workspace_bytes:
+ *                              six partial sums per workgroup and, behind them, a coefficient record -- mu_d, mu_t,
+ *                              1 / sqrt(Sxx Syy), rho / Sxx, both 0 when degenerate).  weight finite and >= 0.
+ *   lr_depth_pearson_backward: dL_ddepth [H,W] = upstream * d loss / d depth; `upstream` a device scalar or NULL for 1.  UNLIKE
+ *                              lr_depth_l1_backward it READS the coefficient record the forward left in `workspace`: pass the same
+ *                              workspace, untouched since the forward of the same depth, target, on the same stream (or ordered
+ *                              behind it).  One elementwise pass.
+ * No host synchronisation.  Return 0 or a negative LR_ERR_*; the argument checks (NULL pointers, sizes, workspace_bytes, weight)
+ * precede every device call.
+ */
+size_t lr_depth_pearson_workspace_bytes(int height, int width);
+int lr_depth_pearson_forward(int height, int width, const float* depth, const float* target, float weight, float* out,
+                             void* workspace, size_t workspace_bytes, void* stream);
+int lr_depth_pearson_backward(int height, int width, const float* depth, const float* target, float weight, const float* upstream,
+                              const void* workspace, size_t workspace_bytes, float* dL_ddepth, void* stream);
 
 /*
  * Mask supervision of one view (the single-view building blocks of lr_views_accumulate with masks).  mask: [H,W] float32

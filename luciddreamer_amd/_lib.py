@@ -36,6 +36,7 @@ EXPORTS = ("lr_last_error", "lr_version", "lr_geom_bytes", "lr_img_bytes", "lr_b
            "lr_loss_workspace_bytes", "lr_l1_dssim_forward", "lr_l1_dssim_backward", "lr_l1_dssim_backward_weights",
            "lr_select_workspace_bytes", "lr_select_rows", "lr_pack_ply_rows", "lr_adam_step", "lr_adam_step_masked", "lr_densify_stats",
            "lr_depth_l1_workspace_bytes", "lr_depth_l1_forward", "lr_depth_l1_backward",
+           "lr_depth_pearson_workspace_bytes", "lr_depth_pearson_forward", "lr_depth_pearson_backward",
            "lr_video_workspace_bytes", "lr_frames_to_u8", "lr_depth_colorize",
            "lr_masked_l1_dssim_forward", "lr_masked_l1_dssim_backward", "lr_alpha_hole_workspace_bytes", "lr_alpha_hole_forward",
            "lr_alpha_hole_backward", "lr_set_antialiasing", "lr_get_antialiasing",
@@ -43,6 +44,9 @@ EXPORTS = ("lr_last_error", "lr_version", "lr_geom_bytes", "lr_img_bytes", "lr_b
 
 # lr_views_workspace_bytes / lr_views_check `parts`: what a step's workspace slots hold besides a view's scratch
 LR_VIEWS_LOSS, LR_VIEWS_DEPTH_LOSS, LR_VIEWS_MASK_LOSS = 1, 2, 4
+LR_VIEWS_DEPTH_PEARSON = 16         # the slot's depth-loss workspace is the Pearson term's (8 is not a flag)
+# lr_views_args.depth_loss: the depth term of the fused training step
+LR_DEPTH_LOSS_L1, LR_DEPTH_LOSS_PEARSON = 0, 1
 
 
 class ViewsArgs(ctypes.Structure):
@@ -70,7 +74,9 @@ class ViewsArgs(ctypes.Structure):
                 # densification statistics [P]: all three or none; stat_absgrad selects the absolute gradient's norm
                 ("stat_grad_accum", _vp), ("stat_denom", _vp), ("stat_max_radii", _vp), ("stat_absgrad", _ci),
                 ("workspace", _vp), ("workspace_bytes", ctypes.c_size_t), ("binning_capacity", ctypes.c_longlong),
-                ("n_streams", _ci), ("stream", _vp)]
+                ("n_streams", _ci), ("stream", _vp),
+                # LR_DEPTH_LOSS_*; the last member, so that sizeof grew with it (see the header)
+                ("depth_loss", _ci)]
 
     def __init__(self, **fields):
         super().__init__(struct_bytes=ctypes.sizeof(ViewsArgs), **fields)
@@ -209,6 +215,12 @@ def lib():
         L.lr_depth_l1_forward.argtypes = [ci, ci, vp, vp, cf, vp, vp, ctypes.c_size_t, vp]
         L.lr_depth_l1_backward.restype = ci
         L.lr_depth_l1_backward.argtypes = [ci, ci, vp, vp, cf, vp, vp, vp]
+        L.lr_depth_pearson_workspace_bytes.restype = ctypes.c_size_t
+        L.lr_depth_pearson_workspace_bytes.argtypes = [ci, ci]
+        L.lr_depth_pearson_forward.restype = ci
+        L.lr_depth_pearson_forward.argtypes = [ci, ci, vp, vp, cf, vp, vp, ctypes.c_size_t, vp]
+        L.lr_depth_pearson_backward.restype = ci
+        L.lr_depth_pearson_backward.argtypes = [ci, ci, vp, vp, cf, vp, vp, ctypes.c_size_t, vp, vp]
         L.lr_masked_l1_dssim_forward.restype = ci
         L.lr_masked_l1_dssim_forward.argtypes = [ci, ci, ci, vp, vp, vp, cf, vp, vp, ctypes.c_size_t, vp]
         L.lr_masked_l1_dssim_backward.restype = ci

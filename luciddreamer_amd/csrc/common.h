@@ -567,6 +567,14 @@ void launch_depth_l1_forward(int H, int W, const float* depth, const float* targ
                              hipStream_t s, DepthL1Final final_mode = DEPTH_L1_VALUE);
 void launch_depth_l1_backward(int H, int W, const float* depth, const float* target, float weight, const float* upstream,
                               const char* ws, float* grad, hipStream_t s, float* fused_out = nullptr);
+// Pearson depth loss (loss.hip): weight * (1 - rho) over the pixels with target > 0, sums in double.  The forward (two launches:
+// partials, then one workgroup) leaves the partials and the coefficient record in ws and writes out = {loss, rho}, or, fused
+// (the fused step's {loss, l1, ssim, depth term}), out[0] += weight * term, out[3] = term; the backward reads that record.
+size_t depth_pearson_workspace_bytes(int H, int W);
+void launch_depth_pearson_forward(int H, int W, const float* depth, const float* target, float weight, float* out, char* ws,
+                                  hipStream_t s, bool fused = false);
+void launch_depth_pearson_backward(int H, int W, const float* depth, const float* target, float weight, const float* upstream,
+                                   const char* ws, float* grad, hipStream_t s);
 // alpha hole term (loss.hip): weight * mean(A (1 - m)) with A the alpha image, or 1 - src when from_T (src = the blend forward's
 // final_T; alpha_out, if given, receives that A).  final_mode as the depth L1's, the fused value going to out[4]
 // ({loss, l1, ssim, depth_l1, alpha_hole}; fused_no_depth: out[3] = 0 as well, a step without a depth term); the backward

@@ -17,7 +17,8 @@
 // HBM-bound by construction: ~60 B per pixel-channel over both passes; no atomics, deterministic.
 // k_ssim_fwd_masked / k_ssim_bwd_masked (lr_masked_l1_dssim_*): the same bodies (loss_ssim_*_body.h) on the masked pair
 // (m I, m G), m a content mask [H,W]; 4 B more per pixel-channel and pass.  Below them: the masked depth L1 and the alpha hole
-// term, elementwise passes with fixed-order double reductions.
+// term, elementwise passes with fixed-order double reductions, and the Pearson depth loss (k_depth_pearson_*), whose sums are
+// double from the pixel on.
 #include "common.h"
 #include <cmath>
 
@@ -332,6 +333,136 @@ k_alpha_hole_bwd(int n, float weight, const float* __restrict__ upstream, const 
     }
 }
 
+// ---- Pearson depth loss (scale- and shift-invariant supervision of the rendered depth by an estimated depth map) ------------
+// The valid set is M = {i : target_i > 0}, exactly the masked depth L1's (NaN targets and targets <= 0 are excluded; excluded
+// pixels are SELECTED away, never multiplied), m = |M|.  All sums run over M, in double:
+//     Sd = sum d, St = sum t, Sdd = sum d^2, Stt = sum t^2, Sdt = sum d t
+//     mu_d = Sd / m, mu_t = St / m
+//     Sxx = Sdd - Sd^2 / m, Syy = Stt - St^2 / m, Sxy = Sdt - Sd St / m
+//     rho = Sxy / sqrt(Sxx Syy), clamped to [-1, 1];  term = 1 - rho, loss = weight * term
+//     for i in M: dloss/dd_i = -weight * ( (t_i - mu_t) / sqrt(Sxx Syy) - rho (d_i - mu_d) / Sxx ), 0 outside M
+// (the mean-subtraction terms cancel exactly, so the backward is elementwise once mu_d, mu_t, 1 / sqrt(Sxx Syy), rho / Sxx and
+// upstream * weight are known).  Degenerate inputs -- m < 2, Sxx <= 1e-12 Sdd or Syy <= 1e-12 Stt (a non-finite sum is neither
+// > anything) -- have no correlation: term = 0, loss = 0, rho = 0 and the gradient is exactly zero everywhere.  1e-12 sits
+// four orders of magnitude above the double-precision cancellation error of the one-pass variance.
+// Every pixel's d and t are converted to double BEFORE any product or sum is formed; per-lane, per-workgroup and final sums
+// are double, in a fixed order, no atomics: the value is bit-repeatable.  (A float sum of d^2 loses the variance of a distant,
+// flat depth map.)  HBM-bound like the L1 pair: 8 B per pixel forward, 8 + 4 backward; the fp64 FMAs hide under that.
+//   k_depth_pearson_fwd  : six partials per workgroup {Sd, St, Sdd, Stt, Sdt, m}
+//   k_depth_pearson_final: one workgroup; reduces the partials, decides degeneracy, writes the coefficient record and the value(s)
+//   k_depth_pearson_bwd  : one elementwise pass that reads the record (every workgroup needs the coefficients: it must not
+//                          re-reduce the partials itself, unlike the L1 backward whose constant needs no sum)
+constexpr int DP_SUMS = 6;
+// the coefficient record behind the partials (doubles): what the backward and the callers read
+enum { DP_MU_D = 0, DP_MU_T = 1, DP_INV_NORM = 2, DP_RHO_OVER_SXX = 3, DP_TERM = 4, DP_RHO = 5, DP_RECORD = 8 };
+
+__global__ void __launch_bounds__(LTHREADS)
+k_depth_pearson_fwd(int n, const float* __restrict__ depth, const float* __restrict__ target, double* __restrict__ partials)
+{
+    __shared__ double s_tmp[4][DP_SUMS];
+    const int base = (int)blockIdx.x * DL_BLOCK + (int)threadIdx.x;
+    float d[DL_ITEMS], t[DL_ITEMS];
+#pragma unroll
+    for (int i = 0; i < DL_ITEMS; i++) {             // all loads first; pixel base + 256 i: coalesced
+        const int q = base + i * LTHREADS;
+        const bool ok = q < n;
+        d[i] = ok ? depth[q] : 0.f;
+        t[i] = ok ? target[q] : 0.f;
+    }
+    double s[DP_SUMS] = { 0.0, 0.0, 0.0, 0.0, 0.0, 0.0 };
+#pragma unroll
+    for (int i = 0; i < DL_ITEMS; i++) {
+        const bool valid = t[i] > 0.f;
+        const double dd = valid ? (double)d[i] : 0.0, tt = valid ? (double)t[i] : 0.0;
+        s[0] += dd; s[1] += tt; s[2] += dd * dd; s[3] += tt * tt; s[4] += dd * tt; s[5] += valid ? 1.0 : 0.0;
+    }
+#pragma unroll
+    for (int j = 0; j < DP_SUMS; j++) {
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) s[j] += __shfl_xor(s[j], off);
+    }
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int j = 0; j < DP_SUMS; j++) s_tmp[threadIdx.x >> 6][j] = s[j];
+    }
+    lds_barrier();
+    if (threadIdx.x < DP_SUMS)
+        partials[(size_t)blockIdx.x * DP_SUMS + threadIdx.x] =
+            (s_tmp[0][threadIdx.x] + s_tmp[1][threadIdx.x]) + (s_tmp[2][threadIdx.x] + s_tmp[3][threadIdx.x]);
+}
+
+// fused 0: out = {weight * term, rho}; fused 1 (out = the view's {loss, l1, ssim, depth term} of lr_views_accumulate, the colour
+// loss already in out[0]): out[0] += weight * term when weight != 0, out[3] = term -- what depth_l1_final does in fused mode
+__global__ void __launch_bounds__(LTHREADS)
+k_depth_pearson_final(int n_blocks, float weight, const double* __restrict__ partials, double* __restrict__ record,
+                      float* __restrict__ out, int fused)
+{
+    __shared__ double s_a[DP_SUMS][LTHREADS];
+    double a[DP_SUMS] = { 0.0, 0.0, 0.0, 0.0, 0.0, 0.0 };
+    for (int i = threadIdx.x; i < n_blocks; i += LTHREADS) {
+#pragma unroll
+        for (int j = 0; j < DP_SUMS; j++) a[j] += partials[(size_t)i * DP_SUMS + j];
+    }
+#pragma unroll
+    for (int j = 0; j < DP_SUMS; j++) s_a[j][threadIdx.x] = a[j];
+    lds_barrier();
+    for (int off = LTHREADS / 2; off > 0; off >>= 1) {
+        if ((int)threadIdx.x < off) {
+#pragma unroll
+            for (int j = 0; j < DP_SUMS; j++) s_a[j][threadIdx.x] += s_a[j][threadIdx.x + off];
+        }
+        lds_barrier();
+    }
+    if (threadIdx.x == 0) {
+        const double Sd = s_a[0][0], St = s_a[1][0], Sdd = s_a[2][0], Stt = s_a[3][0], Sdt = s_a[4][0], m = s_a[5][0];
+        double mu_d = 0.0, mu_t = 0.0, inv_norm = 0.0, rho_over_sxx = 0.0, rho = 0.0;
+        if (m >= 2.0) {
+            const double Sxx = Sdd - Sd * Sd / m, Syy = Stt - St * St / m, Sxy = Sdt - Sd * St / m;
+            if (Sxx > 1e-12 * Sdd && Syy > 1e-12 * Stt) {          // false for non-finite sums as well
+                mu_d = Sd / m; mu_t = St / m;
+                inv_norm = 1.0 / sqrt(Sxx * Syy);
+                rho = fmin(fmax(Sxy * inv_norm, -1.0), 1.0);
+                rho_over_sxx = rho / Sxx;
+            }
+        }
+        const bool live = inv_norm > 0.0 && inv_norm <= 1.79769313486231570e308;      // an overflowed product is degenerate too
+        if (!live) { mu_d = mu_t = inv_norm = rho_over_sxx = rho = 0.0; }
+        const double term = live ? 1.0 - rho : 0.0;
+        record[DP_MU_D] = mu_d; record[DP_MU_T] = mu_t; record[DP_INV_NORM] = inv_norm; record[DP_RHO_OVER_SXX] = rho_over_sxx;
+        record[DP_TERM] = term; record[DP_RHO] = rho; record[6] = m; record[7] = 0.0;
+        if (fused) { if (weight != 0.f) out[0] = out[0] + weight * (float)term; out[3] = (float)term; }
+        else { out[0] = (float)((double)weight * term); out[1] = (float)rho; }
+    }
+}
+
+// dL/dd_i = -(upstream * weight) * ( (t_i - mu_t) / sqrt(Sxx Syy) - (rho / Sxx) (d_i - mu_d) ) on M, in double, rounded to float
+// once; a degenerate record (both coefficients 0) writes exact zeros whatever the pixels hold
+__global__ void __launch_bounds__(LTHREADS)
+k_depth_pearson_bwd(int n, float weight, const float* __restrict__ upstream, const float* __restrict__ depth,
+                    const float* __restrict__ target, const double* __restrict__ record, float* __restrict__ grad)
+{
+    const int base = (int)blockIdx.x * DL_BLOCK + (int)threadIdx.x;
+    float d[DL_ITEMS], t[DL_ITEMS];
+#pragma unroll
+    for (int i = 0; i < DL_ITEMS; i++) {
+        const int q = base + i * LTHREADS;
+        const bool ok = q < n;
+        d[i] = ok ? depth[q] : 0.f;
+        t[i] = ok ? target[q] : 0.f;
+    }
+    const double mu_d = record[DP_MU_D], mu_t = record[DP_MU_T], c_t = record[DP_INV_NORM], c_d = record[DP_RHO_OVER_SXX];
+    const bool live = c_t != 0.0;
+    const double k = -((double)(upstream != nullptr ? upstream[0] : 1.0f) * (double)weight);
+#pragma unroll
+    for (int i = 0; i < DL_ITEMS; i++) {
+        const int q = base + i * LTHREADS;
+        if (q < n) {
+            const double g = k * (((double)t[i] - mu_t) * c_t - c_d * ((double)d[i] - mu_d));
+            grad[q] = (live && t[i] > 0.f) ? (float)g : 0.f;
+        }
+    }
+}
+
 }  // namespace
 
 size_t loss_workspace_bytes(int C, int H, int W)
@@ -408,6 +539,42 @@ void launch_depth_l1_backward(int H, int W, const float* depth, const float* tar
     const int blocks = (n + DL_BLOCK - 1) / DL_BLOCK;
     hipLaunchKernelGGL(k_depth_l1_bwd, dim3(blocks), dim3(LTHREADS), 0, s, n, weight, upstream, depth, target, grad,
                        reinterpret_cast<const double*>(ws), blocks, fused_out);
+}
+
+}  // namespace lr
+
+namespace lr {
+
+// the partials [workgroups][6] and, behind them, the coefficient record
+static size_t depth_pearson_record_offset(int H, int W)
+{
+    const size_t n = (size_t)H * W;
+    return align_up(((n + DL_BLOCK - 1) / DL_BLOCK) * DP_SUMS * sizeof(double));
+}
+
+size_t depth_pearson_workspace_bytes(int H, int W)
+{
+    return depth_pearson_record_offset(H, W) + align_up(DP_RECORD * sizeof(double));
+}
+
+void launch_depth_pearson_forward(int H, int W, const float* depth, const float* target, float weight, float* out, char* ws,
+                                  hipStream_t s, bool fused)
+{
+    const int n = H * W;
+    const int blocks = (n + DL_BLOCK - 1) / DL_BLOCK;
+    double* partials = reinterpret_cast<double*>(ws);
+    double* record = reinterpret_cast<double*>(ws + depth_pearson_record_offset(H, W));
+    hipLaunchKernelGGL(k_depth_pearson_fwd, dim3(blocks), dim3(LTHREADS), 0, s, n, depth, target, partials);
+    hipLaunchKernelGGL(k_depth_pearson_final, dim3(1), dim3(LTHREADS), 0, s, blocks, weight, partials, record, out, fused ? 1 : 0);
+}
+
+void launch_depth_pearson_backward(int H, int W, const float* depth, const float* target, float weight, const float* upstream,
+                                   const char* ws, float* grad, hipStream_t s)
+{
+    const int n = H * W;
+    const int blocks = (n + DL_BLOCK - 1) / DL_BLOCK;
+    hipLaunchKernelGGL(k_depth_pearson_bwd, dim3(blocks), dim3(LTHREADS), 0, s, n, weight, upstream, depth, target,
+                       reinterpret_cast<const double*>(ws + depth_pearson_record_offset(H, W)), grad);
 }
 
 }  // namespace lr

@@ -240,6 +240,70 @@ def depth_l1(depth, target, weight=1.0):
     return _DepthL1.apply(depth, target, weight)
 
 
+_PEARSON_WS_BYTES = {}              # (H, W) -> lr_depth_pearson_workspace_bytes
+
+
+def _pearson_forward(depth, target, weight, what):
+    """(d, t, out {loss, rho}, workspace) of one lr_depth_pearson_forward."""
+    if not depth.is_cuda or not target.is_cuda:
+        raise RuntimeError(f"luciddreamer_amd.loss.{what}: depth and target must be on a HIP device (no CPU path)")
+    H, W = _depth_dims(depth, target)
+    d, t = depth.contiguous(), target.contiguous()
+    L = _lib.lib()
+    dev = d.device
+    n = _PEARSON_WS_BYTES.get((H, W))
+    if n is None:
+        n = _PEARSON_WS_BYTES[(H, W)] = int(L.lr_depth_pearson_workspace_bytes(H, W))
+    out = torch.empty((2,), dtype=torch.float32, device=dev)
+    ws = torch.empty((n,), dtype=torch.uint8, device=dev)
+    with _lib.on_device(dev):
+        rc = L.lr_depth_pearson_forward(H, W, d.data_ptr(), t.data_ptr(), float(weight), out.data_ptr(), ws.data_ptr(),
+                                        ws.numel(), torch.cuda.current_stream(dev).cuda_stream)
+    if rc < 0:
+        _lib.raise_for(rc, what)
+    return d, t, out, ws
+
+
+class _DepthPearson(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, depth, target, weight):
+        d, t, out, ws = _pearson_forward(depth, target, weight, "depth_pearson")
+        ctx.save_for_backward(d, t, ws)       # the backward reads the coefficient record the forward left in the workspace
+        ctx.weight, ctx.in_shape = float(weight), depth.shape
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        d, t, ws = ctx.saved_tensors
+        H, W = int(d.shape[-2]), int(d.shape[-1])
+        L = _lib.lib()
+        dev = d.device
+        up = _weight(grad_out, dev)
+        grad = torch.empty_like(d)
+        with _lib.on_device(dev):
+            rc = L.lr_depth_pearson_backward(H, W, d.data_ptr(), t.data_ptr(), ctx.weight, up.data_ptr(), ws.data_ptr(),
+                                             ws.numel(), grad.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+        if rc < 0:
+            _lib.raise_for(rc, "depth_pearson backward")
+        return grad.view(ctx.in_shape), None, None
+
+
+def depth_pearson(depth, target, weight=1.0):
+    """weight * (1 - rho), rho the Pearson correlation of depth and target over the pixels whose target is > 0 (a target that is
+    not > 0, NaN included, is left out, as in depth_l1); depth, target: [1,H,W] or [H,W] float32.  Invariant to target ->
+    a * target + b with a > 0: the term for ESTIMATED (monocular) depth, which is right up to a per-frame scale and shift.
+    Without a correlation (fewer than two valid pixels, constant depth or constant target on them) the loss and the gradient are
+    exactly 0.  Three small HIP kernels (lr_depth_pearson_forward / _backward): the sums in double from the pixel on, reduced in
+    a fixed order -- bit-repeatable.  Gradients flow to `depth` only (the target is data)."""
+    return _DepthPearson.apply(depth, target, weight)
+
+
+def depth_correlation(depth, target):
+    """rho of depth_pearson (0 when there is none), a 0-dim device tensor without a gradient: for logging."""
+    with torch.no_grad():
+        return _pearson_forward(depth.detach(), target, 1.0, "depth_correlation")[2][1]
+
+
 # ---- mask supervision (INTEGRATION.md 2e): a colour loss only where the frame has content, a penalty on alpha in its holes ----
 def content_mask(gt):
     """float32 [1,H,W] mask of the pixels of a target frame [C,H,W] where any channel is non-zero: LucidDreamer's `maskj`

@@ -870,7 +870,7 @@ class ViewBatch:
                  depths: Optional[Sequence[torch.Tensor]] = None,
                  grad_alphas: Optional[Sequence[torch.Tensor]] = None, masks: Optional[Sequence[torch.Tensor]] = None,
                  alpha_weight: Optional[float] = None, alphas: Optional[Sequence[torch.Tensor]] = None,
-                 densify_stats: Optional[str] = None):
+                 densify_stats: Optional[str] = None, depth_loss: str = "l1"):
         """grad_colors: fixed upstream gradients dL/dcolor per view, OR targets: ground-truth images per view, in which
         case every view's L1 + DSSIM loss against its target is formed inside the call (lr_views_accumulate with targets) and
         `self.losses` ([n,3] device tensor: loss, l1, ssim per view) is filled by run().
@@ -881,6 +881,10 @@ class ViewBatch:
             The masked depth L1 (loss.depth_l1) joins each view's loss with depth_weight (default 1.0, >= 0), and
             `self.losses` is [n,4]: loss (= colour loss + depth_weight * depth_l1), l1, ssim, depth_l1.  depth_weight 0
             reports depth_l1 with the colour-only gradients.
+          depth_loss (with depth_targets): "l1" (the default: the above) or "pearson": loss.depth_pearson in its place, 1 - rho
+            of the rendered depth and the target over the pixels with a target -- invariant to a per-view scale and shift of
+            the target, the term for estimated (monocular) depth maps.  The same columns, 1 - rho in the depth_l1 one; a view
+            without a correlation (constant or empty target) reports 0 and gets the colour-only gradients.
           depths: per-view [1,H,W] or [H,W] contiguous float32 device tensors that run() fills with the rendered depth (not
             with targets alone).
         Mask supervision (the alpha output A = 1 - T_final; the arguments are the opt-in):
@@ -912,9 +916,12 @@ class ViewBatch:
         if densify_stats not in (None, "grad", "absgrad"):
             raise ValueError(f'densify_stats must be None, "grad" or "absgrad", got {densify_stats!r}')
         self.densify_stats = densify_stats
+        if depth_loss not in ("l1", "pearson"):
+            raise ValueError(f'depth_loss must be "l1" or "pearson", got {depth_loss!r}')
+        self.depth_loss = depth_loss
         self.W, self.H = int(self.cams[0].image_width), int(self.cams[0].image_height)
         self._check_optional_args(grad_colors, targets, grad_depths, depth_targets, depth_weight, depths, grad_alphas, masks,
-                                  alpha_weight, alphas)
+                                  alpha_weight, alphas, depth_loss)
         from . import _lib
         self._lib = _lib
         self.L = _lib.lib()
@@ -928,7 +935,8 @@ class ViewBatch:
         self.losses = torch.zeros((self.n, n_losses), dtype=torch.float32, device=self.device) if self.train else None
         # what a workspace slot holds besides a view's scratch (lr_views_workspace_bytes, lr_views_check)
         self.parts = ((_lib.LR_VIEWS_LOSS if self.train else 0) | (_lib.LR_VIEWS_DEPTH_LOSS if depth_targets is not None else 0) |
-                      (_lib.LR_VIEWS_MASK_LOSS if masks is not None else 0))
+                      (_lib.LR_VIEWS_MASK_LOSS if masks is not None else 0) |
+                      (_lib.LR_VIEWS_DEPTH_PEARSON if depth_loss == "pearson" else 0))
         self._keep = []                     # what the host arrays below point to, and the arrays themselves
 
         def host_array(values, ctype=ctypes.c_void_p):
@@ -959,15 +967,18 @@ class ViewBatch:
             masks=inputs(masks), alpha_weight=1.0 if alpha_weight is None else float(alpha_weight),
             out_losses=self.losses.data_ptr() if self.train else None,
             out_depth=outputs(self.depths), out_alpha=outputs(self.alphas), binning_capacity=self.capacity,
-            stat_absgrad=1 if densify_stats == "absgrad" else 0)
+            stat_absgrad=1 if densify_stats == "absgrad" else 0,
+            depth_loss=_lib.LR_DEPTH_LOSS_PEARSON if depth_loss == "pearson" else _lib.LR_DEPTH_LOSS_L1)
         self._ws = None
         self._ws_key = None
 
     def _check_optional_args(self, grad_colors, targets, grad_depths, depth_targets, depth_weight, depths, grad_alphas, masks,
-                             alpha_weight, alphas):
+                             alpha_weight, alphas, depth_loss="l1"):
         """Depth supervision, then mask supervision: the same rules over each one's (fixed gradients, training input, weight,
         output) and its table of per-view images."""
         import math
+        if depth_loss != "l1" and depth_targets is None:
+            raise ValueError(f'depth_loss="{depth_loss}" needs depth_targets')
         fixed, train = grad_colors is not None, targets is not None
         for (g_name, grads, t_name, train_in, w_name, weight, no_output, images) in (
                 ("grad_depths", grad_depths, "depth_targets", depth_targets, "depth_weight", depth_weight,

@@ -39,14 +39,10 @@ def _time(fn, steps, warmup):
     return statistics.median(out)
 
 
-def run(name, args, dev):
+def capacity(c, cams, bg, W, H):
+    """The async-mode capacity bench.py uses: 1.25 x the largest exact-mode instance count of the path, + 4096."""
     from depth_diff_gaussian_rasterization_min import GaussianRasterizationSettings, GaussianRasterizer
-    from luciddreamer_amd import _C, cameras, config, parallel, synthetic
-    kind, P, (W, H) = WORKLOADS[name]
-    c = {k: v.to(dev).contiguous() for k, v in synthetic.make_cloud(P, kind, 0).items()}
-    cams = [cc.to(dev) for cc in cameras.rotate360_path(W, H, n_views=args.views)]
-    bg = torch.zeros(3, device=dev)
-    # the async-mode capacity bench.py uses: 1.25 x the largest exact-mode instance count of the path, + 4096
+    from luciddreamer_amd import _C, config
     config.set_async(False)
     n = []
     with torch.no_grad():
@@ -59,7 +55,16 @@ def run(name, args, dev):
             n.append(int(_C.last_num_rendered()))
     config.set_async(True)
     config.reset()
-    cap = int(max(n) * 1.25) + 4096
+    return int(max(n) * 1.25) + 4096
+
+
+def run(name, args, dev):
+    from luciddreamer_amd import cameras, parallel, synthetic
+    kind, P, (W, H) = WORKLOADS[name]
+    c = {k: v.to(dev).contiguous() for k, v in synthetic.make_cloud(P, kind, 0).items()}
+    cams = [cc.to(dev) for cc in cameras.rotate360_path(W, H, n_views=args.views)]
+    bg = torch.zeros(3, device=dev)
+    cap = capacity(c, cams, bg, W, H)
     gc = synthetic.upstream_grad(H, W).to(dev)
     gen = torch.Generator().manual_seed(3)
     gds = [torch.randn(1, H, W, generator=gen).to(dev) for _ in cams]
