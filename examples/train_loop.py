@@ -8,6 +8,7 @@ piece of this repository on the MI355X:
     FusedAdam         torch.optim.Adam's arithmetic in one launch per step                              (8e: the step after the all-reduce)
     distCUDA2         initial scales from the 3-nearest-neighbour distance                              8f-1
     MCMCStrategy      --mcmc: relocation, capped growth and position noise instead of densify_and_prune   DESIGN.md 4b-MCMC
+    filter3d          --filter3d: the 3D smoothing filter of Mip-Splatting on what the rasterizer is shown   DESIGN.md 4b-F3D
 
 Targets are renders of a hidden "ground truth" cloud from a look-around camera path; the trained cloud starts from
 a perturbed subset of it.  Prints the loss every `--log` iterations and the time per iteration.
@@ -17,6 +18,7 @@ a perturbed subset of it.  Prints the loss every `--log` iterations and the time
                                   [--multi-view 4 [--absgrad]]
                                   [--mcmc --cap-max 150000]
                                   [--multi-view 4 --depth-weight 0.1 [--depth-loss pearson]]
+                                  [--filter3d [--antialiasing]]
 
 --multi-view K: the loop body is ONE multi-view step (parallel.ViewBatch: forward, L1 + DSSIM loss and backward of K views in one
 C call, gradients summed) followed by Adam; the densification statistics are formed inside the step, per view
@@ -32,6 +34,13 @@ would be pulled apart by.
 calls: the regularisers' gradients are added before the optimizer's step, and after it dead Gaussians are relocated and the set
 grows by 5 % -- never beyond N -- on the --densify-from / --densify-every / --densify-until schedule, with the position noise
 every iteration.  No gradient threshold and no densification statistics are involved.
+
+--filter3d: in either loop the rasterizer is shown the cloud through luciddreamer_amd.filter3d.filtered(model, filter): every
+Gaussian low-passed by the highest sampling rate at which a training camera sees it (the 3D smoothing filter of Mip-Splatting).
+The filter is computed after build, again after every densify / prune / MCMC change of the set (a filter of another length than
+the model raises), and every 100 iterations once densification has stopped.  The single-view loop renders the stored-domain view
+through render_raw, the multi-view loop feeds the view's activated getters to ViewBatch.run.  Independent of --antialiasing (the
+2D Mip filter): either works without the other, Mip-Splatting uses both.
 """
 import argparse
 import math
@@ -43,7 +52,7 @@ from types import SimpleNamespace
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from luciddreamer_amd import cameras, config, densify, mcmc, synthetic     # noqa: E402
+from luciddreamer_amd import cameras, config, densify, filter3d, mcmc, synthetic     # noqa: E402
 from luciddreamer_amd.gaussian_renderer import GaussianCloud, render_raw   # noqa: E402
 from luciddreamer_amd.loss import l1_dssim_loss                            # noqa: E402
 from luciddreamer_amd.optim import FusedAdam                               # noqa: E402
@@ -128,6 +137,30 @@ def _mcmc_strategy(args, model):
     return mcmc.MCMCStrategy(cap, refine_start=args.densify_from, refine_stop=args.densify_until, refine_every=args.densify_every)
 
 
+class _Filter3D:
+    """--filter3d: the filter of the current set of Gaussians and the view of the model under it (the model itself without)."""
+    REFRESH = 100                  # iterations between two updates once densification has stopped
+
+    def __init__(self, args, model, cams, dev):
+        self.on = bool(getattr(args, "filter3d", False))
+        self.filter = None
+        if self.on:
+            self.cams = filter3d.pack_cameras(cams, dev)
+            self.update(model)
+
+    def update(self, model):
+        if self.on:
+            self.filter = filter3d.compute_filter_3d(model._xyz.detach(), self.cams)
+
+    def after_step(self, model, it, changed, densify_until):
+        """The set changed (densify / prune / MCMC), or densification is over and REFRESH iterations have passed."""
+        if changed or (it >= densify_until and it % self.REFRESH == 0):
+            self.update(model)
+
+    def view(self, model):
+        return filter3d.filtered(model, self.filter) if self.on else model
+
+
 def _capacity(model, cams, bg):
     """Binning capacity of a multi-view step: twice the largest exact-mode instance count over the path, + 4096 (the cloud
     moves between two densifications; an overflow is reported by ViewBatch.check, never silent)."""
@@ -160,7 +193,8 @@ def train_multi_view(args, log=print):
     mode = "absgrad" if args.absgrad else "grad"
     config.set_antialiasing(args.antialiasing)
     groups = [list(range(i, i + K)) for i in range(0, len(cams) - K + 1, K)]      # consecutive views of the path
-    batches, cap = {}, _capacity(model, cams, bg)
+    f3 = _Filter3D(args, model, cams, dev)
+    batches, cap = {}, _capacity(f3.view(model), cams, bg)
     depth_weight = float(getattr(args, "depth_weight", 0.0))
     dts = depth_targets_for(args, dev) if depth_weight > 0 else None
 
@@ -183,7 +217,8 @@ def train_multi_view(args, log=print):
         with_stats = strategy is None and it < args.densify_until
         batch = batch_for(gi, with_stats)
         # the step takes activated parameters and accumulates their gradients; autograd carries them to the stored ones
-        act = {"means3D": model.get_xyz, "opacities": model.get_opacity, "scales": model.get_scaling,
+        shown = f3.view(model)                     # --filter3d: the activated getters of the filtered view
+        act = {"means3D": model.get_xyz, "opacities": shown.get_opacity, "scales": shown.get_scaling,
                "rotations": model.get_rotation, "shs": model.get_features}
         P = act["means3D"].shape[0]
         acc = {"means3D": torch.zeros(P, 3, device=dev), "means2D": torch.zeros(P, 3, device=dev),
@@ -205,8 +240,9 @@ def train_multi_view(args, log=print):
             model.optimizer.zero_grad(set_to_none=True)
             if strategy is not None:               # relocated Gaussians sit elsewhere, added ones change P
                 densified = any(strategy.step(model, it, LR_XYZ))
+            f3.after_step(model, it, densified, args.densify_until)
             if densified:                          # another P: another capacity, and the batches are rebuilt on it
-                batches, cap = {}, _capacity(model, cams, bg)
+                batches, cap = {}, _capacity(f3.view(model), cams, bg)
         if it % args.log == 0 or it == 1:
             batch.check()
             losses.append((it, float(batch.losses[:, 0].mean().item()), int(model._xyz.shape[0])))
@@ -232,25 +268,29 @@ def train(args, log=print):
     losses = []
     gen = torch.Generator().manual_seed(0)
     strategy = _mcmc_strategy(args, model)
+    f3 = _Filter3D(args, model, cams, dev)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for it in range(1, args.iters + 1):
         v = int(torch.randint(0, len(cams), (1,), generator=gen))
-        pkg = render_raw(cams[v], model, bg_color=bg)                                     # luciddreamer.py:296
+        pkg = render_raw(cams[v], f3.view(model), bg_color=bg)                            # luciddreamer.py:296
         loss = l1_dssim_loss(pkg["render"], targets[v], args.lambda_dssim)                # :301-303
         loss.backward()                                                                   # :304
         with torch.no_grad():
             vis, radii = pkg["visibility_filter"], pkg["radii"]
+            changed = False
             if strategy is not None:
                 strategy.add_regularizer_grads(model)
             elif it < args.densify_until:                                                 # :308-318
                 densify.add_densification_stats(model, pkg["viewspace_points"], radii)   # :310-311 + stats, one kernel
                 if it >= args.densify_from and it % args.densify_every == 0:
                     densify.densify_and_prune(model, args.densify_grad_threshold, 0.005, 5.0, 20)
+                    changed = True
             model.optimizer.step()                                                        # :322-324
             model.optimizer.zero_grad(set_to_none=True)
             if strategy is not None:
-                strategy.step(model, it, LR_XYZ)
+                changed = any(strategy.step(model, it, LR_XYZ))
+            f3.after_step(model, it, changed, args.densify_until)
         if it % args.log == 0 or it == 1:
             losses.append((it, float(loss.item()), int(model._xyz.shape[0])))
             log(f"iter {it:5d}  loss {losses[-1][1]:.5f}  gaussians {losses[-1][2]}")
@@ -266,12 +306,15 @@ def train(args, log=print):
 def default_args(**kw):
     d = dict(gaussians=200_000, iters=300, resolution="512x512", views=12, lambda_dssim=0.2, log=50, densify_from=100,
              densify_every=100, densify_until=10_000, exact=False, torch_adam=False, antialiasing=False, absgrad=False,
-             densify_grad_threshold=0.0002, multi_view=0, mcmc=False, cap_max=0, depth_weight=0.0, depth_loss="l1")
+             densify_grad_threshold=0.0002, multi_view=0, mcmc=False, cap_max=0, depth_weight=0.0, depth_loss="l1", filter3d=False)
     d.update(kw)
     return SimpleNamespace(**d)
 
 
 HELP = {
+    "filter3d": "the 3D smoothing filter of Mip-Splatting (luciddreamer_amd.filter3d): render the cloud low-passed per Gaussian by "
+                "the highest sampling rate of any training camera; recomputed after every change of the set and every 100 "
+                "iterations after densification.  Independent of --antialiasing (the 2D Mip filter); Mip-Splatting uses both",
     "mcmc": "MCMC densification (luciddreamer_amd.mcmc.MCMCStrategy) instead of densify_and_prune: dead Gaussians are relocated, "
             "the set grows 5 % per refinement up to --cap-max, a position noise follows every step; no gradient threshold",
     "cap_max": "with --mcmc: the largest number of Gaussians (0: 1.5 x the initial count)",

@@ -591,6 +591,52 @@ int lr_mcmc_reg_grad(int P, const float* raw_opacity, const float* raw_scale, fl
                      float* dL_dopacity, float* dL_dscale, void* stream);
 
 /*
+ * 3D smoothing filter (Yu et al., "Mip-Splatting: Alias-free 3D Gaussian Splatting", 2024): the half of Mip-Splatting that acts
+ * on the Gaussians themselves; the other half, the 2D Mip filter, is lr_set_antialiasing, and the two are independent.  Every
+ * Gaussian is convolved with an isotropic low-pass whose size follows the highest sampling rate at which any training camera
+ * sees it (luciddreamer_amd/filter3d.py drives it).  All tensors float32, contiguous, device.
+ *
+ *   lr_filter3d_update: cams [V,20] = per camera the 16 floats of world_view_transform M in the row-vector convention the
+ *     rasterizer uses ([x y z 1] M), then fx = W / (2 tan(FoVx / 2)), fy = H / (2 tan(FoVy / 2)), W, H.  With (x, y, z) the
+ *     view-space position, formed as ((M[0][j] px + M[1][j] py) + M[2][j] pz) + M[3][j], camera n SEES Gaussian k iff
+ *         z > 0.2   and   |x / z * fx| <= 0.65 W   and   |y / z * fy| <= 0.65 H
+ *     (the near cull of the rasterizer; the image extended by 15 % on every side).  All of it in float32, one rounding per
+ *     operation, no fused multiply-add.  Then
+ *         d_k = min over the cameras that see k of z / fx        (the reciprocal of the paper's maximal sampling rate)
+ *         filter3D[k] = sqrt(variance) d_k                       (variance: 0.2 in the paper)
+ *     a Gaussian no camera sees gets sqrt(variance) max_k d_k over the seen ones, the widest filter in use, and if no Gaussian
+ *     is seen at all (V == 0 included) every filter is 0 = no filtering.  seen [P] (one byte each, may be NULL) tells which.
+ *     This is the paper's definition; its released code takes min z and max focal length separately, which is the same when
+ *     all cameras share a focal length and a smaller filter otherwise.  Two launches, min and max only: bit-repeatable.
+ *     workspace: lr_filter3d_workspace_bytes(P) device bytes.
+ *   lr_filter3d_apply_forward: r_j = raw_scale[k][j] (log scale), q = raw_opacity[k] (logit), f = filter3D[k]:
+ *         t_j = f^2 exp(-2 r_j),   h_j = log1p(t_j) / 2    (for t_j > 1: log f - r_j + log1p(1 / t_j) / 2, finite for tiny scales)
+ *         log s'_j = r_j + h_j           so that s'_j = sqrt(s_j^2 + f^2)
+ *         log c = -(h_0 + h_1 + h_2)     so that c = sqrt(prod s_j^2 / prod (s_j^2 + f^2))
+ *         o' = sigmoid(q) c
+ *     activated != 0: out_scale = s' = exp(log s'), out_opacity = o'   (what a rasterizer fed with activated values takes)
+ *     activated == 0: out_scale = log s', out_opacity = logit(o') = log sigmoid(q) + log c - log(1 - o'), with
+ *                     1 - o' = sigmoid(-q) + sigmoid(q) (-expm1(log c))   (what every raw-parameter path and a .ply take)
+ *     A row with f <= 0 is not filtered: in the stored domain it keeps its bits.
+ *   lr_filter3d_apply_backward: the gradient of the above with respect to raw_scale and raw_opacity (the filter is a constant),
+ *     recomputed from the inputs; dL_dscale_out [P,3] / dL_dopacity_out [P] are the upstream gradients, NULL = zero.  With
+ *     u_j = 1 / (1 + t_j), w_j = 1 - u_j (both formed without a subtraction):
+ *         activated: dL/dr_j = g_j s'_j u_j + g_o o' w_j              dL/dq = g_o c sigmoid(q) sigmoid(-q)
+ *         stored   : dL/dr_j = g_j u_j + g_o w_j / (1 - o')           dL/dq = g_o sigmoid(-q) / (1 - o')
+ *     Both outputs are written in full.
+ * 36 bytes per Gaussian forward, 52 backward.  P == 0 succeeds and launches nothing.  No host synchronisation.  Checked on the
+ * host (LR_ERR_INVALID_ARG): P, V >= 0, variance finite and >= 0, the required pointers.
+ */
+size_t lr_filter3d_workspace_bytes(int P);
+int lr_filter3d_update(int P, int V, const float* means3D, const float* cams, float variance, float* filter3D,
+                       unsigned char* seen, char* workspace, void* stream);
+int lr_filter3d_apply_forward(int P, const float* raw_scale, const float* raw_opacity, const float* filter3D, int activated,
+                              float* out_scale, float* out_opacity, void* stream);
+int lr_filter3d_apply_backward(int P, const float* raw_scale, const float* raw_opacity, const float* filter3D, int activated,
+                               const float* dL_dscale_out, const float* dL_dopacity_out, float* dL_draw_scale,
+                               float* dL_draw_opacity, void* stream);
+
+/*
  * Fused photometric loss of the training loop:
  *     loss = (1 - lambda) * mean|image - gt| + lambda * (1 - mean(SSIM_map(image, gt)))
  * replacing l1_loss + ssim of R/utils/loss.py:18-69 as composed in R/luciddreamer.py:301-304 (11x11 window = outer

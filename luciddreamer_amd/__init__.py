@@ -14,8 +14,9 @@ def uninstall(handle):
 
 
 def __getattr__(name):
-    """`luciddreamer_amd.mcmc` (MCMCStrategy: relocation, capped growth, position noise) without importing torch with the package."""
-    if name == "mcmc":
+    """`luciddreamer_amd.mcmc` (MCMCStrategy: relocation, capped growth, position noise) and `luciddreamer_amd.filter3d` (the 3D
+    smoothing filter of Mip-Splatting) without importing torch with the package."""
+    if name in ("mcmc", "filter3d"):
         import importlib
-        return importlib.import_module(".mcmc", __name__)
+        return importlib.import_module("." + name, __name__)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

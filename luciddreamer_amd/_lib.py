@@ -40,7 +40,8 @@ EXPORTS = ("lr_last_error", "lr_version", "lr_geom_bytes", "lr_img_bytes", "lr_b
            "lr_video_workspace_bytes", "lr_frames_to_u8", "lr_depth_colorize",
            "lr_masked_l1_dssim_forward", "lr_masked_l1_dssim_backward", "lr_alpha_hole_workspace_bytes", "lr_alpha_hole_forward",
            "lr_alpha_hole_backward", "lr_set_antialiasing", "lr_get_antialiasing",
-           "lr_mcmc_workspace_bytes", "lr_mcmc_relocate", "lr_mcmc_noise", "lr_mcmc_reg_grad")
+           "lr_mcmc_workspace_bytes", "lr_mcmc_relocate", "lr_mcmc_noise", "lr_mcmc_reg_grad",
+           "lr_filter3d_workspace_bytes", "lr_filter3d_update", "lr_filter3d_apply_forward", "lr_filter3d_apply_backward")
 
 # lr_views_workspace_bytes / lr_views_check `parts`: what a step's workspace slots hold besides a view's scratch
 LR_VIEWS_LOSS, LR_VIEWS_DEPTH_LOSS, LR_VIEWS_MASK_LOSS = 1, 2, 4
@@ -267,6 +268,14 @@ def lib():
         L.lr_mcmc_noise.argtypes = [ci, vp, vp, vp, vp, vp, cf, vp]              # P xyz scale rotation opacity noise scaler stream
         L.lr_mcmc_reg_grad.restype = ci
         L.lr_mcmc_reg_grad.argtypes = [ci, vp, vp, cf, cf, vp, vp, vp]           # P opacity scale w_opacity w_scale dL_do dL_ds stream
+        L.lr_filter3d_workspace_bytes.restype = ctypes.c_size_t
+        L.lr_filter3d_workspace_bytes.argtypes = [ci]
+        L.lr_filter3d_update.restype = ci
+        L.lr_filter3d_update.argtypes = [ci, ci, vp, vp, cf, vp, vp, vp, vp]     # P V means3D cams variance filter seen workspace stream
+        L.lr_filter3d_apply_forward.restype = ci
+        L.lr_filter3d_apply_forward.argtypes = [ci, vp, vp, vp, ci, vp, vp, vp]  # P scale opacity filter activated out_scale out_opacity stream
+        L.lr_filter3d_apply_backward.restype = ci
+        L.lr_filter3d_apply_backward.argtypes = [ci, vp, vp, vp, ci, vp, vp, vp, vp, vp]   # ... g_scale g_opacity d_scale d_opacity stream
         L.lr_step_begin.restype = ci
         L.lr_step_begin.argtypes = []
         L.lr_step_end.restype = ci

@@ -35,6 +35,9 @@ SOURCES = {
     "rows.hip": [],
     "adam.hip": [],
     "mcmc.hip": [],             # MCMC densification: relocation / growth, position noise, regulariser gradients
+    # 3D smoothing filter: the visibility tests are the header's float32 operations, one rounding each (a host restatement
+    # agrees to the bit): no FMA contraction
+    "filter3d.hip": ["-ffp-contract=off"],
     # video frames: bit-exact to numpy's float32 operations (np.round, np.percentile, colorize's normalisation): no FMA contraction
     "video.hip": ["-ffp-contract=off"],
     "api.hip": [],

@@ -548,6 +548,16 @@ void launch_mcmc_noise(int P, float* xyz, const float* raw_scale, const float* r
                        const float* noise, float scaler, hipStream_t s);
 void launch_mcmc_reg_grad(int P, const float* raw_opacity, const float* raw_scale, float opacity_reg, float scale_reg,
                           float* dL_dopacity, float* dL_dscale, hipStream_t s);
+// 3D smoothing filter of Mip-Splatting (filter3d.hip): the per-Gaussian filter size from the cameras' sampling rates, and the
+// filter applied to the stored scale / opacity in the stored (log, logit) or the activated domain.  cams: device [V,20] (16 matrix
+// floats in the row-vector convention, fx, fy, W, H); ws: filter3d_workspace_bytes(P) device bytes; a NULL upstream is zero.
+size_t filter3d_workspace_bytes(int P);
+void launch_filter3d_update(int P, int V, const float* means3D, const float* cams, float variance, float* filter3D,
+                            unsigned char* seen, char* ws, hipStream_t s);
+void launch_filter3d_apply_forward(int P, const float* raw_scale, const float* raw_opacity, const float* filter3D, bool activated,
+                                   float* out_scale, float* out_opacity, hipStream_t s);
+void launch_filter3d_apply_backward(int P, const float* raw_scale, const float* raw_opacity, const float* filter3D, bool activated,
+                                    const float* g_scale, const float* g_opacity, float* d_scale, float* d_opacity, hipStream_t s);
 // fused L1 + DSSIM loss (loss.hip)
 size_t loss_workspace_bytes(int C, int H, int W);
 // defer_final: leave {loss, l1, ssim} to the launch_loss_backward(..., final_out3) that follows on the same stream
