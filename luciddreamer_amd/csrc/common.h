@@ -558,43 +558,60 @@ void launch_filter3d_apply_forward(int P, const float* raw_scale, const float* r
                                    float* out_scale, float* out_opacity, hipStream_t s);
 void launch_filter3d_apply_backward(int P, const float* raw_scale, const float* raw_opacity, const float* filter3D, bool activated,
                                     const float* g_scale, const float* g_opacity, float* d_scale, float* d_opacity, hipStream_t s);
-// fused L1 + DSSIM loss (loss.hip)
+// ---- loss terms (loss.hip) ----
+// Where a term's value goes.  LOSS_VALUE: the term alone, out[0] = weight * term (the colour pair: out = {loss, l1, ssim}; the
+// Pearson term: out = {loss, rho}).  In a step, out is the view's row {loss, l1, ssim[, depth term[, alpha_hole]]}: the colour
+// pair fills its first three floats, a later term does out[0] += weight * term and writes its own slot -- LOSS_ROW: by the
+// forward's final kernel; LOSS_ROW_BY_BACKWARD: by workgroup 0 of the backward kernel that follows on the same stream (the
+// forward launches no final kernel then: one launch less per term).  A backward given anything else writes no value.
+// row_has_depth (the alpha hole term in a row): false for a step without a depth term, whose out[3] the term sets to 0.
+enum LossValueWhere { LOSS_VALUE, LOSS_ROW, LOSS_ROW_BY_BACKWARD };
+struct LossValue {
+    LossValueWhere where;
+    float* out;
+    bool row_has_depth;
+    float* by_backward() const { return where == LOSS_ROW_BY_BACKWARD ? out : nullptr; }
+};
+inline LossValue loss_value(float* out) { return { LOSS_VALUE, out, true }; }
+inline LossValue loss_value_by_forward() { return { LOSS_VALUE, nullptr, true }; }     // for the backward of such a forward
+// fused L1 + DSSIM of one image pair, what its forward and its backward share.  mask != nullptr: the masked pair (mask [H,W]
+// shared by the C channels): the loss of (m img, m gt), dL/dimg = m dL/d(m img).  ws: loss_workspace_bytes(C, H, W), written by
+// the forward and read by the backward.
+struct LossPair {
+    int C, H, W;
+    const float* img;
+    const float* gt;
+    const float* mask;
+    float lambda;
+    char* ws;
+};
 size_t loss_workspace_bytes(int C, int H, int W);
-// defer_final: leave {loss, l1, ssim} to the launch_loss_backward(..., final_out3) that follows on the same stream
-// (workgroup 0 of the backward kernel sums the partials: one launch less per view in the fused step)
-// mask != nullptr: the masked pair (mask [H,W] shared by the C channels): the loss of (m img, m gt), dL/dimg = m dL/d(m img)
-void launch_loss_forward(int C, int H, int W, const float* img, const float* gt, float lambda, float* out3, char* ws,
-                         hipStream_t s, bool defer_final = false, const float* mask = nullptr);
-void launch_loss_backward(int C, int H, int W, const float* img, const float* gt, float lambda, const float* upstream,
-                          const char* ws, float* grad, hipStream_t s, float* final_out3 = nullptr, const float* w_ssim = nullptr,
-                          const float* mask = nullptr);
-// masked depth L1 (loss.hip).  The value, by final_mode: DEPTH_L1_VALUE out[0] = weight * mean(|depth - target| [target > 0]);
-// DEPTH_L1_FUSED (fused step, out = the view's {loss, l1, ssim, depth_l1}) out[0] += weight * mean, out[3] = mean;
-// DEPTH_L1_DEFER left to launch_depth_l1_backward(..., fused_out), which does what DEPTH_L1_FUSED does
-enum DepthL1Final { DEPTH_L1_VALUE = 0, DEPTH_L1_FUSED = 1, DEPTH_L1_DEFER = 2 };
+void launch_loss_forward(const LossPair& p, LossValue value, hipStream_t s);
+// dL/dimg = upstream * dL/dimg of the lambda mix (device scalars; a NULL upstream is 1), or, with w_ssim != nullptr,
+// upstream * d l1/dimg + w_ssim * d ssim/dimg (lambda is not read then)
+void launch_loss_backward(const LossPair& p, const float* upstream, const float* w_ssim, float* grad, LossValue value,
+                          hipStream_t s);
+// masked depth L1: the term is mean(|depth - target| [target > 0]), its row slot out[3]
 size_t depth_l1_workspace_bytes(int H, int W);
-void launch_depth_l1_forward(int H, int W, const float* depth, const float* target, float weight, float* out, char* ws,
-                             hipStream_t s, DepthL1Final final_mode = DEPTH_L1_VALUE);
+void launch_depth_l1_forward(int H, int W, const float* depth, const float* target, float weight, char* ws, LossValue value,
+                             hipStream_t s);
 void launch_depth_l1_backward(int H, int W, const float* depth, const float* target, float weight, const float* upstream,
-                              const char* ws, float* grad, hipStream_t s, float* fused_out = nullptr);
-// Pearson depth loss (loss.hip): weight * (1 - rho) over the pixels with target > 0, sums in double.  The forward (two launches:
-// partials, then one workgroup) leaves the partials and the coefficient record in ws and writes out = {loss, rho}, or, fused
-// (the fused step's {loss, l1, ssim, depth term}), out[0] += weight * term, out[3] = term; the backward reads that record.
+                              const char* ws, float* grad, LossValue value, hipStream_t s);
+// Pearson depth loss: the term is 1 - rho over the pixels with target > 0, sums in double, its row slot out[3].  The forward (two
+// launches: partials, then one workgroup) leaves the partials and the coefficient record in ws and always forms the value itself
+// (LOSS_VALUE or LOSS_ROW); the backward reads that record.
 size_t depth_pearson_workspace_bytes(int H, int W);
-void launch_depth_pearson_forward(int H, int W, const float* depth, const float* target, float weight, float* out, char* ws,
-                                  hipStream_t s, bool fused = false);
+void launch_depth_pearson_forward(int H, int W, const float* depth, const float* target, float weight, char* ws, LossValue value,
+                                  hipStream_t s);
 void launch_depth_pearson_backward(int H, int W, const float* depth, const float* target, float weight, const float* upstream,
                                    const char* ws, float* grad, hipStream_t s);
-// alpha hole term (loss.hip): weight * mean(A (1 - m)) with A the alpha image, or 1 - src when from_T (src = the blend forward's
-// final_T; alpha_out, if given, receives that A).  final_mode as the depth L1's, the fused value going to out[4]
-// ({loss, l1, ssim, depth_l1, alpha_hole}; fused_no_depth: out[3] = 0 as well, a step without a depth term); the backward
-// writes dL/dA = upstream * weight * (1 - m) / (H*W).
+// alpha hole term: mean(A (1 - m)) with A the alpha image, or 1 - src when from_T (src = the blend forward's final_T; alpha_out,
+// if not NULL, receives that A), its row slot out[4]; the backward writes dL/dA = upstream * weight * (1 - m) / (H*W).
 size_t alpha_hole_workspace_bytes(int H, int W);
-void launch_alpha_hole_forward(int H, int W, const float* src, bool from_T, const float* mask, float weight, float* out, char* ws,
-                               hipStream_t s, DepthL1Final final_mode = DEPTH_L1_VALUE, float* alpha_out = nullptr,
-                               bool fused_no_depth = false);
-void launch_alpha_hole_backward(int H, int W, const float* mask, float weight, const float* upstream, const char* ws,
-                                float* grad, hipStream_t s, float* fused_out = nullptr, bool fused_no_depth = false);
+void launch_alpha_hole_forward(int H, int W, const float* src, bool from_T, float* alpha_out, const float* mask, float weight,
+                               char* ws, LossValue value, hipStream_t s);
+void launch_alpha_hole_backward(int H, int W, const float* mask, float weight, const float* upstream, const char* ws, float* grad,
+                                LossValue value, hipStream_t s);
 // bit positions of lr_backward's accumulate_mask (LR_ACC_* in lucid_raster.h)
 enum { ACC_MEAN2D = 0, ACC_CONIC = 1, ACC_OPACITY = 2, ACC_COLOR = 3, ACC_MEAN3D = 4, ACC_COV3D = 5, ACC_SH = 6,
        ACC_SCALE = 7, ACC_ROT = 8 };

@@ -240,7 +240,8 @@ k_depth_l1_bwd(int n, float weight, const float* __restrict__ upstream, const fl
 //     loss = weight * mean_{H*W}( A * (1 - m) ),   d loss / d A = weight * (1 - m) / (H*W)
 // A = 1 - T_final, the alpha output; m [H,W] the content mask in [0, 1].  The forward reads A -- or T_final itself, from_T, and
 // forms A = 1 - T_final as lr_render_alpha does, writing it to alpha_out when the caller keeps the alpha image.  Partials,
-// fixed-order double reduction and the DEFER / FUSED finalisation as k_depth_l1_*; the fused value goes to out[4].
+// fixed-order double reduction and the value formed by the final kernel or by the backward (LossValue) as k_depth_l1_*; the
+// row slot is out[4].
 __global__ void __launch_bounds__(LTHREADS)
 k_alpha_hole_fwd(int n, const float* __restrict__ src, int from_T, const float* __restrict__ mask, double* __restrict__ partials,
                  float* __restrict__ alpha_out)
@@ -472,41 +473,43 @@ size_t loss_workspace_bytes(int C, int H, int W)
     return align_up(3 * n * sizeof(float)) + align_up(blocks * sizeof(float2));
 }
 
-void launch_loss_forward(int C, int H, int W, const float* img, const float* gt, float lambda, float* out3, char* ws,
-                         hipStream_t s, bool defer_final, const float* mask)
+void launch_loss_forward(const LossPair& p, LossValue value, hipStream_t s)
 {
     static const Win win = make_window();
-    const size_t n = (size_t)C * H * W;
+    const int H = p.H, W = p.W;
+    const size_t n = (size_t)p.C * H * W;
     const int tx = (W + LT - 1) / LT, ty = (H + LT - 1) / LT;
-    const int blocks = C * tx * ty;
-    float* D = reinterpret_cast<float*>(ws);
-    float2* partials = reinterpret_cast<float2*>(ws + align_up(3 * n * sizeof(float)));
-    if (mask != nullptr)
-        hipLaunchKernelGGL(k_ssim_fwd_masked, dim3((blocks + 7) / 8 * 8), dim3(LTHREADS), 0, s, H, W, tx, ty, win, img, gt, mask, D,
-                           D + n, D + 2 * n, partials, blocks);
+    const int blocks = p.C * tx * ty;
+    float* D = reinterpret_cast<float*>(p.ws);
+    float2* partials = reinterpret_cast<float2*>(p.ws + align_up(3 * n * sizeof(float)));
+    if (p.mask != nullptr)
+        hipLaunchKernelGGL(k_ssim_fwd_masked, dim3((blocks + 7) / 8 * 8), dim3(LTHREADS), 0, s, H, W, tx, ty, win, p.img, p.gt,
+                           p.mask, D, D + n, D + 2 * n, partials, blocks);
     else
-        hipLaunchKernelGGL(k_ssim_fwd, dim3((blocks + 7) / 8 * 8), dim3(LTHREADS), 0, s, H, W, tx, ty, win, img, gt, D, D + n,
+        hipLaunchKernelGGL(k_ssim_fwd, dim3((blocks + 7) / 8 * 8), dim3(LTHREADS), 0, s, H, W, tx, ty, win, p.img, p.gt, D, D + n,
                            D + 2 * n, partials, blocks);
-    if (!defer_final)      // otherwise launch_loss_backward(..., final_out3) follows on the same stream and forms the value
-        hipLaunchKernelGGL(k_loss_final, dim3(1), dim3(LTHREADS), 0, s, blocks, (double)n, lambda, partials, out3);
+    if (value.where != LOSS_ROW_BY_BACKWARD)     // the pair's three floats lead the row: one final kernel for value and row
+        hipLaunchKernelGGL(k_loss_final, dim3(1), dim3(LTHREADS), 0, s, blocks, (double)n, p.lambda, partials, value.out);
 }
 
-void launch_loss_backward(int C, int H, int W, const float* img, const float* gt, float lambda, const float* upstream,
-                          const char* ws, float* grad, hipStream_t s, float* final_out3, const float* w_ssim, const float* mask)
+void launch_loss_backward(const LossPair& p, const float* upstream, const float* w_ssim, float* grad, LossValue value,
+                          hipStream_t s)
 {
     static const Win win = make_window();
-    const size_t n = (size_t)C * H * W;
+    const int H = p.H, W = p.W;
+    const size_t n = (size_t)p.C * H * W;
     const int tx = (W + LT - 1) / LT, ty = (H + LT - 1) / LT;
-    const float* D = reinterpret_cast<const float*>(ws);
-    const float2* partials = reinterpret_cast<const float2*>(ws + align_up(3 * n * sizeof(float)));
-    if (mask != nullptr)
-        hipLaunchKernelGGL(k_ssim_bwd_masked, dim3((C * tx * ty + 7) / 8 * 8), dim3(LTHREADS), 0, s, H, W, tx, ty, win, lambda,
-                           (float)(1.0 / (double)n), upstream, w_ssim, img, gt, mask, D, D + n, D + 2 * n, grad, partials, C * tx * ty,
-                           (double)n, final_out3);
+    const int blocks = p.C * tx * ty;
+    const float* D = reinterpret_cast<const float*>(p.ws);
+    const float2* partials = reinterpret_cast<const float2*>(p.ws + align_up(3 * n * sizeof(float)));
+    if (p.mask != nullptr)
+        hipLaunchKernelGGL(k_ssim_bwd_masked, dim3((blocks + 7) / 8 * 8), dim3(LTHREADS), 0, s, H, W, tx, ty, win, p.lambda,
+                           (float)(1.0 / (double)n), upstream, w_ssim, p.img, p.gt, p.mask, D, D + n, D + 2 * n, grad, partials,
+                           blocks, (double)n, value.by_backward());
     else
-        hipLaunchKernelGGL(k_ssim_bwd, dim3((C * tx * ty + 7) / 8 * 8), dim3(LTHREADS), 0, s, H, W, tx, ty, win, lambda,
-                           (float)(1.0 / (double)n), upstream, w_ssim, img, gt, D, D + n, D + 2 * n, grad, partials, C * tx * ty,
-                           (double)n, final_out3);
+        hipLaunchKernelGGL(k_ssim_bwd, dim3((blocks + 7) / 8 * 8), dim3(LTHREADS), 0, s, H, W, tx, ty, win, p.lambda,
+                           (float)(1.0 / (double)n), upstream, w_ssim, p.img, p.gt, D, D + n, D + 2 * n, grad, partials, blocks,
+                           (double)n, value.by_backward());
 }
 
 }  // namespace lr
@@ -519,26 +522,25 @@ size_t depth_l1_workspace_bytes(int H, int W)
     return align_up(((n + DL_BLOCK - 1) / DL_BLOCK) * sizeof(double));
 }
 
-void launch_depth_l1_forward(int H, int W, const float* depth, const float* target, float weight, float* out, char* ws,
-                             hipStream_t s, DepthL1Final final_mode)
+void launch_depth_l1_forward(int H, int W, const float* depth, const float* target, float weight, char* ws, LossValue value,
+                             hipStream_t s)
 {
     const int n = H * W;
     const int blocks = (n + DL_BLOCK - 1) / DL_BLOCK;
     double* partials = reinterpret_cast<double*>(ws);
     hipLaunchKernelGGL(k_depth_l1_fwd, dim3(blocks), dim3(LTHREADS), 0, s, n, depth, target, partials);
-    // DEPTH_L1_DEFER: launch_depth_l1_backward(..., fused_out) follows on the same stream and forms the value
-    if (final_mode != DEPTH_L1_DEFER)
-        hipLaunchKernelGGL(k_depth_l1_final, dim3(1), dim3(LTHREADS), 0, s, blocks, (double)n, weight, partials, out,
-                           final_mode == DEPTH_L1_FUSED ? 1 : 0);
+    if (value.where != LOSS_ROW_BY_BACKWARD)
+        hipLaunchKernelGGL(k_depth_l1_final, dim3(1), dim3(LTHREADS), 0, s, blocks, (double)n, weight, partials, value.out,
+                           value.where == LOSS_ROW ? 1 : 0);
 }
 
 void launch_depth_l1_backward(int H, int W, const float* depth, const float* target, float weight, const float* upstream,
-                              const char* ws, float* grad, hipStream_t s, float* fused_out)
+                              const char* ws, float* grad, LossValue value, hipStream_t s)
 {
     const int n = H * W;
     const int blocks = (n + DL_BLOCK - 1) / DL_BLOCK;
     hipLaunchKernelGGL(k_depth_l1_bwd, dim3(blocks), dim3(LTHREADS), 0, s, n, weight, upstream, depth, target, grad,
-                       reinterpret_cast<const double*>(ws), blocks, fused_out);
+                       reinterpret_cast<const double*>(ws), blocks, value.by_backward());
 }
 
 }  // namespace lr
@@ -557,15 +559,16 @@ size_t depth_pearson_workspace_bytes(int H, int W)
     return depth_pearson_record_offset(H, W) + align_up(DP_RECORD * sizeof(double));
 }
 
-void launch_depth_pearson_forward(int H, int W, const float* depth, const float* target, float weight, float* out, char* ws,
-                                  hipStream_t s, bool fused)
+void launch_depth_pearson_forward(int H, int W, const float* depth, const float* target, float weight, char* ws, LossValue value,
+                                  hipStream_t s)
 {
     const int n = H * W;
     const int blocks = (n + DL_BLOCK - 1) / DL_BLOCK;
     double* partials = reinterpret_cast<double*>(ws);
     double* record = reinterpret_cast<double*>(ws + depth_pearson_record_offset(H, W));
     hipLaunchKernelGGL(k_depth_pearson_fwd, dim3(blocks), dim3(LTHREADS), 0, s, n, depth, target, partials);
-    hipLaunchKernelGGL(k_depth_pearson_final, dim3(1), dim3(LTHREADS), 0, s, blocks, weight, partials, record, out, fused ? 1 : 0);
+    hipLaunchKernelGGL(k_depth_pearson_final, dim3(1), dim3(LTHREADS), 0, s, blocks, weight, partials, record, value.out,
+                       value.where == LOSS_VALUE ? 0 : 1);
 }
 
 void launch_depth_pearson_backward(int H, int W, const float* depth, const float* target, float weight, const float* upstream,
@@ -583,27 +586,26 @@ namespace lr {
 
 size_t alpha_hole_workspace_bytes(int H, int W) { return depth_l1_workspace_bytes(H, W); }
 
-void launch_alpha_hole_forward(int H, int W, const float* src, bool from_T, const float* mask, float weight, float* out, char* ws,
-                               hipStream_t s, DepthL1Final final_mode, float* alpha_out, bool fused_no_depth)
+void launch_alpha_hole_forward(int H, int W, const float* src, bool from_T, float* alpha_out, const float* mask, float weight,
+                               char* ws, LossValue value, hipStream_t s)
 {
     const int n = H * W;
     const int blocks = (n + DL_BLOCK - 1) / DL_BLOCK;
     double* partials = reinterpret_cast<double*>(ws);
     hipLaunchKernelGGL(k_alpha_hole_fwd, dim3(blocks), dim3(LTHREADS), 0, s, n, src, from_T ? 1 : 0, mask, partials,
                        from_T ? alpha_out : nullptr);
-    // DEPTH_L1_DEFER: launch_alpha_hole_backward(..., fused_out) follows on the same stream and forms the value
-    if (final_mode != DEPTH_L1_DEFER)
-        hipLaunchKernelGGL(k_alpha_hole_final, dim3(1), dim3(LTHREADS), 0, s, blocks, (double)n, weight, partials, out,
-                           final_mode == DEPTH_L1_FUSED ? (fused_no_depth ? 2 : 1) : 0);
+    if (value.where != LOSS_ROW_BY_BACKWARD)
+        hipLaunchKernelGGL(k_alpha_hole_final, dim3(1), dim3(LTHREADS), 0, s, blocks, (double)n, weight, partials, value.out,
+                           value.where == LOSS_ROW ? (value.row_has_depth ? 1 : 2) : 0);
 }
 
-void launch_alpha_hole_backward(int H, int W, const float* mask, float weight, const float* upstream, const char* ws,
-                                float* grad, hipStream_t s, float* fused_out, bool fused_no_depth)
+void launch_alpha_hole_backward(int H, int W, const float* mask, float weight, const float* upstream, const char* ws, float* grad,
+                                LossValue value, hipStream_t s)
 {
     const int n = H * W;
     const int blocks = (n + DL_BLOCK - 1) / DL_BLOCK;
     hipLaunchKernelGGL(k_alpha_hole_bwd, dim3(blocks), dim3(LTHREADS), 0, s, n, weight, upstream, mask, grad,
-                       reinterpret_cast<const double*>(ws), blocks, fused_out, fused_no_depth ? 2 : 1);
+                       reinterpret_cast<const double*>(ws), blocks, value.by_backward(), value.row_has_depth ? 1 : 2);
 }
 
 }  // namespace lr

@@ -11,14 +11,22 @@ import torch
 
 from . import _lib
 
-_WS_BYTES = {}                      # (C, H, W) -> lr_loss_workspace_bytes: a C call per forward otherwise
+_WS_BYTES = {}                      # (size query's name, dims) -> its answer: a C call per forward otherwise
 
 
-def _ws_bytes(L, C, H, W):
-    n = _WS_BYTES.get((C, H, W))
+def _ws_bytes(query, *dims):
+    n = _WS_BYTES.get((query, dims))
     if n is None:
-        n = _WS_BYTES[(C, H, W)] = int(L.lr_loss_workspace_bytes(C, H, W))
+        n = _WS_BYTES[(query, dims)] = int(getattr(_lib.lib(), query)(*dims))
     return n
+
+
+def _call(fn, what, dev, *args):
+    """fn(*args, the current stream of dev) with dev the current HIP device; a refusal raises as `what`."""
+    with _lib.on_device(dev):
+        rc = fn(*args, torch.cuda.current_stream(dev).cuda_stream)
+    if rc < 0:
+        _lib.raise_for(rc, what)
 
 
 def _weight(t, dev):
@@ -31,45 +39,81 @@ def _weight(t, dev):
     return t.detach().to(device=dev, dtype=torch.float32).reshape(1).contiguous()
 
 
+def _image_pair(image, gt):
+    """(image, gt, C, H, W) of a float32 device pair of one [..., H, W] shape, contiguous."""
+    if not image.is_cuda or not gt.is_cuda:
+        raise RuntimeError("luciddreamer_amd.loss: image and gt must be on a HIP device (no CPU path)")
+    if image.shape != gt.shape or image.dim() < 2:
+        raise RuntimeError(f"image {tuple(image.shape)} and gt {tuple(gt.shape)} must have the same [..., H, W] shape")
+    if image.dtype != torch.float32 or gt.dtype != torch.float32:
+        raise RuntimeError("image and gt must be float32")
+    x, g = image.contiguous(), gt.contiguous()
+    H, W = int(x.shape[-2]), int(x.shape[-1])
+    return x, g, x.numel() // (H * W), H, W
+
+
+def _plane(t, name, what):
+    """A float32 device plane [1,H,W] or [H,W], contiguous."""
+    if not t.is_cuda:
+        raise RuntimeError(f"luciddreamer_amd.loss.{what}: {name} must be on a HIP device (no CPU path)")
+    if t.dtype != torch.float32:
+        raise RuntimeError(f"{name} must be float32")
+    if not (t.dim() == 2 or (t.dim() == 3 and t.shape[0] == 1)):
+        raise RuntimeError(f"{name} {tuple(t.shape)} must be [1,H,W] or [H,W]")
+    return t.contiguous()
+
+
+def _depth_pair(depth, target, what):
+    """(depth, target, H, W) of two planes of one H, W."""
+    d, t = _plane(depth, "depth", what), _plane(target, "target", what)
+    if d.shape[-2:] != t.shape[-2:]:
+        raise RuntimeError(f"depth {tuple(depth.shape)} and target {tuple(target.shape)} must be [1,H,W] or [H,W] of one H, W")
+    return d, t, int(d.shape[-2]), int(d.shape[-1])
+
+
+def _mask_hw(mask, H, W, dev):
+    if not mask.is_cuda or mask.device != dev or mask.dtype != torch.float32:
+        raise RuntimeError("mask must be a float32 tensor on the device of the image")
+    if tuple(mask.shape) not in ((H, W), (1, H, W)):
+        raise RuntimeError(f"mask {tuple(mask.shape)} must be [1,H,W] or [H,W] with H,W = {H},{W}")
+    return mask.contiguous()
+
+
+def _pair_forward(ctx, what, image, gt, lam, mask=None):
+    """One lr_l1_dssim_forward (lr_masked_l1_dssim_forward with a mask): {loss, l1, ssim} on the device, and on ctx what the
+    three colour backwards read."""
+    x, g, C, H, W = _image_pair(image, gt)
+    dev = x.device
+    m = None if mask is None else _mask_hw(mask, H, W, dev)
+    L = _lib.lib()
+    out3 = torch.empty((3,), dtype=torch.float32, device=dev)
+    ws = torch.empty((_ws_bytes("lr_loss_workspace_bytes", C, H, W),), dtype=torch.uint8, device=dev)
+    if m is None:
+        _call(L.lr_l1_dssim_forward, what, dev, C, H, W, x.data_ptr(), g.data_ptr(), lam, out3.data_ptr(), ws.data_ptr(), ws.numel())
+        ctx.save_for_backward(x, g, ws)
+    else:
+        _call(L.lr_masked_l1_dssim_forward, what, dev, C, H, W, x.data_ptr(), g.data_ptr(), m.data_ptr(), lam, out3.data_ptr(),
+              ws.data_ptr(), ws.numel())
+        ctx.save_for_backward(x, g, m, ws)
+    ctx.lam, ctx.dims, ctx.in_shape = lam, (C, H, W), image.shape
+    return out3
+
+
 class _L1DSSIM(torch.autograd.Function):
     @staticmethod
     def forward(ctx, image, gt, lambda_dssim):
-        if not image.is_cuda or not gt.is_cuda:
-            raise RuntimeError("luciddreamer_amd.loss: image and gt must be on a HIP device (no CPU path)")
-        if image.shape != gt.shape or image.dim() < 2:
-            raise RuntimeError(f"image {tuple(image.shape)} and gt {tuple(gt.shape)} must have the same [..., H, W] shape")
-        if image.dtype != torch.float32 or gt.dtype != torch.float32:
-            raise RuntimeError("image and gt must be float32")
-        x, g = image.contiguous(), gt.contiguous()
-        H, W = int(x.shape[-2]), int(x.shape[-1])
-        C = x.numel() // (H * W)
-        L = _lib.lib()
-        dev = x.device
-        out3 = torch.empty((3,), dtype=torch.float32, device=dev)
-        ws = torch.empty((_ws_bytes(L, C, H, W),), dtype=torch.uint8, device=dev)
-        with _lib.on_device(dev):
-            rc = L.lr_l1_dssim_forward(C, H, W, x.data_ptr(), g.data_ptr(), float(lambda_dssim), out3.data_ptr(),
-                                       ws.data_ptr(), ws.numel(), torch.cuda.current_stream(dev).cuda_stream)
-        if rc < 0:
-            _lib.raise_for(rc, "l1_dssim_loss")
-        ctx.save_for_backward(x, g, ws)
-        ctx.lam, ctx.dims, ctx.in_shape = float(lambda_dssim), (C, H, W), image.shape
+        out3 = _pair_forward(ctx, "l1_dssim_loss", image, gt, float(lambda_dssim))
         ctx.parts = out3                      # {loss, l1, ssim}, device
         return out3[0]
 
     @staticmethod
     def backward(ctx, grad_out):
         x, g, ws = ctx.saved_tensors
-        C, H, W = ctx.dims
-        L = _lib.lib()
         dev = x.device
         up = _weight(grad_out, dev)
         grad = torch.empty_like(x)
-        with _lib.on_device(dev):
-            rc = L.lr_l1_dssim_backward(C, H, W, x.data_ptr(), g.data_ptr(), ctx.lam, up.data_ptr(), ws.data_ptr(),
-                                        grad.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
-        if rc < 0:
-            _lib.raise_for(rc, "l1_dssim_loss backward")
+        _call(_lib.lib().lr_l1_dssim_backward, "l1_dssim_loss backward", dev, *ctx.dims, x.data_ptr(), g.data_ptr(), ctx.lam,
+              up.data_ptr(), ws.data_ptr(), grad.data_ptr())
         return grad.view(ctx.in_shape), None, None
 
 
@@ -97,39 +141,17 @@ class _L1SSIMPair(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, image, gt):
-        if not image.is_cuda or not gt.is_cuda:
-            raise RuntimeError("luciddreamer_amd.loss: image and gt must be on a HIP device (no CPU path)")
-        if image.shape != gt.shape or image.dim() < 2 or image.dtype != torch.float32 or gt.dtype != torch.float32:
-            raise RuntimeError("image and gt must be float32 tensors of the same [..., H, W] shape")
-        x, g = image.contiguous(), gt.contiguous()
-        H, W = int(x.shape[-2]), int(x.shape[-1])
-        C = x.numel() // (H * W)
-        L = _lib.lib()
-        dev = x.device
-        out3 = torch.empty((3,), dtype=torch.float32, device=dev)
-        ws = torch.empty((_ws_bytes(L, C, H, W),), dtype=torch.uint8, device=dev)
-        with _lib.on_device(dev):
-            rc = L.lr_l1_dssim_forward(C, H, W, x.data_ptr(), g.data_ptr(), 0.0, out3.data_ptr(), ws.data_ptr(), ws.numel(),
-                                       torch.cuda.current_stream(dev).cuda_stream)
-        if rc < 0:
-            _lib.raise_for(rc, "l1 / ssim pair")
-        ctx.save_for_backward(x, g, ws)
-        ctx.dims, ctx.in_shape = (C, H, W), image.shape
+        out3 = _pair_forward(ctx, "l1 / ssim pair", image, gt, 0.0)
         return out3[1], out3[2]
 
     @staticmethod
     def backward(ctx, g_l1, g_ssim):
         x, g, ws = ctx.saved_tensors
-        C, H, W = ctx.dims
-        L = _lib.lib()
         dev = x.device
         w1, w2 = _weight(g_l1, dev), _weight(g_ssim, dev)
         grad = torch.empty_like(x)
-        with _lib.on_device(dev):
-            rc = L.lr_l1_dssim_backward_weights(C, H, W, x.data_ptr(), g.data_ptr(), w1.data_ptr(), w2.data_ptr(), ws.data_ptr(),
-                                                grad.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
-        if rc < 0:
-            _lib.raise_for(rc, "l1 / ssim pair backward")
+        _call(_lib.lib().lr_l1_dssim_backward_weights, "l1 / ssim pair backward", dev, *ctx.dims, x.data_ptr(), g.data_ptr(),
+              w1.data_ptr(), w2.data_ptr(), ws.data_ptr(), grad.data_ptr())
         return grad.view(ctx.in_shape), None
 
 
@@ -181,37 +203,21 @@ class PairedLoss:
         return self._get(img1, img2)[1]
 
 
-_DEPTH_WS_BYTES = {}                # (H, W) -> lr_depth_l1_workspace_bytes
-
-
-def _depth_dims(depth, target):
-    if not depth.is_cuda or not target.is_cuda:
-        raise RuntimeError("luciddreamer_amd.loss.depth_l1: depth and target must be on a HIP device (no CPU path)")
-    if depth.dtype != torch.float32 or target.dtype != torch.float32:
-        raise RuntimeError("depth and target must be float32")
-    ok = lambda t: t.dim() == 2 or (t.dim() == 3 and t.shape[0] == 1)
-    if not ok(depth) or not ok(target) or depth.shape[-2:] != target.shape[-2:]:
-        raise RuntimeError(f"depth {tuple(depth.shape)} and target {tuple(target.shape)} must be [1,H,W] or [H,W] of one H, W")
-    return int(depth.shape[-2]), int(depth.shape[-1])
+def _plane_forward(fn, query, what, n_out, H, W, a, b, weight):
+    """One forward of a plane term over the planes a, b: (out [n_out], workspace)."""
+    dev = a.device
+    out = torch.empty((n_out,), dtype=torch.float32, device=dev)
+    ws = torch.empty((_ws_bytes(query, H, W),), dtype=torch.uint8, device=dev)
+    _call(fn, what, dev, H, W, a.data_ptr(), b.data_ptr(), weight, out.data_ptr(), ws.data_ptr(), ws.numel())
+    return out, ws
 
 
 class _DepthL1(torch.autograd.Function):
     @staticmethod
     def forward(ctx, depth, target, weight):
-        H, W = _depth_dims(depth, target)
-        d, t = depth.contiguous(), target.contiguous()
-        L = _lib.lib()
-        dev = d.device
-        n = _DEPTH_WS_BYTES.get((H, W))
-        if n is None:
-            n = _DEPTH_WS_BYTES[(H, W)] = int(L.lr_depth_l1_workspace_bytes(H, W))
-        out = torch.empty((1,), dtype=torch.float32, device=dev)
-        ws = torch.empty((n,), dtype=torch.uint8, device=dev)
-        with _lib.on_device(dev):
-            rc = L.lr_depth_l1_forward(H, W, d.data_ptr(), t.data_ptr(), float(weight), out.data_ptr(), ws.data_ptr(),
-                                       ws.numel(), torch.cuda.current_stream(dev).cuda_stream)
-        if rc < 0:
-            _lib.raise_for(rc, "depth_l1")
+        d, t, H, W = _depth_pair(depth, target, "depth_l1")
+        out, _ = _plane_forward(_lib.lib().lr_depth_l1_forward, "lr_depth_l1_workspace_bytes", "depth_l1", 1, H, W, d, t,
+                                float(weight))
         ctx.save_for_backward(d, t)
         ctx.weight, ctx.dims, ctx.in_shape = float(weight), (H, W), depth.shape
         return out[0]
@@ -219,16 +225,11 @@ class _DepthL1(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_out):
         d, t = ctx.saved_tensors
-        H, W = ctx.dims
-        L = _lib.lib()
         dev = d.device
         up = _weight(grad_out, dev)
         grad = torch.empty_like(d)
-        with _lib.on_device(dev):
-            rc = L.lr_depth_l1_backward(H, W, d.data_ptr(), t.data_ptr(), ctx.weight, up.data_ptr(), grad.data_ptr(),
-                                        torch.cuda.current_stream(dev).cuda_stream)
-        if rc < 0:
-            _lib.raise_for(rc, "depth_l1 backward")
+        _call(_lib.lib().lr_depth_l1_backward, "depth_l1 backward", dev, *ctx.dims, d.data_ptr(), t.data_ptr(), ctx.weight,
+              up.data_ptr(), grad.data_ptr())
         return grad.view(ctx.in_shape), None, None
 
 
@@ -240,27 +241,11 @@ def depth_l1(depth, target, weight=1.0):
     return _DepthL1.apply(depth, target, weight)
 
 
-_PEARSON_WS_BYTES = {}              # (H, W) -> lr_depth_pearson_workspace_bytes
-
-
 def _pearson_forward(depth, target, weight, what):
     """(d, t, out {loss, rho}, workspace) of one lr_depth_pearson_forward."""
-    if not depth.is_cuda or not target.is_cuda:
-        raise RuntimeError(f"luciddreamer_amd.loss.{what}: depth and target must be on a HIP device (no CPU path)")
-    H, W = _depth_dims(depth, target)
-    d, t = depth.contiguous(), target.contiguous()
-    L = _lib.lib()
-    dev = d.device
-    n = _PEARSON_WS_BYTES.get((H, W))
-    if n is None:
-        n = _PEARSON_WS_BYTES[(H, W)] = int(L.lr_depth_pearson_workspace_bytes(H, W))
-    out = torch.empty((2,), dtype=torch.float32, device=dev)
-    ws = torch.empty((n,), dtype=torch.uint8, device=dev)
-    with _lib.on_device(dev):
-        rc = L.lr_depth_pearson_forward(H, W, d.data_ptr(), t.data_ptr(), float(weight), out.data_ptr(), ws.data_ptr(),
-                                        ws.numel(), torch.cuda.current_stream(dev).cuda_stream)
-    if rc < 0:
-        _lib.raise_for(rc, what)
+    d, t, H, W = _depth_pair(depth, target, what)
+    out, ws = _plane_forward(_lib.lib().lr_depth_pearson_forward, "lr_depth_pearson_workspace_bytes", what, 2, H, W, d, t,
+                             float(weight))
     return d, t, out, ws
 
 
@@ -275,16 +260,11 @@ class _DepthPearson(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_out):
         d, t, ws = ctx.saved_tensors
-        H, W = int(d.shape[-2]), int(d.shape[-1])
-        L = _lib.lib()
         dev = d.device
         up = _weight(grad_out, dev)
         grad = torch.empty_like(d)
-        with _lib.on_device(dev):
-            rc = L.lr_depth_pearson_backward(H, W, d.data_ptr(), t.data_ptr(), ctx.weight, up.data_ptr(), ws.data_ptr(),
-                                             ws.numel(), grad.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
-        if rc < 0:
-            _lib.raise_for(rc, "depth_pearson backward")
+        _call(_lib.lib().lr_depth_pearson_backward, "depth_pearson backward", dev, int(d.shape[-2]), int(d.shape[-1]), d.data_ptr(),
+              t.data_ptr(), ctx.weight, up.data_ptr(), ws.data_ptr(), ws.numel(), grad.data_ptr())
         return grad.view(ctx.in_shape), None, None
 
 
@@ -314,51 +294,19 @@ def content_mask(gt):
     return (gt != 0).any(dim=0, keepdim=True).to(torch.float32)
 
 
-def _mask_hw(mask, H, W, dev):
-    if not mask.is_cuda or mask.device != dev or mask.dtype != torch.float32:
-        raise RuntimeError("mask must be a float32 tensor on the device of the image")
-    if tuple(mask.shape) not in ((H, W), (1, H, W)):
-        raise RuntimeError(f"mask {tuple(mask.shape)} must be [1,H,W] or [H,W] with H,W = {H},{W}")
-    return mask.contiguous()
-
-
 class _MaskedL1DSSIM(torch.autograd.Function):
     @staticmethod
     def forward(ctx, image, gt, mask, lambda_dssim):
-        if not image.is_cuda or not gt.is_cuda:
-            raise RuntimeError("luciddreamer_amd.loss: image and gt must be on a HIP device (no CPU path)")
-        if image.shape != gt.shape or image.dim() < 2 or image.dtype != torch.float32 or gt.dtype != torch.float32:
-            raise RuntimeError("image and gt must be float32 tensors of the same [..., H, W] shape")
-        x, g = image.contiguous(), gt.contiguous()
-        H, W = int(x.shape[-2]), int(x.shape[-1])
-        C = x.numel() // (H * W)
-        m = _mask_hw(mask, H, W, x.device)
-        L = _lib.lib()
-        dev = x.device
-        out3 = torch.empty((3,), dtype=torch.float32, device=dev)
-        ws = torch.empty((_ws_bytes(L, C, H, W),), dtype=torch.uint8, device=dev)
-        with _lib.on_device(dev):
-            rc = L.lr_masked_l1_dssim_forward(C, H, W, x.data_ptr(), g.data_ptr(), m.data_ptr(), float(lambda_dssim),
-                                              out3.data_ptr(), ws.data_ptr(), ws.numel(), torch.cuda.current_stream(dev).cuda_stream)
-        if rc < 0:
-            _lib.raise_for(rc, "masked_l1_dssim")
-        ctx.save_for_backward(x, g, m, ws)
-        ctx.lam, ctx.dims, ctx.in_shape = float(lambda_dssim), (C, H, W), image.shape
-        return out3[0]
+        return _pair_forward(ctx, "masked_l1_dssim", image, gt, float(lambda_dssim), mask)[0]
 
     @staticmethod
     def backward(ctx, grad_out):
         x, g, m, ws = ctx.saved_tensors
-        C, H, W = ctx.dims
-        L = _lib.lib()
         dev = x.device
         up = _weight(grad_out, dev)
         grad = torch.empty_like(x)
-        with _lib.on_device(dev):
-            rc = L.lr_masked_l1_dssim_backward(C, H, W, x.data_ptr(), g.data_ptr(), m.data_ptr(), ctx.lam, up.data_ptr(),
-                                               ws.data_ptr(), grad.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
-        if rc < 0:
-            _lib.raise_for(rc, "masked_l1_dssim backward")
+        _call(_lib.lib().lr_masked_l1_dssim_backward, "masked_l1_dssim backward", dev, *ctx.dims, x.data_ptr(), g.data_ptr(),
+              m.data_ptr(), ctx.lam, up.data_ptr(), ws.data_ptr(), grad.data_ptr())
         return grad.view(ctx.in_shape), None, None, None
 
 
@@ -370,31 +318,14 @@ def masked_l1_dssim(image, gt, mask, lambda_dssim=0.2):
     return _MaskedL1DSSIM.apply(image, gt, mask, lambda_dssim)
 
 
-_ALPHA_WS_BYTES = {}                # (H, W) -> lr_alpha_hole_workspace_bytes
-
-
 class _AlphaHole(torch.autograd.Function):
     @staticmethod
     def forward(ctx, alpha, mask, weight):
-        if not alpha.is_cuda or alpha.dtype != torch.float32:
-            raise RuntimeError("luciddreamer_amd.loss.alpha_hole: alpha must be a float32 tensor on a HIP device (no CPU path)")
-        if not (alpha.dim() == 2 or (alpha.dim() == 3 and alpha.shape[0] == 1)):
-            raise RuntimeError(f"alpha {tuple(alpha.shape)} must be [1,H,W] or [H,W]")
-        H, W = int(alpha.shape[-2]), int(alpha.shape[-1])
-        a = alpha.contiguous()
+        a = _plane(alpha, "alpha", "alpha_hole")
+        H, W = int(a.shape[-2]), int(a.shape[-1])
         m = _mask_hw(mask, H, W, a.device)
-        L = _lib.lib()
-        dev = a.device
-        n = _ALPHA_WS_BYTES.get((H, W))
-        if n is None:
-            n = _ALPHA_WS_BYTES[(H, W)] = int(L.lr_alpha_hole_workspace_bytes(H, W))
-        out = torch.empty((1,), dtype=torch.float32, device=dev)
-        ws = torch.empty((n,), dtype=torch.uint8, device=dev)
-        with _lib.on_device(dev):
-            rc = L.lr_alpha_hole_forward(H, W, a.data_ptr(), m.data_ptr(), float(weight), out.data_ptr(), ws.data_ptr(),
-                                         ws.numel(), torch.cuda.current_stream(dev).cuda_stream)
-        if rc < 0:
-            _lib.raise_for(rc, "alpha_hole")
+        out, _ = _plane_forward(_lib.lib().lr_alpha_hole_forward, "lr_alpha_hole_workspace_bytes", "alpha_hole", 1, H, W, a, m,
+                                float(weight))
         ctx.save_for_backward(m)
         ctx.weight, ctx.dims, ctx.in_shape = float(weight), (H, W), alpha.shape
         return out[0]
@@ -402,16 +333,11 @@ class _AlphaHole(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_out):
         m, = ctx.saved_tensors
-        H, W = ctx.dims
-        L = _lib.lib()
         dev = m.device
         up = _weight(grad_out, dev)
         grad = torch.empty(ctx.in_shape, dtype=torch.float32, device=dev)
-        with _lib.on_device(dev):
-            rc = L.lr_alpha_hole_backward(H, W, m.data_ptr(), ctx.weight, up.data_ptr(), grad.data_ptr(),
-                                          torch.cuda.current_stream(dev).cuda_stream)
-        if rc < 0:
-            _lib.raise_for(rc, "alpha_hole backward")
+        _call(_lib.lib().lr_alpha_hole_backward, "alpha_hole backward", dev, *ctx.dims, m.data_ptr(), ctx.weight, up.data_ptr(),
+              grad.data_ptr())
         return grad, None, None
 
 

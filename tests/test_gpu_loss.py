@@ -89,6 +89,107 @@ def test_drop_in_names_and_determinism(hip_device):
         L.l1_dssim_loss(a, b[:, :-1], 0.2)
 
 
+def test_terms_share_the_size_cache_and_the_call_path(hip_device):
+    """Every loss term, forward and backward, at two shapes in one process, shapes and terms alternating and the whole tour made
+    twice: each entry of the shared workspace-size cache is made by one visit and read by the next after five other terms have
+    gone through the same cache and call helper.  16x16 is one workgroup everywhere and smaller than the 32-pixel SSIM tile;
+    47x61 crosses the tile edge in both axes and the 2048-pixel workgroup of the plane kernels.  Each first visit is held to the
+    reference and the bar of the term's own test (this file, test_gpu_depth_views.py, test_gpu_depth_pearson.py,
+    test_gpu_mask_views.py), with that test's upstream scalar (the plane terms' gradients are compared with torch's bit for bit:
+    torch divides by H*W through the reciprocal, which rounds as the kernels' division does for 1.3 * 0.7 at these sizes);
+    each second visit returns the first one's bits."""
+    from luciddreamer_amd import _lib, loss as L
+    from tests import depth_l1_ref, depth_pearson_ref, mask_loss_ref
+    dev, lam, up, up_plane = hip_device, 0.2, 2.5, 1.3
+    data, want = {}, {}
+    for H, W in ((16, 16), (47, 61)):
+        rng = np.random.default_rng(H + W)
+        gt = rng.random((3, H, W)).astype(np.float32)
+        img = np.clip(0.6 * gt + 0.4 * rng.random((3, H, W)), 0, 1).astype(np.float32)
+        m = mask_loss_ref.make_mask(H, W, seed=H * 3 + W, kind="soft")
+        d, t = depth_l1_ref.make_pair(H, W, seed=H + W, lead=(1,))
+        alpha = torch.rand(1, H, W, generator=torch.Generator().manual_seed(H + W))
+        data[H, W] = {k: torch.as_tensor(v).to(dev) for k, v in dict(img=img, gt=gt, m=m, d=d, t=t, alpha=alpha).items()}
+        want[H, W] = dict(pair=loss_oracle.l1_dssim(img, gt, lam), masked=mask_loss_ref.numpy_masked_l1_dssim(img, gt, m.numpy(), lam),
+                          depth_l1=depth_l1_ref.numpy_depth_l1(d.numpy(), t.numpy(), 0.7)[0],
+                          pearson=depth_pearson_ref.numpy_depth_pearson(d.numpy(), t.numpy(), 0.7),
+                          alpha=mask_loss_ref.numpy_alpha_hole(alpha.numpy(), m.numpy(), 0.7)[0])
+    paired = L.PairedLoss()
+
+    def visit(term, D, image=None, lead=()):
+        """(value[s], gradient) of one forward + backward; image: the leaf to use in place of a fresh contiguous [C,H,W] one;
+        lead: leading dims of the image pair."""
+        leaf = {"depth_l1": "d", "depth_pearson": "d", "alpha_hole": "alpha"}.get(term, "img")
+        x = (D[leaf].clone() if image is None else image).requires_grad_(True)
+        gt = D["gt"].reshape(*lead, *D["gt"].shape)
+        if term == "l1_dssim_loss":
+            vals = (L.l1_dssim_loss(x, gt, lam),)
+        elif term == "paired":
+            vals = (paired.l1_loss(x, D["gt"]), paired.ssim(x, D["gt"]))
+        elif term == "masked_l1_dssim":
+            vals = (L.masked_l1_dssim(x, gt, D["m"], lam),)
+        elif term == "depth_l1":
+            vals = (L.depth_l1(x, D["t"], 0.7),)
+        elif term == "depth_pearson":
+            vals = (L.depth_pearson(x, D["t"], 0.7),)
+        else:
+            vals = (L.alpha_hole(x, D["m"], 0.7),)
+        total = vals[0] if len(vals) == 1 else (1.0 - lam) * vals[0] + lam * (1.0 - vals[1])
+        (total * (up if leaf == "img" else up_plane)).backward()
+        return tuple(v.detach().clone() for v in vals), x.grad
+
+    terms = ("l1_dssim_loss", "paired", "masked_l1_dssim", "depth_l1", "depth_pearson", "alpha_hole")
+    tours = [{(term, hw): visit(term, data[hw]) for hw in data for term in terms} for _ in range(2)]
+    for key, (vals, grad) in tours[0].items():
+        again = tours[1][key]
+        assert all(torch.equal(a, b) for a, b in zip(vals, again[0])) and torch.equal(grad, again[1]), key
+    for hw, D in data.items():
+        first = lambda term: tours[0][term, hw]
+        o = want[hw]["pair"]
+        (loss,), grad = first("l1_dssim_loss")
+        print(f"[terms] {hw} l1_dssim_loss {float(loss):.8f} want {o['loss']:.8f}")
+        assert abs(float(loss) - o["loss"]) <= 2e-6
+        assert np.abs(grad.cpu().numpy() - up * o["grad"]).max() <= 2e-5 * np.abs(up * o["grad"]).max()
+        (l1, ss), grad = first("paired")
+        assert abs(float(l1) - o["l1"]) <= 1e-6 and abs(float(ss) - o["ssim"]) <= 2e-6
+        assert np.abs(grad.cpu().numpy() - up * o["grad"]).max() <= 2e-5 * np.abs(up * o["grad"]).max()
+        o = want[hw]["masked"]
+        (loss,), grad = first("masked_l1_dssim")
+        assert abs(float(loss) - o["loss"]) <= 2e-6
+        assert np.abs(grad.cpu().numpy() - up * o["grad"]).max() <= 2e-5 * np.abs(up * o["grad"]).max()
+        (loss,), grad = first("depth_l1")
+        assert abs(float(loss) - want[hw]["depth_l1"]) <= 1e-6 * abs(want[hw]["depth_l1"])
+        ref = D["d"].clone().requires_grad_(True)
+        (depth_l1_ref.torch_depth_l1(ref, D["t"], 0.7) * up_plane).backward()
+        assert torch.equal(grad, ref.grad) and float(grad.abs().max()) > 0
+        w_loss, _, w_grad = want[hw]["pearson"]
+        (loss,), grad = first("depth_pearson")
+        assert abs(float(loss) - w_loss) <= 1e-6
+        assert np.abs(w_grad).max() > 0 and np.abs(grad.cpu().numpy() - up_plane * w_grad).max() <= 1e-6 * up_plane * np.abs(w_grad).max()
+        (loss,), grad = first("alpha_hole")
+        assert abs(float(loss) - want[hw]["alpha"]) <= 1e-6 * abs(want[hw]["alpha"])
+        ref = D["alpha"].clone().requires_grad_(True)
+        (mask_loss_ref.torch_alpha_hole(ref, D["m"], 0.7) * up_plane).backward()
+        assert torch.equal(grad, ref.grad) and float(grad.abs().max()) > 0
+        # the image terms once more through the wrapper's own copy: a transposed view (not contiguous) and [1,C,H,W]
+        for term in ("l1_dssim_loss", "paired", "masked_l1_dssim"):
+            vals, grad = first(term)
+            view = D["img"].transpose(1, 2).contiguous().transpose(1, 2)
+            assert not view.is_contiguous()
+            v2, g2 = visit(term, D, view)
+            assert all(torch.equal(a, b) for a, b in zip(vals, v2)) and torch.equal(grad, g2), (term, hw, "view")
+            if term != "paired":                                           # the shared pass of the pair takes [C,H,W] only
+                v4, g4 = visit(term, D, D["img"][None].clone(), lead=(1,))
+                assert all(torch.equal(a, b) for a, b in zip(vals, v4)) and tuple(g4.shape) == (1, 3, *hw), (term, hw)
+                assert torch.equal(grad, g4[0])
+    # one cache, one entry per size query and shape, holding the library's answer
+    lib = _lib.lib()
+    for H, W in data:
+        assert L._WS_BYTES["lr_loss_workspace_bytes", (3, H, W)] == lib.lr_loss_workspace_bytes(3, H, W)
+        for q in ("lr_depth_l1_workspace_bytes", "lr_depth_pearson_workspace_bytes", "lr_alpha_hole_workspace_bytes"):
+            assert L._WS_BYTES[q, (H, W)] == getattr(lib, q)(H, W) > 0
+
+
 def test_training_step_matches_torch_composition(hip_device):
     """render -> fused loss -> backward gives the same parameter gradients as render -> torch L1/SSIM composition."""
     import torch.nn.functional as F
