@@ -831,7 +831,11 @@ void lr_backward_wait_event(void* event);
  *   "tile_map" 0/1       tile -> workgroup map: XCD bands / plain
  *   "bwd_seg" 0          the blend backward walks whole lists instead of 256-position segments
  *   "bwd_red" 4          every wave of the blend backward takes the loop copy with the `pos < last` test
- *   "preprocess" 0/1     plain / pooled preprocess kernel;  "hit_mask" 0: no tile masks;  "tsort" 0/1/2, "walk_own" n: binning
+ *   "preprocess" 0/1     plain / pooled preprocess kernel;  "hit_mask" 0: no tile masks;  "walk_own" n: binning
+ *   "tsort" 0..4         per-bin sort of the binning, bins of up to 256 entries (one wave): 0 bitonic network (also for 257..1024);
+ *                        1 the same, bucket sort for 257..1024; 2 network up to 64 entries, bucket sort above; 3 rank sort for all of
+ *                        them; 4 rank sort up to 128 entries, bucket sort above.  The rule (-1) is 4.  Every setting writes the same
+ *                        lists.
  *   "gauss_bwd" 0        no interleaved step accumulator
  * Values that select a RETIRED kernel ("part_scan", "bwd_red" 0 / 2 / 3, "fwd_pair" 1) and every LR_* environment override exist only in the
  * diagnostics build (-DLR_DIAGNOSTICS, `python -m luciddreamer_amd.build --diagnostics`; lr_version() then says "+diagnostics");

@@ -114,6 +114,7 @@ constexpr int PART_BLOCKS_MAX = 256;        // workgroups of the count / scatter
 constexpr int PART_THREADS = 1024;
 constexpr int PART_MIN_GAUSS = 1024;        // emitting Gaussians per workgroup before another workgroup is used
 constexpr int TSORT_LDS = 256;              // bin entries sorted by one wave (2 KB of LDS)
+constexpr int TSORT_RANK_DEFAULT = 128;     // ... of them by the rank sort (one or two words per lane) unless the "tsort" knob says otherwise
 constexpr int TSORT_GROUP_LDS = 1024;        // bin entries the four waves of a k_tile_sort_small workgroup sort together (8 KB)
 constexpr int TSORT_THREADS = 512;          // threads of k_tile_sort_large (bins of more than 1024 entries)
 constexpr int TSORT_MID_LDS = 4096;         // ... its bin entries (32 KB of words + 16 KB of bucket counters)

@@ -31,10 +31,10 @@
 //                                        the same walk again; every hit takes the next free position of its bin from
 //                                        an LDS cursor and stores ONE 64-bit word [sub-tile | depth bits | slot].
 //                                        The order inside a bin at this point is arbitrary -- and irrelevant:
-//   k_tile_sort_small / _large           every bin's words are sorted in LDS: <= 256 entries by one wave (bitonic network up
-//                                        to 64, bucket sort above), <= 1024 by a workgroup and <= 4096 by a larger one
-//                                        (bucket sort), beyond that the network (in LDS up to 16384 entries when the
-//                                        launch has the room, else in global memory).
+//   k_tile_sort_small / _large           every bin's words are sorted in LDS: <= 256 entries by one wave (rank sort up to
+//                                        128, bucket sort above), <= 1024 by a workgroup and <= 4096 by a larger one
+//                                        (bucket sort), beyond that the bitonic network (in LDS up to 16384 entries when
+//                                        the launch has the room, else in global memory).
 //                                        The word is a TOTAL order -- depth bits, then slot, and slots ascend with the
 //                                        Gaussian index -- so the result is exactly the reference's list, bit-for-bit
 //                                        repeatable, whatever order the scatter produced.
@@ -516,6 +516,60 @@ __device__ __forceinline__ void write_sorted(const unsigned long long* a, uint32
     }
 }
 
+// One bin of up to 64 * PER entries by ONE wave, as a rank sort: every lane keeps PER words in registers, all are laid out
+// in the wave's LDS slice once, and a walk over the slice (uniform address: the LDS broadcasts two words per 128-bit read)
+// counts for each of the lane's words the words below it.  Words are distinct (slots are unique), so the count IS the position:
+// no tie rule, no stages, no fences inside the walk.  Positions >= n hold ~0 and count for nobody.  When a bin is a tile
+// (sub_shift == 0) the list is written straight from registers; otherwise the words go back to LDS at their ranks and
+// write_sorted derives the per-tile ranges from the neighbours as it does for the other sorts.  `a` must be 16-byte aligned and
+// hold 64 * PER words.
+template <int PER, class Sync>
+__device__ __forceinline__ void rank_sort_wave(const unsigned long long* __restrict__ src, uint32_t n, unsigned long long* a,
+                                               uint32_t start, int bin, int sub_shift, int slot_bits, int num_tiles, uint32_t lane,
+                                               uint32_t* __restrict__ point_list, uint2* __restrict__ ranges,
+                                               const uint32_t* __restrict__ inst_gid, uint32_t* __restrict__ list_gid, Sync sync)
+{
+    const unsigned long long slot_mask = (1ull << slot_bits) - 1ull;
+    unsigned long long mine[PER];
+    uint32_t rank[PER], gid[PER];
+#pragma unroll
+    for (int k = 0; k < PER; k++) {
+        const uint32_t i = lane + 64u * (uint32_t)k;
+        mine[k] = i < n ? src[i] : ~0ull;
+        a[i] = mine[k];
+        rank[k] = 0u; gid[k] = 0u;
+    }
+    if (sub_shift == 0) {
+        // the Gaussian of the list position (write_sorted's second store): asked for before the walk, needed after it
+#pragma unroll
+        for (int k = 0; k < PER; k++)
+            if (lane + 64u * (uint32_t)k < n) gid[k] = inst_gid[(uint32_t)(mine[k] & slot_mask)];
+    }
+    sync();
+    const ulonglong2* a2 = reinterpret_cast<const ulonglong2*>(a);
+    for (uint32_t j = 0; j < n; j += 4) {                 // reads up to 3 positions past n: padding, inside the 64 * PER stored
+        const ulonglong2 u = a2[j >> 1], v = a2[(j >> 1) + 1];
+#pragma unroll
+        for (int k = 0; k < PER; k++)
+            rank[k] += (u.x < mine[k] ? 1u : 0u) + (u.y < mine[k] ? 1u : 0u) + (v.x < mine[k] ? 1u : 0u) + (v.y < mine[k] ? 1u : 0u);
+    }
+    if (sub_shift == 0) {
+#pragma unroll
+        for (int k = 0; k < PER; k++)
+            if (lane + 64u * (uint32_t)k < n) {
+                point_list[start + rank[k]] = (uint32_t)(mine[k] & slot_mask);
+                list_gid[start + rank[k]] = gid[k];
+            }
+        return;
+    }
+    sync();                                               // every lane is done reading before any word moves
+#pragma unroll
+    for (int k = 0; k < PER; k++)
+        if (lane + 64u * (uint32_t)k < n) a[rank[k]] = mine[k];
+    sync();
+    write_sorted(a, n, start, bin, sub_shift, slot_bits, num_tiles, lane, 64u, point_list, ranges, inst_gid, list_gid);
+}
+
 // One bin of up to THREADS * PER entries, sorted by THREADS threads into s_out: the bucket sort described above k_tile_sort_large.
 // s_cnt: THREADS * PER counters; s_red: 2 words per wave; s_wave: one per wave; s_bad: one flag.  Ends with s_out complete
 // (barrier included).  Any monotone map of the keys onto the buckets keeps the result exact -- the order inside a bucket is
@@ -607,20 +661,21 @@ __device__ __forceinline__ void bucket_sort_bin(const unsigned long long* __rest
 // Two launches for all bin sizes (round 2 had four, three of which found nothing to do on a sparse view and still cost a
 // launch each):
 //   k_tile_sort_small  256 threads = 4 waves per workgroup.  Part A of the grid: one workgroup per 4 consecutive bins, a bin
-//                      of up to 256 entries (a C3 tile holds ~70) sorted by ONE wave in its own 2 KB of LDS, no block
-//                      barrier involved.  Part B (up to 2048 more workgroups, striding over the bins): bins of 257..1024
+//                      of up to 256 entries (a C3 tile holds ~50) sorted by ONE wave in its own 2 KB of LDS, no block
+//                      barrier involved: a rank sort up to 128 entries (until then, up to 64, the 21 stages of the bitonic
+//                      network: ~340 VALU and ~510 SALU wave-instructions per tile to order 50 words), the bucket sort above.  Part B (up to 2048 more workgroups, striding over the bins): bins of 257..1024
 //                      entries by a whole workgroup with the four slices as one 8 KB array (the dense 1080p / 1440p
 //                      clouds: 400..700 per tile).
 //   k_tile_sort_large  fed by the queue the scatter kernel built (bins of more than 1024 entries), 512 threads: up to
 //                      4096 entries the bucket sort, beyond that the bitonic network -- in LDS when the launch was given
 //                      room for it (lds_entries), else in place in global memory.
 __global__ void __launch_bounds__(256)
-k_tile_sort_small(int bins, int groups4, int sub_shift, int slot_bits, int num_tiles, int bucket_b, const uint32_t* __restrict__ bin_start,
+k_tile_sort_small(int bins, int groups4, int sub_shift, int slot_bits, int num_tiles, int bucket_b, int rank_max, const uint32_t* __restrict__ bin_start,
                   const uint32_t* __restrict__ bin_total, const unsigned long long* __restrict__ words,
                   uint32_t* __restrict__ point_list, uint2* __restrict__ ranges, const uint32_t* __restrict__ inst_gid,
                   uint32_t* __restrict__ list_gid)
 {
-    __shared__ unsigned long long s_a[4 * TSORT_LDS];         // 4 x 256 entries = TSORT_GROUP_LDS
+    __shared__ __attribute__((aligned(16))) unsigned long long s_a[4 * TSORT_LDS];   // 4 x 256 entries = TSORT_GROUP_LDS
     __shared__ uint32_t s_cnt[TSORT_GROUP_LDS];               // part B's bucket counters
     __shared__ unsigned long long s_red[8];
     __shared__ uint32_t s_wave[4];
@@ -630,16 +685,26 @@ k_tile_sort_small(int bins, int groups4, int sub_shift, int slot_bits, int num_t
         // part A: workgroup g takes bins 4 g .. 4 g + 3, one per wave, if they hold at most 256 entries
         const int bin = (int)blockIdx.x * 4 + w;
         const uint32_t n = bin < bins ? bin_total[bin] : 0u;
+        const uint32_t start = bin < bins ? bin_start[bin] : 0u;     // asked for with the count, not after it: one round trip less
         if (n == 0 || n > (uint32_t)TSORT_LDS) return;
         unsigned long long* a = s_a + w * TSORT_LDS;
-        const uint32_t start = bin_start[bin];
         // one wave, its own slice: LDS operations of a wave execute in order, so a wave-level fence is all the exchange
         // between its lanes needs (no workgroup barrier anywhere in this part)
         auto wsync = [] { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier();
                           __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); };
+        if (n <= (uint32_t)rank_max) {
+            // the rank sort (rank_max: 0, 64, 128 or 256 -- launch_tile_binning): one or two words per lane up to 128 entries, four above
+            // (n and start are the same in every lane: say so, the walk's loop then runs on the scalar unit)
+            const uint32_t un = (uint32_t)__builtin_amdgcn_readfirstlane((int)n), ustart = (uint32_t)__builtin_amdgcn_readfirstlane((int)start);
+            const unsigned long long* src = words + ustart;
+            if (un <= 64u) rank_sort_wave<1>(src, un, a, ustart, bin, sub_shift, slot_bits, num_tiles, (uint32_t)l, point_list, ranges, inst_gid, list_gid, wsync);
+            else if (un <= 128u) rank_sort_wave<2>(src, un, a, ustart, bin, sub_shift, slot_bits, num_tiles, (uint32_t)l, point_list, ranges, inst_gid, list_gid, wsync);
+            else rank_sort_wave<4>(src, un, a, ustart, bin, sub_shift, slot_bits, num_tiles, (uint32_t)l, point_list, ranges, inst_gid, list_gid, wsync);
+            return;
+        }
         if (bucket_b == 2 && n > 64) {
             // the bucket sort by one wave in its own slices (C3: sort stage 19.4 -> 18.5 us, dense 1 M cloud 59.4 -> 56.2;
-            // profiles/r04d_ab_tsort_wave.json); up to 64 entries the network's 21 stages stay cheaper
+            // profiles/r04d_ab_tsort_wave.json)
             bucket_sort_bin<64, TSORT_LDS / 64>(words + start, n, slot_bits, a, s_cnt + w * TSORT_LDS, s_red + 2 * w, s_wave + w,
                                                 &s_bad[w], l, wsync);
             write_sorted(a, n, start, bin, sub_shift, slot_bits, num_tiles, (uint32_t)l, 64u, point_list, ranges, inst_gid, list_gid);
@@ -800,11 +865,15 @@ int launch_tile_binning(int P, int gx, int gy, int slot_bits, const uint32_t* vi
     if (t) t->mark(3, s);
     const int groups4 = (pp.bins + 3) / 4;
     const int part_b = pp.bins < TSORT_CLASS_BLOCKS ? pp.bins : TSORT_CLASS_BLOCKS;
-    // per-bin algorithm: 2 (default) = bucket sort from 65 entries up, 1 = only for 257..1024 (the wave-sized bins through the
-    // bitonic network), 0 = the network for everything up to 1024 (lr_tune_set("tsort", v): A/B runs)
-    const int bucket_b = tune_get(TUNE_TSORT) >= 0 ? tune_get(TUNE_TSORT) : 2;
+    // per-bin algorithm (lr_tune_set("tsort", v): A/B runs): 2 = bucket sort from 65 entries up, the bitonic network below;
+    // 1 = bucket sort only for 257..1024 (the wave-sized bins through the network); 0 = the network for everything up to 1024;
+    // 3 = rank sort for every wave-sized bin (up to 256 entries), bucket sort above; 4 = rank sort up to 128 entries (two words
+    // per lane), bucket sort above.  Unset: rank sort up to TSORT_RANK_DEFAULT entries, otherwise as 2
+    const int tsort = tune_get(TUNE_TSORT);
+    const int bucket_b = (tsort >= 0 && tsort <= 2) ? tsort : 2;
+    const int rank_max = tsort < 0 ? TSORT_RANK_DEFAULT : (tsort == 3 ? TSORT_LDS : (tsort == 4 ? 128 : 0));
     hipLaunchKernelGGL(k_tile_sort_small, dim3(groups4 + part_b), dim3(256), 0, s, pp.bins, groups4, pp.sub_shift, slot_bits,
-                       num_tiles, bucket_b, bin_start, bin_total, words, point_list, ranges, inst_gid, list_gid);
+                       num_tiles, bucket_b, rank_max, bin_start, bin_total, words, point_list, ranges, inst_gid, list_gid);
     // the large bins: LDS for the bucket sort (32 KB of words; three workgroups per CU) unless the AVERAGE bin is already
     // beyond it -- then 128 KB, so that bins of up to 16384 entries are sorted in LDS (a hint for speed only: a bin that
     // does not fit this launch's LDS is sorted in place in global memory).  Capped grid: a sparse view queues nothing
