@@ -94,7 +94,7 @@ def build(force=False, verbose=False, diagnostics=False):
     os.makedirs(OBJDIR, exist_ok=True)
     cc = hipcc()
     hash_header = _write_hash_header()
-    headers = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "gauss_bwd_body.h"), os.path.join(CSRC, "loss_ssim_fwd_body.h"),
+    headers = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "screen_cull.h"), os.path.join(CSRC, "gauss_bwd_body.h"), os.path.join(CSRC, "loss_ssim_fwd_body.h"),
                os.path.join(CSRC, "loss_ssim_bwd_body.h"), os.path.join(INCLUDE, "lucid_raster.h"), os.path.abspath(__file__)]
     objs = []
     procs = []

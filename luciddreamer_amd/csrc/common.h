@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stddef.h>
+#include "screen_cull.h"
 
 namespace lr {
 
@@ -364,6 +365,10 @@ struct ViewParams {
     const float* sh_rest;
     const float* opacity_raw;     // backward only (sigmoid derivative)
     float* dL_dsh_rest;           // backward only
+    // k_preprocess_pool, phase 1: constants of the conservative off-screen test (screen_cull.h) and its switch
+    // (lr_tune_set("pcull", 0) = off; the kernel also leaves it off when the caller brings its own 3D covariances)
+    ScreenCull cull;
+    int pcull;
 };
 
 // activations of the raw mode; one definition so that forward and backward recompute identical values
@@ -418,7 +423,7 @@ int launch_tile_binning(int P, int gx, int gy, int slot_bits, const uint32_t* vi
 
 // Diagnostic tuning knobs (lr_tune_set in api.hip): kernel variants that can be switched at run time so that two of them
 // are measured alternately in ONE process on ONE box (tools/ab_bench.py).  -1 = not set (the launcher's own rule).
-enum TuneKey { TUNE_BWD_RED = 0, TUNE_BLEND_QUAD, TUNE_TILE_MAP, TUNE_PREPROCESS, TUNE_GAUSS_BWD, TUNE_TSORT, TUNE_WALK_OWN, TUNE_HIT_MASK, TUNE_VIEWS_IN_FLIGHT, TUNE_STRICT, TUNE_PART_SCAN, TUNE_BWD_SEG, TUNE_FWD_PAIR, TUNE_COUNT };
+enum TuneKey { TUNE_BWD_RED = 0, TUNE_BLEND_QUAD, TUNE_TILE_MAP, TUNE_PREPROCESS, TUNE_GAUSS_BWD, TUNE_TSORT, TUNE_WALK_OWN, TUNE_HIT_MASK, TUNE_VIEWS_IN_FLIGHT, TUNE_STRICT, TUNE_PART_SCAN, TUNE_BWD_SEG, TUNE_FWD_PAIR, TUNE_PCULL, TUNE_COUNT };
 int tune_get(int key);
 
 // Shape of the backward blend kernel (render_bwd.hip, where the rule and its measurements are): BLEND_QUAD = 4 waves per

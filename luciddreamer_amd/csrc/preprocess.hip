@@ -342,7 +342,8 @@ k_preprocess(ViewParams vp, const float* __restrict__ means3D, const float* __re
 // the near plane and ~9 % end up with a non-empty tile rectangle, so with one thread per Gaussian the covariance chain runs
 // on half-empty waves and the spherical-harmonics / tile-count part on lanes 18 % live.  Here a workgroup owns a POOL of
 // 512 consecutive Gaussians and compacts twice through LDS:
-//   phase 1   all 512: near-plane test (auxiliary.h:152-162) -> dense list of the passers
+//   phase 1   all 512: near-plane test (auxiliary.h:152-162), then a conservative off-screen test (screen_cull.h) -> dense
+//             list of the passers
 //   phase 2   passers, dense lanes: projection, 3D -> 2D covariance, conic, radius, tile rectangle (forward.cu:196-232);
 //             the ones with a non-empty rectangle park their screen-space values in LDS
 //   phase 3a  parked survivors, dense lanes: SH -> RGB (12 x dwordx4 per lane), GaussRec store
@@ -513,17 +514,51 @@ k_preprocess_pool(ViewParams vp, const float* __restrict__ means3D, const float*
     if (tid == 0) { s_nmid = 0u; s_sum[0] = 0u; s_sum[1] = 0u; s_sum[2] = 0u; }
     const float* __restrict__ V = vp.view;
 
-    // ---- phase 1: near-plane test of the whole pool
+    // ---- phase 1: near-plane test of the whole pool, and of its passers the conservative off-screen test (screen_cull.h):
+    // on a camera path four of five near-plane passers have an empty tile rectangle, and in a cloud in random order they sit
+    // on every lane -- dropped here, before the compaction, they leave phase 2 dense lanes of what can reach the screen.  The
+    // test only ever drops what project_gaussian would drop (its full chain still runs on everything passed), so every output
+    // keeps its bits.  Not with the caller's own 3D covariances (need not be positive semi-definite).  Scales and rotations
+    // are read for every lane (row 0 stands in beyond the cloud's end, as for the means): both rounds' loads leave together.
+    const bool cull_on = vp.pcull != 0 && cov3D_precomp == nullptr;
+    const float* __restrict__ Pm = vp.proj;
+    const float kv9 = cull_on ? screen_cull_kv9(vp.cull, V) : 0.0f;
     bool pass[PL_ROUNDS];
     uint64_t m[PL_ROUNDS];
+    float mean[PL_ROUNDS][3], scl[PL_ROUNDS][3];
+    float4 rot[PL_ROUNDS];
+#pragma unroll
+    for (int r = 0; r < PL_ROUNDS; r++) {
+        const int gid = base + r * PL_THREADS + tid;
+        const size_t li = gid < vp.P ? (size_t)gid : 0;
+#pragma unroll
+        for (int k = 0; k < 3; k++) mean[r][k] = means3D[3 * li + k];
+        if (cull_on) {
+#pragma unroll
+            for (int k = 0; k < 3; k++) scl[r][k] = scales[3 * li + k];
+            rot[r] = reinterpret_cast<const float4*>(rotations)[li];
+        }
+    }
 #pragma unroll
     for (int r = 0; r < PL_ROUNDS; r++) {
         const int loc = r * PL_THREADS + tid, gid = base + loc;
         const bool in_range = gid < vp.P;
-        const size_t li = in_range ? (size_t)gid : 0;
-        const float vz1 = V[2] * means3D[3 * li] + V[6] * means3D[3 * li + 1] + V[10] * means3D[3 * li + 2] + V[14];
-        pass[r] = in_range && !(vz1 <= 0.2f);
-        if (in_range && !pass[r] && prefiltered) *trap = 1;
+        const float px_w = mean[r][0], py_w = mean[r][1], pz_w = mean[r][2];
+        const float vz1 = V[2] * px_w + V[6] * py_w + V[10] * pz_w + V[14];
+        const bool near = in_range && !(vz1 <= 0.2f);
+        if (in_range && !near && prefiltered) *trap = 1;
+        bool culled = false;
+        if (cull_on) {
+            float sx = scl[r][0], sy = scl[r][1], sz = scl[r][2];
+            float qr = rot[r].x, qx = rot[r].y, qy = rot[r].z, qz = rot[r].w;
+            if (RAW) {
+                sx = act_scale(sx); sy = act_scale(sy); sz = act_scale(sz);
+                const float inv = act_quat_inv_norm(qr, qx, qy, qz);
+                qr *= inv; qx *= inv; qy *= inv; qz *= inv;
+            }
+            culled = screen_cull_point(vp.cull, kv9, Pm, vp.scale_modifier, px_w, py_w, pz_w, vz1, sx, sy, sz, qr, qx, qy, qz);
+        }
+        pass[r] = near && !culled;
         s_radius[loc] = 0; s_tiles[loc] = 0u;
         m[r] = __ballot(pass[r]);
         if (l == 0) s_wcnt[r * PL_WAVES + w] = (uint32_t)__popcll(m[r]);
