@@ -766,6 +766,78 @@ int lr_depth_colorize(int n_frames, int height, int width, const float* depths, 
                       const unsigned char* background, unsigned char* out_rgba, float* out_vmin_vmax, void* workspace,
                       size_t workspace_bytes, void* stream);
 
+/*
+ * Point-cloud reprojection on the device (generate_pcd, R/luciddreamer.py:382-413 "Dreaming" and :516-570 "Aligning"): the
+ * accumulated cloud projected into n_frames poses, every frame in the same launches; the warped image, the hit / hole masks of
+ * the reference bit for bit, and the lift of a depth map back into the world.  Nothing reads back to the host.
+ *
+ *   Project.  x, y, z = the point's float32 coordinates as float64.  Every operation below is one IEEE float64 operation in the
+ *   order written (no fma), so a numpy restatement gives the same bits (tests/reproject_ref.py):
+ *       p_i = ((R_i0 x + R_i1 y) + R_i2 z) + T_i        q_i = (K_i0 p_0 + K_i1 p_1) + K_i2 p_2        u = q_0 / q_2, v = q_1 / q_2
+ *       valid = q_2 > 0 and 0 <= u <= W - 1 and 0 <= v <= H - 1   (closed bounds; NaN is invalid)
+ *       iu, iv = rint(u), rint(v)  (half to even, as np.round)    z = float32(q_2)
+ *   Masks (the reference's, exactly).  hit[iv, iu] = 1;  dilated = 9x9 maximum of hit (round_mask2 / maskj after the filter);
+ *   mask = 11x11 minimum of dilated (mask2 / maskj: the reference's (image.sum(-1) != -3) equals `dilated` whatever the image
+ *   holds);  border = mask_hf of :411-413.  Windows are clamped to the image, which for maximum and minimum filters equals
+ *   scipy's default `reflect` border.  out_valid[i] = valid, out_pix[i] = iv W + iu or -1: the caller's valid_idx,
+ *   round_coord_cam2 and border_valid_idx follow from them by indexing.
+ *   Image (OUR definition, not scipy.interpolate.griddata's Delaunay interpolation; the reference's has no occlusion handling):
+ *   a z-tested bilinear splat in fixed point.
+ *       zmin[y, x] = min z over the points that rounded to (x, y)  (atomicMin on the bits; +inf where there is none)
+ *       x0, y0 = floor(u), floor(v);  fx, fy = u - x0, v - y0;  the neighbour (x0 + dx, y0 + dy), if inside the image, has
+ *       w = (dx ? fx : 1 - fx) * (dy ? fy : 1 - fy) in float64,  wq = rint(w * 65536),
+ *       cq_c = rint(float64(min(max(C_c, 0), 1)) * 65535)  (NaN -> 0),
+ *       and is accepted iff z <= zmin[y', x'] * (1.0f + z_tolerance), float32 operations.
+ *       A_c[y', x'] += wq cq_c and S[y', x'] += wq in uint64 (integer atomics: the sums do not depend on the order).
+ *       A pixel with S == 0 takes the integer sums of A_c and S over its clamped 9x9 window (non-zero inside `dilated`: a hit
+ *       pixel always has S >= 16384).
+ *       image = float32((float64(A_c) / float64(S)) / 65535) inside mask, exact 0 outside (:409, :565), HWC;
+ *       image_u8 = uint8(rint(image * 255.0f)) (:568);  depth = zmin inside mask where finite, else 0.
+ *   The reference's `edgemask` patch (:400, :554) repairs griddata's hull edge and has no counterpart here.
+ *
+ *   points: device float32, the x of point i at points[i * point_stride], y and z coord_stride floats further each
+ *   ([N,3]: 3, 1;  [3,N]: 1, N).  colors: device float32 [N,3], required when out_image or out_image_u8 is given.
+ *   K [9], R [n_frames][9] (row-major), T [n_frames][3]: HOST float64, world to camera; all finite.
+ *   Outputs are optional device pointers, frames contiguous: out_image float32 [F,H,W,3], out_image_u8 uint8 [F,H,W,3],
+ *   out_mask / out_dilated / out_border uint8 [F,H,W], out_depth float32 [F,H,W]; out_valid uint8 [N] and out_pix int32 [N]
+ *   only with n_frames == 1.  workspace: lr_reproject_workspace_bytes(n_frames, H, W) device bytes, 8-byte aligned.
+ *   0 <= n_points < 2^31, 1 <= n_frames <= 65535, H, W >= 2 and H W <= 2^31 - 2^12; z_tolerance finite and >= 0.
+ *   struct_bytes is checked before anything else; every check sits in front of the first HIP call.
+ *
+ *   lr_lift (:370-371, :451-453): depth [H,W] float32 -> out_points [3, H W] float32,
+ *       c_i = (Kinv_i0 (x d) + Kinv_i1 (y d)) + Kinv_i2 d,   out_i = float32(((Rinv_i0 c_0 + Rinv_i1 c_1) + Rinv_i2 c_2) - RinvT_i)
+ *   with x, y the pixel's column and row, x d and y d float64 products.  Kinv [9], Rinv [9], RinvT [3] (= inv(R) T): HOST
+ *   float64, formed by the caller.
+ * Return 0 or a negative LR_ERR_*.
+ */
+typedef struct lr_reproject_args {
+    size_t struct_bytes;                     /* = sizeof(lr_reproject_args); anything else is LR_ERR_INVALID_ARG */
+    long long n_points;
+    const float* points;
+    long long point_stride, coord_stride;    /* in floats */
+    const float* colors;
+    int n_frames, height, width;
+    float z_tolerance;
+    const double* K;                         /* host */
+    const double* R;                         /* host */
+    const double* T;                         /* host */
+    float* out_image;
+    unsigned char* out_image_u8;
+    unsigned char* out_mask;
+    unsigned char* out_dilated;
+    unsigned char* out_border;
+    float* out_depth;
+    unsigned char* out_valid;
+    int* out_pix;
+    void* workspace;
+    size_t workspace_bytes;
+    void* stream;
+} lr_reproject_args;
+size_t lr_reproject_workspace_bytes(int n_frames, int height, int width);
+int lr_reproject(const lr_reproject_args* a);
+int lr_lift(int height, int width, const float* depth, const double* Kinv, const double* Rinv, const double* RinvT,
+            float* out_points, void* stream);
+
 /* present[P] (1 byte each) = view-space z > 0.2.  Returns 0 or a negative LR_ERR_*. */
 int lr_mark_visible(int P, const float* means3D, const float* viewmatrix, const float* projmatrix,
                     unsigned char* present, void* stream);

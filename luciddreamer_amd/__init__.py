@@ -14,9 +14,10 @@ def uninstall(handle):
 
 
 def __getattr__(name):
-    """`luciddreamer_amd.mcmc` (MCMCStrategy: relocation, capped growth, position noise) and `luciddreamer_amd.filter3d` (the 3D
-    smoothing filter of Mip-Splatting) without importing torch with the package."""
-    if name in ("mcmc", "filter3d"):
+    """`luciddreamer_amd.mcmc` (MCMCStrategy: relocation, capped growth, position noise), `luciddreamer_amd.filter3d` (the 3D
+    smoothing filter of Mip-Splatting) and `luciddreamer_amd.reproject` (point-cloud reprojection: warped frames and hole masks)
+    without importing torch with the package."""
+    if name in ("mcmc", "filter3d", "reproject"):
         import importlib
         return importlib.import_module("." + name, __name__)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -41,7 +41,8 @@ EXPORTS = ("lr_last_error", "lr_version", "lr_geom_bytes", "lr_img_bytes", "lr_b
            "lr_masked_l1_dssim_forward", "lr_masked_l1_dssim_backward", "lr_alpha_hole_workspace_bytes", "lr_alpha_hole_forward",
            "lr_alpha_hole_backward", "lr_set_antialiasing", "lr_get_antialiasing",
            "lr_mcmc_workspace_bytes", "lr_mcmc_relocate", "lr_mcmc_noise", "lr_mcmc_reg_grad",
-           "lr_filter3d_workspace_bytes", "lr_filter3d_update", "lr_filter3d_apply_forward", "lr_filter3d_apply_backward")
+           "lr_filter3d_workspace_bytes", "lr_filter3d_update", "lr_filter3d_apply_forward", "lr_filter3d_apply_backward",
+           "lr_reproject_workspace_bytes", "lr_reproject", "lr_lift")
 
 # lr_views_workspace_bytes / lr_views_check `parts`: what a step's workspace slots hold besides a view's scratch
 LR_VIEWS_LOSS, LR_VIEWS_DEPTH_LOSS, LR_VIEWS_MASK_LOSS = 1, 2, 4
@@ -132,6 +133,21 @@ class McmcRelocateArgs(ctypes.Structure):
 
     def __init__(self, **fields):
         super().__init__(struct_bytes=ctypes.sizeof(McmcRelocateArgs), **fields)
+
+
+class ReprojectArgs(ctypes.Structure):
+    """lr_reproject_args, field for field (tests/test_reproject_cpu.py compares the offsets with the host compiler's).
+    K, R, T are HOST float64 arrays; every out_* is optional."""
+    _vp, _ci, _ll = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong
+    _fields_ = [("struct_bytes", ctypes.c_size_t), ("n_points", _ll), ("points", _vp), ("point_stride", _ll),
+                ("coord_stride", _ll), ("colors", _vp), ("n_frames", _ci), ("height", _ci), ("width", _ci),
+                ("z_tolerance", ctypes.c_float), ("K", _vp), ("R", _vp), ("T", _vp),
+                ("out_image", _vp), ("out_image_u8", _vp), ("out_mask", _vp), ("out_dilated", _vp), ("out_border", _vp),
+                ("out_depth", _vp), ("out_valid", _vp), ("out_pix", _vp),
+                ("workspace", _vp), ("workspace_bytes", ctypes.c_size_t), ("stream", _vp)]
+
+    def __init__(self, **fields):
+        super().__init__(struct_bytes=ctypes.sizeof(ReprojectArgs), **fields)
 
 
 def assert_single_copy():
@@ -276,6 +292,12 @@ def lib():
         L.lr_filter3d_apply_forward.argtypes = [ci, vp, vp, vp, ci, vp, vp, vp]  # P scale opacity filter activated out_scale out_opacity stream
         L.lr_filter3d_apply_backward.restype = ci
         L.lr_filter3d_apply_backward.argtypes = [ci, vp, vp, vp, ci, vp, vp, vp, vp, vp]   # ... g_scale g_opacity d_scale d_opacity stream
+        L.lr_reproject_workspace_bytes.restype = ctypes.c_size_t
+        L.lr_reproject_workspace_bytes.argtypes = [ci, ci, ci]
+        L.lr_reproject.restype = ci
+        L.lr_reproject.argtypes = [ctypes.POINTER(ReprojectArgs)]
+        L.lr_lift.restype = ci
+        L.lr_lift.argtypes = [ci, ci, vp, vp, vp, vp, vp, vp]                   # H W depth Kinv Rinv RinvT (host) out stream
         L.lr_step_begin.restype = ci
         L.lr_step_begin.argtypes = []
         L.lr_step_end.restype = ci

@@ -40,6 +40,9 @@ SOURCES = {
     "filter3d.hip": ["-ffp-contract=off"],
     # video frames: bit-exact to numpy's float32 operations (np.round, np.percentile, colorize's normalisation): no FMA contraction
     "video.hip": ["-ffp-contract=off"],
+    # point-cloud reprojection: float64 projection in a fixed order, one IEEE operation each (a numpy restatement agrees to the
+    # bit): no FMA contraction
+    "reproject.hip": ["-ffp-contract=off"],
     "api.hip": [],
 }
 

@@ -630,6 +630,29 @@ hipError_t launch_depth_colorize(int n, int HW, const float* depths, bool from_r
                                  float q_hi, const float* fixed_vmm, const uint32_t* lut, int lut_n, uint32_t background,
                                  uint32_t* out, float* out_vmm, void* workspace, hipStream_t s);
 
+// point-cloud reprojection (reproject.hip): F frames of one cloud in the same launches.  K, R, T are HOST float64 arrays
+// (R [F][9] row-major, T [F][3]); they travel as kernel arguments, REPROJECT_FRAMES_PER_LAUNCH frames per per-point launch.
+constexpr int REPROJECT_FRAMES_PER_LAUNCH = 8;
+struct ReprojectLaunch {
+    int n_points, n_frames, height, width;
+    const float* points;            // x at points[i * point_stride], y and z each coord_stride floats further
+    long long point_stride, coord_stride;
+    const float* colors;            // [N,3]; read only when an image is asked for
+    const double *K, *R, *T;
+    float z_tolerance;
+    float* out_image;               // [F,H,W,3]
+    uint8_t* out_image_u8;          // [F,H,W,3]
+    uint8_t *out_mask, *out_dilated, *out_border;     // [F,H,W]
+    float* out_depth;               // [F,H,W]
+    uint8_t* out_valid;             // [N], one frame only
+    int* out_pix;                   // [N], one frame only
+    void* workspace;
+};
+size_t reproject_workspace_bytes(int n_frames, int height, int width);
+hipError_t launch_reproject(const ReprojectLaunch& a, hipStream_t s);
+hipError_t launch_lift(int height, int width, const float* depth, const double* Kinv, const double* Rinv, const double* RinvT,
+                       float* out, hipStream_t s);
+
 void launch_dist2(int P, const float* points, float* out, char* workspace, hipStream_t s);
 size_t dist2_workspace_bytes(int P);
 void dist2_workspace_layout(int P, size_t offsets[4]);

@@ -64,3 +64,18 @@ def upstream_grad(height: int, width: int, seed: int = 1) -> torch.Tensor:
     """dL/dcolor = N(0,1) of shape (3,H,W)."""
     g = torch.Generator().manual_seed(seed)
     return torch.randn(3, height, width, generator=g)
+
+
+def rgbd_view(height: int, width: int, seed: int = 0):
+    """One synthetic RGB-D view, what LucidDreamer's networks hand to generate_pcd: image (H,W,3) float32 in [0,1] and depth
+    (H,W) float32.  A tilted back wall 4..5 units away with a box 2 units away in front of it, so that a camera that moves
+    sideways sees behind the box: the holes the dreaming loop then fills."""
+    g = torch.Generator().manual_seed(seed)
+    y, x = torch.meshgrid(torch.arange(height, dtype=torch.float32), torch.arange(width, dtype=torch.float32), indexing="ij")
+    depth = 4.0 + x / float(width)
+    box = (x > 0.35 * width) & (x < 0.65 * width) & (y > 0.3 * height) & (y < 0.8 * height)
+    depth = torch.where(box, torch.full_like(depth, 2.0), depth)
+    stripes = 0.5 + 0.5 * torch.sin(x * (12.0 * math.pi / width)) * torch.cos(y * (8.0 * math.pi / height))
+    image = torch.stack([stripes, 1.0 - stripes, torch.where(box, torch.ones_like(stripes), 0.25 * torch.ones_like(stripes))], dim=-1)
+    image = (image + 0.05 * torch.rand(height, width, 3, generator=g)).clamp(0.0, 1.0)
+    return image.float().contiguous(), depth.float().contiguous()
