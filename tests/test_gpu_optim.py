@@ -140,10 +140,10 @@ def test_coefficients_above_the_active_sh_degree_stay_untouched_and_equal_torch(
 # ---------------------------------------------------------------------------------------------------------------------
 # The armed pair: backward without zero-fill + masked step (LR_ACC_NO_ZERO_FILL + lr_adam_step_masked; optim.FusedAdam.arm_fused_backward)
 # ---------------------------------------------------------------------------------------------------------------------
-def _two_clouds(P, dev, seed=7):
+def _two_clouds(P, dev, seed=7, sh_coeffs=16):
     from luciddreamer_amd import synthetic
     from luciddreamer_amd.gaussian_renderer import GaussianCloud
-    c = synthetic.make_cloud(P, "band", seed)
+    c = synthetic.make_cloud(P, "band", seed, sh_coeffs=sh_coeffs)
     mk = lambda: GaussianCloud(c["means3D"].to(dev), c["scales"].to(dev), c["rotations"].to(dev), c["opacities"].to(dev),
                                c["shs"].to(dev), active_sh_degree=0)
     return mk(), mk()
@@ -157,18 +157,12 @@ def _adam_for(cloud):
                       for k, v in named.items()], lr=0.0, eps=1e-15)
 
 
-@pytest.mark.parametrize("W,H", [(320, 192), (1280, 720)])
-def test_step_taken_by_the_backward_gives_the_bits_of_backward_plus_step(hip_device, W, H):
-    """Same cloud twice, same views, same upstream gradients.  A: raw-mode backward writes the gradients, FusedAdam.step()
-    applies them (lr_view_backward with raw = 1 + lr_adam_step).  B: the optimizer is armed, the backward writes only the rows of the Gaussians
-    the view touches into tensors autograd never sees (LR_ACC_NO_ZERO_FILL) and step() takes every other gradient as zero without
-    reading it (lr_adam_step_masked).  After every iteration all six parameter tensors and both moments must be the SAME BITS, and so must
-    the screen-space gradients the densification statistics read -- over views that see a fraction of the band cloud (most
-    rows are 'the rest'), with the SH degree raised and a learning rate changed on the way, and an un-armed iteration in between."""
+def _armed_pair_against_backward_plus_step(hip_device, P, sh_coeffs, W, H, raised_degree):
+    """The body of test_step_taken_by_the_backward_gives_the_bits_of_backward_plus_step (below).  The active SH degree starts at
+    0 and becomes `raised_degree` at the fifth iteration."""
     from luciddreamer_amd import cameras, synthetic
     from luciddreamer_amd.gaussian_renderer import render_raw
-    P = 40_000
-    a, b = _two_clouds(P, hip_device)
+    a, b = _two_clouds(P, hip_device, sh_coeffs=sh_coeffs)
     for cl in (a, b):
         for n in ("_xyz", "_features_dc", "_features_rest", "_opacity", "_scaling", "_rotation"):
             setattr(cl, n, nn.Parameter(getattr(cl, n).detach()))
@@ -181,7 +175,7 @@ def test_step_taken_by_the_backward_gives_the_bits_of_backward_plus_step(hip_dev
     for it in range(10):
         cam = cams[(5 * it) % 12]
         if it == 4:
-            a.active_sh_degree = b.active_sh_degree = 2
+            a.active_sh_degree = b.active_sh_degree = raised_degree
         if it == 6:
             for opt in (opt_a, opt_b):
                 for grp in opt.param_groups:
@@ -204,7 +198,7 @@ def test_step_taken_by_the_backward_gives_the_bits_of_backward_plus_step(hip_dev
         if armed:
             assert all(getattr(b, n).grad is None for n in names) and opt_b._fused_pending is not None
         else:
-            assert all(getattr(b, n).grad is not None for n in names)
+            assert all(getattr(b, n).grad is not None for n in names if getattr(b, n).numel())
         opt_b.step()
         opt_b.zero_grad(set_to_none=True)
         assert opt_b._fused_pending is None
@@ -217,7 +211,32 @@ def test_step_taken_by_the_backward_gives_the_bits_of_backward_plus_step(hip_dev
             assert int(sa["step"]) == int(sb["step"]) == it + 1
             assert torch.equal(sa["exp_avg"], sb["exp_avg"]) and torch.equal(sa["exp_avg_sq"], sb["exp_avg_sq"]), (it, n)
     assert 0.02 < min(visited) and max(visited) < 0.6, visited      # the views really split the cloud into visited rows and the rest
-    assert float((a._xyz.detach() - _two_clouds(P, hip_device)[0]._xyz.detach()).abs().max()) > 0
+    assert float((a._xyz.detach() - _two_clouds(P, hip_device, sh_coeffs=sh_coeffs)[0]._xyz.detach()).abs().max()) > 0
+    return visited
+
+
+@pytest.mark.parametrize("W,H", [(320, 192), (1280, 720)])
+def test_step_taken_by_the_backward_gives_the_bits_of_backward_plus_step(hip_device, W, H):
+    """Same cloud twice, same views, same upstream gradients.  A: raw-mode backward writes the gradients, FusedAdam.step()
+    applies them (lr_view_backward with raw = 1 + lr_adam_step).  B: the optimizer is armed, the backward writes only the rows of the Gaussians
+    the view touches into tensors autograd never sees (LR_ACC_NO_ZERO_FILL) and step() takes every other gradient as zero without
+    reading it (lr_adam_step_masked).  After every iteration all six parameter tensors and both moments must be the SAME BITS, and so must
+    the screen-space gradients the densification statistics read -- over views that see a fraction of the band cloud (most
+    rows are 'the rest'), with the SH degree raised and a learning rate changed on the way, and an un-armed iteration in between."""
+    _armed_pair_against_backward_plus_step(hip_device, 40_000, 16, W, H, raised_degree=2)
+
+
+@pytest.mark.parametrize("P,sh_coeffs", [(10_001, 4), (9_999, 9), (10_003, 1)])
+def test_step_taken_by_the_backward_at_the_other_model_shapes(hip_device, P, sh_coeffs):
+    """The same pair where the model's maximum SH degree is 1, 2 or 0: features_rest rows of 9 and 24 floats go through the masked
+    step's run-time row length, a [P,0,3] features_rest is left out of its launch, and no P is a multiple of 4, so the scalar
+    tail of every tensor with an odd row length runs.  The degree is raised from 0 to the model's maximum on the way (where
+    that is above 0): from then on the backward writes the rows of visited Gaussians in full, and until then it writes zeros
+    above the active degree for them (gauss_bwd_body.h) -- the rows of the others hold the allocator's NaN poison throughout."""
+    max_degree = {1: 0, 4: 1, 9: 2}[sh_coeffs]
+    a, _ = _two_clouds(8, hip_device, sh_coeffs=sh_coeffs)
+    assert a.max_sh_degree == max_degree and a._features_rest.shape == (8, sh_coeffs - 1, 3)
+    _armed_pair_against_backward_plus_step(hip_device, P, sh_coeffs, 320, 192, raised_degree=max_degree)
 
 
 def test_fused_step_refuses_what_it_cannot_do_exactly(hip_device):
