@@ -1,12 +1,14 @@
 """The point-cloud stage of LucidDreamer.generate_pcd (R/luciddreamer.py:363-570) on the device, on synthetic data.
 
-    python examples/align_frames.py [--size 256] [--poses 4]
+    python examples/align_frames.py [--size 256] [--poses 4] [--depth-scale 1.1]
 
 One synthetic RGB-D view (luciddreamer_amd.synthetic.rgbd_view) is lifted into a cloud.  For every dream pose the accumulated
-cloud is projected into the new view (reproject.project: warped image + hole mask); where the reference would now run its
-inpainting and depth networks and align their depth, this example takes the synthetic view's own colours and depth for the
-masked-out pixels, lifts them at the dream pose and appends them.  Then reproject.align_frames renders the training frames:
-every dream pose seen from 5 inner poses.  Needs a HIP device; no network, no scipy.
+cloud is projected into the new view (reproject.project: warped image + hole mask).  Where the reference would now run its
+inpainting and depth networks, this example takes the synthetic view's own colours, and its depth with a wrong scale and a
+smooth offset (synthetic.miscalibrated_depth: what a monocular depth network hands back).  reproject.dream_step then does what
+follows the networks (R/luciddreamer.py:424-493) on the device: it fits the scale, measures the depth offsets along the hole's
+border, interpolates them into the holes, lifts the corrected depth and appends the hole pixels.  Then reproject.align_frames
+renders the training frames: every dream pose seen from 5 inner poses.  Needs a HIP device; no network, no scipy.
 """
 import argparse
 import math
@@ -34,6 +36,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--size", type=int, default=256)
     ap.add_argument("--poses", type=int, default=4)
+    ap.add_argument("--depth-scale", type=float, default=1.1, help="the stand-in depth network is off by this factor")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("examples/align_frames.py needs a HIP device (there is no CPU path)")
@@ -49,17 +52,23 @@ def main():
     points = reproject.lift(depth, K, render_poses[0, :3, :3], render_poses[0, :3, 3:4])          # [3, H*W]
     colors = image.reshape(-1, 3).contiguous()
     print(f"view 0: {points.shape[1]} points lifted from a {H} x {W} RGB-D view")
+    net_depth = synthetic.miscalibrated_depth(depth, scale=a.depth_scale)                          # the depth "network"
+    border_error = lambda comp: float(comp.corr_value[:comp.n_corr].abs().nanmean()) if comp.n_corr else 0.0
     for i in range(1, a.poses):
         R, T = render_poses[i, :3, :3], render_poses[i, :3, 3:4]
         f = reproject.project(points, colors, K, R, T, H, W)
         hole = f.mask == 0
-        # the networks' part, stood in for by the synthetic view: colours and depth of the pixels the cloud left empty
-        new = reproject.lift(depth, K, R, T)[:, hole.reshape(-1)]
-        points = torch.cat([points, new], dim=1).contiguous()
-        colors = torch.cat([colors, image.reshape(-1, 3)[hole.reshape(-1)]], dim=0).contiguous()
+        # cloud-to-depth distance along the camera rays of the border points, before (scale 1) and after the fit
+        before = border_error(reproject.compensate(points, f, net_depth, K, R, T, scale=1.0))
+        old = points
+        points, colors, info = reproject.dream_step(points, colors, f, image, net_depth, K, R, T)
+        after = border_error(reproject.compensate(old, f, net_depth, K, R, T, scale=info.scale))
         print(f"dream pose {i}: {int(f.valid.sum())} of {f.valid.numel()} points on screen, {int(f.mask.sum())} mask pixels, "
               f"{int(hole.sum())} hole pixels ({100.0 * float(hole.float().mean()):.1f} %), {int(f.border.sum())} border pixels, "
               f"cloud now {points.shape[1]} points")
+        print(f"    fitted scale {info.scale:.4f} over {info.fit.n_used} points (mse {info.fit.mse_before:.4g} -> "
+              f"{info.fit.mse_after:.4g}); {info.n_corr} border correspondences, mean |cloud - depth| along the border "
+              f"{before:.4f} -> {after:.4f}; {info.n_added} points appended")
 
     data = reproject.align_frames(points, colors, K, render_poses, inner_poses, H, W, fov_x, as_tensors=True)
     frames = torch.stack([f["image"] for f in data["frames"]])

@@ -838,6 +838,106 @@ int lr_reproject(const lr_reproject_args* a);
 int lr_lift(int height, int width, const float* depth, const double* Kinv, const double* Rinv, const double* RinvT,
             float* out_points, void* stream);
 
+/*
+ * Dreaming on the device (generate_pcd, R/luciddreamer.py:424-493): once the networks have produced the new view's depth map D,
+ * its scale against the cloud, the depth offsets along the hole's border, their interpolation into every hole pixel, and the
+ * lift of the corrected depth.  The inputs are lr_reproject's of the same pose: out_valid, out_pix, and an index list formed from
+ * out_border.  Nothing reads back to the host.
+ *
+ * All arithmetic is float64, one IEEE operation each in the order written (no fma), so a numpy restatement gives the same bits
+ * (tests/dream_ref.py).  x, y are a pixel's column and row; Kinv, Rinv, RinvT as for lr_lift, K, R, T as for lr_reproject (one
+ * pose), all HOST float64 and finite.
+ *     liftw(x, y, d)_i = ((Rinv_i0 c_0 + Rinv_i1 c_1) + Rinv_i2 c_2) - RinvT_i,   c_i = (Kinv_i0 (x d) + Kinv_i1 (y d)) + Kinv_i2 d
+ *   (lr_lift's formula without its rounding to float32).  a.b = (a_0 b_0 + a_1 b_1) + a_2 b_2.
+ *
+ *   lr_dream_scale_sums (:424-440; what the reference meant to fit: its 100 Adam steps act on a leaf that is rebuilt from the
+ *   scale's VALUE every step, so the scale never receives a gradient and stays 1).  For every point i with valid[i] != 0 and
+ *   0 <= pix[i] < H W:  P = the point as float64,  q = liftw(pix_i % W, pix_i / W, D[pix_i]);  a pair whose q has a non-finite
+ *   component is left out.  out_sums = {sum P.P, sum P.q, sum q.q} (device, 3 doubles), out_count = the number of pairs (device,
+ *   one long long).  The minimiser of mean |P - s q|^2 is s = Spq / Sqq.  Summation order: thread t of workgroup b holds the
+ *   term of point 256 b + t (0 where there is none); for st = 128, 64, ..., 1: term[t] += term[t + st] for t < st; then the
+ *   workgroup sums are added in index order.  No float atomics: two runs give the same bits.
+ *   workspace: lr_dream_workspace_bytes(n_points) device bytes, 8-byte aligned.
+ *
+ *   lr_dream_correspond (:443-474).  corr [n_corr] int32 (device, ascending): indices of cloud points on the hole's border.  For
+ *   j < n_corr, i = corr[j]:  u, v = lr_reproject's exact projected coordinates of point i (the same operations),
+ *       c = scale * liftw(pix_i % W, pix_i / W, D[pix_i])  (componentwise),   o = -RinvT,  a = c - o,  p = P_i - o,
+ *       t = (p.a) / (a.a),   m = o + a t,   value_j = rowz(m) - rowz(c),   rowz(X) = ((R_20 X_0 + R_21 X_1) + R_22 X_2) + T_2:
+ *   how far along the camera ray the new depth is from the foot of the cloud point.  a.a == 0, a non-finite value_j or a pix_i
+ *   outside [0, H W) gives value_j = NaN (the sample is skipped downstream); an i outside [0, n_points) gives NaN in all three.
+ *   out_su, out_sv, out_sval: device double [n_corr + 4]; the last four are the corners (0,0), (0,H-1), (W-1,0), (W-1,H-1) with
+ *   value 0, in that order (:469-474).
+ *
+ *   lr_scatter_interpolate (OUR definition, in place of :478-479's scipy.interpolate.griddata: linear over a Delaunay
+ *   triangulation with a nearest-neighbour fallback).  A moving least squares fit of an affine function with inverse-distance
+ *   weights.  n_samples >= 0 samples (su, sv, sval), device double; a pixel is a query iff its byte of where [H,W] is 0.  For a
+ *   query (x, y), over the samples in index order, skipping those whose sval is NaN:
+ *       dx = su_j - x,  dy = sv_j - y,  d2 = (dx dx + dy dy) + 1e-12,  w = 1.0 / (d2 d2),  wx = w dx,  wy = w dy,  wv = w sval_j
+ *       S00 += w, S01 += wx, S02 += wy, S11 += wx dx, S12 += wx dy, S22 += wy dy;   B0 += wv, B1 += wv dx, B2 += wv dy
+ *       vmin, vmax = the smallest and largest sval_j
+ *   then  C0 = S11 S22 - S12 S12,  C1 = S02 S12 - S01 S22,  C2 = S01 S12 - S02 S11,
+ *       det = (S00 C0 + S01 C1) + S02 C2,   num = (B0 C0 + B1 C1) + B2 C2,
+ *       r = num / det  if det > 1e-12 ((S00 S11) S22),  else B0 / S00  (Shepard's weighted mean: collinear samples, a query on a
+ *       sample),   t = r > vmin ? r : vmin,   t = t < vmax ? t : vmax   (the affine fit overshoots outside the samples' hull; a
+ *       NaN r takes vmin),   out = float32(t).
+ *   out is 0 where where != 0 or where no sample was usable.  The accumulation is sequential in j: bit-repeatable.  Samples are
+ *   staged on chip in tiles of LR_SCATTER_TILE.
+ *
+ *   lr_dream_lift (:481-489).  dd = float64(D[y,x]) + float64(new_depth[y,x]),  out_i = float32(scale * liftw(x, y, dd)_i),
+ *   out_points [3, H W].  The reference lifts D and new_depth separately, adds, rounds to float32 and then scales; this rounds
+ *   once.  With new_depth = 0 and scale = 1 the result is lr_lift's, bit for bit.
+ *
+ *   0 <= n_points < 2^31, 0 <= n_corr <= 2^31 - 5, 0 <= n_samples < 2^31, H, W >= 1 and H W <= 2^31 - 2^12; scale finite.
+ *   struct_bytes is checked before anything else; every check sits in front of the first HIP call.  Each entry point reads the
+ *   members named with it and ignores the others.  Return 0 or a negative LR_ERR_*.
+ */
+#define LR_SCATTER_TILE 256
+typedef struct lr_dream_args {
+    size_t struct_bytes;                     /* = sizeof(lr_dream_args); anything else is LR_ERR_INVALID_ARG */
+    long long n_points;                      /* scale_sums, correspond */
+    const float* points;                     /* scale_sums, correspond: as lr_reproject_args */
+    long long point_stride, coord_stride;
+    const unsigned char* valid;              /* scale_sums: lr_reproject's out_valid [N] */
+    const int* pix;                          /* scale_sums, correspond: lr_reproject's out_pix [N] */
+    int height, width;
+    const float* depth;                      /* all three: D [H,W] */
+    const double* K;                         /* correspond; host */
+    const double* R;                         /* correspond; host */
+    const double* T;                         /* correspond; host */
+    const double* Kinv;                      /* all three; host */
+    const double* Rinv;                      /* all three; host */
+    const double* RinvT;                     /* all three; host */
+    double scale;                            /* correspond, lift */
+    const int* corr;                         /* correspond: [n_corr] */
+    long long n_corr;
+    double* out_su;                          /* correspond: [n_corr + 4] each */
+    double* out_sv;
+    double* out_sval;
+    double* out_sums;                        /* scale_sums: [3] */
+    long long* out_count;                    /* scale_sums: [1] */
+    const float* new_depth;                  /* lift: [H,W] */
+    float* out_points;                       /* lift: [3, H W] */
+    void* workspace;                         /* scale_sums */
+    size_t workspace_bytes;
+    void* stream;
+} lr_dream_args;
+typedef struct lr_scatter_args {
+    size_t struct_bytes;                     /* = sizeof(lr_scatter_args); anything else is LR_ERR_INVALID_ARG */
+    long long n_samples;
+    const double* su;                        /* [n_samples] each; may be NULL when n_samples == 0 */
+    const double* sv;
+    const double* sval;
+    int height, width;
+    const unsigned char* where;              /* [H,W]: 0 = query */
+    float* out;                              /* [H,W] */
+    void* stream;
+} lr_scatter_args;
+size_t lr_dream_workspace_bytes(long long n_points);
+int lr_dream_scale_sums(const lr_dream_args* a);
+int lr_dream_correspond(const lr_dream_args* a);
+int lr_dream_lift(const lr_dream_args* a);
+int lr_scatter_interpolate(const lr_scatter_args* a);
+
 /* present[P] (1 byte each) = view-space z > 0.2.  Returns 0 or a negative LR_ERR_*. */
 int lr_mark_visible(int P, const float* means3D, const float* viewmatrix, const float* projmatrix,
                     unsigned char* present, void* stream);

@@ -20,4 +20,7 @@ def __getattr__(name):
     if name in ("mcmc", "filter3d", "reproject"):
         import importlib
         return importlib.import_module("." + name, __name__)
+    if name in ("fit_scale", "scatter_interpolate", "compensate", "dream_step"):     # dreaming on the device (reproject.py)
+        import importlib
+        return getattr(importlib.import_module(".reproject", __name__), name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

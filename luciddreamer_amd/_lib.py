@@ -42,7 +42,8 @@ EXPORTS = ("lr_last_error", "lr_version", "lr_geom_bytes", "lr_img_bytes", "lr_b
            "lr_alpha_hole_backward", "lr_set_antialiasing", "lr_get_antialiasing",
            "lr_mcmc_workspace_bytes", "lr_mcmc_relocate", "lr_mcmc_noise", "lr_mcmc_reg_grad",
            "lr_filter3d_workspace_bytes", "lr_filter3d_update", "lr_filter3d_apply_forward", "lr_filter3d_apply_backward",
-           "lr_reproject_workspace_bytes", "lr_reproject", "lr_lift")
+           "lr_reproject_workspace_bytes", "lr_reproject", "lr_lift",
+           "lr_dream_workspace_bytes", "lr_dream_scale_sums", "lr_dream_correspond", "lr_dream_lift", "lr_scatter_interpolate")
 
 # lr_views_workspace_bytes / lr_views_check `parts`: what a step's workspace slots hold besides a view's scratch
 LR_VIEWS_LOSS, LR_VIEWS_DEPTH_LOSS, LR_VIEWS_MASK_LOSS = 1, 2, 4
@@ -148,6 +149,34 @@ class ReprojectArgs(ctypes.Structure):
 
     def __init__(self, **fields):
         super().__init__(struct_bytes=ctypes.sizeof(ReprojectArgs), **fields)
+
+
+class DreamArgs(ctypes.Structure):
+    """lr_dream_args, field for field (tests/test_dream_cpu.py compares the offsets with the host compiler's).  K, R, T, Kinv, Rinv
+    and RinvT are HOST float64 arrays; each entry point reads its own members."""
+    _vp, _ci, _ll = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong
+    _fields_ = [("struct_bytes", ctypes.c_size_t), ("n_points", _ll), ("points", _vp), ("point_stride", _ll),
+                ("coord_stride", _ll), ("valid", _vp), ("pix", _vp), ("height", _ci), ("width", _ci), ("depth", _vp),
+                ("K", _vp), ("R", _vp), ("T", _vp), ("Kinv", _vp), ("Rinv", _vp), ("RinvT", _vp), ("scale", ctypes.c_double),
+                ("corr", _vp), ("n_corr", _ll), ("out_su", _vp), ("out_sv", _vp), ("out_sval", _vp),
+                ("out_sums", _vp), ("out_count", _vp), ("new_depth", _vp), ("out_points", _vp),
+                ("workspace", _vp), ("workspace_bytes", ctypes.c_size_t), ("stream", _vp)]
+
+    def __init__(self, **fields):
+        super().__init__(struct_bytes=ctypes.sizeof(DreamArgs), **fields)
+
+
+class ScatterArgs(ctypes.Structure):
+    """lr_scatter_args, field for field."""
+    _vp, _ci = ctypes.c_void_p, ctypes.c_int
+    _fields_ = [("struct_bytes", ctypes.c_size_t), ("n_samples", ctypes.c_longlong), ("su", _vp), ("sv", _vp), ("sval", _vp),
+                ("height", _ci), ("width", _ci), ("where", _vp), ("out", _vp), ("stream", _vp)]
+
+    def __init__(self, **fields):
+        super().__init__(struct_bytes=ctypes.sizeof(ScatterArgs), **fields)
+
+
+LR_SCATTER_TILE = 256               # samples per on-chip tile of lr_scatter_interpolate (include/lucid_raster.h)
 
 
 def assert_single_copy():
@@ -298,6 +327,13 @@ def lib():
         L.lr_reproject.argtypes = [ctypes.POINTER(ReprojectArgs)]
         L.lr_lift.restype = ci
         L.lr_lift.argtypes = [ci, ci, vp, vp, vp, vp, vp, vp]                   # H W depth Kinv Rinv RinvT (host) out stream
+        L.lr_dream_workspace_bytes.restype = ctypes.c_size_t
+        L.lr_dream_workspace_bytes.argtypes = [ll]
+        for fn in (L.lr_dream_scale_sums, L.lr_dream_correspond, L.lr_dream_lift):
+            fn.restype = ci
+            fn.argtypes = [ctypes.POINTER(DreamArgs)]
+        L.lr_scatter_interpolate.restype = ci
+        L.lr_scatter_interpolate.argtypes = [ctypes.POINTER(ScatterArgs)]
         L.lr_step_begin.restype = ci
         L.lr_step_begin.argtypes = []
         L.lr_step_end.restype = ci

@@ -43,6 +43,8 @@ SOURCES = {
     # point-cloud reprojection: float64 projection in a fixed order, one IEEE operation each (a numpy restatement agrees to the
     # bit): no FMA contraction
     "reproject.hip": ["-ffp-contract=off"],
+    # dreaming (scale sums, correspondences, scattered interpolation, compensated lift): float64 in a fixed order, as above
+    "dream.hip": ["-ffp-contract=off"],
     "api.hip": [],
 }
 
@@ -97,7 +99,7 @@ def build(force=False, verbose=False, diagnostics=False):
     os.makedirs(OBJDIR, exist_ok=True)
     cc = hipcc()
     hash_header = _write_hash_header()
-    headers = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "screen_cull.h"), os.path.join(CSRC, "gauss_bwd_body.h"), os.path.join(CSRC, "loss_ssim_fwd_body.h"),
+    headers = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "screen_cull.h"), os.path.join(CSRC, "project_point.h"), os.path.join(CSRC, "gauss_bwd_body.h"), os.path.join(CSRC, "loss_ssim_fwd_body.h"),
                os.path.join(CSRC, "loss_ssim_bwd_body.h"), os.path.join(INCLUDE, "lucid_raster.h"), os.path.abspath(__file__)]
     objs = []
     procs = []

@@ -653,6 +653,34 @@ hipError_t launch_reproject(const ReprojectLaunch& a, hipStream_t s);
 hipError_t launch_lift(int height, int width, const float* depth, const double* Kinv, const double* Rinv, const double* RinvT,
                        float* out, hipStream_t s);
 
+// dreaming on the device (dream.hip): scale sums, border correspondences, scattered interpolation, compensated lift.
+// K, R, T, Kinv, Rinv, RinvT are HOST float64 arrays of one pose; they travel as kernel arguments.
+struct DreamLaunch {
+    int n_points, height, width;
+    const float* points;            // as ReprojectLaunch
+    long long point_stride, coord_stride;
+    const uint8_t* valid;           // [N]
+    const int* pix;                 // [N]
+    const float* depth;             // [H,W]
+    const double *K, *R, *T, *Kinv, *Rinv, *RinvT;
+    double scale;
+    const int* corr;                // [n_corr]
+    int n_corr;
+    double *out_su, *out_sv, *out_sval;     // [n_corr + 4]
+    double* out_sums;               // [3]
+    long long* out_count;           // [1]
+    const float* new_depth;         // [H,W]
+    float* out_points;              // [3, H W]
+    void* workspace;
+};
+constexpr int DREAM_BLOCK = 256;    // points per workgroup partial of the scale sums; samples per LDS tile of the interpolation
+size_t dream_workspace_bytes(long long n_points);
+hipError_t launch_dream_scale_sums(const DreamLaunch& a, hipStream_t s);
+hipError_t launch_dream_correspond(const DreamLaunch& a, hipStream_t s);
+hipError_t launch_dream_lift(const DreamLaunch& a, hipStream_t s);
+hipError_t launch_scatter_interpolate(long long n_samples, const double* su, const double* sv, const double* sval, int height,
+                                      int width, const uint8_t* where, float* out, hipStream_t s);
+
 void launch_dist2(int P, const float* points, float* out, char* workspace, hipStream_t s);
 size_t dist2_workspace_bytes(int P);
 void dist2_workspace_layout(int P, size_t offsets[4]);

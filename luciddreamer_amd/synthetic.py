@@ -79,3 +79,12 @@ def rgbd_view(height: int, width: int, seed: int = 0):
     image = torch.stack([stripes, 1.0 - stripes, torch.where(box, torch.ones_like(stripes), 0.25 * torch.ones_like(stripes))], dim=-1)
     image = (image + 0.05 * torch.rand(height, width, 3, generator=g)).clamp(0.0, 1.0)
     return image.float().contiguous(), depth.float().contiguous()
+
+
+def miscalibrated_depth(depth: torch.Tensor, scale: float = 1.1, offset: float = 0.05) -> torch.Tensor:
+    """What a monocular depth network hands back for a view whose true depth is `depth` (H,W): off by a global scale
+    (depth / scale) and by a smooth offset of amplitude `offset`.  The stand-in that reproject.dream_step aligns."""
+    height, width = depth.shape
+    y, x = torch.meshgrid(torch.arange(height, dtype=torch.float32), torch.arange(width, dtype=torch.float32), indexing="ij")
+    wave = torch.sin(x * (2.0 * math.pi / width)) * torch.cos(y * (math.pi / height))
+    return (depth.cpu() / scale + offset * wave).float().contiguous().to(depth.device)

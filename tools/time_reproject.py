@@ -13,6 +13,12 @@ including its allocations and the gap to the next launch.
   lift            one depth map
   restatement     tests/reproject_ref.py project() for one pose on the host (one run, wall clock), whose every output the device's
                   frame must equal at this size too ("equal": true)
+  dream           what follows the networks (csrc/dream.hip), on the first pose's frame and a miscalibrated synthetic depth map:
+                  fit_scale (a, with its 32-byte read-back), correspond (b), scatter_interpolate (c) on the frame's own samples and
+                  holes, dream_lift (d), compensate and dream_step as called; (c) again with 10 000 random samples on a half-empty
+                  frame (the left half of the pixels are holes) and on an all-hole frame, with the float64 operation rate reached
+                  (25 operations per pixel and sample); tests/dream_ref.py on the host beside each (one run, wall clock; for the
+                  10 000-sample case on every 32nd hole pixel only), and whether the device's output equals it
 --resources compiles csrc/reproject.hip with -Rpass-analysis=kernel-resource-usage and records registers, scratch, LDS and
 occupancy per kernel; a kernel with scratch is an error.  Both modes merge their section into --out (default
 profiles/reproject_timing.json), keeping the other's.
@@ -34,10 +40,11 @@ if ROOT not in sys.path:
 
 def resources():
     from luciddreamer_amd import build
-    src = os.path.join(build.CSRC, "reproject.hip")
-    cmd = [build.hipcc(), "-c", src, "-o", os.devnull] + build.COMMON_FLAGS + ["-I", build.OBJDIR] + build.SOURCES["reproject.hip"] + \
-          ["-Rpass-analysis=kernel-resource-usage"]
-    text = subprocess.run(cmd, check=True, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True).stdout
+    text = ""
+    for name in ("reproject.hip", "dream.hip"):
+        cmd = [build.hipcc(), "-c", os.path.join(build.CSRC, name), "-o", os.devnull] + build.COMMON_FLAGS + \
+              ["-I", build.OBJDIR] + build.SOURCES[name] + ["-Rpass-analysis=kernel-resource-usage"]
+        text += subprocess.run(cmd, check=True, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True).stdout
     out, name = {}, None
     keys = {"VGPRs": "vgprs", "TotalSGPRs": "sgprs", "ScratchSize [bytes/lane]": "scratch_bytes_per_lane",
             "Occupancy [waves/SIMD]": "occupancy_waves_per_simd", "LDS Size [bytes/block]": "lds_bytes_per_block"}
@@ -45,7 +52,7 @@ def resources():
         m = re.search(r"remark: Function Name: (\S+)", line)
         if m:
             mangled = m.group(1)
-            k = re.search(r"k_(project|splat|window|resolve|lift)", mangled)
+            k = re.search(r"k_(project|splat|window|resolve|lift|scale_partial|scale_final|correspond|interp|dream_lift)", mangled)
             name = k.group(0) if k else mangled
             if name == "k_window":
                 name += "<dilate>" if "ILi4E" in mangled else "<erode>"
@@ -130,7 +137,74 @@ def timing(a):
     got = dict(image=f.image, image_u8=f.image_u8, mask=f.mask, dil=f.dilated, border=f.border, depth=f.depth, valid=f.valid,
                pix=f.pix)
     out["equal"] = all(np.array_equal(got[k].cpu().numpy(), ref[k]) for k in got)
+    out["dream"] = dream_timing(window, dev, X, C, Xh, Ch, f, ref, K, Rs[0], Ts[0], H, W)
     return out
+
+
+def dream_timing(window, dev, X, C, Xh, Ch, f, ref, K, R, T, H, W):
+    """(a)-(d) of csrc/dream.hip on the frame `f` (restated: `ref`) of the timing run's cloud."""
+    import ctypes
+    import numpy as np
+    import torch
+    from luciddreamer_amd import _lib, reproject, synthetic
+    from tests import dream_ref as DR
+    L = _lib.lib()
+    net = synthetic.miscalibrated_depth(synthetic.rgbd_view(H, W)[1]).to(dev)
+    neth = net.cpu().numpy()
+    image = (synthetic.rgbd_view(H, W)[0] * 255.0).round().to(torch.uint8).to(dev)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    pose = reproject._Pose(K, R, T)
+    N = int(X.shape[1])
+    fit = reproject.fit_scale(X, f, net, K, R, T)
+    comp = reproject.compensate(X, f, net, K, R, T, scale=fit.scale)
+    M = comp.n_corr
+    holes = int((f.mask == 0).sum())
+    d = {"n_corr": M, "hole_pixels": holes, "valid_points": int(f.valid.sum()), "scale": fit.scale, "mse_before": fit.mse_before,
+         "mse_after": fit.mse_after}
+    d["a_fit_scale"] = window(lambda: reproject.fit_scale(X, f, net, K, R, T))
+    corr = (f.border.reshape(-1)[f.pix.clamp(min=0).long()].bool() & f.valid.bool()).nonzero()[:, 0].to(torch.int32).contiguous()
+    s3 = torch.empty((3, M + 4), dtype=torch.float64, device=dev)
+    common = dict(height=H, width=W, depth=net.data_ptr(), scale=fit.scale, stream=stream, **pose.fields())
+    ca = _lib.DreamArgs(n_points=N, points=X.data_ptr(), point_stride=1, coord_stride=N, pix=f.pix.data_ptr(),
+                        corr=corr.data_ptr() if M else None, n_corr=M, out_su=s3[0].data_ptr(), out_sv=s3[1].data_ptr(),
+                        out_sval=s3[2].data_ptr(), **common)
+    d["b_correspond"] = window(lambda: L.lr_dream_correspond(ctypes.byref(ca)))
+    uv, val = comp.corr_uv.contiguous(), comp.corr_value.contiguous()
+    d["c_scatter_interpolate"] = window(lambda: reproject.scatter_interpolate(uv, val, H, W, f.mask))
+    lifted = torch.empty((3, H * W), dtype=torch.float32, device=dev)
+    la = _lib.DreamArgs(new_depth=comp.new_depth.data_ptr(), out_points=lifted.data_ptr(), **common)
+    d["d_dream_lift"] = window(lambda: L.lr_dream_lift(ctypes.byref(la)))
+    d["compensate"] = window(lambda: reproject.compensate(X, f, net, K, R, T, scale=fit.scale))
+    d["dream_step"] = window(lambda: reproject.dream_step(X, C, f, image, net, K, R, T))
+    # the host restatement of the same call, and equality
+    t0 = time.perf_counter()
+    want_p, want_c, info = DR.dream_step(Xh, Ch, ref, image.cpu().numpy(), neth, K, R, T, H, W, "lstsq")
+    d["restatement_dream_step_s"] = time.perf_counter() - t0
+    pts, cols, got = reproject.dream_step(X, C, f, image, net, K, R, T)
+    d["equal"] = bool(np.array_equal(pts.cpu().numpy(), want_p) and np.array_equal(cols.cpu().numpy(), want_c) and
+                      got.scale == info["scale"] and np.array_equal(comp.new_depth.cpu().numpy(), info["comp"]["new_depth"]))
+    # (c) at the size the kernel is built for: 10 000 samples, half of the frame / all of it to fill
+    rng = np.random.default_rng(1)
+    Ms = 10_000
+    su, sv, sv_ = rng.uniform(0, W - 1, Ms), rng.uniform(0, H - 1, Ms), rng.uniform(-0.5, 0.5, Ms)
+    uvd = torch.from_numpy(np.stack([su, sv], axis=1)).to(dev)
+    vald = torch.from_numpy(sv_).to(dev)
+    for name, where in (("half_empty", np.tile((np.arange(W) >= W // 2).astype(np.uint8), (H, 1))),
+                        ("all_holes", np.zeros((H, W), dtype=np.uint8))):
+        wd = torch.from_numpy(where).to(dev)
+        r = window(lambda: reproject.scatter_interpolate(uvd, vald, H, W, wd))
+        q = int((where == 0).sum())
+        r["samples"], r["hole_pixels"] = Ms, q
+        r["float64_gops_per_s"] = 25.0 * q * Ms / (r["median_ms"] * 1e-3) / 1e9
+        sub = np.full((H, W), 1, dtype=np.uint8)
+        sub.reshape(-1)[np.nonzero(where.reshape(-1) == 0)[0][::32]] = 0
+        t0 = time.perf_counter()
+        host = DR.scatter(su, sv, sv_, H, W, sub)
+        r["restatement_every_32nd_hole_s"] = time.perf_counter() - t0
+        g = reproject.scatter_interpolate(uvd, vald, H, W, wd).cpu().numpy()
+        r["equal_on_those"] = bool(np.array_equal(g[sub == 0], host[sub == 0]))
+        d["c_10000_samples_" + name] = r
+    return d
 
 
 def main():
@@ -159,6 +233,8 @@ def main():
     print(json.dumps(data["kernel_resources" if a.resources else "timing"], indent=1))
     if not a.resources and not data["timing"]["equal"]:
         raise SystemExit("the device's frame differs from the restatement")
+    if not a.resources and not data["timing"]["dream"]["equal"]:
+        raise SystemExit("the device's dream step differs from the restatement")
 
 
 if __name__ == "__main__":
