@@ -20,12 +20,15 @@ from oracle.torch_oracle import cov3d_from_scale_rot, sh_to_rgb
 def render(means3D, opacities, viewmatrix, projmatrix, campos, tanfovx, tanfovy, H, W, bg,
            scales=None, rotations=None, scale_modifier=1.0, cov3D_precomp=None,
            shs=None, degree=0, colors_precomp=None, means2D=None, dtype=torch.float64, detach_depth=False, alpha=False,
-           with_layers=False):
+           with_layers=False, pixel_probe=None):
     """oracle.torch_oracle.render with a differentiable depth output: returns (color (3,H,W), depth (1,H,W), radii (P,)
     int32).  detach_depth=True puts back the two detach() calls of torch_oracle (its docstring, point iii).
     alpha=True: (color, depth, alpha (1,H,W), radii), alpha = 1 - T_final differentiable.
     with_layers=True appends a list of per-tile dicts {ids, contrib, alpha, T_fin, pix} (the applied layers of every pixel of
-    the tile, detached) for closed-form checks."""
+    the tile, detached) for closed-form checks.
+    pixel_probe: a list; every non-empty tile appends (ids, (ys, xs), E) with E a zero leaf [256, len(ids), 2] added to every
+    pixel's own offset (dx, dy) to the Gaussians of the tile, so that dL/dE[p, k] is the share of dL/d(mean of ids[k], in pixels)
+    that flows through pixel p -- all shares from one backward."""
     cv = lambda t: None if t is None else t.to(dtype)
     means3D, opacities, scales, rotations = cv(means3D), cv(opacities), cv(scales), cv(rotations)
     cov3D_precomp, shs, colors_precomp, means2D = cv(cov3D_precomp), cv(shs), cv(colors_precomp), cv(means2D)
@@ -104,6 +107,10 @@ def render(means3D, opacities, viewmatrix, projmatrix, campos, tanfovx, tanfovy,
             else:
                 dx = px[ids][None, :] - pxf[:, None]
                 dy = py[ids][None, :] - pyf[:, None]
+                if pixel_probe is not None:
+                    E = torch.zeros(256, ids.numel(), 2, dtype=dtype, requires_grad=True)
+                    dx, dy = dx + E[:, :, 0], dy + E[:, :, 1]
+                    pixel_probe.append((ids, (ys.reshape(-1), xs.reshape(-1)), E))
                 cn = conic[ids]
                 power = -0.5 * (cn[:, 0][None] * dx * dx + cn[:, 2][None] * dy * dy) - cn[:, 1][None] * dx * dy
                 G = torch.exp(torch.clamp_max(power, 0.0))

@@ -129,8 +129,6 @@ def compare_grads_by_row(hip, ref, P, names=("means2D", "opacity", "means3D", "s
     T = 1e-4: "fragile") -- those within 1e-3, at most `max_outliers` per tensor, and each one must be located on such
     a pixel.  Returns {tensor: (worst relative row error, outliers)}."""
     st = ref["res"].stage()
-    fy, fx = np.nonzero(st["fragile"] != 0)
-    m2, radii = st["means2D"], ref["radii"]
     report = {}
     for k in names:
         a = hip["grads"][k].reshape(P, -1)
@@ -142,14 +140,20 @@ def compare_grads_by_row(hip, ref, P, names=("means2D", "opacity", "means3D", "s
         assert len(bad) <= max_outliers, (k, len(bad))
         assert row_err.max() <= 1e-3 * scale, (k, row_err.max(), scale)
         for i in bad:
-            # each outlier must TOUCH a flagged pixel: its own alpha there reaches the 1/255 threshold (to within 10 %),
-            # i.e. the pixel lies inside the splat's actual support, not merely inside its bounding square
-            ca, cb, cc, op = st["conic_opacity"][i].astype(np.float64)
-            dx, dy = m2[i, 0] - fx.astype(np.float64), m2[i, 1] - fy.astype(np.float64)
-            power = -0.5 * (ca * dx * dx + cc * dy * dy) - cb * dx * dy
-            touches = (power <= 1e-6) & (op * np.exp(np.minimum(power, 0.0)) >= 0.9 / 255.0)
-            assert touches.any(), f"{k}: Gaussian {i} differs by {row_err[i] / scale:.2e} and touches no threshold-fragile pixel"
+            assert touches_fragile(st, i), \
+                f"{k}: Gaussian {i} differs by {row_err[i] / scale:.2e} and touches no threshold-fragile pixel"
     return report
+
+
+def touches_fragile(st, i):
+    """Does Gaussian i TOUCH a pixel the oracle flags as sitting on a discrete threshold (st: the oracle result's stage())?  Its
+    own alpha there reaches the 1/255 threshold (to within 10 %), i.e. the pixel lies inside the splat's actual support, not
+    merely inside its bounding square."""
+    fy, fx = np.nonzero(st["fragile"] != 0)
+    ca, cb, cc, op = st["conic_opacity"][i].astype(np.float64)
+    dx, dy = st["means2D"][i, 0] - fx.astype(np.float64), st["means2D"][i, 1] - fy.astype(np.float64)
+    power = -0.5 * (ca * dx * dx + cc * dy * dy) - cb * dx * dy
+    return bool(((power <= 1e-6) & (op * np.exp(np.minimum(power, 0.0)) >= 0.9 / 255.0)).any())
 
 
 def box_setup(P, W, H, seed=0, scale_mult=1.0, sh_coeffs=16):
