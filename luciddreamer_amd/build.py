@@ -99,8 +99,9 @@ def build(force=False, verbose=False, diagnostics=False):
     os.makedirs(OBJDIR, exist_ok=True)
     cc = hipcc()
     hash_header = _write_hash_header()
-    headers = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "screen_cull.h"), os.path.join(CSRC, "project_point.h"), os.path.join(CSRC, "gauss_bwd_body.h"), os.path.join(CSRC, "loss_ssim_fwd_body.h"),
-               os.path.join(CSRC, "loss_ssim_bwd_body.h"), os.path.join(INCLUDE, "lucid_raster.h"), os.path.abspath(__file__)]
+    # every header under csrc/ (as source_hash() takes them): a new one cannot be missed as a dependency
+    headers = [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC)) if f.endswith(".h")] + \
+              [os.path.join(INCLUDE, "lucid_raster.h"), os.path.abspath(__file__)]
     objs = []
     procs = []
     for src, extra in SOURCES.items():

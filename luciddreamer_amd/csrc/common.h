@@ -5,11 +5,10 @@
 #include <stdint.h>
 #include <stddef.h>
 #include "screen_cull.h"
+#include "gauss_project.h"     // TILE_X / TILE_Y, the projection chain, aa_coef
 
 namespace lr {
 
-constexpr int TILE_X = 16;          // RAST/cuda_rasterizer/config.h:16-17 (tile geometry is part of the
-constexpr int TILE_Y = 16;          // observable behaviour: it decides which Gaussians reach a pixel)
 constexpr int TILE_PIX = TILE_X * TILE_Y;
 constexpr int WAVE = 64;
 
@@ -248,26 +247,6 @@ __device__ __forceinline__ float cull_qmax(float opacity)
     return (opacity > 0.f) ? (logf(255.0f * opacity) + CULL_MARGIN) : -3.0e38f;
 }
 
-// ---- anti-aliasing (lr_set_antialiasing): opacity compensation for the 2D dilation ---------------------------------------
-// The screen-space covariance {a0, b, c0} is dilated by AA_DILATION on its diagonal before it is inverted (forward.cu:219), which
-// spreads a splat without dimming it: a sub-pixel splat deposits more energy than it holds.  With anti-aliasing on the record's
-// opacity is multiplied by coef = sqrt(max(AA_RHO_FLOOR, det0 / det)), det0 / det the determinants before / after the dilation
-// (the 2D Mip filter of Mip-Splatting, the `antialiasing` switch of the upstream rasterizer).  ONE definition, every operation
-// rounded on its own in this order whatever the contraction setting of the translation unit: both preprocess kernels must give
-// the same bits, and tests/aa_ref.py restates it operation for operation.  `det` = (a0 + h) (c0 + h) - b b as preprocess forms it.
-constexpr float AA_DILATION = 0.3f;
-constexpr float AA_RHO_FLOOR = 0.000025f;
-struct AACoef { float det0, rho, coef; };
-__device__ __forceinline__ AACoef aa_coef(float a0, float b, float c0, float det)
-{
-#pragma clang fp contract(off)
-    AACoef r;
-    r.det0 = a0 * c0 - b * b;
-    r.rho = r.det0 / det;
-    r.coef = sqrtf(fmaxf(AA_RHO_FLOOR, r.rho));
-    return r;
-}
-
 // ---- launchers (one per translation unit) ------------------------------------------------------
 // Exponent of a splat at a pixel (offsets dx, dy from the centre):
 //   power = -0.5 (a dx^2 + c dy^2) - b dx dy  (forward.cu:332-334)  =  (Ap dx + Bp dy) dx + Cp dy dy
@@ -383,9 +362,8 @@ __device__ __forceinline__ float act_quat_inv_norm(float r, float x, float y, fl
 void launch_preprocess(const ViewParams& vp, const float* means3D, const float* scales, const float* rotations,
                        const float* opacities, const float* shs, const float* cov3D_precomp,
                        const float* colors_precomp, bool prefiltered, int* radii, GaussRec* rec,
-                       uint8_t* clamped, uint32_t* tiles_touched, uint4* hitrec, uint32_t* depth_key,
-                       GeomHeader* hdr, uint32_t binning_capacity, uint32_t* chunk_sums, bool sparse_view_hint, hipStream_t s,
-                       bool antialiasing = false);
+                       uint8_t* clamped, uint32_t* tiles_touched, uint4* hitrec, GeomHeader* hdr,
+                       uint32_t* chunk_sums, bool sparse_view_hint, hipStream_t s, bool antialiasing = false);
 // antialiasing: the <RAW, AA = true> kernels, which store opacity * aa_coef(...).coef (and its cull threshold) in the record
 // chunk_sums: [ceil(P / SCAN_TILE)] x {emitting Gaussians, instances, rectangle areas, -} + one word (the prefilter trap), ZERO on
 // entry -- the library's own per-stream scratch (api.hip StreamScratch), cleared again by the first binning kernel once

@@ -19,40 +19,6 @@ namespace lr {
 
 namespace {
 
-__device__ constexpr float SH_C0 = 0.28209479177387814f;
-__device__ constexpr float SH_C1 = 0.4886025119029199f;
-__device__ constexpr float SH_C2[5] = { 1.0925484305920792f, -1.0925484305920792f, 0.31539156525252005f,
-                                        -1.0925484305920792f, 0.5462742152960396f };
-__device__ constexpr float SH_C3[7] = { -0.5900435899266435f, 2.890611442640554f, -0.4570457994644658f,
-                                        0.3731763325901154f, -0.4570457994644658f, 1.445305721320277f,
-                                        -0.5900435899266435f };
-
-struct M3 { float c[3][3]; };   // column-major like glm::mat3: c[col][row]
-__device__ __forceinline__ M3 m3_mul(const M3& A, const M3& B)
-{
-    M3 R;
-#pragma unroll
-    for (int j = 0; j < 3; j++)
-#pragma unroll
-        for (int i = 0; i < 3; i++)
-            R.c[j][i] = A.c[0][i] * B.c[j][0] + A.c[1][i] * B.c[j][1] + A.c[2][i] * B.c[j][2];
-    return R;
-}
-__device__ __forceinline__ M3 m3_t(const M3& A)
-{
-    M3 R;
-#pragma unroll
-    for (int j = 0; j < 3; j++)
-#pragma unroll
-        for (int i = 0; i < 3; i++) R.c[j][i] = A.c[i][j];
-    return R;
-}
-
-struct V3 { float x, y, z; };
-__device__ __forceinline__ V3 operator+(V3 a, V3 b) { return { a.x + b.x, a.y + b.y, a.z + b.z }; }
-__device__ __forceinline__ V3 operator*(float s, V3 a) { return { s * a.x, s * a.y, s * a.z }; }
-__device__ __forceinline__ float dot(V3 a, V3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
-
 // SH basis values and their derivatives w.r.t. the (normalised) view direction, band by band
 // (the coefficients of backward.cu:20-139: dRGB/dx = sum_k dbx[k] * sh[k], dL/dsh[k] = b[k] * dL/dRGB).
 template <int DEG>
@@ -119,7 +85,7 @@ __device__ __forceinline__ float row_sum(float v)
 // DEPTH (k_gauss_bwd_depth): g2.y is the Gaussian's dL/d(view depth) from the depth-mode blend backward; it reaches the mean
 // through z = view[2] x + view[6] y + view[10] z + view[14] (column-major view matrix, auxiliary.h:58-66) -- in the raw path
 // the same term is dL/dxyz.
-// AA (the view's forward ran anti-aliased, common.h aa_coef): the record's opacity is opacity * coef(a0, b, c0), so g1.y is
+// AA (the view's forward ran anti-aliased, gauss_project.h aa_coef): the record's opacity is opacity * coef(a0, b, c0), so g1.y is
 // dL/d(record opacity): dL/dopacity = g coef, and dL/drho = g rec_opacity / (2 rho) above the floor reaches the 2D covariance
 // next to the conic's terms.  rec_opacity: the record's opacity (non-raw: read from the geom buffer by the caller; raw: recomputed).
 // STATS (k_gauss_bwd_stats: lr_views_accumulate with the stat_* members): stat_norm, the norm of THIS view's screen-space gradient
@@ -175,9 +141,7 @@ gauss_backward_one(const int idx, const ViewParams& vp, const float* __restrict_
             }
             sx *= vp.scale_modifier; sy *= vp.scale_modifier; sz *= vp.scale_modifier;
             M3 S = { { { sx, 0, 0 }, { 0, sy, 0 }, { 0, 0, sz } } };
-            Rm = { { { 1.f - 2.f * (qy * qy + qz * qz), 2.f * (qx * qy - qr * qz), 2.f * (qx * qz + qr * qy) },
-                     { 2.f * (qx * qy + qr * qz), 1.f - 2.f * (qx * qx + qz * qz), 2.f * (qy * qz - qr * qx) },
-                     { 2.f * (qx * qz - qr * qy), 2.f * (qy * qz + qr * qx), 1.f - 2.f * (qx * qx + qy * qy) } } };
+            Rm = quat_rotation(qr, qx, qy, qz);
             Mm = m3_mul(S, Rm);
             M3 Sig = m3_mul(m3_t(Mm), Mm);
             c3[0] = Sig.c[0][0]; c3[1] = Sig.c[0][1]; c3[2] = Sig.c[0][2];

@@ -115,10 +115,10 @@ k_mcmc_noise(int P, float* __restrict__ xyz, const float* __restrict__ raw_scale
     float px = xyz[i3], py = xyz[i3 + 1], pz = xyz[i3 + 2];
     const float inv = act_quat_inv_norm(q.x, q.y, q.z, q.w);
     const float r = q.x * inv, x = q.y * inv, y = q.z * inv, z = q.w * inv;
-    // the rotation preprocess builds (rows)
-    const float r00 = 1.f - 2.f * (y * y + z * z), r01 = 2.f * (x * y - r * z), r02 = 2.f * (x * z + r * y);
-    const float r10 = 2.f * (x * y + r * z), r11 = 1.f - 2.f * (x * x + z * z), r12 = 2.f * (y * z - r * x);
-    const float r20 = 2.f * (x * z - r * y), r21 = 2.f * (y * z + r * x), r22 = 1.f - 2.f * (x * x + y * y);
+    // the rotation preprocess builds (gauss_project.h; c[k] is row k)
+    const M3 R = quat_rotation(r, x, y, z);
+    const float r00 = R.c[0][0], r01 = R.c[0][1], r02 = R.c[0][2], r10 = R.c[1][0], r11 = R.c[1][1], r12 = R.c[1][2];
+    const float r20 = R.c[2][0], r21 = R.c[2][1], r22 = R.c[2][2];
     // Sigma xi = R (s^2 * (R^T xi))
     const float vx = (r00 * nx + r10 * ny + r20 * nz) * (sx * sx);
     const float vy = (r01 * nx + r11 * ny + r21 * nz) * (sy * sy);

@@ -11,132 +11,69 @@
 // operand order the reference source uses (GLM column-major operator order), so that radii, tile
 // rectangles, depths and conics are bit-identical to the CPU oracle and the discrete outputs
 // (radii, num_rendered, per-tile order) can be compared exactly.  The kernel is HBM-bound, so the
-// missing FMAs cost nothing.
+// missing FMAs cost nothing.  The arithmetic is gauss_project.h, one text for both kernels and for a host build
+// (tests/test_gauss_project_cpu.py pins it to the oracle without a GPU); here: loads, raw-mode activations, record, work split.
 #include <cstddef>
+#include <type_traits>
 #include "common.h"
 
 namespace lr {
 
 namespace {
 
-__device__ constexpr float SH_C0 = 0.28209479177387814f;
-__device__ constexpr float SH_C1 = 0.4886025119029199f;
-__device__ constexpr float SH_C2[5] = { 1.0925484305920792f, -1.0925484305920792f, 0.31539156525252005f,
-                                        -1.0925484305920792f, 0.5462742152960396f };
-__device__ constexpr float SH_C3[7] = { -0.5900435899266435f, 2.890611442640554f, -0.4570457994644658f,
-                                        0.3731763325901154f, -0.4570457994644658f, 1.445305721320277f,
-                                        -0.5900435899266435f };
-
-struct M3 { float c[3][3]; };   // column-major like glm::mat3: c[col][row]
-
-__device__ __forceinline__ M3 m3_mul(const M3& A, const M3& B)
+// The chain (gauss_project.h project_chain, forward.cu:196-232) for Gaussian idx, which passed the near plane: its loads and,
+// in raw mode, its activations.  false: culled (det == 0 or empty tile rectangle).
+template <bool RAW, bool AA>
+__device__ __forceinline__ bool project_gaussian(const ViewParams& vp, int idx, const float* __restrict__ means3D,
+                                                 const float* __restrict__ scales, const float* __restrict__ rotations,
+                                                 const float* __restrict__ cov3D_precomp, GaussProj& out)
 {
-    M3 R;
+    const size_t li = (size_t)idx;
+    const float px_w = means3D[3 * li], py_w = means3D[3 * li + 1], pz_w = means3D[3 * li + 2];
+    float c3[6];
+    if (cov3D_precomp != nullptr) {
 #pragma unroll
-    for (int j = 0; j < 3; j++)
-#pragma unroll
-        for (int i = 0; i < 3; i++)
-            R.c[j][i] = A.c[0][i] * B.c[j][0] + A.c[1][i] * B.c[j][1] + A.c[2][i] * B.c[j][2];
-    return R;
-}
-__device__ __forceinline__ M3 m3_t(const M3& A)
-{
-    M3 R;
-#pragma unroll
-    for (int j = 0; j < 3; j++)
-#pragma unroll
-        for (int i = 0; i < 3; i++) R.c[j][i] = A.c[i][j];
-    return R;
-}
-
-struct V3 { float x, y, z; };
-__device__ __forceinline__ V3 sh_fma(V3 acc, float s, const V3& c, bool sub = false)
-{
-    // acc (+|-) s * c, each product rounded separately (contraction is off in this TU)
-    V3 r;
-    if (sub) { r.x = acc.x - s * c.x; r.y = acc.y - s * c.y; r.z = acc.z - s * c.z; }
-    else     { r.x = acc.x + s * c.x; r.y = acc.y + s * c.y; r.z = acc.z + s * c.z; }
-    return r;
-}
-
-// Load K coefficient triples of Gaussian idx.  M==16 rows are 192 B (16-byte aligned): 12 x dwordx4.
-template <int K>
-__device__ __forceinline__ void load_sh(const float* __restrict__ shs, size_t idx, int M, V3 (&sh)[16])
-{
-    const float* base = shs + idx * (size_t)M * 3;
-    constexpr int NF = 3 * K;
-    float f[(NF + 3) / 4 * 4];
-    if (((M * 3) & 3) == 0 && ((reinterpret_cast<uintptr_t>(shs) & 15) == 0)) {
-        const float4* b4 = reinterpret_cast<const float4*>(base);
-#pragma unroll
-        for (int q = 0; q < (NF + 3) / 4; q++) {
-            float4 v = b4[q];
-            f[4 * q] = v.x; f[4 * q + 1] = v.y; f[4 * q + 2] = v.z; f[4 * q + 3] = v.w;
-        }
+        for (int i = 0; i < 6; i++) c3[i] = cov3D_precomp[6 * (size_t)idx + i];
     } else {
-#pragma unroll
-        for (int q = 0; q < NF; q++) f[q] = base[q];
-    }
-#pragma unroll
-    for (int k = 0; k < K; k++) { sh[k].x = f[3 * k]; sh[k].y = f[3 * k + 1]; sh[k].z = f[3 * k + 2]; }
-}
-
-// raw mode: coefficient 0 from features_dc [P,3], coefficients 1.. from features_rest [P,M-1,3]
-template <int K>
-__device__ __forceinline__ void load_sh_split(const float* __restrict__ dc, const float* __restrict__ rest, size_t idx, int M,
-                                              V3 (&sh)[16])
-{
-    sh[0].x = dc[3 * idx]; sh[0].y = dc[3 * idx + 1]; sh[0].z = dc[3 * idx + 2];
-    const float* base = rest + idx * (size_t)(M - 1) * 3;
-#pragma unroll
-    for (int k = 1; k < K; k++) { sh[k].x = base[3 * (k - 1)]; sh[k].y = base[3 * (k - 1) + 1]; sh[k].z = base[3 * (k - 1) + 2]; }
-}
-
-template <int DEG>
-__device__ __forceinline__ V3 eval_sh(const float* __restrict__ shs, const float* __restrict__ sh_rest, size_t idx, int M, V3 dir,
-                                      uint8_t& clamp_bits)
-{
-    V3 sh[16];
-    if (sh_rest != nullptr) load_sh_split<(DEG + 1) * (DEG + 1)>(shs, sh_rest, idx, M, sh);
-    else load_sh<(DEG + 1) * (DEG + 1)>(shs, idx, M, sh);
-    V3 res = { SH_C0 * sh[0].x, SH_C0 * sh[0].y, SH_C0 * sh[0].z };
-    if (DEG > 0) {
-        float x = dir.x, y = dir.y, z = dir.z;
-        res = sh_fma(res, SH_C1 * y, sh[1], true);
-        res = sh_fma(res, SH_C1 * z, sh[2]);
-        res = sh_fma(res, SH_C1 * x, sh[3], true);
-        if (DEG > 1) {
-            float xx = x * x, yy = y * y, zz = z * z, xy = x * y, yz = y * z, xz = x * z;
-            res = sh_fma(res, SH_C2[0] * xy, sh[4]);
-            res = sh_fma(res, SH_C2[1] * yz, sh[5]);
-            res = sh_fma(res, SH_C2[2] * (2.0f * zz - xx - yy), sh[6]);
-            res = sh_fma(res, SH_C2[3] * xz, sh[7]);
-            res = sh_fma(res, SH_C2[4] * (xx - yy), sh[8]);
-            if (DEG > 2) {
-                res = sh_fma(res, SH_C3[0] * y * (3.0f * xx - yy), sh[9]);
-                res = sh_fma(res, SH_C3[1] * xy * z, sh[10]);
-                res = sh_fma(res, SH_C3[2] * y * (4.0f * zz - xx - yy), sh[11]);
-                res = sh_fma(res, SH_C3[3] * z * (2.0f * zz - 3.0f * xx - 3.0f * yy), sh[12]);
-                res = sh_fma(res, SH_C3[4] * x * (4.0f * zz - xx - yy), sh[13]);
-                res = sh_fma(res, SH_C3[5] * z * (xx - yy), sh[14]);
-                res = sh_fma(res, SH_C3[6] * x * (xx - 3.0f * yy), sh[15]);
-            }
+        float sx = scales[3 * (size_t)idx], sy = scales[3 * (size_t)idx + 1], sz = scales[3 * (size_t)idx + 2];
+        const float4 q = reinterpret_cast<const float4*>(rotations)[idx];
+        float r = q.x, x = q.y, y = q.z, z = q.w;
+        if (RAW) {
+            sx = act_scale(sx); sy = act_scale(sy); sz = act_scale(sz);
+            const float inv = act_quat_inv_norm(r, x, y, z);
+            r *= inv; x *= inv; y *= inv; z *= inv;
         }
+        cov3d_scale_rot(vp.scale_modifier * sx, vp.scale_modifier * sy, vp.scale_modifier * sz, r, x, y, z, c3);
     }
-    res.x += 0.5f; res.y += 0.5f; res.z += 0.5f;
-    clamp_bits = (uint8_t)((res.x < 0 ? 1 : 0) | (res.y < 0 ? 2 : 0) | (res.z < 0 ? 4 : 0));
-    res.x = fmaxf(res.x, 0.0f); res.y = fmaxf(res.y, 0.0f); res.z = fmaxf(res.z, 0.0f);
-    return res;
+    return project_chain<AA>(vp, px_w, py_w, pz_w, c3, out);
 }
 
-// Tile rectangle of a splat (RAST/cuda_rasterizer/auxiliary.h:46-56).
-__device__ __forceinline__ void tile_rect(float px, float py, int radius, int gx, int gy,
-                                          int& minx, int& miny, int& maxx, int& maxy)
+// forward.cu:236-255 for a survivor at world position (wx, wy, wz): colour and record.  Returns the cull threshold for the
+// exact tile count that follows.
+template <bool RAW, bool AA>
+__device__ __forceinline__ float colour_and_record(const ViewParams& vp, int idx, const GaussProj& pj, float wx, float wy, float wz,
+                                                   const float* __restrict__ opacities, const float* __restrict__ shs,
+                                                   const float* __restrict__ colors_precomp, GaussRec* __restrict__ rec,
+                                                   uint8_t* __restrict__ clamped)
 {
-    minx = min(gx, max(0, (int)((px - radius) / TILE_X)));
-    miny = min(gy, max(0, (int)((py - radius) / TILE_Y)));
-    maxx = min(gx, max(0, (int)((px + radius + TILE_X - 1) / TILE_X)));
-    maxy = min(gy, max(0, (int)((py + radius + TILE_Y - 1) / TILE_Y)));
+    V3 rgb;
+    uint8_t cbits = 0;
+    if (colors_precomp != nullptr) {
+        rgb.x = colors_precomp[3 * (size_t)idx]; rgb.y = colors_precomp[3 * (size_t)idx + 1];
+        rgb.z = colors_precomp[3 * (size_t)idx + 2];
+    } else {
+        rgb = sh_colour(vp, shs, RAW ? vp.sh_rest : nullptr, (size_t)idx, wx, wy, wz, cbits);
+    }
+    clamped[idx] = cbits;
+
+    float opacity = RAW ? act_opacity(opacities[idx]) : opacities[idx];
+    if constexpr (AA) opacity = opacity * pj.coef;
+    const float qmax = cull_qmax(opacity);
+    float4* dst = reinterpret_cast<float4*>(rec + idx);
+    dst[0] = make_float4(pj.pix, pj.piy, pj.con_a, pj.con_b);
+    dst[1] = make_float4(pj.con_c, opacity, rgb.x, rgb.y);
+    dst[2] = make_float4(rgb.z, pj.vz, qmax, 0.f);
+    return qmax;
 }
 
 // RAW (lr_view_forward with raw = 1) is a template parameter so that the standard path keeps its register budget (100 VGPRs,
@@ -144,7 +81,10 @@ __device__ __forceinline__ void tile_rect(float px, float py, int radius, int gx
 constexpr int PP_THREADS = 128;                 // Gaussians per workgroup (measured: 64 -> 0.047, 128 -> 0.039, 256 -> 0.042, 512 -> 0.042 ms on C3)
 constexpr int PP_WAVES = PP_THREADS / 64;
 
-// AA (lr_set_antialiasing): the record's opacity is opacity * aa_coef(...).coef (common.h); nothing else differs
+// AA (lr_set_antialiasing): the record's opacity is opacity * aa_coef(...).coef (gauss_project.h); nothing else differs
+// The kernel keeps the flow between the pieces of gauss_project.h (conic, radius, pixel centre: project_chain's own lines) in
+// one body: routed through project_gaussian like the pooled kernel it compiled to 67 registers instead of 87 and measured 2 us
+// faster on the dense 1 M cloud but 0.6 us (1.5 %) slower on C3, outside the run-to-run spread.
 template <bool RAW, bool AA>
 __global__ void __launch_bounds__(PP_THREADS)
 k_preprocess(ViewParams vp, const float* __restrict__ means3D, const float* __restrict__ scales,
@@ -152,8 +92,7 @@ k_preprocess(ViewParams vp, const float* __restrict__ means3D, const float* __re
              const float* __restrict__ shs, const float* __restrict__ cov3D_precomp,
              const float* __restrict__ colors_precomp, int prefiltered,
              int* __restrict__ radii, GaussRec* __restrict__ rec, uint8_t* __restrict__ clamped,
-             uint32_t* __restrict__ tiles_touched, uint4* __restrict__ hitrec,
-             uint32_t* __restrict__ depth_key, GeomHeader* hdr, uint32_t binning_capacity,
+             uint32_t* __restrict__ tiles_touched, uint4* __restrict__ hitrec, GeomHeader* hdr,
              uint32_t* __restrict__ chunk_sums)
 {
     // Phase 1, one thread per Gaussian: the near-plane test (auxiliary.h:152-162).  Survivors are compacted, in index
@@ -164,9 +103,8 @@ k_preprocess(ViewParams vp, const float* __restrict__ means3D, const float* __re
     const int gid = blockIdx.x * blockDim.x + threadIdx.x;
     // the prefilter trap lives behind the chunk sums, in the library's own scratch (zero between forwards: api.hip)
     uint32_t* const trap = chunk_sums != nullptr ? chunk_sums + 4 * ((size_t)(vp.P + SCAN_TILE - 1) / SCAN_TILE) : &hdr->prefilter_trap;
-    const float* __restrict__ V = vp.view;
-    const float* __restrict__ Pm = vp.proj;
     {
+        const float* __restrict__ V = vp.view;
         const bool in_range = gid < vp.P;
         const size_t li = in_range ? (size_t)gid : 0;
         const float vz1 = V[2] * means3D[3 * li] + V[6] * means3D[3 * li + 1] + V[10] * means3D[3 * li + 2] + V[14];
@@ -174,7 +112,6 @@ k_preprocess(ViewParams vp, const float* __restrict__ means3D, const float* __re
         if (in_range && !pass) {
             if (prefiltered) *trap = 1;
             radii[gid] = 0; tiles_touched[gid] = 0;
-            if (depth_key) depth_key[gid] = 0xFFFFFFFFu;
         }
         const uint64_t m = __ballot(pass);
         const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
@@ -195,25 +132,22 @@ k_preprocess(ViewParams vp, const float* __restrict__ means3D, const float* __re
     int radius_out = 0;
     uint32_t tiles_out = 0;               // tile instances this Gaussian will emit (after exact tile culling)
     uint32_t area_ref = 0;                // the reference's tiles_touched (rectangle area)
-    uint32_t key_out = 0xFFFFFFFFu;       // culled Gaussians sort to the end and emit nothing
-
+    const float* __restrict__ V = vp.view;
+    const float* __restrict__ Pm = vp.proj;
     const size_t li = (size_t)idx;
     const float px_w = means3D[3 * li], py_w = means3D[3 * li + 1], pz_w = means3D[3 * li + 2];
-    // view-space point (auxiliary.h:58-66)
     const float vx = V[0] * px_w + V[4] * py_w + V[8] * pz_w + V[12];
     const float vy = V[1] * px_w + V[5] * py_w + V[9] * pz_w + V[13];
     const float vz = V[2] * px_w + V[6] * py_w + V[10] * pz_w + V[14];
 
     do {
         if (!live) break;
-        // clip-space projection (forward.cu:196-200)
         const float hx = Pm[0] * px_w + Pm[4] * py_w + Pm[8] * pz_w + Pm[12];
         const float hy = Pm[1] * px_w + Pm[5] * py_w + Pm[9] * pz_w + Pm[13];
         const float hw = Pm[3] * px_w + Pm[7] * py_w + Pm[11] * pz_w + Pm[15];
         const float p_w = 1.0f / (hw + 0.0000001f);
         const float ndcx = hx * p_w, ndcy = hy * p_w;
 
-        // 3D covariance (forward.cu:118-152), quaternion used as given
         float c3[6];
         if (cov3D_precomp != nullptr) {
 #pragma unroll
@@ -227,28 +161,9 @@ k_preprocess(ViewParams vp, const float* __restrict__ means3D, const float* __re
                 const float inv = act_quat_inv_norm(r, x, y, z);
                 r *= inv; x *= inv; y *= inv; z *= inv;
             }
-            M3 S = { { { vp.scale_modifier * sx, 0, 0 }, { 0, vp.scale_modifier * sy, 0 }, { 0, 0, vp.scale_modifier * sz } } };
-            M3 R = { { { 1.f - 2.f * (y * y + z * z), 2.f * (x * y - r * z), 2.f * (x * z + r * y) },
-                       { 2.f * (x * y + r * z), 1.f - 2.f * (x * x + z * z), 2.f * (y * z - r * x) },
-                       { 2.f * (x * z - r * y), 2.f * (y * z + r * x), 1.f - 2.f * (x * x + y * y) } } };
-            M3 Mm = m3_mul(S, R);
-            M3 Sig = m3_mul(m3_t(Mm), Mm);
-            c3[0] = Sig.c[0][0]; c3[1] = Sig.c[0][1]; c3[2] = Sig.c[0][2];
-            c3[3] = Sig.c[1][1]; c3[4] = Sig.c[1][2]; c3[5] = Sig.c[2][2];
+            cov3d_scale_rot(vp.scale_modifier * sx, vp.scale_modifier * sy, vp.scale_modifier * sz, r, x, y, z, c3);
         }
-
-        // EWA 2D covariance (forward.cu:74-113)
-        const float limx = 1.3f * vp.tan_fovx, limy = 1.3f * vp.tan_fovy;
-        const float txtz = vx / vz, tytz = vy / vz;
-        const float tx = fminf(limx, fmaxf(-limx, txtz)) * vz;
-        const float ty = fminf(limy, fmaxf(-limy, tytz)) * vz;
-        M3 J = { { { vp.focal_x / vz, 0.0f, -(vp.focal_x * tx) / (vz * vz) },
-                   { 0.0f, vp.focal_y / vz, -(vp.focal_y * ty) / (vz * vz) },
-                   { 0, 0, 0 } } };
-        M3 Wm = { { { V[0], V[4], V[8] }, { V[1], V[5], V[9] }, { V[2], V[6], V[10] } } };
-        M3 T = m3_mul(Wm, J);
-        M3 Vrk = { { { c3[0], c3[1], c3[2] }, { c3[1], c3[3], c3[4] }, { c3[2], c3[4], c3[5] } } };
-        M3 cov = m3_mul(m3_mul(m3_t(T), m3_t(Vrk)), T);
+        const M3 cov = ewa_cov2d(vp, vx, vy, vz, c3);
         const float ca = cov.c[0][0] + 0.3f, cb = cov.c[0][1], cc = cov.c[1][1] + 0.3f;
 
         const float det = ca * cc - cb * cb;                   // forward.cu:219-223
@@ -260,7 +175,6 @@ k_preprocess(ViewParams vp, const float* __restrict__ means3D, const float* __re
         const float lambda1 = mid + sqrtf(fmaxf(0.1f, mid * mid - det));
         const float lambda2 = mid - sqrtf(fmaxf(0.1f, mid * mid - det));
         const float my_radius = ceilf(3.f * sqrtf(fmaxf(lambda1, lambda2)));
-        // ndc2Pix evaluates in double (auxiliary.h:41-44)
         const float pix = (float)(((ndcx + 1.0) * vp.W - 1.0) * 0.5);
         const float piy = (float)(((ndcy + 1.0) * vp.H - 1.0) * 0.5);
         int minx, miny, maxx, maxy;
@@ -268,44 +182,16 @@ k_preprocess(ViewParams vp, const float* __restrict__ means3D, const float* __re
         const uint32_t area = (uint32_t)(maxx - minx) * (uint32_t)(maxy - miny);
         if (area == 0) break;
 
-        V3 rgb;
-        uint8_t cbits = 0;
-        if (colors_precomp != nullptr) {
-            rgb.x = colors_precomp[3 * (size_t)idx]; rgb.y = colors_precomp[3 * (size_t)idx + 1];
-            rgb.z = colors_precomp[3 * (size_t)idx + 2];
-        } else {
-            V3 dir = { px_w - vp.campos[0], py_w - vp.campos[1], pz_w - vp.campos[2] };
-            const float len = sqrtf(dir.x * dir.x + dir.y * dir.y + dir.z * dir.z);
-            dir.x = dir.x / len; dir.y = dir.y / len; dir.z = dir.z / len;
-            switch (vp.D) {
-                case 0: rgb = eval_sh<0>(shs, RAW ? vp.sh_rest : nullptr, idx, vp.M, dir, cbits); break;
-                case 1: rgb = eval_sh<1>(shs, RAW ? vp.sh_rest : nullptr, idx, vp.M, dir, cbits); break;
-                case 2: rgb = eval_sh<2>(shs, RAW ? vp.sh_rest : nullptr, idx, vp.M, dir, cbits); break;
-                default: rgb = eval_sh<3>(shs, RAW ? vp.sh_rest : nullptr, idx, vp.M, dir, cbits); break;
-            }
-        }
-        clamped[idx] = cbits;
-
-        GaussRec g;
-        g.x = pix; g.y = piy; g.ca = con_a; g.cb = con_b;
-        g.cc = con_c; g.opacity = RAW ? act_opacity(opacities[idx]) : opacities[idx]; g.r = rgb.x; g.g = rgb.y;
-        if constexpr (AA) g.opacity = g.opacity * aa_coef(cov.c[0][0], cb, cov.c[1][1], det).coef;
-        g.b = rgb.z; g.depth = vz; g.qmax = cull_qmax(g.opacity); g.pad1 = 0.f;
-        float4* dst = reinterpret_cast<float4*>(rec + idx);
-        dst[0] = make_float4(g.x, g.y, g.ca, g.cb);
-        dst[1] = make_float4(g.cc, g.opacity, g.r, g.g);
-        dst[2] = make_float4(g.b, g.depth, g.qmax, 0.f);
-
+        GaussProj pj = { pix, piy, con_a, con_b, con_c, vz, (int)my_radius, 0.f };
+        if constexpr (AA) pj.coef = aa_coef(cov.c[0][0], cb, cov.c[1][1], det).coef;
+        const float qmax = colour_and_record<RAW, AA>(vp, idx, pj, px_w, py_w, pz_w, opacities, shs, colors_precomp, rec, clamped);
         radius_out = (int)my_radius;
         area_ref = area;
-        key_out = __float_as_uint(vz);                         // vz > 0.2: bit order == float order
-        // exact tile culling (common.h): count the tiles of the rectangle that can actually matter
-        // ... and leave the outcome per tile for the binning (common.h HitRec)
+        // exact tile culling (common.h): count the tiles that can matter, and leave the outcome per tile for the binning (HitRec)
         unsigned long long mask = 0ull;
         if (area > CULL_MAX_TILES) {
             tiles_out = area;
         } else {
-            const float qmax = g.qmax;
             const float r_c = -con_b / con_c, r_a = -con_b / con_a;
             uint32_t cnt = 0, j = 0;
             for (int ty = miny; ty < maxy; ty++)
@@ -313,8 +199,9 @@ k_preprocess(ViewParams vp, const float* __restrict__ means3D, const float* __re
                     if (tile_hit(pix, piy, con_a, con_b, con_c, r_c, r_a, qmax, tx, ty)) { cnt++; mask |= 1ull << (j & 63u); }
             tiles_out = cnt;
         }
-        if (tiles_out != 0)
-            hitrec[idx] = make_uint4((uint32_t)mask, (uint32_t)(mask >> 32), hit_geo(minx, miny, maxx - minx, area, vp.hit_origin_limit), key_out);
+        if (tiles_out != 0)                                    // vz > 0.2: bit order == float order
+            hitrec[idx] = make_uint4((uint32_t)mask, (uint32_t)(mask >> 32), hit_geo(minx, miny, maxx - minx, area, vp.hit_origin_limit),
+                                     __float_as_uint(vz));
     } while (false);
 
     // this wave's share of the compaction's chunk sums (tilebin.hip k_compact_write): emitting Gaussians, instances,
@@ -334,7 +221,6 @@ k_preprocess(ViewParams vp, const float* __restrict__ means3D, const float* __re
     if (!live) return;
     radii[idx] = radius_out;
     tiles_touched[idx] = tiles_out;
-    if (depth_key) depth_key[idx] = key_out;
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -351,8 +237,8 @@ k_preprocess(ViewParams vp, const float* __restrict__ means3D, const float* __re
 //             its wave wait for the largest rectangle among 64, and the ~46 survivors of a pool fill one of the four waves
 //   finally   radii and tiles_touched of the whole pool leave in two fully coalesced passes, chunk sums by three integer
 //             atomics per workgroup.
-// Arithmetic is the same code in the same order as in k_preprocess (project_gaussian / colour_and_record are its loop body
-// cut in two), so every record stays bit-identical to the oracle.  Measured on MI355X (profiles/r03g_ab_preprocess.json):
+// Arithmetic is the same code in the same order as in k_preprocess (both call project_gaussian / colour_and_record), so
+// every record stays bit-identical to the oracle.  Measured on MI355X (profiles/r03g_ab_preprocess.json):
 // C3 (9 % visible) 36.5 -> 28.1 us; the thread-per-Gaussian kernel stays ahead when most of the scene is in view (dense
 // 1 M cloud 73 vs 79 us: the compactions buy nothing there) and below ~400 k Gaussians (too few pools to hide a pool's
 // longer chain: 100 k Gaussians 25 vs 35 us) -- launch_preprocess picks per call.
@@ -361,128 +247,6 @@ constexpr int PL_THREADS = 256;
 constexpr int PL_POOL = 512;
 constexpr int PL_WAVES = PL_THREADS / 64;
 constexpr int PL_ROUNDS = PL_POOL / PL_THREADS;
-
-struct Projected { float pix, piy, con_a, con_b, con_c, vz; int radius; float coef; };   // coef: anti-aliased kernels only
-
-// forward.cu:196-232 for one Gaussian that passed the near plane.  false: culled (det == 0 or empty tile rectangle).
-template <bool RAW, bool AA>
-__device__ __forceinline__ bool project_gaussian(const ViewParams& vp, int idx, const float* __restrict__ means3D,
-                                                 const float* __restrict__ scales, const float* __restrict__ rotations,
-                                                 const float* __restrict__ cov3D_precomp, Projected& out)
-{
-    const float* __restrict__ V = vp.view;
-    const float* __restrict__ Pm = vp.proj;
-    const size_t li = (size_t)idx;
-    const float px_w = means3D[3 * li], py_w = means3D[3 * li + 1], pz_w = means3D[3 * li + 2];
-    // view-space point (auxiliary.h:58-66)
-    const float vx = V[0] * px_w + V[4] * py_w + V[8] * pz_w + V[12];
-    const float vy = V[1] * px_w + V[5] * py_w + V[9] * pz_w + V[13];
-    const float vz = V[2] * px_w + V[6] * py_w + V[10] * pz_w + V[14];
-    // clip-space projection (forward.cu:196-200)
-    const float hx = Pm[0] * px_w + Pm[4] * py_w + Pm[8] * pz_w + Pm[12];
-    const float hy = Pm[1] * px_w + Pm[5] * py_w + Pm[9] * pz_w + Pm[13];
-    const float hw = Pm[3] * px_w + Pm[7] * py_w + Pm[11] * pz_w + Pm[15];
-    const float p_w = 1.0f / (hw + 0.0000001f);
-    const float ndcx = hx * p_w, ndcy = hy * p_w;
-
-    // 3D covariance (forward.cu:118-152), quaternion used as given
-    float c3[6];
-    if (cov3D_precomp != nullptr) {
-#pragma unroll
-        for (int i = 0; i < 6; i++) c3[i] = cov3D_precomp[6 * (size_t)idx + i];
-    } else {
-        float sx = scales[3 * (size_t)idx], sy = scales[3 * (size_t)idx + 1], sz = scales[3 * (size_t)idx + 2];
-        const float4 q = reinterpret_cast<const float4*>(rotations)[idx];
-        float r = q.x, x = q.y, y = q.z, z = q.w;
-        if (RAW) {
-            sx = act_scale(sx); sy = act_scale(sy); sz = act_scale(sz);
-            const float inv = act_quat_inv_norm(r, x, y, z);
-            r *= inv; x *= inv; y *= inv; z *= inv;
-        }
-        M3 S = { { { vp.scale_modifier * sx, 0, 0 }, { 0, vp.scale_modifier * sy, 0 }, { 0, 0, vp.scale_modifier * sz } } };
-        M3 R = { { { 1.f - 2.f * (y * y + z * z), 2.f * (x * y - r * z), 2.f * (x * z + r * y) },
-                   { 2.f * (x * y + r * z), 1.f - 2.f * (x * x + z * z), 2.f * (y * z - r * x) },
-                   { 2.f * (x * z - r * y), 2.f * (y * z + r * x), 1.f - 2.f * (x * x + y * y) } } };
-        M3 Mm = m3_mul(S, R);
-        M3 Sig = m3_mul(m3_t(Mm), Mm);
-        c3[0] = Sig.c[0][0]; c3[1] = Sig.c[0][1]; c3[2] = Sig.c[0][2];
-        c3[3] = Sig.c[1][1]; c3[4] = Sig.c[1][2]; c3[5] = Sig.c[2][2];
-    }
-
-    // EWA 2D covariance (forward.cu:74-113)
-    const float limx = 1.3f * vp.tan_fovx, limy = 1.3f * vp.tan_fovy;
-    const float txtz = vx / vz, tytz = vy / vz;
-    const float tx = fminf(limx, fmaxf(-limx, txtz)) * vz;
-    const float ty = fminf(limy, fmaxf(-limy, tytz)) * vz;
-    M3 J = { { { vp.focal_x / vz, 0.0f, -(vp.focal_x * tx) / (vz * vz) },
-               { 0.0f, vp.focal_y / vz, -(vp.focal_y * ty) / (vz * vz) },
-               { 0, 0, 0 } } };
-    M3 Wm = { { { V[0], V[4], V[8] }, { V[1], V[5], V[9] }, { V[2], V[6], V[10] } } };
-    M3 T = m3_mul(Wm, J);
-    M3 Vrk = { { { c3[0], c3[1], c3[2] }, { c3[1], c3[3], c3[4] }, { c3[2], c3[4], c3[5] } } };
-    M3 cov = m3_mul(m3_mul(m3_t(T), m3_t(Vrk)), T);
-    const float ca = cov.c[0][0] + 0.3f, cb = cov.c[0][1], cc = cov.c[1][1] + 0.3f;
-
-    const float det = ca * cc - cb * cb;                   // forward.cu:219-223
-    if (det == 0.0f) return false;
-    const float det_inv = 1.f / det;
-    out.con_a = cc * det_inv; out.con_b = -cb * det_inv; out.con_c = ca * det_inv;
-    if constexpr (AA) out.coef = aa_coef(cov.c[0][0], cb, cov.c[1][1], det).coef;
-
-    const float mid = 0.5f * (ca + cc);                    // forward.cu:229-232
-    const float lambda1 = mid + sqrtf(fmaxf(0.1f, mid * mid - det));
-    const float lambda2 = mid - sqrtf(fmaxf(0.1f, mid * mid - det));
-    const float my_radius = ceilf(3.f * sqrtf(fmaxf(lambda1, lambda2)));
-    // ndc2Pix evaluates in double (auxiliary.h:41-44)
-    out.pix = (float)(((ndcx + 1.0) * vp.W - 1.0) * 0.5);
-    out.piy = (float)(((ndcy + 1.0) * vp.H - 1.0) * 0.5);
-    out.radius = (int)my_radius;
-    out.vz = vz;
-    int minx, miny, maxx, maxy;
-    tile_rect(out.pix, out.piy, out.radius, vp.gx, vp.gy, minx, miny, maxx, maxy);
-    return (uint32_t)(maxx - minx) * (uint32_t)(maxy - miny) != 0u;
-}
-
-// forward.cu:236-255 for a survivor: colour and record.  Returns the tile rectangle (origin, width, area) and the cull
-// threshold for the exact tile count that follows.
-template <bool RAW, bool AA>
-__device__ __forceinline__ void colour_and_record(const ViewParams& vp, int idx, const Projected& pj,
-                                                  const float* __restrict__ means3D, const float* __restrict__ opacities,
-                                                  const float* __restrict__ shs, const float* __restrict__ colors_precomp,
-                                                  GaussRec* __restrict__ rec, uint8_t* __restrict__ clamped,
-                                                  int& minx, int& miny, int& width, uint32_t& area, float& qmax)
-{
-    int maxx, maxy;
-    tile_rect(pj.pix, pj.piy, pj.radius, vp.gx, vp.gy, minx, miny, maxx, maxy);
-    width = maxx - minx;
-    area = (uint32_t)(maxx - minx) * (uint32_t)(maxy - miny);
-    V3 rgb;
-    uint8_t cbits = 0;
-    if (colors_precomp != nullptr) {
-        rgb.x = colors_precomp[3 * (size_t)idx]; rgb.y = colors_precomp[3 * (size_t)idx + 1];
-        rgb.z = colors_precomp[3 * (size_t)idx + 2];
-    } else {
-        const size_t li = (size_t)idx;
-        V3 dir = { means3D[3 * li] - vp.campos[0], means3D[3 * li + 1] - vp.campos[1], means3D[3 * li + 2] - vp.campos[2] };
-        const float len = sqrtf(dir.x * dir.x + dir.y * dir.y + dir.z * dir.z);
-        dir.x = dir.x / len; dir.y = dir.y / len; dir.z = dir.z / len;
-        switch (vp.D) {
-            case 0: rgb = eval_sh<0>(shs, RAW ? vp.sh_rest : nullptr, idx, vp.M, dir, cbits); break;
-            case 1: rgb = eval_sh<1>(shs, RAW ? vp.sh_rest : nullptr, idx, vp.M, dir, cbits); break;
-            case 2: rgb = eval_sh<2>(shs, RAW ? vp.sh_rest : nullptr, idx, vp.M, dir, cbits); break;
-            default: rgb = eval_sh<3>(shs, RAW ? vp.sh_rest : nullptr, idx, vp.M, dir, cbits); break;
-        }
-    }
-    clamped[idx] = cbits;
-
-    float opacity = RAW ? act_opacity(opacities[idx]) : opacities[idx];
-    if constexpr (AA) opacity = opacity * pj.coef;
-    qmax = cull_qmax(opacity);
-    float4* dst = reinterpret_cast<float4*>(rec + idx);
-    dst[0] = make_float4(pj.pix, pj.piy, pj.con_a, pj.con_b);
-    dst[1] = make_float4(pj.con_c, opacity, rgb.x, rgb.y);
-    dst[2] = make_float4(rgb.z, pj.vz, qmax, 0.f);
-}
 
 // 5 workgroups per CU (29.7 KB of LDS each; 80 VGPRs, no scratch); the split SH loader of raw mode needs 126 registers
 // AA: one more parked plane (the coefficient of phase 2 for phase 3a), 31.7 KB: five workgroups still fit the CU's 160 KB
@@ -494,7 +258,7 @@ k_preprocess_pool(ViewParams vp, const float* __restrict__ means3D, const float*
                   const float* __restrict__ colors_precomp, int prefiltered,
                   int* __restrict__ radii, GaussRec* __restrict__ rec, uint8_t* __restrict__ clamped,
                   uint32_t* __restrict__ tiles_touched, uint4* __restrict__ hitrec, GeomHeader* hdr,
-                  uint32_t binning_capacity, uint32_t* __restrict__ chunk_sums)
+                  uint32_t* __restrict__ chunk_sums)
 {
     __shared__ uint16_t s_near[PL_POOL];                     // pool-local ids of the near-plane passers, index order
     __shared__ int s_radius[PL_POOL];                        // results of the whole pool (0 for everything culled)
@@ -578,7 +342,7 @@ k_preprocess_pool(ViewParams vp, const float* __restrict__ means3D, const float*
     // observable depends on it -- every output is per Gaussian, the chunk sums are integer sums)
     for (uint32_t i0 = 0; i0 < n_near; i0 += PL_THREADS) {
         const uint32_t i = i0 + (uint32_t)tid;
-        Projected pj;
+        GaussProj pj;
         bool ok = false;
         uint32_t loc = 0;
         if (i < n_near) {
@@ -606,15 +370,19 @@ k_preprocess_pool(ViewParams vp, const float* __restrict__ means3D, const float*
         const uint32_t i = i0 + (uint32_t)tid;
         uint32_t tests = 0;
         if (i < n_mid) {
-            Projected pj;
+            GaussProj pj;
             pj.pix = s_mid[0][i]; pj.piy = s_mid[1][i]; pj.con_a = s_mid[2][i]; pj.con_b = s_mid[3][i];
             pj.con_c = s_mid[4][i]; pj.vz = s_mid[5][i];
             if constexpr (AA) pj.coef = s_coef[i];
             const uint32_t loc = s_mid_id[i];
             pj.radius = s_radius[loc];
-            int minx, miny, width; uint32_t area; float qmax;
-            colour_and_record<RAW, AA>(vp, base + (int)loc, pj, means3D, opacities, shs, colors_precomp, rec, clamped,
-                                   minx, miny, width, area, qmax);
+            int minx, miny, maxx, maxy;
+            tile_rect(pj.pix, pj.piy, pj.radius, vp.gx, vp.gy, minx, miny, maxx, maxy);
+            const size_t li = (size_t)(base + (int)loc);
+            const float qmax = colour_and_record<RAW, AA>(vp, base + (int)loc, pj, means3D[3 * li], means3D[3 * li + 1], means3D[3 * li + 2],
+                                                          opacities, shs, colors_precomp, rec, clamped);
+            const int width = maxx - minx;
+            const uint32_t area = (uint32_t)(maxx - minx) * (uint32_t)(maxy - miny);
             my_ref += area;
             // rectangles of more than CULL_MAX_TILES tiles are emitted unculled (common.h): nothing to test
             if (area > CULL_MAX_TILES) s_tiles[loc] = area; else tests = area;
@@ -712,12 +480,19 @@ k_mark_visible(int P, const float* __restrict__ means3D, const float* __restrict
 
 }  // namespace
 
+// f(RAW, AA) with the two switches as compile-time constants (std::bool_constant)
+template <class F>
+static void dispatch_raw_aa(bool raw, bool aa, F&& f)
+{
+    if (raw) { if (aa) f(std::true_type{}, std::true_type{}); else f(std::true_type{}, std::false_type{}); }
+    else     { if (aa) f(std::false_type{}, std::true_type{}); else f(std::false_type{}, std::false_type{}); }
+}
+
 void launch_preprocess(const ViewParams& vp, const float* means3D, const float* scales, const float* rotations,
                        const float* opacities, const float* shs, const float* cov3D_precomp,
                        const float* colors_precomp, bool prefiltered, int* radii, GaussRec* rec,
-                       uint8_t* clamped, uint32_t* tiles_touched, uint4* hitrec, uint32_t* depth_key,
-                       GeomHeader* hdr, uint32_t binning_capacity, uint32_t* chunk_sums, bool sparse_view_hint, hipStream_t s,
-                       bool antialiasing)
+                       uint8_t* clamped, uint32_t* tiles_touched, uint4* hitrec, GeomHeader* hdr,
+                       uint32_t* chunk_sums, bool sparse_view_hint, hipStream_t s, bool antialiasing)
 {
     static_assert(SCAN_TILE % PP_THREADS == 0, "a preprocess workgroup must lie inside one compaction chunk");
     static_assert(SCAN_TILE % PL_POOL == 0, "a preprocess pool must lie inside one compaction chunk");
@@ -726,33 +501,15 @@ void launch_preprocess(const ViewParams& vp, const float* means3D, const float* 
     // header); `sparse_view_hint` is what the caller knows from earlier views of this scene (api.hip view_hint: visible
     // fraction of the last forward whose counts reached the host).  lr_tune_set("preprocess", 0 / 1) forces one (A/B runs).
     const int forced = tune_get(TUNE_PREPROCESS);
-    const bool pooled = forced >= 0 ? forced != 0 : (sparse_view_hint && vp.P >= 400000);
-    const int variant = (vp.raw ? 1 : 0) | (antialiasing ? 2 : 0);
-    if (pooled && depth_key == nullptr && vp.gx <= 65535 && vp.gy <= 65535) {
-        dim3 grid((vp.P + PL_POOL - 1) / PL_POOL), block(PL_THREADS);
-#define LR_PP_POOL(RAW_, AA_) hipLaunchKernelGGL((k_preprocess_pool<RAW_, AA_>), grid, block, 0, s, vp, means3D, scales, rotations, \
-                               opacities, shs, cov3D_precomp, colors_precomp, prefiltered ? 1 : 0, radii, rec, clamped,            \
-                               tiles_touched, hitrec, hdr, binning_capacity, chunk_sums)
-        switch (variant) {
-            case 0: LR_PP_POOL(false, false); break;
-            case 1: LR_PP_POOL(true, false); break;
-            case 2: LR_PP_POOL(false, true); break;
-            default: LR_PP_POOL(true, true); break;
-        }
-#undef LR_PP_POOL
-        return;
-    }
-    dim3 grid((vp.P + PP_THREADS - 1) / PP_THREADS), block(PP_THREADS);
-#define LR_PP(RAW_, AA_) hipLaunchKernelGGL((k_preprocess<RAW_, AA_>), grid, block, 0, s, vp, means3D, scales, rotations, opacities, \
-                           shs, cov3D_precomp, colors_precomp, prefiltered ? 1 : 0, radii, rec, clamped, tiles_touched, hitrec,    \
-                           depth_key, hdr, binning_capacity, chunk_sums)
-    switch (variant) {
-        case 0: LR_PP(false, false); break;
-        case 1: LR_PP(true, false); break;
-        case 2: LR_PP(false, true); break;
-        default: LR_PP(true, true); break;
-    }
-#undef LR_PP
+    const bool pooled = (forced >= 0 ? forced != 0 : (sparse_view_hint && vp.P >= 400000)) && vp.gx <= 65535 && vp.gy <= 65535;
+    dispatch_raw_aa(vp.raw != 0, antialiasing, [&](auto raw, auto aa) {
+        constexpr bool RAW = decltype(raw)::value, AA = decltype(aa)::value;
+#define LR_PP_ARGS 0, s, vp, means3D, scales, rotations, opacities, shs, cov3D_precomp, colors_precomp, prefiltered ? 1 : 0, radii, \
+                   rec, clamped, tiles_touched, hitrec, hdr, chunk_sums
+        if (pooled) hipLaunchKernelGGL((k_preprocess_pool<RAW, AA>), dim3((vp.P + PL_POOL - 1) / PL_POOL), dim3(PL_THREADS), LR_PP_ARGS);
+        else hipLaunchKernelGGL((k_preprocess<RAW, AA>), dim3((vp.P + PP_THREADS - 1) / PP_THREADS), dim3(PP_THREADS), LR_PP_ARGS);
+#undef LR_PP_ARGS
+    });
 }
 
 void launch_mark_visible(int P, const float* means3D, const float* view, const float* proj, uint8_t* present,

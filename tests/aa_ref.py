@@ -83,7 +83,7 @@ def cov2d32(means3D, viewmatrix, tanfovx, tanfovy, W, H, scales=None, rotations=
 
 
 def coef_from_cov32(a0, b, c0):
-    """det0, det, rho, coef in the order of common.h aa_coef (det as preprocess forms it from the dilated entries)."""
+    """det0, det, rho, coef in the order of csrc/gauss_project.h aa_coef (det as preprocess forms it from the dilated entries)."""
     h = _f(H_DILATION)
     with np.errstate(all="ignore"):
         a, c = a0 + h, c0 + h

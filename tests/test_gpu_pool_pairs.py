@@ -194,9 +194,9 @@ def test_rectangle_areas_around_the_mask_and_culling_limits(hip_device):
         assert (geo[i, :2] != 0).all() == (n <= 64)             # a mask up to 64 tiles, none beyond
 
 
-def test_conics_that_are_no_ellipse(hip_device):
-    """Precomputed 3D covariances, some of them indefinite: the screen-space covariance then has a negative determinant, the
-    conic a non-positive diagonal, and the tile test keeps every tile of the rectangle ("not a proper ellipse")."""
+def no_ellipse_scene():
+    """(cam, cloud) with precomputed 3D covariances, a third of them indefinite (tests/test_gauss_project_cpu.py runs the
+    same rows through the host build of the projection chain)."""
     W = H = 256
     cam = cameras.identity_camera(W, H)
     rng = np.random.default_rng(13)
@@ -213,6 +213,14 @@ def test_conics_that_are_no_ellipse(hip_device):
     opac = rng.uniform(0.02, 1.0, (P, 1)).astype(np.float32)
     cloud = dict(means3D=torch.from_numpy(_unproject(cam, rng.uniform(4, W - 4, P), rng.uniform(4, H - 4, P), z)),
                  cov3D=torch.from_numpy(cov), opacities=torch.from_numpy(opac), shs=_shs(P, rng))
+    return cam, cloud
+
+
+def test_conics_that_are_no_ellipse(hip_device):
+    """Precomputed 3D covariances, some of them indefinite: the screen-space covariance then has a negative determinant, the
+    conic a non-positive diagonal, and the tile test keeps every tile of the rectangle ("not a proper ellipse")."""
+    cam, cloud = no_ellipse_scene()
+    W = H = 256
     u = _compare(cloud, cam, hip_device)
     rec = u["rec"].view(np.float32)
     improper = (u["radii"] > 0) & ~((rec[:, 2] > 0) & (rec[:, 4] > 0))
