@@ -6,6 +6,7 @@
 #include <stddef.h>
 #include "screen_cull.h"
 #include "gauss_project.h"     // TILE_X / TILE_Y, the projection chain, aa_coef
+#include "../../include/lucid_raster.h"   // lr_view: the scene's input pointers, as the launchers take them
 
 namespace lr {
 
@@ -198,6 +199,42 @@ __host__ __device__ inline BinLayout bin_layout(long long R) {
 }
 inline long long bin_seg_capacity(long long R) { return (R > 0 ? R : 1) / BWD_SEG + 2; }
 
+// ---- typed views of the three buffers (host) -----------------------------------------------------
+// One pointer per layout member, under the member's name; the three functions below are the only place that casts.  The buffers
+// arrive const from the entry points that only read them: the views drop it (they are what the writers take as well).
+struct GeomView { GeomHeader* header; GaussRec* rec; uint8_t* clamped; uint32_t *tiles_touched, *offsets, *vis_list; uint4* hitrec; };
+struct ImgView {
+    float* final_T; uint32_t* n_contrib; uint2* ranges; uint32_t *part_hist, *bin_total, *bin_start, *big_queue, *tile_seg0;
+    float4* c_final;
+};
+struct BinView {
+    char* base;                      // the kernels of the backward resolve the R-dependent offsets themselves (bin_layout on the device)
+    uint32_t* point_list; unsigned long long* words; uint8_t* quad_hits;      // words / quad_hits: the same bytes (bin_layout)
+    uint32_t* inst_gid; GradRec* inst_grad; uint2* seg_list; float4* ckpt; uint32_t* list_gid;
+};
+template <class T> inline T* view_at(const char* base, size_t offset) { return reinterpret_cast<T*>(const_cast<char*>(base) + offset); }
+inline GeomView geom_view(const char* base, int P) {
+    const GeomLayout L = geom_layout(P);
+    return { view_at<GeomHeader>(base, L.header), view_at<GaussRec>(base, L.rec), view_at<uint8_t>(base, L.clamped),
+             view_at<uint32_t>(base, L.tiles_touched), view_at<uint32_t>(base, L.offsets), view_at<uint32_t>(base, L.vis_list),
+             view_at<uint4>(base, L.hitrec) };
+}
+inline ImgView img_view(const char* base, int W, int H) {
+    const ImgLayout L = img_layout(W, H);
+    return { view_at<float>(base, L.final_T), view_at<uint32_t>(base, L.n_contrib), view_at<uint2>(base, L.ranges),
+             view_at<uint32_t>(base, L.part_hist), view_at<uint32_t>(base, L.bin_total), view_at<uint32_t>(base, L.bin_start),
+             view_at<uint32_t>(base, L.big_queue), view_at<uint32_t>(base, L.tile_seg0), view_at<float4>(base, L.c_final) };
+}
+inline BinView bin_view(const char* base, long long R) {
+    const BinLayout L = bin_layout(R);
+    return { view_at<char>(base, 0), view_at<uint32_t>(base, L.point_list), view_at<unsigned long long>(base, L.words),
+             view_at<uint8_t>(base, L.quad_hits), view_at<uint32_t>(base, L.inst_gid), view_at<GradRec>(base, L.inst_grad),
+             view_at<uint2>(base, L.seg_list), view_at<float4>(base, L.ckpt), view_at<uint32_t>(base, L.list_gid) };
+}
+// The backward's view of a binning buffer whose R the host does not know: the tile-sorted list always sits at offset 0, whatever
+// R / capacity the forward used, so nothing has to be read back; every other member stays NULL on the host.
+inline BinView bin_view_list(const char* base) { BinView b = {}; b.base = view_at<char>(base, 0); b.point_list = view_at<uint32_t>(base, 0); return b; }
+
 // ---- exact tile culling ------------------------------------------------------------------------
 // A (Gaussian, tile) pair can only matter if some pixel of the tile reaches alpha >= 1/255, i.e. if
 // q(d) = 0.5*(a dx^2 + c dy^2) + b dx dy <= log(255*opacity) somewhere on the tile's 16x16 pixel centres.
@@ -359,11 +396,12 @@ __device__ __forceinline__ float act_quat_inv_norm(float r, float x, float y, fl
     return 1.0f / fmaxf(sqrtf(r * r + x * x + y * y + z * z), 1e-12f);
 }
 
-void launch_preprocess(const ViewParams& vp, const float* means3D, const float* scales, const float* rotations,
-                       const float* opacities, const float* shs, const float* cov3D_precomp,
-                       const float* colors_precomp, bool prefiltered, int* radii, GaussRec* rec,
-                       uint8_t* clamped, uint32_t* tiles_touched, uint4* hitrec, GeomHeader* hdr,
-                       uint32_t* chunk_sums, bool sparse_view_hint, hipStream_t s, bool antialiasing = false);
+// a run of device words a kernel zeroes on the way (launch_compact, launch_tile_binning)
+struct WordSpan { uint32_t* words; uint32_t n; };
+// v: the scene's input pointers (means3D, scales, rotations, opacities, shs, cov3D_precomp, colors_precomp); g: rec, clamped,
+// tiles_touched, hitrec and the header are written
+void launch_preprocess(const ViewParams& vp, const lr_view& v, bool prefiltered, int* radii, const GeomView& g,
+                       uint32_t* chunk_sums, bool sparse_view_hint, bool antialiasing, hipStream_t s);
 // antialiasing: the <RAW, AA = true> kernels, which store opacity * aa_coef(...).coef (and its cull threshold) in the record
 // chunk_sums: [ceil(P / SCAN_TILE)] x {emitting Gaussians, instances, rectangle areas, -} + one word (the prefilter trap), ZERO on
 // entry -- the library's own per-stream scratch (api.hip StreamScratch), cleared again by the first binning kernel once
@@ -386,18 +424,17 @@ void radix_sort_pairs(uint32_t* key_a, uint32_t* key_b, uint32_t* val_a, uint32_
 // block_sums: per SCAN_TILE chunk {emitting Gaussians, instances, rectangle areas, -}, accumulated by k_preprocess.
 // capacity: the binning capacity of the call (0 = exact mode); log_slot: 12 host-visible words of the library's forward log or
 // nullptr -- the kernel leaves the header there behind `log_tag` (lr_header_poll on a log ticket spins on the tag).
-void launch_compact(int P, const uint32_t* tiles_touched, const uint4* block_sums,
-                    uint32_t* vis_list, uint32_t* offsets, GeomHeader* hdr, uint32_t capacity, uint32_t* log_slot,
-                    uint32_t log_tag, uint32_t* zero_words, uint32_t n_zero, bool reset_sticky, hipStream_t s);
+// g: tiles_touched is read; vis_list, offsets and the header are written.  zero: words the scan clears on the way.
+void launch_compact(int P, const GeomView& g, const uint4* block_sums, uint32_t capacity, uint32_t* log_slot, uint32_t log_tag,
+                    WordSpan zero, bool reset_sticky, hipStream_t s);
 // optional per-stage timing hook of launch_tile_binning (api.hip ProfScope events)
 struct TileBinTimes { virtual void mark(int boundary, hipStream_t s) = 0; virtual ~TileBinTimes() {} };
 // count -> scan -> scatter -> per-bin sort: point_list, inst_gid and ranges from the compacted list.  Returns 0, -1
 // (LDS attribute) or -2 (sub-tile + depth + slot bits exceed 64).
-int launch_tile_binning(int P, int gx, int gy, int slot_bits, const uint32_t* vis_list, const uint32_t* offsets,
-                        const uint4* hitrec, const GaussRec* rec, const int* radii, GeomHeader* hdr,
-                        uint32_t* part_hist, uint32_t* bin_total, uint32_t* bin_start, uint32_t* big_queue,
-                        uint32_t* inst_gid, unsigned long long* words, uint32_t* point_list, uint32_t* list_gid, uint2* ranges,
-                        long long bin_bound_hint, TileBinTimes* t, uint32_t* clear_words, uint32_t n_clear, hipStream_t s);
+// g: vis_list, offsets, hitrec, rec, header; im: part_hist, bin_total, bin_start, big_queue, ranges; b: inst_gid, words,
+// point_list, list_gid.  clear: words the count kernel clears on the way (the per-stream chunk sums).
+int launch_tile_binning(const ViewParams& vp, int slot_bits, const GeomView& g, const ImgView& im, const BinView& b,
+                        const int* radii, long long bin_bound_hint, TileBinTimes* t, WordSpan clear, hipStream_t s);
 
 // Diagnostic tuning knobs (lr_tune_set in api.hip): kernel variants that can be switched at run time so that two of them
 // are measured alternately in ONE process on ONE box (tools/ab_bench.py).  -1 = not set (the launcher's own rule).
@@ -439,27 +476,30 @@ __device__ __forceinline__ int blend_tile(int map, int num_tiles)
     }
     return t < num_tiles ? t : -1;
 }
-void launch_render_fwd(int W, int H, int gx, int gy, const uint2* ranges, const uint32_t* point_list,
-                       const uint32_t* list_gid, const GaussRec* rec, const float* bg, float* final_T,
-                       uint32_t* n_contrib, float* out_color, float* out_depth, uint8_t* quad_hits,
-                       GeomHeader* hdr, uint2* seg_list, float4* ckpt, uint32_t* tile_seg0, float4* c_final,
-                       long long inst_hint, hipStream_t s);
+// g: rec, header; im: ranges, final_T, n_contrib, tile_seg0, c_final; b: point_list, list_gid, quad_hits, seg_list, ckpt (all NULL
+// for a view without Gaussians, whose ranges are empty)
+void launch_render_fwd(const ViewParams& vp, const GeomView& g, const ImgView& im, const BinView& b, const float* bg,
+                       float* out_color, float* out_depth, long long inst_hint, hipStream_t s);
 // out_depth == nullptr: the depth-free kernels (no depth channel in the per-pixel state, no depth image); everything else to the bit
 // alpha [n] = 1 - final_T [n]: the accumulated opacity of the forward that left final_T (lr_render_alpha)
 void launch_render_alpha(const float* final_T, long long n, float* alpha, hipStream_t s);
+// The upstream gradients a view's backward is given.
+struct ViewGrads {
+    const float* color;     // dL_dpix [3,H,W]
+    const float* depth;     // != nullptr: depth mode (lr_view_backward with dL_depths and depth_image) -- the depth-mode kernels differentiate
+                            // the forward's depth image for the upstream gradient dL_ddepth [H*W] as well, and write dL/dz of every
+                            // instance to its slot's free float
+    const float* alpha;     // != nullptr: alpha mode (lr_view_backward with dL_dalpha) -- the gradient of the accumulated opacity
+                            // 1 - final_T [H*W] as well; alone it keeps the default shape and segments, with depth mode it joins the
+                            // depth-mode kernel
+    const float* depth_img; // the forward's depth image [H*W] (depth mode)
+};
 // seg_bound: upper bound of GeomHeader::n_seg known to the host (bin_seg_capacity of the instance bound of the call)
-// dL_ddepth != nullptr: depth mode (lr_view_backward with dL_depths and depth_image) -- the depth-mode kernels differentiate the forward's depth image
-// depth_img [H*W] for the upstream gradient dL_ddepth [H*W] as well, and write dL/dz of every instance to its slot's free float
-// dL_dalpha != nullptr: alpha mode (lr_view_backward with dL_dalpha) -- the gradient of the accumulated opacity 1 - final_T [H*W] as well;
-// alone it keeps the default shape and segments, with depth mode it joins the depth-mode kernel
-void launch_render_bwd(int W, int H, int gx, int gy, const uint2* ranges, const uint32_t* point_list,
-                       const GaussRec* rec, const float* bg, const float* final_T,
-                       const uint32_t* n_contrib, const float* dL_dpix, char* bin_base, const GeomHeader* hdr,
-                       const uint32_t* tile_seg0, const float4* c_final, long long seg_bound, hipStream_t s,
-                       const float* dL_ddepth = nullptr, const float* depth_img = nullptr, const float* dL_dalpha = nullptr,
-                       bool absgrad = false);
 // absgrad: absgrad mode (lr_view_backward with dL_dmean2D_abs) -- the k_render_bwd_abs kernels (2-wave shape, whole lists, with the depth / alpha
 // terms the pointers ask for), which also leave each instance's sums of |per-pixel dL/dmean2D| in its slot's last two floats
+// g: rec, header; im: ranges, final_T, n_contrib, tile_seg0, c_final; b: base, point_list
+void launch_render_bwd(const ViewParams& vp, const GeomView& g, const ImgView& im, const BinView& b, const float* bg,
+                       const ViewGrads& up, bool absgrad, long long seg_bound, hipStream_t s);
 // ---- Adam, element-wise (adam.hip and the step fused into the per-Gaussian backward, gauss_bwd.hip) -----------------------
 // torch's single-tensor Adam (torch/optim/adam.py _single_tensor_adam; no weight decay, amsgrad or maximize) with the roundings
 // of torch's own kernels: lerp = fma(w, b - a, a), addcmul = fma(value * t1, t2, self), addcdiv = fma(value, t1 / t2, self);
@@ -474,26 +514,32 @@ __device__ __forceinline__ void adam_one(float gi, float& mi, float& vi, float& 
     const float denom = sqrtf(vi) / bc2_sqrt + eps;
     pi = __builtin_fmaf(-step_size, mi / denom, pi);
 }
-void launch_gauss_bwd(const ViewParams& vp, const float* means3D, const float* scales, const float* rotations,
-                      const float* shs, const float* cov3D_precomp, const float* colors_precomp,
-                      const uint32_t* vis_list, const uint8_t* clamped, const uint32_t* offsets,
-                      const char* bin_base, const GeomHeader* hdr,
-                      float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor,
-                      float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot,
-                      uint32_t accum_mask, float* acc16, hipStream_t s, bool depth = false, bool antialiasing = false,
-                      float* dL_dmean2D_abs = nullptr, float* stat_accum = nullptr, bool stat_abs = false);
-// stat_accum != nullptr [P] (lr_views_accumulate's stat_grad_accum; activated parameters, dL_dmean2D_abs NULL): the k_gauss_bwd_stats
-// kernels, which also accumulate the norm of the view's own dL/dmean2D -- stat_abs: of its absgrad pair, after the absgrad blend
-// backward -- into float 13 of the acc16 row, or without acc16 into stat_accum itself
-// dL_dmean2D_abs != nullptr [P,3]: the k_gauss_bwd_abs kernels, which also sum the slots' two absgrad floats per Gaussian and
-// WRITE {x, y, 0} to the rows of visible Gaussians (never accumulated; the caller zero-fills the tensor)
+// bit positions of lr_backward's accumulate_mask (LR_ACC_* in lucid_raster.h), and the order of GradOut::row
+enum { ACC_MEAN2D = 0, ACC_CONIC = 1, ACC_OPACITY = 2, ACC_COLOR = 3, ACC_MEAN3D = 4, ACC_COV3D = 5, ACC_SH = 6,
+       ACC_SCALE = 7, ACC_ROT = 8, ACC_ROWS = 9 };
+// Where the per-Gaussian backward leaves its gradients.
+struct GradOut {
+    float* row[ACC_ROWS];       // by ACC_*: dL_dmean2D [P,3], dL_dconic [P,4], dL_dopacity [P], dL_dcolor [P,3], dL_dmean3D [P,3], dL_dcov3D
+                                // [P,6], dL_dsh [P,M,3] (raw mode: the features_dc gradient [P,3]; ViewParams::dL_dsh_rest has the rest),
+                                // dL_dscale [P,3], dL_drot [P,4]; NULL = not asked for
+    float* mean2D_abs;          // != nullptr [P,3]: the k_gauss_bwd_abs kernels, which also sum the slots' two absgrad floats per Gaussian
+                                // and WRITE {x, y, 0} to the rows of visible Gaussians (never accumulated; the caller zero-fills the tensor)
+    uint32_t accumulate_mask;   // bit ACC_* set: the row is added to, not written (LR_ACC_*)
+    float* acc16;               // [P][16]: per-step interleaved accumulator of the five small gradient rows (gauss_bwd.hip); added to
+                                // the caller's tensors once per step
+    float* stat_accum;          // != nullptr [P] (lr_views_accumulate's stat_grad_accum; activated parameters, mean2D_abs NULL): the
+                                // k_gauss_bwd_stats kernels, which also accumulate the norm of the view's own dL/dmean2D into float 13 of
+                                // the acc16 row, or without acc16 into stat_accum itself
+    bool stat_abs;              // ... of its absgrad pair, after the absgrad blend backward
+};
 // antialiasing: the view's forward ran under lr_set_antialiasing(1) -- the <RAW, AA = true> kernels chain the record's opacity
 // gradient through aa_coef to the opacity and to the 2D covariance (the non-raw ones read the record's opacity from the geom
-// buffer, which starts at `hdr`)
+// buffer, which starts at the header)
 // depth: the depth-mode kernel (k_gauss_bwd_depth), which adds each Gaussian's summed dL/dz (GradRec::pad0, written by the
 // depth-mode blend backward) to dL/dmean3D through z = view[2] x + view[6] y + view[10] z + view[14]
-// acc16 [P][16]: per-step interleaved accumulator of the five small gradient rows (gauss_bwd.hip); added to the caller's
-// tensors once per step
+// v: the scene's input pointers; g: vis_list, clamped, offsets, header; b: base
+void launch_gauss_bwd(const ViewParams& vp, const lr_view& v, const GeomView& g, const BinView& b, const GradOut& out,
+                      bool depth, bool antialiasing, hipStream_t s);
 // stat_accum != nullptr [P]: float 13 of the rows (the step's sum of per-view gradient norms) is added to it as well
 void launch_uninterleave_add(int P, const float* acc16, float* mean2D, float* opacity, float* mean3D, float* scale, float* rot,
                              hipStream_t s, float* stat_accum = nullptr);
@@ -596,9 +642,6 @@ void launch_alpha_hole_forward(int H, int W, const float* src, bool from_T, floa
                                char* ws, LossValue value, hipStream_t s);
 void launch_alpha_hole_backward(int H, int W, const float* mask, float weight, const float* upstream, const char* ws, float* grad,
                                 LossValue value, hipStream_t s);
-// bit positions of lr_backward's accumulate_mask (LR_ACC_* in lucid_raster.h)
-enum { ACC_MEAN2D = 0, ACC_CONIC = 1, ACC_OPACITY = 2, ACC_COLOR = 3, ACC_MEAN3D = 4, ACC_COV3D = 5, ACC_SH = 6,
-       ACC_SCALE = 7, ACC_ROT = 8 };
 void launch_zero_outputs(float* const* ptrs, const unsigned long long* nfloats, int count, hipStream_t s);
 
 // video frames on the device (video.hip)

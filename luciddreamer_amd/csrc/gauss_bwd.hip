@@ -13,6 +13,7 @@
 //                touched at all -- this fuses autograd's `grad += new_grad` pass (another 3 x 236 B per
 //                Gaussian per view of HBM traffic) into the kernel when several views are accumulated.
 #include "common.h"
+#include "dispatch_flags.h"
 #include <algorithm>
 
 namespace lr {
@@ -447,68 +448,26 @@ void launch_zero_outputs(float* const* ptrs, const unsigned long long* nfloats, 
     hipLaunchKernelGGL(k_zero_segments, dim3((unsigned)blocks), dim3(256), 0, s, z);
 }
 
-void launch_gauss_bwd(const ViewParams& vp, const float* means3D, const float* scales, const float* rotations,
-                      const float* shs, const float* cov3D_precomp, const float* colors_precomp,
-                      const uint32_t* vis_list, const uint8_t* clamped, const uint32_t* offsets,
-                      const char* bin_base, const GeomHeader* hdr,
-                      float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor,
-                      float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot,
-                      uint32_t accum_mask, float* acc16, hipStream_t s, bool depth, bool antialiasing, float* dL_dmean2D_abs,
-                      float* stat_accum, bool stat_abs)
+void launch_gauss_bwd(const ViewParams& vp, const lr_view& v, const GeomView& g, const BinView& b, const GradOut& out, bool depth,
+                      bool antialiasing, hipStream_t s)
 {
-    (void)colors_precomp;
     if (vp.P <= 0) return;
-    const int groups = std::min((vp.P + GB_THREADS - 1) / GB_THREADS, GB_MAX_GROUPS);
-    if (stat_accum != nullptr) {
-#define LR_GBS(AA_, DEPTH_, ABSG_) hipLaunchKernelGGL((k_gauss_bwd_stats<AA_, DEPTH_, ABSG_>), dim3(groups), dim3(GB_THREADS), 0, s, vp, \
-                               means3D, scales, rotations, shs, cov3D_precomp, vis_list, clamped, offsets, bin_base, hdr, dL_dmean2D,  \
-                               dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, accum_mask, acc16, \
-                               stat_accum)
-        switch ((antialiasing ? 1 : 0) | (depth ? 2 : 0) | (stat_abs ? 4 : 0)) {
-            case 0: LR_GBS(false, false, false); break;
-            case 1: LR_GBS(true, false, false); break;
-            case 2: LR_GBS(false, true, false); break;
-            case 3: LR_GBS(true, true, false); break;
-            case 4: LR_GBS(false, false, true); break;
-            case 5: LR_GBS(true, false, true); break;
-            case 6: LR_GBS(false, true, true); break;
-            default: LR_GBS(true, true, true); break;
-        }
-#undef LR_GBS
-        return;
-    }
-    if (dL_dmean2D_abs != nullptr) {
-#define LR_GBA(RAW_, AA_, DEPTH_) hipLaunchKernelGGL((k_gauss_bwd_abs<RAW_, AA_, DEPTH_>), dim3(groups), dim3(GB_THREADS), 0, s, vp,   \
-                               means3D, scales, rotations, shs, cov3D_precomp, vis_list, clamped, offsets, bin_base, hdr, dL_dmean2D,  \
-                               dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, accum_mask, acc16, \
-                               dL_dmean2D_abs)
-        switch ((vp.raw ? 1 : 0) | (antialiasing ? 2 : 0) | (depth ? 4 : 0)) {
-            case 0: LR_GBA(false, false, false); break;
-            case 1: LR_GBA(true, false, false); break;
-            case 2: LR_GBA(false, true, false); break;
-            case 3: LR_GBA(true, true, false); break;
-            case 4: LR_GBA(false, false, true); break;
-            case 5: LR_GBA(true, false, true); break;
-            case 6: LR_GBA(false, true, true); break;
-            default: LR_GBA(true, true, true); break;
-        }
-#undef LR_GBA
-        return;
-    }
-#define LR_GB(KERNEL_, RAW_, AA_) hipLaunchKernelGGL((KERNEL_<RAW_, AA_>), dim3(groups), dim3(GB_THREADS), 0, s, vp, means3D, scales,  \
-                               rotations, shs, cov3D_precomp, vis_list, clamped, offsets, bin_base, hdr, dL_dmean2D, dL_dconic,     \
-                               dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, accum_mask, acc16)
-    switch ((vp.raw ? 1 : 0) | (antialiasing ? 2 : 0) | (depth ? 4 : 0)) {
-        case 0: LR_GB(k_gauss_bwd, false, false); break;
-        case 1: LR_GB(k_gauss_bwd, true, false); break;
-        case 2: LR_GB(k_gauss_bwd, false, true); break;
-        case 3: LR_GB(k_gauss_bwd, true, true); break;
-        case 4: LR_GB(k_gauss_bwd_depth, false, false); break;
-        case 5: LR_GB(k_gauss_bwd_depth, true, false); break;
-        case 6: LR_GB(k_gauss_bwd_depth, false, true); break;
-        default: LR_GB(k_gauss_bwd_depth, true, true); break;
-    }
-#undef LR_GB
+    const dim3 grid(std::min((vp.P + GB_THREADS - 1) / GB_THREADS, GB_MAX_GROUPS)), block(GB_THREADS);
+    float* const* r = out.row;
+#define LR_GB_ARGS 0, s, vp, v.means3D, v.scales, v.rotations, v.shs, v.cov3D_precomp, g.vis_list, g.clamped, g.offsets, b.base,    \
+                   g.header, r[ACC_MEAN2D], r[ACC_CONIC], r[ACC_OPACITY], r[ACC_COLOR], r[ACC_MEAN3D], r[ACC_COV3D], r[ACC_SH],     \
+                   r[ACC_SCALE], r[ACC_ROT], out.accumulate_mask, out.acc16
+    if (out.stat_accum != nullptr)
+        dispatch_flags<3>(flag_bits(antialiasing, depth, out.stat_abs), [&](auto aa, auto dp, auto absg) {
+            hipLaunchKernelGGL((k_gauss_bwd_stats<aa.value, dp.value, absg.value>), grid, block, LR_GB_ARGS, out.stat_accum); });
+    else if (out.mean2D_abs != nullptr)
+        dispatch_flags<3>(flag_bits(vp.raw != 0, antialiasing, depth), [&](auto raw, auto aa, auto dp) {
+            hipLaunchKernelGGL((k_gauss_bwd_abs<raw.value, aa.value, dp.value>), grid, block, LR_GB_ARGS, out.mean2D_abs); });
+    else
+        dispatch_flags<3>(flag_bits(vp.raw != 0, antialiasing, depth), [&](auto raw, auto aa, auto dp) {
+            if constexpr (dp.value) hipLaunchKernelGGL((k_gauss_bwd_depth<raw.value, aa.value>), grid, block, LR_GB_ARGS);
+            else hipLaunchKernelGGL((k_gauss_bwd<raw.value, aa.value>), grid, block, LR_GB_ARGS); });
+#undef LR_GB_ARGS
 }
 
 namespace {

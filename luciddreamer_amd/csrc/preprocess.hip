@@ -14,8 +14,8 @@
 // missing FMAs cost nothing.  The arithmetic is gauss_project.h, one text for both kernels and for a host build
 // (tests/test_gauss_project_cpu.py pins it to the oracle without a GPU); here: loads, raw-mode activations, record, work split.
 #include <cstddef>
-#include <type_traits>
 #include "common.h"
+#include "dispatch_flags.h"
 
 namespace lr {
 
@@ -480,19 +480,8 @@ k_mark_visible(int P, const float* __restrict__ means3D, const float* __restrict
 
 }  // namespace
 
-// f(RAW, AA) with the two switches as compile-time constants (std::bool_constant)
-template <class F>
-static void dispatch_raw_aa(bool raw, bool aa, F&& f)
-{
-    if (raw) { if (aa) f(std::true_type{}, std::true_type{}); else f(std::true_type{}, std::false_type{}); }
-    else     { if (aa) f(std::false_type{}, std::true_type{}); else f(std::false_type{}, std::false_type{}); }
-}
-
-void launch_preprocess(const ViewParams& vp, const float* means3D, const float* scales, const float* rotations,
-                       const float* opacities, const float* shs, const float* cov3D_precomp,
-                       const float* colors_precomp, bool prefiltered, int* radii, GaussRec* rec,
-                       uint8_t* clamped, uint32_t* tiles_touched, uint4* hitrec, GeomHeader* hdr,
-                       uint32_t* chunk_sums, bool sparse_view_hint, hipStream_t s, bool antialiasing)
+void launch_preprocess(const ViewParams& vp, const lr_view& v, bool prefiltered, int* radii, const GeomView& g,
+                       uint32_t* chunk_sums, bool sparse_view_hint, bool antialiasing, hipStream_t s)
 {
     static_assert(SCAN_TILE % PP_THREADS == 0, "a preprocess workgroup must lie inside one compaction chunk");
     static_assert(SCAN_TILE % PL_POOL == 0, "a preprocess pool must lie inside one compaction chunk");
@@ -502,12 +491,11 @@ void launch_preprocess(const ViewParams& vp, const float* means3D, const float* 
     // fraction of the last forward whose counts reached the host).  lr_tune_set("preprocess", 0 / 1) forces one (A/B runs).
     const int forced = tune_get(TUNE_PREPROCESS);
     const bool pooled = (forced >= 0 ? forced != 0 : (sparse_view_hint && vp.P >= 400000)) && vp.gx <= 65535 && vp.gy <= 65535;
-    dispatch_raw_aa(vp.raw != 0, antialiasing, [&](auto raw, auto aa) {
-        constexpr bool RAW = decltype(raw)::value, AA = decltype(aa)::value;
-#define LR_PP_ARGS 0, s, vp, means3D, scales, rotations, opacities, shs, cov3D_precomp, colors_precomp, prefiltered ? 1 : 0, radii, \
-                   rec, clamped, tiles_touched, hitrec, hdr, chunk_sums
-        if (pooled) hipLaunchKernelGGL((k_preprocess_pool<RAW, AA>), dim3((vp.P + PL_POOL - 1) / PL_POOL), dim3(PL_THREADS), LR_PP_ARGS);
-        else hipLaunchKernelGGL((k_preprocess<RAW, AA>), dim3((vp.P + PP_THREADS - 1) / PP_THREADS), dim3(PP_THREADS), LR_PP_ARGS);
+    dispatch_flags<2>(flag_bits(vp.raw != 0, antialiasing), [&](auto raw, auto aa) {
+#define LR_PP_ARGS 0, s, vp, v.means3D, v.scales, v.rotations, v.opacities, v.shs, v.cov3D_precomp, v.colors_precomp,              \
+                   prefiltered ? 1 : 0, radii, g.rec, g.clamped, g.tiles_touched, g.hitrec, g.header, chunk_sums
+        if (pooled) hipLaunchKernelGGL((k_preprocess_pool<raw.value, aa.value>), dim3((vp.P + PL_POOL - 1) / PL_POOL), dim3(PL_THREADS), LR_PP_ARGS);
+        else hipLaunchKernelGGL((k_preprocess<raw.value, aa.value>), dim3((vp.P + PP_THREADS - 1) / PP_THREADS), dim3(PP_THREADS), LR_PP_ARGS);
 #undef LR_PP_ARGS
     });
 }

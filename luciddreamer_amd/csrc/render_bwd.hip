@@ -23,6 +23,7 @@
 //                     in a fixed order, by k_gauss_bwd.  No global atomics at all, nothing to pre-zero.
 #include <cstdlib>
 #include "common.h"
+#include "dispatch_flags.h"
 
 namespace lr {
 
@@ -157,7 +158,6 @@ __device__ __forceinline__ uint32_t wave_max_u32(uint32_t v)
     for (int off = 32; off > 0; off >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, off));
     return v;
 }
-template <bool B> struct BoolTag { static constexpr bool value = B; };
 
 // s_acc column of each term: 0 sum D dx, 1 sum D dy, 2 sum D dx^2, 3 sum D dx dy, 4 sum D dy^2, 5 sum D (= dop), 6 dr, 7 dg,
 // 8-11 db (one column per 16-lane row); the flush turns columns 0-4 into GradRec's dmx, dmy, dca, dcb, dcc (same float order)
@@ -512,7 +512,7 @@ __device__ __forceinline__ void render_bwd_item(const int tile, const int seg, c
                 }
             }
             };
-            if (any_stopped) walk(BoolTag<true>{}); else walk(BoolTag<false>{});
+            if (any_stopped) walk(std::true_type{}); else walk(std::false_type{});
         }
         lds_barrier();
         if (tid < cnt) {
@@ -987,13 +987,10 @@ void note_fwd_shape(int shape) { g_last_fwd_shape = shape; }
 int last_fwd_shape() { return g_last_fwd_shape; }
 int last_bwd_shape() { return g_last_bwd_shape; }
 
-void launch_render_bwd(int W, int H, int gx, int gy, const uint2* ranges, const uint32_t* point_list,
-                       const GaussRec* rec, const float* bg, const float* final_T,
-                       const uint32_t* n_contrib, const float* dL_dpix, char* bin_base, const GeomHeader* hdr,
-                       const uint32_t* tile_seg0, const float4* c_final, long long seg_bound, hipStream_t s,
-                       const float* dL_ddepth, const float* depth_img, const float* dL_dalpha, bool absgrad)
+void launch_render_bwd(const ViewParams& vp, const GeomView& g, const ImgView& im, const BinView& b, const float* bg,
+                       const ViewGrads& up, bool absgrad, long long seg_bound, hipStream_t s)
 {
-    const int num_tiles = gx * gy;
+    const int gx = vp.gx, num_tiles = vp.gx * vp.gy;
     if (num_tiles <= 0) return;
     const int tile_map = blend_tile_map(num_tiles);
     const int grid = ((num_tiles + 7) / 8) * 8;
@@ -1010,42 +1007,20 @@ void launch_render_bwd(int W, int H, int gx, int gy, const uint2* ranges, const 
 #else
     constexpr int pad = 0;
 #endif
-#define LR_BWD_ARGS W, H, gx, num_tiles, tile_map, ranges, point_list, rec, bg, final_T, n_contrib, dL_dpix, bin_base, hdr, force_check
-    // instances the caller's bound allows (bin_seg_capacity(bound) = bound / BWD_SEG + 2): an upper estimate of the lists' lengths
-    const bool strict = tune_get(TUNE_STRICT) > 0;
-    if (absgrad) {
-        // absgrad mode: as depth mode ONE shape at every image size, one workgroup per tile over its whole list (seg_on = 0)
+#define LR_BWD_ARGS vp.W, vp.H, gx, num_tiles, tile_map, im.ranges, b.point_list, g.rec, bg, im.final_T, im.n_contrib, up.color, b.base, \
+                    g.header, force_check
+    const bool strict = tune_get(TUNE_STRICT) > 0, depth = up.depth != nullptr, alpha = up.alpha != nullptr;
+    if (absgrad || depth) {
+        // absgrad mode and depth mode: ONE shape at every image size (the 2-wave one), one workgroup per tile over its whole list --
+        // correct for any launch size, no listed segments (seg_on = 0); the shape rule and the segment switch do not apply
         g_last_bwd_shape = BLEND_HALF;
-#define LR_ABS(S_, D_, A_) hipLaunchKernelGGL((k_render_bwd_abs<S_, D_, A_>), dim3(grid), dim3(128), 0, s, LR_BWD_ARGS, tile_seg0,   \
-                                              c_final, grid, 0, dL_ddepth, depth_img, dL_dalpha)
-        switch ((strict ? 1 : 0) | (dL_ddepth != nullptr ? 2 : 0) | (dL_dalpha != nullptr ? 4 : 0)) {
-            case 0: LR_ABS(false, false, false); break;
-            case 1: LR_ABS(true, false, false); break;
-            case 2: LR_ABS(false, true, false); break;
-            case 3: LR_ABS(true, true, false); break;
-            case 4: LR_ABS(false, false, true); break;
-            case 5: LR_ABS(true, false, true); break;
-            case 6: LR_ABS(false, true, true); break;
-            default: LR_ABS(true, true, true); break;
-        }
-#undef LR_ABS
-        return;
-    }
-    if (dL_ddepth != nullptr) {
-        // depth mode: ONE shape at every image size (the 2-wave one), one workgroup per tile over its whole list -- correct for
-        // any launch size, no listed segments (seg_on = 0); the shape rule and the segment switch do not apply
-        g_last_bwd_shape = BLEND_HALF;
-        if (dL_dalpha != nullptr) {                 // depth + alpha
-            if (strict) hipLaunchKernelGGL(k_render_bwd_depth_alpha<true>, dim3(grid), dim3(128), 0, s, LR_BWD_ARGS, tile_seg0, c_final,
-                                           grid, 0, dL_ddepth, depth_img, dL_dalpha);
-            else hipLaunchKernelGGL(k_render_bwd_depth_alpha<false>, dim3(grid), dim3(128), 0, s, LR_BWD_ARGS, tile_seg0, c_final,
-                                    grid, 0, dL_ddepth, depth_img, dL_dalpha);
-            return;
-        }
-        if (strict) hipLaunchKernelGGL(k_render_bwd_depth<true>, dim3(grid), dim3(128), 0, s, LR_BWD_ARGS, tile_seg0, c_final, grid, 0,
-                                       dL_ddepth, depth_img);
-        else hipLaunchKernelGGL(k_render_bwd_depth<false>, dim3(grid), dim3(128), 0, s, LR_BWD_ARGS, tile_seg0, c_final, grid, 0,
-                                dL_ddepth, depth_img);
+#define LR_WHOLE_ARGS dim3(grid), dim3(128), 0, s, LR_BWD_ARGS, im.tile_seg0, im.c_final, grid, 0, up.depth, up.depth_img
+        dispatch_flags<3>(flag_bits(strict, depth, alpha), [&](auto st, auto dp, auto al) {
+            if (absgrad) hipLaunchKernelGGL((k_render_bwd_abs<st.value, dp.value, al.value>), LR_WHOLE_ARGS, up.alpha);
+            else if constexpr (dp.value && al.value) hipLaunchKernelGGL(k_render_bwd_depth_alpha<st.value>, LR_WHOLE_ARGS, up.alpha);
+            else if constexpr (dp.value) hipLaunchKernelGGL(k_render_bwd_depth<st.value>, LR_WHOLE_ARGS);
+        });
+#undef LR_WHOLE_ARGS
         return;
     }
     int shape = blend_shape(num_tiles, seg_bound > 2 ? (seg_bound - 2) * (long long)BWD_SEG : -1);
@@ -1060,41 +1035,35 @@ void launch_render_bwd(int W, int H, int gx, int gy, const uint2* ranges, const 
     g_last_bwd_shape = shape;
     const long long cap = shape == BLEND_TILE ? 0x3fffffffll : 262144ll;
     const int extra = seg_on ? (int)(seg_bound < 1 ? 1024 : seg_bound > cap ? cap : seg_bound) : 0;
-    const dim3 g(grid + extra);
-#define LR_SEG_ARGS LR_BWD_ARGS, tile_seg0, c_final, grid, seg_on
-    if (dL_dalpha != nullptr) {
-        // alpha mode: the shape and the segment set the default backward takes for this view (the diagnostics-only variants,
-        // bwd_red 0 / 2 / 3, fall back to the default alpha kernel of the shape)
-        if (shape == BLEND_TILE) {
-            if (strict) hipLaunchKernelGGL(k_render_bwd_tile_alpha<true>, g, dim3(64), 0, s, LR_SEG_ARGS, dL_dalpha);
-            else hipLaunchKernelGGL(k_render_bwd_tile_alpha<false>, g, dim3(64), 0, s, LR_SEG_ARGS, dL_dalpha);
-        } else if (shape == BLEND_QUAD) {
-            if (strict) hipLaunchKernelGGL((k_render_bwd_alpha<true, true>), g, dim3(256), 0, s, LR_SEG_ARGS, dL_dalpha);
-            else hipLaunchKernelGGL((k_render_bwd_alpha<true, false>), g, dim3(256), 0, s, LR_SEG_ARGS, dL_dalpha);
-        } else {
-            if (strict) hipLaunchKernelGGL((k_render_bwd_alpha<false, true>), g, dim3(128), pad, s, LR_SEG_ARGS, dL_dalpha);
-            else hipLaunchKernelGGL((k_render_bwd_alpha<false, false>), g, dim3(128), pad, s, LR_SEG_ARGS, dL_dalpha);
+    const dim3 gd(grid + extra);
+#define LR_SEG_ARGS LR_BWD_ARGS, im.tile_seg0, im.c_final, grid, seg_on
+    dispatch_flags<2>(flag_bits(strict, alpha), [&](auto st, auto al) {
+        if constexpr (al.value) {
+            // alpha mode: the shape and the segment set the default backward takes for this view (the diagnostics-only variants,
+            // bwd_red 0 / 2 / 3, fall back to the default alpha kernel of the shape)
+            if (shape == BLEND_TILE) hipLaunchKernelGGL(k_render_bwd_tile_alpha<st.value>, gd, dim3(64), 0, s, LR_SEG_ARGS, up.alpha);
+            else if (shape == BLEND_QUAD) hipLaunchKernelGGL((k_render_bwd_alpha<true, st.value>), gd, dim3(256), 0, s, LR_SEG_ARGS, up.alpha);
+            else hipLaunchKernelGGL((k_render_bwd_alpha<false, st.value>), gd, dim3(128), pad, s, LR_SEG_ARGS, up.alpha);
+            return;
         }
-    } else if (shape == BLEND_TILE) {
-        if (strict) hipLaunchKernelGGL(k_render_bwd_tile<true>, g, dim3(64), 0, s, LR_SEG_ARGS);
 #ifdef LR_DIAGNOSTICS
-        else if (red == 2) hipLaunchKernelGGL(k_render_bwd_tile_swap, g, dim3(64), 0, s, LR_SEG_ARGS);
-        else if (red == 3) hipLaunchKernelGGL(k_render_bwd_tile7, g, dim3(64), 0, s, LR_SEG_ARGS);
+        if constexpr (!st.value) {
+            if (shape == BLEND_TILE && (red == 2 || red == 3)) {
+                if (red == 2) hipLaunchKernelGGL(k_render_bwd_tile_swap, gd, dim3(64), 0, s, LR_SEG_ARGS);
+                else hipLaunchKernelGGL(k_render_bwd_tile7, gd, dim3(64), 0, s, LR_SEG_ARGS);
+                return;
+            }
+            if (shape != BLEND_TILE && !merge) {    // the round-2 reduction (three row sums, three LDS float atomics into a shared copy)
+                if (shape == BLEND_QUAD) hipLaunchKernelGGL((k_render_bwd<true, false>), gd, dim3(256), 0, s, LR_SEG_ARGS);
+                else hipLaunchKernelGGL((k_render_bwd<false, false>), gd, dim3(128), pad, s, LR_SEG_ARGS);
+                return;
+            }
+        }
 #endif
-        else hipLaunchKernelGGL(k_render_bwd_tile<false>, g, dim3(64), 0, s, LR_SEG_ARGS);
-    } else if (strict) {
-        if (shape == BLEND_QUAD) hipLaunchKernelGGL((k_render_bwd<true, true, true>), g, dim3(256), 0, s, LR_SEG_ARGS);
-        else hipLaunchKernelGGL((k_render_bwd<false, true, true>), g, dim3(128), pad, s, LR_SEG_ARGS);
-#ifdef LR_DIAGNOSTICS
-    } else if (!merge) {                    // the round-2 reduction (three row sums, three LDS float atomics into a shared copy)
-        if (shape == BLEND_QUAD) hipLaunchKernelGGL((k_render_bwd<true, false>), g, dim3(256), 0, s, LR_SEG_ARGS);
-        else hipLaunchKernelGGL((k_render_bwd<false, false>), g, dim3(128), pad, s, LR_SEG_ARGS);
-#endif
-    } else if (shape == BLEND_QUAD) {
-        hipLaunchKernelGGL((k_render_bwd<true, true>), g, dim3(256), 0, s, LR_SEG_ARGS);
-    } else {
-        hipLaunchKernelGGL((k_render_bwd<false, true>), g, dim3(128), pad, s, LR_SEG_ARGS);
-    }
+        if (shape == BLEND_TILE) hipLaunchKernelGGL(k_render_bwd_tile<st.value>, gd, dim3(64), 0, s, LR_SEG_ARGS);
+        else if (shape == BLEND_QUAD) hipLaunchKernelGGL((k_render_bwd<true, true, st.value>), gd, dim3(256), 0, s, LR_SEG_ARGS);
+        else hipLaunchKernelGGL((k_render_bwd<false, true, st.value>), gd, dim3(128), pad, s, LR_SEG_ARGS);
+    });
 #undef LR_SEG_ARGS
 #undef LR_BWD_ARGS
 }

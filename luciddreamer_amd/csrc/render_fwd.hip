@@ -27,6 +27,7 @@
 //   * tiles are assigned to workgroups so that each XCD (its own 4 MiB L2) renders a contiguous
 //     band of the image and re-uses the GaussRecs of Gaussians that straddle neighbouring tiles.
 #include "common.h"
+#include "dispatch_flags.h"
 
 namespace lr {
 
@@ -432,12 +433,10 @@ k_render_fwd_tile(LR_FWD_TILE_PARAMS)
 
 }  // namespace
 
-void launch_render_fwd(int W, int H, int gx, int gy, const uint2* ranges, const uint32_t* point_list,
-                       const uint32_t* list_gid, const GaussRec* rec, const float* bg, float* final_T,
-                       uint32_t* n_contrib, float* out_color, float* out_depth, uint8_t* quad_hits,
-                       GeomHeader* hdr, uint2* seg_list, float4* ckpt, uint32_t* tile_seg0, float4* c_final,
-                       long long inst_hint, hipStream_t s)
+void launch_render_fwd(const ViewParams& vp, const GeomView& g, const ImgView& im, const BinView& b, const float* bg,
+                       float* out_color, float* out_depth, long long inst_hint, hipStream_t s)
 {
+    const int gx = vp.gx, gy = vp.gy;
     const int num_tiles = gx * gy;
     if (num_tiles <= 0) return;
     const int tile_map = blend_tile_map(num_tiles);
@@ -463,25 +462,17 @@ void launch_render_fwd(int W, int H, int gx, int gy, const uint2* ranges, const 
 #endif
     const bool strict = tune_get(TUNE_STRICT) > 0;
     note_fwd_shape(tile_shape ? 2 : pair ? 1 : 0);
-#define LR_FWD_ARGS W, H, gx, num_tiles, tile_map, ranges, point_list, list_gid, rec, bg, final_T, n_contrib, out_color, out_depth, \
-                    quad_hits, hdr, seg_list, ckpt, tile_seg0, c_final
+#define LR_FWD_ARGS 0, s, vp.W, vp.H, gx, num_tiles, tile_map, im.ranges, b.point_list, b.list_gid, g.rec, bg, im.final_T, im.n_contrib, \
+                    out_color, out_depth, b.quad_hits, g.header, b.seg_list, b.ckpt, im.tile_seg0, im.c_final
     // out_depth == nullptr: the depth-free instantiations (DEPTH = false never touches the pointer)
-    const bool depth = out_depth != nullptr;
-    if (tile_shape) {
-#define LR_FWD_TILE(S, DP) hipLaunchKernelGGL((k_render_fwd_tile<S, DP>), dim3(grid), dim3(64), 0, s, LR_FWD_ARGS)
-        if (depth) { if (strict) LR_FWD_TILE(true, true); else LR_FWD_TILE(false, true); }
-        else { if (strict) LR_FWD_TILE(true, false); else LR_FWD_TILE(false, false); }
-#undef LR_FWD_TILE
-        return;
-    }
-#define LR_FWD(S, PR) do { if (depth) hipLaunchKernelGGL((k_render_fwd<S, PR, true>), dim3(grid), dim3(THREADS), 0, s, LR_FWD_ARGS); \
-                           else hipLaunchKernelGGL((k_render_fwd<S, PR, false>), dim3(grid), dim3(THREADS), 0, s, LR_FWD_ARGS); } while (0)
+    dispatch_flags<2>(flag_bits(strict, out_depth != nullptr), [&](auto st, auto dp) {
+        if (tile_shape) hipLaunchKernelGGL((k_render_fwd_tile<st.value, dp.value>), dim3(grid), dim3(64), LR_FWD_ARGS);
 #ifdef LR_DIAGNOSTICS
-    if (pair) { if (strict) LR_FWD(true, true); else LR_FWD(false, true); return; }
+        else if (pair) hipLaunchKernelGGL((k_render_fwd<st.value, true, dp.value>), dim3(grid), dim3(THREADS), LR_FWD_ARGS);
 #endif
-    if (strict) LR_FWD(true, false); else LR_FWD(false, false);
+        else hipLaunchKernelGGL((k_render_fwd<st.value, false, dp.value>), dim3(grid), dim3(THREADS), LR_FWD_ARGS);
+    });
 #undef LR_FWD_ARGS
-#undef LR_FWD
 }
 
 // The alpha output (lr_render_alpha): 1 - T_final of every pixel, from the final_T the blend forward left in the image state --

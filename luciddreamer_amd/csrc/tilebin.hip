@@ -795,21 +795,18 @@ PartPlan part_plan(int num_tiles)
     return p;
 }
 
-void launch_compact(int P, const uint32_t* tiles_touched, const uint4* block_sums,
-                    uint32_t* vis_list, uint32_t* offsets, GeomHeader* hdr, uint32_t capacity, uint32_t* log_slot,
-                    uint32_t log_tag, uint32_t* zero_words, uint32_t n_zero, bool reset_sticky, hipStream_t s)
+void launch_compact(int P, const GeomView& g, const uint4* block_sums, uint32_t capacity, uint32_t* log_slot, uint32_t log_tag,
+                    WordSpan zero, bool reset_sticky, hipStream_t s)
 {
     const int nb = (P + SCAN_TILE - 1) / SCAN_TILE;
-    hipLaunchKernelGGL(k_compact_write, dim3(nb), dim3(SCAN_THREADS), 0, s, P, tiles_touched, block_sums, vis_list,
-                       offsets, hdr, capacity, log_slot, log_tag, zero_words, n_zero, reset_sticky ? 1 : 0);
+    hipLaunchKernelGGL(k_compact_write, dim3(nb), dim3(SCAN_THREADS), 0, s, P, g.tiles_touched, block_sums, g.vis_list,
+                       g.offsets, g.header, capacity, log_slot, log_tag, zero.words, zero.n, reset_sticky ? 1 : 0);
 }
 
-int launch_tile_binning(int P, int gx, int gy, int slot_bits, const uint32_t* vis_list, const uint32_t* offsets,
-                        const uint4* hitrec, const GaussRec* rec, const int* radii, GeomHeader* hdr,
-                        uint32_t* part_hist, uint32_t* bin_total, uint32_t* bin_start, uint32_t* big_queue,
-                        uint32_t* inst_gid, unsigned long long* words, uint32_t* point_list, uint32_t* list_gid, uint2* ranges,
-                        long long bin_bound_hint, TileBinTimes* t, uint32_t* clear_words, uint32_t n_clear, hipStream_t s)
+int launch_tile_binning(const ViewParams& vp, int slot_bits, const GeomView& g, const ImgView& im, const BinView& b,
+                        const int* radii, long long bin_bound_hint, TileBinTimes* t, WordSpan clear, hipStream_t s)
 {
+    const int P = vp.P, gx = vp.gx, gy = vp.gy;
     // the partition kernels keep one counter per bin in LDS (up to 64 KB), the large-bin sort up to 128 KB.  The attribute is
     // set once per DEVICE (a process may drive several; runtimes that keep it per device would otherwise refuse the
     // > 64 KB launches on the second one)
@@ -848,20 +845,19 @@ int launch_tile_binning(int P, int gx, int gy, int slot_bits, const uint32_t* vi
     constexpr int reserve = 1;
 #endif
     if (t) t->mark(0, s);
-    hipLaunchKernelGGL(k_part<0>, dim3((unsigned)nb), dim3(PART_THREADS), lds, s, gx, gy, pp.bins, pp.sub_shift, slot_bits,
-                       own_max, vis_list, offsets, hitrec, rec, radii, hdr, part_hist, bin_total, bin_start, ranges, big_queue,
-                       inst_gid, words, clear_words, n_clear, reserve);
+#define LR_PART_ARGS gx, gy, pp.bins, pp.sub_shift, slot_bits, own_max, g.vis_list, g.offsets, g.hitrec, g.rec, radii, g.header,     \
+                     im.part_hist, im.bin_total, im.bin_start, im.ranges, im.big_queue, b.inst_gid, b.words
+    hipLaunchKernelGGL(k_part<0>, dim3((unsigned)nb), dim3(PART_THREADS), lds, s, LR_PART_ARGS, clear.words, clear.n, reserve);
 #ifdef LR_DIAGNOSTICS
     if (!reserve) {
         if (t) t->mark(1, s);
-        hipLaunchKernelGGL(k_part_scan1, dim3((pp.bins + SCAN1_BINS - 1) / SCAN1_BINS), dim3(SCAN1_BINS * SCAN1_GROUPS), 0, s, pp.bins, hdr,
-                           part_hist, bin_total);
+        hipLaunchKernelGGL(k_part_scan1, dim3((pp.bins + SCAN1_BINS - 1) / SCAN1_BINS), dim3(SCAN1_BINS * SCAN1_GROUPS), 0, s, pp.bins,
+                           g.header, im.part_hist, im.bin_total);
     }
 #endif
     if (t) t->mark(2, s);                                   // closes the stage that is open, opens the scatter's
-    hipLaunchKernelGGL(k_part<1>, dim3((unsigned)nb), dim3(PART_THREADS), lds, s, gx, gy, pp.bins, pp.sub_shift, slot_bits,
-                       own_max, vis_list, offsets, hitrec, rec, radii, hdr, part_hist, bin_total, bin_start, ranges, big_queue,
-                       inst_gid, words, nullptr, 0u, reserve);
+    hipLaunchKernelGGL(k_part<1>, dim3((unsigned)nb), dim3(PART_THREADS), lds, s, LR_PART_ARGS, nullptr, 0u, reserve);
+#undef LR_PART_ARGS
     if (t) t->mark(3, s);
     const int groups4 = (pp.bins + 3) / 4;
     const int part_b = pp.bins < TSORT_CLASS_BLOCKS ? pp.bins : TSORT_CLASS_BLOCKS;
@@ -873,7 +869,7 @@ int launch_tile_binning(int P, int gx, int gy, int slot_bits, const uint32_t* vi
     const int bucket_b = (tsort >= 0 && tsort <= 2) ? tsort : 2;
     const int rank_max = tsort < 0 ? TSORT_RANK_DEFAULT : (tsort == 3 ? TSORT_LDS : (tsort == 4 ? 128 : 0));
     hipLaunchKernelGGL(k_tile_sort_small, dim3(groups4 + part_b), dim3(256), 0, s, pp.bins, groups4, pp.sub_shift, slot_bits,
-                       num_tiles, bucket_b, rank_max, bin_start, bin_total, words, point_list, ranges, inst_gid, list_gid);
+                       num_tiles, bucket_b, rank_max, im.bin_start, im.bin_total, b.words, b.point_list, im.ranges, b.inst_gid, b.list_gid);
     // the large bins: LDS for the bucket sort (32 KB of words; three workgroups per CU) unless the AVERAGE bin is already
     // beyond it -- then 128 KB, so that bins of up to 16384 entries are sorted in LDS (a hint for speed only: a bin that
     // does not fit this launch's LDS is sorted in place in global memory).  Capped grid: a sparse view queues nothing
@@ -886,7 +882,8 @@ int launch_tile_binning(int P, int gx, int gy, int slot_bits, const uint32_t* vi
     const int large_cap = huge ? TSORT_BIG_BLOCKS : (avg_bin <= (long long)TSORT_LDS ? TSORT_LARGE_BLOCKS / 12 : TSORT_LARGE_BLOCKS);
     const int large_blocks = pp.bins < large_cap ? pp.bins : large_cap;
     hipLaunchKernelGGL(k_tile_sort_large, dim3(large_blocks), dim3(TSORT_THREADS), (size_t)lds_entries * 8, s, pp.sub_shift,
-                       slot_bits, num_tiles, lds_entries, bin_start, bin_total, words, point_list, ranges, big_queue, inst_gid, list_gid);
+                       slot_bits, num_tiles, lds_entries, im.bin_start, im.bin_total, b.words, b.point_list, im.ranges, im.big_queue,
+                       b.inst_gid, b.list_gid);
     if (t) t->mark(4, s);
     return hipGetLastError() == hipSuccess ? 0 : -1;        // a refused launch (LDS attribute, grid) surfaces here, not at the blend
 }
