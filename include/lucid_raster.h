@@ -331,6 +331,67 @@ int lr_view_backward(const lr_backward_args* a);
 int lr_render_alpha(const char* image_buffer, int width, int height, float* out_alpha, void* stream);
 
 /*
+ * Median depth and per-pixel Gaussian ids of a forward, from its three scratch buffers; a pass of its own behind the forward,
+ * whose kernels are not changed by it.
+ *
+ * Definition.  For one pixel, walk its tile's list front to back exactly as the blend forward does, T = 1 at the start:
+ * power > 0 -> skip; alpha = min(0.99, opacity exp(power)), alpha < 1/255 -> skip; test_T = T (1 - alpha), test_T < 1e-4 -> stop,
+ * not blended; otherwise blend, T = test_T.  The median Gaussian is the first blended Gaussian with test_T < 0.5: the layer at
+ * which the transmittance first falls below one half.
+ *   out_median_depth [1,H,W] float32: that Gaussian's view-space z, the per-Gaussian value the expected depth blends; 0 where T never
+ *     falls below 0.5 (the depth output's "0 = no surface").  Unlike the expected depth D / acc it never lies between a foreground
+ *     and a background surface.
+ *   out_ids [H,W] int32, may be NULL: its row among the caller's P rows; -1 where there is none.
+ * With the 0.99 clamp a pixel still at T >= 0.5 cannot trigger the 1e-4 stop (test_T >= 0.005): the two thresholds never interact.
+ * The values hold under strict parity (lr_tune_set("strict"), which must be what the forward ran under), anti-aliasing, the 3D
+ * filter, raw and activated parameters and both forward shapes: the pass evaluates alpha from the forward's records with the
+ * forward's arithmetic in the forward's order, so its T sequence is the forward's bit for bit.
+ * Valid for raw and activated forwards, exact and async mode (binning_capacity: the value the forward was given; the layout of
+ * the binning buffer is resolved on the device), before or after the view's backward.  An async view that overflowed its binning
+ * buffer writes 0 / -1 everywhere (rc 0; lr_check reports the overflow); so does a view without Gaussians, and P = 0 without
+ * reading a buffer.  width x height must stay below 2^31.
+ *
+ * lr_median_backward: the gradient of out_median_depth.  The selection of the median Gaussian is a constant (as the sort order is
+ * everywhere else): d median_depth[p] / d z_g = 1 for g = ids[p] and nothing else, reaching dL_dmean3D [P,3] (raw mode: dL/dxyz)
+ * through z = view[2] x + view[6] y + view[10] z + view[14].  Nothing flows to opacity, covariance or colour: a weaker signal
+ * than the expected depth's gradient (depth mode of lr_view_backward), enough to put lr_depth_l1_* / lr_depth_pearson_* on the
+ * median depth.  ids: what lr_render_median wrote for the same buffers; radii: the forward's.  accumulate != 0: the rows of
+ * Gaussians that own a tile instance are added to and every other row stays untouched; else dL_dmean3D is written in full,
+ * rows with radii <= 0 as exact zeros.  An overflowed async view contributes nothing.  A gather per Gaussian in a fixed order,
+ * no global float atomics: bit-repeatable.
+ */
+typedef struct lr_median_args {
+    size_t struct_bytes;                     /* = sizeof(lr_median_args); anything else is LR_ERR_INVALID_ARG */
+    const char* geom_buffer;
+    const char* binning_buffer;
+    const char* image_buffer;
+    int P, width, height;
+    long long binning_capacity;              /* the value the forward was given */
+    float* out_median_depth;
+    int* out_ids;                            /* may be NULL */
+    void* stream;
+} lr_median_args;
+
+typedef struct lr_median_backward_args {
+    size_t struct_bytes;                     /* = sizeof(lr_median_backward_args); anything else is LR_ERR_INVALID_ARG */
+    const char* geom_buffer;
+    const char* binning_buffer;
+    const char* image_buffer;
+    int P, width, height;
+    long long binning_capacity;
+    const int* radii;
+    const int* ids;
+    const float* dL_dmedian;
+    const float* viewmatrix;
+    float* dL_dmean3D;
+    int accumulate;
+    void* stream;
+} lr_median_backward_args;
+
+int lr_render_median(const lr_median_args* a);
+int lr_median_backward(const lr_median_backward_args* a);
+
+/*
  * Multi-view step (new; the reference renders one view per Python iteration, luciddreamer.py:291-304).
  * lr_views_accumulate runs lr_forward + the backward for n_views views of ONE parameter set and ACCUMULATES the gradients
  * into the acc_* buffers.  Everything is enqueued from C in one call: views alternate over up to 4 chains (forward of view

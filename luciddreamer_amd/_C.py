@@ -112,6 +112,57 @@ rasterize_autograd = _C_ext.rasterize_autograd
 # the alpha output 1 - T_final (1, H, W) of a forward, from its image buffer (lr_render_alpha); no autograd.  (With alpha=True
 # rasterize_autograd returns it as a fifth, differentiable output.)
 render_alpha = _C_ext.render_alpha
+
+
+def render_median(geomBuffer, binningBuffer, imageBuffer, P, image_height, image_width, *, binning_capacity=0, want_ids=True):
+    """(median_depth (1, H, W) float32, median_ids (H, W) int32 or None) of the forward that left the three buffers
+    (lr_render_median, on the current stream): the view-space depth and the row of the Gaussian at which each pixel's
+    transmittance first falls below one half; 0 / -1 where it never does.  No autograd."""
+    import torch
+    H, W = int(image_height), int(image_width)
+    dev = imageBuffer.device
+    depth = torch.empty((1, H, W), dtype=torch.float32, device=dev)
+    ids = torch.empty((H, W), dtype=torch.int32, device=dev) if want_ids else None
+    a = _lib_check.MedianArgs(geom_buffer=geomBuffer.data_ptr(), binning_buffer=binningBuffer.data_ptr(),
+                              image_buffer=imageBuffer.data_ptr(), P=int(P), width=W, height=H,
+                              binning_capacity=int(binning_capacity), out_median_depth=depth.data_ptr(),
+                              out_ids=ids.data_ptr() if want_ids else None, stream=torch.cuda.current_stream(dev).cuda_stream)
+    with _lib_check.on_device(dev):
+        rc = _lib_check.lib().lr_render_median(a)
+    if rc < 0:
+        _lib_check.raise_for(rc, "render_median")
+    return depth, ids
+
+
+def median_backward(geomBuffer, binningBuffer, imageBuffer, radii, median_ids, dL_dmedian, viewmatrix, *, binning_capacity=0,
+                    accumulate_into=None):
+    """dL/dmeans3D (P, 3) of the median depth (lr_median_backward): dL_dmedian (1, H, W) gathered per Gaussian through
+    median_ids and taken through the view matrix's z row.  accumulate_into: a contiguous float32 (P, 3) tensor whose rows of
+    visible Gaussians are added to in place (returned); else a new tensor, zero where radii <= 0."""
+    import torch
+    H, W = median_ids.shape
+    P = radii.shape[0]
+    dev = median_ids.device
+    out = accumulate_into if accumulate_into is not None else torch.empty((P, 3), dtype=torch.float32, device=dev)
+    if accumulate_into is not None and (not out.is_contiguous() or out.dtype != torch.float32 or out.numel() != 3 * P):
+        raise RuntimeError("median_backward: accumulate_into must be a contiguous float32 (P, 3) tensor")
+    dL = dL_dmedian.contiguous().float()
+    view = viewmatrix.contiguous().float()
+    if dL.numel() != H * W:
+        raise RuntimeError("median_backward: dL_dmedian must have H x W elements")
+    a = _lib_check.MedianBackwardArgs(geom_buffer=geomBuffer.data_ptr(), binning_buffer=binningBuffer.data_ptr(),
+                                      image_buffer=imageBuffer.data_ptr(), P=int(P), width=int(W), height=int(H),
+                                      binning_capacity=int(binning_capacity), radii=radii.data_ptr(), ids=median_ids.data_ptr(),
+                                      dL_dmedian=dL.data_ptr(), viewmatrix=view.data_ptr(), dL_dmean3D=out.data_ptr(),
+                                      accumulate=1 if accumulate_into is not None else 0,
+                                      stream=torch.cuda.current_stream(dev).cuda_stream)
+    with _lib_check.on_device(dev):
+        rc = _lib_check.lib().lr_median_backward(a)
+    if rc < 0:
+        _lib_check.raise_for(rc, "median_backward")
+    return out
+
+
 # forward + backward of one view in one call for a caller that holds dL/dcolor up front; [] = an input does not qualify
 rasterize_view_step = _C_ext.rasterize_view_step
 last_num_rendered = _C_ext.last_num_rendered

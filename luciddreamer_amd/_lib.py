@@ -27,7 +27,8 @@ _lib = None
 _lock = threading.Lock()
 
 EXPORTS = ("lr_last_error", "lr_version", "lr_geom_bytes", "lr_img_bytes", "lr_binning_bytes", "lr_forward",
-           "lr_backward", "lr_view_forward", "lr_view_backward", "lr_render_alpha", "lr_mark_visible", "lr_check",
+           "lr_backward", "lr_view_forward", "lr_view_backward", "lr_render_alpha", "lr_render_median", "lr_median_backward",
+           "lr_mark_visible", "lr_check",
            "lr_dist2_workspace_bytes", "lr_dist2",
            "lr_dist2_workspace_layout",
            "lr_profile_enable", "lr_profile_stage_name", "lr_profile_read", "lr_tune_set", "lr_last_launch_shapes", "lr_request_early_header",
@@ -121,6 +122,29 @@ class BackwardArgs(ctypes.Structure):
 
     def __init__(self, **fields):
         super().__init__(struct_bytes=ctypes.sizeof(BackwardArgs), **fields)
+
+
+class MedianArgs(ctypes.Structure):
+    """lr_median_args, field for field (tests/test_median_cpu.py compares the offsets with the host compiler's)."""
+    _vp, _ci = ctypes.c_void_p, ctypes.c_int
+    _fields_ = [("struct_bytes", ctypes.c_size_t), ("geom_buffer", _vp), ("binning_buffer", _vp), ("image_buffer", _vp),
+                ("P", _ci), ("width", _ci), ("height", _ci), ("binning_capacity", ctypes.c_longlong),
+                ("out_median_depth", _vp), ("out_ids", _vp), ("stream", _vp)]
+
+    def __init__(self, **fields):
+        super().__init__(struct_bytes=ctypes.sizeof(MedianArgs), **fields)
+
+
+class MedianBackwardArgs(ctypes.Structure):
+    """lr_median_backward_args, field for field."""
+    _vp, _ci = ctypes.c_void_p, ctypes.c_int
+    _fields_ = [("struct_bytes", ctypes.c_size_t), ("geom_buffer", _vp), ("binning_buffer", _vp), ("image_buffer", _vp),
+                ("P", _ci), ("width", _ci), ("height", _ci), ("binning_capacity", ctypes.c_longlong),
+                ("radii", _vp), ("ids", _vp), ("dL_dmedian", _vp), ("viewmatrix", _vp), ("dL_dmean3D", _vp),
+                ("accumulate", _ci), ("stream", _vp)]
+
+    def __init__(self, **fields):
+        super().__init__(struct_bytes=ctypes.sizeof(MedianBackwardArgs), **fields)
 
 
 class McmcRelocateArgs(ctypes.Structure):
@@ -239,6 +263,10 @@ def lib():
         L.lr_view_backward.argtypes = [ctypes.POINTER(BackwardArgs)]
         L.lr_render_alpha.restype = ci
         L.lr_render_alpha.argtypes = [vp, ci, ci, vp, vp]                        # image_buffer W H out_alpha stream
+        L.lr_render_median.restype = ci
+        L.lr_render_median.argtypes = [ctypes.POINTER(MedianArgs)]
+        L.lr_median_backward.restype = ci
+        L.lr_median_backward.argtypes = [ctypes.POINTER(MedianBackwardArgs)]
         L.lr_mark_visible.restype = ci
         L.lr_mark_visible.argtypes = [ci, vp, vp, vp, vp, vp]
         L.lr_check.restype = ci

@@ -28,6 +28,7 @@ SOURCES = {
     # scalar per-pixel state on purpose (see the kernel): keep the SLP vectoriser from re-packing it
     "render_fwd.hip": ["-fno-slp-vectorize"],
     "render_bwd.hip": ["-fno-slp-vectorize"],
+    "render_median.hip": ["-fno-slp-vectorize"],     # median depth / ids pass and its gather backward: the forward's alpha arithmetic
     "gauss_bwd.hip": [],
     "knn.hip": [],
     # the separable window sums are long fma chains: packed f32 costs two issue slots plus the moves that form the pairs

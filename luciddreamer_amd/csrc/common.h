@@ -483,6 +483,14 @@ void launch_render_fwd(const ViewParams& vp, const GeomView& g, const ImgView& i
 // out_depth == nullptr: the depth-free kernels (no depth channel in the per-pixel state, no depth image); everything else to the bit
 // alpha [n] = 1 - final_T [n]: the accumulated opacity of the forward that left final_T (lr_render_alpha)
 void launch_render_alpha(const float* final_T, long long n, float* alpha, hipStream_t s);
+// median depth [H*W] and Gaussian ids [H*W] (or nullptr) of a finished forward, and the gradient of the median depth to
+// dL_dmean3D [P,3] (render_median.hip: definition, kernels).  g: rec, header, vis_list; im: ranges; bin_base: the binning buffer,
+// whose list_gid offset the kernel resolves itself.  P <= 0: 0 / -1 everywhere without reading a buffer.
+void launch_render_median(int W, int H, int P, const GeomView& g, const ImgView& im, const char* bin_base, float* out_depth,
+                          int* out_ids, hipStream_t s);
+// accumulate: the rows of emitting Gaussians are added to, else written (the caller zero-fills the others)
+void launch_median_bwd(int W, int H, int P, const GeomView& g, const int* radii, const int* ids, const float* dL_dmedian,
+                       const float* view, float* dL_dmean3D, bool accumulate, hipStream_t s);
 // The upstream gradients a view's backward is given.
 struct ViewGrads {
     const float* color;     // dL_dpix [3,H,W]

@@ -7,6 +7,12 @@
 
 Beyond the reference: return_alpha=True (GaussianRasterizer.forward, rasterize_gaussians, rasterize_gaussians_raw) returns
 (color, radii, depth, alpha) -- alpha (1, H, W) = 1 - T_final, the accumulated opacity, differentiable (lr_view_backward with dL_dalpha).
+return_median=True (same three entry points) appends (median_depth, median_ids) to the outputs: median_depth (1, H, W) is the view-space
+depth of the Gaussian at which the pixel's transmittance first falls below one half (0 where it never does), median_ids (H, W) int32
+that Gaussian's row (-1 where there is none; not differentiable) -- lr_render_median, a pass behind the forward.  Unlike the expected
+depth it never lies between a foreground and a background surface.  Its gradient reaches means3D / xyz only (the selection is a
+constant; nothing flows to opacity, covariance or colour): a weaker signal than the expected depth's, enough for loss.depth_l1 /
+loss.depth_pearson on the median depth.
 config.set_absgrad(True): the backward of a view attaches `means2D.absgrad` [P,3] (AbsGS; lr_view_backward with dL_dmean2D_abs) to the means2D
 tensor the caller passed.
 
@@ -92,12 +98,38 @@ def _snapshot(args, path):
     torch.save(tuple(a.detach().cpu().clone() if isinstance(a, torch.Tensor) else a for a in args), path)
 
 
+def _median_outputs(ctx, P, rs, geom, binning, img, capacity):
+    """(median_depth, median_ids) of the forward whose buffers are given -- after an overflow re-render the re-render's, as alpha's --
+    and what the backward of a node needs of them: the ids (not differentiable, so keeping them on ctx is no reference cycle)."""
+    median_depth, median_ids = _C.render_median(geom, binning, img, P, rs.image_height, rs.image_width, binning_capacity=capacity)
+    ctx.mark_non_differentiable(median_ids)
+    ctx.median_ids = median_ids
+    return median_depth, median_ids
+
+
+def _more_grads(ctx, grad_more):
+    """(grad_alpha, grad_median) from the gradients behind (color, radii, depth): [alpha], [median_depth, median_ids]."""
+    grad_alpha = grad_more[0] if ctx.return_alpha else None
+    grad_median = grad_more[-2] if ctx.median_ids is not None else None
+    return grad_alpha, grad_median
+
+
+def _median_backward(ctx, grad_median, grad_means3D, fused_grad, radii, geom, binning, img):
+    """The median depth's term of dL/dmeans3D (lr_median_backward), added behind the view's backward on the same stream: into the
+    tensor that backward returned, or, where it accumulated into the leaf's .grad in place (returned None), into that .grad --
+    the same additions in the same order either way."""
+    target = grad_means3D if grad_means3D is not None else fused_grad
+    _C.median_backward(geom, binning, img, radii, ctx.median_ids, grad_median, ctx.raster_settings.viewmatrix,
+                       binning_capacity=ctx.binning_capacity, accumulate_into=target)
+    return grad_means3D
+
+
 class _RasterizeGaussians(torch.autograd.Function):
     """forward/backward wiring of RAST/.../__init__.py:44-156."""
 
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                raster_settings, return_alpha=False):
+                raster_settings, return_alpha=False, return_median=False):
         rs = raster_settings
         args = (rs.bg, means3D, colors_precomp, opacities, scales, rotations, rs.scale_modifier, cov3Ds_precomp,
                 rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, rs.image_height, rs.image_width, sh,
@@ -126,15 +158,23 @@ class _RasterizeGaussians(torch.autograd.Function):
         if ctx.depth_image is not None:
             ctx.set_materialize_grads(False)        # an unused depth output arrives as None: the default kernels
         ctx.save_for_backward(colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geom, binning, img)
-        if not return_alpha:
+        ctx.return_alpha = bool(return_alpha)
+        ctx.median_ids = None
+        if not return_alpha and not return_median:
             return color, radii, depth
         # the alpha output, from the image state of the forward returned above (after a re-render, the re-render's); the
         # backward needs that state's final T only -- the alpha tensor itself is not kept (see depth_image above)
-        ctx.set_materialize_grads(False)            # an unused alpha output arrives as None: the default kernels
-        return color, radii, depth, _C.render_alpha(img, rs.image_height, rs.image_width)
+        ctx.set_materialize_grads(False)            # an unused alpha / median output arrives as None: the default kernels
+        out = (color, radii, depth)
+        if return_alpha:
+            out += (_C.render_alpha(img, rs.image_height, rs.image_width),)
+        if return_median:
+            out += _median_outputs(ctx, means3D.shape[0], rs, geom, binning, img, capacity)
+        return out
 
     @staticmethod
-    def backward(ctx, grad_out_color, grad_radii, grad_depth, grad_alpha=None):
+    def backward(ctx, grad_out_color, grad_radii, grad_depth, *grad_more):
+        grad_alpha, grad_median = _more_grads(ctx, grad_more)
         config.require_antialiasing(ctx.antialiasing)   # before anything is launched or written
         rs = ctx.raster_settings
         colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geom, binning, img = ctx.saved_tensors
@@ -155,6 +195,9 @@ class _RasterizeGaussians(torch.autograd.Function):
              grad_scales, grad_rotations) = g[:8]
             if ctx.absgrad_to is not None:              # gsplat's convention; replaced at every backward
                 ctx.absgrad_to.absgrad = g[8]
+            if grad_median is not None:
+                grad_means3D = _median_backward(ctx, grad_median, grad_means3D, (accumulate_into or {}).get("means3D"),
+                                                radii, geom, binning, img)
         except Exception:
             if rs.debug:
                 _snapshot(args, "snapshot_bw.dump")
@@ -162,20 +205,26 @@ class _RasterizeGaussians(torch.autograd.Function):
             raise
         # order of the forward inputs (RAST/.../__init__.py:144-154); gradients of absent inputs are None-able
         return (grad_means3D, grad_means2D, grad_sh, grad_colors_precomp, grad_opacities, grad_scales, grad_rotations,
-                grad_cov3Ds_precomp, None, None)
+                grad_cov3Ds_precomp, None, None, None)
 
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                        raster_settings, return_alpha=False):
+                        raster_settings, return_alpha=False, return_median=False):
     """The operator.  Its autograd node is compiled (csrc/torch_ext.cpp RasterizeFn: forward and backward run without the
     interpreter -- the Python node below cost more host time per 1080p view than the GPU needs for it); with settings.debug
     the Python node runs instead, because it is the one that writes the reference's snapshot_fw.dump / snapshot_bw.dump.
     return_alpha: (color, radii, depth, alpha) -- alpha = 1 - T_final (1, H, W), differentiable; a gradient reaching it runs the
-    alpha-mode backward (lr_view_backward with dL_dalpha), an unused alpha output the default one."""
+    alpha-mode backward (lr_view_backward with dL_dalpha), an unused alpha output the default one.
+    return_median: the outputs gain (median_depth, median_ids) at their end (module docstring).  Such a call always runs the
+    Python node, which holds the forward's geom, binning and image buffers in hand as debug does -- never the compiled node or
+    the one-call rasterize_view_step route: the interpreter's share of a view (the node's forward and backward, plus two ctypes
+    calls and two small launches) is paid per call, which at 1080p is more host time than the GPU needs for the view.  Unused
+    median outputs leave the backward exactly as it is without them; a gradient reaching median_depth adds its term to the
+    gradient of means3D, with config.set_fused_grad_accumulation on or off."""
     rs = raster_settings
-    if rs.debug:
+    if rs.debug or return_median:
         return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
-                                         cov3Ds_precomp, rs, bool(return_alpha))
+                                         cov3Ds_precomp, rs, bool(return_alpha), bool(return_median))
     capacity = config.capacity_for(means3D, rs)
     fused = config.fused_grad_accumulation()
     offered = config.offered_grad_output()
@@ -214,7 +263,8 @@ class _RasterizeGaussiansRaw(torch.autograd.Function):
     exp / normalize / sigmoid / cat and their autograd nodes (R/scene/gaussian_model.py:97-117)."""
 
     @staticmethod
-    def forward(ctx, xyz, means2D, features_dc, features_rest, opacity, scaling, rotation, raster_settings, return_alpha=False):
+    def forward(ctx, xyz, means2D, features_dc, features_rest, opacity, scaling, rotation, raster_settings, return_alpha=False,
+                return_median=False):
         rs = raster_settings
         ctx.antialiasing = config.antialiasing()        # as _RasterizeGaussians
         ctx.absgrad_to = means2D if config.absgrad() else None
@@ -235,13 +285,21 @@ class _RasterizeGaussiansRaw(torch.autograd.Function):
         if ctx.depth_image is not None:
             ctx.set_materialize_grads(False)
         ctx.save_for_backward(xyz, features_dc, features_rest, opacity, scaling, rotation, radii, geom, binning, img)
-        if not return_alpha:
+        ctx.return_alpha = bool(return_alpha)
+        ctx.median_ids = None
+        if not return_alpha and not return_median:
             return color, radii, depth
         ctx.set_materialize_grads(False)                # as _RasterizeGaussians
-        return color, radii, depth, _C.render_alpha(img, rs.image_height, rs.image_width)
+        out = (color, radii, depth)
+        if return_alpha:
+            out += (_C.render_alpha(img, rs.image_height, rs.image_width),)
+        if return_median:
+            out += _median_outputs(ctx, xyz.shape[0], rs, geom, binning, img, capacity)
+        return out
 
     @staticmethod
-    def backward(ctx, grad_out_color, grad_radii, grad_depth, grad_alpha=None):
+    def backward(ctx, grad_out_color, grad_radii, grad_depth, *grad_more):
+        grad_alpha, grad_median = _more_grads(ctx, grad_more)
         config.require_antialiasing(ctx.antialiasing)   # before anything is launched or written
         rs = ctx.raster_settings
         xyz, features_dc, features_rest, opacity, scaling, rotation, radii, geom, binning, img = ctx.saved_tensors
@@ -271,8 +329,10 @@ class _RasterizeGaussiansRaw(torch.autograd.Function):
                 binning, img, False, binning_capacity=ctx.binning_capacity, no_zero_fill=True, **modes)
             if ctx.absgrad_to is not None:              # written in full also here (zero-filled like means2D): not part of the step
                 ctx.absgrad_to.absgrad = g[7]
+            if grad_median is not None:                 # the rows it adds to are rows the view visited
+                _median_backward(ctx, grad_median, g[1], None, radii, geom, binning, img)
             opt.apply_armed_step(geom, [xyz, features_dc, features_rest, opacity, scaling, rotation], list(g[1:7]))
-            return None, g[0], None, None, None, None, None, None, None
+            return None, g[0], None, None, None, None, None, None, None, None
         g = _C.rasterize_gaussians_raw_backward(
             rs.bg, xyz, radii, features_dc, features_rest, opacity, scaling, rotation, rs.scale_modifier, rs.viewmatrix,
             rs.projmatrix, rs.tanfovx, rs.tanfovy, grad_out_color, rs.sh_degree, rs.campos, geom, ctx.num_rendered,
@@ -280,15 +340,18 @@ class _RasterizeGaussiansRaw(torch.autograd.Function):
         if ctx.absgrad_to is not None:
             ctx.absgrad_to.absgrad = g[7]
         g_means2D, g_xyz, g_dc, g_rest, g_op, g_sc, g_rot = g[:7]
-        return g_xyz, g_means2D, g_dc, g_rest, g_op, g_sc, g_rot, None, None
+        if grad_median is not None:
+            g_xyz = _median_backward(ctx, grad_median, g_xyz, (accumulate_into or {}).get("xyz"), radii, geom, binning, img)
+        return g_xyz, g_means2D, g_dc, g_rest, g_op, g_sc, g_rot, None, None, None
 
 
 def rasterize_gaussians_raw(xyz, means2D, features_dc, features_rest, opacity, scaling, rotation, raster_settings,
-                            return_alpha=False):
+                            return_alpha=False, return_median=False):
     """(color, radii, depth) from the stored GaussianModel parameters (pre-activation), see _RasterizeGaussiansRaw;
-    return_alpha: (color, radii, depth, alpha) as rasterize_gaussians."""
+    return_alpha: (color, radii, depth, alpha) as rasterize_gaussians; return_median: (median_depth, median_ids) behind them, as
+    rasterize_gaussians (this entry point always runs its Python node); the median depth's gradient reaches xyz."""
     return _RasterizeGaussiansRaw.apply(xyz, means2D, features_dc, features_rest, opacity, scaling, rotation,
-                                        raster_settings, bool(return_alpha))
+                                        raster_settings, bool(return_alpha), bool(return_median))
 
 
 _EMPTY = torch.Tensor([])           # never written: one instance serves every call (three constructions per call were ~6 us)
@@ -306,8 +369,9 @@ class GaussianRasterizer(nn.Module):
             return _C.mark_visible(positions, rs.viewmatrix, rs.projmatrix)
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
-                cov3D_precomp=None, return_alpha=False):
-        """(color, radii, depth), or with return_alpha=True (color, radii, depth, alpha): alpha (1, H, W) = 1 - T_final."""
+                cov3D_precomp=None, return_alpha=False, return_median=False):
+        """(color, radii, depth), or with return_alpha=True (color, radii, depth, alpha): alpha (1, H, W) = 1 - T_final; with
+        return_median=True the outputs gain (median_depth, median_ids) at their end (rasterize_gaussians)."""
         rs = self.raster_settings
         if (shs is None) == (colors_precomp is None):
             raise Exception('Please provide excatly one of either SHs or precomputed colors!')
@@ -322,8 +386,8 @@ class GaussianRasterizer(nn.Module):
         scales = empty if scales is None else scales
         rotations = empty if rotations is None else rotations
         cov3D_precomp = empty if cov3D_precomp is None else cov3D_precomp
-        if return_alpha:
+        if return_alpha or return_median:
             return rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
-                                       cov3D_precomp, rs, return_alpha=True)
+                                       cov3D_precomp, rs, return_alpha=return_alpha, return_median=return_median)
         return rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
                                    cov3D_precomp, rs)

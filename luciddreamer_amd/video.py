@@ -196,6 +196,9 @@ def colorize_depth(depth, vmin=None, vmax=None, cmap="jet", invalid_val=-99, inv
 def iter_video_frames(views, pc, opt, bg_color, *, depth=True, in_flight=8, to_host=True, render_fn=None):
     """The loop of render_video (R/luciddreamer.py:250-255) with its post-processing on the device.  Yields
     (frame_u8 [H,W,3], depth_rgba [H,W,4] or None when depth=False) per view, in view order.
+    depth="median" colourises the median depth instead of the expected one (no smear between foreground and background at object
+    edges): the view is rendered with return_median=True, which `render_fn` must then accept (gaussian_renderer.render and
+    render_raw do), and out["median_depth"] goes to colorize_depth.
 
     Each view runs `render_fn(view, pc, opt, bg_color)` (default: gaussian_renderer.render, the forward the drop-in takes;
     pass gaussian_renderer.render_raw or the caller's own render) under torch.no_grad(), then frames_to_uint8 and
@@ -203,6 +206,8 @@ def iter_video_frames(views, pc, opt, bg_color, *, depth=True, in_flight=8, to_h
     into `in_flight` pinned slots guarded by events: the host waits only when it yields a frame or reuses a slot, and the
     yielded numpy arrays are the caller's own (copied out of the slot).  With to_host=False the device tensors are yielded.
     The global configuration (luciddreamer_amd.config) is not touched."""
+    if depth not in (True, False, "median"):
+        raise ValueError('iter_video_frames: depth must be True, False or "median"')
     in_flight = int(in_flight)
     if in_flight < 1:
         raise ValueError("iter_video_frames: in_flight must be >= 1")
@@ -228,9 +233,10 @@ def _frames(views, pc, opt, bg_color, depth, in_flight, to_host, render_fn, dev)
     try:
         for i, view in enumerate(views):
             with torch.no_grad():
-                out = render_fn(view, pc, opt, bg_color)
+                median = isinstance(depth, str)             # "median" (iter_video_frames checked it)
+                out = render_fn(view, pc, opt, bg_color, return_median=True) if median else render_fn(view, pc, opt, bg_color)
                 f = frames_to_uint8(out["render"])
-                c = colorize_depth(out["depth"])[0] if depth else None
+                c = colorize_depth(out["median_depth" if median else "depth"])[0] if depth else None
             if not to_host:
                 yield f, c
                 continue
