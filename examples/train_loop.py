@@ -9,6 +9,7 @@ piece of this repository on the MI355X:
     distCUDA2         initial scales from the 3-nearest-neighbour distance                              8f-1
     MCMCStrategy      --mcmc: relocation, capped growth and position noise instead of densify_and_prune   DESIGN.md 4b-MCMC
     filter3d          --filter3d: the 3D smoothing filter of Mip-Splatting on what the rasterizer is shown   DESIGN.md 4b-F3D
+    normals           --normal-weight / --normal-consistency: normals from depth and the fused normal losses  DESIGN.md 4b-NRM
 
 Targets are renders of a hidden "ground truth" cloud from a look-around camera path; the trained cloud starts from
 a perturbed subset of it.  Prints the loss every `--log` iterations and the time per iteration.
@@ -19,6 +20,7 @@ a perturbed subset of it.  Prints the loss every `--log` iterations and the time
                                   [--mcmc --cap-max 150000]
                                   [--multi-view 4 --depth-weight 0.1 [--depth-loss pearson]]
                                   [--filter3d [--antialiasing]]
+                                  [--normal-weight 0.05] [--normal-consistency 0.05]
 
 --multi-view K: the loop body is ONE multi-view step (parallel.ViewBatch: forward, L1 + DSSIM loss and backward of K views in one
 C call, gradients summed) followed by Adam; the densification statistics are formed inside the step, per view
@@ -34,6 +36,12 @@ would be pulled apart by.
 calls: the regularisers' gradients are added before the optimizer's step, and after it dead Gaussians are relocated and the set
 grows by 5 % -- never beyond N -- on the --densify-from / --densify-every / --densify-until schedule, with the position noise
 every iteration.  No gradient threshold and no densification statistics are involved.
+
+--normal-weight W (single-view loop): the rendered depth's normals are held to the normals of the hidden cloud's depth map
+(normals.depth_normals of it, no gradient: what a monocular normal estimate would be) by normals.normal_loss with weight W, with
+the depth gradient on (config.set_depth_gradient).  --normal-consistency W: the forward also returns the median depth
+(return_median=True) and normals.normal_consistency(depth, median_depth) with weight W is added; the median's side of it moves
+the means only.  The multi-view step has no normal term of its own: a caller reaches it through ViewBatch(grad_depths=).
 
 --filter3d: in either loop the rasterizer is shown the cloud through luciddreamer_amd.filter3d.filtered(model, filter): every
 Gaussian low-passed by the highest sampling rate at which a training camera sees it (the 3D smoothing filter of Mip-Splatting).
@@ -55,6 +63,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from luciddreamer_amd import cameras, config, densify, filter3d, mcmc, synthetic     # noqa: E402
 from luciddreamer_amd.gaussian_renderer import GaussianCloud, render_raw   # noqa: E402
 from luciddreamer_amd.loss import l1_dssim_loss                            # noqa: E402
+from luciddreamer_amd.normals import depth_normals, normal_consistency, normal_loss     # noqa: E402
 from luciddreamer_amd.optim import FusedAdam                               # noqa: E402
 from simple_knn._C import distCUDA2                                        # noqa: E402
 
@@ -124,6 +133,17 @@ def depth_targets_for(args, dev):
             a, b = 0.5 + 1.5 * float(torch.rand(1, generator=g)), -1.0 + 2.0 * float(torch.rand(1, generator=g))
             depths[i] = torch.where(d > 0, (a * d + b).clamp_min(1e-3), d)       # a pixel with a target keeps one
     return depths
+
+
+def normal_targets_for(args, dev):
+    """--normal-weight: per view, the normals of the hidden cloud's depth map ((0,0,0) where it has none: no target there)."""
+    W, H = (int(v) for v in args.resolution.split("x"))
+    gt_cloud = {k: v.to(dev) for k, v in synthetic.make_cloud(args.gaussians, "box", 0).items()}
+    gt = GaussianCloud(gt_cloud["means3D"], gt_cloud["scales"], gt_cloud["rotations"], gt_cloud["opacities"], gt_cloud["shs"],
+                       requires_grad=False)
+    cams = [c.to(dev) for c in cameras.lookaround_path(W, H, n_views=args.views)]
+    with torch.no_grad():
+        return [depth_normals(render_raw(c, gt, render_only=True)["depth"].reshape(1, H, W).contiguous(), c) for c in cams]
 
 
 LR_XYZ = 1.6e-4                # the position learning rate of build(): the noise is scaled by it
@@ -255,10 +275,17 @@ def train_multi_view(args, log=print):
 
 
 def train(args, log=print):
+    normal_w, consistency_w = getattr(args, "normal_weight", 0.0), getattr(args, "normal_consistency", 0.0)
     if getattr(args, "multi_view", 0) > 0:
+        if normal_w > 0 or consistency_w > 0:
+            raise SystemExit("--normal-weight / --normal-consistency: the single-view loop only (the multi-view step takes an "
+                             "external depth term through ViewBatch(grad_depths=))")
         return train_multi_view(args, log)
     dev = torch.device("cuda:0")
     model, cams, targets = build(args, dev)
+    normal_targets = normal_targets_for(args, dev) if normal_w > 0 else None
+    if normal_w > 0 or consistency_w > 0:
+        config.set_depth_gradient(True)            # the normal terms act on the rendered depth
     bg = torch.zeros(3, device=dev)
     # no host round trip per forward ("Host sync"); instance counts drift while the cloud is
     # optimised, so the capacity is taken over the views of the path, with generous headroom
@@ -273,8 +300,12 @@ def train(args, log=print):
     t0 = time.perf_counter()
     for it in range(1, args.iters + 1):
         v = int(torch.randint(0, len(cams), (1,), generator=gen))
-        pkg = render_raw(cams[v], f3.view(model), bg_color=bg)                            # luciddreamer.py:296
+        pkg = render_raw(cams[v], f3.view(model), bg_color=bg, return_median=consistency_w > 0)    # luciddreamer.py:296
         loss = l1_dssim_loss(pkg["render"], targets[v], args.lambda_dssim)                # :301-303
+        if normal_w > 0:
+            loss = loss + normal_loss(pkg["depth"], normal_targets[v], cams[v], weight=normal_w)
+        if consistency_w > 0:
+            loss = loss + normal_consistency(pkg["depth"], pkg["median_depth"], cams[v], weight=consistency_w)
         loss.backward()                                                                   # :304
         with torch.no_grad():
             vis, radii = pkg["visibility_filter"], pkg["radii"]
@@ -299,6 +330,8 @@ def train(args, log=print):
     config.set_async(True)              # back to the library defaults
     config.set_antialiasing(False)
     config.set_absgrad(False)
+    if normal_w > 0 or consistency_w > 0:
+        config.set_depth_gradient(False)
     log(f"{args.iters} iterations in {dt:.2f} s = {dt / args.iters * 1e3:.3f} ms/iteration")
     return losses, dt
 
@@ -306,7 +339,8 @@ def train(args, log=print):
 def default_args(**kw):
     d = dict(gaussians=200_000, iters=300, resolution="512x512", views=12, lambda_dssim=0.2, log=50, densify_from=100,
              densify_every=100, densify_until=10_000, exact=False, torch_adam=False, antialiasing=False, absgrad=False,
-             densify_grad_threshold=0.0002, multi_view=0, mcmc=False, cap_max=0, depth_weight=0.0, depth_loss="l1", filter3d=False)
+             densify_grad_threshold=0.0002, multi_view=0, mcmc=False, cap_max=0, depth_weight=0.0, depth_loss="l1", filter3d=False,
+             normal_weight=0.0, normal_consistency=0.0)
     d.update(kw)
     return SimpleNamespace(**d)
 
@@ -325,6 +359,10 @@ HELP = {
     "depth_weight": "with --multi-view: > 0 adds depth supervision against the hidden cloud's depth maps with this weight",
     "depth_loss": "the depth term of --depth-weight: l1 (absolute values, loss.depth_l1) or pearson (1 - correlation, "
                   "loss.depth_pearson; the targets are then corrupted by a per-view scale in [0.5, 2] and shift in [-1, 1])",
+    "normal_weight": "single-view loop: > 0 holds the rendered depth's normals to the normals of the hidden cloud's depth map "
+                     "(normals.normal_loss) with this weight; turns the depth gradient on",
+    "normal_consistency": "single-view loop: > 0 adds normals.normal_consistency(depth, median_depth) with this weight "
+                          "(return_median=True); the median's side moves the means only",
     "densify_grad_threshold": "clone / split threshold on the accumulated view-space gradient norm (reference: 0.0002).  Summed "
                               "magnitudes are larger than the signed norm: with --absgrad use about 4x (0.0008)",
 }

@@ -797,6 +797,93 @@ int lr_alpha_hole_backward(int height, int width, const float* mask, float weigh
                            void* stream);
 
 /*
+ * Surface normals from a depth map, and the normal losses on them (luciddreamer_amd/csrc/normals.hip).
+ *
+ * depth: [H,W] float32 device image, contiguous: the rasterizer's depth or median depth, 0 = "no surface".  The camera is
+ * tan_fovx, tan_fovy with the pixel convention of gauss_project.h: pixel (x, y) has the view-space ray (u, v, 1), axes x right,
+ * y down, z forward.  Every operation below is ONE float32 operation in the order written (no fma; division and square root
+ * correctly rounded), so a numpy float32 restatement gives the same bits (tests/normal_ref.py):
+ *     ax = (2 tan_fovx) / W,  ay = (2 tan_fovy) / H
+ *     u = ax (x + 0.5) - tan_fovx,  v = ay (y + 0.5) - tan_fovy
+ * For an interior pixel (1 <= x <= W-2, 1 <= y <= H-2) with E, W, N, S the depths at (x+1,y), (x-1,y), (x,y-1), (x,y+1):
+ *     gx = E - W,  sx = E + W,  gy = S - N,  sy = S + N
+ *     p = ax sx,  r = ay sy
+ *     a = r gx,  b = p gy
+ *     c = ( a,  b,  -((b v + a u) + p r) )
+ *     m2 = (c0 c0 + c1 c1) + c2 c2,  len = sqrt(m2),  n = ( c0 / len, c1 / len, c2 / len )
+ * This is 2DGS's depth_to_normal: the normalised cross product of the central differences of the lifted points
+ * P(x, y) = d(x, y) (u, v, 1), n ~ (P_S - P_N) x (P_E - P_W), oriented towards the camera (n.(u, v, 1) < 0).  It is NOT evaluated
+ * by lifting and subtracting points: expanded, the cross product's terms in u^2, v^2 and u v cancel identically, and what is
+ * left is written so that the only cancellation is the depth difference itself (gx, gy): the lifted form loses digits with the
+ * resolution (neighbouring rays differ by ax), this one does not.  Because c.(u, v, 1) = -ax ay sx sy < 0, |c| > 0 whenever the
+ * four depths are positive.  n(k depth) = n(depth) bit for bit for k a power of two.
+ * A pixel is VALID when it is interior, its own depth and its four neighbours' depths are all > 0 (NaN fails), and m2 is finite
+ * (and, against underflow, > 0).  An invalid pixel has the normal (0,0,0) and contributes nothing to any value or gradient.
+ * H < 3 or W < 3 has no valid pixel: every output is exactly 0.
+ *
+ *   lr_depth_normals          : out_normals [3,H,W] = n (planes n0, n1, n2).
+ *   lr_depth_normals_backward : dL_ddepth [H,W] from Gn = dL_dnormals [3,H,W]; per valid pixel
+ *                                   dn = (n0 Gn0 + n1 Gn1) + n2 Gn2,   G_i = (Gn_i - n_i dn) / len
+ *                               then the chain below.
+ *   lr_normal_loss_forward    : loss = weight * sum_counted w_p (1 - n_p.t_p) / (H*W)  (divided by ALL pixels, as lr_depth_l1_forward),
+ *                               out (device, 2 floats) = {loss, number of pixels that counted (exact up to 2^24)}.
+ *                               pixel_weight: optional [H,W] plane w_p >= 0, NULL = 1; a value that is not > 0 (NaN included)
+ *                               excludes the pixel.  The target is EXACTLY ONE of
+ *                                   target_normals [3,H,W]: data, normalised here: tt = (t0 t0 + t1 t1) + t2 t2, tl = sqrt(tt),
+ *                                       t = (t0 / tl, t1 / tl, t2 / tl); a pixel whose tt is not > 0 or not finite is excluded;
+ *                                   target_depth [H,W]: t = its normals by the formula and validity rule above (the consistency
+ *                                       term, e.g. expected depth against median depth).
+ *                               A pixel COUNTS when its normal is valid, its target is, and its weight is.  Per pixel, float32:
+ *                                   dot = (n0 t0 + n1 t1) + n2 t2,   term = w_p (1 - dot)
+ *                               The terms are summed in double: per workgroup in a fixed order into `workspace`
+ *                               (lr_normals_workspace_bytes), then by one workgroup in a fixed order.  No atomics: bit-repeatable.
+ *   lr_normal_loss_backward   : dL_ddepth [H,W] = upstream * d loss / d depth; in consistency mode, optionally,
+ *                               dL_dtarget_depth [H,W] = upstream * d loss / d target_depth: the same formula with the roles of
+ *                               the two depths swapped.  `upstream` is a device scalar or NULL for 1.  The normals are recomputed
+ *                               from the depths: no stored normal plane, no workspace.  Per counted pixel
+ *                                   k = (upstream weight) / (float)(H W),   q = k w_p  (k without a weight plane)
+ *                                   kk = q / len,   G_i = -(kk (t_i - n_i dot))
+ * The chain from G to the four neighbour depths of a pixel:
+ *     A = G0 - u G2,  B = G1 - v G2
+ *     dgx = r A,  dgy = p B
+ *     dsx = ax (gy B - r G2),  dsy = ay (gx A - p G2)
+ *     tE = dgx + dsx,  tW = dsx - dgx,  tS = dgy + dsy,  tN = dsy - dgy
+ * and the gradient is GATHERED, not scattered: output pixel (x, y) is
+ *     ((tE of (x-1,y) + tW of (x+1,y)) + tS of (x,y-1)) + tN of (x,y+1)
+ * -- the terms of its W, E, N and S neighbours' normals in that fixed order, a term of a pixel that does not count (or lies
+ * outside the image) being +0.  No atomics: bit-repeatable.  A pixel's own normal does not depend on its own depth (only its
+ * validity does), and the four image corners get exactly 0.
+ *
+ * height, width >= 1 and H*W < 2^31; tan_fovx, tan_fovy finite and > 0; weight finite and >= 0.  struct_bytes is checked before
+ * anything else; every check sits in front of the first HIP call.  Each entry point reads the members named with it and ignores
+ * the others.  No host synchronisation.  Return 0 or a negative LR_ERR_*.
+ */
+typedef struct lr_normals_args {
+    size_t struct_bytes;                     /* = sizeof(lr_normals_args); anything else is LR_ERR_INVALID_ARG */
+    int height, width;
+    float tan_fovx, tan_fovy;
+    const float* depth;                      /* all four: [H,W] */
+    float* out_normals;                      /* lr_depth_normals: [3,H,W] */
+    const float* dL_dnormals;                /* lr_depth_normals_backward: [3,H,W] */
+    const float* target_normals;             /* loss forward / backward: [3,H,W], or */
+    const float* target_depth;               /* ... [H,W]: exactly one of the two */
+    const float* pixel_weight;               /* loss forward / backward: [H,W], optional */
+    float weight;                            /* loss forward / backward */
+    const float* upstream;                   /* loss backward: device scalar, optional */
+    float* out;                              /* loss forward: {loss, count} */
+    float* dL_ddepth;                        /* both backwards: [H,W] */
+    float* dL_dtarget_depth;                 /* loss backward with target_depth: [H,W], optional */
+    void* workspace;                         /* loss forward */
+    size_t workspace_bytes;
+    void* stream;
+} lr_normals_args;
+size_t lr_normals_workspace_bytes(int height, int width);
+int lr_depth_normals(const lr_normals_args* a);
+int lr_depth_normals_backward(const lr_normals_args* a);
+int lr_normal_loss_forward(const lr_normals_args* a);
+int lr_normal_loss_backward(const lr_normals_args* a);
+
+/*
  * Video frames on the device (the per-frame post-processing of the video renderer, R/luciddreamer.py:250-265).  Every entry
  * point takes n_frames contiguous frames of one H, W and handles them in the same launches; nothing reads back to the host.
  *

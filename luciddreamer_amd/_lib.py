@@ -44,7 +44,9 @@ EXPORTS = ("lr_last_error", "lr_version", "lr_geom_bytes", "lr_img_bytes", "lr_b
            "lr_mcmc_workspace_bytes", "lr_mcmc_relocate", "lr_mcmc_noise", "lr_mcmc_reg_grad",
            "lr_filter3d_workspace_bytes", "lr_filter3d_update", "lr_filter3d_apply_forward", "lr_filter3d_apply_backward",
            "lr_reproject_workspace_bytes", "lr_reproject", "lr_lift",
-           "lr_dream_workspace_bytes", "lr_dream_scale_sums", "lr_dream_correspond", "lr_dream_lift", "lr_scatter_interpolate")
+           "lr_dream_workspace_bytes", "lr_dream_scale_sums", "lr_dream_correspond", "lr_dream_lift", "lr_scatter_interpolate",
+           "lr_normals_workspace_bytes", "lr_depth_normals", "lr_depth_normals_backward", "lr_normal_loss_forward",
+           "lr_normal_loss_backward")
 
 # lr_views_workspace_bytes / lr_views_check `parts`: what a step's workspace slots hold besides a view's scratch
 LR_VIEWS_LOSS, LR_VIEWS_DEPTH_LOSS, LR_VIEWS_MASK_LOSS = 1, 2, 4
@@ -200,7 +202,19 @@ class ScatterArgs(ctypes.Structure):
         super().__init__(struct_bytes=ctypes.sizeof(ScatterArgs), **fields)
 
 
-LR_SCATTER_TILE = 256               # samples per on-chip tile of lr_scatter_interpolate (include/lucid_raster.h)
+class NormalsArgs(ctypes.Structure):
+    """lr_normals_args, field for field (tests/test_normals_cpu.py compares the offsets with the host compiler's)."""
+    _vp, _ci, _cf = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
+    _fields_ = [("struct_bytes", ctypes.c_size_t), ("height", _ci), ("width", _ci), ("tan_fovx", _cf), ("tan_fovy", _cf),
+                ("depth", _vp), ("out_normals", _vp), ("dL_dnormals", _vp), ("target_normals", _vp), ("target_depth", _vp),
+                ("pixel_weight", _vp), ("weight", _cf), ("upstream", _vp), ("out", _vp), ("dL_ddepth", _vp),
+                ("dL_dtarget_depth", _vp), ("workspace", _vp), ("workspace_bytes", ctypes.c_size_t), ("stream", _vp)]
+
+    def __init__(self, **fields):
+        super().__init__(struct_bytes=ctypes.sizeof(NormalsArgs), **fields)
+
+
+LR_SCATTER_TILE = 256             # samples per on-chip tile of lr_scatter_interpolate (include/lucid_raster.h)
 
 
 def assert_single_copy():
@@ -362,6 +376,11 @@ def lib():
             fn.argtypes = [ctypes.POINTER(DreamArgs)]
         L.lr_scatter_interpolate.restype = ci
         L.lr_scatter_interpolate.argtypes = [ctypes.POINTER(ScatterArgs)]
+        L.lr_normals_workspace_bytes.restype = ctypes.c_size_t
+        L.lr_normals_workspace_bytes.argtypes = [ci, ci]
+        for fn in (L.lr_depth_normals, L.lr_depth_normals_backward, L.lr_normal_loss_forward, L.lr_normal_loss_backward):
+            fn.restype = ci
+            fn.argtypes = [ctypes.POINTER(NormalsArgs)]
         L.lr_step_begin.restype = ci
         L.lr_step_begin.argtypes = []
         L.lr_step_end.restype = ci

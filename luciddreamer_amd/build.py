@@ -46,6 +46,9 @@ SOURCES = {
     "reproject.hip": ["-ffp-contract=off"],
     # dreaming (scale sums, correspondences, scattered interpolation, compensated lift): float64 in a fixed order, as above
     "dream.hip": ["-ffp-contract=off"],
+    # normals from depth and the normal losses: the header's float32 operations, one rounding each (a numpy restatement agrees
+    # to the bit): no FMA contraction
+    "normals.hip": ["-ffp-contract=off"],
     "api.hip": [],
 }
 

@@ -652,6 +652,14 @@ void launch_alpha_hole_backward(int H, int W, const float* mask, float weight, c
                                 LossValue value, hipStream_t s);
 void launch_zero_outputs(float* const* ptrs, const unsigned long long* nfloats, int count, hipStream_t s);
 
+// surface normals from depth and the normal losses (normals.hip): the launchers take lr_normals_args as the entry points
+// checked it; each reads the members of its entry point.  workspace: normals_workspace_bytes, {sum, count} per workgroup.
+size_t normals_workspace_bytes(int H, int W);
+void launch_depth_normals(const lr_normals_args& a, hipStream_t s);
+void launch_depth_normals_backward(const lr_normals_args& a, hipStream_t s);
+void launch_normal_loss_forward(const lr_normals_args& a, hipStream_t s);
+void launch_normal_loss_backward(const lr_normals_args& a, hipStream_t s);
+
 // video frames on the device (video.hip)
 size_t video_workspace_bytes(int n_frames);
 void launch_frames_u8(int n, int HW, const float* images, uint8_t* out, hipStream_t s);
