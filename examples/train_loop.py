@@ -20,7 +20,7 @@ a perturbed subset of it.  Prints the loss every `--log` iterations and the time
                                   [--mcmc --cap-max 150000]
                                   [--multi-view 4 --depth-weight 0.1 [--depth-loss pearson]]
                                   [--filter3d [--antialiasing]]
-                                  [--normal-weight 0.05] [--normal-consistency 0.05]
+                                  [--normal-weight 0.05] [--normal-consistency 0.05] [--distortion-weight 100]
 
 --multi-view K: the loop body is ONE multi-view step (parallel.ViewBatch: forward, L1 + DSSIM loss and backward of K views in one
 C call, gradients summed) followed by Adam; the densification statistics are formed inside the step, per view
@@ -42,6 +42,9 @@ every iteration.  No gradient threshold and no densification statistics are invo
 the depth gradient on (config.set_depth_gradient).  --normal-consistency W: the forward also returns the median depth
 (return_median=True) and normals.normal_consistency(depth, median_depth) with weight W is added; the median's side of it moves
 the means only.  The multi-view step has no normal term of its own: a caller reaches it through ViewBatch(grad_depths=).
+
+--distortion-weight W (single-view loop): the forward also returns the depth distortion (return_distortion=True: Mip-NeRF 360's
+distortion loss as 2DGS uses it, on the "ndc" mapping) and W x its mean over the image is added to the loss.
 
 --filter3d: in either loop the rasterizer is shown the cloud through luciddreamer_amd.filter3d.filtered(model, filter): every
 Gaussian low-passed by the highest sampling rate at which a training camera sees it (the 3D smoothing filter of Mip-Splatting).
@@ -276,10 +279,13 @@ def train_multi_view(args, log=print):
 
 def train(args, log=print):
     normal_w, consistency_w = getattr(args, "normal_weight", 0.0), getattr(args, "normal_consistency", 0.0)
+    distortion_w = getattr(args, "distortion_weight", 0.0)
     if getattr(args, "multi_view", 0) > 0:
         if normal_w > 0 or consistency_w > 0:
             raise SystemExit("--normal-weight / --normal-consistency: the single-view loop only (the multi-view step takes an "
                              "external depth term through ViewBatch(grad_depths=))")
+        if distortion_w > 0:
+            raise SystemExit("--distortion-weight: the single-view loop only (the multi-view step has no distortion term)")
         return train_multi_view(args, log)
     dev = torch.device("cuda:0")
     model, cams, targets = build(args, dev)
@@ -300,12 +306,15 @@ def train(args, log=print):
     t0 = time.perf_counter()
     for it in range(1, args.iters + 1):
         v = int(torch.randint(0, len(cams), (1,), generator=gen))
-        pkg = render_raw(cams[v], f3.view(model), bg_color=bg, return_median=consistency_w > 0)    # luciddreamer.py:296
+        pkg = render_raw(cams[v], f3.view(model), bg_color=bg, return_median=consistency_w > 0,    # luciddreamer.py:296
+                         return_distortion=distortion_w > 0)
         loss = l1_dssim_loss(pkg["render"], targets[v], args.lambda_dssim)                # :301-303
         if normal_w > 0:
             loss = loss + normal_loss(pkg["depth"], normal_targets[v], cams[v], weight=normal_w)
         if consistency_w > 0:
             loss = loss + normal_consistency(pkg["depth"], pkg["median_depth"], cams[v], weight=consistency_w)
+        if distortion_w > 0:
+            loss = loss + distortion_w * pkg["distortion"].mean()
         loss.backward()                                                                   # :304
         with torch.no_grad():
             vis, radii = pkg["visibility_filter"], pkg["radii"]
@@ -340,7 +349,7 @@ def default_args(**kw):
     d = dict(gaussians=200_000, iters=300, resolution="512x512", views=12, lambda_dssim=0.2, log=50, densify_from=100,
              densify_every=100, densify_until=10_000, exact=False, torch_adam=False, antialiasing=False, absgrad=False,
              densify_grad_threshold=0.0002, multi_view=0, mcmc=False, cap_max=0, depth_weight=0.0, depth_loss="l1", filter3d=False,
-             normal_weight=0.0, normal_consistency=0.0)
+             normal_weight=0.0, normal_consistency=0.0, distortion_weight=0.0)
     d.update(kw)
     return SimpleNamespace(**d)
 
@@ -363,6 +372,8 @@ HELP = {
                      "(normals.normal_loss) with this weight; turns the depth gradient on",
     "normal_consistency": "single-view loop: > 0 adds normals.normal_consistency(depth, median_depth) with this weight "
                           "(return_median=True); the median's side moves the means only",
+    "distortion_weight": "single-view loop: > 0 adds W x the mean depth distortion of the view (return_distortion=True, the "
+                         "\"ndc\" mapping of 2DGS): pulls the layers a ray blends together in depth",
     "densify_grad_threshold": "clone / split threshold on the accumulated view-space gradient norm (reference: 0.0002).  Summed "
                               "magnitudes are larger than the signed norm: with --absgrad use about 4x (0.0008)",
 }

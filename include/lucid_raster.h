@@ -392,6 +392,83 @@ int lr_render_median(const lr_median_args* a);
 int lr_median_backward(const lr_median_backward_args* a);
 
 /*
+ * Depth distortion of a forward (Mip-NeRF 360's distortion loss, as 2DGS and gsplat's `distloss` use it), from its three scratch
+ * buffers; a pass of its own behind the forward, whose kernels are not changed by it.
+ *
+ * Definition.  For one pixel, walk its tile's list front to back exactly as the blend forward and lr_render_median do, T = 1 at the
+ * start: power > 0 -> skip; alpha = min(0.99, opacity exp(power)), alpha < 1/255 -> skip; test_T = T (1 - alpha), test_T < 1e-4 ->
+ * stop, not blended; otherwise the entry is blended with weight w_i = alpha_i T_i, then T = test_T.  Each blended layer has a mapped
+ * depth m_i = map_c0 + map_c1 z_i + map_c2 / z_i, z_i the Gaussian's view-space depth (the per-Gaussian value the expected depth
+ * blends).  Two mappings in use: 2DGS's far / (far - near) (1 - near / z), i.e. (c0, c1, c2) = (far / (far - near), 0,
+ * -far near / (far - near)), and the linear one, (0, 1, 0).  The distortion of the pixel is
+ *     D = sum_i w_i sum_{j<i} w_j (m_i - m_j)^2 = sum_i w_i (mt_i^2 A_{i-1} + M2_{i-1} - 2 mt_i M1_{i-1}),
+ * A, M1, M2 the running sums of w, w mt and w mt^2, mt_i = m_i - m_ref, m_ref the mapped depth of the pixel's first blended layer
+ * (D depends on differences only; the shift keeps the float32 moments from cancelling).
+ *   out_distortion [1,H,W] float32: D >= 0; exactly 0 for a pixel with fewer than two blended layers.
+ *   out_moments    [H,W,4] float32: {A, M1, M2, m_ref} per pixel, what lr_distortion_backward needs of this pass.
+ * The values hold under strict parity (lr_tune_set("strict"), which must be what the forward ran under), anti-aliasing, the 3D
+ * filter, raw and activated parameters and both forward shapes, as lr_render_median's do: the T sequence is the forward's bit for
+ * bit.  Exact and async mode (binning_capacity: the value the forward was given); an async view that overflowed its binning buffer
+ * writes zeros (rc 0; lr_check reports the overflow), as does P = 0, without reading a buffer.  width x height below 2^31.
+ *
+ * lr_distortion_backward: the gradient of out_distortion for the upstream dL_ddistortion [1,H,W], with `distortion` and `moments`
+ * what lr_render_distortion wrote for the same buffers and the same three coefficients.  With g = dL/dD and the pixel's totals:
+ *     q_i = dD/dw_i = mt_i^2 A - 2 mt_i M1 + M2,   dD/dm_i = 2 w_i (mt_i A - M1),
+ *     dD/dalpha_i = T_i q_i - S_i / (1 - alpha_i),  S_i = sum_{k>i} w_k q_k = 2 D - sum_{k<=i} w_k q_k  (taken front to back).
+ * The conventions of the colour path hold: the 0.99 clamp of alpha is not differentiated; the skips, the stop, the sort order and
+ * m_ref are constants.  alpha = opacity G reaches dL_dmean2D, dL_dconic, dL_dopacity and through them the mean, scales, rotations
+ * and cov3D; dL/dz_i = g dD/dm_i (map_c1 - map_c2 / z_i^2) reaches dL_dmean3D (raw: dL/dxyz) through the view matrix's z row.
+ * Colours and SH get nothing: dL_dcolor, dL_dsh and dL_dsh_rest may be NULL and are never added to; given in write mode they are
+ * zero-filled.  The other outputs, their units, accumulate_mask (LR_ACC_*, LR_ACC_NO_ZERO_FILL) and the alignment rule are
+ * lr_backward_args'; `view` is the forward's (its shs / colors_precomp are not read).  Order: the per-tile kernel, the zero-fill of
+ * rows in write mode, the depth-mode per-Gaussian backward.  The per-tile kernel OVERWRITES the per-instance gradient slots of the
+ * binning buffer: the call runs after the colour backward (lr_view_backward) of the same forward state, on the same stream or
+ * ordered behind it, and before another forward reuses the buffers.  An overflowed async view adds nothing.  No global float
+ * atomics: bit-repeatable.  Not part of lr_views_accumulate.
+ */
+typedef struct lr_distortion_args {
+    size_t struct_bytes;                     /* = sizeof(lr_distortion_args); anything else is LR_ERR_INVALID_ARG */
+    const char* geom_buffer;
+    const char* binning_buffer;
+    const char* image_buffer;
+    int P, width, height;
+    long long binning_capacity;              /* the value the forward was given */
+    float map_c0, map_c1, map_c2;            /* m = map_c0 + map_c1 z + map_c2 / z */
+    float* out_distortion;
+    float* out_moments;
+    void* stream;
+} lr_distortion_args;
+
+typedef struct lr_distortion_backward_args {
+    size_t struct_bytes;                     /* = sizeof(lr_distortion_backward_args); anything else is LR_ERR_INVALID_ARG */
+    lr_view view;
+    char* geom_buffer;
+    char* binning_buffer;
+    char* image_buffer;
+    long long binning_capacity;
+    const float* dL_ddistortion;
+    const float* moments;
+    const float* distortion;
+    float map_c0, map_c1, map_c2;
+    /* gradient outputs, as lr_backward_args */
+    float* dL_dmean2D;
+    float* dL_dconic;
+    float* dL_dopacity;
+    float* dL_dcolor;
+    float* dL_dmean3D;
+    float* dL_dcov3D;
+    float* dL_dsh;
+    float* dL_dsh_rest;
+    float* dL_dscale;
+    float* dL_drot;
+    unsigned int accumulate_mask;
+    void* stream;
+} lr_distortion_backward_args;
+
+int lr_render_distortion(const lr_distortion_args* a);
+int lr_distortion_backward(const lr_distortion_backward_args* a);
+
+/*
  * Multi-view step (new; the reference renders one view per Python iteration, luciddreamer.py:291-304).
  * lr_views_accumulate runs lr_forward + the backward for n_views views of ONE parameter set and ACCUMULATES the gradients
  * into the acc_* buffers.  Everything is enqueued from C in one call: views alternate over up to 4 chains (forward of view

@@ -163,6 +163,92 @@ def median_backward(geomBuffer, binningBuffer, imageBuffer, radii, median_ids, d
     return out
 
 
+distortion_map_coefficients = _lib_check.distortion_map_coefficients
+
+
+def render_distortion(geomBuffer, binningBuffer, imageBuffer, P, image_height, image_width, *, distortion_map="ndc",
+                      binning_capacity=0):
+    """(distortion (1, H, W), moments (H, W, 4)) float32 of the forward that left the three buffers (lr_render_distortion, on the
+    current stream): the depth distortion of each pixel's blended layers for the mapped depth of `distortion_map`
+    (distortion_map_coefficients), and the per-pixel sums distortion_backward needs.  No autograd."""
+    import torch
+    H, W = int(image_height), int(image_width)
+    dev = imageBuffer.device
+    c0, c1, c2 = distortion_map_coefficients(distortion_map)
+    dist = torch.empty((1, H, W), dtype=torch.float32, device=dev)
+    mom = torch.empty((H, W, 4), dtype=torch.float32, device=dev)
+    a = _lib_check.DistortionArgs(geom_buffer=geomBuffer.data_ptr(), binning_buffer=binningBuffer.data_ptr(),
+                                  image_buffer=imageBuffer.data_ptr(), P=int(P), width=W, height=H,
+                                  binning_capacity=int(binning_capacity), map_c0=c0, map_c1=c1, map_c2=c2,
+                                  out_distortion=dist.data_ptr(), out_moments=mom.data_ptr(),
+                                  stream=torch.cuda.current_stream(dev).cuda_stream)
+    with _lib_check.on_device(dev):
+        rc = _lib_check.lib().lr_render_distortion(a)
+    if rc < 0:
+        _lib_check.raise_for(rc, "render_distortion")
+    return dist, mom
+
+
+def distortion_backward(geomBuffer, binningBuffer, imageBuffer, dL_ddistortion, distortion, moments, rs, *, means3D,
+                        opacities=None, scales=None, rotations=None, cov3D_precomp=None, raw=False, distortion_map="ndc", binning_capacity=0,
+                        accumulate_into=None):
+    """The distortion's gradient (lr_distortion_backward, on the current stream, behind the colour backward of the same forward).
+    rs: the forward's raster settings; means3D .. cov3D_precomp: its inputs (raw=True: the stored xyz, opacity, scaling, rotation;
+    the opacities are read in raw mode only, for the sigmoid's derivative).
+    accumulate_into: {"means2D", "opacity", "means3D", "scales", "rotations", "cov3D": contiguous float32 tensor or None} -- a
+    given tensor is ADDED to in place (rows of Gaussians that own a tile instance; the others stay untouched), a missing one is
+    a new tensor written in full.  Returns the dict of the six (None for the representation not in use)."""
+    import torch
+    dev = imageBuffer.device
+    P = int(means3D.shape[0])
+    H, W = int(rs.image_height), int(rs.image_width)
+    c0, c1, c2 = distortion_map_coefficients(distortion_map)
+    present = lambda t: t is not None and t.numel() != 0
+    cont = lambda t: t.detach().contiguous().float()
+    keep = [cont(dL_ddistortion), cont(distortion), cont(moments), cont(rs.viewmatrix), cont(rs.projmatrix), cont(rs.campos),
+            cont(means3D), cont(opacities) if opacities is not None else None]
+    dL, dist, mom, view, proj, campos, m3, op = keep
+    if raw and op is None:
+        raise RuntimeError("distortion_backward: raw mode needs the stored opacities")
+    if dL.numel() != H * W or dist.numel() != H * W or mom.numel() != 4 * H * W:
+        raise RuntimeError("distortion_backward: dL_ddistortion, distortion and moments must be (1, H, W), (1, H, W), (H, W, 4)")
+    sc = cont(scales) if present(scales) else None
+    rot = cont(rotations) if present(rotations) else None
+    cov = cont(cov3D_precomp) if present(cov3D_precomp) else None
+    shapes = {"means2D": (P, 3), "opacity": (P, 1), "means3D": (P, 3), "scales": (P, 3) if sc is not None else None,
+              "rotations": (P, 4) if rot is not None else None, "cov3D": (P, 6) if cov is not None else None}
+    bits = {"means2D": 0, "opacity": 2, "means3D": 4, "cov3D": 5, "scales": 7, "rotations": 8}
+    out, mask = {}, 0
+    for name, shape in shapes.items():
+        t = (accumulate_into or {}).get(name)
+        if shape is None:
+            out[name] = None
+        elif t is not None:
+            if not t.is_contiguous() or t.dtype != torch.float32 or t.numel() != int(torch.Size(shape).numel()):
+                raise RuntimeError(f"distortion_backward: accumulate_into[{name!r}] must be a contiguous float32 tensor of {shape}")
+            out[name] = t
+            mask |= 1 << bits[name]
+        else:
+            out[name] = torch.empty(shape, dtype=torch.float32, device=dev)
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    v = _lib_check.View(P=P, D=0, M=1, raw=1 if raw else 0, width=W, height=H, means3D=m3.data_ptr(), opacities=ptr(op),
+                        scales=ptr(sc), scale_modifier=float(rs.scale_modifier), rotations=ptr(rot), cov3D_precomp=ptr(cov),
+                        viewmatrix=view.data_ptr(), projmatrix=proj.data_ptr(), campos=campos.data_ptr(),
+                        tan_fovx=float(rs.tanfovx), tan_fovy=float(rs.tanfovy))
+    a = _lib_check.DistortionBackwardArgs(
+        view=v, geom_buffer=geomBuffer.data_ptr(), binning_buffer=binningBuffer.data_ptr(), image_buffer=imageBuffer.data_ptr(),
+        binning_capacity=int(binning_capacity), dL_ddistortion=dL.data_ptr(), moments=mom.data_ptr(), distortion=dist.data_ptr(),
+        map_c0=c0, map_c1=c1, map_c2=c2, dL_dmean2D=ptr(out["means2D"]), dL_dopacity=ptr(out["opacity"]),
+        dL_dmean3D=ptr(out["means3D"]), dL_dcov3D=ptr(out["cov3D"]), dL_dscale=ptr(out["scales"]), dL_drot=ptr(out["rotations"]),
+        accumulate_mask=mask, stream=torch.cuda.current_stream(dev).cuda_stream)
+    with _lib_check.on_device(dev):
+        rc = _lib_check.lib().lr_distortion_backward(a)
+    if rc < 0:
+        _lib_check.raise_for(rc, "distortion_backward")
+    del keep
+    return out
+
+
 # forward + backward of one view in one call for a caller that holds dL/dcolor up front; [] = an input does not qualify
 rasterize_view_step = _C_ext.rasterize_view_step
 last_num_rendered = _C_ext.last_num_rendered

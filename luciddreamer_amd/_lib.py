@@ -28,6 +28,7 @@ _lock = threading.Lock()
 
 EXPORTS = ("lr_last_error", "lr_version", "lr_geom_bytes", "lr_img_bytes", "lr_binning_bytes", "lr_forward",
            "lr_backward", "lr_view_forward", "lr_view_backward", "lr_render_alpha", "lr_render_median", "lr_median_backward",
+           "lr_render_distortion", "lr_distortion_backward",
            "lr_mark_visible", "lr_check",
            "lr_dist2_workspace_bytes", "lr_dist2",
            "lr_dist2_workspace_layout",
@@ -147,6 +148,51 @@ class MedianBackwardArgs(ctypes.Structure):
 
     def __init__(self, **fields):
         super().__init__(struct_bytes=ctypes.sizeof(MedianBackwardArgs), **fields)
+
+
+class DistortionArgs(ctypes.Structure):
+    """lr_distortion_args, field for field (tests/test_distort_cpu.py compares the offsets with the host compiler's)."""
+    _vp, _ci, _cf = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
+    _fields_ = [("struct_bytes", ctypes.c_size_t), ("geom_buffer", _vp), ("binning_buffer", _vp), ("image_buffer", _vp),
+                ("P", _ci), ("width", _ci), ("height", _ci), ("binning_capacity", ctypes.c_longlong),
+                ("map_c0", _cf), ("map_c1", _cf), ("map_c2", _cf),
+                ("out_distortion", _vp), ("out_moments", _vp), ("stream", _vp)]
+
+    def __init__(self, **fields):
+        super().__init__(struct_bytes=ctypes.sizeof(DistortionArgs), **fields)
+
+
+class DistortionBackwardArgs(ctypes.Structure):
+    """lr_distortion_backward_args, field for field."""
+    _vp, _ci, _cf = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
+    _fields_ = [("struct_bytes", ctypes.c_size_t), ("view", View),
+                ("geom_buffer", _vp), ("binning_buffer", _vp), ("image_buffer", _vp), ("binning_capacity", ctypes.c_longlong),
+                ("dL_ddistortion", _vp), ("moments", _vp), ("distortion", _vp),
+                ("map_c0", _cf), ("map_c1", _cf), ("map_c2", _cf),
+                ("dL_dmean2D", _vp), ("dL_dconic", _vp), ("dL_dopacity", _vp), ("dL_dcolor", _vp), ("dL_dmean3D", _vp),
+                ("dL_dcov3D", _vp), ("dL_dsh", _vp), ("dL_dsh_rest", _vp), ("dL_dscale", _vp), ("dL_drot", _vp),
+                ("accumulate_mask", ctypes.c_uint), ("stream", _vp)]
+
+    def __init__(self, **fields):
+        super().__init__(struct_bytes=ctypes.sizeof(DistortionBackwardArgs), **fields)
+
+
+def distortion_map_coefficients(distortion_map):
+    """(c0, c1, c2) of the mapped depth m = c0 + c1 z + c2 / z (include/lucid_raster.h) for "ndc" (2DGS's
+    far / (far - near) (1 - near / z) with near = 0.2, far = 100), ("ndc", near, far), "linear" (m = z), or three numbers."""
+    m = distortion_map
+    if m == "linear":
+        return 0.0, 1.0, 0.0
+    if m == "ndc":
+        m = ("ndc", 0.2, 100.0)
+    if isinstance(m, (tuple, list)) and len(m) == 3 and m[0] == "ndc":
+        near, far = float(m[1]), float(m[2])
+        if not 0.0 < near < far:
+            raise ValueError("distortion_map: need 0 < near < far")
+        return far / (far - near), 0.0, -far * near / (far - near)
+    if isinstance(m, (tuple, list)) and len(m) == 3 and all(isinstance(c, (int, float)) for c in m):
+        return tuple(float(c) for c in m)
+    raise ValueError('distortion_map must be "ndc", ("ndc", near, far), "linear" or three coefficients')
 
 
 class McmcRelocateArgs(ctypes.Structure):
@@ -281,6 +327,10 @@ def lib():
         L.lr_render_median.argtypes = [ctypes.POINTER(MedianArgs)]
         L.lr_median_backward.restype = ci
         L.lr_median_backward.argtypes = [ctypes.POINTER(MedianBackwardArgs)]
+        L.lr_render_distortion.restype = ci
+        L.lr_render_distortion.argtypes = [ctypes.POINTER(DistortionArgs)]
+        L.lr_distortion_backward.restype = ci
+        L.lr_distortion_backward.argtypes = [ctypes.POINTER(DistortionBackwardArgs)]
         L.lr_mark_visible.restype = ci
         L.lr_mark_visible.argtypes = [ci, vp, vp, vp, vp, vp]
         L.lr_check.restype = ci

@@ -29,6 +29,7 @@ SOURCES = {
     "render_fwd.hip": ["-fno-slp-vectorize"],
     "render_bwd.hip": ["-fno-slp-vectorize"],
     "render_median.hip": ["-fno-slp-vectorize"],     # median depth / ids pass and its gather backward: the forward's alpha arithmetic
+    "render_distort.hip": ["-fno-slp-vectorize"],    # depth distortion pass and its backward: the forward's alpha arithmetic again
     "gauss_bwd.hip": [],
     "knn.hip": [],
     # the separable window sums are long fma chains: packed f32 costs two issue slots plus the moves that form the pairs

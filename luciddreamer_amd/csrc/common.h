@@ -491,6 +491,14 @@ void launch_render_median(int W, int H, int P, const GeomView& g, const ImgView&
 // accumulate: the rows of emitting Gaussians are added to, else written (the caller zero-fills the others)
 void launch_median_bwd(int W, int H, int P, const GeomView& g, const int* radii, const int* ids, const float* dL_dmedian,
                        const float* view, float* dL_dmean3D, bool accumulate, hipStream_t s);
+// depth distortion [H*W] and its moments image [H*W][4] of a finished forward, for the mapped depth m = c0 + c1 z + c2 / z, and the
+// distortion's gradient as one GradRec per instance in inst_grad (render_distort.hip: definition, kernels).  g: rec, header; im:
+// ranges; bin_base: the binning buffer, whose offsets the kernels resolve themselves.  P <= 0: zeros without reading a buffer
+// (forward), nothing (backward).
+void launch_render_distort(int W, int H, int P, const GeomView& g, const ImgView& im, const char* bin_base, float c0, float c1,
+                           float c2, float* out_distortion, float* out_moments, hipStream_t s);
+void launch_distort_bwd(int W, int H, int P, const GeomView& g, const ImgView& im, char* bin_base, const float* dL_ddistortion,
+                        const float* distortion, const float* moments, float c0, float c1, float c2, hipStream_t s);
 // The upstream gradients a view's backward is given.
 struct ViewGrads {
     const float* color;     // dL_dpix [3,H,W]

@@ -13,6 +13,11 @@ that Gaussian's row (-1 where there is none; not differentiable) -- lr_render_me
 depth it never lies between a foreground and a background surface.  Its gradient reaches means3D / xyz only (the selection is a
 constant; nothing flows to opacity, covariance or colour): a weaker signal than the expected depth's, enough for loss.depth_l1 /
 loss.depth_pearson on the median depth.
+return_distortion=True (same three entry points) appends distortion (1, H, W) LAST, behind alpha and the median pair: the depth distortion
+of the pixel's blended layers (Mip-NeRF 360 / 2DGS / gsplat's `distloss`), D = sum_i w_i sum_{j<i} w_j (m_i - m_j)^2 with w_i the blend
+weights and m_i the mapped depth of `distortion_map` -- "ndc" (default; ("ndc", near, far), 2DGS's far / (far - near) (1 - near / z) with
+near = 0.2, far = 100) or "linear" (m = z) -- lr_render_distortion, a pass behind the forward.  Differentiable: a gradient reaching it runs
+lr_distortion_backward behind the view's backward and reaches means3D / xyz, opacities, scales, rotations (cov3D) and means2D.
 config.set_absgrad(True): the backward of a view attaches `means2D.absgrad` [P,3] (AbsGS; lr_view_backward with dL_dmean2D_abs) to the means2D
 tensor the caller passed.
 
@@ -107,11 +112,23 @@ def _median_outputs(ctx, P, rs, geom, binning, img, capacity):
     return median_depth, median_ids
 
 
+def _distortion_outputs(ctx, P, rs, geom, binning, img, capacity, distortion_map):
+    """(distortion,) of the forward whose buffers are given, as _median_outputs; the backward needs the moments image, the value
+    (detached: the output itself on ctx would be a reference cycle) and the mapping."""
+    distortion, moments = _C.render_distortion(geom, binning, img, P, rs.image_height, rs.image_width,
+                                               distortion_map=distortion_map, binning_capacity=capacity)
+    ctx.distortion = (distortion.detach(), moments, distortion_map)
+    return (distortion,)
+
+
 def _more_grads(ctx, grad_more):
-    """(grad_alpha, grad_median) from the gradients behind (color, radii, depth): [alpha], [median_depth, median_ids]."""
+    """(grad_alpha, grad_median, grad_distortion) from the gradients behind (color, radii, depth): [alpha], [median_depth,
+    median_ids], [distortion]."""
+    tail = 1 if ctx.distortion is not None else 0
     grad_alpha = grad_more[0] if ctx.return_alpha else None
-    grad_median = grad_more[-2] if ctx.median_ids is not None else None
-    return grad_alpha, grad_median
+    grad_median = grad_more[-2 - tail] if ctx.median_ids is not None else None
+    grad_distortion = grad_more[-1] if tail else None
+    return grad_alpha, grad_median, grad_distortion
 
 
 def _median_backward(ctx, grad_median, grad_means3D, fused_grad, radii, geom, binning, img):
@@ -124,12 +141,26 @@ def _median_backward(ctx, grad_median, grad_means3D, fused_grad, radii, geom, bi
     return grad_means3D
 
 
+def _distortion_backward(ctx, grad_distortion, returned, fused, geom, binning, img, **inputs):
+    """The distortion's term of every geometric gradient (lr_distortion_backward), added behind the view's backward on the same
+    stream: per tensor into what that backward returned, or, where it accumulated into the leaf's .grad in place (returned None),
+    into that .grad -- the same additions in the same order either way.  returned / fused: {name: tensor or None} under the names of
+    _C.distortion_backward.  Returns `returned` (an input neither of them covers gets the term alone)."""
+    fused = fused or {}
+    targets = {k: (t if t is not None else fused.get(k)) for k, t in returned.items()}
+    value, moments, distortion_map = ctx.distortion
+    out = _C.distortion_backward(geom, binning, img, grad_distortion, value, moments, ctx.raster_settings,
+                                 distortion_map=distortion_map, binning_capacity=ctx.binning_capacity, accumulate_into=targets,
+                                 **inputs)
+    return {k: (t if (t is not None or fused.get(k) is not None) else out[k]) for k, t in returned.items()}
+
+
 class _RasterizeGaussians(torch.autograd.Function):
     """forward/backward wiring of RAST/.../__init__.py:44-156."""
 
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                raster_settings, return_alpha=False, return_median=False):
+                raster_settings, return_alpha=False, return_median=False, return_distortion=False, distortion_map="ndc"):
         rs = raster_settings
         args = (rs.bg, means3D, colors_precomp, opacities, scales, rotations, rs.scale_modifier, cov3Ds_precomp,
                 rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, rs.image_height, rs.image_width, sh,
@@ -160,7 +191,8 @@ class _RasterizeGaussians(torch.autograd.Function):
         ctx.save_for_backward(colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geom, binning, img)
         ctx.return_alpha = bool(return_alpha)
         ctx.median_ids = None
-        if not return_alpha and not return_median:
+        ctx.distortion = None
+        if not return_alpha and not return_median and not return_distortion:
             return color, radii, depth
         # the alpha output, from the image state of the forward returned above (after a re-render, the re-render's); the
         # backward needs that state's final T only -- the alpha tensor itself is not kept (see depth_image above)
@@ -170,11 +202,13 @@ class _RasterizeGaussians(torch.autograd.Function):
             out += (_C.render_alpha(img, rs.image_height, rs.image_width),)
         if return_median:
             out += _median_outputs(ctx, means3D.shape[0], rs, geom, binning, img, capacity)
+        if return_distortion:
+            out += _distortion_outputs(ctx, means3D.shape[0], rs, geom, binning, img, capacity, distortion_map)
         return out
 
     @staticmethod
     def backward(ctx, grad_out_color, grad_radii, grad_depth, *grad_more):
-        grad_alpha, grad_median = _more_grads(ctx, grad_more)
+        grad_alpha, grad_median, grad_distortion = _more_grads(ctx, grad_more)
         config.require_antialiasing(ctx.antialiasing)   # before anything is launched or written
         rs = ctx.raster_settings
         colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geom, binning, img = ctx.saved_tensors
@@ -198,6 +232,17 @@ class _RasterizeGaussians(torch.autograd.Function):
             if grad_median is not None:
                 grad_means3D = _median_backward(ctx, grad_median, grad_means3D, (accumulate_into or {}).get("means3D"),
                                                 radii, geom, binning, img)
+            if grad_distortion is not None:
+                fused = accumulate_into or {}
+                d = _distortion_backward(
+                    ctx, grad_distortion,
+                    dict(means2D=grad_means2D, opacity=grad_opacities, means3D=grad_means3D, scales=grad_scales,
+                         rotations=grad_rotations, cov3D=grad_cov3Ds_precomp),
+                    {k: fused.get(k) for k in ("means2D", "opacity", "means3D", "scales", "rotations", "cov3D")},
+                    geom, binning, img, means3D=means3D, scales=scales, rotations=rotations,
+                    cov3D_precomp=cov3Ds_precomp)
+                grad_means2D, grad_opacities, grad_means3D = d["means2D"], d["opacity"], d["means3D"]
+                grad_scales, grad_rotations, grad_cov3Ds_precomp = d["scales"], d["rotations"], d["cov3D"]
         except Exception:
             if rs.debug:
                 _snapshot(args, "snapshot_bw.dump")
@@ -205,11 +250,11 @@ class _RasterizeGaussians(torch.autograd.Function):
             raise
         # order of the forward inputs (RAST/.../__init__.py:144-154); gradients of absent inputs are None-able
         return (grad_means3D, grad_means2D, grad_sh, grad_colors_precomp, grad_opacities, grad_scales, grad_rotations,
-                grad_cov3Ds_precomp, None, None, None)
+                grad_cov3Ds_precomp, None, None, None, None, None)
 
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                        raster_settings, return_alpha=False, return_median=False):
+                        raster_settings, return_alpha=False, return_median=False, return_distortion=False, distortion_map="ndc"):
     """The operator.  Its autograd node is compiled (csrc/torch_ext.cpp RasterizeFn: forward and backward run without the
     interpreter -- the Python node below cost more host time per 1080p view than the GPU needs for it); with settings.debug
     the Python node runs instead, because it is the one that writes the reference's snapshot_fw.dump / snapshot_bw.dump.
@@ -220,11 +265,15 @@ def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales,
     the one-call rasterize_view_step route: the interpreter's share of a view (the node's forward and backward, plus two ctypes
     calls and two small launches) is paid per call, which at 1080p is more host time than the GPU needs for the view.  Unused
     median outputs leave the backward exactly as it is without them; a gradient reaching median_depth adds its term to the
-    gradient of means3D, with config.set_fused_grad_accumulation on or off."""
+    gradient of means3D, with config.set_fused_grad_accumulation on or off.
+    return_distortion: the outputs gain distortion (1, H, W) as their LAST entry (module docstring), for the mapped depth of
+    distortion_map.  As return_median it always runs the Python node; an unused distortion output leaves the backward exactly as it
+    is, a gradient reaching it runs lr_distortion_backward behind the view's backward, fused accumulation on or off."""
     rs = raster_settings
-    if rs.debug or return_median:
+    if rs.debug or return_median or return_distortion:
         return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
-                                         cov3Ds_precomp, rs, bool(return_alpha), bool(return_median))
+                                         cov3Ds_precomp, rs, bool(return_alpha), bool(return_median), bool(return_distortion),
+                                         distortion_map)
     capacity = config.capacity_for(means3D, rs)
     fused = config.fused_grad_accumulation()
     offered = config.offered_grad_output()
@@ -264,7 +313,7 @@ class _RasterizeGaussiansRaw(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, xyz, means2D, features_dc, features_rest, opacity, scaling, rotation, raster_settings, return_alpha=False,
-                return_median=False):
+                return_median=False, return_distortion=False, distortion_map="ndc"):
         rs = raster_settings
         ctx.antialiasing = config.antialiasing()        # as _RasterizeGaussians
         ctx.absgrad_to = means2D if config.absgrad() else None
@@ -287,7 +336,8 @@ class _RasterizeGaussiansRaw(torch.autograd.Function):
         ctx.save_for_backward(xyz, features_dc, features_rest, opacity, scaling, rotation, radii, geom, binning, img)
         ctx.return_alpha = bool(return_alpha)
         ctx.median_ids = None
-        if not return_alpha and not return_median:
+        ctx.distortion = None
+        if not return_alpha and not return_median and not return_distortion:
             return color, radii, depth
         ctx.set_materialize_grads(False)                # as _RasterizeGaussians
         out = (color, radii, depth)
@@ -295,11 +345,13 @@ class _RasterizeGaussiansRaw(torch.autograd.Function):
             out += (_C.render_alpha(img, rs.image_height, rs.image_width),)
         if return_median:
             out += _median_outputs(ctx, xyz.shape[0], rs, geom, binning, img, capacity)
+        if return_distortion:
+            out += _distortion_outputs(ctx, xyz.shape[0], rs, geom, binning, img, capacity, distortion_map)
         return out
 
     @staticmethod
     def backward(ctx, grad_out_color, grad_radii, grad_depth, *grad_more):
-        grad_alpha, grad_median = _more_grads(ctx, grad_more)
+        grad_alpha, grad_median, grad_distortion = _more_grads(ctx, grad_more)
         config.require_antialiasing(ctx.antialiasing)   # before anything is launched or written
         rs = ctx.raster_settings
         xyz, features_dc, features_rest, opacity, scaling, rotation, radii, geom, binning, img = ctx.saved_tensors
@@ -331,8 +383,12 @@ class _RasterizeGaussiansRaw(torch.autograd.Function):
                 ctx.absgrad_to.absgrad = g[7]
             if grad_median is not None:                 # the rows it adds to are rows the view visited
                 _median_backward(ctx, grad_median, g[1], None, radii, geom, binning, img)
+            if grad_distortion is not None:             # likewise, before the step reads the rows
+                _distortion_backward(ctx, grad_distortion, dict(means2D=g[0], opacity=g[4], means3D=g[1], scales=g[5], rotations=g[6]),
+                                     None, geom, binning, img, means3D=xyz, opacities=opacity, scales=scaling, rotations=rotation,
+                                     raw=True)
             opt.apply_armed_step(geom, [xyz, features_dc, features_rest, opacity, scaling, rotation], list(g[1:7]))
-            return None, g[0], None, None, None, None, None, None, None, None
+            return None, g[0], None, None, None, None, None, None, None, None, None, None
         g = _C.rasterize_gaussians_raw_backward(
             rs.bg, xyz, radii, features_dc, features_rest, opacity, scaling, rotation, rs.scale_modifier, rs.viewmatrix,
             rs.projmatrix, rs.tanfovx, rs.tanfovy, grad_out_color, rs.sh_degree, rs.campos, geom, ctx.num_rendered,
@@ -342,16 +398,26 @@ class _RasterizeGaussiansRaw(torch.autograd.Function):
         g_means2D, g_xyz, g_dc, g_rest, g_op, g_sc, g_rot = g[:7]
         if grad_median is not None:
             g_xyz = _median_backward(ctx, grad_median, g_xyz, (accumulate_into or {}).get("xyz"), radii, geom, binning, img)
-        return g_xyz, g_means2D, g_dc, g_rest, g_op, g_sc, g_rot, None, None, None
+        if grad_distortion is not None:
+            fused = accumulate_into or {}
+            d = _distortion_backward(ctx, grad_distortion, dict(means2D=g_means2D, opacity=g_op, means3D=g_xyz, scales=g_sc, rotations=g_rot),
+                                     dict(means2D=fused.get("means2D"), opacity=fused.get("opacity"), means3D=fused.get("xyz"),
+                                          scales=fused.get("scaling"), rotations=fused.get("rotation")),
+                                     geom, binning, img, means3D=xyz, opacities=opacity, scales=scaling, rotations=rotation, raw=True)
+            g_means2D, g_op, g_xyz, g_sc, g_rot = d["means2D"], d["opacity"], d["means3D"], d["scales"], d["rotations"]
+        return g_xyz, g_means2D, g_dc, g_rest, g_op, g_sc, g_rot, None, None, None, None, None
 
 
 def rasterize_gaussians_raw(xyz, means2D, features_dc, features_rest, opacity, scaling, rotation, raster_settings,
-                            return_alpha=False, return_median=False):
+                            return_alpha=False, return_median=False, return_distortion=False, distortion_map="ndc"):
     """(color, radii, depth) from the stored GaussianModel parameters (pre-activation), see _RasterizeGaussiansRaw;
     return_alpha: (color, radii, depth, alpha) as rasterize_gaussians; return_median: (median_depth, median_ids) behind them, as
-    rasterize_gaussians (this entry point always runs its Python node); the median depth's gradient reaches xyz."""
+    rasterize_gaussians (this entry point always runs its Python node); the median depth's gradient reaches xyz;
+    return_distortion / distortion_map: distortion last, as rasterize_gaussians; its gradient reaches xyz, opacity, scaling and
+    rotation."""
     return _RasterizeGaussiansRaw.apply(xyz, means2D, features_dc, features_rest, opacity, scaling, rotation,
-                                        raster_settings, bool(return_alpha), bool(return_median))
+                                        raster_settings, bool(return_alpha), bool(return_median), bool(return_distortion),
+                                        distortion_map)
 
 
 _EMPTY = torch.Tensor([])           # never written: one instance serves every call (three constructions per call were ~6 us)
@@ -369,9 +435,10 @@ class GaussianRasterizer(nn.Module):
             return _C.mark_visible(positions, rs.viewmatrix, rs.projmatrix)
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
-                cov3D_precomp=None, return_alpha=False, return_median=False):
+                cov3D_precomp=None, return_alpha=False, return_median=False, return_distortion=False, distortion_map="ndc"):
         """(color, radii, depth), or with return_alpha=True (color, radii, depth, alpha): alpha (1, H, W) = 1 - T_final; with
-        return_median=True the outputs gain (median_depth, median_ids) at their end (rasterize_gaussians)."""
+        return_median=True the outputs gain (median_depth, median_ids) at their end, with return_distortion=True the distortion
+        (1, H, W) of distortion_map's mapped depth behind those (rasterize_gaussians)."""
         rs = self.raster_settings
         if (shs is None) == (colors_precomp is None):
             raise Exception('Please provide excatly one of either SHs or precomputed colors!')
@@ -386,8 +453,9 @@ class GaussianRasterizer(nn.Module):
         scales = empty if scales is None else scales
         rotations = empty if rotations is None else rotations
         cov3D_precomp = empty if cov3D_precomp is None else cov3D_precomp
-        if return_alpha or return_median:
+        if return_alpha or return_median or return_distortion:
             return rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
-                                       cov3D_precomp, rs, return_alpha=return_alpha, return_median=return_median)
+                                       cov3D_precomp, rs, return_alpha=return_alpha, return_median=return_median,
+                                       return_distortion=return_distortion, distortion_map=distortion_map)
         return rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
                                    cov3D_precomp, rs)
