@@ -114,6 +114,25 @@ rasterize_autograd = _C_ext.rasterize_autograd
 render_alpha = _C_ext.render_alpha
 
 
+def _forward_state(geomBuffer, binningBuffer, imageBuffer, binning_capacity, dev, P=None, W=None, H=None):
+    """The fields every argument struct of a pass behind a finished forward shares: its three buffers, the capacity it ran under, the
+    current stream of `dev`, and (where the struct has no lr_view of its own) P, width, height."""
+    import torch
+    f = dict(geom_buffer=geomBuffer.data_ptr(), binning_buffer=binningBuffer.data_ptr(), image_buffer=imageBuffer.data_ptr(),
+             binning_capacity=int(binning_capacity), stream=torch.cuda.current_stream(dev).cuda_stream)
+    if P is not None:
+        f.update(P=int(P), width=int(W), height=int(H))
+    return f
+
+
+def _call(entry, args, dev, who):
+    """lib().<entry>(args) with `dev` current; a refusal raises as `who`."""
+    with _lib_check.on_device(dev):
+        rc = getattr(_lib_check.lib(), entry)(args)
+    if rc < 0:
+        _lib_check.raise_for(rc, who)
+
+
 def render_median(geomBuffer, binningBuffer, imageBuffer, P, image_height, image_width, *, binning_capacity=0, want_ids=True):
     """(median_depth (1, H, W) float32, median_ids (H, W) int32 or None) of the forward that left the three buffers
     (lr_render_median, on the current stream): the view-space depth and the row of the Gaussian at which each pixel's
@@ -123,14 +142,9 @@ def render_median(geomBuffer, binningBuffer, imageBuffer, P, image_height, image
     dev = imageBuffer.device
     depth = torch.empty((1, H, W), dtype=torch.float32, device=dev)
     ids = torch.empty((H, W), dtype=torch.int32, device=dev) if want_ids else None
-    a = _lib_check.MedianArgs(geom_buffer=geomBuffer.data_ptr(), binning_buffer=binningBuffer.data_ptr(),
-                              image_buffer=imageBuffer.data_ptr(), P=int(P), width=W, height=H,
-                              binning_capacity=int(binning_capacity), out_median_depth=depth.data_ptr(),
-                              out_ids=ids.data_ptr() if want_ids else None, stream=torch.cuda.current_stream(dev).cuda_stream)
-    with _lib_check.on_device(dev):
-        rc = _lib_check.lib().lr_render_median(a)
-    if rc < 0:
-        _lib_check.raise_for(rc, "render_median")
+    a = _lib_check.MedianArgs(out_median_depth=depth.data_ptr(), out_ids=ids.data_ptr() if want_ids else None,
+                              **_forward_state(geomBuffer, binningBuffer, imageBuffer, binning_capacity, dev, P, W, H))
+    _call("lr_render_median", a, dev, "render_median")
     return depth, ids
 
 
@@ -150,16 +164,11 @@ def median_backward(geomBuffer, binningBuffer, imageBuffer, radii, median_ids, d
     view = viewmatrix.contiguous().float()
     if dL.numel() != H * W:
         raise RuntimeError("median_backward: dL_dmedian must have H x W elements")
-    a = _lib_check.MedianBackwardArgs(geom_buffer=geomBuffer.data_ptr(), binning_buffer=binningBuffer.data_ptr(),
-                                      image_buffer=imageBuffer.data_ptr(), P=int(P), width=int(W), height=int(H),
-                                      binning_capacity=int(binning_capacity), radii=radii.data_ptr(), ids=median_ids.data_ptr(),
-                                      dL_dmedian=dL.data_ptr(), viewmatrix=view.data_ptr(), dL_dmean3D=out.data_ptr(),
+    a = _lib_check.MedianBackwardArgs(radii=radii.data_ptr(), ids=median_ids.data_ptr(), dL_dmedian=dL.data_ptr(),
+                                      viewmatrix=view.data_ptr(), dL_dmean3D=out.data_ptr(),
                                       accumulate=1 if accumulate_into is not None else 0,
-                                      stream=torch.cuda.current_stream(dev).cuda_stream)
-    with _lib_check.on_device(dev):
-        rc = _lib_check.lib().lr_median_backward(a)
-    if rc < 0:
-        _lib_check.raise_for(rc, "median_backward")
+                                      **_forward_state(geomBuffer, binningBuffer, imageBuffer, binning_capacity, dev, P, W, H))
+    _call("lr_median_backward", a, dev, "median_backward")
     return out
 
 
@@ -177,15 +186,9 @@ def render_distortion(geomBuffer, binningBuffer, imageBuffer, P, image_height, i
     c0, c1, c2 = distortion_map_coefficients(distortion_map)
     dist = torch.empty((1, H, W), dtype=torch.float32, device=dev)
     mom = torch.empty((H, W, 4), dtype=torch.float32, device=dev)
-    a = _lib_check.DistortionArgs(geom_buffer=geomBuffer.data_ptr(), binning_buffer=binningBuffer.data_ptr(),
-                                  image_buffer=imageBuffer.data_ptr(), P=int(P), width=W, height=H,
-                                  binning_capacity=int(binning_capacity), map_c0=c0, map_c1=c1, map_c2=c2,
-                                  out_distortion=dist.data_ptr(), out_moments=mom.data_ptr(),
-                                  stream=torch.cuda.current_stream(dev).cuda_stream)
-    with _lib_check.on_device(dev):
-        rc = _lib_check.lib().lr_render_distortion(a)
-    if rc < 0:
-        _lib_check.raise_for(rc, "render_distortion")
+    a = _lib_check.DistortionArgs(map_c0=c0, map_c1=c1, map_c2=c2, out_distortion=dist.data_ptr(), out_moments=mom.data_ptr(),
+                                  **_forward_state(geomBuffer, binningBuffer, imageBuffer, binning_capacity, dev, P, W, H))
+    _call("lr_render_distortion", a, dev, "render_distortion")
     return dist, mom
 
 
@@ -236,15 +239,11 @@ def distortion_backward(geomBuffer, binningBuffer, imageBuffer, dL_ddistortion, 
                         viewmatrix=view.data_ptr(), projmatrix=proj.data_ptr(), campos=campos.data_ptr(),
                         tan_fovx=float(rs.tanfovx), tan_fovy=float(rs.tanfovy))
     a = _lib_check.DistortionBackwardArgs(
-        view=v, geom_buffer=geomBuffer.data_ptr(), binning_buffer=binningBuffer.data_ptr(), image_buffer=imageBuffer.data_ptr(),
-        binning_capacity=int(binning_capacity), dL_ddistortion=dL.data_ptr(), moments=mom.data_ptr(), distortion=dist.data_ptr(),
-        map_c0=c0, map_c1=c1, map_c2=c2, dL_dmean2D=ptr(out["means2D"]), dL_dopacity=ptr(out["opacity"]),
-        dL_dmean3D=ptr(out["means3D"]), dL_dcov3D=ptr(out["cov3D"]), dL_dscale=ptr(out["scales"]), dL_drot=ptr(out["rotations"]),
-        accumulate_mask=mask, stream=torch.cuda.current_stream(dev).cuda_stream)
-    with _lib_check.on_device(dev):
-        rc = _lib_check.lib().lr_distortion_backward(a)
-    if rc < 0:
-        _lib_check.raise_for(rc, "distortion_backward")
+        view=v, dL_ddistortion=dL.data_ptr(), moments=mom.data_ptr(), distortion=dist.data_ptr(), map_c0=c0, map_c1=c1, map_c2=c2,
+        dL_dmean2D=ptr(out["means2D"]), dL_dopacity=ptr(out["opacity"]), dL_dmean3D=ptr(out["means3D"]), dL_dcov3D=ptr(out["cov3D"]),
+        dL_dscale=ptr(out["scales"]), dL_drot=ptr(out["rotations"]), accumulate_mask=mask,
+        **_forward_state(geomBuffer, binningBuffer, imageBuffer, binning_capacity, dev))
+    _call("lr_distortion_backward", a, dev, "distortion_backward")
     del keep
     return out
 

@@ -24,6 +24,7 @@
 #include <cstdlib>
 #include "common.h"
 #include "dispatch_flags.h"
+#include "wave_reduce.h"
 
 namespace lr {
 
@@ -37,46 +38,7 @@ constexpr int BATCH2 = 64;          // staged Gaussians per round of the 2-wave 
 // threads per workgroup: 128 (2 wave64), or 256 with QUAD (one 8x8 quadrant per wave, one pixel per lane, as in the
 // forward; chosen for small images by blend_quad below)
 
-template <int CTRL, int ROW_MASK = 0xf>
-__device__ __forceinline__ float dpp(float v)
-{
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, ROW_MASK, 0xf, false));
-}
-// sum within each 16-lane row; every lane of the row ends with the row total
-__device__ __forceinline__ float row_sum(float v)
-{
-    v += dpp<0xB1>(v);
-    v += dpp<0x4E>(v);
-    v += dpp<0x141>(v);
-    v += dpp<0x140>(v);
-    return v;
-}
-// (inline asm below: with ROCm 7.2 hipcc, __builtin_amdgcn_permlane32_swap followed by r[0] + r[1] returned 2 * r[0] --
-//  verified on hardware)
-// Reduce eight per-lane terms over the wave down to 16-lane rows: on return row r of `a0` holds the row partials of term
-// {a0, a2, a1, a3}[r] and row r of `b0` those of {b0, b2, b1, b3}[r]; a row_sum of each finishes the job.  One asm block so
-// that the six swaps share two hazard waits instead of paying one each (VALU write -> v_permlane*_swap read needs two
-// wait states, swap -> VALU read one; every dependent pair below has that many instructions in between):
-//   4 x [x <- (lanes<32: x[l] + x[l+32]) | (lanes>=32: y[l-32] + y[l])]   then   2 x the same over 16-lane rows
-__device__ __forceinline__ void reduce8(float& a0, float a1, float a2, float a3, float& b0, float b1, float b2, float b3)
-{
-    asm volatile("s_nop 1\n\t"
-                 "v_permlane32_swap_b32 %0, %1\n\t"
-                 "v_permlane32_swap_b32 %2, %3\n\t"
-                 "v_permlane32_swap_b32 %4, %5\n\t"
-                 "v_permlane32_swap_b32 %6, %7\n\t"
-                 "v_add_f32 %0, %0, %1\n\t"
-                 "v_add_f32 %2, %2, %3\n\t"
-                 "v_add_f32 %4, %4, %5\n\t"
-                 "v_add_f32 %6, %6, %7\n\t"
-                 "v_permlane16_swap_b32 %0, %2\n\t"
-                 "s_nop 0\n\t"
-                 "v_permlane16_swap_b32 %4, %6\n\t"
-                 "v_add_f32 %0, %0, %2\n\t"
-                 "v_add_f32 %4, %4, %6\n\t"
-                 "s_nop 1"                                  // whatever follows may be a DPP read of %0 / %4 (two wait states)
-                 : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+v"(b0), "+v"(b1), "+v"(b2), "+v"(b3));
-}
+// dpp / row_sum / reduce8: wave_reduce.h
 // Finish the wave reduction inside the 16-lane rows with the terms kept TRANSPOSED: instead of three independent row sums
 // (4 DPP adds each: every level adds a register to a shifted copy of itself and all sixteen lanes end up with the same
 // total), each level hands one half of the lanes to another term -- a DPP add under a bank mask writes only the lanes it

@@ -28,26 +28,25 @@
 // slot's free float, which the depth-mode per-Gaussian backward (k_gauss_bwd_depth) takes to the mean.
 //
 // A pass of its own behind the forward, as lr_render_alpha and lr_render_median: the hand-scheduled blend pair stays as it is.
-// k_render_distort: the quadrant shape of k_render_median -- one 256-thread workgroup per tile through blend_tile, a wave per 8x8
-// quadrant, a lane per pixel, 256 list entries staged per round with m_i formed once per staged entry, box_hit as the cull, alpha
-// by gauss_row / gauss_weight<STRICT> on the forward's staged coefficients: its T sequence is the forward's under both forward
-// shapes.  Unlike the median pass it needs the 1e-4 stop.
-// k_distort_bwd: one workgroup per tile over the whole list (as depth mode), the same walk with the per-pixel terms above; the
+// k_render_distort: the quadrant walk of tile_walk.h (shape, staging, cull and alpha arithmetic are there), 256 list entries per
+// round, the value kept per staged entry the mapped depth m_i, formed once per entry: its T sequence is the forward's under both
+// forward shapes.  Unlike the median pass it needs the 1e-4 stop.
+// k_distort_bwd: one workgroup per tile over the whole list (as depth mode), the same walk written out (tile_walk.h says why), 128
+// entries per round with dm/dz in the slopes plane and the emission index beside it, with the per-pixel terms above; the
 // seven sums of a list entry (D dx, D dy, D dx^2, D dx dy, D dy^2, D, dz with D = opacity G dL/dalpha) are reduced over the 64
-// pixels of a wave with the blend backward's lane swaps and row sums, stored per wave in LDS and added in wave order by the flush,
-// which writes ONE plain 48-byte GradRec per instance -- {mean2D x, y, conic a, b | conic c, opacity, 0, 0 | 0, dz, 0, 0} in the blend
+// pixels of a wave with the blend backward's lane swaps and row sums (wave_reduce.h), stored per wave in LDS and added in wave
+// order by the flush, which writes ONE plain 48-byte GradRec per instance -- {mean2D x, y, conic a, b | conic c, opacity, 0, 0 | 0, dz, 0, 0} in the blend
 // backward's units, exact zeros for an entry no pixel blended, every slot of every list position written.  No global float atomics:
 // bit-repeatable.  It OVERWRITES inst_grad: it runs after the colour backward of the same forward state and before another forward
 // reuses the buffers.
 #include "common.h"
-#include "dispatch_flags.h"
+#include "tile_walk.h"
+#include "wave_reduce.h"
 
 namespace lr {
 
 namespace {
 
-constexpr int DST_THREADS = 256;        // 4 wave64 per tile
-constexpr int DST_WAVES = DST_THREADS / 64;
 constexpr int DST_BATCH = 256;          // forward: staged list entries per round (10 KB of LDS)
 constexpr int DSB_BATCH = 128;          // backward: staged list entries per round (6.5 KB + 16 KB of per-wave accumulators)
 constexpr int DSB_COLS = 8;             // sums per entry and wave: D dx, D dy, D dx^2, D dx dy, D dy^2, D, dz, -
@@ -60,100 +59,48 @@ __device__ __forceinline__ float dst_map(float c0, float c1, float c2, float z)
 }
 
 template <bool STRICT>
-__global__ void __launch_bounds__(DST_THREADS)
+__global__ void __launch_bounds__(WALK_THREADS)
 k_render_distort(int W, int H, int gx, int num_tiles, int tile_map, const uint2* __restrict__ ranges,
                  const char* __restrict__ bin_base, const GaussRec* __restrict__ rec, const GeomHeader* __restrict__ hdr,
                  float c0, float c1, float c2, float* __restrict__ out_dist, float4* __restrict__ out_mom)
 {
-    __shared__ float4 s_q0[DST_BATCH];      // x, y, Ap, Bp (x log2 e; strict: conic a, b)           -- as k_render_fwd
-    __shared__ float4 s_q1[DST_BATCH];      // Cp (strict: conic c), opacity, mapped depth m, qmax (cull threshold)
-    __shared__ float2 s_q3[DST_BATCH];      // -b/c, -b/a (edge minimiser slopes for box_hit)
-    __shared__ int s_wdone[DST_WAVES];
+    __shared__ float4 s_q0[DST_BATCH];      // WalkPlanes; the value kept in s_q1[].z: mapped depth m
+    __shared__ float4 s_q1[DST_BATCH];
+    __shared__ float2 s_q3[DST_BATCH];
+    __shared__ int s_wdone[WALK_WAVES];
 
     const int tile = blend_tile(tile_map, num_tiles);
     if (tile < 0) return;
-    const int tx = tile % gx, ty = tile / gx;
-    const int tid = threadIdx.x, w = tid >> 6, l = tid & 63;
-    const int x0 = tx * TILE_X + (w & 1) * 8, y0 = ty * TILE_Y + (w >> 1) * 8;
-    const int px = x0 + (l & 7), py = y0 + (l >> 3);
-    const bool inside = px < W && py < H;
-    const float pxf = (float)px, pyf = (float)py;
-    const float bx0 = (float)x0, bx1 = (float)(x0 + 7), by0 = (float)y0, by1 = (float)(y0 + 7);
-
-    // an overflowed view's list is truncated: no distortion anywhere (wave-uniform: no barrier is skipped by part of a workgroup)
-    const uint2 range = hdr->overflow != 0u ? make_uint2(0u, 0u) : ranges[tile];
-    const int total = (int)(range.y - range.x);
-    const uint32_t* __restrict__ list_gid =
-        reinterpret_cast<const uint32_t*>(bin_base + bin_layout((long long)hdr->bin_bound).list_gid) + range.x;
+    const QuadLane q = quad_lane(tile, gx, W, H);
+    const TileList tl = tile_list(hdr, ranges, bin_base, tile);     // overflowed: empty, no distortion anywhere
 
     float T = 1.0f, A = 0.0f, M1 = 0.0f, M2 = 0.0f, D = 0.0f, mref = 0.0f;
-    uint64_t done = __builtin_amdgcn_ballot_w64(!inside);             // pixels that have stopped (or lie outside the image)
-    bool wave_done = done == ~0ull;
+    uint64_t done = __builtin_amdgcn_ballot_w64(!q.inside);           // pixels that have stopped (or lie outside the image)
 
-    for (int base = 0; base < total; base += DST_BATCH) {
-        if (l == 0) s_wdone[w] = wave_done ? 1 : 0;
-        lds_barrier();                                                // (also protects the planes of the previous round)
-        if (s_wdone[0] + s_wdone[1] + s_wdone[2] + s_wdone[3] == DST_WAVES) break;
-        const int cnt = min(DST_BATCH, total - base);
-        if (tid < cnt) {
-            const uint32_t id = list_gid[base + tid];
-            const float4* g = reinterpret_cast<const float4*>(rec + id);
-            const float4 a = g[0], b = g[1], c = g[2];
-            const float m = dst_map(c0, c1, c2, c.y);
-            s_q0[tid] = STRICT ? make_float4(a.x, a.y, a.z, a.w) : make_float4(a.x, a.y, (-0.5f * LOG2E) * a.z, -LOG2E * a.w);
-            s_q1[tid] = STRICT ? make_float4(b.x, b.y, m, c.z) : make_float4((-0.5f * LOG2E) * b.x, b.y, m, LOG2E * c.z);
-            s_q3[tid] = make_float2(-a.w / b.x, -a.w / a.z);
-        }
-        lds_barrier();
-        if (wave_done) continue;
-
-        for (int sb = 0; sb < cnt; sb += 64) {
-            bool hit = false;
-            const int jl = sb + l;
-            if (jl < cnt) {
-                const float4 a = s_q0[jl];
-                const float4 b = s_q1[jl];
-                const float2 r = s_q3[jl];
-                const float ca = STRICT ? a.z : -2.0f * a.z, cb = STRICT ? a.w : -a.w, cc = STRICT ? b.x : -2.0f * b.x;
-                hit = box_hit(a.x, a.y, ca, cb, cc, r.x, r.y, b.w, bx0, bx1, by0, by1);
+    tile_walk<STRICT, DST_BATCH>(
+        q, tl, rec, WalkPlanes{s_q0, s_q1, s_q3, s_wdone}, done,
+        [&](int, uint32_t, float z) { return dst_map(c0, c1, c2, z); },
+        [&](int, float m, float alpha, uint64_t use) {
+            const float test_T = T * (1.0f - alpha);
+            const uint64_t stop = use & __builtin_amdgcn_ballot_w64(test_T < 0.0001f);
+            if (__builtin_amdgcn_inverse_ballot_w64(use & ~stop)) {
+                const float wt = alpha * T;
+                if (A == 0.0f) mref = m;                              // the first blended layer (every weight is > 0)
+                const float mt = m - mref;
+                const float qq = fmaxf(0.0f, __builtin_fmaf(mt, __builtin_fmaf(mt, A, -2.0f * M1), M2));
+                D = __builtin_fmaf(wt, qq, D);
+                const float wm = wt * mt;
+                A += wt;
+                M1 += wm;
+                M2 = __builtin_fmaf(wm, mt, M2);
+                T = test_T;
             }
-            uint64_t mask = __ballot(hit);
-            while (mask) {
-                const int k = __ffsll((long long)mask) - 1;
-                mask &= mask - 1;
-                const int j = sb + k;
-                const float4 a = s_q0[j];
-                const float4 b = s_q1[j];
-                float r0, r1, power;
-                gauss_row<STRICT>(a.w, b.x, a.y - pyf, r0, r1);
-                const float alpha = fminf(0.99f, b.y * gauss_weight<STRICT>(a.z, a.w, b.x, r0, r1, a.x - pxf, power));
-                const float test_T = T * (1.0f - alpha);
-                // the forward's order of tests
-                const uint64_t use = ~done & __builtin_amdgcn_ballot_w64(power <= 0.0f) & __builtin_amdgcn_ballot_w64(alpha >= 1.0f / 255.0f);
-                const uint64_t stop = use & __builtin_amdgcn_ballot_w64(test_T < 0.0001f);
-                if (__builtin_amdgcn_inverse_ballot_w64(use & ~stop)) {
-                    const float wt = alpha * T;
-                    if (A == 0.0f) mref = b.z;                        // the first blended layer (every weight is > 0)
-                    const float mt = b.z - mref;
-                    const float q = fmaxf(0.0f, __builtin_fmaf(mt, __builtin_fmaf(mt, A, -2.0f * M1), M2));
-                    D = __builtin_fmaf(wt, q, D);
-                    const float wm = wt * mt;
-                    A += wt;
-                    M1 += wm;
-                    M2 = __builtin_fmaf(wm, mt, M2);
-                    T = test_T;
-                }
-                if (stop != 0ull) {
-                    done |= stop;
-                    if (done == ~0ull) break;
-                }
-            }
-            if (done == ~0ull) { wave_done = true; break; }
-        }
-    }
+            return stop;
+        },
+        [](int, float, uint64_t) {});
 
-    if (inside) {
-        const size_t pix = (size_t)py * W + px;
+    if (q.inside) {
+        const size_t pix = (size_t)q.py * W + q.px;
         out_dist[pix] = D;
         out_mom[pix] = make_float4(A, M1, M2, mref);
     }
@@ -170,44 +117,6 @@ __global__ void __launch_bounds__(256) k_distort_fill(long long n, float* __rest
 }
 
 // ---- backward ------------------------------------------------------------------------------------------------------------------
-// The wave reduction of the blend backward (render_bwd.hip reduce8 / row_sum, restated: that file's kernels stay as they are).
-template <int CTRL>
-__device__ __forceinline__ float dst_dpp(float v)
-{
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, false));
-}
-// sum within each 16-lane row; every lane of the row ends with the row total
-__device__ __forceinline__ float dst_row_sum(float v)
-{
-    v += dst_dpp<0xB1>(v);
-    v += dst_dpp<0x4E>(v);
-    v += dst_dpp<0x141>(v);
-    v += dst_dpp<0x140>(v);
-    return v;
-}
-// Eight per-lane terms over the wave down to 16-lane rows: on return row r of `a0` holds the row partials of term
-// {a0, a2, a1, a3}[r] and row r of `b0` those of {b0, b2, b1, b3}[r].  One asm block, wait states by hand (VALU write ->
-// v_permlane*_swap read: two, swap -> VALU read: one; whatever follows may be a DPP read: two).
-__device__ __forceinline__ void dst_reduce8(float& a0, float a1, float a2, float a3, float& b0, float b1, float b2, float b3)
-{
-    asm volatile("s_nop 1\n\t"
-                 "v_permlane32_swap_b32 %0, %1\n\t"
-                 "v_permlane32_swap_b32 %2, %3\n\t"
-                 "v_permlane32_swap_b32 %4, %5\n\t"
-                 "v_permlane32_swap_b32 %6, %7\n\t"
-                 "v_add_f32 %0, %0, %1\n\t"
-                 "v_add_f32 %2, %2, %3\n\t"
-                 "v_add_f32 %4, %4, %5\n\t"
-                 "v_add_f32 %6, %6, %7\n\t"
-                 "v_permlane16_swap_b32 %0, %2\n\t"
-                 "s_nop 0\n\t"
-                 "v_permlane16_swap_b32 %4, %6\n\t"
-                 "v_add_f32 %0, %0, %2\n\t"
-                 "v_add_f32 %4, %4, %6\n\t"
-                 "s_nop 1"
-                 : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+v"(b0), "+v"(b1), "+v"(b2), "+v"(b3));
-}
-
 __device__ __forceinline__ void dst_zero_slot(float4* __restrict__ inst_grad, uint32_t e)
 {
     float4* slot = inst_grad + 3 * (size_t)e;
@@ -216,7 +125,7 @@ __device__ __forceinline__ void dst_zero_slot(float4* __restrict__ inst_grad, ui
 
 // Launch bounds: at most 128 VGPRs, so that with 22.6 KB of LDS four workgroups fit a CU (the issue's floor is two).
 template <bool STRICT>
-__global__ void __launch_bounds__(DST_THREADS) __attribute__((amdgpu_waves_per_eu(4, 8)))
+__global__ void __launch_bounds__(WALK_THREADS) __attribute__((amdgpu_waves_per_eu(4, 8)))
 k_distort_bwd(int W, int H, int gx, int num_tiles, int tile_map, const uint2* __restrict__ ranges, char* __restrict__ bin_base,
               const GaussRec* __restrict__ rec, const GeomHeader* __restrict__ hdr, const float* __restrict__ dL_ddist,
               const float* __restrict__ dist, const float4* __restrict__ mom, float c0, float c1, float c2)
@@ -225,8 +134,8 @@ k_distort_bwd(int W, int H, int gx, int num_tiles, int tile_map, const uint2* __
     __shared__ float4 s_q1[DSB_BATCH];      // Cp (strict: conic c), opacity, mapped depth m, qmax
     __shared__ float4 s_q2[DSB_BATCH];      // -b/c, -b/a, dm/dz = c1 - c2 / z^2, -
     __shared__ uint32_t s_id[DSB_BATCH];    // emission index (instance slot) of each staged entry
-    __shared__ float s_acc[DSB_BATCH][DST_WAVES][DSB_COLS];   // every wave its own copy: plain stores, summed in wave order
-    __shared__ int s_wdone[DST_WAVES];
+    __shared__ float s_acc[DSB_BATCH][WALK_WAVES][DSB_COLS];   // every wave its own copy: plain stores, summed in wave order
+    __shared__ int s_wdone[WALK_WAVES];
 
     const int tile = blend_tile(tile_map, num_tiles);
     if (tile < 0) return;
@@ -234,13 +143,10 @@ k_distort_bwd(int W, int H, int gx, int num_tiles, int tile_map, const uint2* __
     const uint2 range = ranges[tile];
     const int total = (int)(range.y - range.x);
     if (total == 0) return;
-    const int tx = tile % gx, ty = tile / gx;
-    const int tid = threadIdx.x, w = tid >> 6, l = tid & 63;
-    const int x0 = tx * TILE_X + (w & 1) * 8, y0 = ty * TILE_Y + (w >> 1) * 8;
-    const int px = x0 + (l & 7), py = y0 + (l >> 3);
-    const bool inside = px < W && py < H;
-    const float pxf = (float)px, pyf = (float)py;
-    const float bx0 = (float)x0, bx1 = (float)(x0 + 7), by0 = (float)y0, by1 = (float)(y0 + 7);
+    const QuadLane q = quad_lane(tile, gx, W, H);
+    const int tid = q.tid, w = q.w, l = q.l, px = q.px, py = q.py;
+    const bool inside = q.inside;
+    const float pxf = q.pxf, pyf = q.pyf, bx0 = q.bx0, bx1 = q.bx1, by0 = q.by0, by1 = q.by1;
 
     const BinLayout BL = bin_layout((long long)hdr->bin_bound);
     const uint32_t* __restrict__ point_list = reinterpret_cast<const uint32_t*>(bin_base + BL.point_list) + range.x;
@@ -262,15 +168,15 @@ k_distort_bwd(int W, int H, int gx, int num_tiles, int tile_map, const uint2* __
     const float ddelx_dx = (float)(0.5 * W), ddely_dy = (float)(0.5 * H);    // the NDC scale of dL/dmean2D (render_bwd.hip)
 
     const int row = l >> 4;
-    const int col_a = (row == 0) ? 0 : (row == 1) ? 2 : (row == 2) ? 1 : 3;  // dst_reduce8: rows hold terms {0, 2, 1, 3}
+    const int col_a = (row == 0) ? 0 : (row == 1) ? 2 : (row == 2) ? 1 : 3;  // reduce8: rows hold terms {0, 2, 1, 3}
     const bool row_leader = (l & 15) == 0;
 
     for (int base = 0; base < total; base += DSB_BATCH) {
         if (l == 0) s_wdone[w] = wave_done ? 1 : 0;
         lds_barrier();                                                // (previous round fully flushed)
-        if (s_wdone[0] + s_wdone[1] + s_wdone[2] + s_wdone[3] == DST_WAVES) {
+        if (s_wdone[0] + s_wdone[1] + s_wdone[2] + s_wdone[3] == WALK_WAVES) {
             // every pixel of the tile has stopped: the rest of the list was blended by nobody, its slots read as zero
-            for (int p = base + tid; p < total; p += DST_THREADS) dst_zero_slot(inst_grad, point_list[p]);
+            for (int p = base + tid; p < total; p += WALK_THREADS) dst_zero_slot(inst_grad, point_list[p]);
             break;
         }
         const int cnt = min(DSB_BATCH, total - base);
@@ -286,8 +192,8 @@ k_distort_bwd(int W, int H, int gx, int num_tiles, int tile_map, const uint2* __
         }
         {
             float4* z4 = reinterpret_cast<float4*>(&s_acc[0][0][0]);
-            const int n4 = cnt * (DST_WAVES * DSB_COLS / 4);
-            for (int i = tid; i < n4; i += DST_THREADS) z4[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+            const int n4 = cnt * (WALK_WAVES * DSB_COLS / 4);
+            for (int i = tid; i < n4; i += WALK_THREADS) z4[i] = make_float4(0.f, 0.f, 0.f, 0.f);
         }
         lds_barrier();
 
@@ -336,9 +242,9 @@ k_distort_bwd(int W, int H, int gx, int num_tiles, int tile_map, const uint2* __
                         T = bl ? test_T : T;
                         const float mx = dop * dx, my = dop * dy;
                         float ra = mx, rb = my * dy;
-                        dst_reduce8(ra, my, mx * dx, mx * dy, rb, dop, zt, 0.0f);
-                        ra = dst_row_sum(ra);
-                        rb = dst_row_sum(rb);
+                        reduce8(ra, my, mx * dx, mx * dy, rb, dop, zt, 0.0f);
+                        ra = row_sum(ra);
+                        rb = row_sum(rb);
                         if (row_leader) {
                             float* dst = &s_acc[j][w][col_a];
                             dst[0] = ra;
@@ -357,7 +263,7 @@ k_distort_bwd(int W, int H, int gx, int num_tiles, int tile_map, const uint2* __
             for (int k = 0; k < DSB_COLS; k++) {
                 float v = s_acc[tid][0][k];
 #pragma unroll
-                for (int a = 1; a < DST_WAVES; a++) v += s_acc[tid][a][k];                  // fixed order over the waves
+                for (int a = 1; a < WALK_WAVES; a++) v += s_acc[tid][a][k];                  // fixed order over the waves
                 a8[k] = v;
             }
             // the factors that are constant per Gaussian, as the blend backward's flush applies them
@@ -379,19 +285,16 @@ k_distort_bwd(int W, int H, int gx, int num_tiles, int tile_map, const uint2* __
 void launch_render_distort(int W, int H, int P, const GeomView& g, const ImgView& im, const char* bin_base, float c0, float c1,
                            float c2, float* out_distortion, float* out_moments, hipStream_t s)
 {
-    const int gx = (W + TILE_X - 1) / TILE_X, gy = (H + TILE_Y - 1) / TILE_Y;
-    const int num_tiles = gx * gy;
-    if (num_tiles <= 0) return;
+    const TileGrid t = tile_grid(W, H);
+    if (t.num_tiles <= 0) return;
     float4* mom = reinterpret_cast<float4*>(out_moments);
     if (P <= 0) {                                                     // the forward of an empty cloud wrote no header and no list
         const long long n = (long long)W * H;
         hipLaunchKernelGGL(k_distort_fill, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, n, out_distortion, mom);
         return;
     }
-    const int tile_map = blend_tile_map(num_tiles);
-    const int grid = ((num_tiles + 7) / 8) * 8;
-    dispatch_flags<1>(flag_bits(tune_get(TUNE_STRICT) > 0), [&](auto st) {
-        hipLaunchKernelGGL((k_render_distort<st.value>), dim3(grid), dim3(DST_THREADS), 0, s, W, H, gx, num_tiles, tile_map,
+    dispatch_strict([&](auto st) {
+        hipLaunchKernelGGL((k_render_distort<st.value>), dim3(t.grid), dim3(WALK_THREADS), 0, s, W, H, t.gx, t.num_tiles, t.tile_map,
                            im.ranges, bin_base, g.rec, g.header, c0, c1, c2, out_distortion, mom);
     });
 }
@@ -399,14 +302,12 @@ void launch_render_distort(int W, int H, int P, const GeomView& g, const ImgView
 void launch_distort_bwd(int W, int H, int P, const GeomView& g, const ImgView& im, char* bin_base, const float* dL_ddistortion,
                         const float* distortion, const float* moments, float c0, float c1, float c2, hipStream_t s)
 {
-    const int gx = (W + TILE_X - 1) / TILE_X, gy = (H + TILE_Y - 1) / TILE_Y;
-    const int num_tiles = gx * gy;
-    if (P <= 0 || num_tiles <= 0) return;
-    const int tile_map = blend_tile_map(num_tiles);
-    const int grid = ((num_tiles + 7) / 8) * 8;
-    dispatch_flags<1>(flag_bits(tune_get(TUNE_STRICT) > 0), [&](auto st) {
-        hipLaunchKernelGGL((k_distort_bwd<st.value>), dim3(grid), dim3(DST_THREADS), 0, s, W, H, gx, num_tiles, tile_map, im.ranges,
-                           bin_base, g.rec, g.header, dL_ddistortion, distortion, reinterpret_cast<const float4*>(moments), c0, c1, c2);
+    const TileGrid t = tile_grid(W, H);
+    if (P <= 0 || t.num_tiles <= 0) return;
+    dispatch_strict([&](auto st) {
+        hipLaunchKernelGGL((k_distort_bwd<st.value>), dim3(t.grid), dim3(WALK_THREADS), 0, s, W, H, t.gx, t.num_tiles, t.tile_map,
+                           im.ranges, bin_base, g.rec, g.header, dL_ddistortion, distortion, reinterpret_cast<const float4*>(moments), c0,
+                           c1, c2);
     });
 }
 

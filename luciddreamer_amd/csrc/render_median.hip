@@ -14,22 +14,17 @@
 // The two thresholds never interact: alpha <= 0.99, so a pixel still at T >= 0.5 has test_T >= 0.5 (1 - 0.99) > 1e-4 -- the
 // 1e-4 stop cannot trigger in front of the median, and the walk below does not test it.
 // The values hold under strict parity, anti-aliasing, the 3D filter, raw and activated parameters and both forward shapes: all of
-// that already sits in the GaussRec records and the tile lists, and the walk evaluates alpha with the gauss_row<STRICT> /
-// gauss_weight<STRICT> arithmetic of the forward that produced the state (the "strict" knob as it is at this call), on the same
-// staged coefficients, in the same order.  Its T sequence is the forward's bit for bit up to the median.
+// that already sits in the GaussRec records and the tile lists, and the walk (tile_walk.h) evaluates alpha with the arithmetic of
+// the forward that produced the state, on the same staged coefficients, in the same order.  Its T sequence is the forward's bit
+// for bit up to the median.
 //
 // A pass of its own (as lr_render_alpha): the blend-forward kernels stay as they are.  It stops at T < 0.5, far earlier than the
 // blend's T < 1e-4, and carries no colour.
 //
-// Forward, k_render_median: the quadrant shape of k_render_fwd -- one 256-thread workgroup per 16x16 tile through the same
-// blend_tile map, a wave owns one 8x8 quadrant, a lane one pixel.  A round stages what alpha needs of 256 list entries in LDS
-// (x, y, three conic terms, opacity, depth, cull threshold, the two slopes of box_hit, Gaussian id: 44 bytes each); lane l
-// culls staged entry sb + l against the wave's quadrant with box_hit (the forward's test on the forward's operands; a
-// non-candidate cannot reach alpha >= 1/255 on any pixel of the box, so skipping it is exactly a `continue` -- repeating the
-// test instead of reading the forward's quad_hits bytes keeps the pass independent of which forward shape left them), and the
-// wave walks the ballot mask in list order.  A
-// quadrant stops when every pixel of it has its median or the list ends.  The R-dependent offset of list_gid is resolved on the
-// device from GeomHeader::bin_bound, as the blend backward does; a view whose header says `overflow` writes 0 / -1 everywhere.
+// Forward, k_render_median: the quadrant walk of tile_walk.h (shape, staging, cull and alpha arithmetic are there), 256 list
+// entries per round; the value it keeps per staged entry is the view depth, and the Gaussian id is staged beside it (44 bytes per
+// entry in all).  A quadrant stops when every pixel of it has its median or the list ends; a view whose header says `overflow`
+// writes 0 / -1 everywhere.
 //
 // Gradient.  The selection of the median Gaussian is a constant (as the sort order is everywhere else), so
 //     d median_depth[p] / d z_g = 1   for g = median_ids[p], nothing else:
@@ -45,103 +40,51 @@
 // MB_WAVE_PIX pixels are summed by one wave; larger ones by a whole 1024-thread workgroup of the second kernel: wave w takes the
 // 64-pixel chunks w, w + 16, ... and the 16 partial sums are added in wave order.
 #include "common.h"
-#include "dispatch_flags.h"
+#include "tile_walk.h"
 
 namespace lr {
 
 namespace {
 
-constexpr int MED_THREADS = 256;        // 4 wave64 per tile
-constexpr int MED_WAVES = MED_THREADS / 64;
 constexpr int MED_BATCH = 256;          // staged list entries per round (11 KB of LDS)
 
 template <bool STRICT>
-__global__ void __launch_bounds__(MED_THREADS)
+__global__ void __launch_bounds__(WALK_THREADS)
 k_render_median(int W, int H, int gx, int num_tiles, int tile_map, const uint2* __restrict__ ranges,
                 const char* __restrict__ bin_base, const GaussRec* __restrict__ rec, const GeomHeader* __restrict__ hdr,
                 float* __restrict__ out_depth, int* __restrict__ out_ids)
 {
-    __shared__ float4 s_q0[MED_BATCH];      // x, y, Ap, Bp (x log2 e; strict: conic a, b)           -- as k_render_fwd
-    __shared__ float4 s_q1[MED_BATCH];      // Cp (strict: conic c), opacity, depth, qmax (cull threshold)
-    __shared__ float2 s_q3[MED_BATCH];      // -b/c, -b/a (edge minimiser slopes for box_hit)
+    __shared__ float4 s_q0[MED_BATCH];      // WalkPlanes; the value kept in s_q1[].z: view depth
+    __shared__ float4 s_q1[MED_BATCH];
+    __shared__ float2 s_q3[MED_BATCH];
     __shared__ uint32_t s_id[MED_BATCH];
-    __shared__ int s_wdone[MED_WAVES];
+    __shared__ int s_wdone[WALK_WAVES];
 
     const int tile = blend_tile(tile_map, num_tiles);
     if (tile < 0) return;
-    const int tx = tile % gx, ty = tile / gx;
-    const int tid = threadIdx.x, w = tid >> 6, l = tid & 63;
-    const int x0 = tx * TILE_X + (w & 1) * 8, y0 = ty * TILE_Y + (w >> 1) * 8;
-    const int px = x0 + (l & 7), py = y0 + (l >> 3);
-    const bool inside = px < W && py < H;
-    const float pxf = (float)px, pyf = (float)py;
-    const float bx0 = (float)x0, bx1 = (float)(x0 + 7), by0 = (float)y0, by1 = (float)(y0 + 7);
-
-    // an overflowed view's list is truncated: no median anywhere (wave-uniform: no barrier is skipped by part of a workgroup)
-    const uint2 range = hdr->overflow != 0u ? make_uint2(0u, 0u) : ranges[tile];
-    const int total = (int)(range.y - range.x);
-    const uint32_t* __restrict__ list_gid =
-        reinterpret_cast<const uint32_t*>(bin_base + bin_layout((long long)hdr->bin_bound).list_gid) + range.x;
+    const QuadLane q = quad_lane(tile, gx, W, H);
+    const TileList tl = tile_list(hdr, ranges, bin_base, tile);     // overflowed: empty, no median anywhere
 
     float T = 1.0f, med_depth = 0.0f;
     int med_id = -1;
-    uint64_t done = __builtin_amdgcn_ballot_w64(!inside);             // pixels that have their median (or lie outside the image)
-    bool wave_done = done == ~0ull;
+    uint64_t done = __builtin_amdgcn_ballot_w64(!q.inside);           // pixels that have their median (or lie outside the image)
 
-    for (int base = 0; base < total; base += MED_BATCH) {
-        if (l == 0) s_wdone[w] = wave_done ? 1 : 0;
-        lds_barrier();                                                // (also protects the planes of the previous round)
-        if (s_wdone[0] + s_wdone[1] + s_wdone[2] + s_wdone[3] == MED_WAVES) break;
-        const int cnt = min(MED_BATCH, total - base);
-        if (tid < cnt) {
-            const uint32_t id = list_gid[base + tid];
-            const float4* g = reinterpret_cast<const float4*>(rec + id);
-            const float4 a = g[0], b = g[1], c = g[2];
-            s_q0[tid] = STRICT ? make_float4(a.x, a.y, a.z, a.w) : make_float4(a.x, a.y, (-0.5f * LOG2E) * a.z, -LOG2E * a.w);
-            s_q1[tid] = STRICT ? make_float4(b.x, b.y, c.y, c.z) : make_float4((-0.5f * LOG2E) * b.x, b.y, c.y, LOG2E * c.z);
-            s_q3[tid] = make_float2(-a.w / b.x, -a.w / a.z);
-            s_id[tid] = id;
-        }
-        lds_barrier();
-        if (wave_done) continue;
+    tile_walk<STRICT, MED_BATCH>(
+        q, tl, rec, WalkPlanes{s_q0, s_q1, s_q3, s_wdone}, done,
+        [&](int slot, uint32_t id, float z) { s_id[slot] = id; return z; },
+        [&](int, float, float alpha, uint64_t use) {
+            const float test_T = T * (1.0f - alpha);
+            // the forward's T < 1e-4 stop cannot trigger while T >= 0.5 (header comment)
+            const uint64_t found = use & __builtin_amdgcn_ballot_w64(test_T < 0.5f);
+            T = __builtin_amdgcn_inverse_ballot_w64(use) ? test_T : T;
+            return found;
+        },
+        [&](int j, float z, uint64_t found) {
+            if (__builtin_amdgcn_inverse_ballot_w64(found)) { med_depth = z; med_id = (int)s_id[j]; }
+        });
 
-        for (int sb = 0; sb < cnt; sb += 64) {
-            bool hit = false;
-            const int jl = sb + l;
-            if (jl < cnt) {
-                const float4 a = s_q0[jl];
-                const float4 b = s_q1[jl];
-                const float2 r = s_q3[jl];
-                const float ca = STRICT ? a.z : -2.0f * a.z, cb = STRICT ? a.w : -a.w, cc = STRICT ? b.x : -2.0f * b.x;
-                hit = box_hit(a.x, a.y, ca, cb, cc, r.x, r.y, b.w, bx0, bx1, by0, by1);
-            }
-            uint64_t mask = __ballot(hit);
-            while (mask) {
-                const int k = __ffsll((long long)mask) - 1;
-                mask &= mask - 1;
-                const int j = sb + k;
-                const float4 a = s_q0[j];
-                const float4 b = s_q1[j];
-                float r0, r1, power;
-                gauss_row<STRICT>(a.w, b.x, a.y - pyf, r0, r1);
-                const float alpha = fminf(0.99f, b.y * gauss_weight<STRICT>(a.z, a.w, b.x, r0, r1, a.x - pxf, power));
-                const float test_T = T * (1.0f - alpha);
-                // the forward's order of tests; its T < 1e-4 stop cannot trigger while T >= 0.5 (header comment)
-                const uint64_t use = ~done & __builtin_amdgcn_ballot_w64(power <= 0.0f) & __builtin_amdgcn_ballot_w64(alpha >= 1.0f / 255.0f);
-                const uint64_t found = use & __builtin_amdgcn_ballot_w64(test_T < 0.5f);
-                T = __builtin_amdgcn_inverse_ballot_w64(use) ? test_T : T;
-                if (found != 0ull) {
-                    if (__builtin_amdgcn_inverse_ballot_w64(found)) { med_depth = b.z; med_id = (int)s_id[j]; }
-                    done |= found;
-                    if (done == ~0ull) break;
-                }
-            }
-            if (done == ~0ull) { wave_done = true; break; }
-        }
-    }
-
-    if (inside) {
-        const size_t pix = (size_t)py * W + px;
+    if (q.inside) {
+        const size_t pix = (size_t)q.py * W + q.px;
         out_depth[pix] = med_depth;
         if (out_ids != nullptr) out_ids[pix] = med_id;
     }
@@ -339,18 +282,15 @@ k_median_bwd_wide(int W, int H, int gx, int gy, const GeomHeader* __restrict__ h
 void launch_render_median(int W, int H, int P, const GeomView& g, const ImgView& im, const char* bin_base, float* out_depth,
                           int* out_ids, hipStream_t s)
 {
-    const int gx = (W + TILE_X - 1) / TILE_X, gy = (H + TILE_Y - 1) / TILE_Y;
-    const int num_tiles = gx * gy;
-    if (num_tiles <= 0) return;
+    const TileGrid t = tile_grid(W, H);
+    if (t.num_tiles <= 0) return;
     if (P <= 0) {                                                     // the forward of an empty cloud wrote no header and no list
         const long long n = (long long)W * H;
         hipLaunchKernelGGL(k_median_fill, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, n, out_depth, out_ids);
         return;
     }
-    const int tile_map = blend_tile_map(num_tiles);
-    const int grid = ((num_tiles + 7) / 8) * 8;
-    dispatch_flags<1>(flag_bits(tune_get(TUNE_STRICT) > 0), [&](auto st) {
-        hipLaunchKernelGGL((k_render_median<st.value>), dim3(grid), dim3(MED_THREADS), 0, s, W, H, gx, num_tiles, tile_map,
+    dispatch_strict([&](auto st) {
+        hipLaunchKernelGGL((k_render_median<st.value>), dim3(t.grid), dim3(WALK_THREADS), 0, s, W, H, t.gx, t.num_tiles, t.tile_map,
                            im.ranges, bin_base, g.rec, g.header, out_depth, out_ids);
     });
 }

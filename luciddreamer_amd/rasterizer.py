@@ -131,14 +131,12 @@ def _more_grads(ctx, grad_more):
     return grad_alpha, grad_median, grad_distortion
 
 
-def _median_backward(ctx, grad_median, grad_means3D, fused_grad, radii, geom, binning, img):
-    """The median depth's term of dL/dmeans3D (lr_median_backward), added behind the view's backward on the same stream: into the
-    tensor that backward returned, or, where it accumulated into the leaf's .grad in place (returned None), into that .grad --
-    the same additions in the same order either way."""
-    target = grad_means3D if grad_means3D is not None else fused_grad
+def _median_backward(ctx, grad_median, target, radii, geom, binning, img):
+    """The median depth's term of dL/dmeans3D (lr_median_backward), added behind the view's backward on the same stream into
+    `target`: the tensor that backward returned, or, where it accumulated into the leaf's .grad in place (returned None), that
+    .grad -- the same additions in the same order either way."""
     _C.median_backward(geom, binning, img, radii, ctx.median_ids, grad_median, ctx.raster_settings.viewmatrix,
                        binning_capacity=ctx.binning_capacity, accumulate_into=target)
-    return grad_means3D
 
 
 def _distortion_backward(ctx, grad_distortion, returned, fused, geom, binning, img, **inputs):
@@ -153,6 +151,41 @@ def _distortion_backward(ctx, grad_distortion, returned, fused, geom, binning, i
                                  distortion_map=distortion_map, binning_capacity=ctx.binning_capacity, accumulate_into=targets,
                                  **inputs)
     return {k: (t if (t is not None or fused.get(k) is not None) else out[k]) for k, t in returned.items()}
+
+
+def _forward_tail(ctx, out, P, rs, geom, binning, img, capacity, return_alpha, return_median, return_distortion, distortion_map):
+    """The end of both nodes' forward: `out` = (color, radii, depth) gains alpha, (median_depth, median_ids), distortion, in that
+    order, from the state of the forward whose buffers are given (after a re-render, the re-render's), and ctx what they need."""
+    ctx.return_alpha = bool(return_alpha)
+    ctx.median_ids = None
+    ctx.distortion = None
+    if not return_alpha and not return_median and not return_distortion:
+        return out
+    # the backward needs the image state's final T only -- the alpha tensor itself is not kept (as depth_image)
+    ctx.set_materialize_grads(False)            # an unused alpha / median / distortion output arrives as None: the default kernels
+    if return_alpha:
+        out += (_C.render_alpha(img, rs.image_height, rs.image_width),)
+    if return_median:
+        out += _median_outputs(ctx, P, rs, geom, binning, img, capacity)
+    if return_distortion:
+        out += _distortion_outputs(ctx, P, rs, geom, binning, img, capacity, distortion_map)
+    return out
+
+
+def _backward_extras(ctx, grad_median, grad_distortion, returned, fused, radii, geom, binning, img, **inputs):
+    """The median depth's term, then the distortion's, added behind the view's backward.  returned / fused: {name: tensor or None}
+    of what that backward returned / of the leaves' .grad it accumulated into, under _C.distortion_backward's names, as `inputs`."""
+    fused = fused or {}
+    if grad_median is not None:
+        m3 = returned["means3D"]
+        _median_backward(ctx, grad_median, m3 if m3 is not None else fused.get("means3D"), radii, geom, binning, img)
+    if grad_distortion is not None:
+        returned = _distortion_backward(ctx, grad_distortion, returned, fused, geom, binning, img, **inputs)
+    return returned
+
+
+_RAW_NAMES = dict(xyz="means3D", scaling="scales", rotation="rotations")     # the raw node's names -> _C.distortion_backward's
+_from_raw_names = lambda d: {_RAW_NAMES.get(k, k): v for k, v in (d or {}).items()}
 
 
 class _RasterizeGaussians(torch.autograd.Function):
@@ -189,22 +222,8 @@ class _RasterizeGaussians(torch.autograd.Function):
         if ctx.depth_image is not None:
             ctx.set_materialize_grads(False)        # an unused depth output arrives as None: the default kernels
         ctx.save_for_backward(colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geom, binning, img)
-        ctx.return_alpha = bool(return_alpha)
-        ctx.median_ids = None
-        ctx.distortion = None
-        if not return_alpha and not return_median and not return_distortion:
-            return color, radii, depth
-        # the alpha output, from the image state of the forward returned above (after a re-render, the re-render's); the
-        # backward needs that state's final T only -- the alpha tensor itself is not kept (see depth_image above)
-        ctx.set_materialize_grads(False)            # an unused alpha / median output arrives as None: the default kernels
-        out = (color, radii, depth)
-        if return_alpha:
-            out += (_C.render_alpha(img, rs.image_height, rs.image_width),)
-        if return_median:
-            out += _median_outputs(ctx, means3D.shape[0], rs, geom, binning, img, capacity)
-        if return_distortion:
-            out += _distortion_outputs(ctx, means3D.shape[0], rs, geom, binning, img, capacity, distortion_map)
-        return out
+        return _forward_tail(ctx, (color, radii, depth), means3D.shape[0], rs, geom, binning, img, capacity, return_alpha,
+                             return_median, return_distortion, distortion_map)
 
     @staticmethod
     def backward(ctx, grad_out_color, grad_radii, grad_depth, *grad_more):
@@ -229,20 +248,14 @@ class _RasterizeGaussians(torch.autograd.Function):
              grad_scales, grad_rotations) = g[:8]
             if ctx.absgrad_to is not None:              # gsplat's convention; replaced at every backward
                 ctx.absgrad_to.absgrad = g[8]
-            if grad_median is not None:
-                grad_means3D = _median_backward(ctx, grad_median, grad_means3D, (accumulate_into or {}).get("means3D"),
-                                                radii, geom, binning, img)
-            if grad_distortion is not None:
-                fused = accumulate_into or {}
-                d = _distortion_backward(
-                    ctx, grad_distortion,
-                    dict(means2D=grad_means2D, opacity=grad_opacities, means3D=grad_means3D, scales=grad_scales,
-                         rotations=grad_rotations, cov3D=grad_cov3Ds_precomp),
-                    {k: fused.get(k) for k in ("means2D", "opacity", "means3D", "scales", "rotations", "cov3D")},
-                    geom, binning, img, means3D=means3D, scales=scales, rotations=rotations,
-                    cov3D_precomp=cov3Ds_precomp)
-                grad_means2D, grad_opacities, grad_means3D = d["means2D"], d["opacity"], d["means3D"]
-                grad_scales, grad_rotations, grad_cov3Ds_precomp = d["scales"], d["rotations"], d["cov3D"]
+            d = _backward_extras(
+                ctx, grad_median, grad_distortion,
+                dict(means2D=grad_means2D, opacity=grad_opacities, means3D=grad_means3D, scales=grad_scales,
+                     rotations=grad_rotations, cov3D=grad_cov3Ds_precomp),
+                accumulate_into, radii, geom, binning, img, means3D=means3D, scales=scales, rotations=rotations,
+                cov3D_precomp=cov3Ds_precomp)
+            grad_means2D, grad_opacities, grad_means3D = d["means2D"], d["opacity"], d["means3D"]
+            grad_scales, grad_rotations, grad_cov3Ds_precomp = d["scales"], d["rotations"], d["cov3D"]
         except Exception:
             if rs.debug:
                 _snapshot(args, "snapshot_bw.dump")
@@ -334,20 +347,8 @@ class _RasterizeGaussiansRaw(torch.autograd.Function):
         if ctx.depth_image is not None:
             ctx.set_materialize_grads(False)
         ctx.save_for_backward(xyz, features_dc, features_rest, opacity, scaling, rotation, radii, geom, binning, img)
-        ctx.return_alpha = bool(return_alpha)
-        ctx.median_ids = None
-        ctx.distortion = None
-        if not return_alpha and not return_median and not return_distortion:
-            return color, radii, depth
-        ctx.set_materialize_grads(False)                # as _RasterizeGaussians
-        out = (color, radii, depth)
-        if return_alpha:
-            out += (_C.render_alpha(img, rs.image_height, rs.image_width),)
-        if return_median:
-            out += _median_outputs(ctx, xyz.shape[0], rs, geom, binning, img, capacity)
-        if return_distortion:
-            out += _distortion_outputs(ctx, xyz.shape[0], rs, geom, binning, img, capacity, distortion_map)
-        return out
+        return _forward_tail(ctx, (color, radii, depth), xyz.shape[0], rs, geom, binning, img, capacity, return_alpha,
+                             return_median, return_distortion, distortion_map)
 
     @staticmethod
     def backward(ctx, grad_out_color, grad_radii, grad_depth, *grad_more):
@@ -367,6 +368,12 @@ class _RasterizeGaussiansRaw(torch.autograd.Function):
             g_dc, g_rest = _fusable_grad(li["features_dc"], xyz.device), _fusable_grad(li["features_rest"], xyz.device)
             if g_dc is not None and (g_rest is not None or features_rest.numel() == 0):
                 accumulate_into["features"] = (g_dc, g_rest)
+        def extras(g, fused):
+            # the median's and the distortion's terms on the result g of the raw backward, under the activated node's names
+            returned = _from_raw_names(dict(means2D=g[0], xyz=g[1], opacity=g[4], scaling=g[5], rotation=g[6]))
+            return _backward_extras(ctx, grad_median, grad_distortion, returned, _from_raw_names(fused), radii, geom, binning, img,
+                                    means3D=xyz, opacities=opacity, scales=scaling, rotations=rotation, raw=True)
+
         # an armed FusedAdam over exactly these six tensors (optim.FusedAdam.arm_fused_backward): the gradients go to tensors
         # autograd never sees -- visited rows only, nothing zero-filled -- and the optimizer's masked step
         # (lr_adam_step_masked: the view's own visibility is the mask) is launched right behind the backward's kernels;
@@ -381,12 +388,8 @@ class _RasterizeGaussiansRaw(torch.autograd.Function):
                 binning, img, False, binning_capacity=ctx.binning_capacity, no_zero_fill=True, **modes)
             if ctx.absgrad_to is not None:              # written in full also here (zero-filled like means2D): not part of the step
                 ctx.absgrad_to.absgrad = g[7]
-            if grad_median is not None:                 # the rows it adds to are rows the view visited
-                _median_backward(ctx, grad_median, g[1], None, radii, geom, binning, img)
-            if grad_distortion is not None:             # likewise, before the step reads the rows
-                _distortion_backward(ctx, grad_distortion, dict(means2D=g[0], opacity=g[4], means3D=g[1], scales=g[5], rotations=g[6]),
-                                     None, geom, binning, img, means3D=xyz, opacities=opacity, scales=scaling, rotations=rotation,
-                                     raw=True)
+            # the rows the extras add to are rows the view visited; before the step reads them
+            extras(g, None)
             opt.apply_armed_step(geom, [xyz, features_dc, features_rest, opacity, scaling, rotation], list(g[1:7]))
             return None, g[0], None, None, None, None, None, None, None, None, None, None
         g = _C.rasterize_gaussians_raw_backward(
@@ -395,16 +398,9 @@ class _RasterizeGaussiansRaw(torch.autograd.Function):
             binning, img, rs.debug, binning_capacity=ctx.binning_capacity, accumulate_into=accumulate_into, **modes)
         if ctx.absgrad_to is not None:
             ctx.absgrad_to.absgrad = g[7]
-        g_means2D, g_xyz, g_dc, g_rest, g_op, g_sc, g_rot = g[:7]
-        if grad_median is not None:
-            g_xyz = _median_backward(ctx, grad_median, g_xyz, (accumulate_into or {}).get("xyz"), radii, geom, binning, img)
-        if grad_distortion is not None:
-            fused = accumulate_into or {}
-            d = _distortion_backward(ctx, grad_distortion, dict(means2D=g_means2D, opacity=g_op, means3D=g_xyz, scales=g_sc, rotations=g_rot),
-                                     dict(means2D=fused.get("means2D"), opacity=fused.get("opacity"), means3D=fused.get("xyz"),
-                                          scales=fused.get("scaling"), rotations=fused.get("rotation")),
-                                     geom, binning, img, means3D=xyz, opacities=opacity, scales=scaling, rotations=rotation, raw=True)
-            g_means2D, g_op, g_xyz, g_sc, g_rot = d["means2D"], d["opacity"], d["means3D"], d["scales"], d["rotations"]
+        g_dc, g_rest = g[2], g[3]
+        d = extras(g, accumulate_into)
+        g_means2D, g_op, g_xyz, g_sc, g_rot = d["means2D"], d["opacity"], d["means3D"], d["scales"], d["rotations"]
         return g_xyz, g_means2D, g_dc, g_rest, g_op, g_sc, g_rot, None, None, None, None, None
 
 
