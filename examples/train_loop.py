@@ -21,6 +21,7 @@ a perturbed subset of it.  Prints the loss every `--log` iterations and the time
                                   [--multi-view 4 --depth-weight 0.1 [--depth-loss pearson]]
                                   [--filter3d [--antialiasing]]
                                   [--normal-weight 0.05] [--normal-consistency 0.05] [--distortion-weight 100]
+                                  [--rendered-normal-consistency 0.05]
 
 --multi-view K: the loop body is ONE multi-view step (parallel.ViewBatch: forward, L1 + DSSIM loss and backward of K views in one
 C call, gradients summed) followed by Adam; the densification statistics are formed inside the step, per view
@@ -46,6 +47,11 @@ the means only.  The multi-view step has no normal term of its own: a caller rea
 --distortion-weight W (single-view loop): the forward also returns the depth distortion (return_distortion=True: Mip-NeRF 360's
 distortion loss as 2DGS uses it, on the "ndc" mapping) and W x its mean over the image is added to the loss.
 
+--rendered-normal-consistency W (single-view loop): the forward also returns the rendered normal map (return_normals=True: the
+blend of the Gaussians' own normals, their shortest axes turned towards the camera) and
+normals.rendered_normal_consistency(normals, depth) with weight W is added: the normal consistency of 2DGS / RaDe-GS / PGSR,
+which turns the Gaussians' flat sides into the surface the rendered depth describes.  Turns the depth gradient on.
+
 --filter3d: in either loop the rasterizer is shown the cloud through luciddreamer_amd.filter3d.filtered(model, filter): every
 Gaussian low-passed by the highest sampling rate at which a training camera sees it (the 3D smoothing filter of Mip-Splatting).
 The filter is computed after build, again after every densify / prune / MCMC change of the set (a filter of another length than
@@ -66,7 +72,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from luciddreamer_amd import cameras, config, densify, filter3d, mcmc, synthetic     # noqa: E402
 from luciddreamer_amd.gaussian_renderer import GaussianCloud, render_raw   # noqa: E402
 from luciddreamer_amd.loss import l1_dssim_loss                            # noqa: E402
-from luciddreamer_amd.normals import depth_normals, normal_consistency, normal_loss     # noqa: E402
+from luciddreamer_amd.normals import depth_normals, normal_consistency, normal_loss, rendered_normal_consistency     # noqa: E402
 from luciddreamer_amd.optim import FusedAdam                               # noqa: E402
 from simple_knn._C import distCUDA2                                        # noqa: E402
 
@@ -280,17 +286,20 @@ def train_multi_view(args, log=print):
 def train(args, log=print):
     normal_w, consistency_w = getattr(args, "normal_weight", 0.0), getattr(args, "normal_consistency", 0.0)
     distortion_w = getattr(args, "distortion_weight", 0.0)
+    rendered_w = getattr(args, "rendered_normal_consistency", 0.0)
     if getattr(args, "multi_view", 0) > 0:
         if normal_w > 0 or consistency_w > 0:
             raise SystemExit("--normal-weight / --normal-consistency: the single-view loop only (the multi-view step takes an "
                              "external depth term through ViewBatch(grad_depths=))")
         if distortion_w > 0:
             raise SystemExit("--distortion-weight: the single-view loop only (the multi-view step has no distortion term)")
+        if rendered_w > 0:
+            raise SystemExit("--rendered-normal-consistency: the single-view loop only (the multi-view step renders no normals)")
         return train_multi_view(args, log)
     dev = torch.device("cuda:0")
     model, cams, targets = build(args, dev)
     normal_targets = normal_targets_for(args, dev) if normal_w > 0 else None
-    if normal_w > 0 or consistency_w > 0:
+    if normal_w > 0 or consistency_w > 0 or rendered_w > 0:
         config.set_depth_gradient(True)            # the normal terms act on the rendered depth
     bg = torch.zeros(3, device=dev)
     # no host round trip per forward ("Host sync"); instance counts drift while the cloud is
@@ -307,7 +316,7 @@ def train(args, log=print):
     for it in range(1, args.iters + 1):
         v = int(torch.randint(0, len(cams), (1,), generator=gen))
         pkg = render_raw(cams[v], f3.view(model), bg_color=bg, return_median=consistency_w > 0,    # luciddreamer.py:296
-                         return_distortion=distortion_w > 0)
+                         return_distortion=distortion_w > 0, return_normals=rendered_w > 0)
         loss = l1_dssim_loss(pkg["render"], targets[v], args.lambda_dssim)                # :301-303
         if normal_w > 0:
             loss = loss + normal_loss(pkg["depth"], normal_targets[v], cams[v], weight=normal_w)
@@ -315,6 +324,8 @@ def train(args, log=print):
             loss = loss + normal_consistency(pkg["depth"], pkg["median_depth"], cams[v], weight=consistency_w)
         if distortion_w > 0:
             loss = loss + distortion_w * pkg["distortion"].mean()
+        if rendered_w > 0:
+            loss = loss + rendered_normal_consistency(pkg["normals"], pkg["depth"], cams[v], weight=rendered_w)
         loss.backward()                                                                   # :304
         with torch.no_grad():
             vis, radii = pkg["visibility_filter"], pkg["radii"]
@@ -339,7 +350,7 @@ def train(args, log=print):
     config.set_async(True)              # back to the library defaults
     config.set_antialiasing(False)
     config.set_absgrad(False)
-    if normal_w > 0 or consistency_w > 0:
+    if normal_w > 0 or consistency_w > 0 or rendered_w > 0:
         config.set_depth_gradient(False)
     log(f"{args.iters} iterations in {dt:.2f} s = {dt / args.iters * 1e3:.3f} ms/iteration")
     return losses, dt
@@ -349,7 +360,8 @@ def default_args(**kw):
     d = dict(gaussians=200_000, iters=300, resolution="512x512", views=12, lambda_dssim=0.2, log=50, densify_from=100,
              densify_every=100, densify_until=10_000, exact=False, torch_adam=False, antialiasing=False, absgrad=False,
              densify_grad_threshold=0.0002, multi_view=0, mcmc=False, cap_max=0, depth_weight=0.0, depth_loss="l1", filter3d=False,
-             normal_weight=0.0, normal_consistency=0.0, distortion_weight=0.0)
+             normal_weight=0.0, normal_consistency=0.0, distortion_weight=0.0,
+             rendered_normal_consistency=0.0)
     d.update(kw)
     return SimpleNamespace(**d)
 
@@ -374,6 +386,8 @@ HELP = {
                           "(return_median=True); the median's side moves the means only",
     "distortion_weight": "single-view loop: > 0 adds W x the mean depth distortion of the view (return_distortion=True, the "
                          "\"ndc\" mapping of 2DGS): pulls the layers a ray blends together in depth",
+    "rendered_normal_consistency": "single-view loop: > 0 adds normals.rendered_normal_consistency(normals, depth) with this "
+                                   "weight (return_normals=True): the rendered normal map against the normals of the rendered depth",
     "densify_grad_threshold": "clone / split threshold on the accumulated view-space gradient norm (reference: 0.0002).  Summed "
                               "magnitudes are larger than the signed norm: with --absgrad use about 4x (0.0008)",
 }

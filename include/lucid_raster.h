@@ -469,6 +469,91 @@ int lr_render_distortion(const lr_distortion_args* a);
 int lr_distortion_backward(const lr_distortion_backward_args* a);
 
 /*
+ * Rendered normal map of a forward (the "normal consistency" input of 2DGS section 5, RaDe-GS and PGSR: the per-pixel blend of the
+ * Gaussians' normals, to be compared with the normals of the rendered depth), from its three scratch buffers; a pass of its own
+ * behind the forward, whose kernels are not changed by it.
+ *
+ * Per-Gaussian normal.  Needs scales + rotations: with cov3D_precomp there is no normal and both entries return
+ * LR_ERR_INVALID_ARG.
+ *   Axis: k = argmin over the three scales; on ties the lowest index wins.  The comparison is made on the floats as given --
+ *   activated scales, or in raw mode the stored log-scales -- an exact comparison of inputs.  scale_modifier, the 3D filter and
+ *   anti-aliasing do not change k.  An isotropic Gaussian (LucidDreamer's freshly initialised ones are) takes axis 0.
+ *   World space: n_world = R(q)[:, k], R the quaternion matrix for which Sigma = R S^2 R^T, so Sigma n = s_k^2 n.  Activated mode
+ *   uses q as given, with no normalisation, as the covariance does; raw mode uses q / max(|q|, 1e-12).
+ *   View space: n_view = W n_world, W the rotation part of the view matrix.  Axes: x right, y down, z forward (those of
+ *   lr_depth_normals).
+ *   Orientation: towards the camera (n . (u, v, 1) < 0, the depth normals' convention), decided once per Gaussian: with p_view the
+ *   Gaussian's view-space mean, n_view . p_view > 0 -> n_view = -n_view.
+ *   The axis choice and the sign are constants of the view, as the sort order is: nothing flows to scales or the mean through them.
+ * Per-pixel map.  N = sum_i w_i n_i over the layers the blend forward applied to the pixel, w_i = alpha_i T_i with the forward's
+ * skips, 0.99 clamp and 1e-4 stop: exactly the walk of lr_render_distortion.  No background term, no normalisation: |N| <= alpha,
+ * and a caller divides by alpha or normalises as their method asks.
+ *   out_normals       [3,H,W] float32: N; exact zeros for a pixel with no layer, for P = 0 and for an overflowed async view.
+ *   out_gauss_normals [P,4]   float32: {n_view.xyz, sign (k + 1)} per Gaussian, zeros for radii <= 0; what
+ *                                      lr_render_normals_backward needs of this pass.  16-byte aligned.
+ * As for lr_render_distortion the definition holds under strict parity, anti-aliasing, the 3D filter, raw and activated
+ * parameters, both forward shapes, and exact and async mode.  `view` is the forward's: scales, rotations, means3D, viewmatrix and
+ * raw are read.  P = 0 returns 0 and writes zeros without reading a buffer.
+ *
+ * lr_render_normals_backward: the gradient of out_normals for the upstream dL_dnormals [3,H,W], with `normals` and `gauss_normals`
+ * what lr_render_normals wrote for the same buffers.  With g = dL/dN of the pixel and c_i = n_i . g:
+ *     dL/dn_i += w_i g,   dL/dalpha_i = T_i c_i - S_i / (1 - alpha_i),   S_i = sum_{k>i} w_k c_k = N.g - sum_{k<=i} w_k c_k,
+ * S_i taken front to back on the forward's own T sequence.  The conventions of the colour path hold: the clamp is not
+ * differentiated; skips, stop and order are constants.  alpha = opacity G reaches dL_dmean2D, dL_dconic and dL_dopacity and
+ * through them the mean, scales and rotations.  dL/dn_i is summed per Gaussian into dL_dgauss_normal [P,3] (a public output,
+ * written in full, 16-byte aligned) and goes on to dL_drot only: un-flip, W^T, the Jacobian of column k of R(q), and in raw mode
+ * the normalisation Jacobian (g - q (q.g)) / |r|; it is ADDED to the rows of dL_drot with radii > 0.  Colours and SH get nothing:
+ * dL_dcolor, dL_dsh and dL_dsh_rest may be NULL and are never added to; given in write mode they are zero-filled.  The other
+ * outputs, their units, accumulate_mask and the alignment rule are lr_distortion_backward_args'.  Order: the per-tile kernel, the
+ * zero-fill of rows in write mode, the per-Gaussian backward, the rotation chain.  The per-tile kernel OVERWRITES the per-instance
+ * gradient slots of the binning buffer: the ordering rule is lr_distortion_backward's (behind the colour backward of the same
+ * forward state -- and behind lr_distortion_backward, if both run -- and before another forward reuses the buffers).  An
+ * overflowed async view adds nothing.  No global float atomics: bit-repeatable.  Not part of lr_views_accumulate.
+ */
+typedef struct lr_normals_render_args {
+    size_t struct_bytes;                     /* = sizeof(lr_normals_render_args); anything else is LR_ERR_INVALID_ARG */
+    lr_view view;
+    const int* radii;                        /* the forward's [P] */
+    const char* geom_buffer;
+    const char* binning_buffer;
+    const char* image_buffer;
+    long long binning_capacity;              /* the value the forward was given */
+    float* out_normals;
+    float* out_gauss_normals;
+    void* stream;
+} lr_normals_render_args;
+
+typedef struct lr_normals_render_backward_args {
+    size_t struct_bytes;                     /* = sizeof(lr_normals_render_backward_args); anything else is LR_ERR_INVALID_ARG */
+    lr_view view;
+    char* geom_buffer;
+    char* binning_buffer;
+    char* image_buffer;
+    long long binning_capacity;
+    const float* dL_dnormals;
+    const float* normals;
+    const float* gauss_normals;
+    const int* radii;
+    float* dL_dgauss_normal;
+    /* gradient outputs, as lr_backward_args */
+    float* dL_dmean2D;
+    float* dL_dconic;
+    float* dL_dopacity;
+    float* dL_dcolor;
+    float* dL_dmean3D;
+    float* dL_dcov3D;                        /* never written: there is no normal with cov3D_precomp */
+    float* dL_dsh;
+    float* dL_dsh_rest;
+    float* dL_dscale;
+    float* dL_drot;
+    unsigned int accumulate_mask;
+    void* stream;
+} lr_normals_render_backward_args;
+
+int lr_render_normals(const lr_normals_render_args* a);
+int lr_render_normals_backward(const lr_normals_render_backward_args* a);
+
+/*
  * Multi-view step (new; the reference renders one view per Python iteration, luciddreamer.py:291-304).
  * lr_views_accumulate runs lr_forward + the backward for n_views views of ONE parameter set and ACCUMULATES the gradients
  * into the acc_* buffers.  Everything is enqueued from C in one call: views alternate over up to 4 chains (forward of view

@@ -248,6 +248,98 @@ def distortion_backward(geomBuffer, binningBuffer, imageBuffer, dL_ddistortion, 
     return out
 
 
+def _normals_view(rs, P, means3D, opacities, scales, rotations, raw):
+    """(lr_view, tensors to keep alive) of the rendered-normal entries: the forward's camera and scales + rotations."""
+    cont = lambda t: t.detach().contiguous().float()
+    keep = [cont(rs.viewmatrix), cont(rs.projmatrix), cont(rs.campos), cont(means3D), cont(scales), cont(rotations),
+            cont(opacities) if opacities is not None else None]
+    view, proj, campos, m3, sc, rot, op = keep
+    v = _lib_check.View(P=P, D=0, M=1, raw=1 if raw else 0, width=int(rs.image_width), height=int(rs.image_height),
+                        means3D=m3.data_ptr(), opacities=op.data_ptr() if op is not None else None, scales=sc.data_ptr(),
+                        scale_modifier=float(rs.scale_modifier), rotations=rot.data_ptr(), viewmatrix=view.data_ptr(),
+                        projmatrix=proj.data_ptr(), campos=campos.data_ptr(), tan_fovx=float(rs.tanfovx), tan_fovy=float(rs.tanfovy))
+    return v, keep
+
+
+def require_scale_rot(who, scales, rotations, cov3D_precomp):
+    present = lambda t: t is not None and t.numel() != 0
+    if present(cov3D_precomp) or not present(scales) or not present(rotations):
+        raise ValueError(f"{who}: the rendered normal map needs scales + rotations (a Gaussian given by cov3D_precomp has no normal)")
+
+
+def render_normals(geomBuffer, binningBuffer, imageBuffer, radii, rs, *, means3D, scales, rotations, cov3D_precomp=None, raw=False,
+                   binning_capacity=0):
+    """(normals (3, H, W), gauss_normals (P, 4)) float32 of the forward that left the three buffers (lr_render_normals, on the
+    current stream): N = sum_i w_i n_i over each pixel's blended layers, n_i the Gaussian's view-space normal (its shortest
+    axis, turned towards the camera), and the per-Gaussian {n.xyz, sign (k + 1)} render_normals_backward needs.  rs: the
+    forward's raster settings; radii: its radii.  ValueError with cov3D_precomp, before any launch.  No autograd."""
+    import torch
+    require_scale_rot("render_normals", scales, rotations, cov3D_precomp)
+    dev = imageBuffer.device
+    P = int(means3D.shape[0])
+    H, W = int(rs.image_height), int(rs.image_width)
+    normals = torch.empty((3, H, W), dtype=torch.float32, device=dev)
+    gauss_normals = torch.empty((P, 4), dtype=torch.float32, device=dev)
+    v, keep = _normals_view(rs, P, means3D, None, scales, rotations, raw)
+    rad = radii.contiguous()
+    a = _lib_check.NormalsRenderArgs(view=v, radii=rad.data_ptr(), geom_buffer=geomBuffer.data_ptr(),
+                                     binning_buffer=binningBuffer.data_ptr(), image_buffer=imageBuffer.data_ptr(),
+                                     binning_capacity=int(binning_capacity), out_normals=normals.data_ptr(),
+                                     out_gauss_normals=gauss_normals.data_ptr(), stream=torch.cuda.current_stream(dev).cuda_stream)
+    with _lib_check.on_device(dev):
+        rc = _lib_check.lib().lr_render_normals(a)
+    if rc < 0:
+        _lib_check.raise_for(rc, "render_normals")
+    del keep
+    return normals, gauss_normals
+
+
+def render_normals_backward(geomBuffer, binningBuffer, imageBuffer, dL_dnormals, normals, gauss_normals, radii, rs, *, means3D,
+                            opacities=None, scales=None, rotations=None, cov3D_precomp=None, raw=False, binning_capacity=0,
+                            accumulate_into=None):
+    """The rendered normal map's gradient (lr_render_normals_backward, on the current stream, behind the colour backward -- and the
+    distortion backward -- of the same forward).  Arguments as distortion_backward; accumulate_into: {"means2D", "opacity",
+    "means3D", "scales", "rotations": tensor or None}, a given tensor is ADDED to in place, a missing one is a new tensor written in
+    full.  Returns the dict of the five plus "gauss_normal": dL/dn per Gaussian (P, 3), always a new tensor."""
+    import torch
+    require_scale_rot("render_normals_backward", scales, rotations, cov3D_precomp)
+    dev = imageBuffer.device
+    P = int(means3D.shape[0])
+    H, W = int(rs.image_height), int(rs.image_width)
+    cont = lambda t: t.detach().contiguous().float()
+    dL, nrm, gn, rad = cont(dL_dnormals), cont(normals), cont(gauss_normals), radii.contiguous()
+    if raw and opacities is None:
+        raise RuntimeError("render_normals_backward: raw mode needs the stored opacities")
+    if dL.numel() != 3 * H * W or nrm.numel() != 3 * H * W or gn.numel() != 4 * P:
+        raise RuntimeError("render_normals_backward: dL_dnormals, normals and gauss_normals must be (3, H, W), (3, H, W), (P, 4)")
+    shapes = {"means2D": (P, 3), "opacity": (P, 1), "means3D": (P, 3), "scales": (P, 3), "rotations": (P, 4)}
+    bits = {"means2D": 0, "opacity": 2, "means3D": 4, "scales": 7, "rotations": 8}
+    out, mask = {}, 0
+    for name, shape in shapes.items():
+        t = (accumulate_into or {}).get(name)
+        if t is not None:
+            if not t.is_contiguous() or t.dtype != torch.float32 or t.numel() != int(torch.Size(shape).numel()):
+                raise RuntimeError(f"render_normals_backward: accumulate_into[{name!r}] must be a contiguous float32 tensor of {shape}")
+            out[name] = t
+            mask |= 1 << bits[name]
+        else:
+            out[name] = torch.empty(shape, dtype=torch.float32, device=dev)
+    out["gauss_normal"] = torch.empty((P, 3), dtype=torch.float32, device=dev)
+    v, keep = _normals_view(rs, P, means3D, opacities, scales, rotations, raw)
+    a = _lib_check.NormalsRenderBackwardArgs(
+        view=v, geom_buffer=geomBuffer.data_ptr(), binning_buffer=binningBuffer.data_ptr(), image_buffer=imageBuffer.data_ptr(),
+        binning_capacity=int(binning_capacity), dL_dnormals=dL.data_ptr(), normals=nrm.data_ptr(), gauss_normals=gn.data_ptr(),
+        radii=rad.data_ptr(), dL_dgauss_normal=out["gauss_normal"].data_ptr(), dL_dmean2D=out["means2D"].data_ptr(),
+        dL_dopacity=out["opacity"].data_ptr(), dL_dmean3D=out["means3D"].data_ptr(), dL_dscale=out["scales"].data_ptr(),
+        dL_drot=out["rotations"].data_ptr(), accumulate_mask=mask, stream=torch.cuda.current_stream(dev).cuda_stream)
+    with _lib_check.on_device(dev):
+        rc = _lib_check.lib().lr_render_normals_backward(a)
+    if rc < 0:
+        _lib_check.raise_for(rc, "render_normals_backward")
+    del keep
+    return out
+
+
 # forward + backward of one view in one call for a caller that holds dL/dcolor up front; [] = an input does not qualify
 rasterize_view_step = _C_ext.rasterize_view_step
 last_num_rendered = _C_ext.last_num_rendered

@@ -28,7 +28,7 @@ _lock = threading.Lock()
 
 EXPORTS = ("lr_last_error", "lr_version", "lr_geom_bytes", "lr_img_bytes", "lr_binning_bytes", "lr_forward",
            "lr_backward", "lr_view_forward", "lr_view_backward", "lr_render_alpha", "lr_render_median", "lr_median_backward",
-           "lr_render_distortion", "lr_distortion_backward",
+           "lr_render_distortion", "lr_distortion_backward", "lr_render_normals", "lr_render_normals_backward",
            "lr_mark_visible", "lr_check",
            "lr_dist2_workspace_bytes", "lr_dist2",
            "lr_dist2_workspace_layout",
@@ -175,6 +175,31 @@ class DistortionBackwardArgs(ctypes.Structure):
 
     def __init__(self, **fields):
         super().__init__(struct_bytes=ctypes.sizeof(DistortionBackwardArgs), **fields)
+
+
+class NormalsRenderArgs(ctypes.Structure):
+    """lr_normals_render_args, field for field (tests/test_render_normals_cpu.py compares the offsets with the host compiler's)."""
+    _vp = ctypes.c_void_p
+    _fields_ = [("struct_bytes", ctypes.c_size_t), ("view", View), ("radii", _vp),
+                ("geom_buffer", _vp), ("binning_buffer", _vp), ("image_buffer", _vp), ("binning_capacity", ctypes.c_longlong),
+                ("out_normals", _vp), ("out_gauss_normals", _vp), ("stream", _vp)]
+
+    def __init__(self, **fields):
+        super().__init__(struct_bytes=ctypes.sizeof(NormalsRenderArgs), **fields)
+
+
+class NormalsRenderBackwardArgs(ctypes.Structure):
+    """lr_normals_render_backward_args, field for field."""
+    _vp = ctypes.c_void_p
+    _fields_ = [("struct_bytes", ctypes.c_size_t), ("view", View),
+                ("geom_buffer", _vp), ("binning_buffer", _vp), ("image_buffer", _vp), ("binning_capacity", ctypes.c_longlong),
+                ("dL_dnormals", _vp), ("normals", _vp), ("gauss_normals", _vp), ("radii", _vp), ("dL_dgauss_normal", _vp),
+                ("dL_dmean2D", _vp), ("dL_dconic", _vp), ("dL_dopacity", _vp), ("dL_dcolor", _vp), ("dL_dmean3D", _vp),
+                ("dL_dcov3D", _vp), ("dL_dsh", _vp), ("dL_dsh_rest", _vp), ("dL_dscale", _vp), ("dL_drot", _vp),
+                ("accumulate_mask", ctypes.c_uint), ("stream", _vp)]
+
+    def __init__(self, **fields):
+        super().__init__(struct_bytes=ctypes.sizeof(NormalsRenderBackwardArgs), **fields)
 
 
 def distortion_map_coefficients(distortion_map):
@@ -331,6 +356,10 @@ def lib():
         L.lr_render_distortion.argtypes = [ctypes.POINTER(DistortionArgs)]
         L.lr_distortion_backward.restype = ci
         L.lr_distortion_backward.argtypes = [ctypes.POINTER(DistortionBackwardArgs)]
+        L.lr_render_normals.restype = ci
+        L.lr_render_normals.argtypes = [ctypes.POINTER(NormalsRenderArgs)]
+        L.lr_render_normals_backward.restype = ci
+        L.lr_render_normals_backward.argtypes = [ctypes.POINTER(NormalsRenderBackwardArgs)]
         L.lr_mark_visible.restype = ci
         L.lr_mark_visible.argtypes = [ci, vp, vp, vp, vp, vp]
         L.lr_check.restype = ci

@@ -499,6 +499,18 @@ void launch_render_distort(int W, int H, int P, const GeomView& g, const ImgView
                            float c2, float* out_distortion, float* out_moments, hipStream_t s);
 void launch_distort_bwd(int W, int H, int P, const GeomView& g, const ImgView& im, char* bin_base, const float* dL_ddistortion,
                         const float* distortion, const float* moments, float c0, float c1, float c2, hipStream_t s);
+// rendered normal map of a finished forward (render_normals.hip: definition, kernels).  launch_gauss_normals: the per-Gaussian
+// view-space normal [P,4] = {n.xyz, sign (k + 1)}, zeros for radii <= 0.  launch_render_normals: N = sum w n, [3,H,W]; P <= 0:
+// zeros without reading a buffer.  launch_normals_bwd: the map's gradient as one GradRec per instance in inst_grad (the colour
+// floats carry dL/dn).  launch_normal_rot_bwd: dL_dgauss_normal [P,3] -> ADDED into dL_drot [P,4] for radii > 0.
+void launch_gauss_normals(int P, bool raw, const float* means3D, const float* scales, const float* rotations, const float* view,
+                          const int* radii, float* out_gauss_normals, hipStream_t s);
+void launch_render_normals(int W, int H, int P, const GeomView& g, const ImgView& im, const char* bin_base,
+                           const float* gauss_normals, float* out_normals, hipStream_t s);
+void launch_normals_bwd(int W, int H, int P, const GeomView& g, const ImgView& im, char* bin_base, const float* dL_dnormals,
+                        const float* normals, const float* gauss_normals, hipStream_t s);
+void launch_normal_rot_bwd(int P, bool raw, const float* rotations, const float* view, const int* radii, const GeomView& g,
+                           const float* gauss_normals, const float* dL_dgauss_normal, float* dL_drot, hipStream_t s);
 // The upstream gradients a view's backward is given.
 struct ViewGrads {
     const float* color;     // dL_dpix [3,H,W]

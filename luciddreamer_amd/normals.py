@@ -194,6 +194,18 @@ def normal_consistency(depth_a, depth_b, camera, pixel_weight=None, weight=1.0):
     return _NormalConsistency.apply(depth_a, depth_b, camera, pixel_weight, weight)
 
 
+def rendered_normal_consistency(rendered_normals, depth, camera, weight=1.0):
+    """The normal consistency of 2DGS section 5 / RaDe-GS / PGSR between the RENDERED normal map N [3,H,W] (return_normals=True:
+    the blend of the Gaussians' own normals, not normalised) and the normals n of the rendered depth:
+    weight * sum over the valid pixels of (1 - N_p . n_p) / (H*W), n = depth_normals(depth, camera), valid = the pixels with a
+    valid depth normal.  Composed from depth_normals and three torch ops; gradients go to both arguments -- through N to the
+    rotations directly, which two depth maps (normal_consistency) reach only at second hand."""
+    n = depth_normals(depth, camera)
+    N = _normal_image(rendered_normals, "rendered_normals", "rendered_normal_consistency", n)
+    valid = (n.detach() != 0).any(dim=0).sum()          # an invalid normal is (0,0,0): its dot product is an exact zero
+    return (valid - (N * n).sum()) * (float(weight) / float(n.shape[-2] * n.shape[-1]))
+
+
 def normal_count(depth, target, camera, pixel_weight=None):
     """The number of pixels that count in normal_loss (target [3,H,W]) or normal_consistency (target a depth map [1,H,W] or
     [H,W]) of these inputs: a 0-dim device tensor without a gradient, for renormalising (loss * H * W / count) and logging."""

@@ -18,6 +18,14 @@ of the pixel's blended layers (Mip-NeRF 360 / 2DGS / gsplat's `distloss`), D = s
 weights and m_i the mapped depth of `distortion_map` -- "ndc" (default; ("ndc", near, far), 2DGS's far / (far - near) (1 - near / z) with
 near = 0.2, far = 100) or "linear" (m = z) -- lr_render_distortion, a pass behind the forward.  Differentiable: a gradient reaching it runs
 lr_distortion_backward behind the view's backward and reaches means3D / xyz, opacities, scales, rotations (cov3D) and means2D.
+return_normals=True (same three entry points) appends normals (3, H, W) behind the median pair and in front of the distortion, which
+stays the last output: the rendered normal map N = sum_i w_i n_i over the pixel's blended layers, n_i the Gaussian's view-space normal
+-- its shortest axis (argmin of the scales as given, lowest index on ties: an isotropic Gaussian, as LucidDreamer's freshly
+initialised ones, takes axis 0), rotated by the view matrix (x right, y down, z forward: normals.depth_normals' axes) and turned
+towards the camera -- lr_render_normals, a pass behind the forward.  No background term, no normalisation: |N| <= alpha.  Needs
+scales + rotations (ValueError with cov3D_precomp).  Differentiable: a gradient reaching it runs lr_render_normals_backward behind the
+view's backward (and the distortion's) and reaches means3D / xyz, opacities, scales, rotations and means2D; the normal itself moves
+the rotations only (the axis choice and the sign are constants of the view).
 config.set_absgrad(True): the backward of a view attaches `means2D.absgrad` [P,3] (AbsGS; lr_view_backward with dL_dmean2D_abs) to the means2D
 tensor the caller passed.
 
@@ -121,14 +129,24 @@ def _distortion_outputs(ctx, P, rs, geom, binning, img, capacity, distortion_map
     return (distortion,)
 
 
+def _normals_outputs(ctx, rs, radii, geom, binning, img, capacity, inputs):
+    """(normals,) of the forward whose buffers are given, as _distortion_outputs; the backward needs the value (detached) and the
+    per-Gaussian normals.  inputs: means3D, scales, rotations, cov3D_precomp[, raw] of the node."""
+    normals, gauss_normals = _C.render_normals(geom, binning, img, radii, rs, binning_capacity=capacity, **inputs)
+    ctx.normals = (normals.detach(), gauss_normals)
+    return (normals,)
+
+
 def _more_grads(ctx, grad_more):
-    """(grad_alpha, grad_median, grad_distortion) from the gradients behind (color, radii, depth): [alpha], [median_depth,
-    median_ids], [distortion]."""
+    """(grad_alpha, grad_median, grad_distortion, grad_normals) from the gradients behind (color, radii, depth): [alpha],
+    [median_depth, median_ids], [normals], [distortion]."""
     tail = 1 if ctx.distortion is not None else 0
+    nrm = 1 if ctx.normals is not None else 0
     grad_alpha = grad_more[0] if ctx.return_alpha else None
-    grad_median = grad_more[-2 - tail] if ctx.median_ids is not None else None
+    grad_median = grad_more[-2 - tail - nrm] if ctx.median_ids is not None else None
+    grad_normals = grad_more[-1 - tail] if nrm else None
     grad_distortion = grad_more[-1] if tail else None
-    return grad_alpha, grad_median, grad_distortion
+    return grad_alpha, grad_median, grad_distortion, grad_normals
 
 
 def _median_backward(ctx, grad_median, target, radii, geom, binning, img):
@@ -153,13 +171,35 @@ def _distortion_backward(ctx, grad_distortion, returned, fused, geom, binning, i
     return {k: (t if (t is not None or fused.get(k) is not None) else out[k]) for k, t in returned.items()}
 
 
-def _forward_tail(ctx, out, P, rs, geom, binning, img, capacity, return_alpha, return_median, return_distortion, distortion_map):
-    """The end of both nodes' forward: `out` = (color, radii, depth) gains alpha, (median_depth, median_ids), distortion, in that
-    order, from the state of the forward whose buffers are given (after a re-render, the re-render's), and ctx what they need."""
+def _normals_backward(ctx, grad_normals, returned, fused, radii, geom, binning, img, plus_zero=True, **inputs):
+    """The rendered normal map's term of every geometric gradient (lr_render_normals_backward), added as _distortion_backward adds
+    the distortion's, behind it.  cov3D never takes part: there is no normal without scales + rotations.
+    plus_zero: the tensors the view's backward RETURNED (written, then added to) end with +0 for their zero entries, as the same
+    sums have when they are accumulated into a zeroed .grad -- a Gaussian the view visited and no pixel blended is written as
+    -0 by the per-Gaussian kernel, and -0 + -0 stays -0 where +0 + -0 + -0 is +0: with it the fused and the unfused route give
+    the same bits.  One multi-tensor launch; not for the armed optimizer step, whose rows are read through the view's mask."""
+    fused = fused or {}
+    names = ("means2D", "opacity", "means3D", "scales", "rotations")
+    targets = {k: (returned[k] if returned[k] is not None else fused.get(k)) for k in names}
+    value, gauss_normals = ctx.normals
+    out = _C.render_normals_backward(geom, binning, img, grad_normals, value, gauss_normals, radii, ctx.raster_settings,
+                                     binning_capacity=ctx.binning_capacity, accumulate_into=targets, **inputs)
+    written = [returned[k] for k in names if returned[k] is not None]
+    if plus_zero and written:
+        torch._foreach_add_(written, 0.0)
+    return dict(returned, **{k: (returned[k] if (returned[k] is not None or fused.get(k) is not None) else out[k]) for k in names})
+
+
+def _forward_tail(ctx, out, P, rs, geom, binning, img, capacity, return_alpha, return_median, return_distortion, distortion_map,
+                  return_normals=False, normal_inputs=None):
+    """The end of both nodes' forward: `out` = (color, radii, depth) gains alpha, (median_depth, median_ids), normals, distortion,
+    in that order, from the state of the forward whose buffers are given (after a re-render, the re-render's), and ctx what they
+    need."""
     ctx.return_alpha = bool(return_alpha)
     ctx.median_ids = None
     ctx.distortion = None
-    if not return_alpha and not return_median and not return_distortion:
+    ctx.normals = None
+    if not return_alpha and not return_median and not return_distortion and not return_normals:
         return out
     # the backward needs the image state's final T only -- the alpha tensor itself is not kept (as depth_image)
     ctx.set_materialize_grads(False)            # an unused alpha / median / distortion output arrives as None: the default kernels
@@ -167,13 +207,16 @@ def _forward_tail(ctx, out, P, rs, geom, binning, img, capacity, return_alpha, r
         out += (_C.render_alpha(img, rs.image_height, rs.image_width),)
     if return_median:
         out += _median_outputs(ctx, P, rs, geom, binning, img, capacity)
+    if return_normals:
+        out += _normals_outputs(ctx, rs, out[1], geom, binning, img, capacity, normal_inputs)
     if return_distortion:
         out += _distortion_outputs(ctx, P, rs, geom, binning, img, capacity, distortion_map)
     return out
 
 
-def _backward_extras(ctx, grad_median, grad_distortion, returned, fused, radii, geom, binning, img, **inputs):
-    """The median depth's term, then the distortion's, added behind the view's backward.  returned / fused: {name: tensor or None}
+def _backward_extras(ctx, grad_median, grad_distortion, grad_normals, returned, fused, radii, geom, binning, img, armed=False,
+                     **inputs):
+    """The median depth's term, then the distortion's, then the rendered normals', added behind the view's backward.  returned / fused: {name: tensor or None}
     of what that backward returned / of the leaves' .grad it accumulated into, under _C.distortion_backward's names, as `inputs`."""
     fused = fused or {}
     if grad_median is not None:
@@ -181,6 +224,8 @@ def _backward_extras(ctx, grad_median, grad_distortion, returned, fused, radii, 
         _median_backward(ctx, grad_median, m3 if m3 is not None else fused.get("means3D"), radii, geom, binning, img)
     if grad_distortion is not None:
         returned = _distortion_backward(ctx, grad_distortion, returned, fused, geom, binning, img, **inputs)
+    if grad_normals is not None:
+        returned = _normals_backward(ctx, grad_normals, returned, fused, radii, geom, binning, img, plus_zero=not armed, **inputs)
     return returned
 
 
@@ -193,8 +238,11 @@ class _RasterizeGaussians(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                raster_settings, return_alpha=False, return_median=False, return_distortion=False, distortion_map="ndc"):
+                raster_settings, return_alpha=False, return_median=False, return_distortion=False, distortion_map="ndc",
+                return_normals=False):
         rs = raster_settings
+        if return_normals:                              # before any launch
+            _C.require_scale_rot("return_normals", scales, rotations, cov3Ds_precomp)
         args = (rs.bg, means3D, colors_precomp, opacities, scales, rotations, rs.scale_modifier, cov3Ds_precomp,
                 rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, rs.image_height, rs.image_width, sh,
                 rs.sh_degree, rs.campos, rs.prefiltered, rs.debug)
@@ -223,11 +271,12 @@ class _RasterizeGaussians(torch.autograd.Function):
             ctx.set_materialize_grads(False)        # an unused depth output arrives as None: the default kernels
         ctx.save_for_backward(colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geom, binning, img)
         return _forward_tail(ctx, (color, radii, depth), means3D.shape[0], rs, geom, binning, img, capacity, return_alpha,
-                             return_median, return_distortion, distortion_map)
+                             return_median, return_distortion, distortion_map, return_normals,
+                             dict(means3D=means3D, scales=scales, rotations=rotations, cov3D_precomp=cov3Ds_precomp))
 
     @staticmethod
     def backward(ctx, grad_out_color, grad_radii, grad_depth, *grad_more):
-        grad_alpha, grad_median, grad_distortion = _more_grads(ctx, grad_more)
+        grad_alpha, grad_median, grad_distortion, grad_normals = _more_grads(ctx, grad_more)
         config.require_antialiasing(ctx.antialiasing)   # before anything is launched or written
         rs = ctx.raster_settings
         colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geom, binning, img = ctx.saved_tensors
@@ -249,7 +298,7 @@ class _RasterizeGaussians(torch.autograd.Function):
             if ctx.absgrad_to is not None:              # gsplat's convention; replaced at every backward
                 ctx.absgrad_to.absgrad = g[8]
             d = _backward_extras(
-                ctx, grad_median, grad_distortion,
+                ctx, grad_median, grad_distortion, grad_normals,
                 dict(means2D=grad_means2D, opacity=grad_opacities, means3D=grad_means3D, scales=grad_scales,
                      rotations=grad_rotations, cov3D=grad_cov3Ds_precomp),
                 accumulate_into, radii, geom, binning, img, means3D=means3D, scales=scales, rotations=rotations,
@@ -263,11 +312,12 @@ class _RasterizeGaussians(torch.autograd.Function):
             raise
         # order of the forward inputs (RAST/.../__init__.py:144-154); gradients of absent inputs are None-able
         return (grad_means3D, grad_means2D, grad_sh, grad_colors_precomp, grad_opacities, grad_scales, grad_rotations,
-                grad_cov3Ds_precomp, None, None, None, None, None)
+                grad_cov3Ds_precomp, None, None, None, None, None, None)
 
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                        raster_settings, return_alpha=False, return_median=False, return_distortion=False, distortion_map="ndc"):
+                        raster_settings, return_alpha=False, return_median=False, return_distortion=False, distortion_map="ndc",
+                        return_normals=False):
     """The operator.  Its autograd node is compiled (csrc/torch_ext.cpp RasterizeFn: forward and backward run without the
     interpreter -- the Python node below cost more host time per 1080p view than the GPU needs for it); with settings.debug
     the Python node runs instead, because it is the one that writes the reference's snapshot_fw.dump / snapshot_bw.dump.
@@ -281,12 +331,16 @@ def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales,
     gradient of means3D, with config.set_fused_grad_accumulation on or off.
     return_distortion: the outputs gain distortion (1, H, W) as their LAST entry (module docstring), for the mapped depth of
     distortion_map.  As return_median it always runs the Python node; an unused distortion output leaves the backward exactly as it
-    is, a gradient reaching it runs lr_distortion_backward behind the view's backward, fused accumulation on or off."""
+    is, a gradient reaching it runs lr_distortion_backward behind the view's backward, fused accumulation on or off.
+    return_normals: the outputs gain normals (3, H, W), the rendered normal map (module docstring), behind the median pair and in
+    front of the distortion.  Needs scales + rotations (ValueError otherwise, before any launch).  As its siblings it always runs
+    the Python node; an unused normals output leaves the backward exactly as it is, a gradient reaching it runs
+    lr_render_normals_backward behind the view's backward (and the distortion's), fused accumulation on or off."""
     rs = raster_settings
-    if rs.debug or return_median or return_distortion:
+    if rs.debug or return_median or return_distortion or return_normals:
         return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
                                          cov3Ds_precomp, rs, bool(return_alpha), bool(return_median), bool(return_distortion),
-                                         distortion_map)
+                                         distortion_map, bool(return_normals))
     capacity = config.capacity_for(means3D, rs)
     fused = config.fused_grad_accumulation()
     offered = config.offered_grad_output()
@@ -326,7 +380,7 @@ class _RasterizeGaussiansRaw(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, xyz, means2D, features_dc, features_rest, opacity, scaling, rotation, raster_settings, return_alpha=False,
-                return_median=False, return_distortion=False, distortion_map="ndc"):
+                return_median=False, return_distortion=False, distortion_map="ndc", return_normals=False):
         rs = raster_settings
         ctx.antialiasing = config.antialiasing()        # as _RasterizeGaussians
         ctx.absgrad_to = means2D if config.absgrad() else None
@@ -348,11 +402,12 @@ class _RasterizeGaussiansRaw(torch.autograd.Function):
             ctx.set_materialize_grads(False)
         ctx.save_for_backward(xyz, features_dc, features_rest, opacity, scaling, rotation, radii, geom, binning, img)
         return _forward_tail(ctx, (color, radii, depth), xyz.shape[0], rs, geom, binning, img, capacity, return_alpha,
-                             return_median, return_distortion, distortion_map)
+                             return_median, return_distortion, distortion_map, return_normals,
+                             dict(means3D=xyz, scales=scaling, rotations=rotation, raw=True))
 
     @staticmethod
     def backward(ctx, grad_out_color, grad_radii, grad_depth, *grad_more):
-        grad_alpha, grad_median, grad_distortion = _more_grads(ctx, grad_more)
+        grad_alpha, grad_median, grad_distortion, grad_normals = _more_grads(ctx, grad_more)
         config.require_antialiasing(ctx.antialiasing)   # before anything is launched or written
         rs = ctx.raster_settings
         xyz, features_dc, features_rest, opacity, scaling, rotation, radii, geom, binning, img = ctx.saved_tensors
@@ -368,10 +423,11 @@ class _RasterizeGaussiansRaw(torch.autograd.Function):
             g_dc, g_rest = _fusable_grad(li["features_dc"], xyz.device), _fusable_grad(li["features_rest"], xyz.device)
             if g_dc is not None and (g_rest is not None or features_rest.numel() == 0):
                 accumulate_into["features"] = (g_dc, g_rest)
-        def extras(g, fused):
+        def extras(g, fused, armed=False):
             # the median's and the distortion's terms on the result g of the raw backward, under the activated node's names
             returned = _from_raw_names(dict(means2D=g[0], xyz=g[1], opacity=g[4], scaling=g[5], rotation=g[6]))
-            return _backward_extras(ctx, grad_median, grad_distortion, returned, _from_raw_names(fused), radii, geom, binning, img,
+            return _backward_extras(ctx, grad_median, grad_distortion, grad_normals, returned, _from_raw_names(fused), radii, geom,
+                                    binning, img, armed=armed,
                                     means3D=xyz, opacities=opacity, scales=scaling, rotations=rotation, raw=True)
 
         # an armed FusedAdam over exactly these six tensors (optim.FusedAdam.arm_fused_backward): the gradients go to tensors
@@ -389,9 +445,9 @@ class _RasterizeGaussiansRaw(torch.autograd.Function):
             if ctx.absgrad_to is not None:              # written in full also here (zero-filled like means2D): not part of the step
                 ctx.absgrad_to.absgrad = g[7]
             # the rows the extras add to are rows the view visited; before the step reads them
-            extras(g, None)
+            extras(g, None, armed=True)
             opt.apply_armed_step(geom, [xyz, features_dc, features_rest, opacity, scaling, rotation], list(g[1:7]))
-            return None, g[0], None, None, None, None, None, None, None, None, None, None
+            return None, g[0], None, None, None, None, None, None, None, None, None, None, None
         g = _C.rasterize_gaussians_raw_backward(
             rs.bg, xyz, radii, features_dc, features_rest, opacity, scaling, rotation, rs.scale_modifier, rs.viewmatrix,
             rs.projmatrix, rs.tanfovx, rs.tanfovy, grad_out_color, rs.sh_degree, rs.campos, geom, ctx.num_rendered,
@@ -401,19 +457,21 @@ class _RasterizeGaussiansRaw(torch.autograd.Function):
         g_dc, g_rest = g[2], g[3]
         d = extras(g, accumulate_into)
         g_means2D, g_op, g_xyz, g_sc, g_rot = d["means2D"], d["opacity"], d["means3D"], d["scales"], d["rotations"]
-        return g_xyz, g_means2D, g_dc, g_rest, g_op, g_sc, g_rot, None, None, None, None, None
+        return g_xyz, g_means2D, g_dc, g_rest, g_op, g_sc, g_rot, None, None, None, None, None, None
 
 
 def rasterize_gaussians_raw(xyz, means2D, features_dc, features_rest, opacity, scaling, rotation, raster_settings,
-                            return_alpha=False, return_median=False, return_distortion=False, distortion_map="ndc"):
+                            return_alpha=False, return_median=False, return_distortion=False, distortion_map="ndc",
+                            return_normals=False):
     """(color, radii, depth) from the stored GaussianModel parameters (pre-activation), see _RasterizeGaussiansRaw;
     return_alpha: (color, radii, depth, alpha) as rasterize_gaussians; return_median: (median_depth, median_ids) behind them, as
     rasterize_gaussians (this entry point always runs its Python node); the median depth's gradient reaches xyz;
     return_distortion / distortion_map: distortion last, as rasterize_gaussians; its gradient reaches xyz, opacity, scaling and
-    rotation."""
+    rotation; return_normals: normals (3, H, W) behind the median pair, in front of the distortion, as rasterize_gaussians (the
+    axis is the argmin of the stored log-scales, the quaternion is normalised as the kernels normalise it)."""
     return _RasterizeGaussiansRaw.apply(xyz, means2D, features_dc, features_rest, opacity, scaling, rotation,
                                         raster_settings, bool(return_alpha), bool(return_median), bool(return_distortion),
-                                        distortion_map)
+                                        distortion_map, bool(return_normals))
 
 
 _EMPTY = torch.Tensor([])           # never written: one instance serves every call (three constructions per call were ~6 us)
@@ -431,10 +489,12 @@ class GaussianRasterizer(nn.Module):
             return _C.mark_visible(positions, rs.viewmatrix, rs.projmatrix)
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
-                cov3D_precomp=None, return_alpha=False, return_median=False, return_distortion=False, distortion_map="ndc"):
+                cov3D_precomp=None, return_alpha=False, return_median=False, return_distortion=False, distortion_map="ndc",
+                return_normals=False):
         """(color, radii, depth), or with return_alpha=True (color, radii, depth, alpha): alpha (1, H, W) = 1 - T_final; with
         return_median=True the outputs gain (median_depth, median_ids) at their end, with return_distortion=True the distortion
-        (1, H, W) of distortion_map's mapped depth behind those (rasterize_gaussians)."""
+        (1, H, W) of distortion_map's mapped depth behind those, and with return_normals=True the rendered normal map (3, H, W)
+        between the median pair and the distortion (rasterize_gaussians; ValueError with cov3D_precomp)."""
         rs = self.raster_settings
         if (shs is None) == (colors_precomp is None):
             raise Exception('Please provide excatly one of either SHs or precomputed colors!')
@@ -449,9 +509,10 @@ class GaussianRasterizer(nn.Module):
         scales = empty if scales is None else scales
         rotations = empty if rotations is None else rotations
         cov3D_precomp = empty if cov3D_precomp is None else cov3D_precomp
-        if return_alpha or return_median or return_distortion:
+        if return_alpha or return_median or return_distortion or return_normals:
             return rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
                                        cov3D_precomp, rs, return_alpha=return_alpha, return_median=return_median,
-                                       return_distortion=return_distortion, distortion_map=distortion_map)
+                                       return_distortion=return_distortion, distortion_map=distortion_map,
+                                       return_normals=return_normals)
         return rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
                                    cov3D_precomp, rs)
