@@ -44,13 +44,15 @@ the depth gradient on (config.set_depth_gradient).  --normal-consistency W: the 
 (return_median=True) and normals.normal_consistency(depth, median_depth) with weight W is added; the median's side of it moves
 the means only.  The multi-view step has no normal term of its own: a caller reaches it through ViewBatch(grad_depths=).
 
---distortion-weight W (single-view loop): the forward also returns the depth distortion (return_distortion=True: Mip-NeRF 360's
+--distortion-weight W: the forward also returns the depth distortion (return_distortion=True: Mip-NeRF 360's
 distortion loss as 2DGS uses it, on the "ndc" mapping) and W x its mean over the image is added to the loss.
 
---rendered-normal-consistency W (single-view loop): the forward also returns the rendered normal map (return_normals=True: the
+--rendered-normal-consistency W: the forward also returns the rendered normal map (return_normals=True: the
 blend of the Gaussians' own normals, their shortest axes turned towards the camera) and
 normals.rendered_normal_consistency(normals, depth) with weight W is added: the normal consistency of 2DGS / RaDe-GS / PGSR,
 which turns the Gaussians' flat sides into the surface the rendered depth describes.  Turns the depth gradient on.
+With --multi-view K both terms run inside the step (ViewBatch(distortion_weight=W, normal_consistency_weight=W)): one fused pass
+each way per view behind the blend forward and the colour backward, the same loss as the single-view loop's.
 
 --filter3d: in either loop the rasterizer is shown the cloud through luciddreamer_amd.filter3d.filtered(model, filter): every
 Gaussian low-passed by the highest sampling rate at which a training camera sees it (the 3D smoothing filter of Mip-Splatting).
@@ -226,12 +228,21 @@ def train_multi_view(args, log=print):
     batches, cap = {}, _capacity(f3.view(model), cams, bg)
     depth_weight = float(getattr(args, "depth_weight", 0.0))
     dts = depth_targets_for(args, dev) if depth_weight > 0 else None
+    # the two geometry regularisers run inside the step: one fused pass each way per view (lr_render_geometry / lr_geometry_backward)
+    distortion_w = float(getattr(args, "distortion_weight", 0.0))
+    rendered_w = float(getattr(args, "rendered_normal_consistency", 0.0))
+    geom = {}
+    if distortion_w > 0:
+        geom.update(distortion_weight=distortion_w, distortion_map="ndc")
+    if rendered_w > 0:
+        geom.update(normal_consistency_weight=rendered_w)
 
     def batch_for(gi, with_stats):
         key = (gi, with_stats)
         if key not in batches:
             depth = {} if dts is None else dict(depth_targets=[dts[i] for i in groups[gi]], depth_weight=depth_weight,
                                                 depth_loss=args.depth_loss)
+            depth.update(geom)
             batches[key] = parallel.ViewBatch([cams[i] for i in groups[gi]], None, 3, bg, cap, n_streams=min(3, K),
                                               targets=[targets[i] for i in groups[gi]], lambda_dssim=args.lambda_dssim,
                                               densify_stats=mode if with_stats else None, **depth)
@@ -291,10 +302,6 @@ def train(args, log=print):
         if normal_w > 0 or consistency_w > 0:
             raise SystemExit("--normal-weight / --normal-consistency: the single-view loop only (the multi-view step takes an "
                              "external depth term through ViewBatch(grad_depths=))")
-        if distortion_w > 0:
-            raise SystemExit("--distortion-weight: the single-view loop only (the multi-view step has no distortion term)")
-        if rendered_w > 0:
-            raise SystemExit("--rendered-normal-consistency: the single-view loop only (the multi-view step renders no normals)")
         return train_multi_view(args, log)
     dev = torch.device("cuda:0")
     model, cams, targets = build(args, dev)
@@ -384,10 +391,11 @@ HELP = {
                      "(normals.normal_loss) with this weight; turns the depth gradient on",
     "normal_consistency": "single-view loop: > 0 adds normals.normal_consistency(depth, median_depth) with this weight "
                           "(return_median=True); the median's side moves the means only",
-    "distortion_weight": "single-view loop: > 0 adds W x the mean depth distortion of the view (return_distortion=True, the "
-                         "\"ndc\" mapping of 2DGS): pulls the layers a ray blends together in depth",
-    "rendered_normal_consistency": "single-view loop: > 0 adds normals.rendered_normal_consistency(normals, depth) with this "
-                                   "weight (return_normals=True): the rendered normal map against the normals of the rendered depth",
+    "distortion_weight": "> 0 adds W x the mean depth distortion of the view (return_distortion=True, the \"ndc\" mapping of "
+                         "2DGS): pulls the layers a ray blends together in depth; with --multi-view inside the step",
+    "rendered_normal_consistency": "> 0 adds normals.rendered_normal_consistency(normals, depth) with this weight "
+                                   "(return_normals=True): the rendered normal map against the normals of the rendered depth; "
+                                   "with --multi-view inside the step",
     "densify_grad_threshold": "clone / split threshold on the accumulated view-space gradient norm (reference: 0.0002).  Summed "
                               "magnitudes are larger than the signed norm: with --absgrad use about 4x (0.0008)",
 }

@@ -424,7 +424,7 @@ int lr_median_backward(const lr_median_backward_args* a);
  * rows in write mode, the depth-mode per-Gaussian backward.  The per-tile kernel OVERWRITES the per-instance gradient slots of the
  * binning buffer: the call runs after the colour backward (lr_view_backward) of the same forward state, on the same stream or
  * ordered behind it, and before another forward reuses the buffers.  An overflowed async view adds nothing.  No global float
- * atomics: bit-repeatable.  Not part of lr_views_accumulate.
+ * atomics: bit-repeatable.  In lr_views_accumulate the term runs fused with the rendered normal map's (lr_geometry_backward).
  */
 typedef struct lr_distortion_args {
     size_t struct_bytes;                     /* = sizeof(lr_distortion_args); anything else is LR_ERR_INVALID_ARG */
@@ -508,7 +508,8 @@ int lr_distortion_backward(const lr_distortion_backward_args* a);
  * zero-fill of rows in write mode, the per-Gaussian backward, the rotation chain.  The per-tile kernel OVERWRITES the per-instance
  * gradient slots of the binning buffer: the ordering rule is lr_distortion_backward's (behind the colour backward of the same
  * forward state -- and behind lr_distortion_backward, if both run -- and before another forward reuses the buffers).  An
- * overflowed async view adds nothing.  No global float atomics: bit-repeatable.  Not part of lr_views_accumulate.
+ * overflowed async view adds nothing.  No global float atomics: bit-repeatable.  In lr_views_accumulate the term runs fused with
+ * the distortion's (lr_geometry_backward).
  */
 typedef struct lr_normals_render_args {
     size_t struct_bytes;                     /* = sizeof(lr_normals_render_args); anything else is LR_ERR_INVALID_ARG */
@@ -554,6 +555,83 @@ int lr_render_normals(const lr_normals_render_args* a);
 int lr_render_normals_backward(const lr_normals_render_backward_args* a);
 
 /*
+ * Depth distortion AND rendered normal map of a forward in ONE tile walk each way (render_geom.hip): the pair the multi-view
+ * step runs for its two geometry regularisers.  The definitions are lr_render_distortion's and lr_render_normals', word for word
+ * -- the mapped depth m = map_c0 + map_c1 z + map_c2 / z, the shift by m_ref, D >= 0, N = sum_i w_i n_i, the forward's skips, 0.99
+ * clamp and 1e-4 stop; strict parity, anti-aliasing, the 3D filter, raw and activated parameters, both forward shapes, exact and
+ * async mode; zeros for an overflowed async view and for P = 0 -- and every pixel is updated with the separate passes' expressions
+ * in their order.  The argument structs are the unions of the two pairs' members.
+ *
+ * lr_render_geometry: the per-Gaussian normals first (out_gauss_normals [P,4], as lr_render_normals writes them), then one walk
+ * that writes out_distortion [1,H,W], out_moments [H,W,4] and out_normals [3,H,W]; all four outputs are required (P = 0:
+ * out_gauss_normals may be NULL).  cov3D_precomp has no normal: LR_ERR_INVALID_ARG.
+ *
+ * lr_geometry_backward: the gradient of both maps in one per-tile kernel and ONE per-Gaussian pass.  Upstreams: dL_ddistortion
+ * [1,H,W] and dL_dnormals [3,H,W]; either may be NULL and then contributes nothing (both NULL: nothing is walked, the zero-fill
+ * rule still holds).  With dL_ddistortion NULL, dL_ddistortion_scalar != 0 is the upstream of EVERY pixel (the step's weight x
+ * mean(D) has weight / (H W) everywhere: it saves an image); with the image given the scalar is not read.  `distortion` and
+ * `moments` are required with a distortion upstream, `normals` with dL_dnormals; gauss_normals, radii and dL_dgauss_normal [P,3]
+ * (written in full) always.  Per blended layer the two dL/dalpha contributions are added per pixel before they are multiplied
+ * out; the per-tile kernel leaves one GradRec per instance -- mean2D, conic, opacity, dL/dn in the colour floats, dL/dz in the free
+ * float -- and the depth-mode per-Gaussian backward, as it stands, takes it on with dL_dgauss_normal in the colour row's place;
+ * the rotation chain of lr_render_normals_backward follows.  The gradients agree with lr_distortion_backward +
+ * lr_render_normals_backward on the same upstreams up to the rounding of the reduction order.  Outputs, units, accumulate_mask,
+ * alignment: lr_normals_render_backward_args'.  The ordering rule is the same: behind the colour backward of the same forward
+ * state, and before another forward reuses the buffers (the per-tile kernel OVERWRITES the per-instance gradient slots).  An
+ * overflowed async view adds nothing.  No global float atomics: bit-repeatable.
+ */
+typedef struct lr_geometry_args {
+    size_t struct_bytes;                     /* = sizeof(lr_geometry_args); anything else is LR_ERR_INVALID_ARG */
+    lr_view view;                            /* the forward's: scales, rotations, means3D, viewmatrix, raw, P, width, height */
+    const int* radii;                        /* the forward's [P] */
+    const char* geom_buffer;
+    const char* binning_buffer;
+    const char* image_buffer;
+    long long binning_capacity;              /* the value the forward was given */
+    float map_c0, map_c1, map_c2;            /* m = map_c0 + map_c1 z + map_c2 / z */
+    float* out_distortion;
+    float* out_moments;
+    float* out_normals;
+    float* out_gauss_normals;
+    void* stream;
+} lr_geometry_args;
+
+typedef struct lr_geometry_backward_args {
+    size_t struct_bytes;                     /* = sizeof(lr_geometry_backward_args); anything else is LR_ERR_INVALID_ARG */
+    lr_view view;
+    char* geom_buffer;
+    char* binning_buffer;
+    char* image_buffer;
+    long long binning_capacity;
+    const float* dL_ddistortion;             /* [1,H,W] or NULL */
+    float dL_ddistortion_scalar;             /* with dL_ddistortion NULL: dL/dD of every pixel (0: no distortion term) */
+    const float* moments;
+    const float* distortion;
+    float map_c0, map_c1, map_c2;
+    const float* dL_dnormals;                /* [3,H,W] or NULL */
+    const float* normals;
+    const float* gauss_normals;
+    const int* radii;
+    float* dL_dgauss_normal;
+    /* gradient outputs, as lr_backward_args */
+    float* dL_dmean2D;
+    float* dL_dconic;
+    float* dL_dopacity;
+    float* dL_dcolor;
+    float* dL_dmean3D;
+    float* dL_dcov3D;                        /* never written: there is no normal with cov3D_precomp */
+    float* dL_dsh;
+    float* dL_dsh_rest;
+    float* dL_dscale;
+    float* dL_drot;
+    unsigned int accumulate_mask;
+    void* stream;
+} lr_geometry_backward_args;
+
+int lr_render_geometry(const lr_geometry_args* a);
+int lr_geometry_backward(const lr_geometry_backward_args* a);
+
+/*
  * Multi-view step (new; the reference renders one view per Python iteration, luciddreamer.py:291-304).
  * lr_views_accumulate runs lr_forward + the backward for n_views views of ONE parameter set and ACCUMULATES the gradients
  * into the acc_* buffers.  Everything is enqueued from C in one call: views alternate over up to 4 chains (forward of view
@@ -591,12 +669,31 @@ int lr_render_normals_backward(const lr_normals_render_backward_args* a);
  *       T_final of the view's forward); out_losses holds {loss, l1, ssim, depth_l1, alpha_hole} per view (depth_l1 = 0 without
  *       depth_targets, whose depth_weight is then ignored).  With alpha_weight == 0 the view gets no alpha gradient (for
  *       all-ones masks: the bits of the step without masks) and alpha_hole is still reported.
+ *     distortion_weight / normal_consistency_weight (members of lr_views_geom_args, below; each finite and >= 0; they need
+ *       targets, anything else is LR_ERR_INVALID_ARG): the two geometry regularisers.  A view of a step with a weight > 0 or with out_distortion /
+ *       out_normals given runs lr_render_geometry behind its blend forward, on the view's stream, and
+ *         loss += distortion_weight * mean(D),   D the depth distortion for distortion_map (c0, c1, c2),
+ *         loss += normal_consistency_weight * sum_valid (1 - N . n) / (H W),   N the rendered normal map, n the normals of the
+ *           view's rendered depth by lr_depth_normals' formula and validity rule (a pixel that is not valid adds nothing):
+ *           the consistency term of lr_normal_loss_forward with N as target_normals, not normalised.
+ *       out_losses then has SEVEN columns per view, {loss, l1, ssim, depth term, alpha_hole, distortion, normal_consistency}
+ *       (mean(D) and the unweighted sum / (H W); absent terms 0); without the two terms it keeps its 3 / 4 / 5 columns.
+ *       Backward: dL/dN = -weight n / (H W) on the valid pixels and the scalar weight / (H W) for dL/dD drive
+ *       lr_geometry_backward behind the view's colour backward; its accumulation sits in the event chain that orders the views'.
+ *       dL/ddepth of the normal term (through n) is added to the view's depth-gradient image: a step with
+ *       normal_consistency_weight > 0 runs the depth-mode blend backward, with or without depth_targets.  A weight of 0 reports
+ *       the term and leaves the gradients of the step without it, to the bit; with both weights 0 and no map asked for the pass
+ *       does not run and the two columns are 0.  An overflowed view adds nothing and stays latched.
+ *       The densification statistics (below) keep meaning the view's photometric / depth / alpha gradient: the geometry pass
+ *       adds nothing to stat_grad_accum (with the normal term the depth part of G_v includes that term's dL/ddepth).
  * Workspace: lr_views_workspace_bytes(P, W, H, binning_capacity, n_streams, parts) device bytes, 256-byte aligned, with
  * `parts` the LR_VIEWS_* flags of what the step's slots hold besides a view's scratch: 0 for fixed gradients, LR_VIEWS_LOSS
  * with targets, | LR_VIEWS_DEPTH_LOSS with depth_targets, | LR_VIEWS_MASK_LOSS with masks (a mask step's slot always has the
  * depth part too: LOSS|MASK and LOSS|DEPTH|MASK are one layout), | LR_VIEWS_DEPTH_PEARSON with depth_loss ==
  * LR_DEPTH_LOSS_PEARSON (the slot's depth-loss workspace is then the larger one of lr_depth_pearson_workspace_bytes; valid only
- * together with LOSS and DEPTH or MASK; every other parts value keeps its sizes).  DEPTH or MASK without LOSS, or unknown bits, are invalid:
+ * together with LOSS and DEPTH or MASK; every other parts value keeps its sizes), | LR_VIEWS_GEOM when the step runs the geometry
+ * pass (a weight > 0, or out_distortion / out_normals given; valid only together with LOSS; its part sits behind everything else in
+ * a slot, so every parts value without it keeps its sizes).  DEPTH, MASK or GEOM without LOSS, or unknown bits, are invalid:
  * the size query returns 0 and lr_views_check LR_ERR_INVALID_ARG.  lr_views_check takes the values the step was run with.
  * Densification statistics (0.6.3): with stat_grad_accum, stat_denom and stat_max_radii [P] given -- all three or none, anything
  * else is LR_ERR_INVALID_ARG, as is stat_absgrad != 0 without them; 4-byte aligned, accumulated into, no accumulate-mask bit
@@ -621,13 +718,14 @@ int lr_render_normals_backward(const lr_normals_render_backward_args* a);
 #define LR_VIEWS_DEPTH_LOSS  2u   /* ... and the depth gradient image + depth-L1 workspace      */
 #define LR_VIEWS_MASK_LOSS   4u   /* ... and the alpha gradient image + alpha-hole workspace    */
 #define LR_VIEWS_DEPTH_PEARSON 16u /* the depth-loss workspace holds the Pearson term's (8u is not a flag) */
+#define LR_VIEWS_GEOM        64u  /* ... and the geometry pass's maps, upstream images and workspace (32u is not a flag) */
 
 /* lr_views_args::depth_loss */
 #define LR_DEPTH_LOSS_L1      0   /* masked depth L1 (lr_depth_l1_*) */
 #define LR_DEPTH_LOSS_PEARSON 1   /* 1 - Pearson correlation (lr_depth_pearson_*) */
 
 typedef struct lr_views_args {
-    size_t struct_bytes;                     /* = sizeof(lr_views_args); anything else is LR_ERR_INVALID_ARG */
+    size_t struct_bytes;                     /* = sizeof(lr_views_args) (as lr_views_geom_args::base: of that struct) */
     /* the views: n_views and per-view camera data (all required) */
     int n_views;
     const float* const* viewmatrices;
@@ -694,6 +792,23 @@ typedef struct lr_views_args {
     int depth_loss;
 } lr_views_args;
 
+/*
+ * lr_views_args with the two geometry regularisers of the fused training step (see above).  Their members lie behind depth_loss,
+ * for the reason given there: `base` is the first member, so they follow everything lr_views_args holds, the struct has another
+ * sizeof, and lr_views_args itself keeps its layout, with depth_loss as its last member.  A step with the terms passes
+ * &args.base to lr_views_accumulate with base.struct_bytes = sizeof(lr_views_geom_args); struct_bytes = sizeof(lr_views_args)
+ * is the step without them.  All zero / NULL: that step, to the bit.
+ */
+typedef struct lr_views_geom_args {
+    lr_views_args base;                      /* base.struct_bytes = sizeof(lr_views_geom_args) */
+    float distortion_weight;                 /* finite, >= 0 */
+    float distortion_map[3];                 /* c0, c1, c2 of m = c0 + c1 z + c2 / z; read when the distortion is formed */
+    float normal_consistency_weight;         /* finite, >= 0 */
+    float* const* out_distortion;            /* optional per-view outputs [1,H,W] / [3,H,W], under out_depth's NULL rules */
+    float* const* out_normals;
+} lr_views_geom_args;
+
+/* a->struct_bytes: sizeof(lr_views_args), or sizeof(lr_views_geom_args) for the base of one; anything else is LR_ERR_INVALID_ARG */
 int lr_views_accumulate(const lr_views_args* a);
 size_t lr_views_workspace_bytes(int P, int width, int height, long long binning_capacity, int n_streams, unsigned parts);
 int lr_views_check(const char* workspace, int P, int width, int height, long long binning_capacity, int n_streams,

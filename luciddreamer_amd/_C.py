@@ -340,6 +340,90 @@ def render_normals_backward(geomBuffer, binningBuffer, imageBuffer, dL_dnormals,
     return out
 
 
+def render_geometry(geomBuffer, binningBuffer, imageBuffer, radii, rs, *, means3D, scales, rotations, cov3D_precomp=None, raw=False,
+                    distortion_map="ndc", binning_capacity=0):
+    """(distortion (1, H, W), moments (H, W, 4), normals (3, H, W), gauss_normals (P, 4)): render_distortion and render_normals in
+    ONE tile walk (lr_render_geometry, on the current stream) -- the pass the multi-view step runs.  Arguments as render_normals,
+    with render_distortion's distortion_map.  ValueError with cov3D_precomp, before any launch.  No autograd."""
+    import torch
+    require_scale_rot("render_geometry", scales, rotations, cov3D_precomp)
+    dev = imageBuffer.device
+    P = int(means3D.shape[0])
+    H, W = int(rs.image_height), int(rs.image_width)
+    c0, c1, c2 = distortion_map_coefficients(distortion_map)
+    dist = torch.empty((1, H, W), dtype=torch.float32, device=dev)
+    mom = torch.empty((H, W, 4), dtype=torch.float32, device=dev)
+    normals = torch.empty((3, H, W), dtype=torch.float32, device=dev)
+    gauss_normals = torch.empty((P, 4), dtype=torch.float32, device=dev)
+    v, keep = _normals_view(rs, P, means3D, None, scales, rotations, raw)
+    rad = radii.contiguous()
+    a = _lib_check.GeometryArgs(view=v, radii=rad.data_ptr(), geom_buffer=geomBuffer.data_ptr(),
+                                binning_buffer=binningBuffer.data_ptr(), image_buffer=imageBuffer.data_ptr(),
+                                binning_capacity=int(binning_capacity), map_c0=c0, map_c1=c1, map_c2=c2,
+                                out_distortion=dist.data_ptr(), out_moments=mom.data_ptr(), out_normals=normals.data_ptr(),
+                                out_gauss_normals=gauss_normals.data_ptr(), stream=torch.cuda.current_stream(dev).cuda_stream)
+    with _lib_check.on_device(dev):
+        rc = _lib_check.lib().lr_render_geometry(a)
+    if rc < 0:
+        _lib_check.raise_for(rc, "render_geometry")
+    del keep
+    return dist, mom, normals, gauss_normals
+
+
+def geometry_backward(geomBuffer, binningBuffer, imageBuffer, dL_ddistortion, distortion, moments, dL_dnormals, normals,
+                      gauss_normals, radii, rs, *, means3D, opacities=None, scales=None, rotations=None, cov3D_precomp=None, raw=False,
+                      distortion_map="ndc", binning_capacity=0, accumulate_into=None):
+    """The gradient of both maps of render_geometry in one per-tile kernel and one per-Gaussian pass (lr_geometry_backward, on the
+    current stream, behind the colour backward of the same forward).  dL_ddistortion: (1, H, W), a Python number (the upstream of
+    every pixel) or None; dL_dnormals: (3, H, W) or None; an absent upstream contributes nothing.  The other arguments and the
+    returned dict are render_normals_backward's."""
+    import torch
+    require_scale_rot("geometry_backward", scales, rotations, cov3D_precomp)
+    dev = imageBuffer.device
+    P = int(means3D.shape[0])
+    H, W = int(rs.image_height), int(rs.image_width)
+    c0, c1, c2 = distortion_map_coefficients(distortion_map)
+    cont = lambda t: t.detach().contiguous().float()
+    scalar = float(dL_ddistortion) if isinstance(dL_ddistortion, (int, float)) else 0.0
+    dD = cont(dL_ddistortion) if isinstance(dL_ddistortion, torch.Tensor) else None
+    dN = cont(dL_dnormals) if dL_dnormals is not None else None
+    dist, mom, nrm, gn, rad = cont(distortion), cont(moments), cont(normals), cont(gauss_normals), radii.contiguous()
+    if raw and opacities is None:
+        raise RuntimeError("geometry_backward: raw mode needs the stored opacities")
+    if (dD is not None and dD.numel() != H * W) or dist.numel() != H * W or mom.numel() != 4 * H * W:
+        raise RuntimeError("geometry_backward: dL_ddistortion, distortion and moments must be (1, H, W), (1, H, W), (H, W, 4)")
+    if (dN is not None and dN.numel() != 3 * H * W) or nrm.numel() != 3 * H * W or gn.numel() != 4 * P:
+        raise RuntimeError("geometry_backward: dL_dnormals, normals and gauss_normals must be (3, H, W), (3, H, W), (P, 4)")
+    shapes = {"means2D": (P, 3), "opacity": (P, 1), "means3D": (P, 3), "scales": (P, 3), "rotations": (P, 4)}
+    bits = {"means2D": 0, "opacity": 2, "means3D": 4, "scales": 7, "rotations": 8}
+    out, mask = {}, 0
+    for name, shape in shapes.items():
+        t = (accumulate_into or {}).get(name)
+        if t is not None:
+            if not t.is_contiguous() or t.dtype != torch.float32 or t.numel() != int(torch.Size(shape).numel()):
+                raise RuntimeError(f"geometry_backward: accumulate_into[{name!r}] must be a contiguous float32 tensor of {shape}")
+            out[name] = t
+            mask |= 1 << bits[name]
+        else:
+            out[name] = torch.empty(shape, dtype=torch.float32, device=dev)
+    out["gauss_normal"] = torch.empty((P, 3), dtype=torch.float32, device=dev)
+    v, keep = _normals_view(rs, P, means3D, opacities, scales, rotations, raw)
+    a = _lib_check.GeometryBackwardArgs(
+        view=v, geom_buffer=geomBuffer.data_ptr(), binning_buffer=binningBuffer.data_ptr(), image_buffer=imageBuffer.data_ptr(),
+        binning_capacity=int(binning_capacity), dL_ddistortion=dD.data_ptr() if dD is not None else None,
+        dL_ddistortion_scalar=scalar, moments=mom.data_ptr(), distortion=dist.data_ptr(), map_c0=c0, map_c1=c1, map_c2=c2,
+        dL_dnormals=dN.data_ptr() if dN is not None else None, normals=nrm.data_ptr(), gauss_normals=gn.data_ptr(),
+        radii=rad.data_ptr(), dL_dgauss_normal=out["gauss_normal"].data_ptr(), dL_dmean2D=out["means2D"].data_ptr(),
+        dL_dopacity=out["opacity"].data_ptr(), dL_dmean3D=out["means3D"].data_ptr(), dL_dscale=out["scales"].data_ptr(),
+        dL_drot=out["rotations"].data_ptr(), accumulate_mask=mask, stream=torch.cuda.current_stream(dev).cuda_stream)
+    with _lib_check.on_device(dev):
+        rc = _lib_check.lib().lr_geometry_backward(a)
+    if rc < 0:
+        _lib_check.raise_for(rc, "geometry_backward")
+    del keep
+    return out
+
+
 # forward + backward of one view in one call for a caller that holds dL/dcolor up front; [] = an input does not qualify
 rasterize_view_step = _C_ext.rasterize_view_step
 last_num_rendered = _C_ext.last_num_rendered

@@ -29,6 +29,7 @@ _lock = threading.Lock()
 EXPORTS = ("lr_last_error", "lr_version", "lr_geom_bytes", "lr_img_bytes", "lr_binning_bytes", "lr_forward",
            "lr_backward", "lr_view_forward", "lr_view_backward", "lr_render_alpha", "lr_render_median", "lr_median_backward",
            "lr_render_distortion", "lr_distortion_backward", "lr_render_normals", "lr_render_normals_backward",
+           "lr_render_geometry", "lr_geometry_backward",
            "lr_mark_visible", "lr_check",
            "lr_dist2_workspace_bytes", "lr_dist2",
            "lr_dist2_workspace_layout",
@@ -52,6 +53,7 @@ EXPORTS = ("lr_last_error", "lr_version", "lr_geom_bytes", "lr_img_bytes", "lr_b
 # lr_views_workspace_bytes / lr_views_check `parts`: what a step's workspace slots hold besides a view's scratch
 LR_VIEWS_LOSS, LR_VIEWS_DEPTH_LOSS, LR_VIEWS_MASK_LOSS = 1, 2, 4
 LR_VIEWS_DEPTH_PEARSON = 16         # the slot's depth-loss workspace is the Pearson term's (8 is not a flag)
+LR_VIEWS_GEOM = 64                  # the slot holds the geometry pass's maps, upstream images and workspace (32 is not a flag)
 # lr_views_args.depth_loss: the depth term of the fused training step
 LR_DEPTH_LOSS_L1, LR_DEPTH_LOSS_PEARSON = 0, 1
 
@@ -86,7 +88,16 @@ class ViewsArgs(ctypes.Structure):
                 ("depth_loss", _ci)]
 
     def __init__(self, **fields):
-        super().__init__(struct_bytes=ctypes.sizeof(ViewsArgs), **fields)
+        super().__init__(struct_bytes=ctypes.sizeof(type(self)), **fields)
+
+
+class ViewsGeomArgs(ViewsArgs):
+    """lr_views_geom_args: lr_views_args as its first member (`base`; here the base class, so its members read as this struct's
+    own) and the two geometry regularisers' members behind it.  struct_bytes is this struct's size; lr_views_accumulate takes it
+    where it takes a ViewsArgs.  All zero / NULL: the step without the terms."""
+    _vp, _cf = ctypes.c_void_p, ctypes.c_float
+    _fields_ = [("distortion_weight", _cf), ("distortion_map", _cf * 3), ("normal_consistency_weight", _cf),
+                ("out_distortion", _vp), ("out_normals", _vp)]                                             # [] []
 
 
 class View(ctypes.Structure):
@@ -200,6 +211,34 @@ class NormalsRenderBackwardArgs(ctypes.Structure):
 
     def __init__(self, **fields):
         super().__init__(struct_bytes=ctypes.sizeof(NormalsRenderBackwardArgs), **fields)
+
+
+class GeometryArgs(ctypes.Structure):
+    """lr_geometry_args, field for field (tests/test_geom_views_cpu.py compares the offsets with the host compiler's)."""
+    _vp, _cf = ctypes.c_void_p, ctypes.c_float
+    _fields_ = [("struct_bytes", ctypes.c_size_t), ("view", View), ("radii", _vp),
+                ("geom_buffer", _vp), ("binning_buffer", _vp), ("image_buffer", _vp), ("binning_capacity", ctypes.c_longlong),
+                ("map_c0", _cf), ("map_c1", _cf), ("map_c2", _cf),
+                ("out_distortion", _vp), ("out_moments", _vp), ("out_normals", _vp), ("out_gauss_normals", _vp), ("stream", _vp)]
+
+    def __init__(self, **fields):
+        super().__init__(struct_bytes=ctypes.sizeof(GeometryArgs), **fields)
+
+
+class GeometryBackwardArgs(ctypes.Structure):
+    """lr_geometry_backward_args, field for field."""
+    _vp, _cf = ctypes.c_void_p, ctypes.c_float
+    _fields_ = [("struct_bytes", ctypes.c_size_t), ("view", View),
+                ("geom_buffer", _vp), ("binning_buffer", _vp), ("image_buffer", _vp), ("binning_capacity", ctypes.c_longlong),
+                ("dL_ddistortion", _vp), ("dL_ddistortion_scalar", _cf), ("moments", _vp), ("distortion", _vp),
+                ("map_c0", _cf), ("map_c1", _cf), ("map_c2", _cf),
+                ("dL_dnormals", _vp), ("normals", _vp), ("gauss_normals", _vp), ("radii", _vp), ("dL_dgauss_normal", _vp),
+                ("dL_dmean2D", _vp), ("dL_dconic", _vp), ("dL_dopacity", _vp), ("dL_dcolor", _vp), ("dL_dmean3D", _vp),
+                ("dL_dcov3D", _vp), ("dL_dsh", _vp), ("dL_dsh_rest", _vp), ("dL_dscale", _vp), ("dL_drot", _vp),
+                ("accumulate_mask", ctypes.c_uint), ("stream", _vp)]
+
+    def __init__(self, **fields):
+        super().__init__(struct_bytes=ctypes.sizeof(GeometryBackwardArgs), **fields)
 
 
 def distortion_map_coefficients(distortion_map):
@@ -360,6 +399,10 @@ def lib():
         L.lr_render_normals.argtypes = [ctypes.POINTER(NormalsRenderArgs)]
         L.lr_render_normals_backward.restype = ci
         L.lr_render_normals_backward.argtypes = [ctypes.POINTER(NormalsRenderBackwardArgs)]
+        L.lr_render_geometry.restype = ci
+        L.lr_render_geometry.argtypes = [ctypes.POINTER(GeometryArgs)]
+        L.lr_geometry_backward.restype = ci
+        L.lr_geometry_backward.argtypes = [ctypes.POINTER(GeometryBackwardArgs)]
         L.lr_mark_visible.restype = ci
         L.lr_mark_visible.argtypes = [ci, vp, vp, vp, vp, vp]
         L.lr_check.restype = ci

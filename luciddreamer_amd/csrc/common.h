@@ -511,6 +511,15 @@ void launch_normals_bwd(int W, int H, int P, const GeomView& g, const ImgView& i
                         const float* normals, const float* gauss_normals, hipStream_t s);
 void launch_normal_rot_bwd(int P, bool raw, const float* rotations, const float* view, const int* radii, const GeomView& g,
                            const float* gauss_normals, const float* dL_dgauss_normal, float* dL_drot, hipStream_t s);
+// both of the above in one tile walk each way (render_geom.hip): the outputs of launch_render_distort and launch_render_normals
+// from gauss_normals as launch_gauss_normals wrote it; the gradient of both as ONE GradRec per instance in inst_grad (colour floats:
+// dL/dn, pad0: dL/dz).  dL_ddistortion NULL: dist_scalar is every pixel's dL/dD (0: no distortion term, distortion / moments are
+// not read); dL_dnormals NULL: no normal term (normals is not read).
+void launch_render_geom(int W, int H, int P, const GeomView& g, const ImgView& im, const char* bin_base, const float* gauss_normals,
+                        float c0, float c1, float c2, float* out_distortion, float* out_moments, float* out_normals, hipStream_t s);
+void launch_geom_bwd(int W, int H, int P, const GeomView& g, const ImgView& im, char* bin_base, const float* dL_ddistortion,
+                     float dist_scalar, const float* distortion, const float* moments, float c0, float c1, float c2,
+                     const float* dL_dnormals, const float* normals, const float* gauss_normals, hipStream_t s);
 // The upstream gradients a view's backward is given.
 struct ViewGrads {
     const float* color;     // dL_dpix [3,H,W]
@@ -679,6 +688,26 @@ void launch_depth_normals(const lr_normals_args& a, hipStream_t s);
 void launch_depth_normals_backward(const lr_normals_args& a, hipStream_t s);
 void launch_normal_loss_forward(const lr_normals_args& a, hipStream_t s);
 void launch_normal_loss_backward(const lr_normals_args& a, hipStream_t s);
+// The two geometry terms of a view of the multi-view step (normals.hip): mean(D) of `distortion` [H*W] and the consistency term
+// sum (1 - N.n) / (H W) between `normals` (N, the rendered map [3,H,W]) and n_io (n, what launch_depth_normals wrote), into the
+// view's seven-column row: out_row[5], out_row[6], out_row[0] += distortion_weight [5] + normal_weight [6], and 0 in the depth /
+// alpha_hole columns the step does not have.  normal_weight != 0: n_io becomes dL/dN = -normal_weight n / (H W) and gn_up [3,H,W]
+// receives dL/dn = -normal_weight N / (H W), the upstream of launch_depth_normals_backward; otherwise neither is written.
+// ws: geom_terms_workspace_bytes.  launch_plane_add: dst[i] += src[i].
+struct GeomTerms {
+    int H, W;
+    const float* distortion;
+    const float* normals;
+    float* n_io;
+    float* gn_up;
+    float distortion_weight, normal_weight;
+    bool row_has_depth, row_has_alpha;
+    char* ws;
+    float* out_row;
+};
+size_t geom_terms_workspace_bytes(int H, int W);
+void launch_geom_terms(const GeomTerms& t, hipStream_t s);
+void launch_plane_add(long long n, float* dst, const float* src, hipStream_t s);
 
 // video frames on the device (video.hip)
 size_t video_workspace_bytes(int n_frames);

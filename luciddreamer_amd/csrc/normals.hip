@@ -262,6 +262,82 @@ k_normal_loss_bwd(Plane g, int blocks_x, LossIn in, float weight, const float* _
     gather_tile(g, blocks_x, s, grad, [&](int x, int y) { return loss_terms<CONSIST>(g, in, x, y, k); });
 }
 
+// ---- the two geometry terms of the multi-view step (lr_views_accumulate with distortion_weight / normal_consistency_weight) ----
+// k_geom_terms: per pixel the distortion D and the consistency term 1 - N.n between the rendered normal map N and the depth
+// normals n (what k_depth_normals wrote: an invalid pixel is (0,0,0) and adds nothing), {sum D, sum (1 - N.n)} per workgroup in
+// double and a fixed order, the shape of k_normal_loss_fwd.  With kn = weight / (H W) != 0 it also leaves the two upstream images
+// of the term's backward: dL/dN = -kn n IN PLACE of n (exact zeros on the invalid pixels) and dL/dn = -kn N in gn_up (what
+// k_depth_normals_bwd takes as Gn; it skips the invalid pixels itself).
+__global__ void __launch_bounds__(NTHREADS)
+k_geom_terms(int H, int W, int blocks_x, const float* __restrict__ dist, const float* __restrict__ nmap, float* __restrict__ n_io,
+             float* __restrict__ gn_up, float kn, double2* __restrict__ partials)
+{
+    __shared__ double s_d[NTHREADS / 64], s_c[NTHREADS / 64];
+    const int bx = (int)(blockIdx.x % (unsigned)blocks_x), by = (int)(blockIdx.x / (unsigned)blocks_x);
+    const int x = bx * NB_X + (int)(threadIdx.x & (NB_X - 1));
+    const size_t n = (size_t)H * (size_t)W;
+    double vd = 0.0, vc = 0.0;
+#pragma unroll
+    for (int r = 0; r < FWD_ROWS / NB_Y; r++) {          // rows ty, ty + 4, ...: summed in this order
+        const int y = by * FWD_ROWS + r * NB_Y + (int)(threadIdx.x / NB_X);
+        if (x < W && y < H) {
+            const size_t i = (size_t)y * (size_t)W + (size_t)x;
+            vd += (double)dist[i];
+            const float n0 = n_io[i], n1 = n_io[i + n], n2 = n_io[i + 2 * n];
+            const float N0 = nmap[i], N1 = nmap[i + n], N2 = nmap[i + 2 * n];
+            const bool valid = n0 != 0.f || n1 != 0.f || n2 != 0.f;
+            if (valid) vc += (double)(1.0f - ((N0 * n0 + N1 * n1) + N2 * n2));
+            if (kn != 0.f) {
+                n_io[i] = valid ? -(kn * n0) : 0.f; n_io[i + n] = valid ? -(kn * n1) : 0.f; n_io[i + 2 * n] = valid ? -(kn * n2) : 0.f;
+                gn_up[i] = -(kn * N0); gn_up[i + n] = -(kn * N1); gn_up[i + 2 * n] = -(kn * N2);
+            }
+        }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        vd += __shfl_xor(vd, off);
+        vc += __shfl_xor(vc, off);
+    }
+    const int wv = (int)threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) { s_d[wv] = vd; s_c[wv] = vc; }
+    lds_barrier();
+    if (threadIdx.x == 0)
+        partials[blockIdx.x] = make_double2((s_d[0] + s_d[1]) + (s_d[2] + s_d[3]), (s_c[0] + s_c[1]) + (s_c[2] + s_c[3]));
+}
+
+// one workgroup: the partials in a fixed order -> the view's seven-column row {loss, l1, ssim, depth term, alpha_hole, distortion,
+// normal_consistency}: out[5] = mean(D), out[6] = sum (1 - N.n) / (H W), out[0] += wd out[5] + wn out[6]; the columns of a term
+// the step does not have are set to 0.  Behind every other term of the row on the view's stream.
+__global__ void __launch_bounds__(NTHREADS)
+k_geom_terms_final(int n_blocks, double n_elems, float wd, float wn, int row_has_depth, int row_has_alpha,
+                   const double2* __restrict__ partials, float* __restrict__ out)
+{
+    __shared__ double s_a[NTHREADS], s_b[NTHREADS];
+    double a = 0.0, b = 0.0;
+    for (int i = (int)threadIdx.x; i < n_blocks; i += NTHREADS) { const double2 p = partials[i]; a += p.x; b += p.y; }
+    s_a[threadIdx.x] = a; s_b[threadIdx.x] = b;
+    lds_barrier();
+    for (int off = NTHREADS / 2; off > 0; off >>= 1) {
+        if ((int)threadIdx.x < off) { s_a[threadIdx.x] += s_a[threadIdx.x + off]; s_b[threadIdx.x] += s_b[threadIdx.x + off]; }
+        lds_barrier();
+    }
+    if (threadIdx.x == 0) {
+        const float d = (float)(s_a[0] / n_elems), c = (float)(s_b[0] / n_elems);
+        out[0] = (out[0] + wd * d) + wn * c;
+        if (!row_has_depth) out[3] = 0.f;
+        if (!row_has_alpha) out[4] = 0.f;
+        out[5] = d;
+        out[6] = c;
+    }
+}
+
+// dst += src, elementwise
+__global__ void __launch_bounds__(256) k_plane_add(long long n, float* __restrict__ dst, const float* __restrict__ src)
+{
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) dst[i] += src[i];
+}
+
 Plane plane_of(const lr_normals_args& a)
 {
     Plane g;
@@ -322,6 +398,25 @@ void launch_normal_loss_backward(const lr_normals_args& a, hipStream_t s)
         hipLaunchKernelGGL(k_normal_loss_bwd<true>, dim3(blocks), dim3(NTHREADS), 0, s, plane_of(a), bx, swapped, a.weight,
                            a.upstream, a.dL_dtarget_depth);
     }
+}
+
+size_t geom_terms_workspace_bytes(int H, int W) { return align_up((size_t)blocks_of(H, W, FWD_ROWS) * sizeof(double2)); }
+
+void launch_geom_terms(const GeomTerms& t, hipStream_t s)
+{
+    const int blocks = blocks_of(t.H, t.W, FWD_ROWS);
+    double2* partials = reinterpret_cast<double2*>(t.ws);
+    const float kn = t.normal_weight / (float)(t.H * t.W);
+    hipLaunchKernelGGL(k_geom_terms, dim3(blocks), dim3(NTHREADS), 0, s, t.H, t.W, blocks_x_of(t.W), t.distortion, t.normals, t.n_io,
+                       t.gn_up, kn, partials);
+    hipLaunchKernelGGL(k_geom_terms_final, dim3(1), dim3(NTHREADS), 0, s, blocks, (double)t.H * (double)t.W, t.distortion_weight,
+                       t.normal_weight, t.row_has_depth ? 1 : 0, t.row_has_alpha ? 1 : 0, partials, t.out_row);
+}
+
+void launch_plane_add(long long n, float* dst, const float* src, hipStream_t s)
+{
+    if (n <= 0) return;
+    hipLaunchKernelGGL(k_plane_add, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, n, dst, src);
 }
 
 }  // namespace lr

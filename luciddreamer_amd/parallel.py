@@ -870,7 +870,10 @@ class ViewBatch:
                  depths: Optional[Sequence[torch.Tensor]] = None,
                  grad_alphas: Optional[Sequence[torch.Tensor]] = None, masks: Optional[Sequence[torch.Tensor]] = None,
                  alpha_weight: Optional[float] = None, alphas: Optional[Sequence[torch.Tensor]] = None,
-                 densify_stats: Optional[str] = None, depth_loss: str = "l1"):
+                 densify_stats: Optional[str] = None, depth_loss: str = "l1",
+                 distortion_weight: Optional[float] = None, distortion_map="ndc",
+                 normal_consistency_weight: Optional[float] = None,
+                 distortions: Optional[Sequence[torch.Tensor]] = None, normal_maps: Optional[Sequence[torch.Tensor]] = None):
         """grad_colors: fixed upstream gradients dL/dcolor per view, OR targets: ground-truth images per view, in which
         case every view's L1 + DSSIM loss against its target is formed inside the call (lr_views_accumulate with targets) and
         `self.losses` ([n,3] device tensor: loss, l1, ssim per view) is filled by run().
@@ -904,6 +907,20 @@ class ViewBatch:
             ("absgrad": its absolute one, AbsGS) and radii: the norm per view, then the sum -- which `acc["means2D"]`, the signed
             sum over the views, cannot give.  "grad" leaves the step's gradients bit for bit; "absgrad" runs every view's blend
             backward in the absgrad kernel shape (gradients equal up to the rounding of the reduction order).
+            With the geometry regularisers below the statistics keep meaning the view's photometric / depth / alpha gradient: the
+            geometry pass adds nothing to them (only the normal term's dL/d depth, which travels in the view's depth-gradient
+            image, is part of the depth gradient they see).
+        Geometry regularisers (with targets; the arguments are the opt-in; one fused pass each way per view,
+        lr_render_geometry / lr_geometry_backward, behind the view's blend forward and colour backward):
+          distortion_weight (>= 0): loss += distortion_weight * mean(D), D the depth distortion (return_distortion=True of the
+            rasterizer) for distortion_map: "ndc", ("ndc", near, far) or "linear", the rasterizer's spelling;
+          normal_consistency_weight (>= 0): loss += normals.rendered_normal_consistency(N, depth, cam, weight) with N the
+            rendered normal map (return_normals=True) and depth the view's rendered depth; its dL/d depth joins the view's
+            depth-gradient image, so the view's blend backward is the depth-mode one.
+          With either argument `self.losses` is [n,7]: loss, l1, ssim, depth term, alpha_hole, distortion (= mean(D)),
+            normal_consistency (unweighted); absent terms are 0.  A weight of 0 reports the term and leaves the gradients of
+            the step without it.
+          distortions / normal_maps: per-view [1,H,W] / [3,H,W] contiguous float32 device tensors that run() fills with D / N.
         Arguments are checked before any device work."""
         import ctypes
         import math
@@ -923,6 +940,9 @@ class ViewBatch:
         self._check_optional_args(grad_colors, targets, grad_depths, depth_targets, depth_weight, depths, grad_alphas, masks,
                                   alpha_weight, alphas, depth_loss)
         from . import _lib
+        self.geom = self._check_geom_args(targets, distortion_weight, distortion_map, normal_consistency_weight, distortions,
+                                          normal_maps)
+        map_c = _lib.distortion_map_coefficients(distortion_map)
         self._lib = _lib
         self.L = _lib.lib()
         self.device = self.cams[0].world_view_transform.device
@@ -931,12 +951,20 @@ class ViewBatch:
         self.train = targets is not None
         self.depths = list(depths) if depths is not None else None
         self.alphas = list(alphas) if alphas is not None else None
-        n_losses = 5 if masks is not None else 4 if depth_targets is not None else 3
+        self.distortions = list(distortions) if distortions is not None else None
+        self.normal_maps = list(normal_maps) if normal_maps is not None else None
+        n_losses = 7 if self.geom else 5 if masks is not None else 4 if depth_targets is not None else 3
         self.losses = torch.zeros((self.n, n_losses), dtype=torch.float32, device=self.device) if self.train else None
         # what a workspace slot holds besides a view's scratch (lr_views_workspace_bytes, lr_views_check)
         self.parts = ((_lib.LR_VIEWS_LOSS if self.train else 0) | (_lib.LR_VIEWS_DEPTH_LOSS if depth_targets is not None else 0) |
                       (_lib.LR_VIEWS_MASK_LOSS if masks is not None else 0) |
-                      (_lib.LR_VIEWS_DEPTH_PEARSON if depth_loss == "pearson" else 0))
+                      (_lib.LR_VIEWS_DEPTH_PEARSON if depth_loss == "pearson" else 0) |
+                      (_lib.LR_VIEWS_GEOM if self.geom else 0))
+        # The library runs the geometry pass for a weight > 0 or a map asked for.  Terms given with weight 0 and no map of the
+        # caller's are still reported: run() then asks for the distortion maps into tensors of its own, allocated on first use
+        self._geom_report_only = (self.geom and not (distortion_weight or 0.0) > 0.0 and not (normal_consistency_weight or 0.0) > 0.0
+                                  and distortions is None and normal_maps is None)
+        self._geom_scratch = None
         self._keep = []                     # what the host arrays below point to, and the arrays themselves
 
         def host_array(values, ctype=ctypes.c_void_p):
@@ -954,7 +982,11 @@ class ViewBatch:
         def outputs(tensors):               # ... of the caller's own tensors (checked above: on the device, contiguous)
             return None if tensors is None else host_array(t.data_ptr() for t in tensors)
         # everything that is fixed for the batch; run() adds the parameters, the accumulators and the workspace
-        self._args = _lib.ViewsArgs(
+        # (a step with the geometry regularisers passes lr_views_geom_args, whose first member is lr_views_args)
+        geom_fields = dict(distortion_weight=float(distortion_weight or 0.0), distortion_map=(ctypes.c_float * 3)(*map_c),
+                           normal_consistency_weight=float(normal_consistency_weight or 0.0),
+                           out_distortion=outputs(self.distortions), out_normals=outputs(self.normal_maps)) if self.geom else {}
+        self._args = (_lib.ViewsGeomArgs if self.geom else _lib.ViewsArgs)(
             n_views=self.n, viewmatrices=inputs([c.world_view_transform for c in self.cams]),
             projmatrices=inputs([c.full_proj_transform for c in self.cams]),
             cam_positions=inputs([c.camera_center for c in self.cams]),
@@ -968,7 +1000,7 @@ class ViewBatch:
             out_losses=self.losses.data_ptr() if self.train else None,
             out_depth=outputs(self.depths), out_alpha=outputs(self.alphas), binning_capacity=self.capacity,
             stat_absgrad=1 if densify_stats == "absgrad" else 0,
-            depth_loss=_lib.LR_DEPTH_LOSS_PEARSON if depth_loss == "pearson" else _lib.LR_DEPTH_LOSS_L1)
+            depth_loss=_lib.LR_DEPTH_LOSS_PEARSON if depth_loss == "pearson" else _lib.LR_DEPTH_LOSS_L1, **geom_fields)
         self._ws = None
         self._ws_key = None
 
@@ -1015,6 +1047,32 @@ class ViewBatch:
                         raise ValueError(f"{name}: outputs must be contiguous float32 tensors on the HIP device")
                     if rule == "float32" and t.dtype is not torch.float32:
                         raise ValueError(f"{name}: float32 tensors (loss.content_mask)")
+
+    def _check_geom_args(self, targets, distortion_weight, distortion_map, normal_consistency_weight, distortions, normal_maps):
+        """The geometry regularisers' arguments; True when the step has them (a weight given, 0 included, or a map asked for)."""
+        import math
+        from . import _lib
+        _lib.distortion_map_coefficients(distortion_map)                 # ValueError for a spelling the rasterizer does not take
+        on = any(x is not None for x in (distortion_weight, normal_consistency_weight, distortions, normal_maps))
+        if on and targets is None:
+            raise ValueError("distortion_weight, normal_consistency_weight, distortions and normal_maps go with targets "
+                             "(the fused training step)")
+        for name, w in (("distortion_weight", distortion_weight), ("normal_consistency_weight", normal_consistency_weight)):
+            if w is not None and not (math.isfinite(float(w)) and float(w) >= 0.0):
+                raise ValueError(f"{name} must be finite and >= 0, got {w}")
+        for name, seq, shape in (("distortions", distortions, (1, self.H, self.W)), ("normal_maps", normal_maps, (3, self.H, self.W))):
+            if seq is None:
+                continue
+            seq = list(seq)
+            if len(seq) != self.n:
+                raise ValueError(f"{name}: {len(seq)} entries for {self.n} views")
+            for t in seq:
+                if not (isinstance(t, torch.Tensor) and tuple(t.shape) == shape):
+                    raise ValueError(f"{name}: every entry must be a {list(shape)} tensor, "
+                                     f"got {tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__}")
+                if not (t.is_cuda and t.dtype is torch.float32 and t.is_contiguous()):
+                    raise ValueError(f"{name}: outputs must be contiguous float32 tensors on the HIP device")
+        return on
 
     @property
     def workspace(self) -> Optional[torch.Tensor]:
@@ -1073,6 +1131,12 @@ class ViewBatch:
             if not (t.is_cuda and t.dtype is torch.float32 and t.is_contiguous()):
                 raise RuntimeError("ViewBatch.run needs contiguous float32 tensors on the HIP device")
         a = self._args
+        if self._geom_report_only and self._geom_scratch is None:
+            import ctypes
+            self._geom_scratch = [torch.empty((1, self.H, self.W), dtype=torch.float32, device=self.device) for _ in range(self.n)]
+            arr = (ctypes.c_void_p * self.n)(*(t.data_ptr() for t in self._geom_scratch))
+            self._keep.append(arr)
+            a.out_distortion = ctypes.addressof(arr)
         a.P, a.M = P, int(shs.shape[1])
         a.means3D, a.shs, a.opacities = means3D.data_ptr(), shs.data_ptr(), opacities.data_ptr()
         a.scales, a.rotations = scales.data_ptr(), rotations.data_ptr()
