@@ -23,6 +23,8 @@ except ImportError as e:                                        # pragma: no cov
         f"({e}); build it with `python -m luciddreamer_amd.build` (needs lib/liblucid_raster.so). "
         "There is no CPU / pure-Python fallback.") from e
 
+import torch
+
 from . import _lib as _lib_check
 _lib_check.assert_single_copy()                                 # the binding and ctypes must be on ONE build of the library
 
@@ -118,11 +120,44 @@ def _forward_state(geomBuffer, binningBuffer, imageBuffer, binning_capacity, dev
     """The fields every argument struct of a pass behind a finished forward shares: its three buffers, the capacity it ran under, the
     current stream of `dev`, and (where the struct has no lr_view of its own) P, width, height."""
     import torch
+    _buffers_on(dev, geomBuffer, binningBuffer, imageBuffer)
     f = dict(geom_buffer=geomBuffer.data_ptr(), binning_buffer=binningBuffer.data_ptr(), image_buffer=imageBuffer.data_ptr(),
              binning_capacity=int(binning_capacity), stream=torch.cuda.current_stream(dev).cuda_stream)
     if P is not None:
         f.update(P=int(P), width=int(W), height=int(H))
     return f
+
+
+def _dense(t, dev):
+    """The hand-off rule of every tensor these wrappers READ: float32, contiguous, 16-byte aligned and on `dev` (the device of the
+    forward's buffers, where the kernel runs), made so by a copy where it is not (a camera matrix kept on the host, a column
+    slice, a transposed storage, an expanded upstream gradient, a view that starts inside another tensor's storage -- the kernels
+    read rotations and the per-pixel moments 16 bytes at a time).  The common case costs four tests."""
+    t = t.detach().to(device=dev, dtype=torch.float32).contiguous()
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
+def _buffers_on(dev, geomBuffer, binningBuffer, imageBuffer):
+    """The three buffers a forward left are read where they lie: all on `dev`, contiguous -- refused otherwise.  Their sizes and
+    inner layout are the forward's own (the library reads them from the geometry header)."""
+    for name, t in (("geomBuffer", geomBuffer), ("binningBuffer", binningBuffer), ("imageBuffer", imageBuffer)):
+        if t.device != dev or not t.is_contiguous():
+            raise RuntimeError(f"{name} must be a contiguous tensor on {dev}, the device of the forward's state (got {t.device})")
+
+
+def _int32_on(who, dev, **tensors):
+    """radii, median_ids: read in place as int32 -- RuntimeError unless int32, contiguous and on `dev`."""
+    for name, t in tensors.items():
+        if t.dtype != torch.int32 or not t.is_contiguous() or t.device != dev:
+            raise RuntimeError(f"{who}: {name} must be a contiguous int32 tensor on {dev}, got {t.dtype} on {t.device}")
+
+
+def _sized(who, **tensors):
+    """Every (tensor, element count) pair given by name: RuntimeError unless a present tensor has exactly that many elements --
+    the kernels index these pointers by P, H and W and nothing else knows their extent."""
+    for name, (t, n) in tensors.items():
+        if t is not None and t.numel() != n:
+            raise RuntimeError(f"{who}: {name} must have {n} elements, got {tuple(t.shape)}")
 
 
 def _call(entry, args, dev, who):
@@ -156,14 +191,18 @@ def median_backward(geomBuffer, binningBuffer, imageBuffer, radii, median_ids, d
     import torch
     H, W = median_ids.shape
     P = radii.shape[0]
-    dev = median_ids.device
+    dev = imageBuffer.device
+    _int32_on("median_backward", dev, radii=radii, median_ids=median_ids)
+    if median_ids.dim() != 2 or radii.dim() != 1:
+        raise RuntimeError("median_backward: median_ids must be (H, W) and radii (P)")
     out = accumulate_into if accumulate_into is not None else torch.empty((P, 3), dtype=torch.float32, device=dev)
-    if accumulate_into is not None and (not out.is_contiguous() or out.dtype != torch.float32 or out.numel() != 3 * P):
-        raise RuntimeError("median_backward: accumulate_into must be a contiguous float32 (P, 3) tensor")
-    dL = dL_dmedian.contiguous().float()
-    view = viewmatrix.contiguous().float()
+    if accumulate_into is not None and (not out.is_contiguous() or out.dtype != torch.float32 or out.numel() != 3 * P or
+                                        out.device != dev):
+        raise RuntimeError("median_backward: accumulate_into must be a contiguous float32 (P, 3) tensor on the forward's device")
+    dL, view = _dense(dL_dmedian, dev), _dense(viewmatrix, dev)
     if dL.numel() != H * W:
         raise RuntimeError("median_backward: dL_dmedian must have H x W elements")
+    _sized("median_backward", viewmatrix=(view, 16))
     a = _lib_check.MedianBackwardArgs(radii=radii.data_ptr(), ids=median_ids.data_ptr(), dL_dmedian=dL.data_ptr(),
                                       viewmatrix=view.data_ptr(), dL_dmean3D=out.data_ptr(),
                                       accumulate=1 if accumulate_into is not None else 0,
@@ -207,12 +246,16 @@ def distortion_backward(geomBuffer, binningBuffer, imageBuffer, dL_ddistortion, 
     H, W = int(rs.image_height), int(rs.image_width)
     c0, c1, c2 = distortion_map_coefficients(distortion_map)
     present = lambda t: t is not None and t.numel() != 0
-    cont = lambda t: t.detach().contiguous().float()
+    cont = lambda t: _dense(t, dev)
     keep = [cont(dL_ddistortion), cont(distortion), cont(moments), cont(rs.viewmatrix), cont(rs.projmatrix), cont(rs.campos),
             cont(means3D), cont(opacities) if opacities is not None else None]
     dL, dist, mom, view, proj, campos, m3, op = keep
     if raw and op is None:
         raise RuntimeError("distortion_backward: raw mode needs the stored opacities")
+    _sized("distortion_backward", viewmatrix=(view, 16), projmatrix=(proj, 16), campos=(campos, 3), means3D=(m3, 3 * P),
+           opacities=(op, P), scales=(scales if present(scales) else None, 3 * P),
+           rotations=(rotations if present(rotations) else None, 4 * P),
+           cov3D_precomp=(cov3D_precomp if present(cov3D_precomp) else None, 6 * P))
     if dL.numel() != H * W or dist.numel() != H * W or mom.numel() != 4 * H * W:
         raise RuntimeError("distortion_backward: dL_ddistortion, distortion and moments must be (1, H, W), (1, H, W), (H, W, 4)")
     sc = cont(scales) if present(scales) else None
@@ -227,7 +270,7 @@ def distortion_backward(geomBuffer, binningBuffer, imageBuffer, dL_ddistortion, 
         if shape is None:
             out[name] = None
         elif t is not None:
-            if not t.is_contiguous() or t.dtype != torch.float32 or t.numel() != int(torch.Size(shape).numel()):
+            if not t.is_contiguous() or t.dtype != torch.float32 or t.numel() != int(torch.Size(shape).numel()) or t.device != dev:
                 raise RuntimeError(f"distortion_backward: accumulate_into[{name!r}] must be a contiguous float32 tensor of {shape}")
             out[name] = t
             mask |= 1 << bits[name]
@@ -248,12 +291,14 @@ def distortion_backward(geomBuffer, binningBuffer, imageBuffer, dL_ddistortion, 
     return out
 
 
-def _normals_view(rs, P, means3D, opacities, scales, rotations, raw):
+def _normals_view(rs, P, means3D, opacities, scales, rotations, raw, dev):
     """(lr_view, tensors to keep alive) of the rendered-normal entries: the forward's camera and scales + rotations."""
-    cont = lambda t: t.detach().contiguous().float()
+    cont = lambda t: _dense(t, dev)
     keep = [cont(rs.viewmatrix), cont(rs.projmatrix), cont(rs.campos), cont(means3D), cont(scales), cont(rotations),
             cont(opacities) if opacities is not None else None]
     view, proj, campos, m3, sc, rot, op = keep
+    _sized("rendered normals", viewmatrix=(view, 16), projmatrix=(proj, 16), campos=(campos, 3), means3D=(m3, 3 * P),
+           scales=(sc, 3 * P), rotations=(rot, 4 * P), opacities=(op, P))
     v = _lib_check.View(P=P, D=0, M=1, raw=1 if raw else 0, width=int(rs.image_width), height=int(rs.image_height),
                         means3D=m3.data_ptr(), opacities=op.data_ptr() if op is not None else None, scales=sc.data_ptr(),
                         scale_modifier=float(rs.scale_modifier), rotations=rot.data_ptr(), viewmatrix=view.data_ptr(),
@@ -280,8 +325,11 @@ def render_normals(geomBuffer, binningBuffer, imageBuffer, radii, rs, *, means3D
     H, W = int(rs.image_height), int(rs.image_width)
     normals = torch.empty((3, H, W), dtype=torch.float32, device=dev)
     gauss_normals = torch.empty((P, 4), dtype=torch.float32, device=dev)
-    v, keep = _normals_view(rs, P, means3D, None, scales, rotations, raw)
+    v, keep = _normals_view(rs, P, means3D, None, scales, rotations, raw, dev)
     rad = radii.contiguous()
+    _sized("render_normals", radii=(rad, P))
+    _int32_on("render_normals", dev, radii=rad)
+    _buffers_on(dev, geomBuffer, binningBuffer, imageBuffer)
     a = _lib_check.NormalsRenderArgs(view=v, radii=rad.data_ptr(), geom_buffer=geomBuffer.data_ptr(),
                                      binning_buffer=binningBuffer.data_ptr(), image_buffer=imageBuffer.data_ptr(),
                                      binning_capacity=int(binning_capacity), out_normals=normals.data_ptr(),
@@ -306,26 +354,29 @@ def render_normals_backward(geomBuffer, binningBuffer, imageBuffer, dL_dnormals,
     dev = imageBuffer.device
     P = int(means3D.shape[0])
     H, W = int(rs.image_height), int(rs.image_width)
-    cont = lambda t: t.detach().contiguous().float()
+    cont = lambda t: _dense(t, dev)
     dL, nrm, gn, rad = cont(dL_dnormals), cont(normals), cont(gauss_normals), radii.contiguous()
     if raw and opacities is None:
         raise RuntimeError("render_normals_backward: raw mode needs the stored opacities")
     if dL.numel() != 3 * H * W or nrm.numel() != 3 * H * W or gn.numel() != 4 * P:
         raise RuntimeError("render_normals_backward: dL_dnormals, normals and gauss_normals must be (3, H, W), (3, H, W), (P, 4)")
+    _sized("render_normals_backward", radii=(rad, P))
+    _int32_on("render_normals_backward", dev, radii=rad)
+    _buffers_on(dev, geomBuffer, binningBuffer, imageBuffer)
     shapes = {"means2D": (P, 3), "opacity": (P, 1), "means3D": (P, 3), "scales": (P, 3), "rotations": (P, 4)}
     bits = {"means2D": 0, "opacity": 2, "means3D": 4, "scales": 7, "rotations": 8}
     out, mask = {}, 0
     for name, shape in shapes.items():
         t = (accumulate_into or {}).get(name)
         if t is not None:
-            if not t.is_contiguous() or t.dtype != torch.float32 or t.numel() != int(torch.Size(shape).numel()):
+            if not t.is_contiguous() or t.dtype != torch.float32 or t.numel() != int(torch.Size(shape).numel()) or t.device != dev:
                 raise RuntimeError(f"render_normals_backward: accumulate_into[{name!r}] must be a contiguous float32 tensor of {shape}")
             out[name] = t
             mask |= 1 << bits[name]
         else:
             out[name] = torch.empty(shape, dtype=torch.float32, device=dev)
     out["gauss_normal"] = torch.empty((P, 3), dtype=torch.float32, device=dev)
-    v, keep = _normals_view(rs, P, means3D, opacities, scales, rotations, raw)
+    v, keep = _normals_view(rs, P, means3D, opacities, scales, rotations, raw, dev)
     a = _lib_check.NormalsRenderBackwardArgs(
         view=v, geom_buffer=geomBuffer.data_ptr(), binning_buffer=binningBuffer.data_ptr(), image_buffer=imageBuffer.data_ptr(),
         binning_capacity=int(binning_capacity), dL_dnormals=dL.data_ptr(), normals=nrm.data_ptr(), gauss_normals=gn.data_ptr(),
@@ -355,8 +406,11 @@ def render_geometry(geomBuffer, binningBuffer, imageBuffer, radii, rs, *, means3
     mom = torch.empty((H, W, 4), dtype=torch.float32, device=dev)
     normals = torch.empty((3, H, W), dtype=torch.float32, device=dev)
     gauss_normals = torch.empty((P, 4), dtype=torch.float32, device=dev)
-    v, keep = _normals_view(rs, P, means3D, None, scales, rotations, raw)
+    v, keep = _normals_view(rs, P, means3D, None, scales, rotations, raw, dev)
     rad = radii.contiguous()
+    _sized("render_geometry", radii=(rad, P))
+    _int32_on("render_geometry", dev, radii=rad)
+    _buffers_on(dev, geomBuffer, binningBuffer, imageBuffer)
     a = _lib_check.GeometryArgs(view=v, radii=rad.data_ptr(), geom_buffer=geomBuffer.data_ptr(),
                                 binning_buffer=binningBuffer.data_ptr(), image_buffer=imageBuffer.data_ptr(),
                                 binning_capacity=int(binning_capacity), map_c0=c0, map_c1=c1, map_c2=c2,
@@ -383,7 +437,7 @@ def geometry_backward(geomBuffer, binningBuffer, imageBuffer, dL_ddistortion, di
     P = int(means3D.shape[0])
     H, W = int(rs.image_height), int(rs.image_width)
     c0, c1, c2 = distortion_map_coefficients(distortion_map)
-    cont = lambda t: t.detach().contiguous().float()
+    cont = lambda t: _dense(t, dev)
     scalar = float(dL_ddistortion) if isinstance(dL_ddistortion, (int, float)) else 0.0
     dD = cont(dL_ddistortion) if isinstance(dL_ddistortion, torch.Tensor) else None
     dN = cont(dL_dnormals) if dL_dnormals is not None else None
@@ -394,20 +448,23 @@ def geometry_backward(geomBuffer, binningBuffer, imageBuffer, dL_ddistortion, di
         raise RuntimeError("geometry_backward: dL_ddistortion, distortion and moments must be (1, H, W), (1, H, W), (H, W, 4)")
     if (dN is not None and dN.numel() != 3 * H * W) or nrm.numel() != 3 * H * W or gn.numel() != 4 * P:
         raise RuntimeError("geometry_backward: dL_dnormals, normals and gauss_normals must be (3, H, W), (3, H, W), (P, 4)")
+    _sized("geometry_backward", radii=(rad, P))
+    _int32_on("geometry_backward", dev, radii=rad)
+    _buffers_on(dev, geomBuffer, binningBuffer, imageBuffer)
     shapes = {"means2D": (P, 3), "opacity": (P, 1), "means3D": (P, 3), "scales": (P, 3), "rotations": (P, 4)}
     bits = {"means2D": 0, "opacity": 2, "means3D": 4, "scales": 7, "rotations": 8}
     out, mask = {}, 0
     for name, shape in shapes.items():
         t = (accumulate_into or {}).get(name)
         if t is not None:
-            if not t.is_contiguous() or t.dtype != torch.float32 or t.numel() != int(torch.Size(shape).numel()):
+            if not t.is_contiguous() or t.dtype != torch.float32 or t.numel() != int(torch.Size(shape).numel()) or t.device != dev:
                 raise RuntimeError(f"geometry_backward: accumulate_into[{name!r}] must be a contiguous float32 tensor of {shape}")
             out[name] = t
             mask |= 1 << bits[name]
         else:
             out[name] = torch.empty(shape, dtype=torch.float32, device=dev)
     out["gauss_normal"] = torch.empty((P, 3), dtype=torch.float32, device=dev)
-    v, keep = _normals_view(rs, P, means3D, opacities, scales, rotations, raw)
+    v, keep = _normals_view(rs, P, means3D, opacities, scales, rotations, raw, dev)
     a = _lib_check.GeometryBackwardArgs(
         view=v, geom_buffer=geomBuffer.data_ptr(), binning_buffer=binningBuffer.data_ptr(), image_buffer=imageBuffer.data_ptr(),
         binning_capacity=int(binning_capacity), dL_ddistortion=dD.data_ptr() if dD is not None else None,

@@ -36,8 +36,10 @@ void require_device(const at::Tensor& t, const char* name)
                 "); this rasterizer has no CPU path (neither has the reference: RAST/rasterize_points.cu:72)");
 }
 
-// float32, contiguous, on `dev`; empty tensors (the reference's `torch.Tensor([])` placeholders,
-// RAST/.../__init__.py:198-208) and None become "absent"
+// float32, contiguous, 16-byte aligned, on `dev`; empty tensors (the reference's `torch.Tensor([])` placeholders,
+// RAST/.../__init__.py:198-208) and None become "absent".  Alignment: several kernels read caller rows as float4 (rotations
+// in preprocess.hip / gauss_bwd.hip); a contiguous view that starts inside another tensor's storage need not be aligned and is
+// copied -- one integer test for everything the allocator or a FlatParams segment hands out.
 struct Arg {
     at::Tensor t;
     const float* p = nullptr;
@@ -50,8 +52,79 @@ Arg f32(const OptT& o, const c10::Device& dev, const char* name)
     a.t = *o;
     if (a.t.device() != dev) a.t = a.t.to(dev);
     if (!a.t.is_contiguous()) a.t = a.t.contiguous();
+    if (reinterpret_cast<uintptr_t>(a.t.data_ptr()) % 16 != 0) a.t = a.t.clone();
     a.p = a.t.data_ptr<float>();
     return a;
+}
+
+// The size rule of every tensor handed to the library: a PRESENT tensor (f32's notion: defined, not empty) has exactly the
+// element count the kernels index -- equality of counts, as check_mode_images; `opacities` of [P] is as good as [P,1].  Host
+// integer comparisons only, made before require_device so that they hold for tensors that live on the host too.
+bool present(const OptT& o) { return o.has_value() && o->defined() && o->numel() != 0; }
+void check_numel(const OptT& o, int64_t n, const char* name, const char* shape)
+{
+    TORCH_CHECK(!present(o) || o->numel() == n, name, " must have dimensions ", shape, ": ", n, " elements (got ",
+                present(o) ? o->numel() : 0, ")");
+}
+// [P, M, 3] (sh, features_rest): M is read from size(1), so the shape itself is checked
+void check_coeffs(const OptT& o, int64_t P, const char* name)
+{
+    TORCH_CHECK(!present(o) || (o->dim() == 3 && o->size(0) == P && o->size(2) == 3), name,
+                " must have dimensions (num_points, M, 3) with num_points = ", P, " (got ", present(o) ? o->sizes() : at::IntArrayRef(), ")");
+}
+void check_camera(const at::Tensor& background, const at::Tensor& viewmatrix, const at::Tensor& projmatrix, const at::Tensor& campos)
+{
+    check_numel(background, 3, "background", "(3)");
+    check_numel(viewmatrix, 16, "viewmatrix", "(4, 4)");
+    check_numel(projmatrix, 16, "projmatrix", "(4, 4)");
+    check_numel(campos, 3, "campos", "(3)");
+}
+// the per-Gaussian tensors of the activated representation
+void check_gaussians(int64_t P, const OptT& colors, const OptT& opacity, const OptT& scales, const OptT& rotations, const OptT& cov3D,
+                     const OptT& sh)
+{
+    check_numel(colors, 3 * P, "colors_precomp", "(num_points, 3)");
+    check_numel(opacity, P, "opacities", "(num_points, 1)");
+    check_numel(scales, 3 * P, "scales", "(num_points, 3)");
+    check_numel(rotations, 4 * P, "rotations", "(num_points, 4)");
+    check_numel(cov3D, 6 * P, "cov3D_precomp", "(num_points, 6)");
+    check_coeffs(sh, P, "sh");
+}
+// ... and of the stored one (raw mode)
+void check_raw_gaussians(int64_t P, const at::Tensor& features_dc, const OptT& features_rest, const at::Tensor& opacity,
+                         const at::Tensor& scaling, const at::Tensor& rotation)
+{
+    TORCH_CHECK(features_dc.numel() == 3 * P, "features_dc must have dimensions (num_points, 1, 3)");
+    check_coeffs(features_rest, P, "features_rest");
+    check_numel(opacity, P, "opacity", "(num_points, 1)");
+    check_numel(scaling, 3 * P, "scaling", "(num_points, 3)");
+    check_numel(rotation, 4 * P, "rotation", "(num_points, 4)");
+}
+// What a backward binding takes besides the view: the upstream colour gradient, radii and the forward's three buffers, which are
+// read in place -- on the device of means3D, contiguous.  H and W are read from dL_dout_color, so its shape is checked and held
+// against the image state: the forward allocated exactly lr_img_bytes(W, H) (and lr_geom_bytes(P)) through scratch_alloc, so the
+// byte counts must be equal.  What that cannot see: a gradient of another resolution with the same byte count (W and H swapped) --
+// the buffers hold P but neither W nor H.
+void check_backward_state(int64_t P, const at::Tensor& means3D, const at::Tensor& dL_dout_color, const at::Tensor& radii,
+                          const at::Tensor& geomBuffer, const at::Tensor& binningBuffer, const at::Tensor& imageBuffer)
+{
+    TORCH_CHECK(dL_dout_color.dim() == 3 && dL_dout_color.size(0) == 3, "dL_dout_color must have dimensions (3, H, W) (got ",
+                dL_dout_color.sizes(), ")");
+    TORCH_CHECK(radii.numel() == P, "radii must have dimensions (num_points): ", P, " elements (got ", radii.numel(), ")");
+    if (P == 0) return;
+    const at::Tensor* state[4] = { &radii, &geomBuffer, &binningBuffer, &imageBuffer };
+    static const char* const kName[4] = { "radii", "geomBuffer", "binningBuffer", "imageBuffer" };
+    for (int k = 0; k < 4; k++)
+        TORCH_CHECK(state[k]->device() == means3D.device() && (k == 0 || state[k]->is_contiguous()), kName[k],
+                    " must be the forward's own tensor: contiguous, on the device of means3D (", means3D.device(), ", got ",
+                    state[k]->device(), ")");
+    const int64_t H = dL_dout_color.size(1), W = dL_dout_color.size(2);
+    TORCH_CHECK(H > 0 && W > 0 && H * W < (int64_t(1) << 31) &&
+                    static_cast<size_t>(imageBuffer.numel()) == lr_img_bytes(static_cast<int>(W), static_cast<int>(H)),
+                "dL_dout_color (3, ", H, ", ", W, ") is not the size of the forward that left imageBuffer (", imageBuffer.numel(),
+                " bytes)");
+    TORCH_CHECK(static_cast<size_t>(geomBuffer.numel()) == lr_geom_bytes(static_cast<int>(P)),
+                "geomBuffer (", geomBuffer.numel(), " bytes) is not the state of a forward over ", P, " Gaussians");
 }
 
 struct Scratch {
@@ -175,9 +248,13 @@ FwdResult rasterize_gaussians(const at::Tensor& background, const at::Tensor& me
                               bool prefiltered, bool debug, int64_t binning_capacity)
 {
     TORCH_CHECK(means3D.dim() == 2 && means3D.size(1) == 3, "means3D must have dimensions (num_points, 3)");   // :57-59
+    const int64_t P = means3D.size(0), H = image_height, W = image_width;
+    if (P != 0) {                          // an empty scene launches nothing: placeholders of any size stay accepted
+        check_gaussians(P, colors, opacity, scales, rotations, cov3D_precomp, sh);
+        check_camera(background, viewmatrix, projmatrix, campos);
+    }
     require_device(means3D, "means3D");
     const c10::Device dev = means3D.device();
-    const int64_t P = means3D.size(0), H = image_height, W = image_width;
     if (P == 0) return empty_forward(dev, H, W);
     c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
     FwdOutputs out(dev, P, H, W);
@@ -264,9 +341,15 @@ std::vector<OptT> rasterize_gaussians_backward(
     const at::Tensor& binningBuffer, const at::Tensor& imageBuffer, bool debug, int64_t binning_capacity,
     const std::vector<OptT>& accumulate, bool skip_unused, const OptT& depth_image, const OptT& dL_dout_alpha, bool absgrad)
 {
+    TORCH_CHECK(means3D.dim() == 2 && means3D.size(1) == 3, "means3D must have dimensions (num_points, 3)");
+    const int64_t P = means3D.size(0);
+    if (P != 0) {
+        check_gaussians(P, colors, OptT(), scales, rotations, cov3D_precomp, sh);
+        check_camera(background, viewmatrix, projmatrix, campos);
+    }
+    check_backward_state(P, means3D, dL_dout_color, radii, geomBuffer, binningBuffer, imageBuffer);
     require_device(means3D, "means3D");
     const c10::Device dev = means3D.device();
-    const int64_t P = means3D.size(0);
     const int64_t H = dL_dout_color.size(1), W = dL_dout_color.size(2);
     const int M = sh_coeffs(sh);
     TORCH_CHECK(accumulate.empty() || accumulate.size() == 8, "accumulate: eight entries or none");
@@ -318,11 +401,14 @@ FwdResult rasterize_gaussians_raw(const at::Tensor& background, const at::Tensor
                                   int64_t binning_capacity)
 {
     TORCH_CHECK(xyz.dim() == 2 && xyz.size(1) == 3, "means3D must have dimensions (num_points, 3)");
+    const int64_t P = xyz.size(0), H = image_height, W = image_width;
+    if (P != 0) {
+        check_raw_gaussians(P, features_dc, features_rest, opacity_raw, scaling_raw, rotation_raw);
+        check_camera(background, viewmatrix, projmatrix, campos);
+    }
     require_device(xyz, "xyz");
     const c10::Device dev = xyz.device();
-    const int64_t P = xyz.size(0), H = image_height, W = image_width;
     if (P == 0) return empty_forward(dev, H, W);
-    TORCH_CHECK(features_dc.numel() == 3 * P, "features_dc must have dimensions (num_points, 1, 3)");
     c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
     const Arg rest = f32(features_rest, dev, "features_rest");
     const int M = 1 + (rest.p ? static_cast<int>(features_rest->size(1)) : 0);
@@ -349,9 +435,15 @@ std::vector<OptT> rasterize_gaussians_raw_backward(
     const std::vector<OptT>& accumulate, bool no_zero_fill, const OptT& dL_dout_depth, const OptT& depth_image,
     const OptT& dL_dout_alpha, bool absgrad)
 {
+    TORCH_CHECK(xyz.dim() == 2 && xyz.size(1) == 3, "means3D must have dimensions (num_points, 3)");
+    const int64_t P = xyz.size(0);
+    if (P != 0) {
+        check_raw_gaussians(P, features_dc, features_rest, opacity_raw, scaling_raw, rotation_raw);
+        check_camera(background, viewmatrix, projmatrix, campos);
+    }
+    check_backward_state(P, xyz, dL_dout_color, radii, geomBuffer, binningBuffer, imageBuffer);
     require_device(xyz, "xyz");
     const c10::Device dev = xyz.device();
-    const int64_t P = xyz.size(0);
     const int64_t H = dL_dout_color.size(1), W = dL_dout_color.size(2);
     c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
     const Arg rest = f32(features_rest, dev, "features_rest");

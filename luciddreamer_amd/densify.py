@@ -238,7 +238,8 @@ def add_densification_stats(model, viewspace_point_tensor, radii):
     P = int(radii.shape[0])
     ok = lambda t, n: t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n
     if g is None or not (ok(g, 3 * P) and ok(model.xyz_gradient_accum, P) and ok(model.denom, P) and ok(model.max_radii2D, P)) \
-            or radii.dtype != torch.int32 or not radii.is_contiguous():
+            or radii.dtype != torch.int32 or not radii.is_contiguous() or \
+            any(t.device != radii.device for t in (g, model.xyz_gradient_accum, model.denom, model.max_radii2D)):
         raise RuntimeError("add_densification_stats needs contiguous float32 statistics / gradient and int32 radii on a HIP device")
     L = _lib.lib()
     dev = radii.device
@@ -394,8 +395,11 @@ def save_ply(model, path):
     n_rest = int(model._features_rest.shape[1])
     props = 17 + 3 * n_rest
     rows = torch.empty((P, props), dtype=torch.float32, device=dev)
-    c = lambda t: t.detach().contiguous()
+    c = lambda t: t.detach().to(device=dev, dtype=torch.float32).contiguous()
     t = [c(model._xyz), c(model._features_dc), c(model._features_rest), c(model._opacity), c(model._scaling), c(model._rotation)]
+    for x, n, name in zip(t, (3, 3, 3 * n_rest, 1, 3, 4), ("_xyz", "_features_dc", "_features_rest", "_opacity", "_scaling", "_rotation")):
+        if x.numel() != n * P:
+            raise RuntimeError(f"pack_ply_rows: {name} {tuple(x.shape)} does not hold {n} floats for each of the {P} Gaussians")
     with torch.cuda.device(dev):
         rc = L.lr_pack_ply_rows(P, 1 + n_rest, t[0].data_ptr(), t[1].data_ptr(), t[2].data_ptr() if n_rest else None,
                                 t[3].data_ptr(), t[4].data_ptr(), t[5].data_ptr(), rows.data_ptr(),

@@ -95,6 +95,8 @@ def _check_apply(raw_scaling, raw_opacity, filter_3D):
         raise ValueError(f"luciddreamer_amd.filter3d: the filter has {n} rows, the model {P}: recompute it "
                          "(compute_filter_3d) after every change of the set of Gaussians")
     _f32(raw_scaling, "scaling", 3 * P), _f32(raw_opacity, "opacity", P), _f32(filter_3D, "filter_3D", P)
+    if not (raw_scaling.device == raw_opacity.device == filter_3D.device):
+        raise RuntimeError("luciddreamer_amd.filter3d: scaling, opacity and filter_3D must be on the same device")
     return P
 
 
@@ -131,6 +133,8 @@ def backward(raw_scaling, raw_opacity, filter_3D, grad_scaling=None, grad_opacit
     g_s = _f32(grad_scaling, "the scaling gradient", 3 * P) if grad_scaling is not None else None
     g_o = _f32(grad_opacity, "the opacity gradient", P) if grad_opacity is not None else None
     dev = s.device
+    if any(g is not None and g.device != dev for g in (g_s, g_o)):
+        raise RuntimeError("luciddreamer_amd.filter3d: the upstream gradients must be on the device of the parameters")
     d_s, d_o = torch.empty_like(s), torch.empty_like(o)
     if P:
         with _lib.on_device(dev):

@@ -45,6 +45,8 @@ def _image_pair(image, gt):
         raise RuntimeError("luciddreamer_amd.loss: image and gt must be on a HIP device (no CPU path)")
     if image.shape != gt.shape or image.dim() < 2:
         raise RuntimeError(f"image {tuple(image.shape)} and gt {tuple(gt.shape)} must have the same [..., H, W] shape")
+    if image.device != gt.device:
+        raise RuntimeError(f"image ({image.device}) and gt ({gt.device}) must be on one device")
     if image.dtype != torch.float32 or gt.dtype != torch.float32:
         raise RuntimeError("image and gt must be float32")
     x, g = image.contiguous(), gt.contiguous()
@@ -66,8 +68,9 @@ def _plane(t, name, what):
 def _depth_pair(depth, target, what):
     """(depth, target, H, W) of two planes of one H, W."""
     d, t = _plane(depth, "depth", what), _plane(target, "target", what)
-    if d.shape[-2:] != t.shape[-2:]:
-        raise RuntimeError(f"depth {tuple(depth.shape)} and target {tuple(target.shape)} must be [1,H,W] or [H,W] of one H, W")
+    if d.shape[-2:] != t.shape[-2:] or d.device != t.device:
+        raise RuntimeError(f"depth {tuple(depth.shape)} and target {tuple(target.shape)} must be [1,H,W] or [H,W] of one H, W, "
+                           "on one device")
     return d, t, int(d.shape[-2]), int(d.shape[-1])
 
 

@@ -46,6 +46,13 @@ def _f32(t, what, numel=None):
     return t
 
 
+def _one_device(dev, *tensors):
+    """Every pointer of a call is dereferenced on ONE device: the first tensor's."""
+    for t in tensors:
+        if t is not None and t.device != dev:
+            raise RuntimeError(f"luciddreamer_amd.mcmc: all tensors of a call must be on one device ({dev}), got {t.device}")
+
+
 def relocate_rows(dst, src, params, exp_avg=None, exp_avg_sq=None, *, rows=None, min_opacity=0.005, n_max=51, workspace=None):
     """lr_mcmc_relocate on tensors.  dst, src: int32 device tensors of n rows each ({dst} and {src} disjoint, dst without
     duplicates, every index below `rows` -- the caller's word, see the header); params / exp_avg / exp_avg_sq: {group: tensor}
@@ -68,7 +75,8 @@ def relocate_rows(dst, src, params, exp_avg=None, exp_avg_sq=None, *, rows=None,
             if d is not None and d.get(g) is not None:
                 if int(d[g].shape[0]) < rows:
                     raise RuntimeError(f"luciddreamer_amd.mcmc: {what} has fewer than {rows} rows")
-                _f32(d[g], what, int(d[g].shape[0]) * width[g])
+                _one_device(dev, _f32(d[g], what, int(d[g].shape[0]) * width[g]))
+    _one_device(dev, dst, src)
     L = _lib.lib()
     need = L.lr_mcmc_workspace_bytes(rows, n)
     if workspace is None or workspace.numel() < need or workspace.device != dev:
@@ -93,6 +101,7 @@ def add_noise(xyz, raw_scale, raw_rotation, raw_opacity, noise, scaler):
     _f32(xyz, "xyz", 3 * P), _f32(raw_scale, "scaling", 3 * P), _f32(raw_rotation, "rotation", 4 * P)
     _f32(raw_opacity, "opacity", P), _f32(noise, "noise", 3 * P)
     dev = xyz.device
+    _one_device(dev, raw_scale, raw_rotation, raw_opacity, noise)
     with _lib.on_device(dev):
         rc = _lib.lib().lr_mcmc_noise(P, xyz.data_ptr(), raw_scale.data_ptr(), raw_rotation.data_ptr(), raw_opacity.data_ptr(),
                                       noise.data_ptr(), float(scaler), _stream(dev))
@@ -107,6 +116,7 @@ def add_reg_grad(raw_opacity, raw_scale, opacity_reg, scale_reg, dL_dopacity, dL
     _f32(raw_opacity, "opacity", P), _f32(raw_scale, "scaling", 3 * P)
     _f32(dL_dopacity, "the opacity gradient", P), _f32(dL_dscale, "the scaling gradient", 3 * P)
     dev = raw_opacity.device
+    _one_device(dev, raw_scale, dL_dopacity, dL_dscale)
     with _lib.on_device(dev):
         rc = _lib.lib().lr_mcmc_reg_grad(P, raw_opacity.data_ptr(), raw_scale.data_ptr(), float(opacity_reg), float(scale_reg),
                                          dL_dopacity.data_ptr(), dL_dscale.data_ptr(), _stream(dev))

@@ -937,6 +937,8 @@ class ViewBatch:
             raise ValueError(f'depth_loss must be "l1" or "pearson", got {depth_loss!r}')
         self.depth_loss = depth_loss
         self.W, self.H = int(self.cams[0].image_width), int(self.cams[0].image_height)
+        self._check_fixed_inputs(grad_colors, targets, bg)
+        self.device = self.cams[0].world_view_transform.device          # where every view runs: inputs are moved, outputs must be there
         self._check_optional_args(grad_colors, targets, grad_depths, depth_targets, depth_weight, depths, grad_alphas, masks,
                                   alpha_weight, alphas, depth_loss)
         from . import _lib
@@ -945,7 +947,6 @@ class ViewBatch:
         map_c = _lib.distortion_map_coefficients(distortion_map)
         self._lib = _lib
         self.L = _lib.lib()
-        self.device = self.cams[0].world_view_transform.device
         self.capacity, self.n_streams = int(binning_capacity), int(n_streams)
         self.bg = bg.to(self.device).contiguous()
         self.train = targets is not None
@@ -975,7 +976,8 @@ class ViewBatch:
         def inputs(tensors):                # HOST array of the device pointers of per-view inputs; None stays NULL
             if tensors is None:
                 return None
-            ts = [t.to(self.device).contiguous() for t in tensors]
+            ts = [t.to(self.device).contiguous() for t in tensors]         # dtype and size were checked: never converted
+            ts = [t if t.data_ptr() % 16 == 0 else t.clone() for t in ts]    # a view that starts inside another's storage
             self._keep.extend(ts)
             return host_array(t.data_ptr() for t in ts)
 
@@ -1003,6 +1005,27 @@ class ViewBatch:
             depth_loss=_lib.LR_DEPTH_LOSS_PEARSON if depth_loss == "pearson" else _lib.LR_DEPTH_LOSS_L1, **geom_fields)
         self._ws = None
         self._ws_key = None
+
+    def _check_fixed_inputs(self, grad_colors, targets, bg):
+        """What every step reads through a bare pointer: the per-view colour images ([3,H,W]), the background (3 elements) and
+        each camera's three tensors (16, 16, 3 elements), all float32 -- refused otherwise, never converted -- and one
+        resolution for all cameras.  The layout (device, strides) is made right by a copy later (`inputs`)."""
+        f32 = lambda t: isinstance(t, torch.Tensor) and t.dtype is torch.float32
+        got = lambda t: (tuple(t.shape), t.dtype) if isinstance(t, torch.Tensor) else type(t).__name__
+        name, seq = ("grad_colors", grad_colors) if targets is None else ("targets", targets)
+        for t in seq:
+            if not (f32(t) and tuple(t.shape) == (3, self.H, self.W)):
+                raise ValueError(f"{name}: every entry must be a float32 [3,H,W] tensor with H,W = {self.H},{self.W}, got {got(t)}")
+        if not (f32(bg) and bg.numel() == 3):
+            raise ValueError(f"bg must be a float32 tensor with 3 elements, got {got(bg)}")
+        for i, c in enumerate(self.cams):
+            if (int(c.image_width), int(c.image_height)) != (self.W, self.H):
+                raise ValueError(f"camera {i} is {int(c.image_width)}x{int(c.image_height)}, the first one {self.W}x{self.H}: "
+                                 "all views of a ViewBatch share one resolution")
+            for attr, n in (("world_view_transform", 16), ("full_proj_transform", 16), ("camera_center", 3)):
+                t = getattr(c, attr)
+                if not (f32(t) and t.numel() == n):
+                    raise ValueError(f"camera {i}: {attr} must be a float32 tensor with {n} elements, got {got(t)}")
 
     def _check_optional_args(self, grad_colors, targets, grad_depths, depth_targets, depth_weight, depths, grad_alphas, masks,
                              alpha_weight, alphas, depth_loss="l1"):
@@ -1043,10 +1066,12 @@ class ViewBatch:
                     if not (isinstance(t, torch.Tensor) and tuple(t.shape) in ((self.H, self.W), (1, self.H, self.W))):
                         raise ValueError(f"{name}: every entry must be a [1,H,W] or [H,W] tensor with H,W = {self.H},{self.W}, "
                                          f"got {tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__}")
-                    if rule == "output" and not (t.is_cuda and t.dtype is torch.float32 and t.is_contiguous()):
-                        raise ValueError(f"{name}: outputs must be contiguous float32 tensors on the HIP device")
-                    if rule == "float32" and t.dtype is not torch.float32:
-                        raise ValueError(f"{name}: float32 tensors (loss.content_mask)")
+                    if rule == "output" and not (t.is_cuda and t.device == self.device and t.dtype is torch.float32 and
+                                                 t.is_contiguous()):
+                        raise ValueError(f"{name}: outputs must be contiguous float32 tensors on the HIP device of the cameras")
+                    if rule != "output" and t.dtype is not torch.float32:      # read as they are: never converted silently
+                        raise ValueError(f"{name}: float32 tensors, got {t.dtype}" +
+                                         (" (loss.content_mask)" if rule == "float32" else ""))
 
     def _check_geom_args(self, targets, distortion_weight, distortion_map, normal_consistency_weight, distortions, normal_maps):
         """The geometry regularisers' arguments; True when the step has them (a weight given, 0 included, or a map asked for)."""
@@ -1070,8 +1095,8 @@ class ViewBatch:
                 if not (isinstance(t, torch.Tensor) and tuple(t.shape) == shape):
                     raise ValueError(f"{name}: every entry must be a {list(shape)} tensor, "
                                      f"got {tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__}")
-                if not (t.is_cuda and t.dtype is torch.float32 and t.is_contiguous()):
-                    raise ValueError(f"{name}: outputs must be contiguous float32 tensors on the HIP device")
+                if not (t.is_cuda and t.device == self.device and t.dtype is torch.float32 and t.is_contiguous()):
+                    raise ValueError(f"{name}: outputs must be contiguous float32 tensors on the HIP device of the cameras")
         return on
 
     @property
@@ -1130,6 +1155,24 @@ class ViewBatch:
         for t in (means3D, opacities, scales, rotations, shs, *acc.values()):
             if not (t.is_cuda and t.dtype is torch.float32 and t.is_contiguous()):
                 raise RuntimeError("ViewBatch.run needs contiguous float32 tensors on the HIP device")
+        # host integer comparisons only (no device work, nothing synchronises): every pointer below is indexed by P and M
+        if shs.dim() != 3 or shs.shape[0] != P or shs.shape[2] != 3 or (self._args.D + 1) ** 2 > shs.shape[1]:
+            raise RuntimeError(f"ViewBatch.run: shs must be [P,M,3] with P = {P} and (sh_degree + 1)^2 <= M, got {tuple(shs.shape)}")
+        M, dev = int(shs.shape[1]), self.device
+        for name, t, n in (("means3D", means3D, 3 * P), ("opacities", opacities, P), ("scales", scales, 3 * P),
+                           ("rotations", rotations, 4 * P), ("shs", shs, 3 * P * M), ("acc['means3D']", acc["means3D"], 3 * P),
+                           ("acc['means2D']", acc["means2D"], 3 * P), ("acc['opacity']", acc["opacity"], P),
+                           ("acc['sh']", acc["sh"], 3 * P * M), ("acc['scales']", acc["scales"], 3 * P),
+                           ("acc['rotations']", acc["rotations"], 4 * P)):
+            if t.numel() != n or t.device != dev:
+                raise RuntimeError(f"ViewBatch.run: {name} must have {n} elements (P = {P}, M = {M}) on {dev}, got "
+                                 f"{tuple(t.shape)} on {t.device}")
+        # rows the kernels move 16 bytes at a time (rotations in, their gradient out): allocator-fresh tensors and FlatGrads /
+        # FlatParams segments are aligned; an in-place target cannot be copied, so a view that is not is refused
+        if (rotations.data_ptr() | acc["rotations"].data_ptr()) % 16:
+            raise RuntimeError("ViewBatch.run: rotations and acc['rotations'] must be 16-byte aligned")
+        if stats is not None and any(stats[k].device != dev for k in self.STAT_KEYS):
+            raise ValueError(f"ViewBatch.run: stats tensors must be on {dev}")
         a = self._args
         if self._geom_report_only and self._geom_scratch is None:
             import ctypes
