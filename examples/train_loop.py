@@ -22,6 +22,7 @@ a perturbed subset of it.  Prints the loss every `--log` iterations and the time
                                   [--filter3d [--antialiasing]]
                                   [--normal-weight 0.05] [--normal-consistency 0.05] [--distortion-weight 100]
                                   [--rendered-normal-consistency 0.05]
+                                  [--feature-channels 16]
 
 --multi-view K: the loop body is ONE multi-view step (parallel.ViewBatch: forward, L1 + DSSIM loss and backward of K views in one
 C call, gradients summed) followed by Adam; the densification statistics are formed inside the step, per view
@@ -53,6 +54,11 @@ normals.rendered_normal_consistency(normals, depth) with weight W is added: the 
 which turns the Gaussians' flat sides into the surface the rendered depth describes.  Turns the depth gradient on.
 With --multi-view K both terms run inside the step (ViewBatch(distortion_weight=W, normal_consistency_weight=W)): one fused pass
 each way per view behind the blend forward and the colour backward, the same loss as the single-view loop's.
+
+--feature-channels C (single-view loop): a [P,C] feature table is rendered next to the colour (render_raw(features=table):
+lr_render_features, 16 channels per tile walk) and trained in a torch Adam group of its own with L1 against a fixed seeded [C,3]
+projection of the target image; the term is printed with the loss.  The set of Gaussians stays fixed: a table has no
+densification surgery.
 
 --filter3d: in either loop the rasterizer is shown the cloud through luciddreamer_amd.filter3d.filtered(model, filter): every
 Gaussian low-passed by the highest sampling rate at which a training camera sees it (the 3D smoothing filter of Mip-Splatting).
@@ -298,6 +304,10 @@ def train(args, log=print):
     normal_w, consistency_w = getattr(args, "normal_weight", 0.0), getattr(args, "normal_consistency", 0.0)
     distortion_w = getattr(args, "distortion_weight", 0.0)
     rendered_w = getattr(args, "rendered_normal_consistency", 0.0)
+    feature_c = int(getattr(args, "feature_channels", 0))
+    if feature_c > 0 and (getattr(args, "multi_view", 0) > 0 or getattr(args, "mcmc", False)):
+        raise SystemExit("--feature-channels: the single-view loop with a fixed set of Gaussians only (the multi-view step has no "
+                         "feature pass, and a feature table has no densification surgery)")
     if getattr(args, "multi_view", 0) > 0:
         if normal_w > 0 or consistency_w > 0:
             raise SystemExit("--normal-weight / --normal-consistency: the single-view loop only (the multi-view step takes an "
@@ -318,13 +328,26 @@ def train(args, log=print):
     gen = torch.Generator().manual_seed(0)
     strategy = _mcmc_strategy(args, model)
     f3 = _Filter3D(args, model, cams, dev)
+    # --feature-channels C: a [P,C] table rendered next to the colour (features=: lr_render_features), trained in a torch Adam
+    # group of its own with L1 against a fixed seeded [C,3] projection of the target image.  The set of Gaussians stays as it is:
+    # a table has no densification surgery.
+    table = table_opt = projection = None
+    if feature_c > 0:
+        fgen = torch.Generator().manual_seed(1)
+        table = torch.zeros(model._xyz.shape[0], feature_c, device=dev, requires_grad=True)
+        table_opt = torch.optim.Adam([table], lr=0.0025, eps=1e-15)          # the rate of features_dc
+        projection = (torch.randn(feature_c, 3, generator=fgen) / 3.0 ** 0.5).to(dev)
+    feature_term = None
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for it in range(1, args.iters + 1):
         v = int(torch.randint(0, len(cams), (1,), generator=gen))
         pkg = render_raw(cams[v], f3.view(model), bg_color=bg, return_median=consistency_w > 0,    # luciddreamer.py:296
-                         return_distortion=distortion_w > 0, return_normals=rendered_w > 0)
+                         return_distortion=distortion_w > 0, return_normals=rendered_w > 0, features=table)
         loss = l1_dssim_loss(pkg["render"], targets[v], args.lambda_dssim)                # :301-303
+        if table is not None:
+            feature_term = (pkg["features"] - torch.einsum("ck,khw->chw", projection, targets[v])).abs().mean()
+            loss = loss + feature_term
         if normal_w > 0:
             loss = loss + normal_loss(pkg["depth"], normal_targets[v], cams[v], weight=normal_w)
         if consistency_w > 0:
@@ -339,19 +362,23 @@ def train(args, log=print):
             changed = False
             if strategy is not None:
                 strategy.add_regularizer_grads(model)
-            elif it < args.densify_until:                                                 # :308-318
+            elif it < args.densify_until and table is None:                               # :308-318
                 densify.add_densification_stats(model, pkg["viewspace_points"], radii)   # :310-311 + stats, one kernel
                 if it >= args.densify_from and it % args.densify_every == 0:
                     densify.densify_and_prune(model, args.densify_grad_threshold, 0.005, 5.0, 20)
                     changed = True
             model.optimizer.step()                                                        # :322-324
             model.optimizer.zero_grad(set_to_none=True)
+            if table_opt is not None:
+                table_opt.step()
+                table_opt.zero_grad(set_to_none=True)
             if strategy is not None:
                 changed = any(strategy.step(model, it, LR_XYZ))
             f3.after_step(model, it, changed, args.densify_until)
         if it % args.log == 0 or it == 1:
             losses.append((it, float(loss.item()), int(model._xyz.shape[0])))
-            log(f"iter {it:5d}  loss {losses[-1][1]:.5f}  gaussians {losses[-1][2]}")
+            extra = "" if feature_term is None else f"  feature L1 {float(feature_term.item()):.5f}"
+            log(f"iter {it:5d}  loss {losses[-1][1]:.5f}  gaussians {losses[-1][2]}{extra}")
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     config.set_async(True)              # back to the library defaults
@@ -368,7 +395,7 @@ def default_args(**kw):
              densify_every=100, densify_until=10_000, exact=False, torch_adam=False, antialiasing=False, absgrad=False,
              densify_grad_threshold=0.0002, multi_view=0, mcmc=False, cap_max=0, depth_weight=0.0, depth_loss="l1", filter3d=False,
              normal_weight=0.0, normal_consistency=0.0, distortion_weight=0.0,
-             rendered_normal_consistency=0.0)
+             rendered_normal_consistency=0.0, feature_channels=0)
     d.update(kw)
     return SimpleNamespace(**d)
 
@@ -396,6 +423,9 @@ HELP = {
     "rendered_normal_consistency": "> 0 adds normals.rendered_normal_consistency(normals, depth) with this weight "
                                    "(return_normals=True): the rendered normal map against the normals of the rendered depth; "
                                    "with --multi-view inside the step",
+    "feature_channels": "single-view loop: C > 0 renders a [P,C] feature table next to the colour (features=) and trains it, in a "
+                        "torch Adam group of its own, with L1 against a fixed seeded [C,3] projection of the target image; the "
+                        "term is printed; the set of Gaussians stays fixed (no densification)",
     "densify_grad_threshold": "clone / split threshold on the accumulated view-space gradient norm (reference: 0.0002).  Summed "
                               "magnitudes are larger than the signed norm: with --absgrad use about 4x (0.0008)",
 }

@@ -555,6 +555,100 @@ int lr_render_normals(const lr_normals_render_args* a);
 int lr_render_normals_backward(const lr_normals_render_backward_args* a);
 
 /*
+ * N-channel feature map of a forward (semantic or instance logits, distilled 2D features as Feature-3DGS, LangSplat and
+ * LEGaussians blend them, per-Gaussian appearance codes; gsplat renders any channel count), from its three scratch buffers; a
+ * pass of its own behind the forward, whose kernels are not changed by it.
+ *
+ * Input.  features [P,C] float32, contiguous, 16-byte aligned, 1 <= C = `channels` <= LR_FEATURE_MAX_CHANNELS.  View-independent
+ * and used as given in activated and in raw mode alike: there is no activation.
+ * Per-pixel map.  F[c] = sum_i w_i f_i[c] over the layers the blend forward applied to the pixel, w_i = alpha_i T_i with the
+ * forward's skips, 0.99 clamp and 1e-4 stop: exactly the walk of lr_render_normals and lr_render_distortion, the same T sequence.
+ * No background term, no normalisation.
+ *   out_features [C,H,W] float32, planar: F; exact zeros for a pixel with no layer, for P = 0 (no buffer is read) and for an
+ *                                overflowed async view.
+ * Every channel is an fma chain of its own in list order: a channel's bits do not depend on the other columns of `features` or
+ * on C.  As for lr_render_normals the definition holds under strict parity, anti-aliasing, the 3D filter, raw and activated
+ * parameters, both forward shapes, exact and async mode -- and with cov3D_precomp: nothing here needs scales or rotations.  Of
+ * `view` the forward pass reads P, width and height only.
+ *
+ * lr_render_features_backward: the gradient of out_features for the upstream dL_dout_features [C,H,W], with `out_features` what
+ * lr_render_features wrote for the same buffers and the same `features`.  With g = dL/dF of the pixel and c_i = f_i . g over all C
+ * channels:
+ *     dL/df_i[c] += w_i g[c],   dL/dalpha_i = T_i c_i - S_i / (1 - alpha_i),   S_i = sum_{k>i} w_k c_k = F.g - sum_{k<=i} w_k c_k,
+ * S_i taken front to back on the forward's own T sequence, as lr_render_normals_backward takes it.  The conventions of the colour
+ * path hold: the clamp is not differentiated; skips, stop and order are constants.  alpha = opacity G reaches dL_dmean2D,
+ * dL_dconic and dL_dopacity with the expressions of the blend backward's flush, and through them the per-Gaussian backward, as it
+ * stands and run ONCE per call, carries the gradient to the mean, scales and rotations (or cov3D: dL_dcov3D is written with
+ * cov3D_precomp) and the opacity.
+ *   dL_dfeatures [P,C] float32, 16-byte aligned: written in full in write mode -- rows with radii <= 0 and rows no pixel blended
+ *   are exact zeros --, or with LR_ACC_FEATURES in accumulate_mask ADDED to in the rows of the Gaussians that own a tile instance
+ *   (the others stay untouched).
+ *   workspace: lr_features_workspace_bytes(slots, channels) device bytes, 16-byte aligned, `slots` the bound the binning buffer
+ *   was laid out with or any bound above it: binning_capacity in async mode; in exact mode the value lr_forward returned (the
+ *   reference's num_rendered is never below the instance count).  In async mode a workspace below the capacity's size is refused;
+ *   in exact mode the host does not know the count: the kernels never touch a row outside the workspace, and a view with more
+ *   instances than the workspace has rows is reported by lr_check as an incomplete backward.
+ * Colours and SH get nothing: dL_dcolor, dL_dsh and dL_dsh_rest may be NULL and are never added to; given in write mode they are
+ * zero-filled.  The other outputs, their units, accumulate_mask and the alignment rule are lr_distortion_backward_args'.  Order:
+ * per chunk of channels the per-tile kernel and the per-Gaussian row sums of dL_dfeatures; then the zero-fill of rows in write
+ * mode and the per-Gaussian backward.  The per-tile kernel OVERWRITES the per-instance gradient slots of the binning buffer: the
+ * ordering rule is lr_normals_render_backward_args' (behind the colour backward of the same forward state -- and behind the other
+ * passes' backwards, if they run -- and before another forward reuses the buffers).  An overflowed async view adds nothing.  No
+ * global float atomics: two runs give the same bits, and a column of dL_dfeatures does not depend on the other channels.
+ */
+#define LR_FEATURE_MAX_CHANNELS 256
+#define LR_ACC_FEATURES (1u << 9)            /* accumulate_mask of lr_render_features_backward: dL_dfeatures is added to */
+
+typedef struct lr_feature_render_args {
+    size_t struct_bytes;                     /* = sizeof(lr_feature_render_args); anything else is LR_ERR_INVALID_ARG */
+    lr_view view;
+    const int* radii;                        /* the forward's [P]; not read */
+    const char* geom_buffer;
+    const char* binning_buffer;
+    const char* image_buffer;
+    long long binning_capacity;              /* the value the forward was given */
+    const float* features;                   /* [P,C] */
+    int channels;
+    float* out_features;                     /* [C,H,W] */
+    void* stream;
+} lr_feature_render_args;
+
+typedef struct lr_feature_render_backward_args {
+    size_t struct_bytes;                     /* = sizeof(lr_feature_render_backward_args); anything else is LR_ERR_INVALID_ARG */
+    lr_view view;
+    char* geom_buffer;
+    char* binning_buffer;
+    char* image_buffer;
+    long long binning_capacity;
+    const float* features;                   /* [P,C] */
+    int channels;
+    const float* dL_dout_features;           /* [C,H,W] */
+    const float* out_features;               /* [C,H,W], for F.g */
+    const int* radii;
+    float* dL_dfeatures;                     /* [P,C] */
+    void* workspace;
+    size_t workspace_bytes;
+    /* gradient outputs, as lr_backward_args */
+    float* dL_dmean2D;
+    float* dL_dconic;
+    float* dL_dopacity;
+    float* dL_dcolor;
+    float* dL_dmean3D;
+    float* dL_dcov3D;
+    float* dL_dsh;
+    float* dL_dsh_rest;
+    float* dL_dscale;
+    float* dL_drot;
+    unsigned int accumulate_mask;
+    void* stream;
+} lr_feature_render_backward_args;
+
+/* 0 for slots < 0 or channels outside 1 .. LR_FEATURE_MAX_CHANNELS; never decreasing in either argument otherwise */
+size_t lr_features_workspace_bytes(long long slots, int channels);
+int lr_render_features(const lr_feature_render_args* a);
+int lr_render_features_backward(const lr_feature_render_backward_args* a);
+
+/*
  * Depth distortion AND rendered normal map of a forward in ONE tile walk each way (render_geom.hip): the pair the multi-view
  * step runs for its two geometry regularisers.  The definitions are lr_render_distortion's and lr_render_normals', word for word
  * -- the mapped depth m = map_c0 + map_c1 z + map_c2 / z, the shift by m_ref, D >= 0, N = sum_i w_i n_i, the forward's skips, 0.99

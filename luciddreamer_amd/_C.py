@@ -391,6 +391,111 @@ def render_normals_backward(geomBuffer, binningBuffer, imageBuffer, dL_dnormals,
     return out
 
 
+FEATURE_MAX_CHANNELS = _lib_check.LR_FEATURE_MAX_CHANNELS
+
+
+def require_features(who, features, P):
+    """features as the feature-map entries take it: a float32 (P, C) tensor with 1 <= C <= FEATURE_MAX_CHANNELS -- ValueError
+    otherwise, before any launch (a dtype is not converted here: a float64 or integer table handed in by mistake would be
+    rendered from a silent copy whose gradient the caller never sees).  Returns C."""
+    if not isinstance(features, torch.Tensor) or features.dim() != 2:
+        raise ValueError(f"{who}: features must be a (P, C) tensor")
+    if features.dtype != torch.float32:
+        raise ValueError(f"{who}: features must be float32, got {features.dtype}")
+    if int(features.shape[0]) != int(P):
+        raise ValueError(f"{who}: features has {int(features.shape[0])} rows for {int(P)} Gaussians")
+    C = int(features.shape[1])
+    if not 1 <= C <= FEATURE_MAX_CHANNELS:
+        raise ValueError(f"{who}: features must have 1 .. {FEATURE_MAX_CHANNELS} channels, got {C}")
+    return C
+
+
+def render_features(geomBuffer, binningBuffer, imageBuffer, features, rs, *, binning_capacity=0):
+    """feature_map (C, H, W) float32 of the forward that left the three buffers (lr_render_features, on the current stream):
+    F[c] = sum_i w_i features[i, c] over each pixel's blended layers, no background term, no normalisation.  features: (P, C)
+    float32, used as given; rs: the forward's raster settings.  ValueError for a wrong shape, dtype or row count -- the row count
+    is checked against the P of the forward's geometry buffer by the caller (the operator passes its means3D's) -- before any
+    launch.  No autograd."""
+    dev = imageBuffer.device
+    P = int(features.shape[0]) if isinstance(features, torch.Tensor) and features.dim() == 2 else -1
+    C = require_features("render_features", features, P)
+    H, W = int(rs.image_height), int(rs.image_width)
+    f = _dense(features, dev)
+    out = torch.empty((C, H, W), dtype=torch.float32, device=dev)
+    a = _lib_check.FeatureRenderArgs(view=_lib_check.View(P=P, D=0, M=1, width=W, height=H), features=f.data_ptr(), channels=C,
+                                     out_features=out.data_ptr(),
+                                     **_forward_state(geomBuffer, binningBuffer, imageBuffer, binning_capacity, dev))
+    _call("lr_render_features", a, dev, "render_features")
+    del f
+    return out
+
+
+def render_features_backward(geomBuffer, binningBuffer, imageBuffer, dL_dout_features, out_features, features, radii, rs, *,
+                             means3D, slots, opacities=None, scales=None, rotations=None, cov3D_precomp=None, raw=False,
+                             binning_capacity=0, accumulate_into=None):
+    """The feature map's gradient (lr_render_features_backward, on the current stream, behind the colour backward -- and the other
+    passes' backwards -- of the same forward).  Arguments as distortion_backward; slots: the bound of the forward's instance
+    count the workspace is sized by (the forward's num_rendered in exact mode; async mode takes binning_capacity);
+    accumulate_into: {"means2D", "opacity", "means3D", "scales", "rotations", "cov3D", "features": tensor or None}, a given tensor
+    is ADDED to in place, a missing one is a new tensor written in full.  Returns the dict of the seven (None for the
+    representation not in use)."""
+    dev = imageBuffer.device
+    P = int(means3D.shape[0])
+    C = require_features("render_features_backward", features, P)
+    H, W = int(rs.image_height), int(rs.image_width)
+    present = lambda t: t is not None and t.numel() != 0
+    cont = lambda t: _dense(t, dev)
+    keep = [cont(dL_dout_features), cont(out_features), cont(features), cont(rs.viewmatrix), cont(rs.projmatrix), cont(rs.campos),
+            cont(means3D), cont(opacities) if opacities is not None else None]
+    dL, val, f, view, proj, campos, m3, op = keep
+    if raw and op is None:
+        raise RuntimeError("render_features_backward: raw mode needs the stored opacities")
+    rad = radii.contiguous()
+    _sized("render_features_backward", viewmatrix=(view, 16), projmatrix=(proj, 16), campos=(campos, 3), means3D=(m3, 3 * P),
+           opacities=(op, P), radii=(rad, P), scales=(scales if present(scales) else None, 3 * P),
+           rotations=(rotations if present(rotations) else None, 4 * P),
+           cov3D_precomp=(cov3D_precomp if present(cov3D_precomp) else None, 6 * P),
+           dL_dout_features=(dL, C * H * W), out_features=(val, C * H * W))
+    _int32_on("render_features_backward", dev, radii=rad)
+    sc = cont(scales) if present(scales) else None
+    rot = cont(rotations) if present(rotations) else None
+    cov = cont(cov3D_precomp) if present(cov3D_precomp) else None
+    shapes = {"means2D": (P, 3), "opacity": (P, 1), "means3D": (P, 3), "scales": (P, 3) if sc is not None else None,
+              "rotations": (P, 4) if rot is not None else None, "cov3D": (P, 6) if cov is not None else None, "features": (P, C)}
+    bits = {"means2D": 0, "opacity": 2, "means3D": 4, "cov3D": 5, "scales": 7, "rotations": 8, "features": 9}
+    out, mask = {}, 0
+    for name, shape in shapes.items():
+        t = (accumulate_into or {}).get(name)
+        if shape is None:
+            out[name] = None
+        elif t is not None:
+            if not t.is_contiguous() or t.dtype != torch.float32 or t.numel() != int(torch.Size(shape).numel()) or t.device != dev \
+                    or t.data_ptr() % 16 != 0:
+                raise RuntimeError(f"render_features_backward: accumulate_into[{name!r}] must be a contiguous, 16-byte aligned "
+                                   f"float32 tensor of {shape} on {dev}")
+            out[name] = t
+            mask |= 1 << bits[name]
+        else:
+            out[name] = torch.empty(shape, dtype=torch.float32, device=dev)
+    bound = int(binning_capacity) if int(binning_capacity) > 0 else max(int(slots), 1)
+    ws_bytes = int(_lib_check.lib().lr_features_workspace_bytes(bound, C))
+    ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    v = _lib_check.View(P=P, D=0, M=1, raw=1 if raw else 0, width=W, height=H, means3D=m3.data_ptr(), opacities=ptr(op),
+                        scales=ptr(sc), scale_modifier=float(rs.scale_modifier), rotations=ptr(rot), cov3D_precomp=ptr(cov),
+                        viewmatrix=view.data_ptr(), projmatrix=proj.data_ptr(), campos=campos.data_ptr(),
+                        tan_fovx=float(rs.tanfovx), tan_fovy=float(rs.tanfovy))
+    a = _lib_check.FeatureRenderBackwardArgs(
+        view=v, features=f.data_ptr(), channels=C, dL_dout_features=dL.data_ptr(), out_features=val.data_ptr(), radii=rad.data_ptr(),
+        dL_dfeatures=out["features"].data_ptr(), workspace=ws.data_ptr(), workspace_bytes=ws_bytes,
+        dL_dmean2D=ptr(out["means2D"]), dL_dopacity=ptr(out["opacity"]), dL_dmean3D=ptr(out["means3D"]), dL_dcov3D=ptr(out["cov3D"]),
+        dL_dscale=ptr(out["scales"]), dL_drot=ptr(out["rotations"]), accumulate_mask=mask,
+        **_forward_state(geomBuffer, binningBuffer, imageBuffer, binning_capacity, dev))
+    _call("lr_render_features_backward", a, dev, "render_features_backward")
+    del keep, ws
+    return out
+
+
 def render_geometry(geomBuffer, binningBuffer, imageBuffer, radii, rs, *, means3D, scales, rotations, cov3D_precomp=None, raw=False,
                     distortion_map="ndc", binning_capacity=0):
     """(distortion (1, H, W), moments (H, W, 4), normals (3, H, W), gauss_normals (P, 4)): render_distortion and render_normals in

@@ -30,6 +30,7 @@ EXPORTS = ("lr_last_error", "lr_version", "lr_geom_bytes", "lr_img_bytes", "lr_b
            "lr_backward", "lr_view_forward", "lr_view_backward", "lr_render_alpha", "lr_render_median", "lr_median_backward",
            "lr_render_distortion", "lr_distortion_backward", "lr_render_normals", "lr_render_normals_backward",
            "lr_render_geometry", "lr_geometry_backward",
+           "lr_features_workspace_bytes", "lr_render_features", "lr_render_features_backward",
            "lr_mark_visible", "lr_check",
            "lr_dist2_workspace_bytes", "lr_dist2",
            "lr_dist2_workspace_layout",
@@ -211,6 +212,37 @@ class NormalsRenderBackwardArgs(ctypes.Structure):
 
     def __init__(self, **fields):
         super().__init__(struct_bytes=ctypes.sizeof(NormalsRenderBackwardArgs), **fields)
+
+
+LR_FEATURE_MAX_CHANNELS = 256       # include/lucid_raster.h
+LR_ACC_FEATURES = 1 << 9            # accumulate_mask of lr_render_features_backward: dL_dfeatures is added to
+LR_FEATURE_CHUNK = 16               # channels per tile walk (csrc/render_features.hip FTR_K): C channels cost ceil(C / 16) walks each way
+
+
+class FeatureRenderArgs(ctypes.Structure):
+    """lr_feature_render_args, field for field (tests/test_features_cpu.py compares the offsets with the host compiler's)."""
+    _vp = ctypes.c_void_p
+    _fields_ = [("struct_bytes", ctypes.c_size_t), ("view", View), ("radii", _vp),
+                ("geom_buffer", _vp), ("binning_buffer", _vp), ("image_buffer", _vp), ("binning_capacity", ctypes.c_longlong),
+                ("features", _vp), ("channels", ctypes.c_int), ("out_features", _vp), ("stream", _vp)]
+
+    def __init__(self, **fields):
+        super().__init__(struct_bytes=ctypes.sizeof(FeatureRenderArgs), **fields)
+
+
+class FeatureRenderBackwardArgs(ctypes.Structure):
+    """lr_feature_render_backward_args, field for field."""
+    _vp = ctypes.c_void_p
+    _fields_ = [("struct_bytes", ctypes.c_size_t), ("view", View),
+                ("geom_buffer", _vp), ("binning_buffer", _vp), ("image_buffer", _vp), ("binning_capacity", ctypes.c_longlong),
+                ("features", _vp), ("channels", ctypes.c_int), ("dL_dout_features", _vp), ("out_features", _vp), ("radii", _vp),
+                ("dL_dfeatures", _vp), ("workspace", _vp), ("workspace_bytes", ctypes.c_size_t),
+                ("dL_dmean2D", _vp), ("dL_dconic", _vp), ("dL_dopacity", _vp), ("dL_dcolor", _vp), ("dL_dmean3D", _vp),
+                ("dL_dcov3D", _vp), ("dL_dsh", _vp), ("dL_dsh_rest", _vp), ("dL_dscale", _vp), ("dL_drot", _vp),
+                ("accumulate_mask", ctypes.c_uint), ("stream", _vp)]
+
+    def __init__(self, **fields):
+        super().__init__(struct_bytes=ctypes.sizeof(FeatureRenderBackwardArgs), **fields)
 
 
 class GeometryArgs(ctypes.Structure):
@@ -399,6 +431,12 @@ def lib():
         L.lr_render_normals.argtypes = [ctypes.POINTER(NormalsRenderArgs)]
         L.lr_render_normals_backward.restype = ci
         L.lr_render_normals_backward.argtypes = [ctypes.POINTER(NormalsRenderBackwardArgs)]
+        L.lr_features_workspace_bytes.restype = ctypes.c_size_t
+        L.lr_features_workspace_bytes.argtypes = [ll, ci]                        # slots channels
+        L.lr_render_features.restype = ci
+        L.lr_render_features.argtypes = [ctypes.POINTER(FeatureRenderArgs)]
+        L.lr_render_features_backward.restype = ci
+        L.lr_render_features_backward.argtypes = [ctypes.POINTER(FeatureRenderBackwardArgs)]
         L.lr_render_geometry.restype = ci
         L.lr_render_geometry.argtypes = [ctypes.POINTER(GeometryArgs)]
         L.lr_geometry_backward.restype = ci

@@ -32,6 +32,7 @@ SOURCES = {
     "render_distort.hip": ["-fno-slp-vectorize"],    # depth distortion pass and its backward: the forward's alpha arithmetic again
     "render_normals.hip": ["-fno-slp-vectorize"],    # rendered normal map pass and its backward: the forward's alpha arithmetic once more
     "render_geom.hip": ["-fno-slp-vectorize"],       # distortion and normal map in one walk each way: the same arithmetic, the same flags
+    "render_features.hip": ["-fno-slp-vectorize"],   # N-channel feature map pass and its backward: the same arithmetic, the same flags
     "gauss_bwd.hip": [],
     "knn.hip": [],
     # the separable window sums are long fma chains: packed f32 costs two issue slots plus the moves that form the pairs

@@ -511,6 +511,19 @@ void launch_normals_bwd(int W, int H, int P, const GeomView& g, const ImgView& i
                         const float* normals, const float* gauss_normals, hipStream_t s);
 void launch_normal_rot_bwd(int P, bool raw, const float* rotations, const float* view, const int* radii, const GeomView& g,
                            const float* gauss_normals, const float* dL_dgauss_normal, float* dL_drot, hipStream_t s);
+// N-channel feature map of a finished forward (render_features.hip: definition, kernels).  launch_render_features: F = sum w f,
+// [C,H,W], one walk per features_chunk() channels; P <= 0: zeros without reading a buffer.  launch_features_bwd: per chunk the map's
+// gradient as one GradRec per instance in inst_grad (colour floats zero; the first chunk overwrites, the others add) and w g per
+// instance in `workspace` (features_workspace_bytes(slots), rows by emission slot), then the rows' sums per emitting Gaussian into
+// dL_dfeatures [P,C] (accumulate: added to, else written -- the caller zero-fills the rest).  g: rec, header (bwd_uncovered is set
+// when the workspace holds fewer rows than the view has instances), vis_list, offsets; im: ranges.
+int features_chunk();
+size_t features_workspace_bytes(long long slots);
+void launch_render_features(int W, int H, int P, const GeomView& g, const ImgView& im, const char* bin_base, const float* features,
+                            int C, float* out_features, hipStream_t s);
+void launch_features_bwd(int W, int H, int P, const GeomView& g, const ImgView& im, char* bin_base, const float* dL_dout_features,
+                         const float* out_features, const float* features, int C, char* workspace, size_t workspace_bytes,
+                         bool accumulate, float* dL_dfeatures, hipStream_t s);
 // both of the above in one tile walk each way (render_geom.hip): the outputs of launch_render_distort and launch_render_normals
 // from gauss_normals as launch_gauss_normals wrote it; the gradient of both as ONE GradRec per instance in inst_grad (colour floats:
 // dL/dn, pad0: dL/dz).  dL_ddistortion NULL: dist_scalar is every pixel's dL/dD (0: no distortion term, distortion / moments are

@@ -252,21 +252,22 @@ def install(gaussian_renderer=None, loss=None, gaussian_model=None, *, render=Tr
         orig_render = gaussian_renderer.render
 
         def render_(viewpoint_camera, pc, opt, bg_color, scaling_modifier=1.0, override_color=None, render_only=False,
-                    return_alpha=False, return_median=False, return_distortion=False, distortion_map="ndc", return_normals=False):
-            # return_alpha / return_median / return_distortion / return_normals: the result gains "alpha" / "median_depth" and
-            # "median_ids" / "distortion" / "normals" (gaussian_renderer.render);
+                    return_alpha=False, return_median=False, return_distortion=False, distortion_map="ndc", return_normals=False,
+                    features=None):
+            # return_alpha / return_median / return_distortion / return_normals / features: the result gains "alpha" /
+            # "median_depth" and "median_ids" / "distortion" / "normals" / "features" (gaussian_renderer.render);
             # the reference's own render has no such keywords, so a call that asks for them and that it would take goes to this
             # package's render of the same contract
             if not _raw_ok(pc, opt, override_color):
-                if return_alpha or return_median or return_distortion or return_normals:
+                if return_alpha or return_median or return_distortion or return_normals or features is not None:
                     return gr.render(viewpoint_camera, pc, opt, bg_color, scaling_modifier, override_color, render_only,
                                      return_alpha=return_alpha, return_median=return_median,
                                      return_distortion=return_distortion, distortion_map=distortion_map,
-                                     return_normals=return_normals)
+                                     return_normals=return_normals, features=features)
                 return orig_render(viewpoint_camera, pc, opt, bg_color, scaling_modifier, override_color, render_only)
             out = gr.render_raw(viewpoint_camera, pc, opt, bg_color, scaling_modifier, render_only, return_alpha=return_alpha,
                                 return_median=return_median, return_distortion=return_distortion, distortion_map=distortion_map,
-                                return_normals=return_normals)
+                                return_normals=return_normals, features=features)
             if not render_only:
                 # carries the radii for the fused densification statistics below, and keeps the caller's own
                 # `max_radii2D[filter] = torch.max(max_radii2D[filter], radii[filter])` on the device (_VisFilter above)

@@ -38,7 +38,7 @@ def _view_setup(viewpoint_camera, pc, xyz, opt, bg_color, scaling_modifier):
 
 def render(viewpoint_camera, pc, opt=DEFAULT_OPT, bg_color=None, scaling_modifier=1.0, override_color=None,
            render_only=False, return_alpha=False, return_median=False, return_distortion=False, distortion_map="ndc",
-           return_normals=False):
+           return_normals=False, features=None):
     """Returns {"render", "viewspace_points", "visibility_filter", "radii", "depth"} (or render/depth only); with
     return_alpha the dict gains "alpha", the accumulated opacity 1 - T_final (1, H, W), differentiable; with return_median
     "median_depth" (1, H, W) and "median_ids" (H, W) int32 (rasterizer.rasterize_gaussians: the depth and the row of the Gaussian at
@@ -46,7 +46,9 @@ def render(viewpoint_camera, pc, opt=DEFAULT_OPT, bg_color=None, scaling_modifie
     return_distortion "distortion" (1, H, W), the depth distortion of the pixel's blended layers for the mapped depth of
     distortion_map ("ndc", ("ndc", near, far) or "linear"; rasterizer module docstring), differentiable; with return_normals
     "normals" (3, H, W), the rendered normal map sum_i w_i n_i of the Gaussians' view-space normals (rasterizer module docstring;
-    not normalised: |N| <= alpha), differentiable -- ValueError under opt.compute_cov3D_python, which leaves no normal."""
+    not normalised: |N| <= alpha), differentiable -- ValueError under opt.compute_cov3D_python, which leaves no normal; with
+    features=<(P, C) float32 tensor> "features" (C, H, W), the blend sum_i w_i features[i] of that table (rasterizer module
+    docstring; no background term), differentiable, the table included."""
     xyz = pc.get_xyz
     screenspace_points, raster_settings = _view_setup(viewpoint_camera, pc, xyz, opt, bg_color, scaling_modifier)
     rasterizer = GaussianRasterizer(raster_settings=raster_settings)
@@ -70,20 +72,24 @@ def render(viewpoint_camera, pc, opt=DEFAULT_OPT, bg_color=None, scaling_modifie
         means3D=xyz, means2D=screenspace_points, shs=shs, colors_precomp=colors_precomp,
         opacities=pc.get_opacity, scales=scales, rotations=rotations, cov3D_precomp=cov3D_precomp, return_alpha=return_alpha,
         return_median=return_median, return_distortion=return_distortion, distortion_map=distortion_map,
-        return_normals=return_normals)
-    return _result(out, screenspace_points, render_only, return_alpha, return_median, return_distortion, return_normals)
+        return_normals=return_normals, features=features)
+    return _result(out, screenspace_points, render_only, return_alpha, return_median, return_distortion, return_normals,
+                   features is not None)
 
 
 def _result(out, screenspace_points, render_only, return_alpha=False, return_median=False, return_distortion=False,
-            return_normals=False):
+            return_normals=False, return_features=False):
     rendered_image, radii, depth = out[:3]
     res = {"render": rendered_image, "depth": depth} if render_only else \
         {"render": rendered_image, "viewspace_points": screenspace_points, "visibility_filter": radii > 0, "radii": radii,
          "depth": depth}
     if return_alpha:
         res["alpha"] = out[3]
-    if return_distortion:                   # the last output; the normals and the median pair sit in front of it
+    if return_distortion:                   # the last output; the feature map, the normals and the median pair sit in front of it
         res["distortion"] = out[-1]
+        out = out[:-1]
+    if return_features:
+        res["features"] = out[-1]
         out = out[:-1]
     if return_normals:
         res["normals"] = out[-1]
@@ -94,19 +100,21 @@ def _result(out, screenspace_points, render_only, return_alpha=False, return_med
 
 
 def render_raw(viewpoint_camera, pc, opt=DEFAULT_OPT, bg_color=None, scaling_modifier=1.0, render_only=False,
-               return_alpha=False, return_median=False, return_distortion=False, distortion_map="ndc", return_normals=False):
+               return_alpha=False, return_median=False, return_distortion=False, distortion_map="ndc", return_normals=False,
+               features=None):
     """render() for the common training configuration (SH colours, scale/rotation covariance), reading the STORED
     parameters of `pc` (`_xyz, _features_dc, _features_rest, _opacity, _scaling, _rotation`,
     /root/reference/scene/gaussian_model.py:47-52) instead of the activated getters: the activations and the
     dc|rest concatenation happen inside the rasterizer kernels.  Same return dict as render() (return_alpha,
-    return_median, return_distortion and return_normals included)."""
+    return_median, return_distortion, return_normals and features included)."""
     xyz = pc._xyz
     screenspace_points, rs = _view_setup(viewpoint_camera, pc, xyz, opt, bg_color, scaling_modifier)
     out = rasterize_gaussians_raw(xyz, screenspace_points, pc._features_dc, pc._features_rest, pc._opacity, pc._scaling,
                                   pc._rotation, rs, return_alpha=return_alpha, return_median=return_median,
                                   return_distortion=return_distortion, distortion_map=distortion_map,
-                                  return_normals=return_normals)
-    return _result(out, screenspace_points, render_only, return_alpha, return_median, return_distortion, return_normals)
+                                  return_normals=return_normals, features=features)
+    return _result(out, screenspace_points, render_only, return_alpha, return_median, return_distortion, return_normals,
+                   features is not None)
 
 
 class GaussianCloud:

@@ -26,6 +26,13 @@ towards the camera -- lr_render_normals, a pass behind the forward.  No backgrou
 scales + rotations (ValueError with cov3D_precomp).  Differentiable: a gradient reaching it runs lr_render_normals_backward behind the
 view's backward (and the distortion's) and reaches means3D / xyz, opacities, scales, rotations and means2D; the normal itself moves
 the rotations only (the axis choice and the sign are constants of the view).
+features=<(P, C) float32 tensor> (same three entry points) appends feature_map (C, H, W) behind the normals and in front of the
+distortion, which stays the last output: F[c] = sum_i w_i features[i, c] over the pixel's blended layers (semantic or instance
+logits, distilled 2D features, appearance codes; 1 <= C <= 256), used as given in both nodes -- lr_render_features, a pass behind the
+forward, 16 channels per tile walk.  No background term, no normalisation.  Works with cov3D_precomp.  Differentiable: a gradient
+reaching it runs lr_render_features_backward behind the view's backward (and the distortion's and the normals'), reaches means3D /
+xyz, opacities, scales, rotations (cov3D) and means2D as the other passes' terms do, and `features` itself.  ValueError for a wrong
+shape, dtype or row count, before any launch.
 config.set_absgrad(True): the backward of a view attaches `means2D.absgrad` [P,3] (AbsGS; lr_view_backward with dL_dmean2D_abs) to the means2D
 tensor the caller passed.
 
@@ -137,16 +144,26 @@ def _normals_outputs(ctx, rs, radii, geom, binning, img, capacity, inputs):
     return (normals,)
 
 
+def _features_outputs(ctx, rs, geom, binning, img, capacity, features):
+    """(feature_map,) of the forward whose buffers are given, as _normals_outputs; the backward needs the value (detached) and the
+    features as they were rendered (detached: the gradient goes to the node's input)."""
+    value = _C.render_features(geom, binning, img, features, rs, binning_capacity=capacity)
+    ctx.features = (value.detach(), features.detach())
+    return (value,)
+
+
 def _more_grads(ctx, grad_more):
-    """(grad_alpha, grad_median, grad_distortion, grad_normals) from the gradients behind (color, radii, depth): [alpha],
-    [median_depth, median_ids], [normals], [distortion]."""
+    """(grad_alpha, grad_median, grad_distortion, grad_normals, grad_features) from the gradients behind (color, radii, depth):
+    [alpha], [median_depth, median_ids], [normals], [feature_map], [distortion]."""
     tail = 1 if ctx.distortion is not None else 0
+    ftr = 1 if ctx.features is not None else 0
     nrm = 1 if ctx.normals is not None else 0
     grad_alpha = grad_more[0] if ctx.return_alpha else None
-    grad_median = grad_more[-2 - tail - nrm] if ctx.median_ids is not None else None
-    grad_normals = grad_more[-1 - tail] if nrm else None
+    grad_median = grad_more[-2 - tail - ftr - nrm] if ctx.median_ids is not None else None
+    grad_normals = grad_more[-1 - tail - ftr] if nrm else None
+    grad_features = grad_more[-1 - tail] if ftr else None
     grad_distortion = grad_more[-1] if tail else None
-    return grad_alpha, grad_median, grad_distortion, grad_normals
+    return grad_alpha, grad_median, grad_distortion, grad_normals, grad_features
 
 
 def _median_backward(ctx, grad_median, target, radii, geom, binning, img):
@@ -190,16 +207,36 @@ def _normals_backward(ctx, grad_normals, returned, fused, radii, geom, binning, 
     return dict(returned, **{k: (returned[k] if (returned[k] is not None or fused.get(k) is not None) else out[k]) for k in names})
 
 
+def _features_backward(ctx, grad_features, returned, fused, radii, geom, binning, img, plus_zero=True, **inputs):
+    """The feature map's term of every geometric gradient and dL/dfeatures (lr_render_features_backward), added as
+    _normals_backward adds the normals', behind it; cov3D takes part.  plus_zero: as _normals_backward.  Returns (`returned` with
+    the term, dL/dfeatures or None where it was accumulated into the leaf's .grad)."""
+    fused = fused or {}
+    names = tuple(returned)
+    targets = {k: (returned[k] if returned[k] is not None else fused.get(k)) for k in names}
+    targets["features"] = fused.get("features")
+    value, features = ctx.features
+    out = _C.render_features_backward(geom, binning, img, grad_features, value, features, radii, ctx.raster_settings,
+                                      slots=ctx.num_rendered, binning_capacity=ctx.binning_capacity, accumulate_into=targets,
+                                      **inputs)
+    written = [returned[k] for k in names if returned[k] is not None]
+    if plus_zero and written:
+        torch._foreach_add_(written, 0.0)
+    returned = {k: (returned[k] if (returned[k] is not None or fused.get(k) is not None) else out[k]) for k in names}
+    return returned, (None if fused.get("features") is not None else out["features"])
+
+
 def _forward_tail(ctx, out, P, rs, geom, binning, img, capacity, return_alpha, return_median, return_distortion, distortion_map,
-                  return_normals=False, normal_inputs=None):
-    """The end of both nodes' forward: `out` = (color, radii, depth) gains alpha, (median_depth, median_ids), normals, distortion,
-    in that order, from the state of the forward whose buffers are given (after a re-render, the re-render's), and ctx what they
-    need."""
+                  return_normals=False, normal_inputs=None, features=None):
+    """The end of both nodes' forward: `out` = (color, radii, depth) gains alpha, (median_depth, median_ids), normals, feature_map,
+    distortion, in that order, from the state of the forward whose buffers are given (after a re-render, the re-render's), and ctx
+    what they need."""
     ctx.return_alpha = bool(return_alpha)
     ctx.median_ids = None
     ctx.distortion = None
     ctx.normals = None
-    if not return_alpha and not return_median and not return_distortion and not return_normals:
+    ctx.features = None
+    if not return_alpha and not return_median and not return_distortion and not return_normals and features is None:
         return out
     # the backward needs the image state's final T only -- the alpha tensor itself is not kept (as depth_image)
     ctx.set_materialize_grads(False)            # an unused alpha / median / distortion output arrives as None: the default kernels
@@ -209,15 +246,19 @@ def _forward_tail(ctx, out, P, rs, geom, binning, img, capacity, return_alpha, r
         out += _median_outputs(ctx, P, rs, geom, binning, img, capacity)
     if return_normals:
         out += _normals_outputs(ctx, rs, out[1], geom, binning, img, capacity, normal_inputs)
+    if features is not None:
+        out += _features_outputs(ctx, rs, geom, binning, img, capacity, features)
     if return_distortion:
         out += _distortion_outputs(ctx, P, rs, geom, binning, img, capacity, distortion_map)
     return out
 
 
 def _backward_extras(ctx, grad_median, grad_distortion, grad_normals, returned, fused, radii, geom, binning, img, armed=False,
-                     **inputs):
-    """The median depth's term, then the distortion's, then the rendered normals', added behind the view's backward.  returned / fused: {name: tensor or None}
-    of what that backward returned / of the leaves' .grad it accumulated into, under _C.distortion_backward's names, as `inputs`."""
+                     grad_features=None, **inputs):
+    """The median depth's term, then the distortion's, then the rendered normals', then the feature map's, added behind the view's
+    backward.  returned / fused: {name: tensor or None} of what that backward returned / of the leaves' .grad it accumulated into,
+    under _C.distortion_backward's names, as `inputs` (fused["features"]: the features' .grad).  Returns (returned, dL/dfeatures --
+    None without grad_features, and where it was accumulated into the leaf's .grad)."""
     fused = fused or {}
     if grad_median is not None:
         m3 = returned["means3D"]
@@ -226,7 +267,11 @@ def _backward_extras(ctx, grad_median, grad_distortion, grad_normals, returned, 
         returned = _distortion_backward(ctx, grad_distortion, returned, fused, geom, binning, img, **inputs)
     if grad_normals is not None:
         returned = _normals_backward(ctx, grad_normals, returned, fused, radii, geom, binning, img, plus_zero=not armed, **inputs)
-    return returned
+    grad_of_features = None
+    if grad_features is not None:
+        returned, grad_of_features = _features_backward(ctx, grad_features, returned, fused, radii, geom, binning, img,
+                                                        plus_zero=not armed, **inputs)
+    return returned, grad_of_features
 
 
 _RAW_NAMES = dict(xyz="means3D", scaling="scales", rotation="rotations")     # the raw node's names -> _C.distortion_backward's
@@ -239,10 +284,12 @@ class _RasterizeGaussians(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                 raster_settings, return_alpha=False, return_median=False, return_distortion=False, distortion_map="ndc",
-                return_normals=False):
+                return_normals=False, features=None):
         rs = raster_settings
         if return_normals:                              # before any launch
             _C.require_scale_rot("return_normals", scales, rotations, cov3Ds_precomp)
+        if features is not None:
+            _C.require_features("features", features, means3D.shape[0])
         args = (rs.bg, means3D, colors_precomp, opacities, scales, rotations, rs.scale_modifier, cov3Ds_precomp,
                 rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, rs.image_height, rs.image_width, sh,
                 rs.sh_degree, rs.campos, rs.prefiltered, rs.debug)
@@ -262,7 +309,7 @@ class _RasterizeGaussians(torch.autograd.Function):
         ctx.binning_capacity = capacity
         # leaf inputs whose .grad already exists can be accumulated into in place by the backward kernel
         ctx.leaf_inputs = dict(means3D=means3D, means2D=means2D, sh=sh, colors=colors_precomp, opacity=opacities,
-                               scales=scales, rotations=rotations, cov3D=cov3Ds_precomp) \
+                               scales=scales, rotations=rotations, cov3D=cov3Ds_precomp, features=features) \
             if config.fused_grad_accumulation() else None
         # config.set_depth_gradient as it is at this forward: the depth image is kept for a depth-mode backward
         # (detached: the output itself on ctx would be a reference cycle through its grad_fn, freed only by the cyclic GC)
@@ -272,11 +319,11 @@ class _RasterizeGaussians(torch.autograd.Function):
         ctx.save_for_backward(colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geom, binning, img)
         return _forward_tail(ctx, (color, radii, depth), means3D.shape[0], rs, geom, binning, img, capacity, return_alpha,
                              return_median, return_distortion, distortion_map, return_normals,
-                             dict(means3D=means3D, scales=scales, rotations=rotations, cov3D_precomp=cov3Ds_precomp))
+                             dict(means3D=means3D, scales=scales, rotations=rotations, cov3D_precomp=cov3Ds_precomp), features)
 
     @staticmethod
     def backward(ctx, grad_out_color, grad_radii, grad_depth, *grad_more):
-        grad_alpha, grad_median, grad_distortion, grad_normals = _more_grads(ctx, grad_more)
+        grad_alpha, grad_median, grad_distortion, grad_normals, grad_features = _more_grads(ctx, grad_more)
         config.require_antialiasing(ctx.antialiasing)   # before anything is launched or written
         rs = ctx.raster_settings
         colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geom, binning, img = ctx.saved_tensors
@@ -287,7 +334,7 @@ class _RasterizeGaussians(torch.autograd.Function):
                 rs.campos, geom, ctx.num_rendered, binning, img, rs.debug)
         accumulate_into = None
         if ctx.leaf_inputs is not None:                 # an input without a fusable .grad (None): the dense path
-            accumulate_into = {name: _fusable_grad(t, means3D.device) for name, t in ctx.leaf_inputs.items()}
+            accumulate_into = {name: _fusable_grad(t, means3D.device) for name, t in ctx.leaf_inputs.items() if t is not None}
         try:
             # the binding picks the mode: depth mode needs the kept depth image (switch on at the forward) and grad_depth
             g = _C.rasterize_gaussians_backward(
@@ -297,12 +344,12 @@ class _RasterizeGaussians(torch.autograd.Function):
              grad_scales, grad_rotations) = g[:8]
             if ctx.absgrad_to is not None:              # gsplat's convention; replaced at every backward
                 ctx.absgrad_to.absgrad = g[8]
-            d = _backward_extras(
+            d, grad_of_features = _backward_extras(
                 ctx, grad_median, grad_distortion, grad_normals,
                 dict(means2D=grad_means2D, opacity=grad_opacities, means3D=grad_means3D, scales=grad_scales,
                      rotations=grad_rotations, cov3D=grad_cov3Ds_precomp),
-                accumulate_into, radii, geom, binning, img, means3D=means3D, scales=scales, rotations=rotations,
-                cov3D_precomp=cov3Ds_precomp)
+                accumulate_into, radii, geom, binning, img, grad_features=grad_features, means3D=means3D, scales=scales,
+                rotations=rotations, cov3D_precomp=cov3Ds_precomp)
             grad_means2D, grad_opacities, grad_means3D = d["means2D"], d["opacity"], d["means3D"]
             grad_scales, grad_rotations, grad_cov3Ds_precomp = d["scales"], d["rotations"], d["cov3D"]
         except Exception:
@@ -312,12 +359,12 @@ class _RasterizeGaussians(torch.autograd.Function):
             raise
         # order of the forward inputs (RAST/.../__init__.py:144-154); gradients of absent inputs are None-able
         return (grad_means3D, grad_means2D, grad_sh, grad_colors_precomp, grad_opacities, grad_scales, grad_rotations,
-                grad_cov3Ds_precomp, None, None, None, None, None, None)
+                grad_cov3Ds_precomp, None, None, None, None, None, None, grad_of_features)
 
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                         raster_settings, return_alpha=False, return_median=False, return_distortion=False, distortion_map="ndc",
-                        return_normals=False):
+                        return_normals=False, features=None):
     """The operator.  Its autograd node is compiled (csrc/torch_ext.cpp RasterizeFn: forward and backward run without the
     interpreter -- the Python node below cost more host time per 1080p view than the GPU needs for it); with settings.debug
     the Python node runs instead, because it is the one that writes the reference's snapshot_fw.dump / snapshot_bw.dump.
@@ -335,12 +382,17 @@ def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales,
     return_normals: the outputs gain normals (3, H, W), the rendered normal map (module docstring), behind the median pair and in
     front of the distortion.  Needs scales + rotations (ValueError otherwise, before any launch).  As its siblings it always runs
     the Python node; an unused normals output leaves the backward exactly as it is, a gradient reaching it runs
-    lr_render_normals_backward behind the view's backward (and the distortion's), fused accumulation on or off."""
+    lr_render_normals_backward behind the view's backward (and the distortion's), fused accumulation on or off.
+    features: a (P, C) float32 tensor; the outputs gain feature_map (C, H, W) (module docstring) behind the normals and in front
+    of the distortion.  ValueError for a wrong shape, dtype or row count, before any launch.  As its siblings it always runs the
+    Python node; an unused feature output leaves the backward exactly as it is and launches nothing, a gradient reaching it runs
+    lr_render_features_backward behind the view's backward (and the distortion's and the normals'), fused accumulation on or off,
+    and `features` receives its gradient."""
     rs = raster_settings
-    if rs.debug or return_median or return_distortion or return_normals:
+    if rs.debug or return_median or return_distortion or return_normals or features is not None:
         return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
                                          cov3Ds_precomp, rs, bool(return_alpha), bool(return_median), bool(return_distortion),
-                                         distortion_map, bool(return_normals))
+                                         distortion_map, bool(return_normals), features)
     capacity = config.capacity_for(means3D, rs)
     fused = config.fused_grad_accumulation()
     offered = config.offered_grad_output()
@@ -380,8 +432,10 @@ class _RasterizeGaussiansRaw(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, xyz, means2D, features_dc, features_rest, opacity, scaling, rotation, raster_settings, return_alpha=False,
-                return_median=False, return_distortion=False, distortion_map="ndc", return_normals=False):
+                return_median=False, return_distortion=False, distortion_map="ndc", return_normals=False, features=None):
         rs = raster_settings
+        if features is not None:                        # before any launch
+            _C.require_features("features", features, xyz.shape[0])
         ctx.antialiasing = config.antialiasing()        # as _RasterizeGaussians
         ctx.absgrad_to = means2D if config.absgrad() else None
 
@@ -395,7 +449,7 @@ class _RasterizeGaussiansRaw(torch.autograd.Function):
         ctx.num_rendered = num_rendered
         ctx.binning_capacity = capacity
         ctx.leaf_inputs = dict(xyz=xyz, means2D=means2D, features_dc=features_dc, features_rest=features_rest,
-                               opacity=opacity, scaling=scaling, rotation=rotation) \
+                               opacity=opacity, scaling=scaling, rotation=rotation, features=features) \
             if config.fused_grad_accumulation() else None
         ctx.depth_image = depth.detach() if config.depth_gradient() else None       # as _RasterizeGaussians
         if ctx.depth_image is not None:
@@ -403,11 +457,11 @@ class _RasterizeGaussiansRaw(torch.autograd.Function):
         ctx.save_for_backward(xyz, features_dc, features_rest, opacity, scaling, rotation, radii, geom, binning, img)
         return _forward_tail(ctx, (color, radii, depth), xyz.shape[0], rs, geom, binning, img, capacity, return_alpha,
                              return_median, return_distortion, distortion_map, return_normals,
-                             dict(means3D=xyz, scales=scaling, rotations=rotation, raw=True))
+                             dict(means3D=xyz, scales=scaling, rotations=rotation, raw=True), features)
 
     @staticmethod
     def backward(ctx, grad_out_color, grad_radii, grad_depth, *grad_more):
-        grad_alpha, grad_median, grad_distortion, grad_normals = _more_grads(ctx, grad_more)
+        grad_alpha, grad_median, grad_distortion, grad_normals, grad_features = _more_grads(ctx, grad_more)
         config.require_antialiasing(ctx.antialiasing)   # before anything is launched or written
         rs = ctx.raster_settings
         xyz, features_dc, features_rest, opacity, scaling, rotation, radii, geom, binning, img = ctx.saved_tensors
@@ -423,11 +477,16 @@ class _RasterizeGaussiansRaw(torch.autograd.Function):
             g_dc, g_rest = _fusable_grad(li["features_dc"], xyz.device), _fusable_grad(li["features_rest"], xyz.device)
             if g_dc is not None and (g_rest is not None or features_rest.numel() == 0):
                 accumulate_into["features"] = (g_dc, g_rest)
+        # the feature table's .grad (the raw backward's "features" are the SH pair above)
+        fused_table = _fusable_grad(ctx.leaf_inputs["features"], xyz.device) \
+            if (ctx.leaf_inputs is not None and ctx.leaf_inputs["features"] is not None) else None
         def extras(g, fused, armed=False):
             # the median's and the distortion's terms on the result g of the raw backward, under the activated node's names
             returned = _from_raw_names(dict(means2D=g[0], xyz=g[1], opacity=g[4], scaling=g[5], rotation=g[6]))
-            return _backward_extras(ctx, grad_median, grad_distortion, grad_normals, returned, _from_raw_names(fused), radii, geom,
-                                    binning, img, armed=armed,
+            fused = {k: v for k, v in _from_raw_names(fused).items() if k != "features"}
+            fused["features"] = fused_table
+            return _backward_extras(ctx, grad_median, grad_distortion, grad_normals, returned, fused, radii, geom,
+                                    binning, img, armed=armed, grad_features=grad_features,
                                     means3D=xyz, opacities=opacity, scales=scaling, rotations=rotation, raw=True)
 
         # an armed FusedAdam over exactly these six tensors (optim.FusedAdam.arm_fused_backward): the gradients go to tensors
@@ -445,9 +504,9 @@ class _RasterizeGaussiansRaw(torch.autograd.Function):
             if ctx.absgrad_to is not None:              # written in full also here (zero-filled like means2D): not part of the step
                 ctx.absgrad_to.absgrad = g[7]
             # the rows the extras add to are rows the view visited; before the step reads them
-            extras(g, None, armed=True)
+            _, g_table = extras(g, None, armed=True)
             opt.apply_armed_step(geom, [xyz, features_dc, features_rest, opacity, scaling, rotation], list(g[1:7]))
-            return None, g[0], None, None, None, None, None, None, None, None, None, None, None
+            return None, g[0], None, None, None, None, None, None, None, None, None, None, None, g_table
         g = _C.rasterize_gaussians_raw_backward(
             rs.bg, xyz, radii, features_dc, features_rest, opacity, scaling, rotation, rs.scale_modifier, rs.viewmatrix,
             rs.projmatrix, rs.tanfovx, rs.tanfovy, grad_out_color, rs.sh_degree, rs.campos, geom, ctx.num_rendered,
@@ -455,23 +514,25 @@ class _RasterizeGaussiansRaw(torch.autograd.Function):
         if ctx.absgrad_to is not None:
             ctx.absgrad_to.absgrad = g[7]
         g_dc, g_rest = g[2], g[3]
-        d = extras(g, accumulate_into)
+        d, g_table = extras(g, accumulate_into)
         g_means2D, g_op, g_xyz, g_sc, g_rot = d["means2D"], d["opacity"], d["means3D"], d["scales"], d["rotations"]
-        return g_xyz, g_means2D, g_dc, g_rest, g_op, g_sc, g_rot, None, None, None, None, None, None
+        return g_xyz, g_means2D, g_dc, g_rest, g_op, g_sc, g_rot, None, None, None, None, None, None, g_table
 
 
 def rasterize_gaussians_raw(xyz, means2D, features_dc, features_rest, opacity, scaling, rotation, raster_settings,
                             return_alpha=False, return_median=False, return_distortion=False, distortion_map="ndc",
-                            return_normals=False):
+                            return_normals=False, features=None):
     """(color, radii, depth) from the stored GaussianModel parameters (pre-activation), see _RasterizeGaussiansRaw;
     return_alpha: (color, radii, depth, alpha) as rasterize_gaussians; return_median: (median_depth, median_ids) behind them, as
     rasterize_gaussians (this entry point always runs its Python node); the median depth's gradient reaches xyz;
     return_distortion / distortion_map: distortion last, as rasterize_gaussians; its gradient reaches xyz, opacity, scaling and
     rotation; return_normals: normals (3, H, W) behind the median pair, in front of the distortion, as rasterize_gaussians (the
-    axis is the argmin of the stored log-scales, the quaternion is normalised as the kernels normalise it)."""
+    axis is the argmin of the stored log-scales, the quaternion is normalised as the kernels normalise it); features: a (P, C)
+    float32 tensor, feature_map (C, H, W) behind the normals and in front of the distortion, as rasterize_gaussians (used as
+    given: the table has no activation)."""
     return _RasterizeGaussiansRaw.apply(xyz, means2D, features_dc, features_rest, opacity, scaling, rotation,
                                         raster_settings, bool(return_alpha), bool(return_median), bool(return_distortion),
-                                        distortion_map, bool(return_normals))
+                                        distortion_map, bool(return_normals), features)
 
 
 _EMPTY = torch.Tensor([])           # never written: one instance serves every call (three constructions per call were ~6 us)
@@ -490,11 +551,12 @@ class GaussianRasterizer(nn.Module):
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
                 cov3D_precomp=None, return_alpha=False, return_median=False, return_distortion=False, distortion_map="ndc",
-                return_normals=False):
+                return_normals=False, features=None):
         """(color, radii, depth), or with return_alpha=True (color, radii, depth, alpha): alpha (1, H, W) = 1 - T_final; with
         return_median=True the outputs gain (median_depth, median_ids) at their end, with return_distortion=True the distortion
         (1, H, W) of distortion_map's mapped depth behind those, and with return_normals=True the rendered normal map (3, H, W)
-        between the median pair and the distortion (rasterize_gaussians; ValueError with cov3D_precomp)."""
+        between the median pair and the distortion (rasterize_gaussians; ValueError with cov3D_precomp), and with
+        features=<(P, C) float32 tensor> the feature map (C, H, W) behind the normals, in front of the distortion."""
         rs = self.raster_settings
         if (shs is None) == (colors_precomp is None):
             raise Exception('Please provide excatly one of either SHs or precomputed colors!')
@@ -509,10 +571,10 @@ class GaussianRasterizer(nn.Module):
         scales = empty if scales is None else scales
         rotations = empty if rotations is None else rotations
         cov3D_precomp = empty if cov3D_precomp is None else cov3D_precomp
-        if return_alpha or return_median or return_distortion or return_normals:
+        if return_alpha or return_median or return_distortion or return_normals or features is not None:
             return rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
                                        cov3D_precomp, rs, return_alpha=return_alpha, return_median=return_median,
                                        return_distortion=return_distortion, distortion_map=distortion_map,
-                                       return_normals=return_normals)
+                                       return_normals=return_normals, features=features)
         return rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
                                    cov3D_precomp, rs)
