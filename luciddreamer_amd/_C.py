@@ -212,6 +212,70 @@ def median_backward(geomBuffer, binningBuffer, imageBuffer, radii, median_ids, d
 
 
 distortion_map_coefficients = _lib_check.distortion_map_coefficients
+_present = lambda t: t is not None and t.numel() != 0
+_ptr = lambda t: t.data_ptr() if t is not None else None
+
+
+def _radii_on(who, dev, radii, P):
+    """The forward's radii as the library reads them: int32 [P], contiguous, on `dev`."""
+    rad = radii.contiguous()
+    _sized(who, radii=(rad, P))
+    _int32_on(who, dev, radii=rad)
+    return rad
+
+
+def _side_view(rs, P, dev, *, means3D, opacities, scales, rotations, cov3D_precomp, raw):
+    """(lr_view, tensors to keep alive) of a pass behind a forward: the forward's camera (rs: its raster settings) and its geometry
+    in the representation given -- scales + rotations, cov3D_precomp, or neither where the pass reads none (an empty placeholder is
+    absent) -- each made _dense once and held to its element count."""
+    d = lambda t, given: _dense(t, dev) if given else None
+    keep = view, proj, campos, m3, op, sc, rot, cov = (
+        _dense(rs.viewmatrix, dev), _dense(rs.projmatrix, dev), _dense(rs.campos, dev), _dense(means3D, dev),
+        d(opacities, opacities is not None), d(scales, _present(scales)), d(rotations, _present(rotations)),
+        d(cov3D_precomp, _present(cov3D_precomp)))
+    _sized("the forward's view", viewmatrix=(view, 16), projmatrix=(proj, 16), campos=(campos, 3), means3D=(m3, 3 * P),
+           opacities=(op, P), scales=(sc, 3 * P), rotations=(rot, 4 * P), cov3D_precomp=(cov, 6 * P))
+    v = _lib_check.View(P=P, D=0, M=1, raw=1 if raw else 0, width=int(rs.image_width), height=int(rs.image_height),
+                        means3D=m3.data_ptr(), opacities=_ptr(op), scales=_ptr(sc), scale_modifier=float(rs.scale_modifier),
+                        rotations=_ptr(rot), cov3D_precomp=_ptr(cov), viewmatrix=view.data_ptr(), projmatrix=proj.data_ptr(),
+                        campos=campos.data_ptr(), tan_fovx=float(rs.tanfovx), tan_fovy=float(rs.tanfovy))
+    return v, keep
+
+
+_SIDE_ACC_BITS = {"means2D": 0, "opacity": 2, "means3D": 4, "cov3D": 5, "scales": 7, "rotations": 8, "features": 9}
+
+
+def _geometric_shapes(P, v):
+    """{name: shape, or None for the representation not in use} of the geometric gradients of a pass whose lr_view is `v`."""
+    return {"means2D": (P, 3), "opacity": (P, 1), "means3D": (P, 3), "scales": (P, 3) if v.scales else None,
+            "rotations": (P, 4) if v.rotations else None, "cov3D": (P, 6) if v.cov3D_precomp else None}
+
+
+def _grad_targets(who, dev, shapes, accumulate_into):
+    """(out, accumulate_mask) of a side pass's backward.  shapes: {name: shape or None}; per name `out` holds None (no shape), the
+    tensor accumulate_into gives for it -- contiguous float32 of that many elements on `dev`, 16-byte aligned (the kernels add
+    with 16-byte accesses), RuntimeError otherwise; its bit of the mask is set -- or a new tensor, which the library writes in full."""
+    out, mask = {}, 0
+    for name, shape in shapes.items():
+        t = (accumulate_into or {}).get(name)
+        if shape is None:
+            out[name] = None
+        elif t is not None:
+            if not t.is_contiguous() or t.dtype != torch.float32 or t.numel() != int(torch.Size(shape).numel()) or t.device != dev \
+                    or t.data_ptr() % 16 != 0:
+                raise RuntimeError(f"{who}: accumulate_into[{name!r}] must be a contiguous, 16-byte aligned float32 tensor of "
+                                   f"{shape} on {dev}")
+            out[name] = t
+            mask |= 1 << _SIDE_ACC_BITS[name]
+        else:
+            out[name] = torch.empty(shape, dtype=torch.float32, device=dev)
+    return out, mask
+
+
+def _grad_fields(out, mask):
+    """The gradient-output members of a side pass's backward struct, from _grad_targets' pair."""
+    return dict(dL_dmean2D=_ptr(out["means2D"]), dL_dopacity=_ptr(out["opacity"]), dL_dmean3D=_ptr(out["means3D"]),
+                dL_dcov3D=_ptr(out.get("cov3D")), dL_dscale=_ptr(out["scales"]), dL_drot=_ptr(out["rotations"]), accumulate_mask=mask)
 
 
 def render_distortion(geomBuffer, binningBuffer, imageBuffer, P, image_height, image_width, *, distortion_map="ndc",
@@ -219,7 +283,6 @@ def render_distortion(geomBuffer, binningBuffer, imageBuffer, P, image_height, i
     """(distortion (1, H, W), moments (H, W, 4)) float32 of the forward that left the three buffers (lr_render_distortion, on the
     current stream): the depth distortion of each pixel's blended layers for the mapped depth of `distortion_map`
     (distortion_map_coefficients), and the per-pixel sums distortion_backward needs.  No autograd."""
-    import torch
     H, W = int(image_height), int(image_width)
     dev = imageBuffer.device
     c0, c1, c2 = distortion_map_coefficients(distortion_map)
@@ -240,75 +303,28 @@ def distortion_backward(geomBuffer, binningBuffer, imageBuffer, dL_ddistortion, 
     accumulate_into: {"means2D", "opacity", "means3D", "scales", "rotations", "cov3D": contiguous float32 tensor or None} -- a
     given tensor is ADDED to in place (rows of Gaussians that own a tile instance; the others stay untouched), a missing one is
     a new tensor written in full.  Returns the dict of the six (None for the representation not in use)."""
-    import torch
+    who = "distortion_backward"
     dev = imageBuffer.device
     P = int(means3D.shape[0])
     H, W = int(rs.image_height), int(rs.image_width)
     c0, c1, c2 = distortion_map_coefficients(distortion_map)
-    present = lambda t: t is not None and t.numel() != 0
-    cont = lambda t: _dense(t, dev)
-    keep = [cont(dL_ddistortion), cont(distortion), cont(moments), cont(rs.viewmatrix), cont(rs.projmatrix), cont(rs.campos),
-            cont(means3D), cont(opacities) if opacities is not None else None]
-    dL, dist, mom, view, proj, campos, m3, op = keep
-    if raw and op is None:
-        raise RuntimeError("distortion_backward: raw mode needs the stored opacities")
-    _sized("distortion_backward", viewmatrix=(view, 16), projmatrix=(proj, 16), campos=(campos, 3), means3D=(m3, 3 * P),
-           opacities=(op, P), scales=(scales if present(scales) else None, 3 * P),
-           rotations=(rotations if present(rotations) else None, 4 * P),
-           cov3D_precomp=(cov3D_precomp if present(cov3D_precomp) else None, 6 * P))
-    if dL.numel() != H * W or dist.numel() != H * W or mom.numel() != 4 * H * W:
-        raise RuntimeError("distortion_backward: dL_ddistortion, distortion and moments must be (1, H, W), (1, H, W), (H, W, 4)")
-    sc = cont(scales) if present(scales) else None
-    rot = cont(rotations) if present(rotations) else None
-    cov = cont(cov3D_precomp) if present(cov3D_precomp) else None
-    shapes = {"means2D": (P, 3), "opacity": (P, 1), "means3D": (P, 3), "scales": (P, 3) if sc is not None else None,
-              "rotations": (P, 4) if rot is not None else None, "cov3D": (P, 6) if cov is not None else None}
-    bits = {"means2D": 0, "opacity": 2, "means3D": 4, "cov3D": 5, "scales": 7, "rotations": 8}
-    out, mask = {}, 0
-    for name, shape in shapes.items():
-        t = (accumulate_into or {}).get(name)
-        if shape is None:
-            out[name] = None
-        elif t is not None:
-            if not t.is_contiguous() or t.dtype != torch.float32 or t.numel() != int(torch.Size(shape).numel()) or t.device != dev:
-                raise RuntimeError(f"distortion_backward: accumulate_into[{name!r}] must be a contiguous float32 tensor of {shape}")
-            out[name] = t
-            mask |= 1 << bits[name]
-        else:
-            out[name] = torch.empty(shape, dtype=torch.float32, device=dev)
-    ptr = lambda t: t.data_ptr() if t is not None else None
-    v = _lib_check.View(P=P, D=0, M=1, raw=1 if raw else 0, width=W, height=H, means3D=m3.data_ptr(), opacities=ptr(op),
-                        scales=ptr(sc), scale_modifier=float(rs.scale_modifier), rotations=ptr(rot), cov3D_precomp=ptr(cov),
-                        viewmatrix=view.data_ptr(), projmatrix=proj.data_ptr(), campos=campos.data_ptr(),
-                        tan_fovx=float(rs.tanfovx), tan_fovy=float(rs.tanfovy))
+    dL, dist, mom = _dense(dL_ddistortion, dev), _dense(distortion, dev), _dense(moments, dev)
+    if raw and opacities is None:
+        raise RuntimeError(f"{who}: raw mode needs the stored opacities")
+    _sized(who, dL_ddistortion=(dL, H * W), distortion=(dist, H * W), moments=(mom, 4 * H * W))
+    v, keep = _side_view(rs, P, dev, means3D=means3D, opacities=opacities, scales=scales, rotations=rotations,
+                         cov3D_precomp=cov3D_precomp, raw=raw)
+    out, mask = _grad_targets(who, dev, _geometric_shapes(P, v), accumulate_into)
     a = _lib_check.DistortionBackwardArgs(
         view=v, dL_ddistortion=dL.data_ptr(), moments=mom.data_ptr(), distortion=dist.data_ptr(), map_c0=c0, map_c1=c1, map_c2=c2,
-        dL_dmean2D=ptr(out["means2D"]), dL_dopacity=ptr(out["opacity"]), dL_dmean3D=ptr(out["means3D"]), dL_dcov3D=ptr(out["cov3D"]),
-        dL_dscale=ptr(out["scales"]), dL_drot=ptr(out["rotations"]), accumulate_mask=mask,
-        **_forward_state(geomBuffer, binningBuffer, imageBuffer, binning_capacity, dev))
-    _call("lr_distortion_backward", a, dev, "distortion_backward")
+        **_grad_fields(out, mask), **_forward_state(geomBuffer, binningBuffer, imageBuffer, binning_capacity, dev))
+    _call("lr_distortion_backward", a, dev, who)
     del keep
     return out
 
 
-def _normals_view(rs, P, means3D, opacities, scales, rotations, raw, dev):
-    """(lr_view, tensors to keep alive) of the rendered-normal entries: the forward's camera and scales + rotations."""
-    cont = lambda t: _dense(t, dev)
-    keep = [cont(rs.viewmatrix), cont(rs.projmatrix), cont(rs.campos), cont(means3D), cont(scales), cont(rotations),
-            cont(opacities) if opacities is not None else None]
-    view, proj, campos, m3, sc, rot, op = keep
-    _sized("rendered normals", viewmatrix=(view, 16), projmatrix=(proj, 16), campos=(campos, 3), means3D=(m3, 3 * P),
-           scales=(sc, 3 * P), rotations=(rot, 4 * P), opacities=(op, P))
-    v = _lib_check.View(P=P, D=0, M=1, raw=1 if raw else 0, width=int(rs.image_width), height=int(rs.image_height),
-                        means3D=m3.data_ptr(), opacities=op.data_ptr() if op is not None else None, scales=sc.data_ptr(),
-                        scale_modifier=float(rs.scale_modifier), rotations=rot.data_ptr(), viewmatrix=view.data_ptr(),
-                        projmatrix=proj.data_ptr(), campos=campos.data_ptr(), tan_fovx=float(rs.tanfovx), tan_fovy=float(rs.tanfovy))
-    return v, keep
-
-
 def require_scale_rot(who, scales, rotations, cov3D_precomp):
-    present = lambda t: t is not None and t.numel() != 0
-    if present(cov3D_precomp) or not present(scales) or not present(rotations):
+    if _present(cov3D_precomp) or not _present(scales) or not _present(rotations):
         raise ValueError(f"{who}: the rendered normal map needs scales + rotations (a Gaussian given by cov3D_precomp has no normal)")
 
 
@@ -318,26 +334,17 @@ def render_normals(geomBuffer, binningBuffer, imageBuffer, radii, rs, *, means3D
     current stream): N = sum_i w_i n_i over each pixel's blended layers, n_i the Gaussian's view-space normal (its shortest
     axis, turned towards the camera), and the per-Gaussian {n.xyz, sign (k + 1)} render_normals_backward needs.  rs: the
     forward's raster settings; radii: its radii.  ValueError with cov3D_precomp, before any launch.  No autograd."""
-    import torch
     require_scale_rot("render_normals", scales, rotations, cov3D_precomp)
     dev = imageBuffer.device
     P = int(means3D.shape[0])
-    H, W = int(rs.image_height), int(rs.image_width)
-    normals = torch.empty((3, H, W), dtype=torch.float32, device=dev)
+    normals = torch.empty((3, int(rs.image_height), int(rs.image_width)), dtype=torch.float32, device=dev)
     gauss_normals = torch.empty((P, 4), dtype=torch.float32, device=dev)
-    v, keep = _normals_view(rs, P, means3D, None, scales, rotations, raw, dev)
-    rad = radii.contiguous()
-    _sized("render_normals", radii=(rad, P))
-    _int32_on("render_normals", dev, radii=rad)
-    _buffers_on(dev, geomBuffer, binningBuffer, imageBuffer)
-    a = _lib_check.NormalsRenderArgs(view=v, radii=rad.data_ptr(), geom_buffer=geomBuffer.data_ptr(),
-                                     binning_buffer=binningBuffer.data_ptr(), image_buffer=imageBuffer.data_ptr(),
-                                     binning_capacity=int(binning_capacity), out_normals=normals.data_ptr(),
-                                     out_gauss_normals=gauss_normals.data_ptr(), stream=torch.cuda.current_stream(dev).cuda_stream)
-    with _lib_check.on_device(dev):
-        rc = _lib_check.lib().lr_render_normals(a)
-    if rc < 0:
-        _lib_check.raise_for(rc, "render_normals")
+    v, keep = _side_view(rs, P, dev, means3D=means3D, opacities=None, scales=scales, rotations=rotations, cov3D_precomp=None, raw=raw)
+    rad = _radii_on("render_normals", dev, radii, P)
+    a = _lib_check.NormalsRenderArgs(view=v, radii=rad.data_ptr(), out_normals=normals.data_ptr(),
+                                     out_gauss_normals=gauss_normals.data_ptr(),
+                                     **_forward_state(geomBuffer, binningBuffer, imageBuffer, binning_capacity, dev))
+    _call("lr_render_normals", a, dev, "render_normals")
     del keep
     return normals, gauss_normals
 
@@ -349,44 +356,27 @@ def render_normals_backward(geomBuffer, binningBuffer, imageBuffer, dL_dnormals,
     distortion backward -- of the same forward).  Arguments as distortion_backward; accumulate_into: {"means2D", "opacity",
     "means3D", "scales", "rotations": tensor or None}, a given tensor is ADDED to in place, a missing one is a new tensor written in
     full.  Returns the dict of the five plus "gauss_normal": dL/dn per Gaussian (P, 3), always a new tensor."""
-    import torch
-    require_scale_rot("render_normals_backward", scales, rotations, cov3D_precomp)
+    who = "render_normals_backward"
+    require_scale_rot(who, scales, rotations, cov3D_precomp)
     dev = imageBuffer.device
     P = int(means3D.shape[0])
     H, W = int(rs.image_height), int(rs.image_width)
-    cont = lambda t: _dense(t, dev)
-    dL, nrm, gn, rad = cont(dL_dnormals), cont(normals), cont(gauss_normals), radii.contiguous()
+    dL, nrm, gn = _dense(dL_dnormals, dev), _dense(normals, dev), _dense(gauss_normals, dev)
     if raw and opacities is None:
-        raise RuntimeError("render_normals_backward: raw mode needs the stored opacities")
-    if dL.numel() != 3 * H * W or nrm.numel() != 3 * H * W or gn.numel() != 4 * P:
-        raise RuntimeError("render_normals_backward: dL_dnormals, normals and gauss_normals must be (3, H, W), (3, H, W), (P, 4)")
-    _sized("render_normals_backward", radii=(rad, P))
-    _int32_on("render_normals_backward", dev, radii=rad)
-    _buffers_on(dev, geomBuffer, binningBuffer, imageBuffer)
-    shapes = {"means2D": (P, 3), "opacity": (P, 1), "means3D": (P, 3), "scales": (P, 3), "rotations": (P, 4)}
-    bits = {"means2D": 0, "opacity": 2, "means3D": 4, "scales": 7, "rotations": 8}
-    out, mask = {}, 0
-    for name, shape in shapes.items():
-        t = (accumulate_into or {}).get(name)
-        if t is not None:
-            if not t.is_contiguous() or t.dtype != torch.float32 or t.numel() != int(torch.Size(shape).numel()) or t.device != dev:
-                raise RuntimeError(f"render_normals_backward: accumulate_into[{name!r}] must be a contiguous float32 tensor of {shape}")
-            out[name] = t
-            mask |= 1 << bits[name]
-        else:
-            out[name] = torch.empty(shape, dtype=torch.float32, device=dev)
+        raise RuntimeError(f"{who}: raw mode needs the stored opacities")
+    _sized(who, dL_dnormals=(dL, 3 * H * W), normals=(nrm, 3 * H * W), gauss_normals=(gn, 4 * P))
+    rad = _radii_on(who, dev, radii, P)
+    v, keep = _side_view(rs, P, dev, means3D=means3D, opacities=opacities, scales=scales, rotations=rotations, cov3D_precomp=None,
+                         raw=raw)
+    shapes = _geometric_shapes(P, v)
+    del shapes["cov3D"]
+    out, mask = _grad_targets(who, dev, shapes, accumulate_into)
     out["gauss_normal"] = torch.empty((P, 3), dtype=torch.float32, device=dev)
-    v, keep = _normals_view(rs, P, means3D, opacities, scales, rotations, raw, dev)
     a = _lib_check.NormalsRenderBackwardArgs(
-        view=v, geom_buffer=geomBuffer.data_ptr(), binning_buffer=binningBuffer.data_ptr(), image_buffer=imageBuffer.data_ptr(),
-        binning_capacity=int(binning_capacity), dL_dnormals=dL.data_ptr(), normals=nrm.data_ptr(), gauss_normals=gn.data_ptr(),
-        radii=rad.data_ptr(), dL_dgauss_normal=out["gauss_normal"].data_ptr(), dL_dmean2D=out["means2D"].data_ptr(),
-        dL_dopacity=out["opacity"].data_ptr(), dL_dmean3D=out["means3D"].data_ptr(), dL_dscale=out["scales"].data_ptr(),
-        dL_drot=out["rotations"].data_ptr(), accumulate_mask=mask, stream=torch.cuda.current_stream(dev).cuda_stream)
-    with _lib_check.on_device(dev):
-        rc = _lib_check.lib().lr_render_normals_backward(a)
-    if rc < 0:
-        _lib_check.raise_for(rc, "render_normals_backward")
+        view=v, dL_dnormals=dL.data_ptr(), normals=nrm.data_ptr(), gauss_normals=gn.data_ptr(), radii=rad.data_ptr(),
+        dL_dgauss_normal=out["gauss_normal"].data_ptr(), **_grad_fields(out, mask),
+        **_forward_state(geomBuffer, binningBuffer, imageBuffer, binning_capacity, dev))
+    _call("lr_render_normals_backward", a, dev, who)
     del keep
     return out
 
@@ -439,59 +429,27 @@ def render_features_backward(geomBuffer, binningBuffer, imageBuffer, dL_dout_fea
     accumulate_into: {"means2D", "opacity", "means3D", "scales", "rotations", "cov3D", "features": tensor or None}, a given tensor
     is ADDED to in place, a missing one is a new tensor written in full.  Returns the dict of the seven (None for the
     representation not in use)."""
+    who = "render_features_backward"
     dev = imageBuffer.device
     P = int(means3D.shape[0])
-    C = require_features("render_features_backward", features, P)
+    C = require_features(who, features, P)
     H, W = int(rs.image_height), int(rs.image_width)
-    present = lambda t: t is not None and t.numel() != 0
-    cont = lambda t: _dense(t, dev)
-    keep = [cont(dL_dout_features), cont(out_features), cont(features), cont(rs.viewmatrix), cont(rs.projmatrix), cont(rs.campos),
-            cont(means3D), cont(opacities) if opacities is not None else None]
-    dL, val, f, view, proj, campos, m3, op = keep
-    if raw and op is None:
-        raise RuntimeError("render_features_backward: raw mode needs the stored opacities")
-    rad = radii.contiguous()
-    _sized("render_features_backward", viewmatrix=(view, 16), projmatrix=(proj, 16), campos=(campos, 3), means3D=(m3, 3 * P),
-           opacities=(op, P), radii=(rad, P), scales=(scales if present(scales) else None, 3 * P),
-           rotations=(rotations if present(rotations) else None, 4 * P),
-           cov3D_precomp=(cov3D_precomp if present(cov3D_precomp) else None, 6 * P),
-           dL_dout_features=(dL, C * H * W), out_features=(val, C * H * W))
-    _int32_on("render_features_backward", dev, radii=rad)
-    sc = cont(scales) if present(scales) else None
-    rot = cont(rotations) if present(rotations) else None
-    cov = cont(cov3D_precomp) if present(cov3D_precomp) else None
-    shapes = {"means2D": (P, 3), "opacity": (P, 1), "means3D": (P, 3), "scales": (P, 3) if sc is not None else None,
-              "rotations": (P, 4) if rot is not None else None, "cov3D": (P, 6) if cov is not None else None, "features": (P, C)}
-    bits = {"means2D": 0, "opacity": 2, "means3D": 4, "cov3D": 5, "scales": 7, "rotations": 8, "features": 9}
-    out, mask = {}, 0
-    for name, shape in shapes.items():
-        t = (accumulate_into or {}).get(name)
-        if shape is None:
-            out[name] = None
-        elif t is not None:
-            if not t.is_contiguous() or t.dtype != torch.float32 or t.numel() != int(torch.Size(shape).numel()) or t.device != dev \
-                    or t.data_ptr() % 16 != 0:
-                raise RuntimeError(f"render_features_backward: accumulate_into[{name!r}] must be a contiguous, 16-byte aligned "
-                                   f"float32 tensor of {shape} on {dev}")
-            out[name] = t
-            mask |= 1 << bits[name]
-        else:
-            out[name] = torch.empty(shape, dtype=torch.float32, device=dev)
+    dL, val, f = _dense(dL_dout_features, dev), _dense(out_features, dev), _dense(features, dev)
+    if raw and opacities is None:
+        raise RuntimeError(f"{who}: raw mode needs the stored opacities")
+    _sized(who, dL_dout_features=(dL, C * H * W), out_features=(val, C * H * W))
+    rad = _radii_on(who, dev, radii, P)
+    v, keep = _side_view(rs, P, dev, means3D=means3D, opacities=opacities, scales=scales, rotations=rotations,
+                         cov3D_precomp=cov3D_precomp, raw=raw)
+    out, mask = _grad_targets(who, dev, dict(_geometric_shapes(P, v), features=(P, C)), accumulate_into)
     bound = int(binning_capacity) if int(binning_capacity) > 0 else max(int(slots), 1)
     ws_bytes = int(_lib_check.lib().lr_features_workspace_bytes(bound, C))
     ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
-    ptr = lambda t: t.data_ptr() if t is not None else None
-    v = _lib_check.View(P=P, D=0, M=1, raw=1 if raw else 0, width=W, height=H, means3D=m3.data_ptr(), opacities=ptr(op),
-                        scales=ptr(sc), scale_modifier=float(rs.scale_modifier), rotations=ptr(rot), cov3D_precomp=ptr(cov),
-                        viewmatrix=view.data_ptr(), projmatrix=proj.data_ptr(), campos=campos.data_ptr(),
-                        tan_fovx=float(rs.tanfovx), tan_fovy=float(rs.tanfovy))
     a = _lib_check.FeatureRenderBackwardArgs(
         view=v, features=f.data_ptr(), channels=C, dL_dout_features=dL.data_ptr(), out_features=val.data_ptr(), radii=rad.data_ptr(),
-        dL_dfeatures=out["features"].data_ptr(), workspace=ws.data_ptr(), workspace_bytes=ws_bytes,
-        dL_dmean2D=ptr(out["means2D"]), dL_dopacity=ptr(out["opacity"]), dL_dmean3D=ptr(out["means3D"]), dL_dcov3D=ptr(out["cov3D"]),
-        dL_dscale=ptr(out["scales"]), dL_drot=ptr(out["rotations"]), accumulate_mask=mask,
+        dL_dfeatures=out["features"].data_ptr(), workspace=ws.data_ptr(), workspace_bytes=ws_bytes, **_grad_fields(out, mask),
         **_forward_state(geomBuffer, binningBuffer, imageBuffer, binning_capacity, dev))
-    _call("lr_render_features_backward", a, dev, "render_features_backward")
+    _call("lr_render_features_backward", a, dev, who)
     del keep, ws
     return out
 
@@ -501,7 +459,6 @@ def render_geometry(geomBuffer, binningBuffer, imageBuffer, radii, rs, *, means3
     """(distortion (1, H, W), moments (H, W, 4), normals (3, H, W), gauss_normals (P, 4)): render_distortion and render_normals in
     ONE tile walk (lr_render_geometry, on the current stream) -- the pass the multi-view step runs.  Arguments as render_normals,
     with render_distortion's distortion_map.  ValueError with cov3D_precomp, before any launch.  No autograd."""
-    import torch
     require_scale_rot("render_geometry", scales, rotations, cov3D_precomp)
     dev = imageBuffer.device
     P = int(means3D.shape[0])
@@ -511,20 +468,12 @@ def render_geometry(geomBuffer, binningBuffer, imageBuffer, radii, rs, *, means3
     mom = torch.empty((H, W, 4), dtype=torch.float32, device=dev)
     normals = torch.empty((3, H, W), dtype=torch.float32, device=dev)
     gauss_normals = torch.empty((P, 4), dtype=torch.float32, device=dev)
-    v, keep = _normals_view(rs, P, means3D, None, scales, rotations, raw, dev)
-    rad = radii.contiguous()
-    _sized("render_geometry", radii=(rad, P))
-    _int32_on("render_geometry", dev, radii=rad)
-    _buffers_on(dev, geomBuffer, binningBuffer, imageBuffer)
-    a = _lib_check.GeometryArgs(view=v, radii=rad.data_ptr(), geom_buffer=geomBuffer.data_ptr(),
-                                binning_buffer=binningBuffer.data_ptr(), image_buffer=imageBuffer.data_ptr(),
-                                binning_capacity=int(binning_capacity), map_c0=c0, map_c1=c1, map_c2=c2,
-                                out_distortion=dist.data_ptr(), out_moments=mom.data_ptr(), out_normals=normals.data_ptr(),
-                                out_gauss_normals=gauss_normals.data_ptr(), stream=torch.cuda.current_stream(dev).cuda_stream)
-    with _lib_check.on_device(dev):
-        rc = _lib_check.lib().lr_render_geometry(a)
-    if rc < 0:
-        _lib_check.raise_for(rc, "render_geometry")
+    v, keep = _side_view(rs, P, dev, means3D=means3D, opacities=None, scales=scales, rotations=rotations, cov3D_precomp=None, raw=raw)
+    rad = _radii_on("render_geometry", dev, radii, P)
+    a = _lib_check.GeometryArgs(view=v, radii=rad.data_ptr(), map_c0=c0, map_c1=c1, map_c2=c2, out_distortion=dist.data_ptr(),
+                                out_moments=mom.data_ptr(), out_normals=normals.data_ptr(), out_gauss_normals=gauss_normals.data_ptr(),
+                                **_forward_state(geomBuffer, binningBuffer, imageBuffer, binning_capacity, dev))
+    _call("lr_render_geometry", a, dev, "render_geometry")
     del keep
     return dist, mom, normals, gauss_normals
 
@@ -536,52 +485,33 @@ def geometry_backward(geomBuffer, binningBuffer, imageBuffer, dL_ddistortion, di
     current stream, behind the colour backward of the same forward).  dL_ddistortion: (1, H, W), a Python number (the upstream of
     every pixel) or None; dL_dnormals: (3, H, W) or None; an absent upstream contributes nothing.  The other arguments and the
     returned dict are render_normals_backward's."""
-    import torch
-    require_scale_rot("geometry_backward", scales, rotations, cov3D_precomp)
+    who = "geometry_backward"
+    require_scale_rot(who, scales, rotations, cov3D_precomp)
     dev = imageBuffer.device
     P = int(means3D.shape[0])
     H, W = int(rs.image_height), int(rs.image_width)
     c0, c1, c2 = distortion_map_coefficients(distortion_map)
-    cont = lambda t: _dense(t, dev)
     scalar = float(dL_ddistortion) if isinstance(dL_ddistortion, (int, float)) else 0.0
-    dD = cont(dL_ddistortion) if isinstance(dL_ddistortion, torch.Tensor) else None
-    dN = cont(dL_dnormals) if dL_dnormals is not None else None
-    dist, mom, nrm, gn, rad = cont(distortion), cont(moments), cont(normals), cont(gauss_normals), radii.contiguous()
+    dD = _dense(dL_ddistortion, dev) if isinstance(dL_ddistortion, torch.Tensor) else None
+    dN = _dense(dL_dnormals, dev) if dL_dnormals is not None else None
+    dist, mom, nrm, gn = _dense(distortion, dev), _dense(moments, dev), _dense(normals, dev), _dense(gauss_normals, dev)
     if raw and opacities is None:
-        raise RuntimeError("geometry_backward: raw mode needs the stored opacities")
-    if (dD is not None and dD.numel() != H * W) or dist.numel() != H * W or mom.numel() != 4 * H * W:
-        raise RuntimeError("geometry_backward: dL_ddistortion, distortion and moments must be (1, H, W), (1, H, W), (H, W, 4)")
-    if (dN is not None and dN.numel() != 3 * H * W) or nrm.numel() != 3 * H * W or gn.numel() != 4 * P:
-        raise RuntimeError("geometry_backward: dL_dnormals, normals and gauss_normals must be (3, H, W), (3, H, W), (P, 4)")
-    _sized("geometry_backward", radii=(rad, P))
-    _int32_on("geometry_backward", dev, radii=rad)
-    _buffers_on(dev, geomBuffer, binningBuffer, imageBuffer)
-    shapes = {"means2D": (P, 3), "opacity": (P, 1), "means3D": (P, 3), "scales": (P, 3), "rotations": (P, 4)}
-    bits = {"means2D": 0, "opacity": 2, "means3D": 4, "scales": 7, "rotations": 8}
-    out, mask = {}, 0
-    for name, shape in shapes.items():
-        t = (accumulate_into or {}).get(name)
-        if t is not None:
-            if not t.is_contiguous() or t.dtype != torch.float32 or t.numel() != int(torch.Size(shape).numel()) or t.device != dev:
-                raise RuntimeError(f"geometry_backward: accumulate_into[{name!r}] must be a contiguous float32 tensor of {shape}")
-            out[name] = t
-            mask |= 1 << bits[name]
-        else:
-            out[name] = torch.empty(shape, dtype=torch.float32, device=dev)
+        raise RuntimeError(f"{who}: raw mode needs the stored opacities")
+    _sized(who, dL_ddistortion=(dD, H * W), distortion=(dist, H * W), moments=(mom, 4 * H * W), dL_dnormals=(dN, 3 * H * W),
+           normals=(nrm, 3 * H * W), gauss_normals=(gn, 4 * P))
+    rad = _radii_on(who, dev, radii, P)
+    v, keep = _side_view(rs, P, dev, means3D=means3D, opacities=opacities, scales=scales, rotations=rotations, cov3D_precomp=None,
+                         raw=raw)
+    shapes = _geometric_shapes(P, v)
+    del shapes["cov3D"]
+    out, mask = _grad_targets(who, dev, shapes, accumulate_into)
     out["gauss_normal"] = torch.empty((P, 3), dtype=torch.float32, device=dev)
-    v, keep = _normals_view(rs, P, means3D, opacities, scales, rotations, raw, dev)
     a = _lib_check.GeometryBackwardArgs(
-        view=v, geom_buffer=geomBuffer.data_ptr(), binning_buffer=binningBuffer.data_ptr(), image_buffer=imageBuffer.data_ptr(),
-        binning_capacity=int(binning_capacity), dL_ddistortion=dD.data_ptr() if dD is not None else None,
-        dL_ddistortion_scalar=scalar, moments=mom.data_ptr(), distortion=dist.data_ptr(), map_c0=c0, map_c1=c1, map_c2=c2,
-        dL_dnormals=dN.data_ptr() if dN is not None else None, normals=nrm.data_ptr(), gauss_normals=gn.data_ptr(),
-        radii=rad.data_ptr(), dL_dgauss_normal=out["gauss_normal"].data_ptr(), dL_dmean2D=out["means2D"].data_ptr(),
-        dL_dopacity=out["opacity"].data_ptr(), dL_dmean3D=out["means3D"].data_ptr(), dL_dscale=out["scales"].data_ptr(),
-        dL_drot=out["rotations"].data_ptr(), accumulate_mask=mask, stream=torch.cuda.current_stream(dev).cuda_stream)
-    with _lib_check.on_device(dev):
-        rc = _lib_check.lib().lr_geometry_backward(a)
-    if rc < 0:
-        _lib_check.raise_for(rc, "geometry_backward")
+        view=v, dL_ddistortion=_ptr(dD), dL_ddistortion_scalar=scalar, moments=mom.data_ptr(), distortion=dist.data_ptr(),
+        map_c0=c0, map_c1=c1, map_c2=c2, dL_dnormals=_ptr(dN), normals=nrm.data_ptr(), gauss_normals=gn.data_ptr(),
+        radii=rad.data_ptr(), dL_dgauss_normal=out["gauss_normal"].data_ptr(), **_grad_fields(out, mask),
+        **_forward_state(geomBuffer, binningBuffer, imageBuffer, binning_capacity, dev))
+    _call("lr_geometry_backward", a, dev, who)
     del keep
     return out
 

@@ -139,79 +139,74 @@ class BackwardArgs(ctypes.Structure):
         super().__init__(struct_bytes=ctypes.sizeof(BackwardArgs), **fields)
 
 
-class MedianArgs(ctypes.Structure):
-    """lr_median_args, field for field (tests/test_median_cpu.py compares the offsets with the host compiler's)."""
-    _vp, _ci = ctypes.c_void_p, ctypes.c_int
-    _fields_ = [("struct_bytes", ctypes.c_size_t), ("geom_buffer", _vp), ("binning_buffer", _vp), ("image_buffer", _vp),
-                ("P", _ci), ("width", _ci), ("height", _ci), ("binning_capacity", ctypes.c_longlong),
-                ("out_median_depth", _vp), ("out_ids", _vp), ("stream", _vp)]
+# The passes behind a finished forward (include/lucid_raster.h): their argument structs are built from two runs of members every
+# one of them repeats.  tests/test_{median,distort,render_normals,features,geom_views}_cpu.py compare each struct's offsets with
+# the host compiler's.
+_vp, _ci, _cf = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
+_BUFFERS = [("geom_buffer", _vp), ("binning_buffer", _vp), ("image_buffer", _vp)]
+_CAPACITY = [("binning_capacity", ctypes.c_longlong)]
+# the state a forward left: its three buffers and the capacity it ran under -- with P, width, height between them where the struct
+# has no lr_view of its own
+FORWARD_STATE = _BUFFERS + _CAPACITY
+FORWARD_STATE_PWH = _BUFFERS + [("P", _ci), ("width", _ci), ("height", _ci)] + _CAPACITY
+# the gradient outputs of a backward, as lr_backward_args names them, and the end of the struct
+GRAD_OUTPUTS = [("dL_dmean2D", _vp), ("dL_dconic", _vp), ("dL_dopacity", _vp), ("dL_dcolor", _vp), ("dL_dmean3D", _vp),
+                ("dL_dcov3D", _vp), ("dL_dsh", _vp), ("dL_dsh_rest", _vp), ("dL_dscale", _vp), ("dL_drot", _vp),
+                ("accumulate_mask", ctypes.c_uint), ("stream", _vp)]
+_MAP = [("map_c0", _cf), ("map_c1", _cf), ("map_c2", _cf)]
 
+
+def _struct_bytes_first(cls):
+    """Class decorator of the ten: struct_bytes, the first member of each, is filled in with the class's own size."""
     def __init__(self, **fields):
-        super().__init__(struct_bytes=ctypes.sizeof(MedianArgs), **fields)
+        ctypes.Structure.__init__(self, struct_bytes=ctypes.sizeof(cls), **fields)
+    cls.__init__ = __init__
+    return cls
 
 
+_SIZE, _VIEW, _STREAM = [("struct_bytes", ctypes.c_size_t)], [("view", View)], [("stream", _vp)]
+
+
+@_struct_bytes_first
+class MedianArgs(ctypes.Structure):
+    """lr_median_args, field for field."""
+    _fields_ = _SIZE + FORWARD_STATE_PWH + [("out_median_depth", _vp), ("out_ids", _vp)] + _STREAM
+
+
+@_struct_bytes_first
 class MedianBackwardArgs(ctypes.Structure):
     """lr_median_backward_args, field for field."""
-    _vp, _ci = ctypes.c_void_p, ctypes.c_int
-    _fields_ = [("struct_bytes", ctypes.c_size_t), ("geom_buffer", _vp), ("binning_buffer", _vp), ("image_buffer", _vp),
-                ("P", _ci), ("width", _ci), ("height", _ci), ("binning_capacity", ctypes.c_longlong),
-                ("radii", _vp), ("ids", _vp), ("dL_dmedian", _vp), ("viewmatrix", _vp), ("dL_dmean3D", _vp),
-                ("accumulate", _ci), ("stream", _vp)]
-
-    def __init__(self, **fields):
-        super().__init__(struct_bytes=ctypes.sizeof(MedianBackwardArgs), **fields)
+    _fields_ = (_SIZE + FORWARD_STATE_PWH +
+                [("radii", _vp), ("ids", _vp), ("dL_dmedian", _vp), ("viewmatrix", _vp), ("dL_dmean3D", _vp), ("accumulate", _ci)] +
+                _STREAM)
 
 
+@_struct_bytes_first
 class DistortionArgs(ctypes.Structure):
-    """lr_distortion_args, field for field (tests/test_distort_cpu.py compares the offsets with the host compiler's)."""
-    _vp, _ci, _cf = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
-    _fields_ = [("struct_bytes", ctypes.c_size_t), ("geom_buffer", _vp), ("binning_buffer", _vp), ("image_buffer", _vp),
-                ("P", _ci), ("width", _ci), ("height", _ci), ("binning_capacity", ctypes.c_longlong),
-                ("map_c0", _cf), ("map_c1", _cf), ("map_c2", _cf),
-                ("out_distortion", _vp), ("out_moments", _vp), ("stream", _vp)]
-
-    def __init__(self, **fields):
-        super().__init__(struct_bytes=ctypes.sizeof(DistortionArgs), **fields)
+    """lr_distortion_args, field for field."""
+    _fields_ = _SIZE + FORWARD_STATE_PWH + _MAP + [("out_distortion", _vp), ("out_moments", _vp)] + _STREAM
 
 
+@_struct_bytes_first
 class DistortionBackwardArgs(ctypes.Structure):
     """lr_distortion_backward_args, field for field."""
-    _vp, _ci, _cf = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
-    _fields_ = [("struct_bytes", ctypes.c_size_t), ("view", View),
-                ("geom_buffer", _vp), ("binning_buffer", _vp), ("image_buffer", _vp), ("binning_capacity", ctypes.c_longlong),
-                ("dL_ddistortion", _vp), ("moments", _vp), ("distortion", _vp),
-                ("map_c0", _cf), ("map_c1", _cf), ("map_c2", _cf),
-                ("dL_dmean2D", _vp), ("dL_dconic", _vp), ("dL_dopacity", _vp), ("dL_dcolor", _vp), ("dL_dmean3D", _vp),
-                ("dL_dcov3D", _vp), ("dL_dsh", _vp), ("dL_dsh_rest", _vp), ("dL_dscale", _vp), ("dL_drot", _vp),
-                ("accumulate_mask", ctypes.c_uint), ("stream", _vp)]
-
-    def __init__(self, **fields):
-        super().__init__(struct_bytes=ctypes.sizeof(DistortionBackwardArgs), **fields)
+    _fields_ = (_SIZE + _VIEW + FORWARD_STATE + [("dL_ddistortion", _vp), ("moments", _vp), ("distortion", _vp)] + _MAP +
+                GRAD_OUTPUTS)
 
 
+@_struct_bytes_first
 class NormalsRenderArgs(ctypes.Structure):
-    """lr_normals_render_args, field for field (tests/test_render_normals_cpu.py compares the offsets with the host compiler's)."""
-    _vp = ctypes.c_void_p
-    _fields_ = [("struct_bytes", ctypes.c_size_t), ("view", View), ("radii", _vp),
-                ("geom_buffer", _vp), ("binning_buffer", _vp), ("image_buffer", _vp), ("binning_capacity", ctypes.c_longlong),
-                ("out_normals", _vp), ("out_gauss_normals", _vp), ("stream", _vp)]
-
-    def __init__(self, **fields):
-        super().__init__(struct_bytes=ctypes.sizeof(NormalsRenderArgs), **fields)
+    """lr_normals_render_args, field for field."""
+    _fields_ = _SIZE + _VIEW + [("radii", _vp)] + FORWARD_STATE + [("out_normals", _vp), ("out_gauss_normals", _vp)] + _STREAM
 
 
+_NORMALS_UPSTREAM = [("dL_dnormals", _vp), ("normals", _vp), ("gauss_normals", _vp), ("radii", _vp), ("dL_dgauss_normal", _vp)]
+
+
+@_struct_bytes_first
 class NormalsRenderBackwardArgs(ctypes.Structure):
     """lr_normals_render_backward_args, field for field."""
-    _vp = ctypes.c_void_p
-    _fields_ = [("struct_bytes", ctypes.c_size_t), ("view", View),
-                ("geom_buffer", _vp), ("binning_buffer", _vp), ("image_buffer", _vp), ("binning_capacity", ctypes.c_longlong),
-                ("dL_dnormals", _vp), ("normals", _vp), ("gauss_normals", _vp), ("radii", _vp), ("dL_dgauss_normal", _vp),
-                ("dL_dmean2D", _vp), ("dL_dconic", _vp), ("dL_dopacity", _vp), ("dL_dcolor", _vp), ("dL_dmean3D", _vp),
-                ("dL_dcov3D", _vp), ("dL_dsh", _vp), ("dL_dsh_rest", _vp), ("dL_dscale", _vp), ("dL_drot", _vp),
-                ("accumulate_mask", ctypes.c_uint), ("stream", _vp)]
-
-    def __init__(self, **fields):
-        super().__init__(struct_bytes=ctypes.sizeof(NormalsRenderBackwardArgs), **fields)
+    _fields_ = _SIZE + _VIEW + FORWARD_STATE + _NORMALS_UPSTREAM + GRAD_OUTPUTS
 
 
 LR_FEATURE_MAX_CHANNELS = 256       # include/lucid_raster.h
@@ -219,58 +214,34 @@ LR_ACC_FEATURES = 1 << 9            # accumulate_mask of lr_render_features_back
 LR_FEATURE_CHUNK = 16               # channels per tile walk (csrc/render_features.hip FTR_K): C channels cost ceil(C / 16) walks each way
 
 
+@_struct_bytes_first
 class FeatureRenderArgs(ctypes.Structure):
-    """lr_feature_render_args, field for field (tests/test_features_cpu.py compares the offsets with the host compiler's)."""
-    _vp = ctypes.c_void_p
-    _fields_ = [("struct_bytes", ctypes.c_size_t), ("view", View), ("radii", _vp),
-                ("geom_buffer", _vp), ("binning_buffer", _vp), ("image_buffer", _vp), ("binning_capacity", ctypes.c_longlong),
-                ("features", _vp), ("channels", ctypes.c_int), ("out_features", _vp), ("stream", _vp)]
-
-    def __init__(self, **fields):
-        super().__init__(struct_bytes=ctypes.sizeof(FeatureRenderArgs), **fields)
+    """lr_feature_render_args, field for field."""
+    _fields_ = (_SIZE + _VIEW + [("radii", _vp)] + FORWARD_STATE +
+                [("features", _vp), ("channels", _ci), ("out_features", _vp)] + _STREAM)
 
 
+@_struct_bytes_first
 class FeatureRenderBackwardArgs(ctypes.Structure):
     """lr_feature_render_backward_args, field for field."""
-    _vp = ctypes.c_void_p
-    _fields_ = [("struct_bytes", ctypes.c_size_t), ("view", View),
-                ("geom_buffer", _vp), ("binning_buffer", _vp), ("image_buffer", _vp), ("binning_capacity", ctypes.c_longlong),
-                ("features", _vp), ("channels", ctypes.c_int), ("dL_dout_features", _vp), ("out_features", _vp), ("radii", _vp),
-                ("dL_dfeatures", _vp), ("workspace", _vp), ("workspace_bytes", ctypes.c_size_t),
-                ("dL_dmean2D", _vp), ("dL_dconic", _vp), ("dL_dopacity", _vp), ("dL_dcolor", _vp), ("dL_dmean3D", _vp),
-                ("dL_dcov3D", _vp), ("dL_dsh", _vp), ("dL_dsh_rest", _vp), ("dL_dscale", _vp), ("dL_drot", _vp),
-                ("accumulate_mask", ctypes.c_uint), ("stream", _vp)]
-
-    def __init__(self, **fields):
-        super().__init__(struct_bytes=ctypes.sizeof(FeatureRenderBackwardArgs), **fields)
+    _fields_ = (_SIZE + _VIEW + FORWARD_STATE +
+                [("features", _vp), ("channels", _ci), ("dL_dout_features", _vp), ("out_features", _vp), ("radii", _vp),
+                 ("dL_dfeatures", _vp), ("workspace", _vp), ("workspace_bytes", ctypes.c_size_t)] + GRAD_OUTPUTS)
 
 
+@_struct_bytes_first
 class GeometryArgs(ctypes.Structure):
-    """lr_geometry_args, field for field (tests/test_geom_views_cpu.py compares the offsets with the host compiler's)."""
-    _vp, _cf = ctypes.c_void_p, ctypes.c_float
-    _fields_ = [("struct_bytes", ctypes.c_size_t), ("view", View), ("radii", _vp),
-                ("geom_buffer", _vp), ("binning_buffer", _vp), ("image_buffer", _vp), ("binning_capacity", ctypes.c_longlong),
-                ("map_c0", _cf), ("map_c1", _cf), ("map_c2", _cf),
-                ("out_distortion", _vp), ("out_moments", _vp), ("out_normals", _vp), ("out_gauss_normals", _vp), ("stream", _vp)]
-
-    def __init__(self, **fields):
-        super().__init__(struct_bytes=ctypes.sizeof(GeometryArgs), **fields)
+    """lr_geometry_args, field for field."""
+    _fields_ = (_SIZE + _VIEW + [("radii", _vp)] + FORWARD_STATE + _MAP +
+                [("out_distortion", _vp), ("out_moments", _vp), ("out_normals", _vp), ("out_gauss_normals", _vp)] + _STREAM)
 
 
+@_struct_bytes_first
 class GeometryBackwardArgs(ctypes.Structure):
     """lr_geometry_backward_args, field for field."""
-    _vp, _cf = ctypes.c_void_p, ctypes.c_float
-    _fields_ = [("struct_bytes", ctypes.c_size_t), ("view", View),
-                ("geom_buffer", _vp), ("binning_buffer", _vp), ("image_buffer", _vp), ("binning_capacity", ctypes.c_longlong),
-                ("dL_ddistortion", _vp), ("dL_ddistortion_scalar", _cf), ("moments", _vp), ("distortion", _vp),
-                ("map_c0", _cf), ("map_c1", _cf), ("map_c2", _cf),
-                ("dL_dnormals", _vp), ("normals", _vp), ("gauss_normals", _vp), ("radii", _vp), ("dL_dgauss_normal", _vp),
-                ("dL_dmean2D", _vp), ("dL_dconic", _vp), ("dL_dopacity", _vp), ("dL_dcolor", _vp), ("dL_dmean3D", _vp),
-                ("dL_dcov3D", _vp), ("dL_dsh", _vp), ("dL_dsh_rest", _vp), ("dL_dscale", _vp), ("dL_drot", _vp),
-                ("accumulate_mask", ctypes.c_uint), ("stream", _vp)]
-
-    def __init__(self, **fields):
-        super().__init__(struct_bytes=ctypes.sizeof(GeometryBackwardArgs), **fields)
+    _fields_ = (_SIZE + _VIEW + FORWARD_STATE +
+                [("dL_ddistortion", _vp), ("dL_ddistortion_scalar", _cf), ("moments", _vp), ("distortion", _vp)] + _MAP +
+                _NORMALS_UPSTREAM + GRAD_OUTPUTS)
 
 
 def distortion_map_coefficients(distortion_map):

@@ -174,55 +174,51 @@ def _median_backward(ctx, grad_median, target, radii, geom, binning, img):
                        binning_capacity=ctx.binning_capacity, accumulate_into=target)
 
 
-def _distortion_backward(ctx, grad_distortion, returned, fused, geom, binning, img, **inputs):
-    """The distortion's term of every geometric gradient (lr_distortion_backward), added behind the view's backward on the same
-    stream: per tensor into what that backward returned, or, where it accumulated into the leaf's .grad in place (returned None),
-    into that .grad -- the same additions in the same order either way.  returned / fused: {name: tensor or None} under the names of
-    _C.distortion_backward.  Returns `returned` (an input neither of them covers gets the term alone)."""
-    fused = fused or {}
-    targets = {k: (t if t is not None else fused.get(k)) for k, t in returned.items()}
-    value, moments, distortion_map = ctx.distortion
-    out = _C.distortion_backward(geom, binning, img, grad_distortion, value, moments, ctx.raster_settings,
-                                 distortion_map=distortion_map, binning_capacity=ctx.binning_capacity, accumulate_into=targets,
-                                 **inputs)
-    return {k: (t if (t is not None or fused.get(k) is not None) else out[k]) for k, t in returned.items()}
-
-
-def _normals_backward(ctx, grad_normals, returned, fused, radii, geom, binning, img, plus_zero=True, **inputs):
-    """The rendered normal map's term of every geometric gradient (lr_render_normals_backward), added as _distortion_backward adds
-    the distortion's, behind it.  cov3D never takes part: there is no normal without scales + rotations.
+def _side_backward(call, names, returned, fused, plus_zero):
+    """The term of one pass behind the forward in every geometric gradient, added behind the view's backward on the same stream: per
+    tensor into what that backward returned, or, where it accumulated into the leaf's .grad in place (returned None), into that
+    .grad -- the same additions in the same order either way.  returned / fused: {name: tensor or None} under the names of
+    _C.distortion_backward; names: those the pass has a gradient for; call(targets): its _C.*_backward with accumulate_into.
     plus_zero: the tensors the view's backward RETURNED (written, then added to) end with +0 for their zero entries, as the same
     sums have when they are accumulated into a zeroed .grad -- a Gaussian the view visited and no pixel blended is written as
     -0 by the per-Gaussian kernel, and -0 + -0 stays -0 where +0 + -0 + -0 is +0: with it the fused and the unfused route give
-    the same bits.  One multi-tensor launch; not for the armed optimizer step, whose rows are read through the view's mask."""
-    fused = fused or {}
-    names = ("means2D", "opacity", "means3D", "scales", "rotations")
+    the same bits.  One multi-tensor launch; not for the armed optimizer step, whose rows are read through the view's mask.
+    Returns (`returned` with the term: an input neither of the two covers gets the term alone, the call's dict)."""
     targets = {k: (returned[k] if returned[k] is not None else fused.get(k)) for k in names}
-    value, gauss_normals = ctx.normals
-    out = _C.render_normals_backward(geom, binning, img, grad_normals, value, gauss_normals, radii, ctx.raster_settings,
-                                     binning_capacity=ctx.binning_capacity, accumulate_into=targets, **inputs)
+    out = call(targets)
     written = [returned[k] for k in names if returned[k] is not None]
     if plus_zero and written:
         torch._foreach_add_(written, 0.0)
-    return dict(returned, **{k: (returned[k] if (returned[k] is not None or fused.get(k) is not None) else out[k]) for k in names})
+    return dict(returned, **{k: (returned[k] if (returned[k] is not None or fused.get(k) is not None) else out[k]) for k in names}), out
+
+
+def _distortion_backward(ctx, grad_distortion, returned, fused, geom, binning, img, **inputs):
+    """The distortion's term (lr_distortion_backward): the one pass whose term is added without the +0 rule."""
+    value, moments, distortion_map = ctx.distortion
+    call = lambda targets: _C.distortion_backward(geom, binning, img, grad_distortion, value, moments, ctx.raster_settings,
+                                                  distortion_map=distortion_map, binning_capacity=ctx.binning_capacity,
+                                                  accumulate_into=targets, **inputs)
+    return _side_backward(call, tuple(returned), returned, fused, False)[0]
+
+
+def _normals_backward(ctx, grad_normals, returned, fused, radii, geom, binning, img, plus_zero=True, **inputs):
+    """The rendered normal map's term (lr_render_normals_backward), behind the distortion's.  cov3D never takes part: there is no
+    normal without scales + rotations."""
+    value, gauss_normals = ctx.normals
+    call = lambda targets: _C.render_normals_backward(geom, binning, img, grad_normals, value, gauss_normals, radii,
+                                                      ctx.raster_settings, binning_capacity=ctx.binning_capacity,
+                                                      accumulate_into=targets, **inputs)
+    return _side_backward(call, ("means2D", "opacity", "means3D", "scales", "rotations"), returned, fused, plus_zero)[0]
 
 
 def _features_backward(ctx, grad_features, returned, fused, radii, geom, binning, img, plus_zero=True, **inputs):
-    """The feature map's term of every geometric gradient and dL/dfeatures (lr_render_features_backward), added as
-    _normals_backward adds the normals', behind it; cov3D takes part.  plus_zero: as _normals_backward.  Returns (`returned` with
-    the term, dL/dfeatures or None where it was accumulated into the leaf's .grad)."""
-    fused = fused or {}
-    names = tuple(returned)
-    targets = {k: (returned[k] if returned[k] is not None else fused.get(k)) for k in names}
-    targets["features"] = fused.get("features")
+    """The feature map's term and dL/dfeatures (lr_render_features_backward), behind the normals'; cov3D takes part.  Returns
+    (`returned` with the term, dL/dfeatures or None where it was accumulated into the leaf's .grad)."""
     value, features = ctx.features
-    out = _C.render_features_backward(geom, binning, img, grad_features, value, features, radii, ctx.raster_settings,
-                                      slots=ctx.num_rendered, binning_capacity=ctx.binning_capacity, accumulate_into=targets,
-                                      **inputs)
-    written = [returned[k] for k in names if returned[k] is not None]
-    if plus_zero and written:
-        torch._foreach_add_(written, 0.0)
-    returned = {k: (returned[k] if (returned[k] is not None or fused.get(k) is not None) else out[k]) for k in names}
+    call = lambda targets: _C.render_features_backward(geom, binning, img, grad_features, value, features, radii, ctx.raster_settings,
+                                                       slots=ctx.num_rendered, binning_capacity=ctx.binning_capacity,
+                                                       accumulate_into=dict(targets, features=fused.get("features")), **inputs)
+    returned, out = _side_backward(call, tuple(returned), returned, fused, plus_zero)
     return returned, (None if fused.get("features") is not None else out["features"])
 
 
