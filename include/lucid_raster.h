@@ -1457,6 +1457,92 @@ int lr_dream_correspond(const lr_dream_args* a);
 int lr_dream_lift(const lr_dream_args* a);
 int lr_scatter_interpolate(const lr_scatter_args* a);
 
+/*
+ * TSDF fusion of depth maps and mesh extraction on the device (csrc/tsdf.hip): what the surface-reconstruction code bases do
+ * with Open3D on the host after rendering depth along a trajectory.  The definitions are OURS; every float32 operation below is
+ * one IEEE operation in the order written (no fma), so a numpy restatement gives the same bits (tests/tsdf_ref.py).
+ *
+ *   Volume.  origin (3 floats), voxel_size s > 0, dims nx, ny, nz >= 2, trunc > 0.  Samples sit at the lattice points
+ *   c = origin + s (i, j, k), each coordinate float32(i) * s + origin (one multiply, then one add).  Three device tensors, x
+ *   fastest: tsdf [nz,ny,nx] float32 (initially 1), weight [nz,ny,nx] float32 (initially 0), color [nz,ny,nx,3] float32
+ *   (initially 0); the linear index of a lattice point is (k ny + j) nx + i.  7 nx ny nz <= 2^31 - 2^12 (an edge id is an int;
+ *   the scan reads whole tiles).
+ *
+ *   Integrate (lr_tsdf_integrate).  n_frames frames: depth [F,H,W] float32, optional color [F,H,W,3] and pixel_weight [F,H,W]
+ *   float32; K [9], R [F][9], T [F][3] HOST float64, world to camera, as for lr_reproject.  For every lattice point the frames
+ *   are applied in index order; for each frame
+ *       project the float32 point as lr_reproject does (float64, the same operations, valid test and rint); skip if not valid;
+ *       d = depth[f, iv, iu]; skip unless d is finite, d > 0 and d <= depth_max;
+ *       w = pixel_weight[f, iv, iu], or 1 without the map; skip unless w is finite and w > 0;
+ *       sdf = d - z with z = float32(q_2); skip if sdf < -trunc;   v = min(1, sdf / trunc);   Wn = W + w;
+ *       D = (D W + v w) / Wn, and each colour channel C = (C W + c w) / Wn;   W = min(Wn, max_weight).
+ *   Without a colour stack the colour tensor is not touched; a voxel no frame reached is not written.  A gather, one writer per
+ *   voxel, no atomics: bit-repeatable, and n frames in one call equal the same frames in n calls bit for bit.
+ *   H, W >= 2 and H W <= 2^31 - 2^12; 1 <= n_frames <= 65535; depth_max > 0 and max_weight > 0 (either may be +inf).
+ *
+ *   Extract (lr_tsdf_extract_count, then lr_tsdf_extract_emit).  A cell is the cube with minimum corner (i, j, k); it is valid
+ *   when all eight corners have weight >= min_weight.  A lattice point is inside iff tsdf < 0 (a stored 0 is outside).  Each
+ *   valid cell is split into the six Kuhn tetrahedra along the diagonal (0,0,0)-(1,1,1): for every permutation (a, b, c) of
+ *   the axes in lexicographic order, v0 = 0, v1 = e_a, v2 = e_a + e_b, v3 = (1,1,1).  Per tetrahedron:
+ *       one vertex l alone on its side, the others o0 < o1 < o2: the triangle (l o0, l o1, l o2);
+ *       inside p < q, outside r < s: the quad pr, ps, qs, qr as (pr, ps, qs) and (pr, qs, qr).
+ *   Winding is combinatorial: a triangle (x, y, z) is emitted as (x, z, y) when, with every vertex at its edge's midpoint, the
+ *   normal of (x, y, z) would point from the outside vertices to the inside ones.  That follows from the permutation's parity
+ *   and the inside mask alone; computed positions are never consulted (a stored 0 gives triangles of zero area).
+ *   Vertices are welded: an edge is (lower lattice point, direction), the directions being (1,0,0) (0,1,0) (0,0,1) (1,1,0)
+ *   (1,0,1) (0,1,1) (1,1,1), its id 7 (linear index of the lower point) + direction; the vertex list holds, in ascending id,
+ *   exactly the edges some emitted triangle uses.  With p the lower point, t = D_p / (D_p - D_q), and each component of the
+ *   position and of the colour is x_p + t (x_q - x_p) (subtract, multiply, add).  Faces are int32 [T,3], ordered by the linear
+ *   index of the cell's minimum corner, then tetrahedron 0..5, then triangle.
+ *   count fills the workspace, writes the two sizes to HOST memory and costs one stream synchronisation; the caller allocates
+ *   out_vertices [V,3], out_colors [V,3] float32 and out_faces [T,3] int32 and passes the sizes back to emit with the SAME
+ *   workspace and an unchanged volume.  A size of 0 needs no pointer.  LR_ERR_OVERFLOW when 3 T does not fit an int32.
+ *   workspace: lr_tsdf_workspace_bytes(a) device bytes (dims read from a->vol; 0 for dims it refuses), 40 per lattice point.
+ *
+ *   Every device pointer must be 16-byte aligned.  struct_bytes is checked before anything else; every check sits in front of
+ *   the first HIP call.  Return 0 or a negative LR_ERR_*.
+ */
+typedef struct lr_tsdf_volume {
+    float origin[3];
+    float voxel_size;
+    int nx, ny, nz;
+    float trunc;
+    float* tsdf;
+    float* weight;
+    float* color;
+} lr_tsdf_volume;
+typedef struct lr_tsdf_integrate_args {
+    size_t struct_bytes;                     /* = sizeof(lr_tsdf_integrate_args); anything else is LR_ERR_INVALID_ARG */
+    lr_tsdf_volume vol;
+    int n_frames, height, width;
+    const float* depth;
+    const float* color;                      /* optional */
+    const float* pixel_weight;               /* optional */
+    const double* K;                         /* host */
+    const double* R;                         /* host */
+    const double* T;                         /* host */
+    float depth_max, max_weight;
+    void* stream;
+} lr_tsdf_integrate_args;
+typedef struct lr_tsdf_extract_args {
+    size_t struct_bytes;                     /* = sizeof(lr_tsdf_extract_args); anything else is LR_ERR_INVALID_ARG */
+    lr_tsdf_volume vol;
+    float min_weight;                        /* count; not NaN */
+    void* workspace;
+    size_t workspace_bytes;
+    long long* out_n_vertices;               /* count: HOST */
+    long long* out_n_faces;                  /* count: HOST */
+    long long n_vertices, n_faces;           /* emit: what count returned */
+    float* out_vertices;                     /* emit */
+    float* out_colors;                       /* emit */
+    int* out_faces;                          /* emit */
+    void* stream;
+} lr_tsdf_extract_args;
+size_t lr_tsdf_workspace_bytes(const lr_tsdf_extract_args* a);
+int lr_tsdf_integrate(const lr_tsdf_integrate_args* a);
+int lr_tsdf_extract_count(const lr_tsdf_extract_args* a);
+int lr_tsdf_extract_emit(const lr_tsdf_extract_args* a);
+
 /* present[P] (1 byte each) = view-space z > 0.2.  Returns 0 or a negative LR_ERR_*. */
 int lr_mark_visible(int P, const float* means3D, const float* viewmatrix, const float* projmatrix,
                     unsigned char* present, void* stream);

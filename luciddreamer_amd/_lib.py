@@ -49,7 +49,8 @@ EXPORTS = ("lr_last_error", "lr_version", "lr_geom_bytes", "lr_img_bytes", "lr_b
            "lr_reproject_workspace_bytes", "lr_reproject", "lr_lift",
            "lr_dream_workspace_bytes", "lr_dream_scale_sums", "lr_dream_correspond", "lr_dream_lift", "lr_scatter_interpolate",
            "lr_normals_workspace_bytes", "lr_depth_normals", "lr_depth_normals_backward", "lr_normal_loss_forward",
-           "lr_normal_loss_backward")
+           "lr_normal_loss_backward",
+           "lr_tsdf_workspace_bytes", "lr_tsdf_integrate", "lr_tsdf_extract_count", "lr_tsdf_extract_emit")
 
 # lr_views_workspace_bytes / lr_views_check `parts`: what a step's workspace slots hold besides a view's scratch
 LR_VIEWS_LOSS, LR_VIEWS_DEPTH_LOSS, LR_VIEWS_MASK_LOSS = 1, 2, 4
@@ -327,6 +328,37 @@ class NormalsArgs(ctypes.Structure):
         super().__init__(struct_bytes=ctypes.sizeof(NormalsArgs), **fields)
 
 
+class TsdfVolumeDesc(ctypes.Structure):
+    """lr_tsdf_volume, field for field: the lattice and its three device tensors."""
+    _vp, _ci, _cf = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
+    _fields_ = [("origin", _cf * 3), ("voxel_size", _cf), ("nx", _ci), ("ny", _ci), ("nz", _ci), ("trunc", _cf),
+                ("tsdf", _vp), ("weight", _vp), ("color", _vp)]
+
+
+class TsdfIntegrateArgs(ctypes.Structure):
+    """lr_tsdf_integrate_args, field for field (tests/test_tsdf_cpu.py compares the offsets with the host compiler's).
+    K, R, T are HOST float64 arrays; color and pixel_weight are optional."""
+    _vp, _ci, _cf = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
+    _fields_ = [("struct_bytes", ctypes.c_size_t), ("vol", TsdfVolumeDesc), ("n_frames", _ci), ("height", _ci), ("width", _ci),
+                ("depth", _vp), ("color", _vp), ("pixel_weight", _vp), ("K", _vp), ("R", _vp), ("T", _vp),
+                ("depth_max", _cf), ("max_weight", _cf), ("stream", _vp)]
+
+    def __init__(self, **fields):
+        super().__init__(struct_bytes=ctypes.sizeof(TsdfIntegrateArgs), **fields)
+
+
+class TsdfExtractArgs(ctypes.Structure):
+    """lr_tsdf_extract_args, field for field.  out_n_vertices / out_n_faces are HOST long long."""
+    _vp, _ll = ctypes.c_void_p, ctypes.c_longlong
+    _fields_ = [("struct_bytes", ctypes.c_size_t), ("vol", TsdfVolumeDesc), ("min_weight", ctypes.c_float),
+                ("workspace", _vp), ("workspace_bytes", ctypes.c_size_t), ("out_n_vertices", _vp), ("out_n_faces", _vp),
+                ("n_vertices", _ll), ("n_faces", _ll), ("out_vertices", _vp), ("out_colors", _vp), ("out_faces", _vp),
+                ("stream", _vp)]
+
+    def __init__(self, **fields):
+        super().__init__(struct_bytes=ctypes.sizeof(TsdfExtractArgs), **fields)
+
+
 LR_SCATTER_TILE = 256             # samples per on-chip tile of lr_scatter_interpolate (include/lucid_raster.h)
 
 
@@ -512,6 +544,13 @@ def lib():
         for fn in (L.lr_depth_normals, L.lr_depth_normals_backward, L.lr_normal_loss_forward, L.lr_normal_loss_backward):
             fn.restype = ci
             fn.argtypes = [ctypes.POINTER(NormalsArgs)]
+        L.lr_tsdf_workspace_bytes.restype = ctypes.c_size_t
+        L.lr_tsdf_workspace_bytes.argtypes = [ctypes.POINTER(TsdfExtractArgs)]
+        L.lr_tsdf_integrate.restype = ci
+        L.lr_tsdf_integrate.argtypes = [ctypes.POINTER(TsdfIntegrateArgs)]
+        for fn in (L.lr_tsdf_extract_count, L.lr_tsdf_extract_emit):
+            fn.restype = ci
+            fn.argtypes = [ctypes.POINTER(TsdfExtractArgs)]
         L.lr_step_begin.restype = ci
         L.lr_step_begin.argtypes = []
         L.lr_step_end.restype = ci

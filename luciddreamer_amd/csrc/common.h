@@ -780,6 +780,41 @@ hipError_t launch_dream_lift(const DreamLaunch& a, hipStream_t s);
 hipError_t launch_scatter_interpolate(long long n_samples, const double* su, const double* sv, const double* sval, int height,
                                       int width, const uint8_t* where, float* out, hipStream_t s);
 
+// TSDF fusion of depth maps and mesh extraction (tsdf.hip).  K, R, T are HOST float64 arrays as for ReprojectLaunch; they travel
+// as kernel arguments, REPROJECT_FRAMES_PER_LAUNCH frames per launch.
+struct TsdfVolume {
+    float origin[3];
+    float voxel_size;
+    int nx, ny, nz;
+    float trunc;
+    float* tsdf;                    // [nz,ny,nx]
+    float* weight;                  // [nz,ny,nx]
+    float* color;                   // [nz,ny,nx,3]
+};
+struct TsdfIntegrateLaunch {
+    TsdfVolume vol;
+    int n_frames, height, width;
+    const float* depth;             // [F,H,W]
+    const float* color;             // [F,H,W,3] or nullptr
+    const float* pixel_weight;      // [F,H,W] or nullptr
+    const double *K, *R, *T;
+    float depth_max, max_weight;
+};
+struct TsdfExtractLaunch {
+    TsdfVolume vol;
+    float min_weight;
+    void* workspace;
+    long long n_vertices, n_faces;  // emit: the rows of the outputs
+    float* out_vertices;            // [V,3]
+    float* out_colors;              // [V,3]
+    int* out_faces;                 // [T,3]
+};
+size_t tsdf_workspace_bytes(int nx, int ny, int nz);
+hipError_t launch_tsdf_integrate(const TsdfIntegrateLaunch& a, hipStream_t s);
+// counts[0] = vertices, counts[1] = faces (host); waits for the stream
+hipError_t launch_tsdf_extract_count(const TsdfExtractLaunch& a, uint32_t* counts, hipStream_t s);
+hipError_t launch_tsdf_extract_emit(const TsdfExtractLaunch& a, hipStream_t s);
+
 void launch_dist2(int P, const float* points, float* out, char* workspace, hipStream_t s);
 size_t dist2_workspace_bytes(int P);
 void dist2_workspace_layout(int P, size_t offsets[4]);

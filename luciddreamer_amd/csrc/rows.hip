@@ -14,79 +14,11 @@
 //                                instead of seven copies + a Python list of P tuples.
 // Pure byte movement: HBM-bound, coalesced in source order, no atomics.
 #include "common.h"
+#include "mask_scan.h"       // RS_THREADS, RS_TILE, k_mask_count / k_mask_rank (shared with tsdf.hip)
 
 namespace lr {
 
 namespace {
-
-constexpr int RS_THREADS = 256;
-constexpr int RS_ITEMS = 8;
-constexpr int RS_TILE = RS_THREADS * RS_ITEMS;          // mask bytes per workgroup
-
-__device__ __forceinline__ uint32_t rs_block_sum(uint32_t v, uint32_t* s_tmp)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    lds_barrier();
-    if ((threadIdx.x & 63) == 0) s_tmp[threadIdx.x >> 6] = v;
-    lds_barrier();
-    return s_tmp[0] + s_tmp[1] + s_tmp[2] + s_tmp[3];
-}
-
-__global__ void __launch_bounds__(RS_THREADS)
-k_mask_count(int P, const uint8_t* __restrict__ mask, uint32_t* __restrict__ block_counts)
-{
-    __shared__ uint32_t s_tmp[4];
-    const int base = blockIdx.x * RS_TILE;
-    uint32_t c = 0;
-#pragma unroll
-    for (int i = 0; i < RS_ITEMS; i++) {
-        const int k = base + i * RS_THREADS + threadIdx.x;
-        if (k < P && mask[k] != 0) c++;
-    }
-    c = rs_block_sum(c, s_tmp);
-    if (threadIdx.x == 0) block_counts[blockIdx.x] = c;
-}
-
-// rank[i] = number of selected rows before i (valid where mask[i] != 0); total -> *out_count
-__global__ void __launch_bounds__(RS_THREADS)
-k_mask_rank(int P, const uint8_t* __restrict__ mask, const uint32_t* __restrict__ block_counts,
-            uint32_t* __restrict__ rank, int* __restrict__ out_count)
-{
-    __shared__ uint32_t s_tmp[4];
-    __shared__ uint32_t s_wave[4];
-    uint32_t pre = 0, all = 0;
-    for (int i = threadIdx.x; i < (int)gridDim.x; i += RS_THREADS) {
-        const uint32_t v = block_counts[i];
-        if (i < (int)blockIdx.x) pre += v;
-        all += v;
-    }
-    pre = rs_block_sum(pre, s_tmp);
-    if (blockIdx.x == 0) {
-        all = rs_block_sum(all, s_tmp);
-        if (threadIdx.x == 0) *out_count = (int)all;
-    }
-    // blocked arrangement: thread t owns RS_ITEMS consecutive rows
-    const int base = blockIdx.x * RS_TILE + threadIdx.x * RS_ITEMS;
-    uint32_t flag[RS_ITEMS], sum = 0;
-#pragma unroll
-    for (int i = 0; i < RS_ITEMS; i++) { flag[i] = (base + i < P && mask[base + i] != 0) ? 1u : 0u; sum += flag[i]; }
-    uint32_t inc = sum;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t t = __shfl_up(inc, off);
-        if ((int)(threadIdx.x & 63) >= off) inc += t;
-    }
-    const int w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 63) s_wave[w] = inc;
-    lds_barrier();
-    uint32_t wbase = 0;
-    for (int i = 0; i < w; i++) wbase += s_wave[i];
-    uint32_t run = pre + wbase + inc - sum;
-#pragma unroll
-    for (int i = 0; i < RS_ITEMS; i++)
-        if (base + i < P) { rank[base + i] = run; run += flag[i]; }
-}
 
 constexpr int MAX_ROW_TENSORS = 32;
 struct RowTensors {
@@ -210,8 +142,8 @@ int launch_select_rows(int P, const uint8_t* mask, int n_tensors, const void* co
     uint32_t* rank = reinterpret_cast<uint32_t*>(ws);
     uint32_t* block_counts = reinterpret_cast<uint32_t*>(ws + align_up((size_t)(P > 0 ? P : 1) * 4));
     const int nb = (P + RS_TILE - 1) / RS_TILE;
-    hipLaunchKernelGGL(k_mask_count, dim3(nb), dim3(RS_THREADS), 0, s, P, mask, block_counts);
-    hipLaunchKernelGGL(k_mask_rank, dim3(nb), dim3(RS_THREADS), 0, s, P, mask, block_counts, rank, out_count);
+    hipLaunchKernelGGL(k_mask_count<false>, dim3(nb), dim3(RS_THREADS), 0, s, P, mask, block_counts);
+    hipLaunchKernelGGL(k_mask_rank<false>, dim3(nb), dim3(RS_THREADS), 0, s, P, mask, block_counts, rank, out_count);
     if (n_tensors > 0) {
         RowTensors T;
         T.count = n_tensors;
