@@ -853,7 +853,11 @@ typedef struct lr_views_args {
     float* out_losses;
     /* optional per-view outputs, fully written: colour [3,H,W], depth [H,W], alpha A = 1 - T_final [H,W] (lr_render_alpha's
      * values), radii [P]; NULL entries or arrays: not returned (a view whose depth is neither returned nor read by the step --
-     * depth_targets, dL_ddepth -- is blended without the depth channel: same colour, alpha, radii and gradients to the bit) */
+     * depth_targets, dL_ddepth -- is blended without the depth channel: same colour, alpha, radii and gradients to the bit).
+     * out_color: a NULL entry (or array) means that the view's colour is formed only where the step itself reads it -- the losses
+     * of a step with targets, and a view that carries its depth.  A depth-free view of a step driven by fixed upstream gradients
+     * blends no colour at all: the backward starts from T_final and the last contributor, so alpha, radii and gradients are the
+     * same bits; a view whose out_color entry is given gets its image as ever, and mixed steps are legal. */
     float* const* out_color;
     float* const* out_depth;
     float* const* out_alpha;
@@ -1638,6 +1642,12 @@ int lr_get_antialiasing(void);
  * candidate pairs, 2 one wave per tile; backward 0 two waves per tile, 1 four, 2 one; -1 = none yet.  For tests that must
  * know WHICH kernels a configuration ran (e.g. that the headline's step ran the one-wave-per-tile pair). */
 int lr_last_launch_shapes(int* forward_shape, int* backward_shape);
+/* Channel set of the process's last blend forward (the pointer may be NULL): LR_FWD_CHANNEL_COLOR | LR_FWD_CHANNEL_DEPTH for a
+ * forward that blends colour and depth, LR_FWD_CHANNEL_COLOR for a depth-free one, 0 for the colour-free forward of
+ * lr_views_accumulate (see lr_views_args::out_color); -1 = none yet.  For tests that must know that the colour-free kernel ran. */
+#define LR_FWD_CHANNEL_COLOR 1
+#define LR_FWD_CHANNEL_DEPTH 2
+int lr_last_forward_channels(int* channels);
 /* Optional per-stage timing with HIP events recorded on the call's stream (bench.py roofline leg).
  * lr_profile_enable(1) clears and starts recording, (0) stops; returns the number of stages.
  * lr_profile_read waits for the recorded events and returns, per stage, the summed elapsed

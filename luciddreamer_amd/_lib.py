@@ -34,7 +34,8 @@ EXPORTS = ("lr_last_error", "lr_version", "lr_geom_bytes", "lr_img_bytes", "lr_b
            "lr_mark_visible", "lr_check",
            "lr_dist2_workspace_bytes", "lr_dist2",
            "lr_dist2_workspace_layout",
-           "lr_profile_enable", "lr_profile_stage_name", "lr_profile_read", "lr_tune_set", "lr_last_launch_shapes", "lr_request_early_header",
+           "lr_profile_enable", "lr_profile_stage_name", "lr_profile_read", "lr_tune_set", "lr_last_launch_shapes", "lr_last_forward_channels",
+           "lr_request_early_header",
            "lr_take_early_ticket", "lr_forward_ticket", "lr_backward_wait_event", "lr_step_begin", "lr_step_end", "lr_step_abort",
            "lr_views_workspace_bytes", "lr_views_accumulate", "lr_views_check",
            "lr_loss_workspace_bytes", "lr_l1_dssim_forward", "lr_l1_dssim_backward", "lr_l1_dssim_backward_weights",
@@ -567,6 +568,8 @@ def lib():
         L.lr_get_antialiasing.argtypes = []
         L.lr_last_launch_shapes.restype = ci
         L.lr_last_launch_shapes.argtypes = [ctypes.POINTER(ci), ctypes.POINTER(ci)]
+        L.lr_last_forward_channels.restype = ci
+        L.lr_last_forward_channels.argtypes = [ctypes.POINTER(ci)]
         L.lr_profile_enable.restype = ci
         L.lr_profile_enable.argtypes = [ci]
         L.lr_profile_stage_name.restype = ctypes.c_char_p
@@ -619,6 +622,17 @@ def last_launch_shapes():
     f, b = ctypes.c_int(-1), ctypes.c_int(-1)
     lib().lr_last_launch_shapes(ctypes.byref(f), ctypes.byref(b))
     return FWD_SHAPES.get(f.value, f.value), BWD_SHAPES.get(b.value, b.value)
+
+
+FWD_CHANNELS = {-1: None, 0: "none", 1: "color", 3: "color+depth"}
+
+
+def last_forward_channels():
+    """Channel set of the process's last blend forward (lr_last_forward_channels): "color+depth", "color", or "none" for the
+    colour-free forward of a multi-view step driven by fixed gradients."""
+    c = ctypes.c_int(-1)
+    lib().lr_last_forward_channels(ctypes.byref(c))
+    return FWD_CHANNELS.get(c.value, c.value)
 
 
 def profile_enable(on=True):

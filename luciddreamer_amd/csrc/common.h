@@ -457,6 +457,11 @@ int views_in_flight();
 void note_fwd_shape(int shape);
 int last_fwd_shape();
 int last_bwd_shape();
+// ... and the channels the last blend forward carried in its pixel state and wrote (lr_last_forward_channels): the kernel's
+// instantiation, not what a segmented tile does inside it; -1 = none yet
+enum { FWD_CHANNEL_COLOR = 1, FWD_CHANNEL_DEPTH = 2 };
+void note_fwd_channels(int channels);
+int last_fwd_channels();
 // Tile -> workgroup map of the blend kernels.  Workgroup b runs on XCD b % 8 (each XCD has its own L2):
 //   TILE_MAP_BANDS : XCD x renders the contiguous tile band [x T/8, (x+1) T/8): Gaussians that straddle neighbouring tiles
 //                    are re-read from the same L2.
@@ -481,6 +486,8 @@ __device__ __forceinline__ int blend_tile(int map, int num_tiles)
 void launch_render_fwd(const ViewParams& vp, const GeomView& g, const ImgView& im, const BinView& b, const float* bg,
                        float* out_color, float* out_depth, long long inst_hint, hipStream_t s);
 // out_depth == nullptr: the depth-free kernels (no depth channel in the per-pixel state, no depth image); everything else to the bit
+// out_color == nullptr as well: the colour-free kernels (no colour channels either, no colour image; checkpoints and c_final of
+// segmented tiles as ever); out_color == nullptr with an out_depth is the caller's error
 // alpha [n] = 1 - final_T [n]: the accumulated opacity of the forward that left final_T (lr_render_alpha)
 void launch_render_alpha(const float* final_T, long long n, float* alpha, hipStream_t s);
 // median depth [H*W] and Gaussian ids [H*W] (or nullptr) of a finished forward, and the gradient of the median depth to

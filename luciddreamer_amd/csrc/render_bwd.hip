@@ -948,6 +948,9 @@ static volatile int g_last_fwd_shape = -1, g_last_bwd_shape = -1;
 void note_fwd_shape(int shape) { g_last_fwd_shape = shape; }
 int last_fwd_shape() { return g_last_fwd_shape; }
 int last_bwd_shape() { return g_last_bwd_shape; }
+static volatile int g_last_fwd_channels = -1;
+void note_fwd_channels(int channels) { g_last_fwd_channels = channels; }
+int last_fwd_channels() { return g_last_fwd_channels; }
 
 void launch_render_bwd(const ViewParams& vp, const GeomView& g, const ImgView& im, const BinView& b, const float* bg,
                        const ViewGrads& up, bool absgrad, long long seg_bound, hipStream_t s)

@@ -45,19 +45,26 @@ constexpr int BATCH = 256;          // staged Gaussians per round = threads per 
 // arithmetic, so the gradients are identical -- and the common step loses the two instructions that tracked it.
 // DEPTH = false (launch_render_fwd without out_depth: a view whose depth image nobody reads): no D and acc, and the two
 // instructions per step that carried them are gone; every other field goes through the same operations.
-template <bool DEPTH> struct PixState { float T, Cr, Cg, Cb, D, acc; uint32_t last; };
-template <> struct PixState<false> { float T, Cr, Cg, Cb; uint32_t last; };
-template <bool DEPTH> __device__ __forceinline__ PixState<DEPTH> pix_start()
+// COLOR = false (launch_render_fwd without out_color either: a view of a multi-view step driven by fixed upstream gradients,
+// whose blended colour nobody reads -- the backward starts from final_T and n_contrib, a Gaussian's colour comes from its
+// GaussRec): no Cr / Cg / Cb, and the weight, its select and the three FMAs of a step are gone as well; T, done and last go
+// through the same operations in the same order.  Three channel sets: colour + depth, colour, neither (a step that reads depth
+// keeps carrying colour).
+template <bool DEPTH, bool COLOR = true> struct PixState { float T, Cr, Cg, Cb, D, acc; uint32_t last; };
+template <> struct PixState<false, true> { float T, Cr, Cg, Cb; uint32_t last; };
+template <> struct PixState<false, false> { float T; uint32_t last; };
+template <bool DEPTH, bool COLOR = true> __device__ __forceinline__ PixState<DEPTH, COLOR> pix_start()
 {
-    if constexpr (DEPTH) return PixState<true>{ 1.0f, 0.f, 0.f, 0.f, 0.f, 0.000001f, 0u };
-    else return PixState<false>{ 1.0f, 0.f, 0.f, 0.f, 0u };
+    static_assert(COLOR || !DEPTH, "the depth channel goes with the colour");
+    if constexpr (DEPTH) return PixState<true, true>{ 1.0f, 0.f, 0.f, 0.f, 0.f, 0.000001f, 0u };
+    else if constexpr (COLOR) return PixState<false, true>{ 1.0f, 0.f, 0.f, 0.f, 0u };
+    else return PixState<false, false>{ 1.0f, 0u };
 }
-
 // One candidate for the 64 pixels of the wave.  The per-pixel predicates live in wave-uniform 64-bit lane masks
 // (v_cmp writes them to an SGPR pair; they are combined on the scalar unit and fed back to v_cndmask through
 // inverse_ballot at no VALU cost); `done` is the mask of finished pixels.
-template <bool STRICT, bool DEPTH>
-__device__ __forceinline__ void fwd_pixel(PixState<DEPTH>& p, uint64_t& done, const float qA, const float qB, const float qC,
+template <bool STRICT, bool DEPTH, bool COLOR>
+__device__ __forceinline__ void fwd_pixel(PixState<DEPTH, COLOR>& p, uint64_t& done, const float qA, const float qB, const float qC,
                                           const float r0, const float r1,
                                           const float dx, const float op, const float cr, const float cg, const float cb,
                                           const float depth, const uint32_t pos0)
@@ -72,9 +79,11 @@ __device__ __forceinline__ void fwd_pixel(PixState<DEPTH>& p, uint64_t& done, co
     const uint64_t stop = pass & low_T;
     const bool use = __builtin_amdgcn_inverse_ballot_w64(pass & ~low_T);
     done |= stop;
-    const float wgt = use ? alpha * p.T : 0.f;
-    p.Cr += cr * wgt; p.Cg += cg * wgt; p.Cb += cb * wgt;
-    if constexpr (DEPTH) { p.D += depth * wgt; p.acc += wgt; }
+    if constexpr (COLOR) {
+        const float wgt = use ? alpha * p.T : 0.f;
+        p.Cr += cr * wgt; p.Cg += cg * wgt; p.Cb += cb * wgt;
+        if constexpr (DEPTH) { p.D += depth * wgt; p.acc += wgt; }
+    }
     p.T = use ? test_T : p.T;
     if (stop != 0ull) {                                                 // rare: a pixel stops at most once
         asm volatile("");                                               // keep it a scalar branch (no selects in the common path)
@@ -85,8 +94,8 @@ __device__ __forceinline__ void fwd_pixel(PixState<DEPTH>& p, uint64_t& done, co
 // The same step with the candidate's alpha already formed, and branch-free: for the PAIR loop below, where two candidates'
 // alphas are evaluated side by side and only these few dependent instructions per candidate remain in sequence.  `enable`:
 // all ones, or zero for the second half of an odd pair (the step is then the identity).
-template <bool DEPTH>
-__device__ __forceinline__ void fwd_step(PixState<DEPTH>& p, uint64_t& done, const float alpha, const float power, const uint64_t enable,
+template <bool DEPTH, bool COLOR>
+__device__ __forceinline__ void fwd_step(PixState<DEPTH, COLOR>& p, uint64_t& done, const float alpha, const float power, const uint64_t enable,
                                          const float cr, const float cg, const float cb, const float depth, const uint32_t pos0)
 {
     const float test_T = p.T * (1.0f - alpha);
@@ -95,9 +104,11 @@ __device__ __forceinline__ void fwd_step(PixState<DEPTH>& p, uint64_t& done, con
     const uint64_t stop = pass & low_T;
     const bool use = __builtin_amdgcn_inverse_ballot_w64(pass & ~low_T);
     done |= stop;
-    const float wgt = use ? alpha * p.T : 0.f;
-    p.Cr += cr * wgt; p.Cg += cg * wgt; p.Cb += cb * wgt;
-    if constexpr (DEPTH) { p.D += depth * wgt; p.acc += wgt; }
+    if constexpr (COLOR) {
+        const float wgt = use ? alpha * p.T : 0.f;
+        p.Cr += cr * wgt; p.Cg += cg * wgt; p.Cb += cb * wgt;
+        if constexpr (DEPTH) { p.D += depth * wgt; p.acc += wgt; }
+    }
     p.T = use ? test_T : p.T;
     p.last = __builtin_amdgcn_inverse_ballot_w64(stop) ? pos0 : p.last;
 }
@@ -108,15 +119,23 @@ __device__ __forceinline__ void fwd_step(PixState<DEPTH>& p, uint64_t& done, con
 // Same operations per pixel and candidate in the same order: bit-identical images.  Per tile: only lists of PAIR_MIN_LIST and more
 // (measured, forward alone: dense 512^2, 1 700 per tile, 180 -> 173 us; one layer of pixel-sized splats, 320 per tile, 53.7 -> 55.1).
 constexpr int PAIR_MIN_LIST = 1024;
-template <bool STRICT, bool PAIR, bool DEPTH>
+#define LR_FWD_PARAMS int W, int H, int gx, int num_tiles, int tile_map, const uint2* __restrict__ ranges,                      \
+                  const uint32_t* __restrict__ point_list, const uint32_t* __restrict__ list_gid,                              \
+                  const GaussRec* __restrict__ rec,                                                                            \
+                  const float* __restrict__ bg, float* __restrict__ final_T, uint32_t* __restrict__ n_contrib,                 \
+                  float* __restrict__ out_color, float* __restrict__ out_depth, uint8_t* __restrict__ quad_hits,               \
+                  GeomHeader* __restrict__ hdr, uint2* __restrict__ seg_list, float4* __restrict__ ckpt,                       \
+                  uint32_t* __restrict__ tile_seg0, float4* __restrict__ c_final
+#define LR_FWD_PASS W, H, gx, num_tiles, tile_map, ranges, point_list, list_gid, rec, bg, final_T, n_contrib, out_color,       \
+                  out_depth, quad_hits, hdr, seg_list, ckpt, tile_seg0, c_final
+// COLOR = false: out_color is never touched, and the pixel state has no colour channels -- except in the tiles whose list is cut
+// into segments: their checkpoints and c_final hold the colour so far, which the backward's segment start reads (render_bwd.hip
+// load_pixel).  So such a kernel holds the body twice (render_fwd_quad_body.h: CARRY), and a scalar branch per tile -- the
+// length of its list is uniform and known before the first round -- picks the copy.  (The PAIR variant of the diagnostics build
+// always carries.)
+template <bool STRICT, bool PAIR, bool DEPTH, bool COLOR>
 __global__ void __launch_bounds__(THREADS)
-k_render_fwd(int W, int H, int gx, int num_tiles, int tile_map, const uint2* __restrict__ ranges,
-             const uint32_t* __restrict__ point_list, const uint32_t* __restrict__ list_gid,
-             const GaussRec* __restrict__ rec,
-             const float* __restrict__ bg, float* __restrict__ final_T, uint32_t* __restrict__ n_contrib,
-             float* __restrict__ out_color, float* __restrict__ out_depth, uint8_t* __restrict__ quad_hits,
-             GeomHeader* __restrict__ hdr, uint2* __restrict__ seg_list, float4* __restrict__ ckpt,
-             uint32_t* __restrict__ tile_seg0, float4* __restrict__ c_final)
+k_render_fwd(LR_FWD_PARAMS)
 {
     __shared__ float4 s_q0[BATCH];      // x, y, Ap = -0.5 conic a, Bp = -conic b      (common.h gauss_power; x log2 e)
     __shared__ float4 s_q1[BATCH];      // Cp = -0.5 conic c (x log2 e), opacity, depth, qmax (cull threshold, x log2 e)
@@ -124,136 +143,20 @@ k_render_fwd(int W, int H, int gx, int num_tiles, int tile_map, const uint2* __r
     __shared__ float2 s_q3[BATCH];      // -b/c, -b/a (edge minimiser slopes for box_hit)
     __shared__ int s_wdone[NWAVES];
     __shared__ uint32_t s_seg0;
-
-    const int tile = blend_tile(tile_map, num_tiles);
-    if (tile < 0) return;
-    const int tx = tile % gx, ty = tile / gx;
-    const int tid = threadIdx.x, w = tid >> 6, l = tid & 63;
-    const int x0 = tx * TILE_X + (w & 1) * 8, y0 = ty * TILE_Y + (w >> 1) * 8;      // this wave's 8x8 quadrant
-    const int px = x0 + (l & 7), py = y0 + (l >> 3);
-    const bool inside = px < W && py < H;
-    const float pxf = (float)px, pyf = (float)py;
-    const float bx0 = (float)x0, bx1 = (float)(x0 + 7), by0 = (float)y0, by1 = (float)(y0 + 7);
-
-    const uint2 range = ranges[tile];
-    const int total = (int)(range.y - range.x);
-
-    PixState<DEPTH> A = pix_start<DEPTH>();
-    uint64_t done = __builtin_amdgcn_ballot_w64(!inside);             // lane mask of finished pixels (all 64 lanes are live)
-    bool wave_done = done == ~0ull;
-
-    // A list longer than BWD_SEG is cut into segments for the backward (common.h BinLayout::seg_list / ckpt): one atomic
-    // reserves the tile's slots, the (tile, segment) pairs are listed, and at the top of every later staging round the
-    // waves still blending leave {T, colour so far} of their pixels; the final colour goes to c_final at the end
-    static_assert(BATCH == BWD_SEG, "a staging round of the forward is one segment of the backward");
-    const int n_seg = total > 0 ? (total - 1) / BWD_SEG : 0;
-    uint32_t seg0 = 0;
-    int n_ck = 0;                                                     // checkpoints this wave has written (segments 1 .. n_ck)
-    if (n_seg > 0) {
-        if (tid == 0) { s_seg0 = atomicAdd(&hdr->n_seg, (uint32_t)n_seg); tile_seg0[tile] = s_seg0; }
-        lds_barrier();
-        seg0 = s_seg0;
-        for (int g = 1 + tid; g <= n_seg; g += THREADS) seg_list[seg0 + g - 1] = make_uint2((uint32_t)tile, (uint32_t)g);
-    }
-
-    for (int base = 0; base < total; base += BATCH) {
-        // all quadrants finished?  (also the barrier that protects the LDS planes of the previous batch)
-        if (l == 0) s_wdone[w] = wave_done ? 1 : 0;
-        lds_barrier();
-        if (s_wdone[0] + s_wdone[1] + s_wdone[2] + s_wdone[3] == NWAVES) break;
-        const int cnt = min(BATCH, total - base);
-        if (base > 0 && !wave_done) {
-            // every pixel of a wave that is done stopped in front of this position: the backward starts those from final_T
-            ckpt[(size_t)(seg0 + n_ck) * TILE_PIX + tid] = make_float4(A.T, A.Cr, A.Cg, A.Cb);
-            n_ck++;
+    if constexpr (COLOR || PAIR) {
+        constexpr bool CARRY = true;
+#include "render_fwd_quad_body.h"
+    } else {
+        const int peek = blend_tile(tile_map, num_tiles);
+        if (peek < 0) return;
+        const uint2 peek_range = ranges[peek];
+        if ((int)(peek_range.y - peek_range.x) > BWD_SEG) {
+            constexpr bool CARRY = true;
+#include "render_fwd_quad_body.h"
+        } else {
+            constexpr bool CARRY = false;
+#include "render_fwd_quad_body.h"
         }
-        if (tid < cnt) {
-            const uint32_t id = list_gid[range.x + base + tid];               // the Gaussian of the list position (BinLayout::list_gid)
-            const float4* g = reinterpret_cast<const float4*>(rec + id);
-            const float4 a = g[0], b = g[1], c = g[2];
-            // default: Ap, Bp, Cp and the cull threshold scaled by log2(e); strict: the conic and the threshold as they are
-            s_q0[tid] = STRICT ? make_float4(a.x, a.y, a.z, a.w) : make_float4(a.x, a.y, (-0.5f * LOG2E) * a.z, -LOG2E * a.w);
-            s_q1[tid] = STRICT ? make_float4(b.x, b.y, c.y, c.z) : make_float4((-0.5f * LOG2E) * b.x, b.y, c.y, LOG2E * c.z);
-            s_q2[tid] = make_float4(b.z, b.w, c.x, 0.f);
-            s_q3[tid] = make_float2(-a.w / b.x, -a.w / a.z);
-        }
-        lds_barrier();
-        if (wave_done) continue;
-
-        for (int sb = 0; sb < cnt; sb += 64) {
-            // CULL: lane l tests staged Gaussian sb+l against this wave's 8x8 quadrant
-            bool hit = false;
-            {
-                const int j = sb + l;
-                if (j < cnt) {
-                    const float4 a = s_q0[j];
-                    const float4 b = s_q1[j];
-                    const float2 r = s_q3[j];
-                    const float ca = STRICT ? a.z : -2.0f * a.z, cb = STRICT ? a.w : -a.w, cc = STRICT ? b.x : -2.0f * b.x;   // conic (x log2 e, like qmax)
-                    hit = box_hit(a.x, a.y, ca, cb, cc, r.x, r.y, b.w, bx0, bx1, by0, by1);
-                    // the outcome is kept for the backward (common.h BinLayout::quad_hits): every position a pixel of this
-                    // quadrant can have blended lies in a chunk this wave culled
-                    quad_hits[4 * ((size_t)range.x + (size_t)(base + j)) + w] = hit ? 1 : 0;
-                }
-            }
-            uint64_t mask = __ballot(hit);
-            // BLEND: walk the candidates in list order (a non-candidate is exactly the reference's `continue`: no pixel of
-            // the quadrant can reach alpha >= 1/255)
-            if (PAIR && total >= PAIR_MIN_LIST) {
-                while (mask) {
-                    const int k0 = __ffsll((long long)mask) - 1;
-                    mask &= mask - 1;
-                    const bool two = mask != 0ull;
-                    const int k1 = two ? __ffsll((long long)mask) - 1 : k0;
-                    mask &= mask - 1;                                                  // (0 & anything = 0)
-                    const int j0 = sb + k0, j1 = sb + k1;
-                    float4 a0 = s_q0[j0], a1 = s_q0[j1];
-                    float4 b0 = s_q1[j0], b1 = s_q1[j1];
-                    const float4 c0 = s_q2[j0], c1 = s_q2[j1];
-                    // Both candidates' reads are in flight before any arithmetic, and both alphas exist before the first step of
-                    // the recursion: the empty asm statements tie the two candidates' values together (left to itself the compiler
-                    // finishes candidate 0 -- reads, exponent, step -- before it even issues the reads of candidate 1)
-                    asm volatile("" : "+v"(a0.x), "+v"(a0.y), "+v"(a0.z), "+v"(a0.w), "+v"(b0.x), "+v"(a1.x), "+v"(a1.y), "+v"(a1.z), "+v"(a1.w), "+v"(b1.x));
-                    float r00, r01, r10, r11, power0, power1;
-                    gauss_row<STRICT>(a0.w, b0.x, a0.y - pyf, r00, r01);                        // common.h gauss_power
-                    gauss_row<STRICT>(a1.w, b1.x, a1.y - pyf, r10, r11);
-                    float alpha0 = fminf(0.99f, b0.y * gauss_weight<STRICT>(a0.z, a0.w, b0.x, r00, r01, a0.x - pxf, power0));
-                    float alpha1 = fminf(0.99f, b1.y * gauss_weight<STRICT>(a1.z, a1.w, b1.x, r10, r11, a1.x - pxf, power1));
-                    asm volatile("" : "+v"(alpha0), "+v"(alpha1), "+v"(power0), "+v"(power1));
-                    fwd_step(A, done, alpha0, power0, ~0ull, c0.x, c0.y, c0.z, b0.z, (uint32_t)(base + j0));
-                    fwd_step(A, done, alpha1, power1, two ? ~0ull : 0ull, c1.x, c1.y, c1.z, b1.z, (uint32_t)(base + j1));
-                }
-            } else
-            while (mask) {
-                const int k = __ffsll((long long)mask) - 1;
-                mask &= mask - 1;
-                const int j = sb + k;
-                const float4 a = s_q0[j];
-                const float4 b = s_q1[j];
-                const float4 c = s_q2[j];
-                const uint32_t pos0 = (uint32_t)(base + j);
-                const float dy = a.y - pyf;
-                float r0, r1;
-                gauss_row<STRICT>(a.w, b.x, dy, r0, r1);                                        // common.h gauss_power
-                fwd_pixel<STRICT, DEPTH>(A, done, a.z, a.w, b.x, r0, r1, a.x - pxf, b.y, c.x, c.y, c.z, b.z, pos0);
-            }
-            if (done == ~0ull) { wave_done = true; break; }             // all 64 pixels are finished
-        }
-    }
-
-    if (inside) {
-        const size_t N = (size_t)W * H;
-        const size_t pix = (size_t)py * W + px;
-        final_T[pix] = A.T;
-        n_contrib[pix] = __builtin_amdgcn_inverse_ballot_w64(done) ? A.last : (uint32_t)total;
-        const float fr = A.Cr + A.T * bg[0], fg = A.Cg + A.T * bg[1], fb = A.Cb + A.T * bg[2];
-        out_color[pix] = fr;
-        out_color[N + pix] = fg;
-        out_color[2 * N + pix] = fb;
-        // a segmented tile: the final colour once more, where the backward's later segments find it (they subtract a
-        // checkpoint's colour-so-far from it: the colour still to come behind that position, background included)
-        if (n_seg > 0) c_final[pix] = make_float4(fr, fg, fb, 0.f);
-        if constexpr (DEPTH) out_depth[pix] = (A.acc > 0.5f) ? A.D / A.acc : 0.0f;         // forward.cu:384-388
     }
 }
 
@@ -274,20 +177,20 @@ k_render_fwd(int W, int H, int gx, int num_tiles, int tile_map, const uint2* __r
 // unit, the row terms of the exponent -- is paid once per candidate and TILE (an instance reaches 2.33 of its tile's 4
 // quadrants at C3); no barriers, no partner waves to wait for, 3 KB of LDS.  Same operations per pixel and candidate in the
 // same order as the quadrant kernel: the same bits (tests/test_gpu_variants.py).
+// COLOR and CARRY: as in render_fwd_quad.
 constexpr int TSTAGE = 64;
-template <bool STRICT, bool DEPTH>
+template <bool STRICT, bool DEPTH, bool COLOR, bool CARRY>
 __device__ __forceinline__ void
-render_fwd_tile(int W, int H, int gx, int num_tiles, int tile_map, const uint2* __restrict__ ranges,
-                  const uint32_t* __restrict__ point_list, const uint32_t* __restrict__ list_gid,
-                  const GaussRec* __restrict__ rec,
-                  const float* __restrict__ bg, float* __restrict__ final_T, uint32_t* __restrict__ n_contrib,
-                  float* __restrict__ out_color, float* __restrict__ out_depth, uint8_t* __restrict__ quad_hits,
-                  GeomHeader* __restrict__ hdr, uint2* __restrict__ seg_list, float4* __restrict__ ckpt,
-                  uint32_t* __restrict__ tile_seg0, float4* __restrict__ c_final)
+render_fwd_tile(LR_FWD_PARAMS, float4* s_q0, float4* s_q1, float4* s_q2)
 {
-    __shared__ float4 s_q0[TSTAGE];     // as in k_render_fwd
-    __shared__ float4 s_q1[TSTAGE];
-    __shared__ float4 s_q2[TSTAGE];
+    static_assert(CARRY || !COLOR, "a colour image needs the colour channels");
+    // TIGHT: colour and depth in the state, default mode -- 28 registers of pixel state and the longest exponent chain.  Left to
+    // itself the compiler keeps loop-invariant addresses across the candidate loop and runs out of the 64 registers: 12 bytes of
+    // scratch (the lane's checkpoint address, spilled in front of the rounds).  Three such values are formed where they are
+    // used, from operands the optimiser cannot see through (as the quadrant boxes below are, for every instantiation): no
+    // scratch, a shift per round more.  All three are needed (with two of them 12 to 24 bytes stay); the other instantiations
+    // keep their code.
+    constexpr bool TIGHT = DEPTH && !STRICT;
 
     const int tile = blend_tile(tile_map, num_tiles);
     if (tile < 0) return;
@@ -300,12 +203,12 @@ render_fwd_tile(int W, int H, int gx, int num_tiles, int tile_map, const uint2* 
     const uint2 range = ranges[tile];
     const int total = (int)(range.y - range.x);
 
-    PixState<DEPTH> A[4];
+    PixState<DEPTH, CARRY> A[4];
     uint64_t done[4];
     bool inside[4];
 #pragma unroll
     for (int q = 0; q < 4; q++) {
-        A[q] = pix_start<DEPTH>();
+        A[q] = pix_start<DEPTH, CARRY>();
         inside[q] = pxl + (q & 1) * 8 < W && pyt + (q >> 1) * 8 < H;
         done[q] = __builtin_amdgcn_ballot_w64(!inside[q]);
     }
@@ -332,12 +235,14 @@ render_fwd_tile(int W, int H, int gx, int num_tiles, int tile_map, const uint2* 
         const int cnt = min(TSTAGE, total - base);
         const uint32_t id = id_next;
         if (base + TSTAGE < total) id_next = lgid[min(base + TSTAGE + l, total - 1)];
-        if (base > 0 && base % BWD_SEG == 0) {
+        if constexpr (CARRY) if (base > 0 && base % BWD_SEG == 0) {   // (without the colour channels: no segments, no such round)
             // (a quadrant whose pixels are all done stopped in front of this position: the backward starts those from final_T)
+            float4* ck = ckpt;
+            if constexpr (TIGHT) asm volatile("" : "+s"(ck));               // (the lane's checkpoint address: formed here)
 #pragma unroll
             for (int q = 0; q < 4; q++)
                 if (done[q] != ~0ull)
-                    ckpt[(size_t)(seg0 + base / BWD_SEG - 1) * TILE_PIX + q * 64 + l] = make_float4(A[q].T, A[q].Cr, A[q].Cg, A[q].Cb);
+                    ck[(size_t)(seg0 + base / BWD_SEG - 1) * TILE_PIX + q * 64 + l] = make_float4(A[q].T, A[q].Cr, A[q].Cg, A[q].Cb);
         }
         bool hit[4] = { false, false, false, false };
         lds_barrier();                                                // (the previous round's reads are done: one wave, no waiting)
@@ -353,7 +258,9 @@ render_fwd_tile(int W, int H, int gx, int num_tiles, int tile_map, const uint2* 
             const float4 a = g[0], b = g[1], c = g[2];
             const float4 q0 = STRICT ? make_float4(a.x, a.y, a.z, a.w) : make_float4(a.x, a.y, (-0.5f * LOG2E) * a.z, -LOG2E * a.w);
             const float4 q1 = STRICT ? make_float4(b.x, b.y, c.y, c.z) : make_float4((-0.5f * LOG2E) * b.x, b.y, c.y, LOG2E * c.z);
-            s_q0[l] = q0; s_q1[l] = q1; s_q2[l] = make_float4(b.z, b.w, c.x, 0.f);
+            int ls = l;
+            if constexpr (TIGHT) asm volatile("" : "+v"(ls));               // (the three planes' store addresses: formed per round)
+            s_q0[ls] = q0; s_q1[ls] = q1; s_q2[ls] = make_float4(b.z, b.w, c.x, 0.f);
             const float r_c = -a.w / b.x, r_a = -a.w / a.z;
             const float ca = STRICT ? q0.z : -2.0f * q0.z, cb = STRICT ? q0.w : -q0.w, cc = STRICT ? q1.x : -2.0f * q1.x;
 #pragma unroll
@@ -385,7 +292,7 @@ render_fwd_tile(int W, int H, int gx, int num_tiles, int tile_map, const uint2* 
                 for (int col = 0; col < 2; col++) {
                     const int q = 2 * row + col;
                     if ((m[q] & bit) == 0ull) continue;
-                    fwd_pixel<STRICT, DEPTH>(A[q], done[q], fa.z, fa.w, fb.x, r0, r1, fa.x - pxf[col], fb.y, fc.x, fc.y, fc.z, fb.z, pos0);
+                    fwd_pixel<STRICT, DEPTH, CARRY>(A[q], done[q], fa.z, fa.w, fb.x, r0, r1, fa.x - pxf[col], fb.y, fc.x, fc.y, fc.z, fb.z, pos0);
                     if (done[q] == ~0ull) {                            // the quadrant is finished: its later candidates are nobody's
                         m[q] = 0ull;
                         mask &= (m[0] | m[1]) | (m[2] | m[3]);
@@ -396,40 +303,51 @@ render_fwd_tile(int W, int H, int gx, int num_tiles, int tile_map, const uint2* 
     }
 
     const size_t N = (size_t)W * H;
+    int x0e = x0, y0e = y0;
+    if constexpr (TIGHT) asm volatile("" : "+s"(x0e), "+s"(y0e));           // (the pixel coordinates of the epilogue: formed here)
+    const int pxe = x0e + (l & 7), pye = y0e + (l >> 3);
 #pragma unroll
     for (int q = 0; q < 4; q++) {
         if (!inside[q]) continue;
-        const int px = pxl + (q & 1) * 8, py = pyt + (q >> 1) * 8;
+        const int px = pxe + (q & 1) * 8, py = pye + (q >> 1) * 8;
         const size_t pix = (size_t)py * W + px;
         final_T[pix] = A[q].T;
         n_contrib[pix] = __builtin_amdgcn_inverse_ballot_w64(done[q]) ? A[q].last : (uint32_t)total;
-        const float fr = A[q].Cr + A[q].T * bg[0], fg = A[q].Cg + A[q].T * bg[1], fb = A[q].Cb + A[q].T * bg[2];
-        out_color[pix] = fr;
-        out_color[N + pix] = fg;
-        out_color[2 * N + pix] = fb;
-        if (n_seg > 0) c_final[pix] = make_float4(fr, fg, fb, 0.f);
+        if constexpr (CARRY) {
+            const float fr = A[q].Cr + A[q].T * bg[0], fg = A[q].Cg + A[q].T * bg[1], fb = A[q].Cb + A[q].T * bg[2];
+            if constexpr (COLOR) {
+                out_color[pix] = fr;
+                out_color[N + pix] = fg;
+                out_color[2 * N + pix] = fb;
+            }
+            if (n_seg > 0) c_final[pix] = make_float4(fr, fg, fb, 0.f);
+        }
         if constexpr (DEPTH) out_depth[pix] = (A[q].acc > 0.5f) ? A[q].D / A[q].acc : 0.0f;         // forward.cu:384-388
     }
 }
-#define LR_FWD_TILE_PARAMS int W, int H, int gx, int num_tiles, int tile_map, const uint2* __restrict__ ranges,                 \
-                  const uint32_t* __restrict__ point_list, const uint32_t* __restrict__ list_gid,                              \
-                  const GaussRec* __restrict__ rec,                                                                            \
-                  const float* __restrict__ bg, float* __restrict__ final_T, uint32_t* __restrict__ n_contrib,                 \
-                  float* __restrict__ out_color, float* __restrict__ out_depth, uint8_t* __restrict__ quad_hits,               \
-                  GeomHeader* __restrict__ hdr, uint2* __restrict__ seg_list, float4* __restrict__ ckpt,                       \
-                  uint32_t* __restrict__ tile_seg0, float4* __restrict__ c_final
-#define LR_FWD_TILE_PASS W, H, gx, num_tiles, tile_map, ranges, point_list, list_gid, rec, bg, final_T, n_contrib, out_color,  \
-                  out_depth, quad_hits, hdr, seg_list, ckpt, tile_seg0, c_final
 // 64 registers -> 8 waves per SIMD: the 8160 tiles of a 1080p view are all resident at once, as in the backward's TILE shape
 // (round 6; with the compiler's own budget, 66-72 registers and 7 waves per SIMD, the last 992 waves waited for the first 7168:
 // lone view C3 62.3 -> 59.0 us, C2 101 -> 92 us, dense 1080p 366 -> 342 us, three views in flight equal;
 // profiles/r06h_ab_fwdtile8.json).  The quadrant boxes formed per round are what made room (render_fwd_tile).
-template <bool STRICT, bool DEPTH>
+// (COLOR = false: the two copies of the body and the branch between them, as in k_render_fwd.)
+template <bool STRICT, bool DEPTH, bool COLOR>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8), amdgpu_num_vgpr(64)))
-k_render_fwd_tile(LR_FWD_TILE_PARAMS)
+k_render_fwd_tile(LR_FWD_PARAMS)
 {
-    render_fwd_tile<STRICT, DEPTH>(LR_FWD_TILE_PASS);
+    __shared__ float4 s_q0[TSTAGE];     // as in k_render_fwd
+    __shared__ float4 s_q1[TSTAGE];
+    __shared__ float4 s_q2[TSTAGE];
+    if constexpr (COLOR) render_fwd_tile<STRICT, DEPTH, true, true>(LR_FWD_PASS, s_q0, s_q1, s_q2);
+    else {
+        const int tile = blend_tile(tile_map, num_tiles);
+        if (tile < 0) return;
+        const uint2 range = ranges[tile];
+        if ((int)(range.y - range.x) > BWD_SEG) render_fwd_tile<STRICT, DEPTH, false, true>(LR_FWD_PASS, s_q0, s_q1, s_q2);
+        else render_fwd_tile<STRICT, DEPTH, false, false>(LR_FWD_PASS, s_q0, s_q1, s_q2);
+    }
 }
+#undef LR_FWD_PARAMS
+#undef LR_FWD_PASS
 
 }  // namespace
 
@@ -461,16 +379,21 @@ void launch_render_fwd(const ViewParams& vp, const GeomView& g, const ImgView& i
     constexpr bool pair = false;
 #endif
     const bool strict = tune_get(TUNE_STRICT) > 0;
+    // out_color == nullptr: the colour-free instantiations, which never touch the pointer.  Only without out_depth: a view that
+    // reads its depth keeps carrying the colour and needs an image to write it to (forward_core refuses the combination)
+    const bool depth = out_depth != nullptr, color = out_color != nullptr;
     note_fwd_shape(tile_shape ? 2 : pair ? 1 : 0);
+    note_fwd_channels((color ? FWD_CHANNEL_COLOR : 0) | (depth ? FWD_CHANNEL_DEPTH : 0));
 #define LR_FWD_ARGS 0, s, vp.W, vp.H, gx, num_tiles, tile_map, im.ranges, b.point_list, b.list_gid, g.rec, bg, im.final_T, im.n_contrib, \
                     out_color, out_depth, b.quad_hits, g.header, b.seg_list, b.ckpt, im.tile_seg0, im.c_final
     // out_depth == nullptr: the depth-free instantiations (DEPTH = false never touches the pointer)
-    dispatch_flags<2>(flag_bits(strict, out_depth != nullptr), [&](auto st, auto dp) {
-        if (tile_shape) hipLaunchKernelGGL((k_render_fwd_tile<st.value, dp.value>), dim3(grid), dim3(64), LR_FWD_ARGS);
+    dispatch_flags<3>(flag_bits(strict, depth, color), [&](auto st, auto dp, auto cl) {
+        constexpr bool CL = cl.value || dp.value;                         // three channel sets: depth goes with the colour
+        if (tile_shape) hipLaunchKernelGGL((k_render_fwd_tile<st.value, dp.value, CL>), dim3(grid), dim3(64), LR_FWD_ARGS);
 #ifdef LR_DIAGNOSTICS
-        else if (pair) hipLaunchKernelGGL((k_render_fwd<st.value, true, dp.value>), dim3(grid), dim3(THREADS), LR_FWD_ARGS);
+        else if (pair) hipLaunchKernelGGL((k_render_fwd<st.value, true, dp.value, CL>), dim3(grid), dim3(THREADS), LR_FWD_ARGS);
 #endif
-        else hipLaunchKernelGGL((k_render_fwd<st.value, false, dp.value>), dim3(grid), dim3(THREADS), LR_FWD_ARGS);
+        else hipLaunchKernelGGL((k_render_fwd<st.value, false, dp.value, CL>), dim3(grid), dim3(THREADS), LR_FWD_ARGS);
     });
 #undef LR_FWD_ARGS
 }

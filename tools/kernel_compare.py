@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Are the kernels of two source trees the same machine code?  For a refactor of host code.
 
-    python tools/kernel_compare.py PARENT_TREE BRANCH_TREE [file.hip ...] [-j N]
+    python tools/kernel_compare.py PARENT_TREE BRANCH_TREE [file.hip ...] [-j N] [--rename REGEX=REPL ...] [--new-ok]
 
 Every .hip file named (default: every one of luciddreamer_amd/build.py's SOURCES that differs between the trees, or includes a
 header under csrc/ that does) is compiled in both trees with `hipcc -S --cuda-device-only` and that file's flags from the BRANCH
@@ -9,6 +9,11 @@ tree's build.py, once without and once with -DLR_DIAGNOSTICS.  The kernels (.amd
 the same set, and for each kernel the text from its label to .end_amdhsa_kernel -- code and descriptor: registers, LDS, scratch
 -- must be equal once comments are dropped and the numbers of local labels (.LBB<n>_, .Lfunc_end<n>, ...) are replaced.  Kernels
 are matched by name, so the order in which they are emitted does not matter.  Text is compared, nothing is searched for.
+
+A branch that adds a template argument to a kernel changes its symbol and nothing else: --rename REGEX=REPL (repeatable) is
+applied to the BRANCH's assembly before it is cut into kernels, so that such a kernel meets its parent under the parent's name
+(for a trailing bool that is true in the old instantiations: --rename '(k_render_fwd\w*I(?:Lb[01]E)+)Lb1EE=\1E').  --new-ok:
+kernels that only the branch has (after renaming) are listed and not counted as a difference.
 
 Prints one line per file and build, "<file> [diagnostics]: N kernels, 0 differ", and exits non-zero if any kernel differs or is
 missing on one side.  Needs hipcc; no GPU."""
@@ -52,7 +57,7 @@ def kernels(asm_text):
     return out
 
 
-def assemble(build, tree, src, diagnostics, outdir):
+def assemble(build, tree, src, diagnostics, outdir, renames=()):
     inc = os.path.join(outdir, "inc")
     os.makedirs(inc, exist_ok=True)
     with open(os.path.join(inc, "lr_src_hash.h"), "w") as f:           # api.hip's generated header; the hash is host data
@@ -63,7 +68,10 @@ def assemble(build, tree, src, diagnostics, outdir):
           ["-I", os.path.join(tree, "include"), "-I", inc] + build.SOURCES[src] + (["-DLR_DIAGNOSTICS"] if diagnostics else [])
     subprocess.run(cmd, check=True, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     with open(out) as f:
-        return kernels(f.read())
+        text = f.read()
+    for pattern, repl in renames:
+        text = re.sub(pattern, repl, text)
+    return kernels(text)
 
 
 def touched(build, parent, branch):
@@ -88,7 +96,10 @@ def main():
     ap.add_argument("branch")
     ap.add_argument("files", nargs="*")
     ap.add_argument("-j", type=int, default=8)
+    ap.add_argument("--rename", action="append", default=[], metavar="REGEX=REPL")
+    ap.add_argument("--new-ok", action="store_true")
     args = ap.parse_args()
+    renames = [tuple(r.split("=", 1)) for r in args.rename]
     parent, branch = os.path.abspath(args.parent), os.path.abspath(args.branch)
     build = load_build(branch)
     files = args.files or touched(build, parent, branch)
@@ -102,7 +113,7 @@ def main():
             for diag in (False, True):
                 for side, tree in (("parent", parent), ("branch", branch)):
                     d = os.path.join(tmp, side + ("_diag" if diag else ""))
-                    jobs[(src, diag, side)] = pool.submit(assemble, build, tree, src, diag, d)
+                    jobs[(src, diag, side)] = pool.submit(assemble, build, tree, src, diag, d, renames if side == "branch" else ())
         for src in files:
             for diag in (False, True):
                 try:
@@ -117,7 +128,7 @@ def main():
                       (f", {len(only_a)} only in the parent, {len(only_b)} only in the branch" if only_a or only_b else ""))
                 for k in (differ + only_a + only_b)[:10]:
                     print("    " + k)
-                bad += len(differ) + len(only_a) + len(only_b)
+                bad += len(differ) + len(only_a) + (0 if args.new_ok else len(only_b))
     return 1 if bad else 0
 
 
