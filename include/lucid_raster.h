@@ -1617,6 +1617,10 @@ void lr_backward_wait_event(void* event);
  *                        1 the same, bucket sort for 257..1024; 2 network up to 64 entries, bucket sort above; 3 rank sort for all of
  *                        them; 4 rank sort up to 128 entries, bucket sort above.  The rule (-1) is 4.  Every setting writes the same
  *                        lists.
+ *   "bin_fuse" 0/1       per-bin sort of the binning in async mode: 0 two launches (bins up to 1024 entries, then the queue of the
+ *                        larger ones), 1 one launch where the binning capacity says that the average bin holds at most 256 entries
+ *                        (the small sort's workgroups then serve the queue too).  The rule (-1) is 1.  Exact mode always has two.
+ *                        Every setting writes the same lists.
  *   "gauss_bwd" 0        no interleaved step accumulator
  * Values that select a RETIRED kernel ("part_scan", "bwd_red" 0 / 2 / 3, "fwd_pair" 1) and every LR_* environment override exist only in the
  * diagnostics build (-DLR_DIAGNOSTICS, `python -m luciddreamer_amd.build --diagnostics`; lr_version() then says "+diagnostics");

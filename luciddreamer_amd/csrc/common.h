@@ -433,12 +433,14 @@ struct TileBinTimes { virtual void mark(int boundary, hipStream_t s) = 0; virtua
 // (LDS attribute) or -2 (sub-tile + depth + slot bits exceed 64).
 // g: vis_list, offsets, hitrec, rec, header; im: part_hist, bin_total, bin_start, big_queue, ranges; b: inst_gid, words,
 // point_list, list_gid.  clear: words the count kernel clears on the way (the per-stream chunk sums).
+// one_sort (async mode, unless lr_tune_set("bin_fuse", 0)): one per-bin sort launch instead of two where bin_bound_hint says
+// that the queue of the large bins is expected empty.
 int launch_tile_binning(const ViewParams& vp, int slot_bits, const GeomView& g, const ImgView& im, const BinView& b,
-                        const int* radii, long long bin_bound_hint, TileBinTimes* t, WordSpan clear, hipStream_t s);
+                        const int* radii, long long bin_bound_hint, TileBinTimes* t, WordSpan clear, bool one_sort, hipStream_t s);
 
 // Diagnostic tuning knobs (lr_tune_set in api.hip): kernel variants that can be switched at run time so that two of them
 // are measured alternately in ONE process on ONE box (tools/ab_bench.py).  -1 = not set (the launcher's own rule).
-enum TuneKey { TUNE_BWD_RED = 0, TUNE_BLEND_QUAD, TUNE_TILE_MAP, TUNE_PREPROCESS, TUNE_GAUSS_BWD, TUNE_TSORT, TUNE_WALK_OWN, TUNE_HIT_MASK, TUNE_VIEWS_IN_FLIGHT, TUNE_STRICT, TUNE_PART_SCAN, TUNE_BWD_SEG, TUNE_FWD_PAIR, TUNE_PCULL, TUNE_COUNT };
+enum TuneKey { TUNE_BWD_RED = 0, TUNE_BLEND_QUAD, TUNE_TILE_MAP, TUNE_PREPROCESS, TUNE_GAUSS_BWD, TUNE_TSORT, TUNE_WALK_OWN, TUNE_HIT_MASK, TUNE_VIEWS_IN_FLIGHT, TUNE_STRICT, TUNE_PART_SCAN, TUNE_BWD_SEG, TUNE_FWD_PAIR, TUNE_PCULL, TUNE_BIN_FUSE, TUNE_COUNT };
 int tune_get(int key);
 
 // Shape of the backward blend kernel (render_bwd.hip, where the rule and its measurements are): BLEND_QUAD = 4 waves per

@@ -31,7 +31,10 @@
 //                                        the same walk again; every hit takes the next free position of its bin from
 //                                        an LDS cursor and stores ONE 64-bit word [sub-tile | depth bits | slot].
 //                                        The order inside a bin at this point is arbitrary -- and irrelevant:
-//   k_tile_sort_small / _large           every bin's words are sorted in LDS: <= 256 entries by one wave (rank sort up to
+//   k_tile_sort_resid                    (async mode, where the binning capacity says that the average bin holds at most 256
+//   or k_tile_sort_small / _large        entries: ONE launch -- k_tile_sort_small's grid and body, whose part-B workgroups then
+//                                        serve the queue of the bins of more than 1024 entries, in place; otherwise and in exact
+//                                        mode the two launches)  every bin's words are sorted in LDS: <= 256 entries by one wave (rank sort up to
 //                                        128, bucket sort above), <= 1024 by a workgroup and <= 4096 by a larger one
 //                                        (bucket sort), beyond that the bitonic network (in LDS up to 16384 entries when
 //                                        the launch has the room, else in global memory).
@@ -39,7 +42,7 @@
 //                                        Gaussian index -- so the result is exactly the reference's list, bit-for-bit
 //                                        repeatable, whatever order the scatter produced.
 //
-// 6 launches instead of 21 (7 for the whole forward), no global depth sort (the depth order is only ever needed inside a tile), no global
+// 5 launches in async mode (6 with the blend forward; 6 and 7 in exact mode and on dense views) instead of 21, no global depth sort (the depth order is only ever needed inside a tile), no global
 // atomics per instance (one per workgroup and bin), nothing that depends on a host round trip: every kernel takes its counts
 // from the device-side header.
 #include <mutex>
@@ -675,66 +678,106 @@ k_tile_sort_small(int bins, int groups4, int sub_shift, int slot_bits, int num_t
                   uint32_t* __restrict__ point_list, uint2* __restrict__ ranges, const uint32_t* __restrict__ inst_gid,
                   uint32_t* __restrict__ list_gid)
 {
-    __shared__ __attribute__((aligned(16))) unsigned long long s_a[4 * TSORT_LDS];   // 4 x 256 entries = TSORT_GROUP_LDS
-    __shared__ uint32_t s_cnt[TSORT_GROUP_LDS];               // part B's bucket counters
-    __shared__ unsigned long long s_red[8];
-    __shared__ uint32_t s_wave[4];
-    __shared__ uint32_t s_bad[4];
-    const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
-    if ((int)blockIdx.x < groups4) {
-        // part A: workgroup g takes bins 4 g .. 4 g + 3, one per wave, if they hold at most 256 entries
-        const int bin = (int)blockIdx.x * 4 + w;
-        const uint32_t n = bin < bins ? bin_total[bin] : 0u;
-        const uint32_t start = bin < bins ? bin_start[bin] : 0u;     // asked for with the count, not after it: one round trip less
-        if (n == 0 || n > (uint32_t)TSORT_LDS) return;
-        unsigned long long* a = s_a + w * TSORT_LDS;
-        // one wave, its own slice: LDS operations of a wave execute in order, so a wave-level fence is all the exchange
-        // between its lanes needs (no workgroup barrier anywhere in this part)
-        auto wsync = [] { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier();
-                          __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); };
-        if (n <= (uint32_t)rank_max) {
-            // the rank sort (rank_max: 0, 64, 128 or 256 -- launch_tile_binning): one or two words per lane up to 128 entries, four above
-            // (n and start are the same in every lane: say so, the walk's loop then runs on the scalar unit)
-            const uint32_t un = (uint32_t)__builtin_amdgcn_readfirstlane((int)n), ustart = (uint32_t)__builtin_amdgcn_readfirstlane((int)start);
-            const unsigned long long* src = words + ustart;
-            if (un <= 64u) rank_sort_wave<1>(src, un, a, ustart, bin, sub_shift, slot_bits, num_tiles, (uint32_t)l, point_list, ranges, inst_gid, list_gid, wsync);
-            else if (un <= 128u) rank_sort_wave<2>(src, un, a, ustart, bin, sub_shift, slot_bits, num_tiles, (uint32_t)l, point_list, ranges, inst_gid, list_gid, wsync);
-            else rank_sort_wave<4>(src, un, a, ustart, bin, sub_shift, slot_bits, num_tiles, (uint32_t)l, point_list, ranges, inst_gid, list_gid, wsync);
-            return;
+#include "tile_sort_small_body.h"
+}
+
+// -------------------------------------------------------------------------------------------
+// One residual sort launch (async mode; lr_tune_set("bin_fuse", 0) = the two launches): k_tile_sort_small's grid, whose part-B
+// workgroups -- all four waves reach the end of the body -- go on to serve the queue of bins of more than 1024 entries,
+// striding over it.  At C3 the queue is empty and k_tile_sort_large's launch cost 4.5 us alone and 10 .. 12 us of every view's
+// chain beside two other chains' kernels (profiles/binning_three_launches_ab.txt).
+// The launch rule (launch_tile_binning) asks for this only where the queue is expected empty (the AVERAGE bin holds at most
+// TSORT_LDS entries: every C3 view), and then the launch keeps the small sort's 12 KB of LDS per workgroup: the 48 .. 128 KB of
+// k_tile_sort_large on every small-bin workgroup would leave two or one of them on a compute unit instead of eight.  A queued
+// bin is therefore sorted IN PLACE, in `words`, by one workgroup: every block of 1024 entries in LDS, then the merges of the
+// bitonic network over the blocks -- a merge's steps at distances of 1024 and more in global
+// memory (L2-resident), its remaining ten steps block by block in LDS.  (k_tile_sort_large's own fallback runs EVERY step of
+// the network in global memory.)  The word is a total order: the list is the one any other sort of the bin gives.
+// -------------------------------------------------------------------------------------------
+// one step of the network (bitonic_sort's comparator) on positions [0, n) of a: partner distance 2^lj inside blocks of 2^lk
+__device__ __forceinline__ void bitonic_step(unsigned long long* a, uint32_t n, uint32_t half, uint32_t lk, uint32_t lj, uint32_t tid,
+                                             uint32_t nthreads)
+{
+    const uint32_t k = 1u << lk, j = 1u << lj;
+    const bool flip = (lj == lk - 1);
+    for (uint32_t c = tid; c < half; c += nthreads) {
+        const uint32_t hi = c >> lj, lo = c & (j - 1u);
+        uint32_t i, l;
+        if (flip) { i = (hi << lk) + lo; l = i ^ (k - 1u); }               // mirror inside the block of k
+        else { i = (hi << (lj + 1u)) + lo; l = i + j; }
+        if (l < n) {
+            const unsigned long long x = a[i], y = a[l];
+            if (x > y) { a[i] = y; a[l] = x; }
         }
-        if (bucket_b == 2 && n > 64) {
-            // the bucket sort by one wave in its own slices (C3: sort stage 19.4 -> 18.5 us, dense 1 M cloud 59.4 -> 56.2;
-            // profiles/r04d_ab_tsort_wave.json)
-            bucket_sort_bin<64, TSORT_LDS / 64>(words + start, n, slot_bits, a, s_cnt + w * TSORT_LDS, s_red + 2 * w, s_wave + w,
-                                                &s_bad[w], l, wsync);
-            write_sorted(a, n, start, bin, sub_shift, slot_bits, num_tiles, (uint32_t)l, 64u, point_list, ranges, inst_gid, list_gid);
-            return;
-        }
-        for (uint32_t i = l; i < n; i += 64) a[i] = words[start + i];
-        wsync();
-        if (n > 1) bitonic_sort(a, n, (uint32_t)l, 64u, wsync);
-        write_sorted(a, n, start, bin, sub_shift, slot_bits, num_tiles, (uint32_t)l, 64u, point_list, ranges, inst_gid, list_gid);
-        return;
     }
-    // part B: the remaining workgroups walk the bins with a stride and take those of 257..1024 entries, one at a time, with
-    // the four slices as one array (a sparse view has none: these workgroups read their bins' counts and leave)
-    const int first = (int)blockIdx.x - groups4, stride = (int)gridDim.x - groups4;
-    for (int bin = first; bin < bins; bin += stride) {
+}
+
+constexpr uint32_t RESID_LB = 10;                           // log2(TSORT_GROUP_LDS): a block of the in-place sort
+static_assert((1u << RESID_LB) == (uint32_t)TSORT_GROUP_LDS, "a block is what the workgroup's LDS holds");
+
+// a: the bin's n words in global memory, sorted in place by the 256 threads of one workgroup; s_a: TSORT_GROUP_LDS words of LDS
+__device__ __forceinline__ void sort_bin_in_place(unsigned long long* a, uint32_t n, unsigned long long* s_a, uint32_t tid)
+{
+    constexpr uint32_t B = 1u << RESID_LB;
+    // this workgroup's stores to the bin, complete and visible to all of its waves (nobody else touches a queued bin)
+    auto gsync = [] { __threadfence(); lds_barrier(); };
+    for (uint32_t off = 0; off < n; off += B) {
+        const uint32_t m = n - off < B ? n - off : B;
+        // (the network, not part B's bucket sort: a few registers, and this path is rare -- the launch keeps the small sort's
+        // 8 waves per SIMD without scratch)
+        for (uint32_t i = tid; i < m; i += 256) s_a[i] = a[off + i];
+        lds_barrier();
+        for (uint32_t lk = 1; lk <= RESID_LB; lk++)
+            for (uint32_t lj = lk; lj-- > 0;) {
+                bitonic_step(s_a, m, B >> 1, lk, lj, tid, 256u);
+                lds_barrier();
+            }
+        for (uint32_t i = tid; i < m; i += 256) a[off + i] = s_a[i];
+        lds_barrier();
+    }
+    gsync();
+    uint32_t lm = 0;
+    while ((1u << lm) < n) lm++;
+    const uint32_t half = 1u << (lm - 1);                   // n > B: lm > RESID_LB
+    for (uint32_t lk = RESID_LB + 1; lk <= lm; lk++) {
+        for (uint32_t lj = lk; lj-- > RESID_LB;) {
+            bitonic_step(a, n, half, lk, lj, tid, 256u);
+            gsync();
+        }
+        // distances below a block (never the mirror step: lk - 1 >= RESID_LB) stay inside aligned blocks
+        for (uint32_t off = 0; off < n; off += B) {
+            const uint32_t m = n - off < B ? n - off : B;
+            for (uint32_t i = tid; i < m; i += 256) s_a[i] = a[off + i];
+            lds_barrier();
+            for (uint32_t lj = RESID_LB; lj-- > 0;) {
+                bitonic_step(s_a, m, B >> 1, lk, lj, tid, 256u);
+                lds_barrier();
+            }
+            for (uint32_t i = tid; i < m; i += 256) a[off + i] = s_a[i];
+            lds_barrier();
+        }
+        gsync();
+    }
+}
+
+// (8 waves per SIMD, as k_tile_sort_small has them: the in-place sort, which almost no launch reaches, must not cost the small bins
+// their occupancy)
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8)))
+k_tile_sort_resid(int bins, int groups4, int sub_shift, int slot_bits, int num_tiles, int bucket_b, int rank_max, const uint32_t* __restrict__ bin_start,
+                  const uint32_t* __restrict__ bin_total, unsigned long long* words,
+                  uint32_t* __restrict__ point_list, uint2* __restrict__ ranges, const uint32_t* __restrict__ inst_gid,
+                  uint32_t* __restrict__ list_gid, const uint32_t* __restrict__ big_queue)
+{
+#include "tile_sort_small_body.h"
+    // part B's workgroups, all four waves (part A's waves left in the body)
+    const uint32_t count = big_queue[0];
+    for (uint32_t qi = (uint32_t)first; qi < count; qi += (uint32_t)stride) {
+        const int bin = (int)big_queue[1 + qi];
         const uint32_t n = bin_total[bin];
-        if (n <= (uint32_t)TSORT_LDS || n > (uint32_t)TSORT_GROUP_LDS) continue;
         const uint32_t start = bin_start[bin];
         lds_barrier();
-        if (bucket_b) {
-            // the bucket sort of k_tile_sort_large at this size: 4 entries and 4 buckets per thread, ~7 barriers instead of
-            // the network's 45-55
-            bucket_sort_bin<256, TSORT_GROUP_LDS / 256>(words + start, n, slot_bits, s_a, s_cnt, s_red, s_wave, &s_bad[0],
-                                                        (int)threadIdx.x, [] { lds_barrier(); });
-        } else {
-            for (uint32_t i = threadIdx.x; i < n; i += 256) s_a[i] = words[start + i];
-            lds_barrier();
-            bitonic_sort(s_a, n, threadIdx.x, 256u, [] { lds_barrier(); });
-        }
-        write_sorted(s_a, n, start, bin, sub_shift, slot_bits, num_tiles, threadIdx.x, 256u, point_list, ranges, inst_gid, list_gid);
+        sort_bin_in_place(words + start, n, s_a, threadIdx.x);
+        write_sorted(words + start, n, start, bin, sub_shift, slot_bits, num_tiles, threadIdx.x, 256u, point_list, ranges, inst_gid, list_gid);
     }
 }
 
@@ -804,7 +847,7 @@ void launch_compact(int P, const GeomView& g, const uint4* block_sums, uint32_t 
 }
 
 int launch_tile_binning(const ViewParams& vp, int slot_bits, const GeomView& g, const ImgView& im, const BinView& b,
-                        const int* radii, long long bin_bound_hint, TileBinTimes* t, WordSpan clear, hipStream_t s)
+                        const int* radii, long long bin_bound_hint, TileBinTimes* t, WordSpan clear, bool one_sort, hipStream_t s)
 {
     const int P = vp.P, gx = vp.gx, gy = vp.gy;
     // the partition kernels keep one counter per bin in LDS (up to 64 KB), the large-bin sort up to 128 KB.  The attribute is
@@ -868,12 +911,22 @@ int launch_tile_binning(const ViewParams& vp, int slot_bits, const GeomView& g, 
     const int tsort = tune_get(TUNE_TSORT);
     const int bucket_b = (tsort >= 0 && tsort <= 2) ? tsort : 2;
     const int rank_max = tsort < 0 ? TSORT_RANK_DEFAULT : (tsort == 3 ? TSORT_LDS : (tsort == 4 ? 128 : 0));
+    const long long avg_bin = bin_bound_hint / (long long)pp.bins;
+    // One residual launch (k_tile_sort_resid) where the queue of the large bins is expected empty -- the rule that gives
+    // k_tile_sort_large its small grid below.  Where the average bin is larger, the queue is served by k_tile_sort_large as
+    // before: its 48 .. 128 KB of LDS on every small-bin workgroup would cost the small bins their occupancy.
+    if (one_sort && avg_bin <= (long long)TSORT_LDS) {
+        hipLaunchKernelGGL(k_tile_sort_resid, dim3(groups4 + part_b), dim3(256), 0, s, pp.bins, groups4, pp.sub_shift, slot_bits,
+                           num_tiles, bucket_b, rank_max, im.bin_start, im.bin_total, b.words, b.point_list, im.ranges, b.inst_gid, b.list_gid,
+                           im.big_queue);
+        if (t) t->mark(4, s);
+        return hipGetLastError() == hipSuccess ? 0 : -1;
+    }
     hipLaunchKernelGGL(k_tile_sort_small, dim3(groups4 + part_b), dim3(256), 0, s, pp.bins, groups4, pp.sub_shift, slot_bits,
                        num_tiles, bucket_b, rank_max, im.bin_start, im.bin_total, b.words, b.point_list, im.ranges, b.inst_gid, b.list_gid);
     // the large bins: LDS for the bucket sort (32 KB of words; three workgroups per CU) unless the AVERAGE bin is already
     // beyond it -- then 128 KB, so that bins of up to 16384 entries are sorted in LDS (a hint for speed only: a bin that
     // does not fit this launch's LDS is sorted in place in global memory).  Capped grid: a sparse view queues nothing
-    const long long avg_bin = bin_bound_hint / (long long)pp.bins;
     const bool huge = avg_bin > (long long)TSORT_MID_LDS;
     const uint32_t lds_entries = huge ? (uint32_t)TSORT_BIG_LDS : (uint32_t)TSORT_MID_LDS;
     // what is resident at once (the queue is strided) -- or, where the AVERAGE bin is far below the queue's threshold (a C3
