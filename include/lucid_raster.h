@@ -1547,6 +1547,94 @@ int lr_tsdf_integrate(const lr_tsdf_integrate_args* a);
 int lr_tsdf_extract_count(const lr_tsdf_extract_args* a);
 int lr_tsdf_extract_emit(const lr_tsdf_extract_args* a);
 
+/*
+ * Mesh clean-up on the device (csrc/mesh.hip): what the same code bases do with Open3D on the host after extraction --
+ * cluster_connected_triangles, keep the largest clusters, remove_unreferenced_vertices, remove_degenerate_triangles,
+ * compute_vertex_normals.  The definitions are OURS, stated so that a numpy restatement gives the same bits (tests/mesh_ref.py).
+ *
+ *   Inputs.  vertices [V,3] float32, faces [T,3] int32, optional per-vertex colors and normals [V,3] float32;
+ *   0 <= V, T <= 2^31 - 2^12.  A face with an index outside [0, V) is OUT OF RANGE: no kernel dereferences it, it belongs to no
+ *   component and is never kept.
+ *
+ *   Components (lr_mesh_components).  Two vertices are connected when an in-range face holds both (vertex connectivity; Open3D
+ *   connects triangles across shared edges: the two differ only at a pinch vertex).  vertex_labels[v] is the smallest vertex
+ *   index of v's component; an unreferenced vertex is its own label.  face_labels[t] = vertex_labels[faces[t,0]], or -1 for an
+ *   out-of-range face.  component_faces[l] is the number of in-range faces with label l (0 where l is no label).  A canonical
+ *   label and integer counts: no output depends on an arrival order.
+ *
+ *   Filter (lr_mesh_filter_count, then lr_mesh_filter_emit) with keep_largest K >= 0, min_faces M >= 1, drop_degenerate.
+ *   Let c_1 >= c_2 >= ... be the face counts of the C components that have at least one face; kth = c_K if 1 <= K <= C, else
+ *   0; threshold = max(kth, M).  A face is kept iff it is in range, component_faces[label] >= threshold, and, with
+ *   drop_degenerate, it is not degenerate.  Ties at the threshold are all kept (2DGS's post_process_mesh rule, with a defined
+ *   K > C case).  A face is degenerate when two of its indices are equal or when L below is 0 or not finite; the counts are
+ *   taken before degenerate faces are dropped.  A vertex is kept iff a kept face refers to it.  Kept vertices and kept faces
+ *   stay in input order, faces are re-indexed; out_vertex_index [V'] and out_face_index [T'] (optional) are the source rows.
+ *   count fills the workspace, writes V' and T' to HOST memory and costs one stream synchronisation; the caller allocates the
+ *   outputs and passes the sizes back to emit with the SAME workspace and unchanged inputs.  A size of 0 needs no pointer.
+ *   out_colors / out_normals are required exactly when colors / normals are given.
+ *
+ *   Vertex normals (lr_mesh_vertex_normals): Open3D's compute_vertex_normals, equal weights over unit face normals.  Per
+ *   in-range face, in float64, one IEEE operation per step, no fma: a, b, c the three vertices converted to double,
+ *   e1 = b - a, e2 = c - a, n = (e1y e2z - e1z e2y, e1z e2x - e1x e2z, e1x e2y - e1y e2x), L = sqrt((nx nx + ny ny) + nz nz).
+ *   If L is finite and > 0 the face adds q = (int64) rint(n / L * 2^20) to each of its three vertices, otherwise nothing.  The
+ *   sums are int64 (integer addition is associative: no dependence on the face order).  Per vertex s = (double) sum,
+ *   S = sqrt((sx sx + sy sy) + sz sz); the normal is (float)(s / S), or (0,0,0) when S == 0.
+ *
+ *   workspace: lr_mesh_workspace_bytes(V, T) device bytes for any of the calls (0 for sizes it refuses): 24 per vertex and 9
+ *   per face, plus alignment.
+ *
+ *   Every device pointer must be 16-byte aligned.  struct_bytes is checked before anything else; every check sits in front of
+ *   the first HIP call.  V = 0 and T = 0 are valid (nothing is launched over zero items; a size of 0 needs no pointer).
+ *   Return 0 or a negative LR_ERR_*.
+ */
+typedef struct lr_mesh_components_args {
+    size_t struct_bytes;                     /* = sizeof(lr_mesh_components_args); anything else is LR_ERR_INVALID_ARG */
+    long long n_vertices, n_faces;
+    const int* faces;
+    int* vertex_labels;                      /* out [V] */
+    int* face_labels;                        /* out [T] */
+    int* component_faces;                    /* out [V] */
+    void* workspace;
+    size_t workspace_bytes;
+    void* stream;
+} lr_mesh_components_args;
+typedef struct lr_mesh_filter_args {
+    size_t struct_bytes;                     /* = sizeof(lr_mesh_filter_args); anything else is LR_ERR_INVALID_ARG */
+    long long n_vertices, n_faces;
+    const float* vertices;
+    const int* faces;
+    const float* colors;                     /* optional */
+    const float* normals;                    /* optional */
+    int keep_largest, min_faces, drop_degenerate;
+    void* workspace;
+    size_t workspace_bytes;
+    long long* out_n_vertices;               /* count: HOST */
+    long long* out_n_faces;                  /* count: HOST */
+    long long n_out_vertices, n_out_faces;   /* emit: what count returned */
+    float* out_vertices;                     /* emit */
+    float* out_colors;                       /* emit, with colors */
+    float* out_normals;                      /* emit, with normals */
+    int* out_faces;                          /* emit */
+    int* out_vertex_index;                   /* emit, optional */
+    int* out_face_index;                     /* emit, optional */
+    void* stream;
+} lr_mesh_filter_args;
+typedef struct lr_mesh_normals_args {
+    size_t struct_bytes;                     /* = sizeof(lr_mesh_normals_args); anything else is LR_ERR_INVALID_ARG */
+    long long n_vertices, n_faces;
+    const float* vertices;
+    const int* faces;
+    float* out_normals;                      /* out [V,3] */
+    void* workspace;
+    size_t workspace_bytes;
+    void* stream;
+} lr_mesh_normals_args;
+size_t lr_mesh_workspace_bytes(long long n_vertices, long long n_faces);
+int lr_mesh_components(const lr_mesh_components_args* a);
+int lr_mesh_filter_count(const lr_mesh_filter_args* a);
+int lr_mesh_filter_emit(const lr_mesh_filter_args* a);
+int lr_mesh_vertex_normals(const lr_mesh_normals_args* a);
+
 /* present[P] (1 byte each) = view-space z > 0.2.  Returns 0 or a negative LR_ERR_*. */
 int lr_mark_visible(int P, const float* means3D, const float* viewmatrix, const float* projmatrix,
                     unsigned char* present, void* stream);

@@ -16,9 +16,10 @@ def uninstall(handle):
 def __getattr__(name):
     """`luciddreamer_amd.mcmc` (MCMCStrategy: relocation, capped growth, position noise), `luciddreamer_amd.filter3d` (the 3D
     smoothing filter of Mip-Splatting), `luciddreamer_amd.reproject` (point-cloud reprojection: warped frames and hole masks),
-    `luciddreamer_amd.normals` (normals from depth and the normal losses) and `luciddreamer_amd.tsdf` (TSDF fusion of rendered
-    depth and mesh extraction) without importing torch with the package."""
-    if name in ("mcmc", "filter3d", "reproject", "normals", "tsdf"):
+    `luciddreamer_amd.normals` (normals from depth and the normal losses), `luciddreamer_amd.tsdf` (TSDF fusion of rendered
+    depth and mesh extraction) and `luciddreamer_amd.mesh` (connected components, cluster filter and vertex normals of a mesh)
+    without importing torch with the package."""
+    if name in ("mcmc", "filter3d", "reproject", "normals", "tsdf", "mesh"):
         import importlib
         return importlib.import_module("." + name, __name__)
     if name in ("fit_scale", "scatter_interpolate", "compensate", "dream_step"):     # dreaming on the device (reproject.py)

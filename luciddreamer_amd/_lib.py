@@ -51,7 +51,8 @@ EXPORTS = ("lr_last_error", "lr_version", "lr_geom_bytes", "lr_img_bytes", "lr_b
            "lr_dream_workspace_bytes", "lr_dream_scale_sums", "lr_dream_correspond", "lr_dream_lift", "lr_scatter_interpolate",
            "lr_normals_workspace_bytes", "lr_depth_normals", "lr_depth_normals_backward", "lr_normal_loss_forward",
            "lr_normal_loss_backward",
-           "lr_tsdf_workspace_bytes", "lr_tsdf_integrate", "lr_tsdf_extract_count", "lr_tsdf_extract_emit")
+           "lr_tsdf_workspace_bytes", "lr_tsdf_integrate", "lr_tsdf_extract_count", "lr_tsdf_extract_emit",
+           "lr_mesh_workspace_bytes", "lr_mesh_components", "lr_mesh_filter_count", "lr_mesh_filter_emit", "lr_mesh_vertex_normals")
 
 # lr_views_workspace_bytes / lr_views_check `parts`: what a step's workspace slots hold besides a view's scratch
 LR_VIEWS_LOSS, LR_VIEWS_DEPTH_LOSS, LR_VIEWS_MASK_LOSS = 1, 2, 4
@@ -360,6 +361,40 @@ class TsdfExtractArgs(ctypes.Structure):
         super().__init__(struct_bytes=ctypes.sizeof(TsdfExtractArgs), **fields)
 
 
+class MeshComponentsArgs(ctypes.Structure):
+    """lr_mesh_components_args, field for field (tests/test_mesh_cpu.py compares the offsets with the host compiler's)."""
+    _vp, _ll = ctypes.c_void_p, ctypes.c_longlong
+    _fields_ = [("struct_bytes", ctypes.c_size_t), ("n_vertices", _ll), ("n_faces", _ll), ("faces", _vp), ("vertex_labels", _vp),
+                ("face_labels", _vp), ("component_faces", _vp), ("workspace", _vp), ("workspace_bytes", ctypes.c_size_t),
+                ("stream", _vp)]
+
+    def __init__(self, **fields):
+        super().__init__(struct_bytes=ctypes.sizeof(MeshComponentsArgs), **fields)
+
+
+class MeshFilterArgs(ctypes.Structure):
+    """lr_mesh_filter_args, field for field.  out_n_vertices / out_n_faces are HOST long long."""
+    _vp, _ll, _ci = ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int
+    _fields_ = [("struct_bytes", ctypes.c_size_t), ("n_vertices", _ll), ("n_faces", _ll), ("vertices", _vp), ("faces", _vp),
+                ("colors", _vp), ("normals", _vp), ("keep_largest", _ci), ("min_faces", _ci), ("drop_degenerate", _ci),
+                ("workspace", _vp), ("workspace_bytes", ctypes.c_size_t), ("out_n_vertices", _vp), ("out_n_faces", _vp),
+                ("n_out_vertices", _ll), ("n_out_faces", _ll), ("out_vertices", _vp), ("out_colors", _vp), ("out_normals", _vp),
+                ("out_faces", _vp), ("out_vertex_index", _vp), ("out_face_index", _vp), ("stream", _vp)]
+
+    def __init__(self, **fields):
+        super().__init__(struct_bytes=ctypes.sizeof(MeshFilterArgs), **fields)
+
+
+class MeshNormalsArgs(ctypes.Structure):
+    """lr_mesh_normals_args, field for field."""
+    _vp, _ll = ctypes.c_void_p, ctypes.c_longlong
+    _fields_ = [("struct_bytes", ctypes.c_size_t), ("n_vertices", _ll), ("n_faces", _ll), ("vertices", _vp), ("faces", _vp),
+                ("out_normals", _vp), ("workspace", _vp), ("workspace_bytes", ctypes.c_size_t), ("stream", _vp)]
+
+    def __init__(self, **fields):
+        super().__init__(struct_bytes=ctypes.sizeof(MeshNormalsArgs), **fields)
+
+
 LR_SCATTER_TILE = 256             # samples per on-chip tile of lr_scatter_interpolate (include/lucid_raster.h)
 
 
@@ -552,6 +587,15 @@ def lib():
         for fn in (L.lr_tsdf_extract_count, L.lr_tsdf_extract_emit):
             fn.restype = ci
             fn.argtypes = [ctypes.POINTER(TsdfExtractArgs)]
+        L.lr_mesh_workspace_bytes.restype = ctypes.c_size_t
+        L.lr_mesh_workspace_bytes.argtypes = [ll, ll]
+        L.lr_mesh_components.restype = ci
+        L.lr_mesh_components.argtypes = [ctypes.POINTER(MeshComponentsArgs)]
+        for fn in (L.lr_mesh_filter_count, L.lr_mesh_filter_emit):
+            fn.restype = ci
+            fn.argtypes = [ctypes.POINTER(MeshFilterArgs)]
+        L.lr_mesh_vertex_normals.restype = ci
+        L.lr_mesh_vertex_normals.argtypes = [ctypes.POINTER(MeshNormalsArgs)]
         L.lr_step_begin.restype = ci
         L.lr_step_begin.argtypes = []
         L.lr_step_end.restype = ci

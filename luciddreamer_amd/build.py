@@ -56,6 +56,9 @@ SOURCES = {
     # TSDF fusion and mesh extraction: the shared float64 projection, then the header's float32 operations, one rounding each
     # (a numpy restatement agrees to the bit): no FMA contraction
     "tsdf.hip": ["-ffp-contract=off"],
+    # mesh clean-up (components, cluster filter, vertex normals): the header's float64 operations, one rounding each (a numpy
+    # restatement agrees to the bit): no FMA contraction
+    "mesh.hip": ["-ffp-contract=off"],
     "api.hip": [],
 }
 

@@ -824,6 +824,46 @@ hipError_t launch_tsdf_integrate(const TsdfIntegrateLaunch& a, hipStream_t s);
 hipError_t launch_tsdf_extract_count(const TsdfExtractLaunch& a, uint32_t* counts, hipStream_t s);
 hipError_t launch_tsdf_extract_emit(const TsdfExtractLaunch& a, hipStream_t s);
 
+// Mesh clean-up (mesh.hip): connected components, the cluster filter, vertex normals.  One workspace size serves all of them.
+struct MeshComponentsLaunch {
+    long long n_vertices, n_faces;
+    const int* faces;               // [T,3]
+    int* vertex_labels;             // [V]
+    int* face_labels;               // [T]
+    int* component_faces;           // [V]
+    void* workspace;
+};
+struct MeshFilterLaunch {
+    long long n_vertices, n_faces;
+    const float* vertices;          // [V,3]
+    const int* faces;               // [T,3]
+    const float* colors;            // [V,3] or nullptr
+    const float* normals;           // [V,3] or nullptr
+    int keep_largest, min_faces, drop_degenerate;
+    void* workspace;
+    long long n_out_vertices, n_out_faces;  // emit: the rows of the outputs
+    float* out_vertices;            // [V',3]
+    float* out_colors;              // [V',3] with colors
+    float* out_normals;             // [V',3] with normals
+    int* out_faces;                 // [T',3]
+    int* out_vertex_index;          // [V'] or nullptr
+    int* out_face_index;            // [T'] or nullptr
+};
+struct MeshNormalsLaunch {
+    long long n_vertices, n_faces;
+    const float* vertices;          // [V,3]
+    const int* faces;               // [T,3]
+    float* out_normals;             // [V,3]
+    void* workspace;
+};
+size_t mesh_workspace_bytes(long long n_vertices, long long n_faces);
+// the launches expect V > 0; components and normals take T = 0, the filter expects T > 0
+hipError_t launch_mesh_components(const MeshComponentsLaunch& a, hipStream_t s);
+// counts[0] = kept vertices, counts[1] = kept faces (host); waits for the stream
+hipError_t launch_mesh_filter_count(const MeshFilterLaunch& a, uint32_t* counts, hipStream_t s);
+hipError_t launch_mesh_filter_emit(const MeshFilterLaunch& a, hipStream_t s);
+hipError_t launch_mesh_vertex_normals(const MeshNormalsLaunch& a, hipStream_t s);
+
 void launch_dist2(int P, const float* points, float* out, char* workspace, hipStream_t s);
 size_t dist2_workspace_bytes(int P);
 void dist2_workspace_layout(int P, size_t offsets[4]);

@@ -11,7 +11,7 @@ distance volume, extract a triangle mesh -- with Open3D on the host.  Here:
         .extract_mesh(min_weight=1.0) -> (vertices [V,3] float32, colors [V,3] float32, faces [T,3] int32), device tensors
     pinhole_of(view) -> (K, R, T)     host float64 of a MiniCam / reference camera, the conventions of reproject.py
     fuse_views(volume, views, pc, opt, bg_color, depth="median" | "expected", alpha_min=0.5, render_fn=None)
-    save_mesh_ply(path, vertices, colors, faces)                             binary little-endian, uchar colours
+    save_mesh_ply(path, vertices, colors, faces, normals=None)               binary little-endian, uchar colours
 
 The definitions (include/lucid_raster.h) are this library's own, stated so that numpy reproduces them to the bit
 (tests/tsdf_ref.py): samples at the lattice points origin + s (i, j, k), tensors [nz,ny,nx] with x fastest; the projection is
@@ -228,21 +228,31 @@ def fuse_views(volume, views, pc, opt, bg_color, depth="median", alpha_min=0.5, 
     return volume
 
 
-def save_mesh_ply(path, vertices, colors, faces):
-    """Binary little-endian PLY: float x y z and uchar red green blue per vertex (colour clamped to [0,1], times 255, rounded
-    half to even), one uchar count and three int indices per face."""
+def save_mesh_ply(path, vertices, colors, faces, normals=None):
+    """Binary little-endian PLY: float x y z, with `normals` float nx ny nz behind them, and uchar red green blue per vertex
+    (colour clamped to [0,1], times 255, rounded half to even), one uchar count and three int indices per face.  Without
+    normals the file is what it was before the argument existed."""
     v = vertices.detach().float().cpu().numpy().reshape(-1, 3)
     c = colors.detach().float().cpu().numpy().reshape(-1, 3)
     f = faces.detach().cpu().numpy().astype(np.int32).reshape(-1, 3)
     if c.shape != v.shape:
         raise ValueError(f"tsdf.save_mesh_ply: {v.shape[0]} vertices and {c.shape[0]} colours")
     c8 = np.rint(np.clip(np.nan_to_num(c, nan=0.0), 0.0, 1.0) * 255.0).astype(np.uint8)
-    vrec = np.empty(v.shape[0], dtype=[("xyz", "<f4", 3), ("rgb", "u1", 3)])
+    fields = [("xyz", "<f4", 3), ("rgb", "u1", 3)]
+    if normals is not None:
+        n = normals.detach().float().cpu().numpy().reshape(-1, 3)
+        if n.shape != v.shape:
+            raise ValueError(f"tsdf.save_mesh_ply: {v.shape[0]} vertices and {n.shape[0]} normals")
+        fields.insert(1, ("nxyz", "<f4", 3))
+    vrec = np.empty(v.shape[0], dtype=fields)
     vrec["xyz"], vrec["rgb"] = v, c8
+    if normals is not None:
+        vrec["nxyz"] = n
     frec = np.empty(f.shape[0], dtype=[("n", "u1"), ("idx", "<i4", 3)])
     frec["n"], frec["idx"] = 3, f
     header = ("ply\nformat binary_little_endian 1.0\n"
-              f"element vertex {v.shape[0]}\nproperty float x\nproperty float y\nproperty float z\n"
+              f"element vertex {v.shape[0]}\nproperty float x\nproperty float y\nproperty float z\n" +
+              ("property float nx\nproperty float ny\nproperty float nz\n" if normals is not None else "") +
               "property uchar red\nproperty uchar green\nproperty uchar blue\n"
               f"element face {f.shape[0]}\nproperty list uchar int vertex_indices\nend_header\n")
     with open(path, "wb") as fh:
