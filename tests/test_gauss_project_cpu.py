@@ -19,6 +19,7 @@ import torch
 
 from luciddreamer_amd import cameras, synthetic
 from tests import helpers as hp
+from tests import intrinsics_cases as ic
 from tests import posed_cases as pc
 
 CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "luciddreamer_amd", "csrc")
@@ -159,6 +160,15 @@ def test_posed_cameras(gp, case):
     assert 0 < (radii > 0).sum()
     if case.startswith("band"):
         assert (radii == 0).sum() > 1000             # behind the camera, across the near plane, off the screen
+
+
+@pytest.mark.parametrize("case", sorted(ic.CASES))
+def test_general_intrinsics(gp, case):
+    """The six rows of tests/intrinsics_cases.py: focal_x != focal_y, a shifted principal point, wide and narrow fields of
+    view.  Here a focal_x / focal_y mix-up in the chain shows without a GPU."""
+    cam, cloud, degree = ic.make(case)
+    radii, _ = _hold(gp, cloud, cam, degree, ref=ic.reference(case), what=case)
+    assert (radii > 0).sum() >= 0.4 * radii.size
 
 
 @pytest.fixture(scope="module")

@@ -92,14 +92,14 @@ def _forward_of(out):
                 radii=out["radii"].cpu().numpy())
 
 
-@pytest.mark.parametrize("case", pc.RAW_CASES)
-def test_raw_path_matches_oracle_and_activated_path(hip_device, case):
-    """As tests/test_gpu_raw.py: test_raw_matches_cpu_oracle, then test_raw_matches_activated_path at that file's bars."""
+def check_raw_path(hip_device, cases, case):
+    """As tests/test_gpu_raw.py: test_raw_matches_cpu_oracle, then test_raw_matches_activated_path at that file's bars.  cases: the
+    module of the case (this file's posed_cases; tests/test_gpu_intrinsics.py passes its own)."""
     from luciddreamer_amd.gaussian_renderer import render, render_raw
-    cam, pc_cpu, act, degree = pc.raw_cloud(case)
-    ref = pc.raw_reference(case)
+    cam, pc_cpu, act, degree = cases.raw_cloud(case)
+    ref = cases.raw_reference(case)
     camd, bg = cam.to(hip_device), _bg().to(hip_device)
-    gcol = pc.upstream(cam, 4).to(hip_device)
+    gcol = cases.upstream(cam, 4).to(hip_device)
     raw = _on_device(pc_cpu, hip_device)
     out_r = render_raw(camd, raw, bg_color=bg)
     (out_r["render"] * gcol).sum().backward()
@@ -132,6 +132,11 @@ def test_raw_path_matches_oracle_and_activated_path(hip_device, case):
     hp.compare_grads({"vs": vs_r}, {"vs": vs_a}, names=("vs",), rtol=2e-4)
     for n in RAW_PARAMS:
         hp.compare_grads({n: g_r[n]}, {n: g_a[n]}, names=(n,), rtol=2e-4)
+
+
+@pytest.mark.parametrize("case", pc.RAW_CASES)
+def test_raw_path_matches_oracle_and_activated_path(hip_device, case):
+    check_raw_path(hip_device, pc, case)
 
 
 # ---- c. the depth and alpha outputs and their gradients, against the float64 restatement --------------------------------------
@@ -209,12 +214,12 @@ def _raster(cam, bg):
 class _Step:
     """The step's scene on the device in a given order of the views."""
 
-    def __init__(self, dev, order=None):
-        cams, cloud = pc.step_scene()
+    def __init__(self, dev, order=None, cases=pc):
+        cams, cloud = cases.step_scene()
         self.order = list(range(len(cams))) if order is None else list(order)
         self.dev = dev
         self.cams = [cams[i].to(dev) for i in self.order]
-        self.gs = [pc.step_upstream(i).to(dev) for i in self.order]
+        self.gs = [cases.step_upstream(i).to(dev) for i in self.order]
         self.cloud = {k: v.to(dev) for k, v in cloud.items()}
         self.bg = _bg().to(dev)
         self.P, self.W, self.H = cloud["means3D"].shape[0], cams[0].image_width, cams[0].image_height
@@ -270,8 +275,8 @@ def _close(got, want, what, tol=VIEW_TOL):
     return err / scale
 
 
-def _depth_against_oracle(depth, view, what):
-    ref = pc.step_reference(view)["depth"]
+def _depth_against_oracle(depth, view, what, cases=pc):
+    ref = cases.step_reference(view)["depth"]
     err = float((np.abs(depth.cpu().numpy() - ref) / np.maximum(1.0, np.abs(ref))).max())
     assert err <= hp.DEPTH_RTOL, (what, err)
     return err

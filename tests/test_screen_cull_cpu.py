@@ -261,6 +261,21 @@ def test_conservative_for_a_posed_camera(sc, clouds, res):
     assert (radii > 0).any() and rej[far].all()
 
 
+@pytest.mark.parametrize("case", ["wide", "narrow", "tall_pixels", "wide_pixels", "off_centre", "general"])
+def test_conservative_under_general_intrinsics(sc, case):
+    """The six rows of tests/intrinsics_cases.py (focal_x != focal_y, a shifted principal point, wide and narrow fields of view),
+    each on its own cloud, and on the band cloud, of which every row sees a part only."""
+    from tests import intrinsics_cases as ic
+    assert case in ic.CASES and len(ic.CASES) == 6
+    cam, cloud, _ = ic.make(case)
+    near, rej, radii = _assert_conservative(sc, cloud, cam, whole=True, what=case)
+    assert (radii > 0).sum() >= 0.4 * radii.size and (rej & near).sum() > 0
+    band = _small_cloud(20_000, "band", 1)
+    for mod in (1.0, 3.0):
+        near, rej, _ = _assert_conservative(sc, band, cam, mod, what=f"{case} band modifier {mod}")
+        assert (rej & near).sum() > 0
+
+
 def test_rows_that_are_no_numbers_pass(sc, clouds):
     """NaN / inf / 0 / negative scales, NaN and inf means, NaN quaternions: the test must let them through (NaN, inf) or
     stay conservative (0, negative: |scale| is what the covariance sees)."""
