@@ -542,7 +542,7 @@ def test_view_batch_equals_autograd_accumulation(hip_device):
 def test_view_batch_same_bits_for_every_number_of_chains(hip_device, n_views):
     """lr_views_accumulate spreads a step's views over 1..4 chains -- the chain of the LAST view on the caller's stream, the
     others on streams of the library, the accumulating kernels chained in view order by device-only events, the interleaved
-    accumulator zeroed behind the fork, each slot's overflow word reset by its first forward (csrc/api.hip views_core).  With the
+    accumulator zeroed behind the fork, each slot's overflow word reset by its first forward (csrc/api.hip StepChains::open, step_view).  With the
     kernel shapes pinned (they follow the number of views in flight otherwise), the sums must not depend on the number of chains
     by a single bit -- twice per batch (streams, events and workspace re-used), from accumulators that start as they are left
     -- and the step must be complete on the caller's stream when the call returns to it (the comparison reads on that stream)."""
@@ -592,6 +592,52 @@ def test_view_batch_with_fewer_views_than_streams(hip_device):
     assert batch.workspace.data_ptr() == stale.data_ptr()               # run() kept the planted buffer
     batch.check()
     assert float(acc["means3D"].abs().max()) > 0
+
+
+def test_view_batch_resets_a_slot_s_overflow_word_on_its_first_view_only(hip_device):
+    """The rule the step hands to each forward (csrc/api.hip step_view, ForwardMode::reset_sticky): a slot's sticky overflow word
+    is reset by the slot's FIRST view of the step and by no later one.  Five views on two chains (slot 0: views 0, 2, 4; slot 1:
+    views 1, 3) over a workspace of 0xFF bytes; a capacity between the largest and the second largest per-view instance count
+    makes exactly one view overflow, and the order of the cameras puts that view where the case wants it.  An overflow is a
+    reported condition of async mode: check() raises, nothing faults."""
+    from luciddreamer_amd import parallel
+    from tests.test_gpu_views_stats import _forward
+    P, W, H, ample = 8_000, 128, 96, 100_000
+    cloud = {k: v.to(hip_device) for k, v in synthetic.make_cloud(P, "band", 3).items()}
+    cams = [c.to(hip_device) for c in cameras.rotate360_path(W, H, n_views=5)]
+    g = synthetic.upstream_grad(H, W).to(hip_device)
+    bg = torch.zeros(3, device=hip_device)
+    counts = [_forward(cloud, cam, bg, 3)[6] for cam in cams]
+    by_count = [int(i) for i in np.argsort(counts)]
+    lost, clean = by_count[-1], by_count[:-1]
+    assert counts[clean[-1]] < counts[lost] <= ample, counts
+    cap = (counts[clean[-1]] + counts[lost]) // 2        # second largest <= cap < largest: exactly one view overflows
+    print(f"[sticky word] instances per view {counts}, capacity {cap}: view {lost} overflows")
+    acc = {"means3D": torch.zeros(P, 3, device=hip_device), "means2D": torch.zeros(P, 3, device=hip_device),
+           "opacity": torch.zeros(P, 1, device=hip_device), "sh": torch.zeros(P, 16, 3, device=hip_device),
+           "scales": torch.zeros(P, 3, device=hip_device), "rotations": torch.zeros(P, 4, device=hip_device)}
+    stale = None
+
+    def step(capacity, lost_at=None):
+        """One step on the shared workspace; lost_at: the position of the overflowing view among the five (None: as they come)."""
+        nonlocal stale
+        order = list(range(5)) if lost_at is None else clean[:lost_at] + [lost] + clean[lost_at:]
+        batch = parallel.ViewBatch([cams[i] for i in order], [g] * 5, 3, bg, binning_capacity=capacity, n_streams=2)
+        if stale is None:                                # the ample layout is the larger one
+            stale = torch.full((batch.workspace_bytes(P),), 0xFF, dtype=torch.uint8, device=hip_device)
+        batch.use_workspace(stale, P)
+        batch.run(cloud["means3D"], cloud["opacities"], cloud["scales"], cloud["rotations"], cloud["shs"], acc)
+        assert batch.workspace.data_ptr() == stale.data_ptr()
+        return batch
+
+    step(ample).check()                                  # (a) the first views of both slots reset the stale words
+    assert float(acc["means3D"].abs().max()) > 0
+    # (b) the first view of slot 1; (c) the last view of slot 1 and of slot 0 (the step's last view, on the caller's stream);
+    # (d) the first view of slot 0, two clean views behind it on that slot: a later view must not reset the word
+    for lost_at in (1, 3, 4, 0):
+        with pytest.raises(RuntimeError, match="capacity"):
+            step(cap, lost_at).check()
+    step(ample).check()                                  # (e) on the workspace (d) left: slot 0's word is set at offset 0 of both layouts
 
 
 def test_view_batch_with_fused_loss_equals_autograd(hip_device):
