@@ -1709,6 +1709,10 @@ void lr_backward_wait_event(void* event);
  *                        larger ones), 1 one launch where the binning capacity says that the average bin holds at most 256 entries
  *                        (the small sort's workgroups then serve the queue too).  The rule (-1) is 1.  Exact mode always has two.
  *                        Every setting writes the same lists.
+ *   "blend_fuse" 0/1/2   lr_views_accumulate, a view with a fixed dL_dpix as its only upstream gradient whose image, depth and alpha
+ *                        nobody reads: 0 blend forward and backward as two launches; 1 one launch (the forward and the backward of
+ *                        a tile in one wave) where both would be the one-wave-per-tile kernels; 2 one launch at every image size
+ *                        and with any number of views in flight.  The rule (-1) is 1.  Every setting computes the same bits.
  *   "gauss_bwd" 0        no interleaved step accumulator
  * Values that select a RETIRED kernel ("part_scan", "bwd_red" 0 / 2 / 3, "fwd_pair" 1) and every LR_* environment override exist only in the
  * diagnostics build (-DLR_DIAGNOSTICS, `python -m luciddreamer_amd.build --diagnostics`; lr_version() then says "+diagnostics");

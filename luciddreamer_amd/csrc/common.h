@@ -440,7 +440,7 @@ int launch_tile_binning(const ViewParams& vp, int slot_bits, const GeomView& g, 
 
 // Diagnostic tuning knobs (lr_tune_set in api.hip): kernel variants that can be switched at run time so that two of them
 // are measured alternately in ONE process on ONE box (tools/ab_bench.py).  -1 = not set (the launcher's own rule).
-enum TuneKey { TUNE_BWD_RED = 0, TUNE_BLEND_QUAD, TUNE_TILE_MAP, TUNE_PREPROCESS, TUNE_GAUSS_BWD, TUNE_TSORT, TUNE_WALK_OWN, TUNE_HIT_MASK, TUNE_VIEWS_IN_FLIGHT, TUNE_STRICT, TUNE_PART_SCAN, TUNE_BWD_SEG, TUNE_FWD_PAIR, TUNE_PCULL, TUNE_BIN_FUSE, TUNE_COUNT };
+enum TuneKey { TUNE_BWD_RED = 0, TUNE_BLEND_QUAD, TUNE_TILE_MAP, TUNE_PREPROCESS, TUNE_GAUSS_BWD, TUNE_TSORT, TUNE_WALK_OWN, TUNE_HIT_MASK, TUNE_VIEWS_IN_FLIGHT, TUNE_STRICT, TUNE_PART_SCAN, TUNE_BWD_SEG, TUNE_FWD_PAIR, TUNE_PCULL, TUNE_BIN_FUSE, TUNE_BLEND_FUSE, TUNE_COUNT };
 int tune_get(int key);
 
 // Shape of the backward blend kernel (render_bwd.hip, where the rule and its measurements are): BLEND_QUAD = 4 waves per
@@ -559,6 +559,15 @@ struct ViewGrads {
 // g: rec, header; im: ranges, final_T, n_contrib, tile_seg0, c_final; b: base, point_list
 void launch_render_bwd(const ViewParams& vp, const GeomView& g, const ImgView& im, const BinView& b, const float* bg,
                        const ViewGrads& up, bool absgrad, long long seg_bound, hipStream_t s);
+// The blend forward AND backward of a view in one launch (render_bwd.hip k_render_bwd_tile_step): for a view of the multi-view step
+// whose image nobody reads and whose upstream gradient is a fixed dL_dpix alone, in place of launch_render_fwd (colour-free, depth-free,
+// tile shape) followed by launch_render_bwd (tile shape, segments on) -- the same bits in final_T, n_contrib, quad_hits and every
+// instance slot.  blend_step_fused: the rule (lr_tune_set("blend_fuse", 0 / 1 / 2): never / the two launchers' own shape rules / at
+// every image size); inst_hint as launch_render_fwd's, seg_bound as launch_render_bwd's.
+// g: rec, header; im: ranges, final_T, n_contrib, tile_seg0, c_final; b: base
+bool blend_step_fused(int num_tiles, long long inst_hint, long long seg_bound);
+void launch_render_bwd_step(const ViewParams& vp, const GeomView& g, const ImgView& im, const BinView& b, const float* bg,
+                            const float* dL_dpix, hipStream_t s);
 // ---- Adam, element-wise (adam.hip and the step fused into the per-Gaussian backward, gauss_bwd.hip) -----------------------
 // torch's single-tensor Adam (torch/optim/adam.py _single_tensor_adam; no weight decay, amsgrad or maximize) with the roundings
 // of torch's own kernels: lerp = fma(w, b - a, a), addcmul = fma(value * t1, t2, self), addcdiv = fma(value, t1 / t2, self);

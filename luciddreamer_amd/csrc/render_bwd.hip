@@ -30,6 +30,9 @@ namespace lr {
 
 namespace {
 
+// the one-wave-per-tile blend forward (render_fwd.hip), for k_render_bwd_tile_step below
+#include "render_fwd_tile_body.h"
+
 #ifndef LR_QBATCH_BWD
 #define LR_QBATCH_BWD 128           // staging round of the QUAD shape (per-wave accumulator columns: 24 KB of LDS at 128)
 #endif
@@ -523,6 +526,7 @@ __device__ __forceinline__ void render_bwd_item(const int tile, const int seg, c
 // lower pixel pair apart (D, D dx, D dx^2 each) and applies the dy factors to each pair before the reduction.  Single-wave
 // workgroups: 8160 of them at 1080p, no partner wave to wait for at the batch barriers.
 // ALPHA: as render_bwd_item (the start values of A only).
+// The body is render_bwd_tile_body.h: k_render_bwd_tile_step (below) includes it a second time, behind its forward half.
 template <int BATCH, bool STRICT, bool LDSRED = false, bool ALPHA = false>
 __device__ __forceinline__ void render_bwd_tile(const int tile, const int seg, const uint32_t ck_slot,
                   const float4* __restrict__ c_final, int W, int H, int gx, const uint2* __restrict__ ranges,
@@ -538,180 +542,32 @@ __device__ __forceinline__ void render_bwd_tile(const int tile, const int seg, c
     __shared__ uint32_t s_id[BATCH];
     __shared__ float s_acc[BATCH * 12]; // one wave, one copy: a candidate is met once per batch, so its sums are plain stores
     __shared__ __attribute__((aligned(256))) float s_tr[LDSRED ? 8 * 64 : 1];      // lds_reduce9's planes
-
-    const int tx = tile % gx, ty = tile / gx;
-    const int l = threadIdx.x;
-    const int x0 = tx * TILE_X, y0 = ty * TILE_Y;
-    const int pxL = x0 + (l & 7), pxR = pxL + 8, pyT = y0 + (l >> 3), pyB = pyT + 8;
-    const float pyTf = (float)pyT, pyBf = (float)pyB;
-    const size_t N = (size_t)W * H;
-
-    const uint2 range = ranges[tile];
-    const int total = (int)(range.y - range.x);
-    if (total == 0) return;
-    const int seg_lo = seg < 0 ? 0 : seg * BWD_SEG;                    // as render_bwd_item
-    const int seg_hi = seg < 0 ? total : min(total, seg_lo + BWD_SEG);
-    if (seg_lo >= seg_hi) return;
-    const BinLayout BL = bin_layout((long long)hdr->bin_bound);
-    const uint32_t* __restrict__ list_gid = reinterpret_cast<const uint32_t*>(bin_base + BL.list_gid);
-    float4* __restrict__ inst_grad = reinterpret_cast<float4*>(bin_base + BL.inst_grad);
-    const uint32_t* __restrict__ quad_hits = reinterpret_cast<const uint32_t*>(bin_base + BL.quad_hits);
-    const float4* __restrict__ ck = reinterpret_cast<const float4*>(bin_base + BL.ckpt) + (size_t)ck_slot * TILE_PIX;
-
-    // quadrant q = x half + 2 * y half (the forward's wave q): P0 upper left, P1 upper right, P2 lower left, P3 lower right
-    BwdPix P0, P1, P2, P3;
-    const float bg0 = bg[0], bg1 = bg[1], bg2 = bg[2];
-    auto load_pixel = [&](BwdPix& p, int px, int py, int q) {
-        const bool ins = px < W && py < H;
-        const size_t pix = (size_t)py * W + px;
-        p.pxf = (float)px;
-        p.T = ins ? final_Ts[pix] : 0.f;
-        p.last = ins ? n_contrib[pix] : 0u;
-        p.dLr = ins ? dL_dpix[pix] : 0.f;
-        p.dLg = ins ? dL_dpix[N + pix] : 0.f;
-        p.dLb = ins ? dL_dpix[2 * N + pix] : 0.f;
-        p.A = bg0 * p.dLr + bg1 * p.dLg + bg2 * p.dLb;
-        float ga = 0.f;
-        if constexpr (ALPHA) {
-            ga = ins ? dL_dalpha[pix] : 0.f;
-            p.A -= ga;
-        }
-        if (seg_hi < total && p.last > (uint32_t)seg_hi) {          // as render_bwd_item: the forward's state at the segment's deep end
-            const float4 c = ck[q * 64 + l], f = c_final[pix];
-            if constexpr (ALPHA)
-                p.A = ((f.x - c.y) * p.dLr + (f.y - c.z) * p.dLg + (f.z - c.w) * p.dLb - ga * p.T) * __builtin_amdgcn_rcpf(c.x);
-            p.T = c.x;
-            if constexpr (!ALPHA)
-                p.A = ((f.x - c.y) * p.dLr + (f.y - c.z) * p.dLg + (f.z - c.w) * p.dLb) * __builtin_amdgcn_rcpf(c.x);
-        }
-    };
-    load_pixel(P0, pxL, pyT, 0); load_pixel(P1, pxR, pyT, 1); load_pixel(P2, pxL, pyB, 2); load_pixel(P3, pxR, pyB, 3);
-    const uint32_t last0 = wave_max_u32(P0.last), last1 = wave_max_u32(P1.last);
-    const uint32_t last2 = wave_max_u32(P2.last), last3 = wave_max_u32(P3.last);
-    const uint32_t tile_last = max(max(last0, last1), max(last2, last3));
-
-    const int row = l >> 4;
-    const int col_a = (row == 0) ? 0 : (row == 1) ? 2 : (row == 2) ? 1 : 3;     // as k_render_bwd (reduce8 / row_merge3 layout)
-    const int l16 = l & 15;
-    const bool merge_writer = (l16 & 3) == 0 && l16 < 12;
-    // lds_reduce9 leaves terms 2 row / 2 row + 1 in lanes 0 / 8 (term t IS column t) and the row's db partial in lane 4
-    const int merge_off = LDSRED ? (l16 == 0 ? 2 * row : l16 == 8 ? 2 * row + 1 : 8 + row)
-                                 : (l16 == 0 ? col_a : l16 == 8 ? col_a + 4 : 8 + row);
-    uint32_t tr_base = 0u, tr_a1 = 0u;
-    if (LDSRED) {
-        tr_base = (uint32_t)(uintptr_t)s_tr;
-        const int t = l >> 3, sh = (l >> 2) & 1;
-        tr_a1 = tr_base + (uint32_t)(t * 256 + (((t & 3) < 2) ? sh : 3 - sh) * 64 + (l & 3) * 16);
-    }
-
-    for (int base = 0; base < seg_hi - seg_lo; base += BATCH) {
-        const int cnt = min(BATCH, seg_hi - seg_lo - base);
-        const int pos_hi = seg_hi - 1 - base;            // position of staged element 0 (back to front)
-        const int pos_lo = pos_hi - (cnt - 1);
-        if ((uint32_t)pos_lo >= tile_last) {             // whole batch behind every last contributor: slots read as zero
-            if (l < cnt) {
-                float4* slot = inst_grad + 3 * (size_t)point_list[range.x + (pos_hi - l)];
-                slot[0] = make_float4(0.f, 0.f, 0.f, 0.f); slot[1] = slot[0]; slot[2] = slot[0];
-            }
-            continue;
-        }
-        lds_barrier();
-        // the lane's staging / flush addresses are formed HERE, per round, from a lane index the optimiser cannot see through:
-        // hoisted out of the loop they are seven more live registers in a kernel that has 64, i.e. seven spilled dwords per
-        // lane (15 MB of scratch stores per 1080p view, round 6) for a handful of integer operations per round
-        int lv = l;
-        asm volatile("" : "+v"(lv));
-        uint32_t my_hit = 0u;
-        if (lv < cnt) {
-            const uint32_t e = point_list[range.x + (pos_hi - lv)];
-            my_hit = quad_hits[range.x + (pos_hi - lv)];
-            const uint32_t id = list_gid[range.x + (pos_hi - lv)];       // (BinLayout::list_gid: no gather through e)
-            const float4* g = reinterpret_cast<const float4*>(rec + id);
-            const float4 a = g[0], b = g[1], c = g[2];
-            s_q0[lv] = STRICT ? make_float4(a.x, a.y, a.z, a.w) : make_float4(a.x, a.y, (-0.5f * LOG2E) * a.z, -LOG2E * a.w);
-            *reinterpret_cast<float2*>(&s_q1[lv]) = STRICT ? make_float2(b.x, b.y) : make_float2((-0.5f * LOG2E) * b.x, b.y);
-            s_q2[lv] = make_float4(b.z, b.w, c.x, 0.f);
-            s_id[lv] = e;
-        }
-        if (lv < BATCH) {
-            float4* z = reinterpret_cast<float4*>(&s_acc[lv * 12]);
-            z[0] = make_float4(0.f, 0.f, 0.f, 0.f); z[1] = z[0]; z[2] = z[0];
-        }
-        lds_barrier();
-
-        // CULL: the staging lane IS the lane that holds the element's quadrant tests (one batch = one wave-wide chunk)
-        const uint32_t pos_l = (uint32_t)(pos_hi - l);
-        const bool inb = l < cnt;
-        const uint64_t m0 = __ballot(inb && pos_l < last0 && (my_hit & 0x000000ffu) != 0u);
-        const uint64_t m1 = __ballot(inb && pos_l < last1 && (my_hit & 0x0000ff00u) != 0u);
-        const uint64_t m2 = __ballot(inb && pos_l < last2 && (my_hit & 0x00ff0000u) != 0u);
-        const uint64_t m3 = __ballot(inb && pos_l < last3 && (my_hit & 0xff000000u) != 0u);
-        uint64_t mask = (m0 | m1) | (m2 | m3);
-        // (always the copy WITH the `pos < last` test: a second copy of this loop costs the 64-VGPR budget 28 more spilled bytes
-        //  and the kernel 5 % -- measured 96.0 -> 101.0 us at C3, profiles/r04i_ab_bwd_nocheck_tile.json)
-        constexpr bool CHECK = true;
-        while (mask) {
-            const int j = __ffsll((long long)mask) - 1;       // staged order is already back to front
-            mask &= mask - 1;
-            const uint32_t pos = (uint32_t)(pos_hi - j);
-            const float4 a = s_q0[j];
-            const float2 b = *reinterpret_cast<const float2*>(&s_q1[j]);   // Cp, opacity
-            const float4 c = s_q2[j];
-            const float dysT = a.y - pyTf, dysB = a.y - pyBf;
-            float tD = 0.f, tMx = 0.f, tMxx = 0.f, bD = 0.f, bMx = 0.f, bMxx = 0.f, sR = 0.f, sG = 0.f, sB = 0.f;
-            const bool h0 = (m0 >> j) & 1ull, h1 = (m1 >> j) & 1ull, h2 = (m2 >> j) & 1ull, h3 = (m3 >> j) & 1ull;
-            if (h0 || h1) {
-                float Bd, Cdd;
-                gauss_row<STRICT>(a.w, b.x, dysT, Bd, Cdd);                                              // common.h gauss_power
-                if (h0) bwd_pixel<true, true, CHECK, STRICT>(P0, a.z, a.w, b.x, Bd, Cdd, a.x, b.y, c.x, c.y, c.z, pos, tD, tMx, tMxx, sR, sG, sB);
-                if (h1) bwd_pixel<false, false, CHECK, STRICT>(P1, a.z, a.w, b.x, Bd, Cdd, a.x, b.y, c.x, c.y, c.z, pos, tD, tMx, tMxx, sR, sG, sB);
-            }
-            if (h2 || h3) {
-                float Bd, Cdd;
-                gauss_row<STRICT>(a.w, b.x, dysB, Bd, Cdd);
-                if (h2) bwd_pixel<true, false, CHECK, STRICT>(P2, a.z, a.w, b.x, Bd, Cdd, a.x, b.y, c.x, c.y, c.z, pos, bD, bMx, bMxx, sR, sG, sB);
-                if (h3) bwd_pixel<false, false, CHECK, STRICT>(P3, a.z, a.w, b.x, Bd, Cdd, a.x, b.y, c.x, c.y, c.z, pos, bD, bMx, bMxx, sR, sG, sB);
-            }
-            // the dy factors, per pixel pair (a pair shares its row)
-            const float t1 = dysT * tD, t2 = dysB * bD;
-            const float sD = tD + bD, sMxx = tMxx + bMxx;
-            const float sMy = t1 + t2;
-            const float sMxy = dysT * tMx + dysB * bMx;
-            const float sMyy = dysT * t1 + dysB * t2;
-            float rc;
-            if (LDSRED) {
-                rc = lds_reduce9(tMx + bMx, sMy, sMxx, sMxy, sMyy, sD, sR, sG, sB, tr_base, tr_a1, tr_a1 ^ 128u);
-            } else {
-                float ra = tMx + bMx;
-                float rb = sMyy;
-                reduce8(ra, sMy, sMxx, sMxy, rb, sD, sR, sG);
-                rc = row_merge3(ra, rb, sB);
-            }
-            int jo = j * 12;
-            asm volatile("" : "+s"(jo));                      // scalar product, one v_add for the address (not a v_mad_u64_u32)
-            if (merge_writer) s_acc[jo + merge_off] = rc;
-        }
-        lds_barrier();
-        if (lv < cnt) {
-            int Wv = W, Hv = H;
-            asm volatile("" : "+s"(Wv), "+s"(Hv));               // (as lv: formed per round, not kept in two registers)
-            const float ddelx_dx = (float)(0.5 * Wv);            // backward.cu:473-474 (double product, rounded once)
-            const float ddely_dy = (float)(0.5 * Hv);
-            float a9[12];
-#pragma unroll
-            for (int k = 0; k < 12; k++) a9[k] = s_acc[lv * 12 + k];
-            const float4 q0 = s_q0[lv]; const float2 q1 = *reinterpret_cast<const float2*>(&s_q1[lv]);
-            const float db = (a9[8] + a9[9]) + (a9[10] + a9[11]);
-            const float ca = STRICT ? q0.z : (-2.0f * LN2) * q0.z, cb = STRICT ? q0.w : -LN2 * q0.w,
-                        cc = STRICT ? q1.x : (-2.0f * LN2) * q1.x, o = q1.y;
-            const float sx = a9[0], sy = a9[1], h = -0.5f;          // as k_render_bwd: the sums carry the opacity factor
-            const float dopac = o > 0.f ? a9[5] * __builtin_amdgcn_rcpf(o) : 0.f;      // 1 ulp: the sum itself carries more
-            float4* slot = inst_grad + 3 * (size_t)s_id[lv];
-            slot[0] = make_float4((-ca * sx - cb * sy) * ddelx_dx, (-cc * sy - cb * sx) * ddely_dy, h * a9[2], h * a9[3]);
-            slot[1] = make_float4(h * a9[4], dopac, a9[6], a9[7]);
-            slot[2] = make_float4(db, 0.f, 0.f, 0.f);
-        }
-    }
+    constexpr bool HAND = false, LANE_AGAIN = false;
+    const float* const hand_T = nullptr;
+    const uint32_t* const hand_last = nullptr;
+#include "render_bwd_tile_body.h"
+}
+// The same body on LDS its caller hands it (k_render_bwd_tile_step: the bytes its forward half staged in), with the LDS reduction
+// and without the alpha terms; HAND: see render_bwd_tile_body.h.
+template <int BATCH, bool STRICT, bool HAND>
+__device__ __forceinline__ void render_bwd_tile_in(float4* lds_q0, float4* lds_q1, float4* lds_q2, uint32_t* lds_id, float* lds_acc,
+                  float* lds_tr, const float* hand_T, const uint32_t* hand_last,
+                  const int tile, const int seg, const uint32_t ck_slot,
+                  const float4* __restrict__ c_final, int W, int H, int gx, const uint2* __restrict__ ranges,
+                  const uint32_t* __restrict__ point_list, const GaussRec* __restrict__ rec,
+                  const float* __restrict__ bg, const float* __restrict__ final_Ts,
+                  const uint32_t* __restrict__ n_contrib, const float* __restrict__ dL_dpix,
+                  char* __restrict__ bin_base, const GeomHeader* __restrict__ hdr)
+{
+    constexpr bool LDSRED = true, ALPHA = false, LANE_AGAIN = true;
+    const float* const dL_dalpha = nullptr;
+    float4 (&s_q0)[BATCH] = *reinterpret_cast<float4 (*)[BATCH]>(lds_q0);
+    float4 (&s_q1)[BATCH] = *reinterpret_cast<float4 (*)[BATCH]>(lds_q1);
+    float4 (&s_q2)[BATCH] = *reinterpret_cast<float4 (*)[BATCH]>(lds_q2);
+    uint32_t (&s_id)[BATCH] = *reinterpret_cast<uint32_t (*)[BATCH]>(lds_id);
+    float (&s_acc)[BATCH * 12] = *reinterpret_cast<float (*)[BATCH * 12]>(lds_acc);
+    float (&s_tr)[8 * 64] = *reinterpret_cast<float (*)[8 * 64]>(lds_tr);
+#include "render_bwd_tile_body.h"
 }
 
 #define LR_BWD_PARAMS int W, int H, int gx, int num_tiles, int tile_map, const uint2* __restrict__ ranges,                   \
@@ -852,6 +708,113 @@ k_render_bwd_abs(LR_BWD_SEG_PARAMS, const float* __restrict__ dL_ddepth, const f
     LR_BWD_KERNEL_BODY(LR_ITEM)
 #undef LR_ITEM
 }
+// The fused step kernel (launch_render_bwd_step; a view of the multi-view step whose upstream gradient is the caller's and whose
+// image nobody reads): a tile's wave runs the colour-free tile forward (render_fwd_tile_body.h) and then, without leaving the
+// kernel, the body of k_render_bwd_tile on the same tile -- one dependent launch per view less, no wait for the slowest forward
+// tile of the image, and the pixels' final T and stop position stay in registers.  The arithmetic of both halves is the text
+// of the two kernels in the same order: the same bits.  quad_hits, final_T and n_contrib are written as ever.
+//   * The forward half's 3 KB of staging planes and the backward half's 5 KB are the same bytes (s_lds): 8 waves per SIMD.
+//   * The backward half reads quad_hits, which this wave's forward half wrote (and in a tile longer than one segment final_T,
+//     n_contrib, its checkpoints, c_final and tile_seg0).  `s_waitcnt vmcnt(0)` between the halves is enough: the stores are the
+//     reading wave's own, they go through its own CU's write-through vector L1 to the L2 of its XCD, and a wave's vector
+//     loads are served by that same L1 and L2 -- what MI355X_MICROARCH.md ("Workgroup dispatch, XCD placement & inter-workgroup
+//     visibility") says can be stale is a line ANOTHER CU has rewritten, and no other workgroup writes these bytes.  Every such
+//     read is a vector load (the scalar cache is not written through: tile_seg0's address is made a lane's for that reason).
+//     The pointers both halves use are formed in the kernel from parameters that are not __restrict__, and the asm is a
+//     memory barrier to the compiler, so no load of the backward half moves in front of it.
+//   * A tile longer than one segment (none at C3): the forward half is the colour-carrying copy with checkpoints, and the same
+//     wave then walks the tile's segments one after the other, deepest first, each as its own workgroup would (state from
+//     memory, not handed over) -- the same bits in series.  No listed-segment workgroups: the grid is the tile grid, and
+//     bwd_uncovered is 0.
+//   * The halves do not hold each other's state.  The forward half's pixel state is dead behind the hand-over; the kernel's
+//     arguments (one struct) are read a second time behind it, through an argument-segment pointer the optimiser cannot see
+//     through, so that the backward half's pointers are not kept in scalar registers across the forward half's loops (kept, they
+//     overflow into a vector register the 64-register budget does not have).
+constexpr int STEP_BATCH = 30;          // the staging round of k_render_bwd_tile
+struct StepArgs {
+    int W, H, gx, num_tiles, tile_map;
+    const uint2* ranges; const GaussRec* rec; const float* bg; float* final_T; uint32_t* n_contrib; const float* dL_dpix;
+    char* bin_base; GeomHeader* hdr; uint32_t* tile_seg0; float4* c_final;
+};
+template <bool STRICT>
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8), amdgpu_num_vgpr(64)))
+k_render_bwd_tile_step(const StepArgs a)
+{
+    // forward half: three planes of TSTAGE float4; backward half: lds_reduce9's planes (2 KB, 256-byte aligned), three planes of
+    // STEP_BATCH float4, the accumulator (16-byte aligned), the slots' ids -- 5056 bytes
+    __shared__ __attribute__((aligned(256))) float4 s_lds[128 + 3 * STEP_BATCH + 3 * STEP_BATCH + (STEP_BATCH + 3) / 4];
+    static_assert(3 * TSTAGE <= 128 + 6 * STEP_BATCH, "the forward's planes fit the backward's bytes");
+    __shared__ unsigned long long s_args;   // the argument segment's address, for the backward half (below)
+    const int tile = blend_tile(a.tile_map, a.num_tiles);
+    if (tile < 0) return;
+    float4* f_q0 = s_lds, *f_q1 = s_lds + TSTAGE, *f_q2 = s_lds + 2 * TSTAGE;
+    float* b_tr = reinterpret_cast<float*>(s_lds);
+    float4* b_q0 = s_lds + 128, *b_q1 = b_q0 + STEP_BATCH, *b_q2 = b_q1 + STEP_BATCH;
+    float* b_acc = reinterpret_cast<float*>(b_q2 + STEP_BATCH);
+    uint32_t* b_id = reinterpret_cast<uint32_t*>(b_q2 + STEP_BATCH + 3 * STEP_BATCH);
+    const uint2 range = a.ranges[tile];
+    const int total = (int)(range.y - range.x);
+    // the kernel's one argument, as the backward half reads it again: the segment's address waits in LDS, so that not even
+    // the pointer occupies registers during the forward half (which has none to spare: 64 vector and every scalar register
+    // that 8 waves per SIMD allow, as k_render_fwd_tile)
+    typedef const StepArgs __attribute__((address_space(4))) * ArgPtr;
+    if (threadIdx.x == 0) s_args = (unsigned long long)(ArgPtr)__builtin_amdgcn_kernarg_segment_ptr();
+    ArgPtr ap;
+#define LR_STEP_HALFWAY()                                                                                                          \
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");            /* the forward half's stores are done (see above) */                \
+    {                                                                                                                              \
+        const unsigned long long v = s_args;                                                                                       \
+        ap = (ArgPtr)(((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(v >> 32)) << 32) |                      \
+                      (unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)v));                                      \
+    }                                                                                                                              \
+    /* a view whose binning overflowed is rendered (k_render_fwd_tile does) and not differentiated (k_render_bwd_tile returns) */   \
+    if (ap->hdr->overflow != 0u) return;
+#define LR_STEP_FWD_ARGS(A, BL) A.W, A.H, A.gx, A.num_tiles, A.tile_map, A.ranges, reinterpret_cast<const uint32_t*>(A.bin_base + BL.point_list), \
+        reinterpret_cast<const uint32_t*>(A.bin_base + BL.list_gid), A.rec, A.bg, A.final_T, A.n_contrib, nullptr, nullptr,                \
+        reinterpret_cast<uint8_t*>(A.bin_base + BL.quad_hits), A.hdr, reinterpret_cast<uint2*>(A.bin_base + BL.seg_list),                   \
+        reinterpret_cast<float4*>(A.bin_base + BL.ckpt), A.tile_seg0, A.c_final, f_q0, f_q1, f_q2
+#define LR_STEP_BWD_ARGS(B, BL) B.c_final, B.W, B.H, B.gx, B.ranges, reinterpret_cast<const uint32_t*>(B.bin_base + BL.point_list), B.rec, B.bg,   \
+        B.final_T, B.n_contrib, B.dL_dpix, B.bin_base, B.hdr
+    const BinLayout FL = bin_layout((long long)a.hdr->bin_bound);
+    if (total > BWD_SEG) {
+        render_fwd_tile<STRICT, false, false, true>(LR_STEP_FWD_ARGS(a, FL));
+        LR_STEP_HALFWAY()
+        // (nothing is kept across the forward half: the tile and its list's length are formed again)
+        const int tile_b = blend_tile(ap->tile_map, ap->num_tiles);
+        const uint2 range_b = ap->ranges[tile_b];
+        int tv = tile_b;
+        asm volatile("" : "+v"(tv));                                        // a vector load: not through the scalar cache
+        const uint32_t seg0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)ap->tile_seg0[tv]);
+        for (int seg = ((int)(range_b.y - range_b.x) - 1) / BWD_SEG; seg >= 0; seg--) {
+            // (the loop counter stays scalar; the tile and the arguments are made opaque per segment so that addresses are formed
+            // inside the loop: hoisted out of it they are two dozen spilled dwords)
+            int sg = seg, tl = tile_b;
+            asm volatile("" : "+s"(sg), "+s"(tl), "+s"(ap));
+            const BinLayout BL = bin_layout((long long)ap->hdr->bin_bound);
+            render_bwd_tile_in<STEP_BATCH, STRICT, false>(b_q0, b_q1, b_q2, b_id, b_acc, b_tr, nullptr, nullptr, tl, sg,
+                                                          seg0 + (uint32_t)sg, LR_STEP_BWD_ARGS((*ap), BL));
+            lds_barrier();                                                  // the next segment stages into the same LDS
+        }
+    } else {
+        float hand_T[4];
+        uint32_t hand_last[4];
+        render_fwd_tile<STRICT, false, false, false, true>(LR_STEP_FWD_ARGS(a, FL), hand_T, hand_last);
+        // (the arguments are read behind the asm: the backward half's loads of dL_dpix are not hoisted into the forward half's loop)
+        LR_STEP_HALFWAY()
+        const BinLayout BL = bin_layout((long long)ap->hdr->bin_bound);
+        const int tile_b = blend_tile(ap->tile_map, ap->num_tiles);             // (formed again: nothing is kept across the forward half)
+        render_bwd_tile_in<STEP_BATCH, STRICT, true>(b_q0, b_q1, b_q2, b_id, b_acc, b_tr, hand_T, hand_last, tile_b, 0, 0u,
+                                                     LR_STEP_BWD_ARGS((*ap), BL));
+    }
+    // nothing is left to listed segments.  (Stored last: a store in front of the halves would make their uniform loads vector
+    // loads.  By every lane of workgroup 0: a test of threadIdx.x here keeps it in a register through both halves.)
+    if (blockIdx.x == 0) ap->hdr->bwd_uncovered = 0u;
+#undef LR_STEP_HALFWAY
+#undef LR_STEP_FWD_ARGS
+#undef LR_STEP_BWD_ARGS
+}
+#undef LR_FWD_PARAMS
+#undef LR_FWD_PASS
 #ifdef LR_DIAGNOSTICS
 // rounds 4-5: the lane-swap reduction (reduce8 + row_merge3), 44 staged Gaussians per round: A/B partner (bwd_red = 2)
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8), amdgpu_num_vgpr(64)))
@@ -1031,6 +994,40 @@ void launch_render_bwd(const ViewParams& vp, const GeomView& g, const ImgView& i
     });
 #undef LR_SEG_ARGS
 #undef LR_BWD_ARGS
+}
+
+// The fused step kernel's rule.  The caller (api.hip step_view) has established that nothing reads the view's image and that its
+// upstream gradient is a fixed dL_dpix alone; here: would today's two launches both be the one-wave-per-tile kernels, with
+// segments?  lr_tune_set("blend_fuse", 0) never fuses, 2 fuses at every image size and with any number of views in flight
+// (tests, A/B runs) unless a knob forces another shape; the rule (-1 / 1) is launch_render_fwd's and blend_shape's.
+bool blend_step_fused(int num_tiles, long long inst_hint, long long seg_bound)
+{
+    const int knob = tune_get(TUNE_BLEND_FUSE);
+    if (knob == 0 || num_tiles <= 0 || seg_bound < 0) return false;
+    static const int forced_seg = env_knob("LR_BWD_SEG"), forced_red = env_knob("LR_BWD_RED");
+    if ((tune_get(TUNE_BWD_SEG) >= 0 ? tune_get(TUNE_BWD_SEG) : (forced_seg >= 0 ? forced_seg : 1)) == 0) return false;
+    const int red = tune_get(TUNE_BWD_RED) >= 0 ? tune_get(TUNE_BWD_RED) : forced_red;
+    if (red == 0 || red == 2 || red == 3) return false;               // (diagnostics build: the retired variants keep their launches)
+    const int fwd = tune_get(TUNE_FWD_PAIR), quad = tune_get(TUNE_BLEND_QUAD);
+    if (knob == 2) return (fwd < 0 || fwd == 2) && (quad < 0 || quad == BLEND_TILE);
+    const bool long_lists = inst_hint > 256ll * num_tiles;              // launch_render_fwd's rule
+    const bool fwd_tile = fwd >= 0 ? fwd == 2 : (num_tiles > 3072 && views_in_flight() >= 2 && !long_lists);
+    return fwd_tile && blend_shape(num_tiles, seg_bound > 2 ? (seg_bound - 2) * (long long)BWD_SEG : -1) == BLEND_TILE;
+}
+
+void launch_render_bwd_step(const ViewParams& vp, const GeomView& g, const ImgView& im, const BinView& b, const float* bg,
+                            const float* dL_dpix, hipStream_t s)
+{
+    const int gx = vp.gx, num_tiles = vp.gx * vp.gy;
+    if (num_tiles <= 0) return;
+    const int tile_map = blend_tile_map(num_tiles);
+    const int grid = ((num_tiles + 7) / 8) * 8;
+    g_last_bwd_shape = BLEND_TILE;
+    const StepArgs args = { vp.W, vp.H, gx, num_tiles, tile_map, im.ranges, g.rec, bg, im.final_T, im.n_contrib, dL_dpix, b.base, g.header,
+                            im.tile_seg0, im.c_final };
+    dispatch_flags<1>(flag_bits(tune_get(TUNE_STRICT) > 0), [&](auto st) {
+        hipLaunchKernelGGL(k_render_bwd_tile_step<st.value>, dim3(grid), dim3(64), 0, s, args);
+    });
 }
 
 }  // namespace lr
