@@ -55,6 +55,11 @@ which turns the Gaussians' flat sides into the surface the rendered depth descri
 With --multi-view K both terms run inside the step (ViewBatch(distortion_weight=W, normal_consistency_weight=W)): one fused pass
 each way per view behind the blend forward and the colour backward, the same loss as the single-view loop's.
 
+--depth-smoothness W (single-view loop): smooth.depth_smoothness of the rendered depth, guided by the target image, with weight W
+is added: the edge-aware smoothness term of the Monodepth lineage / DNGaussian / MonoGS, which keeps the depth smooth where the
+image is and lets it jump at image edges.  --smoothness-order 1 or 2 (first or second differences), --smoothness-space depth
+or inverse (on 1 / depth).  Turns the depth gradient on.
+
 --feature-channels C (single-view loop): a [P,C] feature table is rendered next to the colour (render_raw(features=table):
 lr_render_features, 16 channels per tile walk) and trained in a torch Adam group of its own with L1 against a fixed seeded [C,3]
 projection of the target image; the term is printed with the loss.  The set of Gaussians stays fixed: a table has no
@@ -81,6 +86,7 @@ from luciddreamer_amd import cameras, config, densify, filter3d, mcmc, synthetic
 from luciddreamer_amd.gaussian_renderer import GaussianCloud, render_raw   # noqa: E402
 from luciddreamer_amd.loss import l1_dssim_loss                            # noqa: E402
 from luciddreamer_amd.normals import depth_normals, normal_consistency, normal_loss, rendered_normal_consistency     # noqa: E402
+from luciddreamer_amd.smooth import depth_smoothness                       # noqa: E402
 from luciddreamer_amd.optim import FusedAdam                               # noqa: E402
 from simple_knn._C import distCUDA2                                        # noqa: E402
 
@@ -304,20 +310,22 @@ def train(args, log=print):
     normal_w, consistency_w = getattr(args, "normal_weight", 0.0), getattr(args, "normal_consistency", 0.0)
     distortion_w = getattr(args, "distortion_weight", 0.0)
     rendered_w = getattr(args, "rendered_normal_consistency", 0.0)
+    smooth_w = getattr(args, "depth_smoothness", 0.0)
     feature_c = int(getattr(args, "feature_channels", 0))
     if feature_c > 0 and (getattr(args, "multi_view", 0) > 0 or getattr(args, "mcmc", False)):
         raise SystemExit("--feature-channels: the single-view loop with a fixed set of Gaussians only (the multi-view step has no "
                          "feature pass, and a feature table has no densification surgery)")
     if getattr(args, "multi_view", 0) > 0:
-        if normal_w > 0 or consistency_w > 0:
-            raise SystemExit("--normal-weight / --normal-consistency: the single-view loop only (the multi-view step takes an "
-                             "external depth term through ViewBatch(grad_depths=))")
+        if normal_w > 0 or consistency_w > 0 or smooth_w > 0:
+            raise SystemExit("--normal-weight / --normal-consistency / --depth-smoothness: the single-view loop only (the "
+                             "multi-view step takes an external depth term through ViewBatch(grad_depths=))")
         return train_multi_view(args, log)
     dev = torch.device("cuda:0")
     model, cams, targets = build(args, dev)
     normal_targets = normal_targets_for(args, dev) if normal_w > 0 else None
-    if normal_w > 0 or consistency_w > 0 or rendered_w > 0:
-        config.set_depth_gradient(True)            # the normal terms act on the rendered depth
+    depth_terms = normal_w > 0 or consistency_w > 0 or rendered_w > 0 or smooth_w > 0
+    if depth_terms:
+        config.set_depth_gradient(True)            # the normal and smoothness terms act on the rendered depth
     bg = torch.zeros(3, device=dev)
     # no host round trip per forward ("Host sync"); instance counts drift while the cloud is
     # optimised, so the capacity is taken over the views of the path, with generous headroom
@@ -356,6 +364,9 @@ def train(args, log=print):
             loss = loss + distortion_w * pkg["distortion"].mean()
         if rendered_w > 0:
             loss = loss + rendered_normal_consistency(pkg["normals"], pkg["depth"], cams[v], weight=rendered_w)
+        if smooth_w > 0:
+            loss = loss + depth_smoothness(pkg["depth"], targets[v], order=args.smoothness_order, space=args.smoothness_space,
+                                           weight=smooth_w)
         loss.backward()                                                                   # :304
         with torch.no_grad():
             vis, radii = pkg["visibility_filter"], pkg["radii"]
@@ -384,7 +395,7 @@ def train(args, log=print):
     config.set_async(True)              # back to the library defaults
     config.set_antialiasing(False)
     config.set_absgrad(False)
-    if normal_w > 0 or consistency_w > 0 or rendered_w > 0:
+    if depth_terms:
         config.set_depth_gradient(False)
     log(f"{args.iters} iterations in {dt:.2f} s = {dt / args.iters * 1e3:.3f} ms/iteration")
     return losses, dt
@@ -395,7 +406,8 @@ def default_args(**kw):
              densify_every=100, densify_until=10_000, exact=False, torch_adam=False, antialiasing=False, absgrad=False,
              densify_grad_threshold=0.0002, multi_view=0, mcmc=False, cap_max=0, depth_weight=0.0, depth_loss="l1", filter3d=False,
              normal_weight=0.0, normal_consistency=0.0, distortion_weight=0.0,
-             rendered_normal_consistency=0.0, feature_channels=0)
+             rendered_normal_consistency=0.0, feature_channels=0, depth_smoothness=0.0, smoothness_order=1,
+             smoothness_space="depth")
     d.update(kw)
     return SimpleNamespace(**d)
 
@@ -423,6 +435,10 @@ HELP = {
     "rendered_normal_consistency": "> 0 adds normals.rendered_normal_consistency(normals, depth) with this weight "
                                    "(return_normals=True): the rendered normal map against the normals of the rendered depth; "
                                    "with --multi-view inside the step",
+    "depth_smoothness": "single-view loop: > 0 adds smooth.depth_smoothness(depth, target image) with this weight: the rendered "
+                        "depth is held smooth except across image edges; turns the depth gradient on",
+    "smoothness_order": "of --depth-smoothness: 1 (differences of neighbours) or 2 (second differences: planes cost nothing)",
+    "smoothness_space": "of --depth-smoothness: on the depth itself or on its inverse",
     "feature_channels": "single-view loop: C > 0 renders a [P,C] feature table next to the colour (features=) and trains it, in a "
                         "torch Adam group of its own, with L1 against a fixed seeded [C,3] projection of the target image; the "
                         "term is printed; the set of Gaussians stays fixed (no densification)",
@@ -431,7 +447,7 @@ HELP = {
 }
 
 
-CHOICES = {"depth_loss": ("l1", "pearson")}
+CHOICES = {"depth_loss": ("l1", "pearson"), "smoothness_order": (1, 2), "smoothness_space": ("depth", "inverse")}
 
 
 def make_parser():

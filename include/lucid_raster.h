@@ -1259,6 +1259,90 @@ int lr_normal_loss_forward(const lr_normals_args* a);
 int lr_normal_loss_backward(const lr_normals_args* a);
 
 /*
+ * Edge-aware smoothness of a rendered map (luciddreamer_amd/csrc/smooth.hip): the first- or second-order smoothness term of
+ * the Monodepth lineage / DNGaussian / MonoGS on a depth map, an inverse depth map or a normal map, gated by the edges of a
+ * guide image.
+ *
+ * map: [C,H,W] float32 device image, contiguous, 1 <= C <= 4 (a depth map is C = 1, a normal map C = 3).  guide: optional
+ * [G,H,W] image I, G = guide_channels in {1, 3} (guide_channels = 0 without one).  mask: optional [H,W] plane.
+ * order in {1, 2}; space LR_SMOOTH_DIRECT or LR_SMOOTH_INVERSE; positive_only in {0, 1}; gamma, weight finite and >= 0.
+ *
+ * A pixel is VALID when every channel of `map` is finite, with positive_only its channel 0 is > 0 (the project's 0 = "no
+ * surface"; NaN fails), and with a mask its mask value is > 0 (NaN fails).  The mask is a selector only: it is never multiplied
+ * in.  The value used is u = map, in INVERSE space u = 1.0f / map (one float32 division); INVERSE needs C = 1 and positive_only
+ * (anything else is LR_ERR_INVALID_ARG), and a pixel whose reciprocal is not finite (a subnormal depth) is invalid there.
+ *
+ * Order 1 has one term per horizontal pair (p, q = p + x) and one per vertical pair (p, q = p + y):
+ *     a_g = |I_p,g - I_q,g|                                          float32, per guide channel
+ *     a = a_0  (G = 1),   a = ((a_0 + a_1) + a_2) / 3.0f  (G = 3)
+ *     w = expf(-(gamma a)),   w = 1 without a guide
+ *     D_c = (double)u_q,c - (double)u_p,c
+ *     term = (double)w * sum_c |D_c|                                  channels in order, double
+ * Order 2 has one term per horizontal triple (m = p - x, p, q = p + x) and one per vertical triple:
+ *     a_g = max(|I_p,g - I_m,g|, |I_q,g - I_p,g|)                    an edge on either side gates the term; a NaN on either side stays
+ *     a, w as above
+ *     D_c = ((double)u_m,c - 2.0 (double)u_p,c) + (double)u_q,c
+ *     term = (double)w * sum_c |D_c|
+ * A term COUNTS when all of its pixels are valid and a is finite: !(a >= 0) excludes a NaN, and a = +inf (an infinite guide
+ * value on one side of the term) is excluded with it -- at gamma = 0 its weight would be expf(-(0 inf)) = NaN.
+ *
+ *   lr_smooth_forward  : loss = weight * (float)(S / (double)(H*W)), S the sum of the counted terms: divided by ALL pixels, as
+ *                        lr_normal_loss_forward, never by a data-dependent number.  out (device, 2 floats) = {loss, number of
+ *                        counted terms (exact up to 2^24)}.  Without a counted term (H = W = 1; order 2 with H, W < 3) both
+ *                        are exactly 0.  The terms are summed in double: per lane (rows top to bottom, the horizontal term of a
+ *                        pixel before its vertical one), per workgroup in a fixed order into `workspace`
+ *                        (lr_smooth_workspace_bytes), then by one workgroup in a fixed order.  No atomics: bit-repeatable.
+ *   lr_smooth_backward : dL_dmap [C,H,W] = upstream * d loss / d map; `upstream` is a device scalar or NULL for 1.  A GATHER:
+ *                        a pixel adds the terms it belongs to, at most 4 at order 1 and 6 at order 2, their weights and signs
+ *                        recomputed from the inputs (no stored plane, no workspace).  With
+ *                            k = (upstream weight) / (float)(H W)
+ *                        channel c of pixel p is g_u = k s, s the float32 sum of (coef w_t) sign(D_t,c) over its terms:
+ *                        sign(0) = 0; coef = -1 for p and +1 for q at order 1, (1, -2, 1) for (m, p, q) at order 2, so both
+ *                        products are exact.  The terms are added from +0 in this order: the horizontal ones from left to
+ *                        right (order 1: the pair ending at the pixel, the pair starting at it; order 2: the triples centred
+ *                        on x - 1, x, x + 1), then the vertical ones from top to bottom; a term that does not count adds
+ *                        nothing.  k multiplies the SUM, once: multiples of k are not float32 numbers, small integers are,
+ *                        so a pixel whose terms cancel as integers (w = 1 away from the guide's edges) gets an exact zero and
+ *                        not the rounding residue of 3 k - 2 k - k.  INVERSE space then applies g_map = -(g_u u) u.  An invalid pixel, and a pixel without a counted term,
+ *                        gets exactly 0.  The guide and the mask receive no gradient.  No atomics: bit-repeatable.
+ *
+ * Why the differences are formed in double: the gradient of an L1 term is nothing but the sign of its difference, and a float32
+ * second difference can round to the wrong sign near zero.  The double operations are exact -- so the sign, and sign(0) = 0,
+ * are those of the real-number difference -- whenever the magnitudes of the non-zero values of a term lie within a factor 2^27
+ * of each other (values of 24 bits whose exponents differ by at most 27 leave m - 2p within the 53 bits of a double); beyond
+ * that range the final addition is still correctly rounded, so a sign can be lost only where m - 2p itself was rounded.
+ *
+ * height, width >= 1 and H*W < 2^31.  struct_bytes is checked before anything else; every check (NULL pointers, sizes, channels,
+ * guide_channels, order, space, positive_only, gamma, weight, workspace_bytes) sits in front of the first HIP call.  Each entry
+ * point reads the members named with it and ignores the others.  No host synchronisation.  Return 0 or a negative LR_ERR_*.
+ */
+#define LR_SMOOTH_DIRECT  0
+#define LR_SMOOTH_INVERSE 1
+typedef struct lr_smooth_args {
+    size_t struct_bytes;                     /* = sizeof(lr_smooth_args); anything else is LR_ERR_INVALID_ARG */
+    int height, width;
+    int channels;                            /* C of map and dL_dmap: 1..4 */
+    int guide_channels;                      /* G of guide: 1 or 3; 0 without a guide */
+    const float* map;                        /* [C,H,W] */
+    const float* guide;                      /* [G,H,W], optional */
+    const float* mask;                       /* [H,W], optional */
+    int order;                               /* 1 or 2 */
+    int space;                               /* LR_SMOOTH_DIRECT or LR_SMOOTH_INVERSE */
+    int positive_only;                       /* 0 or 1 */
+    float gamma;
+    float weight;
+    const float* upstream;                   /* backward: device scalar, optional */
+    float* out;                              /* forward: {loss, count} */
+    float* dL_dmap;                          /* backward: [C,H,W] */
+    void* workspace;                         /* forward */
+    size_t workspace_bytes;
+    void* stream;
+} lr_smooth_args;
+size_t lr_smooth_workspace_bytes(int height, int width);
+int lr_smooth_forward(const lr_smooth_args* a);
+int lr_smooth_backward(const lr_smooth_args* a);
+
+/*
  * Video frames on the device (the per-frame post-processing of the video renderer, R/luciddreamer.py:250-265).  Every entry
  * point takes n_frames contiguous frames of one H, W and handles them in the same launches; nothing reads back to the host.
  *

@@ -16,10 +16,11 @@ def uninstall(handle):
 def __getattr__(name):
     """`luciddreamer_amd.mcmc` (MCMCStrategy: relocation, capped growth, position noise), `luciddreamer_amd.filter3d` (the 3D
     smoothing filter of Mip-Splatting), `luciddreamer_amd.reproject` (point-cloud reprojection: warped frames and hole masks),
-    `luciddreamer_amd.normals` (normals from depth and the normal losses), `luciddreamer_amd.tsdf` (TSDF fusion of rendered
+    `luciddreamer_amd.normals` (normals from depth and the normal losses), `luciddreamer_amd.smooth` (edge-aware smoothness of
+    a rendered depth or normal map), `luciddreamer_amd.tsdf` (TSDF fusion of rendered
     depth and mesh extraction) and `luciddreamer_amd.mesh` (connected components, cluster filter and vertex normals of a mesh)
     without importing torch with the package."""
-    if name in ("mcmc", "filter3d", "reproject", "normals", "tsdf", "mesh"):
+    if name in ("mcmc", "filter3d", "reproject", "normals", "smooth", "tsdf", "mesh"):
         import importlib
         return importlib.import_module("." + name, __name__)
     if name in ("fit_scale", "scatter_interpolate", "compensate", "dream_step"):     # dreaming on the device (reproject.py)

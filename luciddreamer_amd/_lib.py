@@ -51,6 +51,7 @@ EXPORTS = ("lr_last_error", "lr_version", "lr_geom_bytes", "lr_img_bytes", "lr_b
            "lr_dream_workspace_bytes", "lr_dream_scale_sums", "lr_dream_correspond", "lr_dream_lift", "lr_scatter_interpolate",
            "lr_normals_workspace_bytes", "lr_depth_normals", "lr_depth_normals_backward", "lr_normal_loss_forward",
            "lr_normal_loss_backward",
+           "lr_smooth_workspace_bytes", "lr_smooth_forward", "lr_smooth_backward",
            "lr_tsdf_workspace_bytes", "lr_tsdf_integrate", "lr_tsdf_extract_count", "lr_tsdf_extract_emit",
            "lr_mesh_workspace_bytes", "lr_mesh_components", "lr_mesh_filter_count", "lr_mesh_filter_emit", "lr_mesh_vertex_normals")
 
@@ -330,6 +331,21 @@ class NormalsArgs(ctypes.Structure):
         super().__init__(struct_bytes=ctypes.sizeof(NormalsArgs), **fields)
 
 
+LR_SMOOTH_DIRECT, LR_SMOOTH_INVERSE = 0, 1          # lr_smooth_args.space
+
+
+class SmoothArgs(ctypes.Structure):
+    """lr_smooth_args, field for field (tests/test_smooth_cpu.py compares the offsets with the host compiler's)."""
+    _vp, _ci, _cf = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
+    _fields_ = [("struct_bytes", ctypes.c_size_t), ("height", _ci), ("width", _ci), ("channels", _ci), ("guide_channels", _ci),
+                ("map", _vp), ("guide", _vp), ("mask", _vp), ("order", _ci), ("space", _ci), ("positive_only", _ci),
+                ("gamma", _cf), ("weight", _cf), ("upstream", _vp), ("out", _vp), ("dL_dmap", _vp),
+                ("workspace", _vp), ("workspace_bytes", ctypes.c_size_t), ("stream", _vp)]
+
+    def __init__(self, **fields):
+        super().__init__(struct_bytes=ctypes.sizeof(SmoothArgs), **fields)
+
+
 class TsdfVolumeDesc(ctypes.Structure):
     """lr_tsdf_volume, field for field: the lattice and its three device tensors."""
     _vp, _ci, _cf = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
@@ -580,6 +596,11 @@ def lib():
         for fn in (L.lr_depth_normals, L.lr_depth_normals_backward, L.lr_normal_loss_forward, L.lr_normal_loss_backward):
             fn.restype = ci
             fn.argtypes = [ctypes.POINTER(NormalsArgs)]
+        L.lr_smooth_workspace_bytes.restype = ctypes.c_size_t
+        L.lr_smooth_workspace_bytes.argtypes = [ci, ci]
+        for fn in (L.lr_smooth_forward, L.lr_smooth_backward):
+            fn.restype = ci
+            fn.argtypes = [ctypes.POINTER(SmoothArgs)]
         L.lr_tsdf_workspace_bytes.restype = ctypes.c_size_t
         L.lr_tsdf_workspace_bytes.argtypes = [ctypes.POINTER(TsdfExtractArgs)]
         L.lr_tsdf_integrate.restype = ci

@@ -53,6 +53,9 @@ SOURCES = {
     # normals from depth and the normal losses: the header's float32 operations, one rounding each (a numpy restatement agrees
     # to the bit): no FMA contraction
     "normals.hip": ["-ffp-contract=off"],
+    # edge-aware smoothness of a rendered map: the header's operations, one rounding each (a numpy restatement differs by the
+    # device's expf alone): no FMA contraction
+    "smooth.hip": ["-ffp-contract=off"],
     # TSDF fusion and mesh extraction: the shared float64 projection, then the header's float32 operations, one rounding each
     # (a numpy restatement agrees to the bit): no FMA contraction
     "tsdf.hip": ["-ffp-contract=off"],

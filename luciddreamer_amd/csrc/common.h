@@ -740,6 +740,12 @@ size_t geom_terms_workspace_bytes(int H, int W);
 void launch_geom_terms(const GeomTerms& t, hipStream_t s);
 void launch_plane_add(long long n, float* dst, const float* src, hipStream_t s);
 
+// edge-aware smoothness of a rendered map (smooth.hip): the launchers take lr_smooth_args as the entry points checked it.
+// workspace: smooth_workspace_bytes, {sum, count} per workgroup of the forward.
+size_t smooth_workspace_bytes(int H, int W);
+void launch_smooth_forward(const lr_smooth_args& a, hipStream_t s);
+void launch_smooth_backward(const lr_smooth_args& a, hipStream_t s);
+
 // video frames on the device (video.hip)
 size_t video_workspace_bytes(int n_frames);
 void launch_frames_u8(int n, int HW, const float* images, uint8_t* out, hipStream_t s);

@@ -1,5 +1,5 @@
 // wave_reduce.h -- the wave64 reduction pieces the per-tile backward kernels share (render_bwd.hip, render_distort.hip), for gfx950:
-// DPP moves, the sum over a 16-lane row, and the lane-swap reduction of eight terms down to rows.  What a kernel does with the row
+// DPP moves, the sum over a 16-lane row, the whole-wave sum, and the lane-swap reduction of eight terms down to rows.  What a kernel does with the row
 // partials (render_bwd.hip: row_merge3 / lds_reduce9; render_distort.hip: two row sums) stays with the kernel.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -18,6 +18,15 @@ __device__ __forceinline__ float row_sum(float v)
     v += dpp<0x4E>(v);
     v += dpp<0x141>(v);
     v += dpp<0x140>(v);
+    return v;
+}
+// sum over the wave's 64 lanes in a fixed order (xor butterfly 32, 16, ..., 1); every lane ends with the total.  The double
+// form is what the loss kernels reduce their per-lane sums with (smooth.hip).
+template <class T>
+__device__ __forceinline__ T wave_sum(T v)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
     return v;
 }
 // (inline asm below: with ROCm 7.2 hipcc, __builtin_amdgcn_permlane32_swap followed by r[0] + r[1] returned 2 * r[0] --
